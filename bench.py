@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """End-to-end recommendations/s on the BASELINE.json workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (one child process
@@ -61,6 +61,9 @@ def parse_args(argv=None):
                          "same users twice in a row); the one-batch replay is reported beside it as `same_batch`")
     ap.add_argument("--no-latency-sweep", action="store_true",
                     help="skip `e2e_latency_by_batch` (one recommend_device call at B = 1 / 8 / 64 / 512, N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (ad ids, scores, candidates, "
+                         "logits) as DIR/<name>.npy in float32 / float64, for output-for-output comparison of two builds")
     ap.add_argument("--dry-run", action="store_true",
                     help="form the world (launcher, rendezvous, world-size checks), print a stub line with n_gpus and "
                          "exit without touching a GPU: the CPU test of the N > 1 launch path")
@@ -128,6 +131,35 @@ X3_PEAK_TFLOPS = BF16_PEAK_TFLOPS / 3   # "x3" kernel: 3 fp16 MFMA products per 
 HBM_PEAK_GBS = 8000.0
 MIN_WARMUP = 20               # untimed steps before the timed region whatever --warmup says (the
                               # power-limited ranker kernel is still settling its clock after 10 launches)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, directory, rank=0, limit=DUMP_LIMIT_BYTES):
+    """The result dict of one recommend_device call -> directory/<name>.npy, one file per tensor: floating point as
+    float32, integers (ids, positions) as float64 (exact below 2**53).  Rank r > 0 writes <name>.rank<r>.npy.  If the
+    arrays exceed `limit` bytes together, each is cut to a fixed seeded sample of its flattened elements (same shapes ->
+    same sample) of its share of the limit.  -> {file name: shape written}."""
+    arrays = {}
+    for name, v in out.items():
+        if not isinstance(v, torch.Tensor):
+            continue
+        a = v.detach().cpu()
+        a = a.float() if a.is_floating_point() else a.double()
+        arrays[name] = a.numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    written = {}
+    for name, a in sorted(arrays.items()):
+        if total > limit:
+            keep = max(1, int(a.size * limit / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        fname = f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"
+        np.save(os.path.join(directory, fname), a)
+        written[fname] = list(a.shape)
+    return written
 
 
 def _t(sd):
@@ -574,6 +606,9 @@ def main():
         return dt_, ms, prof_, res, spread
 
     dt, step_ms, prof, out, spread = timed_region(rotating(args.steps))
+    if args.dump_outputs:
+        # the last timed step's own result, copied out before any later region can reuse the workspaces behind it
+        dumped = dump_outputs(out, args.dump_outputs, rank, limit=DUMP_LIMIT_BYTES // world)
     # the same region replaying ONE batch (rounds 1-3 timed this): every step gathers the same 256 000 rows of the ad
     # projection cache and re-scores the same corpus rows, next to a 256 MB Infinity Cache
     dt_same, _, _, _, _ = timed_region(same)
@@ -736,6 +771,8 @@ def main():
             line["e2e_latency_by_batch"] = latency
         if multi is not None:                   # N > 1 only: the N = 1 line carries no such key
             line["multi_gpu"] = multi
+        if args.dump_outputs:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

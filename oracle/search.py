@@ -1,7 +1,7 @@
 """Oracle for the retrieval index (test infrastructure).
 
 The arithmetic lives in faiss (faiss-cpu>=1.7.4, requirements.txt:8), which is absent
-from /root/reference and from this image: PARITY UNPINNED at the faiss boundary.  What is
+from the reference sources and from this environment: PARITY UNPINNED at the faiss boundary.  What is
 restated is (i) the reference wrapper's own steps and (ii) the published semantics of the
 two index types on the path:
 

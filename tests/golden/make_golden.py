@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """Generate golden input/output vectors by running the REFERENCE modules in this container.
 
-Run once in the build container (where /root/reference exists):
+Run once where the reference sources are at hand:
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py <reference directory> [case ...]
 
-It imports ``two_tower_model.py`` and ``transformer_ranker.py`` from /root/reference
+It imports ``two_tower_model.py`` and ``transformer_ranker.py`` from that directory
 (they import cleanly: torch only), loads weights drawn by this repo's own seeded
 generator (amdrec.synth), runs the eval-mode forward on CPU and writes small ``.npz``
 fixtures (inputs, outputs, sha256 of the weights) next to this script.  The reference
@@ -22,7 +22,9 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "movie-recommender-demo_amd"))
-sys.path.insert(0, "/root/reference")
+if len(sys.argv) < 2:
+    sys.exit(f"usage: python {sys.argv[0]} <directory of the reference sources>")
+sys.path.insert(0, os.path.abspath(sys.argv[1]))
 
 from amdrec import synth  # noqa: E402
 import two_tower_model as ref_tt  # noqa: E402
@@ -113,4 +115,4 @@ def main(only=None):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])            # optional: case names to (re)generate; default all
+    main(sys.argv[2:])            # optional: case names to (re)generate; default all

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Loss / gradient / one-optimizer-step fixtures from the REFERENCE modules, run in this container
-(/root/reference importable: two_tower_model.py, transformer_ranker.py; training_pipeline.py is not - it imports faiss
+(the reference directory importable: two_tower_model.py, transformer_ranker.py; training_pipeline.py is not - it imports faiss
 transitively - so the trainers' inner loop is restated here line by line from training_pipeline.py:118-146, :322-358).
 
-    python tests/golden/make_train_golden.py
+    python tests/golden/make_train_golden.py <reference directory>
 
 Models are built with dropout = 0 (the dropout masks of two implementations cannot be matched; BatchNorm batch
 statistics, LayerNorm, the literal 8-head attention and every loss term are all still exercised in train mode),
@@ -18,7 +18,9 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "movie-recommender-demo_amd"))
-sys.path.insert(0, "/root/reference")
+if len(sys.argv) < 2:
+    sys.exit(f"usage: python {sys.argv[0]} <directory of the reference sources>")
+sys.path.insert(0, os.path.abspath(sys.argv[1]))
 
 from amdrec import synth  # noqa: E402
 import two_tower_model as ref_tt  # noqa: E402

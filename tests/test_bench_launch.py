@@ -57,3 +57,55 @@ def test_launcher_runs_before_torch_is_imported():
     """The parent of a self-launched run must never initialise the GPU: the launcher sits above `import torch`."""
     src = open(BENCH).read()
     assert src.index("sys.exit(launch_ranks(") < src.index("import torch")
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """--dump-outputs: every tensor of the result dict becomes <name>.npy, floats as float32, ids as float64 (exact);
+    past the byte limit each array is cut to the same seeded sample on every call."""
+    import numpy as np
+    import torch
+    import bench
+    ids = torch.arange(4 * 500, dtype=torch.int64).reshape(4, 500) * 977
+    out = {"ad_ids": ids[:, :10], "candidate_ids": ids, "logits": torch.randn(3, 2000), "tasks": ["ctr", "a", "b"],
+           "scores": torch.rand(3, 4, 10, dtype=torch.float16)}
+    written = bench.dump_outputs(out, str(tmp_path / "full"))
+    assert sorted(written) == ["ad_ids.npy", "candidate_ids.npy", "logits.npy", "scores.npy"]
+    a = np.load(tmp_path / "full" / "candidate_ids.npy")
+    assert a.dtype == np.float64 and np.array_equal(a, ids.numpy())
+    lg = np.load(tmp_path / "full" / "logits.npy")
+    assert lg.dtype == np.float32 and np.array_equal(lg, out["logits"].numpy())
+    assert np.load(tmp_path / "full" / "scores.npy").dtype == np.float32
+    assert bench.dump_outputs(out, str(tmp_path / "r1"), rank=1) == {k.replace(".npy", ".rank1.npy"): v
+                                                                     for k, v in written.items()}
+    limit = 20_000
+    s1 = bench.dump_outputs(out, str(tmp_path / "s1"), limit=limit)
+    s2 = bench.dump_outputs(out, str(tmp_path / "s2"), limit=limit)
+    assert s1 == s2
+    assert sum(os.path.getsize(tmp_path / "s1" / f) - 128 for f in s1) <= limit
+    for f in s1:
+        assert np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f))
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_bench_runs_the_steps_asked_for_and_dumps_the_last_one(tmp_path):
+    """One small single-GPU bench run: the line reports the timed steps it was given and ms_per_step, and the dumped
+    last step is a consistent recommend_device result (every top-10 id is one of that user's stage-1 candidates)."""
+    import numpy as np
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--ads", "200000",
+                        "--no-cpu-baseline", "--no-strict-fp32", "--no-latency-sweep", "--no-search-sweep",
+                        "--dump-outputs", str(d)], env=_env(), capture_output=True, text=True, timeout=880)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    doc = json.loads(lines[0])
+    assert doc["steps"] == 3 and doc["ms_per_step"] > 0 and doc["value"] > 0
+    assert doc["dumped_outputs"]["dir"] == str(d)
+    ad_ids, cand = np.load(d / "ad_ids.npy"), np.load(d / "candidate_ids.npy")
+    assert ad_ids.dtype == cand.dtype == np.float64 and ad_ids.shape == (512, 10) and cand.shape == (512, 500)
+    assert all(set(ad_ids[b]) <= set(cand[b]) for b in range(512))
+    for name, shape in (("logits", (3, 512 * 500)), ("scores", (3, 512, 10)), ("candidate_scores", (512, 500))):
+        a = np.load(d / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), name
+    assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20

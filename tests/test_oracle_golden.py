@@ -1,5 +1,5 @@
 """Pin the CPU oracle against outputs of the reference's own modules (tests/golden/*.npz,
-produced by tests/golden/make_golden.py from /root/reference/two_tower_model.py and
+produced by tests/golden/make_golden.py from the reference's two_tower_model.py and
 transformer_ranker.py).  CPU only."""
 import numpy as np
 import pytest

@@ -2,7 +2,7 @@
 # rocprofv3 evidence for configs[4] on one GPU (10M clustered ads, IVF 4096 x 64, 512 users): kernel stats + the PMC passes of
 # tools/profile_round.sh for the list-scan kernels.  Copy $OUT/stats/*kernel_stats.csv and $OUT/pmc.json into profiles/.
 OUT=gpurun_out/prof_ivf10m
-cd /root/repo
+cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 rm -rf $OUT; mkdir -p $OUT
 ARGS="--ads 10000000 --index ivf --nlist 4096 --nprobe 64 --no-cpu-baseline --no-search-sweep --no-strict-fp32 --no-latency-sweep"

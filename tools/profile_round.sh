@@ -5,7 +5,7 @@
 # then tools/pmc_summary.py -> $OUT/pmc.json.  Copy what is to be judged into profiles/ (tools/profile_round.sh prints the list).
 R=${1:-r04}
 OUT=gpurun_out/prof_$R
-cd /root/repo
+cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 rm -rf $OUT; mkdir -p $OUT
 ARGS="--no-cpu-baseline --no-search-sweep --no-strict-fp32 --no-latency-sweep"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # kernel timeline of one single-user request (tools/request_trace.py under rocprofv3 --kernel-trace): launches and gaps
 OUT=gpurun_out/prof_request
-cd /root/repo; export TMPDIR=/tmp; rm -rf $OUT; mkdir -p $OUT
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp; rm -rf $OUT; mkdir -p $OUT
 rocprofv3 --kernel-trace -d $OUT/trace -o trace --output-format csv -- python3 tools/request_trace.py 1 60 > $OUT/run.log 2>&1
 cat $OUT/run.log | grep "B="
 python3 - $OUT <<'PY'

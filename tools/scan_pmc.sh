@@ -2,7 +2,7 @@
 # SQ counter passes over a search-only loop (tools/search_only.py B reps): where the corpus pass's wave time goes
 B=${1:-512}
 OUT=${2:-gpurun_out/scan_pmc}
-cd /root/repo; export TMPDIR=/tmp; mkdir -p $OUT
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp; mkdir -p $OUT
 i=0
 for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY" \
            "SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM" \

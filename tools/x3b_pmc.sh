@@ -2,7 +2,7 @@
 # PMC passes over the row-owner probe binary (one counter group per pass; no tracing options besides kernel-trace)
 BIN=${1:-tools/bin/x3b_opt_0}
 OUT=${2:-gpurun_out/x3b_pmc}
-cd /root/repo
+cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 mkdir -p $OUT
 i=0
