@@ -475,6 +475,8 @@ def pack_ranker(sd: Dict, user_names: List[str], ad_names: List[str], n_num: int
     p.b_proj = pk.ptr((_np64(sd["feature_projection.bias"]) + pos0).astype(np.float32))
     l = 0
     while f"transformer_layers.{l}.norm1.weight" in sd:
+        if l >= MAX_LAYERS:
+            raise ValueError(f"at most {MAX_LAYERS} encoder layers are supported (num_layers > {MAX_LAYERS})")
         pre = f"transformer_layers.{l}"
         L = p.layers[l]
         wv, bv = _np64(sd[f"{pre}.self_attention.W_v.weight"]), _np64(sd[f"{pre}.self_attention.W_v.bias"])
@@ -505,7 +507,7 @@ def pack_ranker(sd: Dict, user_names: List[str], ad_names: List[str], n_num: int
         l += 1
     p.n_layers = l
     if l == 0:
-        p.d_ff = 4
+        p.d_ff = 4                  # placeholder (ranker_check wants d_ff >= 4); nothing reads it without encoder layers
     c = 0
     while f"feature_interaction.cross_weights.{c}" in sd:
         w, p.ldw_cross = _pad_k(_np64(sd[f"feature_interaction.cross_weights.{c}"]).T)   # xl @ W == xl (W^T)^T
@@ -567,7 +569,7 @@ def pack_ranker(sd: Dict, user_names: List[str], ad_names: List[str], n_num: int
         p.x3.stream = pk.ptr(x["stream"].view(np.int16))
         p.x3.chunks = x["chunks"]
         p.x3.min_rows = int(x3_min_rows)
-        if x3_variant == 16 and x3_cs_max_rows >= 0 and p.d_ff % 128 == 0 and p.head_h1 % 128 == 0:
+        if x3_variant == 16 and x3_cs_max_rows >= 0 and (p.n_layers == 0 or p.d_ff % 128 == 0) and p.head_h1 % 128 == 0:
             xc = pack_x3_stream(mats, "16cs")               # same planes and scales, the column-split kernel's chunk order
             assert all(xc[k] == x[k] for k in ("sw_ov", "sw_1", "sw_2", "sw_cross", "sw_h1", "sw_h2"))
             p.x3.stream_cs = pk.ptr(xc["stream"].view(np.int16))

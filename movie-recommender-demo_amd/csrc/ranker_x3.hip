@@ -21,7 +21,8 @@ static bool x3_eligible(const amdrec_ranker_params* p) {
     if (p->x3.stream == nullptr || p->x3.chunks <= 0 || p->x3.params == nullptr) return false;
     if (p->x3.variant != 16 && p->x3.variant != 32) return false;
     if (x3_param_floats(p) > x3::PARAM_FLOATS) return false;      // the parameter blob must fit its LDS area
-    if (p->d_model != 256 || p->d_ff % 32 != 0 || p->head_h1 % 32 != 0 || p->head_h2 != 64) return false;
+    // d_ff is a placeholder without encoder layers (amdrec/weights.py pack_ranker)
+    if (p->d_model != 256 || (p->n_layers > 0 && p->d_ff % 32 != 0) || p->head_h1 % 32 != 0 || p->head_h2 != 64) return false;
     if (2 * p->n_layers + p->n_cross + 1 > x3::MAX_PHASES || p->n_tasks > 4) return false;
     for (int l = 0; l < p->n_layers; ++l)
         if (p->layers[l].w_v != nullptr) return false;              // needs the pre-multiplied W_ov form
@@ -30,8 +31,8 @@ static bool x3_eligible(const amdrec_ranker_params* p) {
 
 // the column-split stream (rowowner16c.hpp) is present and the architecture fits its super-steps of four hidden tiles
 static bool x3c_available(const amdrec_ranker_params* p) {
-    return p->x3.variant == 16 && p->x3.stream_cs != nullptr && p->x3.chunks_cs > 0 && p->d_ff % 128 == 0 &&
-           p->head_h1 % 128 == 0;
+    return p->x3.variant == 16 && p->x3.stream_cs != nullptr && p->x3.chunks_cs > 0 &&
+           (p->n_layers == 0 || p->d_ff % 128 == 0) && p->head_h1 % 128 == 0;
 }
 
 // n_phases < 0: the whole chain; cs: the column-split kernel's stream

@@ -14,7 +14,7 @@ BN_EPS = 1e-5       # nn.BatchNorm1d default (two_tower_model.py:86)
 NORM_EPS = 1e-12    # F.normalize default (two_tower_model.py:119)
 
 
-def embed(sd, prefix, cat):
+def embed(sd, prefix, cat, dtype=np.float32):
     """EmbeddingLayer.forward: column i <-> i-th key in insertion order, concat."""
     names = [k for k in sd if k.startswith(prefix) and k.endswith(".weight")]
     cat = np.asarray(cat).astype(np.int64)
@@ -26,38 +26,40 @@ def embed(sd, prefix, cat):
         if idx.size and (idx.min() < 0 or idx.max() >= table.shape[0]):
             raise IndexError("index out of range in self")   # torch's message
         cols.append(table[idx])
-    return np.concatenate(cols, axis=1).astype(np.float32)
+    return np.concatenate(cols, axis=1).astype(dtype)
 
 
-def _mlp(sd, prefix, x):
-    """Sequential(Linear, BN, ReLU, Dropout)*n + Linear in eval mode."""
+def _mlp(sd, prefix, x, dtype=np.float32):
+    """Sequential(Linear, BN, ReLU, Dropout)*n + Linear in eval mode (parameters in ``dtype``)."""
+    dt = lambda a: np.asarray(a).astype(dtype)    # noqa: E731  (float32 parameters: no-op)
     idx = 0
     while f"{prefix}.{idx + 1}.running_mean" in sd:
-        w, b = sd[f"{prefix}.{idx}.weight"], sd[f"{prefix}.{idx}.bias"]
+        w, b = dt(sd[f"{prefix}.{idx}.weight"]), dt(sd[f"{prefix}.{idx}.bias"])
         x = x @ w.T + b
-        g, be = sd[f"{prefix}.{idx + 1}.weight"], sd[f"{prefix}.{idx + 1}.bias"]
-        mu, var = sd[f"{prefix}.{idx + 1}.running_mean"], sd[f"{prefix}.{idx + 1}.running_var"]
-        x = (x - mu) / np.sqrt(var + np.float32(BN_EPS)) * g + be
-        x = np.maximum(x, np.float32(0))
+        g, be = dt(sd[f"{prefix}.{idx + 1}.weight"]), dt(sd[f"{prefix}.{idx + 1}.bias"])
+        mu, var = dt(sd[f"{prefix}.{idx + 1}.running_mean"]), dt(sd[f"{prefix}.{idx + 1}.running_var"])
+        x = (x - mu) / np.sqrt(var + dtype(BN_EPS)) * g + be
+        x = np.maximum(x, dtype(0))
         idx += 4
-    w, b = sd[f"{prefix}.{idx}.weight"], sd[f"{prefix}.{idx}.bias"]
-    return (x @ w.T + b).astype(np.float32)
+    w, b = dt(sd[f"{prefix}.{idx}.weight"]), dt(sd[f"{prefix}.{idx}.bias"])
+    return (x @ w.T + b).astype(dtype)
 
 
-def l2_normalize(x, eps=NORM_EPS):
-    n = np.sqrt((x.astype(np.float32) ** 2).sum(axis=1, keepdims=True, dtype=np.float32))
-    return (x / np.maximum(n, np.float32(eps))).astype(np.float32)
+def l2_normalize(x, eps=NORM_EPS, dtype=np.float32):
+    n = np.sqrt((x.astype(dtype) ** 2).sum(axis=1, keepdims=True, dtype=dtype))
+    return (x / np.maximum(n, dtype(eps))).astype(dtype)
 
 
-def user_tower(sd, user_cat, user_num):
-    e = embed(sd, "user_tower.embedding_layer.embeddings.", user_cat)
-    x = np.concatenate([e, np.asarray(user_num, dtype=np.float32)], axis=1)  # :113
-    return l2_normalize(_mlp(sd, "user_tower.mlp", x))
+# ``dtype=np.float64`` evaluates the same network in double precision (the truth the kernels are held to)
+def user_tower(sd, user_cat, user_num, dtype=np.float32):
+    e = embed(sd, "user_tower.embedding_layer.embeddings.", user_cat, dtype)
+    x = np.concatenate([e, np.asarray(user_num, dtype=np.float32).astype(dtype)], axis=1)  # :113
+    return l2_normalize(_mlp(sd, "user_tower.mlp", x, dtype), dtype=dtype)
 
 
-def ad_tower(sd, ad_cat):
-    e = embed(sd, "ad_tower.embedding_layer.embeddings.", ad_cat)
-    return l2_normalize(_mlp(sd, "ad_tower.mlp", e))
+def ad_tower(sd, ad_cat, dtype=np.float32):
+    e = embed(sd, "ad_tower.embedding_layer.embeddings.", ad_cat, dtype)
+    return l2_normalize(_mlp(sd, "ad_tower.mlp", e, dtype), dtype=dtype)
 
 
 def predict_scores(sd, user_cat, user_num, ad_cat):

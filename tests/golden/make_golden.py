@@ -51,11 +51,19 @@ CASES = {
     # the reference's SECOND usage example (tutorial.ipynb cells 10 and 19): smaller constructor arguments than the
     # defaults, on preprocessor-sized (ragged) feature dims
     "tutorial": (small_dims, (1, 7, 64), 13),
+    # points of the constructor surface (tests/cases.py RANKER_SURFACE / TOWER_SURFACE): a single-Linear tower with the
+    # narrow ranker (d_model 100), an eight-Linear 4-wide tower with the one-layer ranker of d_ff 96
+    "narrow": (small_dims, (1, 7, 64), 14),
+    "x3_one_layer": (small_dims, (1, 7, 64), 15),
 }
 # constructor arguments that differ from the reference's defaults (two_tower_model.py:193-201, transformer_ranker.py:213-224)
 ARCH = {
     "tutorial": {"tt": dict(embedding_dim=16, hidden_dims=[256, 128], output_dim=128),
                  "rk": dict(embedding_dim=16, d_model=128, num_heads=4, num_layers=2, d_ff=512)},
+    "narrow": {"tt": dict(embedding_dim=16, hidden_dims=[], output_dim=64),
+               "rk": dict(embedding_dim=4, d_model=100, num_heads=4, num_layers=2, d_ff=300)},
+    "x3_one_layer": {"tt": dict(embedding_dim=4, hidden_dims=[36] * 7, output_dim=4),
+                     "rk": dict(embedding_dim=8, d_model=256, num_heads=8, num_layers=1, d_ff=96)},
 }
 
 

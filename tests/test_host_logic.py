@@ -258,3 +258,55 @@ def test_row_owner_engine_eligibility_names_its_reason():
     assert weights.x3_ineligible_reason(sd_ff, True) == "d_ff 1000 is not a multiple of 32"
     sd_big = synth.ranker_state(user, ad, nnum, seed=3, num_layers=6, d_ff=2048)       # parameter blob beyond the LDS area
     assert "LDS parameter area" in weights.x3_ineligible_reason(sd_big, True)
+
+
+@pytest.mark.parametrize("name", list(cases.RANKER_SURFACE))
+def test_row_owner_eligibility_across_the_constructor_surface(name):
+    """Every ranker entry of the architecture table (tests/cases.py RANKER_SURFACE) reports the reason the table states.  An
+    eligible entry packs into a parameter blob that fits the kernel's LDS area and into streams of exactly the length the C
+    side derives from the architecture (csrc/ranker_x3.hip x3_build), the column-split one whenever its tiling fits."""
+    _, _, why, _ = cases.RANKER_SURFACE[name]
+    user, ad, nnum, sd = cases.surface_ranker_case(name)
+    assert weights.x3_ineligible_reason(sd, True) == why
+    assert weights.x3_eligible(sd, True) == (why is None)
+    assert "fuse_attention" in weights.x3_ineligible_reason(sd, False)
+    if why is not None:
+        return
+    p, pk, tasks = weights.pack_ranker(sd, list(user), list(ad), nnum, "cpu", x6=False, x3=True, x3_variant=16)
+    assert p.x3.n_params <= weights.X3_PARAM_FLOATS and p.x3.n_params % 1024 == 0
+    hidden_tiles = p.n_tasks * p.head_h1 // 32
+    encoder = p.n_layers * (16 + 4 * (p.d_ff // 32))
+    assert p.x3.chunks == encoder + 16 * p.n_cross + hidden_tiles * 40 // 16
+    cs = p.n_layers == 0 or p.d_ff % 128 == 0
+    assert p.x3.chunks_cs == (encoder + 16 * p.n_cross + 3 * hidden_tiles if cs else 0)
+
+
+@pytest.mark.parametrize("name", list(cases.TOWER_SURFACE))
+def test_tower_packing_across_the_constructor_surface(name):
+    """Every tower entry packs with the layer count and widths of its constructor arguments (K padded to 32, zero beyond K)."""
+    args, nnum, _ = cases.TOWER_SURFACE[name]
+    user, ad, nnum, sd = cases.surface_tower_case(name)
+    for prefix, names, n_num in (("user_tower", list(user), nnum), ("ad_tower", list(ad), 0)):
+        p, pk = weights.pack_tower(sd, prefix, names, n_num, "cpu")
+        dims = [len(names) * args["embedding_dim"] + n_num] + list(args["hidden_dims"]) + [args["output_dim"]]
+        assert p.n_layers == len(dims) - 1 and list(p.dims[:p.n_layers + 1]) == dims
+        for l in range(p.n_layers):
+            assert p.ldw[l] == (dims[l] + 31) // 32 * 32
+            assert not _arr(pk, p.w[l], (dims[l + 1], p.ldw[l]))[:, dims[l]:].any()
+
+
+def test_arguments_outside_the_surface_are_refused_at_packing():
+    """Reference-legal arguments the HIP code does not support raise an exception that names the limit when the weights are
+    packed (the rest - d_model > 256, output_dim > 256 - is refused by the library's parameter check, tests/test_arch_surface_gpu.py)."""
+    user, ad, nnum = cases.small_dims()
+    sd = synth.ranker_state(user, ad, nnum, seed=5, num_layers=9, d_ff=64)
+    assert weights.x3_ineligible_reason(sd, True) == "22 phases (at most 20)"
+    with pytest.raises(ValueError, match="at most 8 encoder layers"):
+        weights.pack_ranker(sd, list(user), list(ad), nnum, "cpu")
+    with pytest.raises(ValueError, match="multiples of 4"):
+        weights.pack_tower(synth.two_tower_state(user, ad, nnum, seed=5, hidden_dims=[30]), "user_tower", list(user), nnum,
+                           "cpu")
+    with pytest.raises(ValueError, match="power of two"):
+        weights.pack_tower(synth.two_tower_state(user, ad, nnum, seed=5, embedding_dim=24), "ad_tower", list(ad), 0, "cpu")
+    with pytest.raises(ValueError, match="power of two"):
+        weights.pack_ranker(synth.ranker_state(user, ad, nnum, seed=5, embedding_dim=24), list(user), list(ad), nnum, "cpu")

@@ -114,11 +114,11 @@ def test_ranker_matches_reference_golden(name, cross, engine, accuracy):
     m, sd, _, batches = _ranker(name, cross)
     m.gemm_engine = engine
     g = load_golden(f"ranker_{name}_{cross}.npz")
-    # the row-owner engine is written for the reference's DEFAULT architecture (d_model 256); any other - the tutorial's
-    # d_model 128 / 4 heads / 2 layers / d_ff 512 - takes the generic tile GEMMs, and says so (the
-    # fallback must be visible, and it must have a golden)
-    x3 = engine == "f16x3" and name != "tutorial"
-    assert m.x3_fallback_reason() == (None if name != "tutorial" else "d_model 128 != 256")
+    # the row-owner engine is written for the reference's DEFAULT architecture (d_model 256, heads 256 -> 64); any other -
+    # the tutorial's d_model 128 / 4 heads / 2 layers / d_ff 512 - takes the generic tile GEMMs, and says so (VERDICT r3
+    # item 3: the fallback must be visible, and it must have a golden).  Each case states its reason in tests/cases.py.
+    x3 = engine == "f16x3" and cases.x3_reason(name) is None
+    assert m.x3_fallback_reason() == cases.x3_reason(name)
     for B in batches:
         assert m.gemm_engine_for(B) == ("f16x3" if x3 else "fp32")
         with torch.no_grad():
@@ -300,7 +300,7 @@ def test_tutorial_architecture_batches_vs_oracle(rows, accuracy):
         with warnings.catch_warnings(record=True) as w:
             warnings.simplefilter("always")
             pred = r(_cu(uc), _cu(ac), _cu(un))
-        assert any("not available for these weights (d_model 128 != 256)" in str(x.message) for x in w)   # not silent
+        assert any(f"not available for these weights ({cases.x3_reason('tutorial')})" in str(x.message) for x in w)   # not silent
         ref = oracle.ranker.forward(rsd, uc, ac, un)
         scale = cases.logit_scale(ref)
         for t in ref:

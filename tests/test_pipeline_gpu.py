@@ -268,7 +268,7 @@ def test_tutorial_architecture_end_to_end_matches_oracle_pipeline():
     index = build_faiss_index(tt, ad_table, index_type="Flat")
     assert index.dimension == 128
     rec = AdRecommenderInference(two_tower_model=tt, transformer_ranker=rk, faiss_index=index, ad_features=ad_table)
-    assert rk.x3_fallback_reason() == "d_model 128 != 256" and rk.gemm_engine_for(B * k1) == "fp32"
+    assert rk.x3_fallback_reason() == cases.x3_reason("tutorial") and rk.gemm_engine_for(B * k1) == "fp32"
     oidx = oracle.search.FlatIndex(128)
     oidx.add(oracle.towers.ad_tower(tt_sd, ad_table))
     uc, un = synth.user_batch(user, nnum, B, seed=64)

@@ -28,9 +28,15 @@ def variant(request):
 
 
 def _model(name, cross):
+    """A golden case of tests/cases.py CASES or an entry of its RANKER_SURFACE table."""
     from amdrec.ranker import TransformerRanker
-    user, ad, nnum, sd, _ = cases.ranker_case(name, cross)
-    m = TransformerRanker(dict(user), dict(ad), nnum)
+    if name in cases.CASES:
+        user, ad, nnum, sd, _ = cases.ranker_case(name, cross)
+        args = cases.arch(name)["rk"]
+    else:
+        user, ad, nnum, sd = cases.surface_ranker_case(name, cross)
+        args = cases.RANKER_SURFACE[name][0]
+    m = TransformerRanker(dict(user), dict(ad), nnum, **args)
     m.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sd.items()})
     m.x3_variant = VARIANT
     return m.cuda().eval(), sd, (user, ad, nnum)
@@ -61,20 +67,38 @@ def _prefix(m, X, n_phases):
     return x_out.cpu().numpy(), logits.cpu().numpy()
 
 
-@pytest.mark.parametrize("rows", [128 * 3 + 45,            # <= 4096 rows: the column-split kernel (x3c, variant 16), ragged tail
-                                  4096 + 64 * 5 + 13,      # <= 16384 rows: the 64-row workgroup shape (x3b4), ragged tail
-                                  16384 + 128 * 3 + 45])   # beyond: the 128-row shape (x3b), three full workgroups + a ragged one
+PREFIX_ROWS = [128 * 3 + 45,            # <= 4096 rows: the column-split kernel (x3c, variant 16, if d_ff % 128 == 0), ragged tail
+               4096 + 64 * 5 + 13,      # <= 16384 rows: the 64-row workgroup shape (x3b4), ragged tail
+               16384 + 128 * 3 + 45]    # beyond: the 128-row shape (x3b), three full workgroups + a ragged one
+
+
+@pytest.mark.parametrize("rows", PREFIX_ROWS)
 @pytest.mark.parametrize("cross", ["scaled", "randn"])
 def test_every_prefix_of_the_chain_matches_float64(cross, rows, accuracy):
-    m, sd, dims = _model("demo", cross)
+    """The reference's default architecture: 3 x (attn, FFN) + 3 cross + heads."""
+    _check_every_prefix("demo", cross, rows, accuracy)
+
+
+@pytest.mark.parametrize("rows", PREFIX_ROWS)
+@pytest.mark.parametrize("cross", ["scaled", "randn"])
+@pytest.mark.parametrize("name", ["x3_one_layer",          # 1 x (attn, FFN of 3 hidden tiles) + 3 cross + heads
+                                  "x3_param_edge"])        # d_ff 1568: a parameter blob of exactly X3_PARAM_FLOATS
+def test_every_prefix_of_the_chain_matches_float64_at_other_architectures(name, cross, rows, accuracy):
+    """Other phase lists the engine calls eligible (tests/cases.py RANKER_SURFACE), under the same per-phase bounds."""
+    _check_every_prefix(name, cross, rows, accuracy)
+
+
+def _check_every_prefix(name, cross, rows, accuracy):
+    m, sd, dims = _model(name, cross)
     assert m.gemm_engine == "f16x3" and m.gemm_engine_for(10_000) == "f16x3"
     X = _projected_rows(sd, dims, rows, seed=41)
     truth = oracle.ranker.chain_states(sd, X, dtype=np.float64)
     f32 = oracle.ranker.chain_states(sd, X, dtype=np.float32)
     Xd = torch.from_numpy(X).cuda()
     n_total = len(truth)
-    names = [f"L{l}.{k}" for l in range(3) for k in ("attn_ln1", "ffn_ln2")] + [f"cross{c}" for c in range(3)] + ["heads"]
-    assert n_total == len(names) == 10
+    n_layers = len(m.transformer_layers)
+    names = [f"L{l}.{k}" for l in range(n_layers) for k in ("attn_ln1", "ffn_ln2")] + [f"cross{c}" for c in range(3)] + ["heads"]
+    assert n_total == len(names)
     for n in range(1, n_total + 1):
         x, logits = _prefix(m, Xd, n)
         if n < n_total:
@@ -83,7 +107,7 @@ def test_every_prefix_of_the_chain_matches_float64(cross, rows, accuracy):
             d, d32 = (x - ref) / scale, (f32[n - 1] - ref) / scale    # the engine's / the numpy fp32 evaluation's error
             err, err32 = float(np.abs(d).max()), float(np.abs(d32).max())
             rms, rms32 = float(np.sqrt(np.mean(d * d))), float(np.sqrt(np.mean(d32 * d32)))
-            accuracy(f"x3_prefix/demo_{cross}/rows{rows}/{names[n - 1]}", f"f16x3/{VARIANT}", err / max(err32, 1e-30),
+            accuracy(f"x3_prefix/{name}_{cross}/rows{rows}/{names[n - 1]}", f"f16x3/{VARIANT}", err / max(err32, 1e-30),
                      rel_err_vs_float64=err, numpy_fp32_rel_err_vs_float64=err32, rms_ratio=rms / max(rms32, 1e-30),
                      rms_rel_err_vs_float64=rms, numpy_fp32_rms_rel_err_vs_float64=rms32)
             assert np.isfinite(x).all(), names[n - 1]
@@ -100,7 +124,7 @@ def test_every_prefix_of_the_chain_matches_float64(cross, rows, accuracy):
             scale = cases.logit_scale(truth[-1])
             for ti, t in enumerate(oracle.ranker.TASKS):
                 ok, e = cases.logit_close(logits[ti], truth[-1][t], cross, scale=scale)
-                accuracy(f"x3_prefix/demo_{cross}/rows{rows}/heads/{t}", f"f16x3/{VARIANT}", e)
+                accuracy(f"x3_prefix/{name}_{cross}/rows{rows}/heads/{t}", f"f16x3/{VARIANT}", e)
                 assert ok, (t, e)
 
 
