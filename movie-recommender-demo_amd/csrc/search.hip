@@ -414,27 +414,9 @@ __device__ __forceinline__ float wave_tau(const float* row, long long n, int r, 
     return __uint_as_float(b);
 }
 
-// Round-4 switches of the corpus pass (bits of AMDREC_SCAN_OPT; same-box A/Bs: tools/scan_ab.sh, profiles/r04_scan_*):
-// DEFAULT 32.  Measured and NOT adopted (profiles/r04_scan_ab.log, same box, search-only loop at 512 / 128 queries): 1 ->
-// 0.287-0.297 against 0.286-0.287 ms per pass, 17 -> 0.285-0.287 against 0.283-0.287, 2 -> 0.288-0.289 against 0.280-0.282
-// (0.151 against 0.118 at 128 queries: a 64-row slot leaves the spare waves of a small group half the row parts), 3 ->
-// 0.298-0.301, 96 -> 0.311-0.312 against 0.289-0.290 (13 spilled registers).  Adopted: 32 -> 0.289-0.292 against 0.296-0.297
-// at 512 queries, neutral below.  Diagnostic bits: 4 = no
-// corpus DMA (the waves compute on whatever the ring holds), 8 = no hit handling (old quarter code only).
-//  32  the quarter's LDS-read / MFMA interleave spelled out with sched_group_barrier (the scheduler otherwise hoists all 16
-//      fragment reads of a quarter in front of its first MFMA)
-//  64  (with 32) two accumulator sets ping-pong: the previous quarter's threshold scan rides between the current quarter's
-//      MFMAs and the next quarter's first fragments are requested behind its last ones
-//  16  (with 1) the A fragments are carried across the units: a unit's last MFMAs prefetch the next unit's first fragments
-//   2  ring of four 64-row slots instead of two 128-row tiles (DESIGN section 7.3's experiment): DMA three slots ahead
-//   1  j-major MFMA order with the threshold scan of the PREVIOUS (32 rows x 32 queries) accumulator interleaved between the
-//      MFMAs of the current one: the scan (and its hit path) used to run after a quarter's last MFMA with the matrix pipe
-//      idle - and both waves of a SIMD reach that point together, the tile barrier keeps them in step.  Costs a second
-//      read of every A fragment (once per query tile); no extra registers (the two accumulators ping-pong).
-#ifndef AMDREC_SCAN_OPT
-#define AMDREC_SCAN_OPT 32
-#endif
-constexpr int SCAN_OPT = AMDREC_SCAN_OPT;
+// Round 4 measured four other variants of the corpus pass and builds without its DMA or its hit path; none is kept
+// (profiles/r04_scan_ab.log, profiles/r04_scan_elim.log).  They are compile-time switches in
+// `git show 4973481e75:movie-recommender-demo_amd/csrc/search.hip`, the last version that has them.
 constexpr int SCAN_ROWS = 128;          // corpus rows per LDS tile
 constexpr int SCAN_WHITS = 128;         // hit-list entries per wave and tile (expected ~11; overflow -> direct append)
 constexpr int SCAN_QGROUP = 512;        // queries per workgroup (8 waves x 64)
@@ -447,14 +429,35 @@ __device__ __forceinline__ void lds_store_hit_opaque(uint32_t key_addr, unsigned
     asm volatile("ds_write_b64 %0, %1\n\tds_write_b32 %2, %3" ::"v"(key_addr), "v"(key), "v"(q_addr), "v"(q) : "memory");
 }
 
-// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): an index walk whose indices are constants in the body
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (N > 0) {
-        static_for<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
+// 16 bytes from global `g` to LDS `l` by LDS-DMA (the LDS address is wave-uniform: lane i's bytes land at l + 16 i)
+__device__ __forceinline__ void lds_dma16(const unsigned char* g, unsigned char* l) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l,
+                                     16, 0, 0);
 }
+
+// The LDS tile of the streaming passes (scan_filter_kernel, sample_max_kernel) for KS = dim / 16: SCAN_ROWS rows of CPR
+// 16-byte chunks, the chunk slot swizzled by row, filled by PASSES LDS-DMA passes of the workgroup's 512 lanes.
+// DMA lane map: LDS chunk slot L = u * 512 + tid of pass u -> row u * RPP + tid / CPR, slot tid % CPR; the source chunk
+// (slot ^ swizzle(row)) does not depend on u (RPP is a multiple of the swizzle period), so a lane's source address is a
+// per-lane byte offset plus a scalar per (tile, pass).
+template <int KS>
+struct ScanTile {
+    static constexpr int CPR = 2 * KS;                                  // 16-byte chunks per row
+    static constexpr int FM = CPR < 16 ? CPR - 1 : 15;                  // swizzle mask
+    static constexpr int FS = CPR >= 16 ? 0 : (CPR == 8 ? 1 : 2);       // swizzle row shift
+    static constexpr int CHUNKS = SCAN_ROWS * CPR;
+    static constexpr int PASSES = CHUNKS / 512;
+    static constexpr int RPP = 512 / CPR;                               // rows per DMA pass
+    static constexpr int AHEAD = KS < 4 ? KS : 4;                       // A fragments read ahead of their MFMA
+    static_assert(CHUNKS % 512 == 0, "tile must fill whole DMA passes");
+
+    // byte offset of lane tid's source chunk in its row (row tid / CPR of every pass)
+    static __device__ __forceinline__ int src_chunk(int tid) { return ((tid % CPR) ^ (((tid / CPR) >> FS) & FM)) * 16; }
+    // byte offset of lane tid's source chunk from a pass's first row, in a corpus of row stride ld16 bf16 values
+    static __device__ __forceinline__ uint32_t lane_off(int tid, long long ld16) {
+        return (uint32_t)(tid / CPR * (int)ld16 * 2 + src_chunk(tid));
+    }
+};
 
 template <int KS>                       // KS = dim / 16 in {2, 4, 8, 16}
 __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __restrict__ X16, long long ld16,
@@ -463,19 +466,9 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
                                                              int* segcnt, int* ocnt, int seg_cap, int nx,
                                                              const float* __restrict__ gm, long long ldm, long long gm_n,
                                                              int rank) {
-    constexpr int CPR = 2 * KS;                                  // 16-byte chunks per row
-    constexpr int FM = CPR < 16 ? CPR - 1 : 15;                  // swizzle mask
-    constexpr int FS = CPR >= 16 ? 0 : (CPR == 8 ? 1 : 2);       // swizzle row shift
-    // SCAN_OPT & 2: the ring is FOUR slots of 64 rows instead of two of 128 (same 128 KB): a slot's DMA is issued three slots
-    // ahead of its first read instead of one tile ahead, and the workgroup meets at a barrier every 64 rows
-    constexpr bool RING4 = (SCAN_OPT & 2) != 0 && KS >= 4;
-    constexpr int TR = RING4 ? 64 : SCAN_ROWS;                   // corpus rows per ring slot
-    constexpr int NSLOT = RING4 ? 4 : 2;
-    constexpr int QPT = TR / 32;                                 // 32-row quarters per slot
-    constexpr int TILE_CHUNKS = TR * CPR;
-    constexpr int PASSES = TILE_CHUNKS / 512;
-    constexpr int AHEAD = KS < 4 ? KS : 4;                       // A fragments read ahead of their MFMA
-    static_assert(TILE_CHUNKS % 512 == 0, "tile must fill whole DMA passes");
+    using Tile = ScanTile<KS>;
+    constexpr int CPR = Tile::CPR, TILE_CHUNKS = Tile::CHUNKS, AHEAD = Tile::AHEAD;
+    constexpr int NSLOT = 2;                                     // ring slots of SCAN_ROWS rows: the DMA runs a tile ahead
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     unsigned char* tilebuf = lds;                                                  // [NSLOT][TILE_CHUNKS * 16]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -492,11 +485,11 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
     // queries of their own take a share of the tile's ROWS instead: 1 / 2 / 4 / 8 query waves x up to four 32-row parts.
     const int nqg = nq - by * SCAN_QGROUP < SCAN_QGROUP ? nq - by * SCAN_QGROUP : SCAN_QGROUP;
     const int qsh = nqg <= 64 ? 0 : (nqg <= 128 ? 1 : (nqg <= 256 ? 2 : 3));       // log2 of the query waves
-    const int parts = (8 >> qsh) < QPT ? (8 >> qsh) : QPT;                          // 128-row slots: 4 / 4 / 2 / 1
+    const int parts = (8 >> qsh) < 4 ? (8 >> qsh) : 4;                              // 4 / 4 / 2 / 1
     const int part = w >> qsh;
     const int q0 = by * SCAN_QGROUP + (w & ((1 << qsh) - 1)) * 64;
     const bool active = q0 < nq && part < parts;
-    const int rq_begin = part * (QPT / parts), rq_end = rq_begin + QPT / parts;
+    const int rq_begin = part * (4 / parts), rq_end = rq_begin + 4 / parts;
     const bool second = q0 + 32 < nq;                                              // second query tile has real queries
     const int ntiles = (int)((nrows + SCAN_ROWS - 1) / SCAN_ROWS);
     const int nrows_i = (int)nrows;                                                // < 2^31 (checked by the entry point)
@@ -513,35 +506,22 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
             qf[j][s_] = *reinterpret_cast<const bf16x8*>(Q16 + (long long)qc * (16 * KS) + (2 * s_ + fh) * 8);
     }
 
-    // DMA lane map: LDS chunk slot L = u * 512 + tid of pass u -> row u * RPP + tid / CPR, slot tid % CPR; the source
-    // chunk (slot ^ swizzle(row)) does not depend on u (RPP is a multiple of the swizzle period), so a lane's source
-    // address is a per-lane byte offset plus a scalar per (tile, pass)
-    constexpr int RPP = 512 / CPR;                                 // rows per DMA pass
-    const int drow = tid / CPR;
-    const uint32_t lane_off = (uint32_t)(drow * (int)ld16 * 2 + (((tid % CPR) ^ ((drow >> FS) & FM)) * 16));
-    auto dma = [&](int row0i, int buf) {                           // TR rows from corpus row `row0i` into ring slot `buf`
-        if (SCAN_OPT & 4) return;                                  // (diagnostic build)
+    const uint32_t lane_off = Tile::lane_off(tid, ld16);
+    auto dma = [&](int row0i, int buf) {                           // SCAN_ROWS rows from corpus row `row0i` into ring slot `buf`
         const long long row0 = row0i;
         unsigned char* lbase = tilebuf + (size_t)buf * TILE_CHUNKS * 16 + (size_t)(w * 64) * 16;           // wave-uniform
-        if (row0 + TR <= nrows) {
+        if (row0 + SCAN_ROWS <= nrows) {
             const unsigned char* gb = reinterpret_cast<const unsigned char*>(X16) + row0 * ld16 * 2;
 #pragma unroll
-            for (int u = 0; u < PASSES; ++u) {
-                const unsigned char* g = gb + (long long)u * RPP * ld16 * 2 + lane_off;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                                 (__attribute__((address_space(3))) void*)(lbase + (size_t)u * 512 * 16),
-                                                 16, 0, 0);
-            }
+            for (int u = 0; u < Tile::PASSES; ++u)
+                lds_dma16(gb + (long long)u * Tile::RPP * ld16 * 2 + lane_off, lbase + (size_t)u * 512 * 16);
         } else {                                                   // last tile: rows past the end are clamped
 #pragma unroll
-            for (int u = 0; u < PASSES; ++u) {
-                long long r = row0 + u * RPP + drow;
-                r = r < nrows ? r : nrows - 1;                     // (a slot wholly past the end reads the last row: never a hit)
-                const unsigned char* g = reinterpret_cast<const unsigned char*>(X16) + r * ld16 * 2 +
-                                         (((tid % CPR) ^ ((drow >> FS) & FM)) * 16);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                                 (__attribute__((address_space(3))) void*)(lbase + (size_t)u * 512 * 16),
-                                                 16, 0, 0);
+            for (int u = 0; u < Tile::PASSES; ++u) {
+                long long r = row0 + u * Tile::RPP + tid / CPR;
+                r = r < nrows ? r : nrows - 1;
+                lds_dma16(reinterpret_cast<const unsigned char*>(X16) + r * ld16 * 2 + Tile::src_chunk(tid),
+                          lbase + (size_t)u * 512 * 16);
             }
         }
     };
@@ -582,18 +562,16 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
             for (int j = 0; j < NJ; ++j)
                 acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur, qf[j][s_], acc[j], 0, 0, 0);
         }
-        if constexpr ((SCAN_OPT & 32) != 0) {
-            // The source reads a fragment AHEAD k-steps before its MFMAs, but the machine scheduler hoists ALL KS reads of the
-            // quarter to its top (it has the registers) and waits for the last of them before the first MFMA: a quarter then
-            // runs [16 LDS reads, one full wait] [32 MFMAs] [threshold scan] with nothing overlapped - 0.21 ms per pass with
-            // DMA and hits compiled out, against 0.10 at the MFMA rate (profiles/r04_scan_elim.log, the ISA in DESIGN.md).
-            // The schedule is therefore spelled out: AHEAD reads, then per k-step the NJ MFMAs followed by one read.
-            __builtin_amdgcn_sched_group_barrier(0x100, AHEAD, 0);                       // DS reads
+        // The source reads a fragment AHEAD k-steps before its MFMAs, but the machine scheduler hoists ALL KS reads of the
+        // quarter to its top (it has the registers) and waits for the last of them before the first MFMA: a quarter then
+        // runs [16 LDS reads, one full wait] [32 MFMAs] [threshold scan] with nothing overlapped - 0.21 ms per pass with
+        // DMA and hits compiled out, against 0.10 at the MFMA rate (profiles/r04_scan_elim.log, the ISA in DESIGN.md).
+        // The schedule is therefore spelled out: AHEAD reads, then per k-step the NJ MFMAs followed by one read.
+        __builtin_amdgcn_sched_group_barrier(0x100, AHEAD, 0);                           // DS reads
 #pragma unroll
-            for (int s_ = 0; s_ < KS; ++s_) {
-                __builtin_amdgcn_sched_group_barrier(0x008, NJ, 0);                      // MFMAs of k-step s_
-                if (s_ + AHEAD < KS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // the read AHEAD steps on
-            }
+        for (int s_ = 0; s_ < KS; ++s_) {
+            __builtin_amdgcn_sched_group_barrier(0x008, NJ, 0);                          // MFMAs of k-step s_
+            if (s_ + AHEAD < KS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // the read AHEAD steps on
         }
         // Threshold scan.  A hit is rare per element (~1.4e-3) but a taken branch per element costs more than the
         // MFMAs it follows, so four elements share one test (their maximum; NaN never wins) and the per-element code is
@@ -606,7 +584,6 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
             for (int g = 0; g < 4; ++g) {
                 const float m4 = fmaxf(fmaxf(acc[j][4 * g], acc[j][4 * g + 1]), fmaxf(acc[j][4 * g + 2], acc[j][4 * g + 3]));
                 if (__builtin_expect(__ballot(m4 >= tq[j]) == 0ull, 1)) continue;
-                if (SCAN_OPT & 8) { asm volatile("" ::"v"(m4)); continue; }     // (diagnostic build: the test, never the hit path)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float sc = acc[j][4 * g + e];
@@ -629,116 +606,12 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
             }
     };
 
-    // SCAN_OPT & 1.  The threshold test of ONE 4-element group of accumulator `p` (rows prow + e + 8 g of query tile j).
-    auto scan_group = [&](auto full_tag, const f32x16& p, auto g_tag, float tqj, int qj0, int prow, uint32_t list_addr, int& wcount) {
-        constexpr bool FULL = decltype(full_tag)::value;
-        constexpr int g = decltype(g_tag)::value;
-        const float m4 = fmaxf(fmaxf(p[4 * g], p[4 * g + 1]), fmaxf(p[4 * g + 2], p[4 * g + 3]));
-        if (__builtin_expect(__ballot(m4 >= tqj) == 0ull, 1)) return;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float sc = p[4 * g + e];
-            const int pr = prow + e + 8 * g;
-            const bool hit = sc >= tqj && (FULL || pr < nrows_i);
-            const unsigned long long mask = __ballot(hit);
-            if (mask) {                                            // wave-uniform
-                if (hit) {
-                    const int q = qj0 + frow;
-                    const unsigned long long key = make_key(sc, (uint32_t)pr);
-                    const int slot = wcount + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-                    if (slot < SCAN_WHITS)
-                        lds_store_hit_opaque(list_addr + slot * 8, key, list_addr + SCAN_WHITS * 8 + slot * 4, q);
-                    else append(q, key);
-                }
-                wcount += __builtin_popcountll(mask);
-            }
-        }
-    };
-    // One unit = 32 corpus rows x query tile J: the K loop into `cur`, with the four group tests of the previous unit's
-    // accumulator `prv` placed behind MFMAs KS/4 - 1, 2 KS/4 - 1, ... (each test - three max, a compare, a ballot - runs in
-    // the shadow of the MFMA in front of it; the wave is back at the next, dependent MFMA before that one has finished).
-    auto chain_scan = [&](auto j_tag, auto scan_tag, auto full_tag, const unsigned char* lb, int G, f32x16& cur,
-                          const f32x16& prv, float tprv, int qprv0, int prow_prv, uint32_t list_addr, int& wcount,
-                          bf16x8 (&a)[AHEAD], const unsigned char* lb_next) {
-        constexpr int J = decltype(j_tag)::value;
-        constexpr bool SCAN = decltype(scan_tag)::value;
-        constexpr bool CARRY = (SCAN_OPT & 16) != 0;               // fragments carried across units (see below)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) cur[r] = 0.f;
-        if constexpr (!CARRY) {
-#pragma unroll
-            for (int s_ = 0; s_ < AHEAD; ++s_) a[s_] = *reinterpret_cast<const bf16x8*>(lb + ((32 * s_) ^ G));
-        }
-        // (a compile-time index walk: with a `#pragma unroll` loop the compiler kept the K loop rolled around the group tests'
-        //  branches and indexed the query fragments dynamically - 512 bytes of scratch per lane)
-        static_for<KS>([&](auto s_tag) {
-            constexpr int s_ = decltype(s_tag)::value;
-            const bf16x8 c = a[s_ % AHEAD];
-            if constexpr (s_ + AHEAD < KS) a[s_ % AHEAD] = *reinterpret_cast<const bf16x8*>(lb + ((32 * (s_ + AHEAD)) ^ G));
-            // SCAN_OPT & 16: the NEXT unit's first fragments are requested behind this unit's last MFMAs (the swizzle term G
-            // is the same for every 32-row quarter), so a unit no longer opens with an LDS round trip on an empty matrix pipe
-            else if constexpr (CARRY) a[s_ % AHEAD] = *reinterpret_cast<const bf16x8*>(lb_next + ((32 * (s_ + AHEAD - KS)) ^ G));
-            cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c, qf[J][s_], cur, 0, 0, 0);
-            if constexpr (SCAN) {
-                static_for<(4 * (s_ + 1)) / KS - (4 * s_) / KS>([&](auto g_tag) {
-                    constexpr int g = (4 * s_) / KS + decltype(g_tag)::value;
-                    __builtin_amdgcn_sched_barrier(0);             // the test stays BEHIND this MFMA (and in front of the next)
-                    scan_group(full_tag, prv, std::integral_constant<int, g>{}, tprv, qprv0, prow_prv, list_addr, wcount);
-                    __builtin_amdgcn_sched_barrier(0);
-                });
-            }
-        });
-    };
-
-    // SCAN_OPT & 64.  One quarter (32 rows x NJ query tiles, k-step major: a fragment feeds both tiles) into `cur`, with (i) the
-    // NEXT quarter's first fragments requested behind its last MFMAs, so that no quarter opens with an LDS round trip on an empty
-    // matrix pipe, and (ii) the threshold scan of the PREVIOUS quarter's accumulators `prv` placed between its MFMAs - one
-    // group of tests behind every KS / 4 k-steps - instead of behind its last MFMA with the pipe idle.  Two accumulator sets
-    // ping-pong (+32 registers, which the spelled-out read schedule of bit 32 had freed).
-    auto step = [&](auto nj_tag, auto scan_tag, auto full_tag, const unsigned char* lq, const unsigned char* lnext, int G,
-                    auto& cur, const auto& prv, int prow_prv, uint32_t list_addr, int& wcount, bf16x8 (&a)[AHEAD]) {
-        constexpr int NJ = decltype(nj_tag)::value;
-        constexpr bool SCAN = decltype(scan_tag)::value;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) cur[j][r] = 0.f;
-        static_for<4>([&](auto seg_tag) {                          // four segments of KS / 4 k-steps, a test group behind each
-            constexpr int SEG = decltype(seg_tag)::value;
-            constexpr int S0 = SEG * KS / 4, S1 = (SEG + 1) * KS / 4;
-            static_for<S1 - S0>([&](auto d_tag) {
-                constexpr int s_ = S0 + decltype(d_tag)::value;
-                const bf16x8 c = a[s_ % AHEAD];
-                if constexpr (s_ + AHEAD < KS) a[s_ % AHEAD] = *reinterpret_cast<const bf16x8*>(lq + ((32 * (s_ + AHEAD)) ^ G));
-                else a[s_ % AHEAD] = *reinterpret_cast<const bf16x8*>(lnext + ((32 * (s_ + AHEAD - KS)) ^ G));
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) cur[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c, qf[j][s_], cur[j], 0, 0, 0);
-            });
-#pragma unroll
-            for (int d = 0; d < S1 - S0; ++d) {                    // this segment's schedule: per k-step its MFMAs, then its read
-                __builtin_amdgcn_sched_group_barrier(0x008, NJ, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-            if constexpr (SCAN) {
-                __builtin_amdgcn_sched_barrier(0);
-                static_for<NJ>([&](auto j_tag) {
-                    constexpr int j = decltype(j_tag)::value;
-                    scan_group(full_tag, prv[j], seg_tag, tq[j], q0 + j * 32, prow_prv, list_addr, wcount);
-                });
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        });
-    };
-
-    // slot sequence of this workgroup: tiles bx, bx + nx, ... of 128 rows, each SPT = 128 / TR slots
-    constexpr int SPT = SCAN_ROWS / TR;
+    // tile sequence of this workgroup: bx, bx + nx, ...
     const int my_tiles = bx < ntiles ? (ntiles - bx + nx - 1) / nx : 0;
-    const int nslots = my_tiles * SPT;
-    auto slot_row0 = [&](int i) { return (bx + (i / SPT) * nx) * SCAN_ROWS + (i % SPT) * TR; };   // < 2^31 (entry point)
+    auto tile_row0 = [&](int i) { return (bx + i * nx) * SCAN_ROWS; };             // < 2^31 (entry point)
 #pragma unroll
     for (int i = 0; i < NSLOT - 1; ++i)
-        if (i < nslots) dma(slot_row0(i), i);
+        if (i < my_tiles) dma(tile_row0(i), i);
     // Thresholds.  Batches of <= 8 queries (gm != nullptr): no threshold launch - while the first tile is in flight wave w
     // computes tau of query w from the sample's group maxima (wave_tau: a deterministic function of gm, so every workgroup
     // arrives at the same value), workgroup 0 publishes it for the finalize.  Columns >= nq get NaN: no score compares >= it.
@@ -752,20 +625,19 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
             }
         }
     }
-    if (NSLOT == 2 || nslots < NSLOT - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSLOT - 2) * PASSES) : "memory");      // slot 0 (the oldest) has landed
-    __syncthreads();                                               // first slot landed, tau_sh written
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();                                               // first tile landed, tau_sh written
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int q = q0 + j * 32 + frow;
         tq[j] = (q < nq) ? (gm != nullptr ? tau_sh[q] : tau[q]) : __builtin_nanf("");
     }
-    int it = 0, wprev = 0;                                         // wprev: hits of the previous slot awaiting their append
-    for (; it < nslots; ++it) {
+    int it = 0, wprev = 0;                                         // wprev: hits of the previous tile awaiting their append
+    for (; it < my_tiles; ++it) {
         const int buf = it % NSLOT, lst = it & 1;
-        const int prow0 = slot_row0(it);
-        // previous slot's hits: slots from the LDS counters, keys to the segment - issued BEFORE this slot's DMA so that the
-        // end-of-slot wait for the DMA (vmcnt counts in order) never waits for these stores
+        const int prow0 = tile_row0(it);
+        // previous tile's hits: slots from the LDS counters, keys to the segment - issued BEFORE this tile's DMA so that the
+        // end-of-tile wait for the DMA (vmcnt counts in order) never waits for these stores
         const unsigned char* lprev = hitbase + (lst ^ 1) * LIST_STRIDE;
         const int npend = wprev < SCAN_WHITS ? wprev : SCAN_WHITS;
         for (int h = lane; h < npend; h += 64)
@@ -774,138 +646,44 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
         // (the DMA goes out right after the barrier: issuing it behind the first quarter's MFMAs, the move that gained 4 % in
         // the row-owner kernel, cost 30 % here - 0.355 against 0.268 ms at 512 queries, profiles/r03_scan_late_dma_ab.log: with a
         // two-deep ring the next tile needs the whole of this tile's compute time to land)
-        // the slot read NSLOT - 1 iterations from now: its ring slot was read in the previous iteration
-        if (it + NSLOT - 1 < nslots) dma(slot_row0(it + NSLOT - 1), (it + NSLOT - 1) % NSLOT);
+        // the tile read NSLOT - 1 iterations from now: its ring slot was read in the previous iteration
+        if (it + NSLOT - 1 < my_tiles) dma(tile_row0(it + NSLOT - 1), (it + NSLOT - 1) % NSLOT);
         int wcount = 0;
         if (active) {
             // fragment address = lane row base + compile-time row offset + ((32 s) ^ G): the swizzle term depends on
             // the lane only through G.  G is made opaque per 32-row step so that the fragment addresses are recomputed
             // (one v_xor each) instead of being hoisted out of the loops into live registers (spills at KS = 16).
-            int G = (fh ^ ((frow >> FS) & FM)) << 4;
+            int G = (fh ^ ((frow >> Tile::FS) & Tile::FM)) << 4;
             const unsigned char* lb = tilebuf + (size_t)buf * TILE_CHUNKS * 16 + frow * CPR * 16;
             const uint32_t list_addr =
                 (uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)(hitbase + lst * LIST_STRIDE);
-            const bool full = prow0 + TR <= nrows_i;
-            using I0 = std::integral_constant<int, 0>;
+            const bool full = prow0 + SCAN_ROWS <= nrows_i;
+            // one quarter LOOP per (query tiles, full tile) variant: with the variant chosen inside the loop the compiler
+            // merged the four variants' identical fragment reads in front of the branch - in a different basic block than
+            // their MFMAs, where no schedule can interleave them
+            auto quarters = [&](auto nj_tag, auto full_tag) {
+#pragma unroll 1
+                for (int rq = rq_begin; rq < rq_end; ++rq) {
+                    asm volatile("" : "+v"(G));
+                    quarter(nj_tag, full_tag, lb + rq * 32 * CPR * 16, G, prow0 + rq * 32 + 4 * fh, list_addr, wcount);
+                }
+            };
             using I1 = std::integral_constant<int, 1>;
             using I2 = std::integral_constant<int, 2>;
-            if ((SCAN_OPT & 1) && second) {
-                // units (rq, j = 0), (rq, 1), (rq + 1, 0) ...: accumulators acc0 / acc1 ping-pong, each unit's MFMAs carry the
-                // threshold scan of the unit before it; the tile's last unit is scanned on its own
-                f32x16 acc0, acc1;
-                const int qa = q0, qb = q0 + 32;
-                auto tile_units = [&](auto full_tag) {
-                    asm volatile("" : "+v"(G));
-                    bf16x8 afr[AHEAD];
-                    const unsigned char* l0 = lb + rq_begin * 32 * CPR * 16;
-                    if constexpr ((SCAN_OPT & 16) != 0) {
-#pragma unroll
-                        for (int s_ = 0; s_ < AHEAD; ++s_) afr[s_] = *reinterpret_cast<const bf16x8*>(l0 + ((32 * s_) ^ G));
-                    }
-                    chain_scan(I0{}, std::false_type{}, full_tag, l0, G, acc0, acc1, 0.f, 0, 0, list_addr, wcount, afr, l0);
-#pragma unroll 1
-                    for (int rq = rq_begin; rq < rq_end; ++rq) {
-                        asm volatile("" : "+v"(G));
-                        const int prow = prow0 + rq * 32 + 4 * fh;
-                        const unsigned char* lq = lb + rq * 32 * CPR * 16;
-                        // (the last unit of the slot prefetches its own quarter again: four harmless reads instead of a branch)
-                        const unsigned char* ln = rq + 1 < rq_end ? lq + 32 * CPR * 16 : lq;
-                        chain_scan(I1{}, std::true_type{}, full_tag, lq, G, acc1, acc0, tq[0], qa, prow, list_addr, wcount, afr, ln);
-                        if (rq + 1 < rq_end) {
-                            chain_scan(I0{}, std::true_type{}, full_tag, ln, G, acc0, acc1, tq[1], qb, prow, list_addr, wcount,
-                                       afr, ln);
-                        } else {
-                            static_for<4>([&](auto g_tag) { scan_group(full_tag, acc1, g_tag, tq[1], qb, prow, list_addr, wcount); });
-                        }
-                    }
-                };
-                if (full) tile_units(std::true_type{});
-                else tile_units(std::false_type{});
-            } else if constexpr ((SCAN_OPT & 32) != 0) {
-                // one quarter LOOP per (query tiles, full slot) variant: with the variant chosen inside the loop the compiler
-                // merged the four variants' identical fragment reads in front of the branch - in a different basic block than
-                // their MFMAs, where no schedule can interleave them
-                auto quarters = [&](auto nj_tag, auto full_tag) {
-                    if constexpr ((SCAN_OPT & 64) != 0) {
-                        constexpr int NJ = decltype(nj_tag)::value;
-                        constexpr int QB = 32 * CPR * 16;                      // LDS bytes of a 32-row quarter
-                        f32x16 accA[NJ], accB[NJ];
-                        bf16x8 afr[AHEAD];
-                        asm volatile("" : "+v"(G));
-                        const unsigned char* l0 = lb + rq_begin * QB;
-                        const int pr0 = prow0 + 4 * fh;
-#pragma unroll
-                        for (int s_ = 0; s_ < AHEAD; ++s_) afr[s_] = *reinterpret_cast<const bf16x8*>(l0 + ((32 * s_) ^ G));
-                        // (the slot's last quarter prefetches its own first fragments again: four harmless reads, no branch)
-                        step(nj_tag, std::false_type{}, full_tag, l0, rq_begin + 1 < rq_end ? l0 + QB : l0, G, accA, accB, 0,
-                             list_addr, wcount, afr);
-                        int rq = rq_begin + 1;
-#pragma unroll 1
-                        for (; rq + 1 < rq_end; rq += 2) {                     // quarters rq (into B) and rq + 1 (into A)
-                            asm volatile("" : "+v"(G));
-                            const unsigned char* lq = lb + rq * QB;
-                            step(nj_tag, std::true_type{}, full_tag, lq, lq + QB, G, accB, accA, pr0 + (rq - 1) * 32, list_addr,
-                                 wcount, afr);
-                            step(nj_tag, std::true_type{}, full_tag, lq + QB, rq + 2 < rq_end ? lq + 2 * QB : lq + QB, G, accA, accB,
-                                 pr0 + rq * 32, list_addr, wcount, afr);
-                        }
-                        if (rq < rq_end) {
-                            asm volatile("" : "+v"(G));
-                            const unsigned char* lq = lb + rq * QB;
-                            step(nj_tag, std::true_type{}, full_tag, lq, lq, G, accB, accA, pr0 + (rq - 1) * 32, list_addr, wcount, afr);
-                            static_for<NJ>([&](auto j_tag) {
-                                constexpr int j = decltype(j_tag)::value;
-                                static_for<4>([&](auto g_tag) {
-                                    scan_group(full_tag, accB[j], g_tag, tq[j], q0 + j * 32, pr0 + rq * 32, list_addr, wcount);
-                                });
-                            });
-                        } else {
-                            static_for<NJ>([&](auto j_tag) {
-                                constexpr int j = decltype(j_tag)::value;
-                                static_for<4>([&](auto g_tag) {
-                                    scan_group(full_tag, accA[j], g_tag, tq[j], q0 + j * 32, pr0 + (rq - 1) * 32, list_addr, wcount);
-                                });
-                            });
-                        }
-                        return;
-                    }
-#pragma unroll 1
-                    for (int rq = rq_begin; rq < rq_end; ++rq) {
-                        asm volatile("" : "+v"(G));
-                        quarter(nj_tag, full_tag, lb + rq * 32 * CPR * 16, G, prow0 + rq * 32 + 4 * fh, list_addr, wcount);
-                    }
-                };
-                if (second) {
-                    if (full) quarters(I2{}, std::true_type{});
-                    else      quarters(I2{}, std::false_type{});
-                } else {
-                    if (full) quarters(I1{}, std::true_type{});
-                    else      quarters(I1{}, std::false_type{});
-                }
-            } else
-#pragma unroll 1
-            for (int rq = rq_begin; rq < rq_end; ++rq) {
-                asm volatile("" : "+v"(G));
-                const int prow = prow0 + rq * 32 + 4 * fh;
-                const unsigned char* lq = lb + rq * 32 * CPR * 16;
-                if (second) {
-                    if (full) quarter(I2{}, std::true_type{}, lq, G, prow, list_addr, wcount);
-                    else      quarter(I2{}, std::false_type{}, lq, G, prow, list_addr, wcount);
-                } else {
-                    if (full) quarter(I1{}, std::true_type{}, lq, G, prow, list_addr, wcount);
-                    else      quarter(I1{}, std::false_type{}, lq, G, prow, list_addr, wcount);
-                }
+            if (second) {
+                if (full) quarters(I2{}, std::true_type{});
+                else      quarters(I2{}, std::false_type{});
+            } else {
+                if (full) quarters(I1{}, std::true_type{});
+                else      quarters(I1{}, std::false_type{});
             }
         }
         wprev = wcount;
-        // my share of the NEXT slot has landed, my hit stores are done.  Two slots: the DMA issued above is the youngest
-        // operation and is waited for.  Four slots: only that DMA (PASSES instructions) may stay in flight - everything older,
-        // the next slot's DMA and the appends included, is complete.
-        if (NSLOT == 2 || !(it + NSLOT - 1 < nslots)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(PASSES) : "memory");
-        __syncthreads();                 // this slot consumed by every wave, the next one visible
+        // my share of the next tile has landed, my hit stores are done: the DMA issued above is the youngest operation
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();                 // this tile consumed by every wave, the next one visible
     }
-    // the last slot's hits
+    // the last tile's hits
     const unsigned char* llast = hitbase + ((it & 1) ^ 1) * LIST_STRIDE;
     const int nlast = wprev < SCAN_WHITS ? wprev : SCAN_WHITS;
     for (int h = lane; h < nlast; h += 64)
@@ -929,15 +707,16 @@ __global__ __launch_bounds__(512, 1) void sample_max_kernel(const uint16_t* __re
                                                             int n_tiles, const float* __restrict__ Q, long long ldq, int nq,
                                                             uint16_t* __restrict__ Q16, float* __restrict__ gm, long long ldm,
                                                             int nx, int* zero, long long n_zero) {
-    constexpr int CPR = 2 * KS, FM = CPR < 16 ? CPR - 1 : 15, FS = CPR >= 16 ? 0 : (CPR == 8 ? 1 : 2);
-    constexpr int TILE_CHUNKS = SCAN_ROWS * CPR, PASSES = TILE_CHUNKS / 512, AHEAD = KS < 4 ? KS : 4, RPP = 512 / CPR;
+    using Tile = ScanTile<KS>;
+    constexpr int CPR = Tile::CPR, TILE_CHUNKS = Tile::CHUNKS, PASSES = Tile::PASSES, AHEAD = Tile::AHEAD;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];                      // [2][TILE_CHUNKS * 16]
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int frow = lane & 31, fh = lane >> 5;
     const int bx = blockIdx.x % nx, by = blockIdx.x / nx;
     for (long long i = (long long)blockIdx.x * 512 + tid; i < n_zero; i += (long long)gridDim.x * 512) zero[i] = 0;
-    // the same work split as the corpus pass: waves without queries of their own take a share of the tile's rows
+    // the same work split as the corpus pass: waves without queries of their own take a share of the tile's rows (written
+    // out in both kernels: a shared helper, or one kernel's expression for `parts` in the other, changes their code)
     const int nqg = nq - by * SCAN_QGROUP < SCAN_QGROUP ? nq - by * SCAN_QGROUP : SCAN_QGROUP;
     const int qsh = nqg <= 64 ? 0 : (nqg <= 128 ? 1 : (nqg <= 256 ? 2 : 3));
     const int parts = qsh <= 1 ? 4 : (qsh == 2 ? 2 : 1);
@@ -970,19 +749,14 @@ __global__ __launch_bounds__(512, 1) void sample_max_kernel(const uint16_t* __re
             if (wr && q0 + j * 32 < nq) *reinterpret_cast<u32x4*>(Q16 + (long long)q * (16 * KS) + (2 * s_ + fh) * 8) = pk;
         }
     }
-    // tile DMA: the lane map of scan_filter_kernel (sample tiles are whole tiles: no clamped path)
-    const int drow = tid / CPR;
-    const uint32_t lane_off = (uint32_t)(drow * (int)ld16 * 2 + (((tid % CPR) ^ ((drow >> FS) & FM)) * 16));
+    // tile DMA (sample tiles are whole tiles: no clamped path)
+    const uint32_t lane_off = Tile::lane_off(tid, ld16);
     auto dma = [&](int st_, int buf) {
         const long long row0 = (long long)st_ * tstride * SCAN_ROWS;
         unsigned char* lbase = lds + (size_t)buf * TILE_CHUNKS * 16 + (size_t)(w * 64) * 16;
         const unsigned char* gb = reinterpret_cast<const unsigned char*>(X16) + row0 * ld16 * 2;
 #pragma unroll
-        for (int u = 0; u < PASSES; ++u) {
-            const unsigned char* g = gb + (long long)u * RPP * ld16 * 2 + lane_off;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                             (__attribute__((address_space(3))) void*)(lbase + (size_t)u * 512 * 16), 16, 0, 0);
-        }
+        for (int u = 0; u < PASSES; ++u) lds_dma16(gb + (long long)u * Tile::RPP * ld16 * 2 + lane_off, lbase + (size_t)u * 512 * 16);
     };
     // both buffers are requested up front (a workgroup of a 1M-row search has one or two tiles: their latencies overlap);
     // from the third tile on a buffer is re-filled as soon as every wave has left it
@@ -999,10 +773,10 @@ __global__ __launch_bounds__(512, 1) void sample_max_kernel(const uint16_t* __re
         const int buf = it & 1;
         if (it > 0 && t + nx < n_tiles) dma(t + nx, buf ^ 1);
         if (active) {
-            int G = (fh ^ ((frow >> FS) & FM)) << 4;
+            int G = (fh ^ ((frow >> Tile::FS) & Tile::FM)) << 4;
             const unsigned char* lb = lds + (size_t)buf * TILE_CHUNKS * 16 + frow * CPR * 16;
-            // one quarter loop per number of live query tiles, the LDS-read / MFMA interleave spelled out (scan_filter_kernel,
-            // SCAN_OPT 32: with `if (second)` inside the K loop every k-step ended a basic block)
+            // one quarter loop per number of live query tiles, the LDS-read / MFMA interleave spelled out (as in
+            // scan_filter_kernel's quarter: with `if (second)` inside the K loop every k-step ended a basic block)
             auto quarters = [&](auto nj_tag) {
                 constexpr int NJ = decltype(nj_tag)::value;
 #pragma unroll 1
