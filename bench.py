@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """End-to-end recommendations/s on the BASELINE.json workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (one child process
@@ -20,6 +20,14 @@ for the global batch (512*N users), the per-shard lists (short, proven exact by 
 amdrec.sharded) are exchanged with one RCCL all-to-all, each rank merges and ranks its own 512
 users ("scaling": "weak").
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs: set-up, warm-up (with the per-kernel pre-pass), the timed steps, the dump
+of the last one if asked for, the line.  `--full` adds every figure and check that takes GPU or CPU time of its own,
+after the timed steps: the one-batch replay (`same_batch`), the strict fp32-MFMA engine (`strict_fp32`), the search
+B sweep (`search.sweep`), the latency by batch (`e2e_latency_by_batch`), the CPU baseline and the full-size parity
+check against the oracle (`cpu_baseline`, `parity_check`), the IVF recall against Flat and scan figures (`search`),
+and at N > 1 the unverified region (`config.no_verify`) and rank 0's per-stage times (`multi_gpu.stages_ms_rank0`).
+The --no-* switches drop single parts of a --full run.
 """
 import argparse
 import json
@@ -37,9 +45,12 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other figure and check (see the module docstring); "
+                         "off: the line carries the headline and what the warm-up and timed steps measured")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-users", type=int, default=192)
-    ap.add_argument("--sweep", action="store_true", help="(kept for old command lines: the latency sweep is in the line by default)")
+    ap.add_argument("--sweep", action="store_true", help="(kept for old command lines: the latency sweep is in every --full line)")
     ap.add_argument("--no-search-sweep", action="store_true",
                     help="skip the search-only B sweep that fills the line's `search.sweep` (< 1 s)")
     ap.add_argument("--corpus", choices=["random", "clustered"], default=None,
@@ -58,7 +69,7 @@ def parse_args(argv=None):
                          "`fp32` = the strict fp32-MFMA engine as the headline (profiles/r04_bench_kernel_stats_fp32.csv)")
     ap.add_argument("--user-batches", type=int, default=8,
                     help="distinct seeded user batches rotated through the timed loop (a serving benchmark never sees the "
-                         "same users twice in a row); the one-batch replay is reported beside it as `same_batch`")
+                         "same users twice in a row); --full reports the one-batch replay beside it as `same_batch`")
     ap.add_argument("--no-latency-sweep", action="store_true",
                     help="skip `e2e_latency_by_batch` (one recommend_device call at B = 1 / 8 / 64 / 512, N = 1 only)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -514,7 +525,7 @@ def main():
         index = FAISSIndex(DIM, index_type="Flat", device=device)
     index.add(shard)                                        # renormalises + stores (faiss_retrieval.py:97-127)
     flat_ref = None
-    if args.index == "ivf":
+    if args.index == "ivf" and args.full:
         flat_ref = FAISSIndex(DIM, index_type="Flat", device=device)     # for recall@500 vs Flat (stderr)
         flat_ref.add(shard)
     del shard
@@ -609,11 +620,15 @@ def main():
     if args.dump_outputs:
         # the last timed step's own result, copied out before any later region can reuse the workspaces behind it
         dumped = dump_outputs(out, args.dump_outputs, rank, limit=DUMP_LIMIT_BYTES // world)
-    # the same region replaying ONE batch (rounds 1-3 timed this): every step gathers the same 256 000 rows of the ad
-    # projection cache and re-scores the same corpus rows, next to a 256 MB Infinity Cache
-    dt_same, _, _, _, _ = timed_region(same)
-    same_batch = {"value": round(B_global * args.steps / dt_same, 1), "ms_per_step": round(dt_same / args.steps * 1000, 3),
-                  "note": "one user batch replayed every step (what rounds 1-3 reported as `value`)"}
+    # everything below that runs steps or other work of its own is --full only; a plain run goes on to its line
+    same_batch = None
+    if args.full:
+        # the same region replaying ONE batch (rounds 1-3 timed this): every step gathers the same 256 000 rows of the ad
+        # projection cache and re-scores the same corpus rows, next to a 256 MB Infinity Cache
+        dt_same, _, _, _, _ = timed_region(same)
+        same_batch = {"value": round(B_global * args.steps / dt_same, 1),
+                      "ms_per_step": round(dt_same / args.steps * 1000, 3),
+                      "note": "one user batch replayed every step (what rounds 1-3 reported as `value`)"}
     short_lists, no_verify, exchange, multi = None, None, None, None
     if world > 1:
         st = runner.short_list_stats()
@@ -623,7 +638,7 @@ def main():
                        "inexact_in_timed_steps": st["unproven_queries"] - stats0["unproven_queries"],
                        "batches_repeated_with_full_lists_in_timed_steps": st["repeated_batches"] - stats0["repeated_batches"],
                        "hit_rate": st["hit_rate"], "switched_off": st["switched_off"]}
-        if runner.list_k(STAGE1_K) < STAGE1_K:
+        if args.full and runner.list_k(STAGE1_K) < STAGE1_K:
             # the same steps without the per-step check; a number is only reported if the proof held for every one of them
             runner.inexact_count()
             rot = rotating(args.steps)
@@ -636,14 +651,16 @@ def main():
         # times from a few EXTRA steps with HIP events at the stage boundaries (outside every timed region: an event
         # pair idles the stream ~10 us), the slowest / fastest rank's wall time over the timed region, and what
         # torch.distributed says the world is.
-        n_diag = max(1, min(5, args.steps))
-        runner.timer = StageTimer(device)
-        rot = rotating(n_diag)
-        for i in range(n_diag):
-            rot(i)
-        stages = runner.timer.report()
-        runner.timer = None
-        barrier()
+        n_diag, stages = None, None
+        if args.full:
+            n_diag = max(1, min(5, args.steps))
+            runner.timer = StageTimer(device)
+            rot = rotating(n_diag)
+            for i in range(n_diag):
+                rot(i)
+            stages = runner.timer.report()
+            runner.timer = None
+            barrier()
         multi = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                  "step_ms_max_over_ranks": round(spread[1] / args.steps * 1000, 3),
                  "step_ms_min_over_ranks": round(spread[0] / args.steps * 1000, 3),
@@ -661,7 +678,7 @@ def main():
     # fp32 (engine f16x3) is transparent: args.steps timed steps (rotating batches) after its own warm-up, with its own
     # roofline block (the fp32 engine's dominant kernel against the 157.3 TF fp32-MFMA peak) and per-kernel table.
     strict = None
-    if not args.no_strict_fp32 and rk.gemm_engine != "fp32":
+    if args.full and not args.no_strict_fp32 and rk.gemm_engine != "fp32":
         eng0 = rk.gemm_engine
         rows_step = USERS_PER_GPU * STAGE1_K
         rk.gemm_engine = "fp32"
@@ -696,7 +713,8 @@ def main():
         sf = next((v for k, v in prof_all.items() if k.startswith("search_filter")), None)
         search = None
         if args.index == "ivf":
-            search = ivf_search_stats(index, flat_ref, tt, uc, un, prof_all, n_pre)
+            if args.full:
+                search = ivf_search_stats(index, flat_ref, tt, uc, un, prof_all, n_pre)
         elif sf:
             ms = sf["total_ms"] / sf["launches"]
             mixed = getattr(index, "_mixed", False)      # bf16 shadow corpus read by the filter pass
@@ -709,13 +727,13 @@ def main():
                       "note": ("filter = one pass over the bf16 corpus; B=512 queries per pass, intensity 512 FLOP/B vs "
                                "bf16 ridge 312: compute-side bound (vector issue + bf16 MFMA), see DESIGN.md section 6" if mixed else
                                "B=512 per corpus pass is fp32-FLOP bound (intensity 255 FLOP/B vs ridge 19.7)")}
-        if search is not None and not args.no_search_sweep and world == 1 and args.index == "flat":
+        if args.full and search is not None and not args.no_search_sweep and world == 1 and args.index == "flat":
             search["sweep"] = search_sweep(index, device)
         # one recommend_device call by batch size - before the CPU legs: ~15 s of idle GPU let the clocks drop, and a
         # 0.45 ms call measured right after them read 1.5 ms
-        latency = latency_sweep(rec, uc, un, device) if world == 1 and not args.no_latency_sweep else None
+        latency = latency_sweep(rec, uc, un, device) if args.full and world == 1 and not args.no_latency_sweep else None
         cpu, parity = None, None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             corpus_cpu = index._xb[:index._n].cpu().numpy()
             n_cpu = min(args.cpu_users, B_global)
             cpu, ref = cpu_baseline(tt_sd, rk_sd, dims, corpus_cpu, ad_table.cpu().numpy(), uc_np, un_np, n_cpu)
@@ -729,14 +747,14 @@ def main():
                       + ("operands scaled by powers of two and split into 2 fp16 planes, 3 fp16-MFMA products per MAC, fp32 "
                          "accumulate - an EMULATION of fp32: each operand keeps 22 significand bits (fp32: 24); error vs float64 "
                          "= 2-3x the fp32-MFMA engine's on the LOGITS and up to 5-6x its worst element mid-chain "
-                         "(profiles/r04_accuracy.json, tests/test_x3_gpu.py); the strict fp32-MFMA figure is `strict_fp32`); "
+                         "(profiles/r04_accuracy.json, tests/test_x3_gpu.py); the strict fp32-MFMA figure is --full's `strict_fp32`); "
                          if eng_step == "f16x3" else
                          ("3 bf16 planes, 6 bf16-MFMA products per MAC, fp32 accumulate; " if eng_step == "bf16x6" else
                           "fp32 MFMA; "))
                       + "search: bf16-MFMA prefilter, fp32 re-score, certified exact; everything else fp32 MFMA / fp32 VALU")
         line = {"metric": "end-to-end recs/sec (1M ads d=256, top-500->10)" if default_cfg else
                           f"end-to-end recs/sec ({n_ads} ads d=256, {args.index}, top-500->10)", "value": round(value, 1),
-                "unit": "recs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "unit": "recs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
                 "warmup_steps_run": n_warm + n_pre, "user_batches": NB, "same_batch": same_batch,
                 "ms_per_step": round(ms_step, 3),
                 "step_ms_median": round(step_ms[len(step_ms) // 2], 3),

@@ -109,3 +109,57 @@ def test_bench_runs_the_steps_asked_for_and_dumps_the_last_one(tmp_path):
         a = np.load(d / f"{name}.npy")
         assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), name
     assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+
+
+def test_full_is_off_by_default():
+    """A plain run is the headline run: every other figure and check waits for --full."""
+    import bench
+    assert bench.parse_args(["--gpus", "1"]).full is False
+    assert bench.parse_args(["--gpus", "1", "--full"]).full is True
+
+
+def _bench_line(args, **extra_env):
+    r = subprocess.run([sys.executable, BENCH, *args], env=_env(**extra_env), capture_output=True, text=True, timeout=880)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_plain_run_carries_the_headline_and_nothing_that_took_runs_of_its_own(gpus):
+    """No --full: the headline and what the warm-up and timed steps measured; the one-batch replay, the strict fp32
+    figure, the sweeps, the CPU legs and (N > 1) the unverified region and stage times are left out.  N = 2 runs both
+    ranks on one GPU (the rehearsal switch)."""
+    env = {"AMDREC_BENCH_REHEARSE": "1"} if gpus > 1 else {}
+    doc = _bench_line(["--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--ads", "200000"], **env)
+    assert doc["full"] is False and doc["n_gpus"] == gpus and doc["steps"] == 2 and doc["warmup_steps_run"] >= 20
+    assert doc["metric"].startswith("end-to-end recs/sec") and doc["unit"] == "recs/s" and doc["higher_is_better"] is True
+    assert doc["value"] > 0 and doc["ms_per_step"] > 0 and doc["dtype"].startswith("f32")
+    assert doc["kernels"] and doc["roofline"]["avg_launch_ms"] > 0
+    assert doc["same_batch"] is None and doc["strict_fp32"] is None
+    assert doc["cpu_baseline"] is None and doc["parity_check"] is None and "e2e_latency_by_batch" not in doc
+    if gpus == 1:
+        assert doc["search"]["filter_pass_ms"] > 0 and "sweep" not in doc["search"]
+    else:
+        assert doc["config"]["no_verify"] is None and doc["multi_gpu"]["stages_ms_rank0"] is None
+        assert doc["multi_gpu"]["verified"]["value"] > 0 and doc["config"]["shard_lists"]["inexact_in_timed_steps"] == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_full_run_adds_every_figure_and_check():
+    """--full at N = 1: the one-batch replay, the strict fp32-MFMA figure, the search sweep, the latency by batch and the
+    CPU baseline with the full-size parity check of the timed step against the oracle."""
+    doc = _bench_line(["--gpus", "1", "--steps", "2", "--warmup", "1", "--ads", "200000", "--full", "--cpu-users", "8"])
+    assert doc["full"] is True and doc["value"] > 0
+    assert doc["same_batch"]["value"] > 0
+    assert doc["strict_fp32"]["value"] > 0 and doc["strict_fp32"]["engine"] == "fp32"
+    assert [r["B"] for r in doc["search"]["sweep"]["rows"]] == [1, 8, 32, 128, 512]
+    assert [r["B"] for r in doc["e2e_latency_by_batch"]] == [1, 8, 64, 512]
+    assert doc["cpu_baseline"]["value"] > 0
+    par = doc["parity_check"]
+    assert par["users"] == 8 and par["topk_set_ok"] and par["top10_selection_exact"]
+    assert par["max_logit_err_over_bound"] <= 1.0

@@ -153,7 +153,8 @@ def test_short_list_merge_on_duplicated_ads_decides_score_ties_by_position(list_
 
 def test_bench_rehearsal_two_ranks_on_one_gpu_prints_n_gpus_2():
     """`python bench.py --gpus 2` with no WORLD_SIZE starts its two ranks itself; under the rehearsal
-    switch both run on cuda:0 over gloo.  One JSON line, n_gpus 2, the exchange described in config."""
+    switch both run on cuda:0 over gloo.  One JSON line, n_gpus 2, the exchange described in config; --full adds the
+    per-stage times and the one-batch replay."""
     import json
     import subprocess
     import sys
@@ -161,7 +162,7 @@ def test_bench_rehearsal_two_ranks_on_one_gpu_prints_n_gpus_2():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["AMDREC_BENCH_REHEARSE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--ads", "200000"], env=env, capture_output=True, text=True, timeout=900)
+                        "--ads", "200000", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
