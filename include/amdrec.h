@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define AMDREC_ABI_VERSION 10
+#define AMDREC_ABI_VERSION 11
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -149,6 +149,40 @@ int amdrec_ivf_assign(const float* x, int64_t rows, int64_t ld, int dim, const f
 int amdrec_ivf_kmeans_workspace(int64_t rows, int dim, int nlist, size_t* bytes /*host*/);
 int amdrec_ivf_kmeans_step(const float* x, int64_t rows, int64_t ld, int dim, float* centroids /*in/out*/, int nlist,
                            int64_t ld_centroids, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- retrieval: IVFPQ (faiss IndexIVFPQ(IndexFlatIP quantizer, d, nlist, m, 8): metric L2, by_residual; faiss_retrieval.py
+ * :56-63, searched at :150-155) - ABI v11 ---------------------------------------------------------------------------------
+ * The coarse level is the IVF index's (centroids, amdrec_ivf_assign, amdrec_ivf_coarse_keys + amdrec_ivf_select,
+ * amdrec_ivf_group).  m in {4, 8, 16, 32} sub-spaces of dsub = dim / m values (dim % m == 0, dsub % 4 == 0, dim <= 2048),
+ * 256 codewords each: codebooks [m][256][dsub] fp32.  x rows are L2-normalised, assign[r] their list, the residual is
+ * x[r] - centroids[assign[r]].
+ * amdrec_ivfpq_encode: codes[r][s] = arg min_j |residual_s - C_s[j]|^2 (computed as arg max <r_s, C_s[j]> - |C_s[j]|^2 / 2;
+ * ties -> lower j), uint8 [rows][m].
+ * amdrec_ivfpq_train_step: one L2 Lloyd iteration of every sub-space in place (encode + 64-bit fixed-point sums: order-
+ * independent, bit-reproducible); an empty codeword keeps its value.  rows <= 2^20. */
+int amdrec_ivfpq_encode(const float* x, int64_t rows, int64_t ld, int dim, const int64_t* assign, const float* centroids,
+                        int64_t ld_centroids, int nlist, const float* codebooks, int m, uint8_t* codes /*[rows][m]*/,
+                        void* stream);
+int amdrec_ivfpq_train_workspace(int64_t rows, int dim, int m, size_t* bytes /*host*/);
+int amdrec_ivfpq_train_step(const float* x, int64_t rows, int64_t ld, int dim, const int64_t* assign, const float* centroids,
+                            int64_t ld_centroids, int nlist, float* codebooks /*in/out*/, int m, void* workspace,
+                            size_t workspace_bytes, void* stream);
+/* Search: probes[nq][nprobe] (amdrec_ivf_select over amdrec_ivf_coarse_keys) ->
+ *   amdrec_ivfpq_tables: tables[q * nprobe + p][s][j] = |(queries[q] - centroids[probes[q][p]])_s - C_s[j]|^2 (fp32)
+ *   amdrec_ivf_group (qtile 32 or 64) -> amdrec_ivfpq_scan: pool_keys[q][pool_base[q][p] + i] = key(-sum_s table[code_s],
+ *       row_pos + pos_offset) over the rows of every probed list (codes stored list-contiguous [N][m], 16-byte aligned)
+ *   amdrec_ivf_select -> (score desc = distance asc, position asc) -> amdrec_ivfpq_distances: distances = -scores
+ *   (unfilled slots: +inf). */
+int amdrec_ivfpq_tables(const float* queries, int64_t nq, int64_t ld_queries, int dim, const int64_t* probes,
+                        int64_t ld_probes, int nprobe, const float* centroids, int64_t ld_centroids, int nlist,
+                        const float* codebooks, int m, float* tables /*[nq*nprobe][m][256]*/, void* stream);
+int amdrec_ivfpq_scan(const uint8_t* codes, int m, const int64_t* row_pos, const int64_t* list_off, int nlist,
+                      int64_t max_list_rows, const float* tables, int nprobe, const int64_t* group_off,
+                      const int64_t* qtile_prefix, int64_t qtile_bound, int qtile, const int64_t* pair_query,
+                      const int64_t* pair_probe, const int64_t* pool_base, int64_t npairs, uint64_t* pool_keys,
+                      int64_t pool_ld, int64_t pos_offset, void* stream);
+int amdrec_ivfpq_distances(const float* scores /*[nq][k]*/, int64_t nq, int k, float* distances /*[nq][k], may alias*/,
+                           void* stream);
 
 /* Cross-shard merge (absent in the single-device reference): for queries
  * [q0, q0+nq) merge n_lists per-shard top-k lists (scores/positions of list g start

@@ -11,6 +11,8 @@ device tensors and never synchronises with the host.
 Layout in HBM: corpus ``[capacity, dimension]`` float32 row-major, rows L2-normalised at
 ``add`` time, 1 KiB per row at d=256 (1.024 GB per 1M ads: the whole 10M corpus of
 BASELINE config 4 is 10.24 GB, 3.6 % of one MI355X's 288 GB); ids int64 ``[capacity]``.
+An IVFPQ index keeps no fp32 corpus: ``pq_m`` bytes of codes per row plus the row's list (amdrec.ivfpq), and its
+``search`` returns approximate squared L2 distances (ascending), faiss IndexIVFPQ's default metric.
 """
 from __future__ import annotations
 
@@ -26,6 +28,7 @@ import torch
 from . import _lib
 
 _MAGIC = b"AMDRECIX1"
+ADD_BATCH = 1 << 18            # IVFPQ add: rows normalised and encoded per batch (256 MB of fp32 at d = 256)
 INDEX_TYPES = ("Flat", "IVF", "IVFPQ", "HNSW")
 
 
@@ -69,7 +72,7 @@ class _Handle:
 
     @property
     def nprobe(self):
-        if self._o.index_type != "IVF":
+        if self._o.index_type not in ("IVF", "IVFPQ"):
             raise AttributeError("nprobe")
         return self._o.nprobe
 
@@ -80,11 +83,12 @@ class _Handle:
 
 class FAISSIndex:
     def __init__(self, dimension: int, index_type: str = "IVF", nlist: int = 100, nprobe: int = 10,
-                 use_gpu: bool = False, device=None, verbose: bool = False, prefilter: str = "bf16"):
+                 use_gpu: bool = False, device=None, verbose: bool = False, prefilter: str = "bf16", pq_m: int = 8):
         """``use_gpu`` is accepted for signature compatibility; the index always lives on the
         HIP device (``device`` or the current one) - there is no CPU engine.
         ``prefilter`` (Flat only): "bf16" keeps a bf16 copy of the corpus next to the fp32 one and searches with
-        amdrec_flat_search_mixed (bf16 MFMA filter, fp32 re-score, certified exact); "fp32" = amdrec_flat_search."""
+        amdrec_flat_search_mixed (bf16 MFMA filter, fp32 re-score, certified exact); "fp32" = amdrec_flat_search.
+        ``pq_m`` (IVFPQ only): sub-quantizers of 8 bits each, 4 / 8 / 16 / 32; 8 is the reference's value."""
         if prefilter not in ("bf16", "fp32"):
             raise ValueError("prefilter must be 'bf16' or 'fp32'")
         self.prefilter = prefilter
@@ -92,6 +96,7 @@ class FAISSIndex:
         self.index_type = index_type
         self.nlist = int(nlist)
         self.nprobe = int(nprobe)
+        self.pq_m = int(pq_m)
         self.use_gpu = use_gpu
         self.verbose = verbose
         self.device = torch.device(device if device is not None else "cuda")
@@ -101,11 +106,15 @@ class FAISSIndex:
     def _create_index(self):
         if self.index_type not in INDEX_TYPES:
             raise ValueError(f"Unknown index type: {self.index_type}")          # :73
-        if self.index_type in ("IVFPQ", "HNSW"):
+        if self.index_type == "HNSW":
             raise NotImplementedError(
-                f"{self.index_type} is outside the MI355X hot path (SURVEY.md §2 #12): use 'Flat' or 'IVF'")
+                f"{self.index_type} is outside the MI355X hot path (SURVEY.md §2 #12): use 'Flat', 'IVF' or 'IVFPQ'")
         if self.dimension % 4 or not (4 <= self.dimension <= 2048):
             raise ValueError("dimension must be a multiple of 4 in [4, 2048]")
+        if self.index_type == "IVFPQ":
+            from . import ivfpq
+            ivfpq.check_pq_m(self.dimension, self.pq_m)
+            ivfpq.check_nlist(self.nlist)
         _lib.load()
         self._xb = torch.empty((0, self.dimension), dtype=torch.float32, device=self.device)
         self._ids = torch.empty((0,), dtype=torch.int64, device=self.device)
@@ -118,6 +127,7 @@ class FAISSIndex:
         self._host_ids: Optional[list] = None   # only for non-integer ids
         self._trained = self.index_type == "Flat"
         self._ivf = None               # set by train() for IVF
+        self._pq = None                # set by train() for IVFPQ
         self.index = _Handle(self)
         self._log(f"Created {self.index_type} index with dimension {self.dimension}")
 
@@ -145,15 +155,19 @@ class FAISSIndex:
         return t
 
     def _reserve(self, n):
-        cap = self._xb.shape[0]
+        cap = self._ids.shape[0] if self.index_type == "IVFPQ" else self._xb.shape[0]
         if n <= cap:
             return
         new_cap = max(n, int(cap * 1.5), 1024)
-        xb = torch.empty((new_cap, self.dimension), dtype=torch.float32, device=self.device)
         ids = torch.empty((new_cap,), dtype=torch.int64, device=self.device)
         if self._n:
-            xb[:self._n].copy_(self._xb[:self._n])
             ids[:self._n].copy_(self._ids[:self._n])
+        if self.index_type == "IVFPQ":                # codes only: no fp32 corpus on the device
+            self._ids = ids
+            return
+        xb = torch.empty((new_cap, self.dimension), dtype=torch.float32, device=self.device)
+        if self._n:
+            xb[:self._n].copy_(self._xb[:self._n])
         self._xb, self._ids = xb, ids
         if self._mixed:
             xb16 = torch.empty((new_cap, self.dimension), dtype=torch.bfloat16, device=self.device)
@@ -172,13 +186,19 @@ class FAISSIndex:
 
     # -- reference API ----------------------------------------------------------------
     def train(self, embeddings):
-        """faiss_retrieval.py:83-95: trains the coarse quantizer of IVF; no-op for Flat."""
+        """faiss_retrieval.py:83-95: trains the coarse quantizer of IVF (and the product quantizer of IVFPQ); no-op for
+        Flat."""
         if self._trained:
             return
         t0 = time.time()
         self._log(f"Training index on {len(embeddings)} samples...")
-        from . import ivf
-        self._ivf = ivf.IVFState.train(self._to_device_f32(embeddings), self.nlist)
+        if self.index_type == "IVFPQ":
+            from . import ivfpq
+            self._pq = ivfpq.IVFPQState.train(self._to_device_f32(embeddings), self.nlist, self.pq_m)
+            self._ivf = self._pq.ivf
+        else:
+            from . import ivf
+            self._ivf = ivf.IVFState.train(self._to_device_f32(embeddings), self.nlist)
         self._trained = True
         self._log(f"Index trained in {time.time() - t0:.2f}s")
 
@@ -217,10 +237,17 @@ class FAISSIndex:
             raise ValueError(f"expected [n, {self.dimension}] embeddings, got {tuple(src.shape)}")
         m = src.shape[0]
         self._reserve(self._n + m)
-        x = self._xb[self._n:self._n + m]
-        x.copy_(src)                                                 # casts + moves to the device
-        self._normalize_(x)
-        self._shadow_rows(self._n, self._n + m)
+        if self.index_type == "IVFPQ":
+            # normalised and encoded batch by batch: only the codes stay.  Nothing is committed to the PQ state before the
+            # ids below are accepted (a rejected add must leave the index as it was)
+            pq_new = [self._pq.encode_rows(self._normalize_(
+                src[b:b + ADD_BATCH].to(device=self.device, dtype=torch.float32, copy=True).contiguous()))
+                for b in range(0, m, ADD_BATCH)]
+        else:
+            x = self._xb[self._n:self._n + m]
+            x.copy_(src)                                             # casts + moves to the device
+            self._normalize_(x)
+            self._shadow_rows(self._n, self._n + m)
         if ad_ids is None:                                           # :121-122
             new_ids = torch.arange(self._n, self._n + m, dtype=torch.int64, device=self.device)
             if self._host_ids is not None:
@@ -245,7 +272,9 @@ class FAISSIndex:
                 self._identity = False
                 new_ids = torch.full((m,), -1, dtype=torch.int64, device=self.device)
         self._ids[self._n:self._n + m].copy_(new_ids)                # :123
-        if self._ivf is not None:
+        if self._pq is not None:
+            self._pq.commit(pq_new)
+        elif self._ivf is not None:
             self._ivf.append(x, self._n)
         self._n += m
         self._log(f"Added embeddings in {time.time() - t0:.2f}s")
@@ -261,7 +290,8 @@ class FAISSIndex:
                       return_positions: bool = False, pos_offset: int = 0):
         """Device-to-device search, asynchronous on the current stream.
         -> (ids int64 [nq,k], scores float32 [nq,k]) on the device.  ``return_positions``: corpus
-        positions (+ ``pos_offset``, the shard's first global row) instead of ids, -1 = unfilled."""
+        positions (+ ``pos_offset``, the shard's first global row) instead of ids, -1 = unfilled.
+        IVFPQ: the scores are approximate squared L2 distances, ascending (+inf = unfilled)."""
         q = _lib.require_gpu(queries, "queries")
         if q.dim() != 2 or q.shape[1] != self.dimension:
             raise ValueError(f"expected [nq, {self.dimension}] queries, got {tuple(q.shape)}")
@@ -281,6 +311,8 @@ class FAISSIndex:
         if self.index_type == "IVF":
             self._ivf.search(self._xb, self._n, q, k, self.nprobe, scores, pos,
                              pos_offset=pos_offset if return_positions else 0)
+        elif self.index_type == "IVFPQ":                              # scores = squared L2 distances, ascending
+            self._pq.search(q, k, self.nprobe, scores, pos, pos_offset=pos_offset if return_positions else 0)
         elif self._mixed:
             flat_search_mixed(self._xb, self._xb16, self._maxnorm, self._n, q, k, scores, pos,
                               pos_offset=pos_offset if return_positions else 0)
@@ -291,7 +323,7 @@ class FAISSIndex:
             # id_map[-1] in the reference (:159) - reproduce that too
             if return_positions:
                 return pos, scores
-            if self._n and (k > self._n or self.index_type == "IVF"):   # only then can a slot be unfilled
+            if self._n and (k > self._n or self.index_type in ("IVF", "IVFPQ")):   # only then can a slot be unfilled
                 pos = torch.where(pos < 0, pos + self._n, pos)
             return pos, scores
         lib = _lib.load()
@@ -333,12 +365,18 @@ class FAISSIndex:
         reference's metadata fields (dimension, index_type, nlist, nprobe) - never pickle."""
         d = os.path.dirname(os.path.abspath(filepath))
         os.makedirs(d, exist_ok=True)
-        arrays = [("xb", self._xb[:self._n].cpu().numpy()), ("ids", self._ids[:self._n].cpu().numpy())]
-        if self._ivf is not None:
-            arrays += self._ivf.export_arrays()
+        arrays = [("ids", self._ids[:self._n].cpu().numpy())]
+        if self._pq is not None:                                     # codes, centroids, codebooks, assignment: no xb
+            arrays += self._pq.export_arrays()
+        else:
+            arrays.insert(0, ("xb", self._xb[:self._n].cpu().numpy()))
+            if self._ivf is not None:
+                arrays += self._ivf.export_arrays()
         header = {"dimension": self.dimension, "index_type": self.index_type, "nlist": self.nlist,
                   "nprobe": self.nprobe, "ntotal": self._n, "identity_ids": self._identity,
                   "arrays": [{"name": n, "dtype": str(a.dtype), "shape": list(a.shape)} for n, a in arrays]}
+        if self.index_type == "IVFPQ":
+            header["pq_m"] = self.pq_m
         if self._host_ids is not None:
             header["host_ids"] = [_encode_id(x) for x in self._host_ids]     # typed: ids round-trip as what they were
         hj = json.dumps(header).encode()
@@ -368,10 +406,12 @@ class FAISSIndex:
         self.index_type = header["index_type"]
         self.nlist = header["nlist"]
         self.nprobe = header["nprobe"]
+        self.pq_m = int(header.get("pq_m", self.pq_m))
         self._create_index()
         n = header["ntotal"]
         self._reserve(n)
-        self._xb[:n].copy_(torch.from_numpy(arrays["xb"].copy()))
+        if self.index_type != "IVFPQ":
+            self._xb[:n].copy_(torch.from_numpy(arrays["xb"].copy()))
         self._ids[:n].copy_(torch.from_numpy(arrays["ids"].copy()))
         self._n = n
         self._shadow_rows(0, n)
@@ -381,6 +421,11 @@ class FAISSIndex:
         if self.index_type == "IVF":
             from . import ivf
             self._ivf = ivf.IVFState.from_arrays(arrays, self.device)
+            self._trained = True
+        elif self.index_type == "IVFPQ":
+            from . import ivfpq
+            self._pq = ivfpq.IVFPQState.from_arrays(arrays, self.device)
+            self._ivf = self._pq.ivf
             self._trained = True
         self._log(f"Index loaded from {filepath}")
         self._log(f"Index size: {self._n}")
@@ -392,16 +437,21 @@ class FAISSIndex:
 
 
 def benchmark_faiss_index(dimension: int = 256, num_vectors: int = 1000000, num_queries: int = 100, k: int = 100,
-                          device="cuda", seed: int = 1234):
+                          device="cuda", seed: int = 1234, index_types=("Flat", "IVF")):
     """The reference's only benchmark (faiss_retrieval.py:372-436): random corpus, add + search timings per
-    index type.  The Flat and IVF arms are built here (IVFPQ / HNSW are outside the hot path); vectors and
+    index type.  ``index_types``: the arms to run, of Flat, IVF and IVFPQ (HNSW is outside the hot path); vectors and
     queries are drawn on the device (randn, as :390-391, seeded here)."""
+    configs = {"Flat": {}, "IVF": {"nlist": 100, "nprobe": 10}, "IVFPQ": {"nlist": 100, "nprobe": 10}}
+    for t in index_types:
+        if t not in configs:
+            raise ValueError(f"benchmark_faiss_index: unsupported index type {t!r}")
     g = torch.Generator(device=device)
     g.manual_seed(seed)
     vectors = torch.randn((num_vectors, dimension), generator=g, device=device)
     queries = torch.randn((num_queries, dimension), generator=g, device=device)
     results = {}
-    for index_type, config in (("Flat", {}), ("IVF", {"nlist": 100, "nprobe": 10})):
+    for index_type in index_types:
+        config = configs[index_type]
         idx = FAISSIndex(dimension, index_type=index_type, device=device, **config)
         torch.cuda.synchronize()
         t0 = time.time()

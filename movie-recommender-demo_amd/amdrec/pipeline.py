@@ -209,7 +209,7 @@ class AdRecommenderInference:
         if ids_are_positions:
             cand_ids = cand_pos
         elif idx._identity:
-            unfilled = idx._n and (stage1_k > idx._n or idx.index_type == "IVF")     # else every slot is filled
+            unfilled = idx._n and (stage1_k > idx._n or idx.index_type in ("IVF", "IVFPQ"))   # else every slot is filled
             # an unfilled slot (-1) reads id_map[-1] like the reference's list indexing (faiss_retrieval.py:159-160): one
             # launch (Python-style remainder: -1 -> n - 1, valid positions unchanged) instead of compare + add + where
             cand_ids = torch.remainder(cand_pos, idx._n) if unfilled else cand_pos
@@ -228,7 +228,8 @@ class AdRecommenderInference:
                          stage1_k: int = 500, check_indices: bool = False):
         """[B,6] / [B,13] device tensors -> dict of device tensors, no host synchronisation:
         ad_ids [B,top_k] int64, scores [3,B,top_k] float32 (sigmoid of the logits), candidate_ids
-        [B,stage1_k], candidate_scores [B,stage1_k], logits [3, B*stage1_k]."""
+        [B,stage1_k], candidate_scores [B,stage1_k], logits [3, B*stage1_k].  candidate_scores are the index's own
+        scores: inner products (descending) for Flat / IVF, approximate squared L2 distances (ascending) for IVFPQ."""
         uc = _lib.require_gpu(user_categorical, "user_categorical")
         un = _lib.require_gpu(user_numerical, "user_numerical")
         cand_pos, cand_scores = self._stage1(uc, un, stage1_k, check_indices)
@@ -427,7 +428,8 @@ class GraphedRecommender:
         idx = rec.faiss_index
         self._pinned = (rec.two_tower_model.user_tower._packed, rec.transformer_ranker._packed, idx._xb, idx._ids,
                         idx._xb16, idx._maxnorm, rec.ad_features, rec.transformer_ranker._ad_cache, getattr(idx, "_ivf", None) and idx._ivf._lists,
-                        getattr(idx, "_ivf", None) and getattr(idx._ivf, "_shadow", None))
+                        getattr(idx, "_ivf", None) and getattr(idx._ivf, "_shadow", None),
+                        getattr(idx, "_pq", None) and (idx._pq._lists, idx._pq.codebooks))
 
     @torch.no_grad()
     def __call__(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor):

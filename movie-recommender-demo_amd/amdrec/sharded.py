@@ -218,6 +218,10 @@ class ShardedRecommender:
         "all_gather" - every rank receives every list (world x as much); "auto" picks all_to_all when it applies.
         ``shard_k``: entries per shard list - "auto" = ``short_list_k(stage1_k, world)``, an int, or None = stage1_k
         (full lists, no proof needed)."""
+        if getattr(getattr(rec, "faiss_index", None), "index_type", None) == "IVFPQ":
+            # the merge orders scores descending (inner products); IVFPQ returns L2 distances, and a sharded IVFPQ index
+            # would need one set of codebooks shared by all ranks
+            raise NotImplementedError("ShardedRecommender does not support an IVFPQ index: use 'Flat' or 'IVF'")
         if exchange not in ("auto", "all_to_all", "all_gather"):
             raise ValueError("exchange must be 'auto', 'all_to_all' or 'all_gather'")
         if not (shard_k is None or shard_k == "auto" or (isinstance(shard_k, int) and shard_k >= 1)):
