@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define AMDREC_ABI_VERSION 11
+#define AMDREC_ABI_VERSION 12
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -297,6 +297,14 @@ typedef struct {
     const void* stream_cs;
     int64_t chunks_cs;
     int64_t cs_max_rows;
+    /* != 0 (ABI v12): layer 1's attention block is folded into the feature projection.  At seq_len 1 everything of
+     * encoder layer 1 before its first LayerNorm is linear in the projection output x0:  z = x0 + W_ov x0 + b_ov =
+     * W_p' f + b_p'  with  W_p' = (I + W_ov) W_p,  b_p' = (I + W_ov) b_p + b_ov  (formed on the host in float64).  Then
+     * w_proj / w_proj_user / w_proj_ad / b_proj (and so ad_proj_cache) hold the folded projection, the chain starts with a
+     * LayerNorm-only phase (LN1 of layer 1: no weights, no stream chunks), layer 1's W_ov fragments are in neither stream
+     * and its b_ov is not in the parameter blob.  Only this engine runs such parameters: requires n_layers >= 1 and
+     * min_rows == 1 (every pass takes the engine); layers[0] keeps the unfolded W_ov / b_ov (amdrec_ranker_x3_prefix). */
+    int64_t fold_attn1;
 } amdrec_x3_weights;
 
 typedef struct {
@@ -354,7 +362,9 @@ int amdrec_ranker_forward(const amdrec_ranker_params* p /*host*/, const int64_t*
  * layer {attention + LN1, FFN + LN2}, then the cross layers, then the heads; n_phases < 0 = all) on dense projected
  * rows X [rows][ldx] and return the rows after the last executed phase in x_out [rows][ld_out] (may be NULL) and, when
  * the heads ran, the logits.  workspace: >= ceil(rows / 128) * 128 * 1024 bytes.  Lets the parity tests localise an
- * error to one phase; amdrec_ranker_forward uses the same kernel for whole passes. */
+ * error to one phase; amdrec_ranker_forward uses the same kernel for whole passes.  X is always the UNFOLDED projection
+ * x0: with x3.fold_attn1 the entry first forms z = x0 + W_ov x0 + b_ov (fp32 fma chains, from layers[0].w_o / b_o) into
+ * the workspace and runs the folded chain on it, whose first phase (LN1 alone) then stands for "attention + LN1". */
 int amdrec_ranker_x3_prefix(const amdrec_ranker_params* p /*host*/, const float* X, int64_t ldx, int64_t rows,
                             int n_phases, float* x_out, int64_t ld_out, float* logits, int64_t ld_logits,
                             void* workspace, size_t workspace_bytes, void* stream);

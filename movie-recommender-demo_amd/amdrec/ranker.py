@@ -81,6 +81,11 @@ class TransformerRanker(nn.Module):
         # W_ov = W_o W_v pre-multiplied on the host (exact algebra at seq_len 1; set False to run the two
         # GEMMs in the reference's order)
         self.fuse_attention = True
+        # encoder layer 1's attention block folded into the feature projection (exact algebra at seq_len 1: x0 + W_ov x0 +
+        # b_ov is linear in the projection's input; weights.folded_projection).  Needs fuse_attention and applies only
+        # where every pass runs the row-owner kernel (gemm_engine "f16x3" on its architecture, x3_min_rows = 1): one
+        # 256 x 256 GEMM less per candidate row.  The fp32 / bf16x6 engines keep the unfolded chain.
+        self.fold_first_attention = True
         # engine of the big passes (> 8192 rows), all fp32 in / fp32 out with fp32-level error:
         #  "f16x3"  (default) the row-owner kernel (csrc/rowowner.hpp): operands split into two fp16 planes, three
         #           fp16-MFMA products per MAC, everything after the projection in ONE kernel, activations in registers
@@ -170,8 +175,10 @@ class TransformerRanker(nn.Module):
     def _pack(self, device):
         if self.gemm_engine not in self.ENGINES:
             raise ValueError(f"gemm_engine must be one of {self.ENGINES}")
-        key = (str(device), self.fuse_attention, self.gemm_engine, int(self.x3_min_rows), int(self.x3_variant),
-               int(self.x3_cs_max_rows),
+        # (the key - and with it the ad-projection cache, which is only served for the key it was built under - covers the
+        # fold: an engine switch repacks and rebuilds the cache in the other projection form)
+        key = (str(device), self.fuse_attention, bool(self.fold_first_attention), self.gemm_engine, int(self.x3_min_rows),
+               int(self.x3_variant), int(self.x3_cs_max_rows),
                _lib.tensor_versions(self))
         if self._packed is None or self._packed[0] != key:
             sd = self.state_dict()
@@ -187,7 +194,8 @@ class TransformerRanker(nn.Module):
                                                       x6=self.gemm_engine == "bf16x6" or
                                                       (self.gemm_engine == "f16x3" and not x3),
                                                       x3=x3, x3_min_rows=self.x3_min_rows, x3_variant=self.x3_variant,
-                                                      x3_cs_max_rows=self.x3_cs_max_rows)
+                                                      x3_cs_max_rows=self.x3_cs_max_rows,
+                                                      fold_first_attention=bool(self.fold_first_attention))
             self._packed = (key, params, keep, tasks)
         return self._packed[1], self._packed[3]
 

@@ -35,7 +35,7 @@ class X3Weights(C.Structure):
                 ("sw_ov", C.c_float * MAX_LAYERS), ("sw_1", C.c_float * MAX_LAYERS), ("sw_2", C.c_float * MAX_LAYERS),
                 ("hn", C.c_float * MAX_LAYERS), ("hb", C.c_float * MAX_LAYERS), ("sw_cross", C.c_float * MAX_LAYERS),
                 ("sw_h1", C.c_float), ("sw_h2", C.c_float), ("hn_head", C.c_float), ("hb_head", C.c_float),
-                ("stream_cs", _FP), ("chunks_cs", C.c_int64), ("cs_max_rows", C.c_int64)]
+                ("stream_cs", _FP), ("chunks_cs", C.c_int64), ("cs_max_rows", C.c_int64), ("fold_attn1", C.c_int64)]
 
 
 class RankerParams(C.Structure):
@@ -269,10 +269,12 @@ def x3c_stream_heads(f1, f2s, tiles_per_task):
     return np.stack(out)
 
 
-def pack_x3_stream(mats: Dict, variant: int = 32) -> Dict:
+def pack_x3_stream(mats: Dict, variant: int = 32, fold_first: bool = False) -> Dict:
     """mats: float64 matrices of the chain {"ov": [L x [256][256]], "w1": [L x [d_ff][256]], "b1": [L x [d_ff]], "w2":
     [L x [256][d_ff]], "cross": [C x [256][256] (already [out][in])], "h1": [T*h1][256], "hb1": [T*h1], "h2": [T x
-    [64][h1]]} -> {"stream": uint16 [n_frag][64][8], "chunks", scales and hidden bounds} for amdrec_x3_weights."""
+    [64][h1]]} -> {"stream": uint16 [n_frag][64][8], "chunks", scales and hidden bounds} for amdrec_x3_weights.
+    ``fold_first``: layer 1's attention block is folded into the projection (amdrec_x3_weights.fold_attn1): its W_ov is
+    not packed (mats["ov"][0] is not read; its scale reads 1.0)."""
     assert variant in (16, 32, "16cs")                  # "16cs": the 16-row fragments in the column-split kernel's order
     frags, s_gemm, s_ffn, s_heads = {32: (x3_frags, x3_stream_gemm256, x3_stream_ffn, x3_stream_heads),
                                      16: (x3b_frags, x3b_stream_gemm256, x3b_stream_ffn, x3b_stream_heads),
@@ -281,8 +283,10 @@ def pack_x3_stream(mats: Dict, variant: int = 32) -> Dict:
     parts = []
     sc = {"sw_ov": [], "sw_1": [], "sw_2": [], "hn": [], "hb": [], "sw_cross": []}
     for l in range(len(mats["ov"])):
-        s_ov = x3_pow2_scale(np.abs(mats["ov"][l]).max())
-        parts.append(s_gemm(frags(mats["ov"][l], s_ov)))
+        s_ov = 1.0
+        if not (fold_first and l == 0):
+            s_ov = x3_pow2_scale(np.abs(mats["ov"][l]).max())
+            parts.append(s_gemm(frags(mats["ov"][l], s_ov)))
         s1, s2 = x3_pow2_scale(np.abs(mats["w1"][l]).max()), x3_pow2_scale(np.abs(mats["w2"][l]).max())
         parts.append(s_ffn(frags(mats["w1"][l], s1), frags(mats["w2"][l], s2)))
         sc["sw_ov"].append(s_ov); sc["sw_1"].append(s1); sc["sw_2"].append(s2)
@@ -308,13 +312,14 @@ def pack_x3_stream(mats: Dict, variant: int = 32) -> Dict:
 X3_PARAM_FLOATS = 11264     # LDS parameter area of the kernel (csrc/rowowner.hpp PARAM_FLOATS)
 
 
-def pack_x3_params(layers: List[Dict], cross_b: List, head_b1, heads: List[Dict]) -> np.ndarray:
+def pack_x3_params(layers: List[Dict], cross_b: List, head_b1, heads: List[Dict], fold_first: bool = False) -> np.ndarray:
     """The parameter blob of the row-owner kernel (layout: csrc/ranker_x3.hip x3_param_floats): per encoder layer
     [b_ov | gamma1 | beta1 | b_1 | b_2 | gamma2 | beta2], per cross layer its bias, heads [stacked b_1] then per task
-    [b_2 (64) | w_3 (64) | b_3 padded to 4]; float32, zero-padded to a multiple of 1024."""
+    [b_2 (64) | w_3 (64) | b_3 padded to 4]; float32, zero-padded to a multiple of 1024.  ``fold_first``: layer 1's b_ov
+    is in the folded projection bias and left out."""
     parts = []
-    for L in layers:
-        parts += [L["b_ov"], L["g1"], L["be1"], L["b1"], L["b2"], L["g2"], L["be2"]]
+    for i, L in enumerate(layers):
+        parts += ([] if fold_first and i == 0 else [L["b_ov"]]) + [L["g1"], L["be1"], L["b1"], L["b2"], L["g2"], L["be2"]]
     parts += list(cross_b)
     parts.append(head_b1)
     for h in heads:
@@ -440,15 +445,31 @@ def x3_eligible(sd: Dict, fuse_attention: bool) -> bool:
     return x3_ineligible_reason(sd, fuse_attention) is None
 
 
+def folded_projection(sd: Dict):
+    """float64 (W_p', b_p') of the feature projection with encoder layer 1's attention block folded in.  At seq_len 1
+    everything of layer 1 before its first LayerNorm is linear in the projection output x0 = W_p f + b_p (b_p incl.
+    pos[0]): z = x0 + W_ov x0 + b_ov = (I + W_ov) W_p f + (I + W_ov) b_p + b_ov, W_ov = W_o W_v, b_ov = W_o b_v + b_o."""
+    wp = _np64(sd["feature_projection.weight"])
+    bp = _np64(sd["feature_projection.bias"]) + _np64(sd["positional_encoding"])[0, 0]
+    pre = "transformer_layers.0.self_attention"
+    wv, bv = _np64(sd[f"{pre}.W_v.weight"]), _np64(sd[f"{pre}.W_v.bias"])
+    wo, bo = _np64(sd[f"{pre}.W_o.weight"]), _np64(sd[f"{pre}.W_o.bias"])
+    wov = wo @ wv
+    return wp + wov @ wp, bp + wov @ bp + (wo @ bv + bo)
+
+
 def pack_ranker(sd: Dict, user_names: List[str], ad_names: List[str], n_num: int, device, ln_eps=1e-5,
                 fuse_attention: bool = True, x6: bool = True, x3: bool = False, x3_min_rows: int = 0,
-                x3_variant: int = 32, x3_cs_max_rows: int = 0):
+                x3_variant: int = 32, x3_cs_max_rows: int = 0, fold_first_attention: bool = False):
     """state_dict-like of the reference TransformerRanker -> (RankerParams, Packed, task names).
     ``fuse_attention``: pre-multiply W_ov = W_o W_v, b_ov = W_o b_v + b_o in float64 (the seq-len-1
     attention is exactly W_o(W_v x + b_v) + b_o, transformer_ranker.py:59-88 with :358), so each
     encoder layer's attention block is one GEMM instead of two.
     ``x6``: also upload the bf16 split planes of the big weight matrices (W_ov / W_o, fc1, fc2, cross, stacked head
-    layer 1) so that passes of more than 8192 rows run on the error-compensated bf16-MFMA GEMM."""
+    layer 1) so that passes of more than 8192 rows run on the error-compensated bf16-MFMA GEMM.
+    ``fold_first_attention``: when every pass runs the row-owner engine (x3 packed, x3_min_rows == 1, at least one
+    encoder layer), pack the projection as ``folded_projection`` (rounded once to fp32) and the engine's chain without
+    layer 1's W_ov / b_ov (amdrec_x3_weights.fold_attn1); otherwise it has no effect."""
     pk = Packed(device)
     tables = [sd[f"user_embeddings.{n}.weight"] for n in user_names] + \
              [sd[f"ad_embeddings.{n}.weight"] for n in ad_names]
@@ -459,6 +480,12 @@ def pack_ranker(sd: Dict, user_names: List[str], ad_names: List[str], n_num: int
     p.n_user_feat, p.n_ad_feat, p.emb_dim, p.n_num = len(user_names), len(ad_names), emb_dim, n_num
     p.tables, p.table_off, p.cards, _ = pack_tables(pk, tables, emb_dim)
     wproj = _np64(sd["feature_projection.weight"])
+    pos0 = _np64(sd["positional_encoding"])[0, 0]                  # only row 0 is ever read (:361)
+    bproj = _np64(sd["feature_projection.bias"]) + pos0
+    fold = bool(fold_first_attention and x3 and int(x3_min_rows) == 1 and x3_eligible(sd, fuse_attention)
+                and "transformer_layers.0.norm1.weight" in sd)
+    if fold:
+        wproj, bproj = folded_projection(sd)
     d_model = wproj.shape[0]
     assert wproj.shape[1] == len(tables) * emb_dim + n_num
     p.d_model = d_model
@@ -471,8 +498,7 @@ def pack_ranker(sd: Dict, user_names: List[str], ad_names: List[str], n_num: int
         p.w_proj_user = pk.ptr(w)
         w, p.ldw_proj_ad = _pad_k(wproj[:, nu:nu + na])
         p.w_proj_ad = pk.ptr(w)
-    pos0 = _np64(sd["positional_encoding"])[0, 0]                  # only row 0 is ever read (:361)
-    p.b_proj = pk.ptr((_np64(sd["feature_projection.bias"]) + pos0).astype(np.float32))
+    p.b_proj = pk.ptr(bproj.astype(np.float32))
     l = 0
     while f"transformer_layers.{l}.norm1.weight" in sd:
         if l >= MAX_LAYERS:
@@ -550,8 +576,9 @@ def pack_ranker(sd: Dict, user_names: List[str], ad_names: List[str], n_num: int
         mats["h1"], mats["hb1"] = f32(w1), f32(b1)
         for t in tasks:
             mats["h2"].append(f32(_np64(sd[f"prediction_heads.{t}.3.weight"])))
-        x = pack_x3_stream(mats, x3_variant)
+        x = pack_x3_stream(mats, x3_variant, fold_first=fold)
         p.x3.variant = x3_variant
+        p.x3.fold_attn1 = int(fold)
         lay = []
         for li in range(p.n_layers):
             pre = f"transformer_layers.{li}"
@@ -562,7 +589,7 @@ def pack_ranker(sd: Dict, user_names: List[str], ad_names: List[str], n_num: int
                         "g2": _np64(sd[f"{pre}.norm2.weight"]), "be2": _np64(sd[f"{pre}.norm2.bias"])})
         blob = pack_x3_params(lay, [_np64(sd[f"feature_interaction.cross_biases.{ci}"]) for ci in range(p.n_cross)], b1,
                               [{"b2": _np64(sd[f"prediction_heads.{t}.3.bias"]), "w3": _np64(sd[f"prediction_heads.{t}.6.weight"]),
-                                "b3": _np64(sd[f"prediction_heads.{t}.6.bias"])} for t in tasks])
+                                "b3": _np64(sd[f"prediction_heads.{t}.6.bias"])} for t in tasks], fold_first=fold)
         assert len(blob) <= X3_PARAM_FLOATS
         p.x3.params = pk.ptr(blob)
         p.x3.n_params = len(blob)
@@ -570,7 +597,7 @@ def pack_ranker(sd: Dict, user_names: List[str], ad_names: List[str], n_num: int
         p.x3.chunks = x["chunks"]
         p.x3.min_rows = int(x3_min_rows)
         if x3_variant == 16 and x3_cs_max_rows >= 0 and (p.n_layers == 0 or p.d_ff % 128 == 0) and p.head_h1 % 128 == 0:
-            xc = pack_x3_stream(mats, "16cs")               # same planes and scales, the column-split kernel's chunk order
+            xc = pack_x3_stream(mats, "16cs", fold_first=fold)   # same planes and scales, the column-split kernel's chunk order
             assert all(xc[k] == x[k] for k in ("sw_ov", "sw_1", "sw_2", "sw_cross", "sw_h1", "sw_h2"))
             p.x3.stream_cs = pk.ptr(xc["stream"].view(np.int16))
             p.x3.chunks_cs = xc["chunks"]

@@ -608,6 +608,7 @@ extern "C" int amdrec_tower_forward(const amdrec_tower_params* p, const int64_t*
 // ============================== ranker ==============================================
 namespace amdrec {   // ranker_x3.hip: the fp16x3 row-owner engine (everything after the feature projection in one kernel)
 bool ranker_x3_wanted(const amdrec_ranker_params* p, long long rows);
+bool ranker_x3_folded(const amdrec_ranker_params* p);
 int ranker_x3_run(const amdrec_ranker_params* p, const float* X, long long ldx, const float* U, const long long* rowmap,
                   long long row_base, int rowdiv, long long n_cache, long long rows, float* scratch, float* logits,
                   long long ld_logits, hipStream_t st);
@@ -821,6 +822,10 @@ extern "C" int amdrec_ranker_forward(const amdrec_ranker_params* p, const int64_
         // fp16x3 row-owner engine: the rest of the chain is one kernel; with the candidate-side cache it also does the
         // gather (x0 = cache row + user half).  Its x0 scratch is the X0 region (sized in whole 128-row workgroups).
         const bool use_x3 = ranker_x3_wanted(p, m);
+        // the folded projection (x3.fold_attn1) already contains layer 1's attention block: only the engine's chain, which
+        // starts with LN1 alone, may follow it
+        REQUIRE(use_x3 || !ranker_x3_folded(p), "x3.fold_attn1 is set but a pass of %lld rows would not run the row-owner "
+                                                "engine (the fold needs n_layers >= 1 and x3.min_rows == 1)", m);
         if (use_x3 && hoist && p->ad_proj_cache) {
             int rc3 = ranker_x3_run(p, nullptr, 0, (const float*)U, (const long long*)ad_rowmap, r0, (int)user_rowdiv,
                                     (long long)(n_ad_rows > 0 ? n_ad_rows : 1), m, X0, out_logits + r0, (long long)ld_logits, st);

@@ -10,9 +10,12 @@ using namespace amdrec;
 
 // Parameter blob layout (floats; amdrec/weights.py pack_x3_params writes exactly this): per encoder layer
 // [b_ov 256 | gamma1 256 | beta1 256 | b_1 d_ff | b_2 256 | gamma2 256 | beta2 256], per cross layer [bias 256], heads
-// [b_1 n_tasks*h1] then per task [b_2 64 | w_3 64 | b_3 4]; padded to a multiple of 1024.
+// [b_1 n_tasks*h1] then per task [b_2 64 | w_3 64 | b_3 4]; padded to a multiple of 1024.  With fold_attn1 layer 1's b_ov
+// is absent (the folded projection bias carries it): that layer's block starts at gamma1.
+static bool x3_folded(const amdrec_ranker_params* p) { return p->x3.fold_attn1 != 0; }
 static long long x3_param_floats(const amdrec_ranker_params* p) {
-    const long long n = (long long)p->n_layers * (6 * 256 + p->d_ff) + 256ll * p->n_cross + (long long)p->n_tasks * (p->head_h1 + 132);
+    const long long n = (long long)p->n_layers * (6 * 256 + p->d_ff) + 256ll * p->n_cross + (long long)p->n_tasks * (p->head_h1 + 132) -
+                        (x3_folded(p) ? 256 : 0);
     return (n + 1023) / 1024 * 1024;
 }
 
@@ -26,6 +29,7 @@ static bool x3_eligible(const amdrec_ranker_params* p) {
     if (2 * p->n_layers + p->n_cross + 1 > x3::MAX_PHASES || p->n_tasks > 4) return false;
     for (int l = 0; l < p->n_layers; ++l)
         if (p->layers[l].w_v != nullptr) return false;              // needs the pre-multiplied W_ov form
+    if (x3_folded(p) && (p->n_layers < 1 || p->x3.min_rows != 1)) return false;   // see amdrec_x3_weights.fold_attn1
     return true;
 }
 
@@ -39,11 +43,17 @@ static bool x3c_available(const amdrec_ranker_params* p) {
 static int x3_build(const amdrec_ranker_params* p, int n_phases, x3::Program& G, bool cs = false) {
     memset(&G, 0, sizeof(G));
     int n = 0, o = 0;                                               // o: running offset into the parameter blob (floats)
+    const bool fold = x3_folded(p);
     for (int l = 0; l < p->n_layers; ++l) {
         x3::Phase& A = G.ph[n++];
-        A.type = x3::PH_ATTN_LN; A.b1 = o; A.gamma = o + 256; A.beta = o + 512; A.sw1 = p->x3.sw_ov[l];
-        A.sw2 = 1.f; A.ln_eps = p->ln_eps;
-        o += 768;
+        if (l == 0 && fold) {                                       // the input rows are z = x0 + W_ov x0 + b_ov: LN1 alone
+            A.type = x3::PH_LN; A.gamma = o; A.beta = o + 256; A.sw1 = 1.f; A.sw2 = 1.f; A.ln_eps = p->ln_eps;
+            o += 512;
+        } else {
+            A.type = x3::PH_ATTN_LN; A.b1 = o; A.gamma = o + 256; A.beta = o + 512; A.sw1 = p->x3.sw_ov[l];
+            A.sw2 = 1.f; A.ln_eps = p->ln_eps;
+            o += 768;
+        }
         x3::Phase& F = G.ph[n++];
         F.type = x3::PH_FFN_LN; F.n_steps = p->d_ff / 32; F.b1 = o; F.b2 = o + p->d_ff; F.gamma = o + p->d_ff + 256;
         F.beta = o + p->d_ff + 512;
@@ -70,7 +80,7 @@ static int x3_build(const amdrec_ranker_params* p, int n_phases, x3::Program& G,
     const long long hidden_tiles = (long long)p->n_tasks * (p->head_h1 / 32);
     const long long heads = cs ? hidden_tiles * 3 : hidden_tiles * 40 / 16;
     REQUIRE(cs || hidden_tiles * 40 % 16 == 0, "x3: head stream is not a whole number of chunks");
-    const long long total = p->n_layers * per_layer + 16ll * p->n_cross + heads;
+    const long long total = p->n_layers * per_layer - (fold ? 16 : 0) + 16ll * p->n_cross + heads;   // fold: no layer-1 W_ov
     const long long have = cs ? p->x3.chunks_cs : p->x3.chunks;
     REQUIRE(total == have, "x3: stream length %lld chunks does not match the architecture (%lld)", have, total);
     G.n_phases = n_phases < 0 || n_phases > n ? n : n_phases;
@@ -80,6 +90,18 @@ static int x3_build(const amdrec_ranker_params* p, int n_phases, x3::Program& G,
 }
 
 constexpr long long X3B4_MAX_ROWS = 256ll * 64;      // one 64-row workgroup per CU
+
+// weight elements a row is multiplied with in the program's phases (the LayerNorm-only phase has none)
+static double x3_weight_elements(const x3::Program& G) {
+    double w = 0;
+    for (int i = 0; i < G.n_phases; ++i) {
+        const x3::Phase& P = G.ph[i];
+        if (P.type == x3::PH_ATTN_LN || P.type == x3::PH_CROSS) w += 256.0 * 256.0;
+        else if (P.type == x3::PH_FFN_LN) w += 2.0 * 256.0 * 32.0 * P.n_steps;
+        else if (P.type == x3::PH_HEADS) w += (double)P.n_tasks * (256.0 * 32.0 * P.n_steps + 64.0 * 32.0 * P.n_steps + 64.0);
+    }
+    return w;
+}
 
 static size_t x3_scratch_bytes(long long rows) {
     return (size_t)((rows + x3::ROWS_PER_WG - 1) / x3::ROWS_PER_WG) * x3::ROWS_PER_WG * 256 * 4;
@@ -104,14 +126,7 @@ static int x3_launch(const x3::Program& G, const x3::Input& in, long long rows, 
                                         hipFuncAttributeMaxDynamicSharedMemorySize, x3c::LDS_BYTES));
             attr_cs.mark();
         }
-        double w = 0;
-        for (int i = 0; i < G.n_phases; ++i) {
-            const x3::Phase& P = G.ph[i];
-            if (P.type == x3::PH_ATTN_LN || P.type == x3::PH_CROSS) w += 256.0 * 256.0;
-            else if (P.type == x3::PH_FFN_LN) w += 2.0 * 256.0 * 32.0 * P.n_steps;
-            else w += (double)P.n_tasks * (256.0 * 32.0 * P.n_steps + 64.0 * 32.0 * P.n_steps + 64.0);
-        }
-        ProfScope prof("ranker_colsplit16_x3", 2.0 * (double)rows * w, (double)rows * (1024.0 + 12.0), st);
+        ProfScope prof("ranker_colsplit16_x3", 2.0 * (double)rows * x3_weight_elements(G), (double)rows * (1024.0 + 12.0), st);
         const int n_pre = x3c::PREFETCH_WGS;           // (A/B against 0: profiles/r03_x3c_prefetch_ab.log)
         const int n_row_wgs = (int)((rows + x3c::ROWS_PER_WG - 1) / x3c::ROWS_PER_WG);
         hipLaunchKernelGGL(x3c::ranker_x3c_kernel, dim3((unsigned)(n_row_wgs + (n_pre > 0 ? n_pre : 0))), dim3(64 * x3c::WAVES),
@@ -127,13 +142,7 @@ static int x3_launch(const x3::Program& G, const x3::Input& in, long long rows, 
     const unsigned grid = (unsigned)((rows + rows_wg - 1) / rows_wg);
     {
         // algorithmic FLOPs: 2 * rows * sum over the phases' weight elements (bench.py prices them against bf16 MFMA / 3)
-        double w = 0;
-        for (int i = 0; i < G.n_phases; ++i) {
-            const x3::Phase& P = G.ph[i];
-            if (P.type == x3::PH_ATTN_LN || P.type == x3::PH_CROSS) w += 256.0 * 256.0;
-            else if (P.type == x3::PH_FFN_LN) w += 2.0 * 256.0 * 32.0 * P.n_steps;
-            else w += (double)P.n_tasks * (256.0 * 32.0 * P.n_steps + 64.0 * 32.0 * P.n_steps + 64.0);
-        }
+        const double w = x3_weight_elements(G);
         ProfScope prof(small ? "ranker_rowowner16_64_x3" : (variant == 16 ? "ranker_rowowner16_128_x3" : "ranker_rowowner_128_x3"),
                        2.0 * (double)rows * w, (double)rows * (1024.0 + 12.0), st);
         if (small)
@@ -156,6 +165,7 @@ bool ranker_x3_wanted(const amdrec_ranker_params* p, long long rows) {
     const long long min_rows = p->x3.min_rows > 0 ? p->x3.min_rows : 8193;
     return rows >= min_rows && x3_eligible(p);
 }
+bool ranker_x3_folded(const amdrec_ranker_params* p) { return x3_folded(p); }
 size_t ranker_x3_scratch_bytes(long long rows) { return x3_scratch_bytes(rows); }
 int ranker_x3_run(const amdrec_ranker_params* p, const float* X, long long ldx, const float* U, const long long* rowmap,
                   long long row_base, int rowdiv, long long n_cache, long long rows, float* scratch, float* logits,
@@ -177,6 +187,21 @@ int ranker_x3_run(const amdrec_ranker_params* p, const float* X, long long ldx, 
 }
 }  // namespace amdrec
 
+// test / debugging entry only: z[r] = x0[r] + (W_ov x0[r] + b_ov), one workgroup per row, thread f = output feature (fp32 fma
+// chain over k ascending, the generic path's order of the bias and the residual)
+__global__ __launch_bounds__(256) void x3_fold_rows_kernel(const float* X, long long ldx, const float* W, long long ldw,
+                                                           const float* b, float* Z) {
+    __shared__ float xr[256];
+    const long long r = blockIdx.x;
+    const int f = threadIdx.x;
+    xr[f] = X[r * ldx + f];
+    __syncthreads();
+    const float* w = W + f * ldw;
+    float acc = 0.f;
+    for (int k = 0; k < 256; ++k) acc = __builtin_fmaf(w[k], xr[k], acc);
+    Z[r * 256 + f] = xr[f] + (acc + b[f]);
+}
+
 extern "C" int amdrec_ranker_x3_prefix(const amdrec_ranker_params* p, const float* X, int64_t ldx, int64_t rows,
                                        int n_phases, float* x_out, int64_t ld_out, float* logits, int64_t ld_logits,
                                        void* workspace, size_t workspace_bytes, void* stream) {
@@ -195,8 +220,19 @@ extern "C" int amdrec_ranker_x3_prefix(const amdrec_ranker_params* p, const floa
     const size_t need = x3_scratch_bytes(rows);
     if (!workspace || workspace_bytes < need)
         return set_error(AMDREC_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    float* scratch = reinterpret_cast<float*>(workspace);
     x3::Input in{};
     in.X = X; in.ldx = ldx;
-    return x3_launch(G, in, rows, reinterpret_cast<float*>(workspace), x_out, ld_out, logits, ld_logits,
-                     reinterpret_cast<hipStream_t>(stream), cs ? 160 : (int)p->x3.variant);
+    if (x3_folded(p)) {
+        // X is x0; the folded chain wants z = x0 + W_ov x0 + b_ov.  z goes to the scratch rows (row r at r * 256): the
+        // 32-row kernel later stores a row's x0 of the cross layers over that same row, after its own lane has read it
+        const amdrec_encoder_layer& L = p->layers[0];
+        REQUIRE(L.w_o != nullptr && L.b_o != nullptr && L.ldw_dm >= 256, "x3: folded parameters without layer 1's W_ov / b_ov");
+        hipLaunchKernelGGL(x3_fold_rows_kernel, dim3((unsigned)rows), dim3(256), 0, st, X, (long long)ldx, L.w_o,
+                           (long long)L.ldw_dm, L.b_o, scratch);
+        HIP_TRY(hipGetLastError());
+        in.X = scratch; in.ldx = 256;
+    }
+    return x3_launch(G, in, rows, scratch, x_out, ld_out, logits, ld_logits, st, cs ? 160 : (int)p->x3.variant);
 }

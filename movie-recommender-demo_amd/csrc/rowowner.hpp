@@ -2,7 +2,9 @@
 //
 // WHAT.  One kernel runs the whole chain  gather/x0 -> n x { x = LN(x + W_ov x + b) ; x = LN(x + W_2 relu(W_1 x + b_1)
 // + b_2) } -> 3 x cross -> 3 heads -> logits  for 128 candidate rows per workgroup (4 waves x 32 rows), with every
-// activation living in REGISTERS between the GEMMs: nothing but the input rows and the logits touches HBM.
+// activation living in REGISTERS between the GEMMs: nothing but the input rows and the logits touches HBM.  (With layer 1's
+// attention folded into the projection, amdrec_x3_weights.fold_attn1, the input rows are z = x0 + W_ov x0 + b_ov and the
+// first phase is x = LN(z) alone: PH_LN.)
 //
 // ARITHMETIC ("x3": fp32 in, fp32 out, fp32-level error on the 16-bit matrix pipe).  Every fp32 operand is multiplied
 // by a power of two (exact) and split into two fp16 planes  v = h + l + e,  h = RN16(v), l = RN16(v - h),
@@ -60,7 +62,9 @@ constexpr int DEPTH = NBUF - 3;                  // chunks in flight beyond the 
 constexpr int ROWS_PER_WAVE = 32, WAVES = 4, ROWS_PER_WG = ROWS_PER_WAVE * WAVES;
 constexpr int TARGET_EXP = 12;                   // scaled row / matrix maxima lie in [2^12, 2^13)
 
-enum PhaseType { PH_ATTN_LN = 0, PH_FFN_LN = 1, PH_CROSS = 2, PH_HEADS = 3 };
+// PH_LN: LayerNorm alone (gamma / beta), no weights and no stream chunks - layer 1's LN1 when its attention block is
+// folded into the feature projection (amdrec_x3_weights.fold_attn1: the input rows are z = x0 + W_ov x0 + b_ov already)
+enum PhaseType { PH_ATTN_LN = 0, PH_FFN_LN = 1, PH_CROSS = 2, PH_HEADS = 3, PH_LN = 4 };
 
 struct Phase {
     int type;
@@ -70,7 +74,7 @@ struct Phase {
     // offsets (in floats) into the parameter blob, which is DMA'd into LDS once per workgroup (see Program::params)
     int b1;                 // ATTN/CROSS: bias [256]; FFN: b_1 [d_ff]; HEADS: stacked b_1 [n_tasks * head_h1]
     int b2;                 // FFN: b_2 [256]
-    int gamma;              // LayerNorm weight / bias [256] (ATTN, FFN)
+    int gamma;              // LayerNorm weight / bias [256] (ATTN, FFN, LN)
     int beta;
     float sw1, sw2;         // power-of-two scales of the packed weight planes (W_ov / W_1 / W_c / head W_1; W_2 / head W_2)
     float hn, hb;           // FFN / HEADS hidden bound: |relu(w_j . x + b_j)| <= hn * (2^13 / row scale) + hb, with
@@ -548,6 +552,8 @@ __global__ __launch_bounds__(256, 1) void ranker_x3_kernel(Program G, Input in, 
         const int type = __builtin_amdgcn_readfirstlane(P.type);
         if (type == PH_ATTN_LN) {
             phase_attn_ln(ring, P, x, pb);
+        } else if (type == PH_LN) {
+            layer_norm(x, pb, P.gamma, P.beta, P.ln_eps);
         } else if (type == PH_FFN_LN) {
             phase_ffn_ln(ring, P, x, pb);
         } else if (type == PH_CROSS) {

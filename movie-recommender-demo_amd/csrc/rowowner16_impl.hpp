@@ -693,6 +693,7 @@ __device__ __forceinline__ void run_chain(const Program& G, const Input& in, lon
         const int type = __builtin_amdgcn_readfirstlane(P.type);
         if (type == x3::PH_ATTN_LN) phase_attn_ln(ring, P, x, pb);
         else if (type == x3::PH_FFN_LN) phase_ffn_ln(ring, P, x, pb);
+        else if (type == x3::PH_LN) layer_norm(x, pb, P.gamma, P.beta, P.ln_eps);     // folded layer-1 attention
         else break;
     }
     if (p < G.n_phases && __builtin_amdgcn_readfirstlane(G.ph[p].type) == x3::PH_CROSS) {

@@ -349,6 +349,13 @@ __device__ __forceinline__ void phase_ffn_ln(Ring& ring, f16x8 (&cur)[4], const 
     layer_norm_own(all, acc2, 1.0f / (P.sw2 * sh), x, xo, w, pb, P.gamma, P.beta, P.ln_eps);
 }
 
+// LayerNorm alone (layer 1's LN1 with its attention folded into the projection): no chunks, no exchange - every wave holds
+// the full rows; the 16-row kernel's own function on the same values, then this wave's tiles picked out of the result
+__device__ __forceinline__ void phase_ln(const Phase& P, f32x4 (&x)[16], f32x4 (&xo)[4], int w, lds_cfloat* pb) {
+    x3b::layer_norm(x, pb, P.gamma, P.beta, P.ln_eps);
+    own4(x, w, xo);
+}
+
 // xl <- x0 * (xl W + b) + xl; x0o / xo = this wave's tiles of the trunk's output / of xl
 __device__ __forceinline__ void phase_cross(Ring& ring, f16x8 (&cur)[4], const Exchange& E, const Phase& P, f32x4 (&x)[16],
                                             f32x4 (&xo)[4], const f32x4 (&x0o)[4], int w, lds_cfloat* pb) {
@@ -510,6 +517,7 @@ __global__ __launch_bounds__(64 * WAVES) void ranker_x3c_kernel(Program G, Input
         const int type = __builtin_amdgcn_readfirstlane(P.type);
         if (type == x3::PH_ATTN_LN) phase_attn_ln(ring, cur, E, P, x, xo, wave, pb);
         else if (type == x3::PH_FFN_LN) phase_ffn_ln(ring, cur, E, P, x, xo, wave, pb);
+        else if (type == x3::PH_LN) phase_ln(P, x, xo, wave, pb);
         else break;
     }
     if (p < G.n_phases && __builtin_amdgcn_readfirstlane(G.ph[p].type) == x3::PH_CROSS) {
