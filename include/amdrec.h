@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define AMDREC_ABI_VERSION 12
+#define AMDREC_ABI_VERSION 13
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -159,7 +159,8 @@ int amdrec_ivf_kmeans_step(const float* x, int64_t rows, int64_t ld, int dim, fl
  * amdrec_ivfpq_encode: codes[r][s] = arg min_j |residual_s - C_s[j]|^2 (computed as arg max <r_s, C_s[j]> - |C_s[j]|^2 / 2;
  * ties -> lower j), uint8 [rows][m].
  * amdrec_ivfpq_train_step: one L2 Lloyd iteration of every sub-space in place (encode + 64-bit fixed-point sums: order-
- * independent, bit-reproducible); an empty codeword keeps its value.  rows <= 2^20. */
+ * independent, bit-reproducible); an empty codeword keeps its value; a row with a non-finite coordinate adds to no
+ * codeword.  rows <= 2^20. */
 int amdrec_ivfpq_encode(const float* x, int64_t rows, int64_t ld, int dim, const int64_t* assign, const float* centroids,
                         int64_t ld_centroids, int nlist, const float* codebooks, int m, uint8_t* codes /*[rows][m]*/,
                         void* stream);
@@ -170,7 +171,9 @@ int amdrec_ivfpq_train_step(const float* x, int64_t rows, int64_t ld, int dim, c
 /* Search: probes[nq][nprobe] (amdrec_ivf_select over amdrec_ivf_coarse_keys) ->
  *   amdrec_ivfpq_tables: tables[q * nprobe + p][s][j] = |(queries[q] - centroids[probes[q][p]])_s - C_s[j]|^2 (fp32)
  *   amdrec_ivf_group (qtile 32 or 64) -> amdrec_ivfpq_scan: pool_keys[q][pool_base[q][p] + i] = key(-sum_s table[code_s],
- *       row_pos + pos_offset) over the rows of every probed list (codes stored list-contiguous [N][m], 16-byte aligned)
+ *       row_pos + pos_offset) over the rows of every probed list (codes stored list-contiguous [N][m], 16-byte aligned);
+ *       amdrec_ivfpq_scan_finite (ABI v13) is the same scan where list l's rows at or past list_off[l] + list_finite[l]
+ *       (rows with a non-finite coordinate, kept at the end of their list) get key(-inf, pos): after every finite row
  *   amdrec_ivf_select -> (score desc = distance asc, position asc) -> amdrec_ivfpq_distances: distances = -scores
  *   (unfilled slots: +inf). */
 int amdrec_ivfpq_tables(const float* queries, int64_t nq, int64_t ld_queries, int dim, const int64_t* probes,
@@ -181,6 +184,11 @@ int amdrec_ivfpq_scan(const uint8_t* codes, int m, const int64_t* row_pos, const
                       const int64_t* qtile_prefix, int64_t qtile_bound, int qtile, const int64_t* pair_query,
                       const int64_t* pair_probe, const int64_t* pool_base, int64_t npairs, uint64_t* pool_keys,
                       int64_t pool_ld, int64_t pos_offset, void* stream);
+int amdrec_ivfpq_scan_finite(const uint8_t* codes, int m, const int64_t* row_pos, const int64_t* list_off,
+                             const int64_t* list_finite /*[nlist]*/, int nlist, int64_t max_list_rows, const float* tables,
+                             int nprobe, const int64_t* group_off, const int64_t* qtile_prefix, int64_t qtile_bound,
+                             int qtile, const int64_t* pair_query, const int64_t* pair_probe, const int64_t* pool_base,
+                             int64_t npairs, uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset, void* stream);
 int amdrec_ivfpq_distances(const float* scores /*[nq][k]*/, int64_t nq, int k, float* distances /*[nq][k], may alias*/,
                            void* stream);
 

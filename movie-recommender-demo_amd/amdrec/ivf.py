@@ -97,6 +97,16 @@ def use_grouped_scan(nq: int, nprobe: int, nlist: int) -> bool:
     return nq >= GROUPED_MIN_QUERIES and pairs >= GROUPED_MIN_PAIRS_PER_LIST * min(nlist, pairs)
 
 
+def search_nprobe(nprobe: int, nlist: int) -> int:
+    """The probes a search takes: nprobe clamped to [1, nlist], as faiss's IndexIVF::search clamps it (the stored nprobe
+    is left as set).  More than AMDREC_MAX_K probes cannot be selected: refused with the limit named."""
+    p = min(max(1, int(nprobe)), nlist)
+    if p > _lib.MAX_K:
+        raise ValueError(f"nprobe {p} (after clamping to nlist {nlist}) exceeds AMDREC_MAX_K = {_lib.MAX_K}, the most probes "
+                         f"a search selects")
+    return p
+
+
 def grouped_chunk_limit(nlist: int, nprobe: int) -> int:
     """Largest query chunk whose grouped scan fits one launch: a launch walks at most pairs / tile + nlist query tiles
     (every list can end in a partial tile) and the tile is re-picked per (chunk, probe-column range) - a phase or a tail
@@ -219,7 +229,7 @@ class IVFState:
             out_pos.fill_(-1)
             return
         xs, spos, off, lens, max_len, _ = self._build_lists(xb, n)
-        nprobe = max(1, int(nprobe))
+        nprobe = search_nprobe(nprobe, self.nlist)
         # 1. coarse quantizer: nprobe best centroids by inner product (IndexFlatIP quantizer) = a dense (score, centroid)
         #    key table + the pool select (step 4's kernel); runs below, once the workspace is sized
         cs = torch.empty((nq, nprobe), dtype=torch.float32, device=self.device)

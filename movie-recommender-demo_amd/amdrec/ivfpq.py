@@ -8,10 +8,12 @@ Build and search are hand-written HIP (csrc/ivfpq.hip): PQ training = ``amdrec_i
 order-independent fixed-point sums: bit-reproducible), encoding = ``amdrec_ivfpq_encode`` (tiled GEMM with an arg-min
 epilogue), search = coarse probes (``amdrec_ivf_coarse_keys`` + ``amdrec_ivf_select``, as IVF) -> ``amdrec_ivfpq_tables``
 (one [m][256] distance table per (query, probed list), as faiss builds them for an IP quantizer) -> ``amdrec_ivf_group`` ->
-``amdrec_ivfpq_scan`` (table lookups, keys with score = -distance) -> ``amdrec_ivf_select`` -> ``amdrec_ivfpq_distances``.
+``amdrec_ivfpq_scan_finite`` (table lookups, keys with score = -distance) -> ``amdrec_ivf_select`` ->
+``amdrec_ivfpq_distances``.
 A search call launches only libamdrec kernels and never synchronises with the host: it can be captured in a HIP graph.
 What stays in torch is build-time plumbing: drawing the training sample, gathering the initial codewords and the one stable
-sort that lays the codes out list-contiguously.
+sort that lays the codes out list-contiguously (a list's rows with a non-finite coordinate last: the scan gives them -inf
+keys, so they rank after every finite row, as IVF-Flat's NaN scores do).
 Deviation from faiss: an empty cluster keeps its codeword (faiss splits a large cluster instead).
 """
 from __future__ import annotations
@@ -21,7 +23,7 @@ import torch
 
 from . import _lib
 from .ivf import (POOL_BYTES, MAX_POINTS_PER_CENTROID, MAX_QUERY_TILES, IVFState, _assign, _normalize,
-                  grouped_chunk_limit)
+                  grouped_chunk_limit, search_nprobe)
 
 KSUB = 256                      # nbits = 8
 PQ_NITER = 25                   # faiss ProductQuantizer's default
@@ -52,7 +54,8 @@ class IVFPQState:
         self.nlist, self.dim = ivf.nlist, ivf.dim
         self.device = ivf.device
         self.codes = torch.empty((0, self.m), dtype=torch.uint8, device=self.device)   # insertion order
-        self._lists = None                                          # (codes list-contiguous, spos, list_off, list_len, max_len, n)
+        self.finite = torch.empty((0,), dtype=torch.bool, device=self.device)          # row has only finite coordinates
+        self._lists = None          # (codes list-contiguous, spos, list_off, list_len, max_len, n, finite rows per list)
 
     @property
     def centroids(self):
@@ -107,16 +110,17 @@ class IVFPQState:
         return codes
 
     def encode_rows(self, x_normalised: torch.Tensor):
-        """-> (assign, codes) of a batch of L2-normalised rows, not yet part of the index (``commit``)."""
+        """-> (assign, codes, finite) of a batch of L2-normalised rows, not yet part of the index (``commit``)."""
         a = _assign(x_normalised, self.centroids)
-        return a, self.encode(x_normalised, a)
+        return a, self.encode(x_normalised, a), torch.isfinite(x_normalised).all(1)
 
     def commit(self, batches):
-        """Append the (assign, codes) pairs of ``encode_rows`` in order."""
+        """Append the (assign, codes, finite) triples of ``encode_rows`` in order."""
         if not batches:
             return
-        self.ivf.assign = torch.cat([self.ivf.assign] + [a for a, _ in batches])
-        self.codes = torch.cat([self.codes] + [c for _, c in batches])
+        self.ivf.assign = torch.cat([self.ivf.assign] + [a for a, _, _ in batches])
+        self.codes = torch.cat([self.codes] + [c for _, c, _ in batches])
+        self.finite = torch.cat([self.finite] + [f for _, _, f in batches])
         self._lists = None
 
     def append(self, x_normalised: torch.Tensor):
@@ -126,13 +130,15 @@ class IVFPQState:
     def _build_lists(self):
         n = self.ntotal
         if self._lists is None or self._lists[5] != n:
-            a = self.assign[:n]
-            order = torch.argsort(a, stable=True)                   # rows of a list keep insertion order
+            a, fin = self.assign[:n], self.finite[:n]
+            # rows of a list keep insertion order, its non-finite rows after its finite ones
+            order = torch.argsort(a * 2 + (~fin).to(torch.int64), stable=True)
             counts = torch.bincount(a, minlength=self.nlist)
+            nfin = torch.bincount(a[fin], minlength=self.nlist).to(torch.int64)
             off = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
             off[1:] = torch.cumsum(counts, 0)
             self._lists = (self.codes[order].contiguous(), order.contiguous(), off, counts.to(torch.int64),
-                           int(counts.max().item()) if n else 0, n)
+                           int(counts.max().item()) if n else 0, n, nfin)
             self.ivf._top_rows = np.cumsum(np.sort(counts.cpu().numpy())[::-1].astype(np.int64))
         return self._lists
 
@@ -178,9 +184,9 @@ class IVFPQState:
             out_dist.fill_(float("inf"))
             out_pos.fill_(-1)
             return
-        codes, spos, off, lens, max_len, _ = self._build_lists()
+        codes, spos, off, lens, max_len, _, nfin = self._build_lists()
         ivf = self.ivf
-        nprobe = max(1, int(nprobe))
+        nprobe = search_nprobe(nprobe, self.nlist)
         st = lambda: _lib.stream_ptr(self.device)      # noqa: E731  (per call: check() ends the call's device scope)
         # 1. coarse quantizer: the IVF index's (dense key table + pool select, or the flat search beyond its limits)
         cs = torch.empty((nq, nprobe), dtype=torch.float32, device=self.device)
@@ -218,10 +224,11 @@ class IVFPQState:
             _lib.check(lib.amdrec_ivf_group(_lib.ptr(probes[s:]), nprobe, m, nprobe, self.nlist, _lib.ptr(lens),
                                             _lib.ptr(base[s:]), _lib.ptr(n_pool[s:]), _lib.ptr(pair_q), _lib.ptr(pair_p),
                                             _lib.ptr(goff), _lib.ptr(qtp), QTILE, _lib.ptr(grp), grp.numel(), st()))
-            _lib.check(lib.amdrec_ivfpq_scan(_lib.ptr(codes), self.m, _lib.ptr(spos), _lib.ptr(off), self.nlist, max_len,
-                                             _lib.ptr(tables), nprobe, _lib.ptr(goff), _lib.ptr(qtp),
-                                             (m * nprobe) // QTILE + self.nlist, QTILE, _lib.ptr(pair_q), _lib.ptr(pair_p),
-                                             _lib.ptr(base[s:]), m * nprobe, _lib.ptr(ws), pool_ld, pos_offset, st()))
+            _lib.check(lib.amdrec_ivfpq_scan_finite(_lib.ptr(codes), self.m, _lib.ptr(spos), _lib.ptr(off), _lib.ptr(nfin),
+                                                    self.nlist, max_len, _lib.ptr(tables), nprobe, _lib.ptr(goff),
+                                                    _lib.ptr(qtp), (m * nprobe) // QTILE + self.nlist, QTILE, _lib.ptr(pair_q),
+                                                    _lib.ptr(pair_p), _lib.ptr(base[s:]), m * nprobe, _lib.ptr(ws), pool_ld,
+                                                    pos_offset, st()))
             # 4. the k best keys (score = -distance) -> distances
             ivf._select(lib, ws, pool_ld, n_pool[s:], m, k, out_dist[s:], out_pos[s:], st())
         _lib.check(lib.amdrec_ivfpq_distances(_lib.ptr(out_dist), nq, k, _lib.ptr(out_dist), st()))
@@ -229,10 +236,14 @@ class IVFPQState:
     # -- persistence ----------------------------------------------------------------------
     def export_arrays(self):
         return [("ivf_centroids", self.centroids.cpu().numpy()), ("ivf_assign", self.assign.cpu().numpy()),
-                ("pq_codebooks", self.codebooks.cpu().numpy()), ("pq_codes", self.codes.cpu().numpy())]
+                ("pq_codebooks", self.codebooks.cpu().numpy()), ("pq_codes", self.codes.cpu().numpy()),
+                ("pq_finite", self.finite.cpu().numpy().astype(np.uint8))]
 
     @classmethod
     def from_arrays(cls, arrays, device) -> "IVFPQState":
         st = cls(IVFState.from_arrays(arrays, device), torch.from_numpy(np.array(arrays["pq_codebooks"])).to(device))
         st.codes = torch.from_numpy(np.array(arrays["pq_codes"])).to(device)
+        fin = arrays.get("pq_finite")                               # (absent from files saved before it was kept)
+        st.finite = (torch.ones(st.codes.shape[0], dtype=torch.bool) if fin is None
+                     else torch.from_numpy(np.array(fin) != 0)).to(device)
         return st

@@ -112,6 +112,10 @@ __global__ __launch_bounds__(256) void pq_accumulate_kernel(const float* x, long
     const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (r >= rows) return;
+    // a row with any non-finite coordinate adds neither sums nor counts (its codes are meaningless): one wave per row
+    bool bad = false;
+    for (int c = lane; c < d; c += 64) bad |= !__builtin_isfinite(x[r * ld + c]);
+    if (__ballot(bad)) return;
     long long a = assign[r];
     a = a < 0 ? 0 : (a >= nlist ? nlist - 1 : a);
     for (int c = lane; c < d; c += 64) {
@@ -179,10 +183,12 @@ __global__ __launch_bounds__(256) void pq_tables_kernel(const float* Q, long lon
 // blockIdx.y = one (list, query tile) of amdrec_ivf_group (qtile_prefix), blockIdx.x = a share of the list's rows (gridDim.x
 // workgroups split a long list).  The tile's queries are taken QS at a time: their tables (m KiB each) fill 64 KiB of LDS
 // (two workgroups per CU); each thread then owns a row: one code load (m bytes), and per query m LDS lookups summed in
-// sub-space order and one 8-byte key store (consecutive rows: consecutive keys of the query's pool row).
+// sub-space order and one 8-byte key store (consecutive rows: consecutive keys of the query's pool row).  A list keeps its
+// rows with a non-finite coordinate after its list_fin[l] finite ones: their keys are -inf (after every finite row).
+// list_fin == nullptr: every row is finite.
 template <int M>
 __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* codes, const long long* spos,
-                                                      const long long* list_off, int nlist, const float* tables, int nprobe,
+                                                      const long long* list_off, const long long* list_fin, int nlist, const float* tables, int nprobe,
                                                       const long long* goff, const long long* qt_prefix, int qtile,
                                                       const long long* pair_q, const long long* pair_p, const long long* base,
                                                       unsigned long long* keys, long long pool_ld, long long pos_offset) {
@@ -205,7 +211,7 @@ __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* codes
         }
     }
     const int l = lo;
-    const long long r0 = list_off[l], len = list_off[l + 1] - r0;
+    const long long r0 = list_off[l], len = list_off[l + 1] - r0, nfin = list_fin ? list_fin[l] : len;
     if ((long long)blockIdx.x * 256 >= len) return;
     const long long g0 = goff[l], g = goff[l + 1] - g0;
     const long long p0 = (y - qt_prefix[l]) * qtile;
@@ -224,7 +230,8 @@ __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* codes
             dst[t] = q * pool_ld + base[q * nprobe + pair_p[g0 + sp + t]];
         }
         __syncthreads();
-        for (long long row = (long long)blockIdx.x * 256 + t; row < len; row += (long long)gridDim.x * 256) {
+        const long long stride = (long long)gridDim.x * 256, row0 = (long long)blockIdx.x * 256 + t;
+        for (long long row = row0; row < nfin; row += stride) {          // the list's finite rows
             uint32_t cw[M / 4];
             const uint32_t* src = reinterpret_cast<const uint32_t*>(codes + (r0 + row) * M);
             if constexpr (M == 4) {
@@ -249,6 +256,13 @@ __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* codes
                 if (!(sc == sc)) sc = -INFINITY;                         // NaN distances rank last
                 keys[dst[j] + row] = make_key(sc, pos);
             }
+        }
+        // its rows with a non-finite coordinate (rare; none when list_fin is null): -inf keys, no lookups.  A loop of
+        // their own keeps the per-(row, query) path above as it is
+        const long long skip = row0 < nfin ? (nfin - row0 + stride - 1) / stride : 0;
+        for (long long row = row0 + skip * stride; row < len; row += stride) {
+            const uint32_t pos = (uint32_t)(spos[r0 + row] + pos_offset);
+            for (int j = 0; j < nsub; ++j) keys[dst[j] + row] = make_key(-INFINITY, pos);
         }
     }
 }
@@ -363,11 +377,11 @@ extern "C" int amdrec_ivfpq_tables(const float* queries, int64_t nq, int64_t ld_
     return AMDREC_OK;
 }
 
-extern "C" int amdrec_ivfpq_scan(const uint8_t* codes, int m, const int64_t* row_pos, const int64_t* list_off, int nlist,
-                                 int64_t max_list_rows, const float* tables, int nprobe, const int64_t* group_off,
-                                 const int64_t* qtile_prefix, int64_t qtile_bound, int qtile, const int64_t* pair_query,
-                                 const int64_t* pair_probe, const int64_t* pool_base, int64_t npairs, uint64_t* pool_keys,
-                                 int64_t pool_ld, int64_t pos_offset, void* stream) {
+static int scan_impl(const uint8_t* codes, int m, const int64_t* row_pos, const int64_t* list_off,
+                     const int64_t* list_finite, int nlist, int64_t max_list_rows, const float* tables, int nprobe,
+                     const int64_t* group_off, const int64_t* qtile_prefix, int64_t qtile_bound, int qtile,
+                     const int64_t* pair_query, const int64_t* pair_probe, const int64_t* pool_base, int64_t npairs,
+                     uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset, void* stream) {
     REQUIRE(pq_m_ok(m), "m=%d must be 4, 8, 16 or 32", m);
     REQUIRE(nlist >= 1 && nprobe >= 1, "bad nlist/nprobe");
     REQUIRE(qtile == 32 || qtile == 64, "qtile must be 32 or 64 (the value given to amdrec_ivf_group)");
@@ -388,8 +402,9 @@ extern "C" int amdrec_ivfpq_scan(const uint8_t* codes, int m, const int64_t* row
     ProfScope prof("ivfpq_scan", 0.0, 0.0, st);
 #define AMDREC_PQ_SCAN(MM)                                                                                                  \
     hipLaunchKernelGGL(pq_scan_kernel<MM>, dim3((unsigned)gx, (unsigned)qtile_bound), dim3(256), 0, st, codes,              \
-                       (const long long*)row_pos, (const long long*)list_off, nlist, tables, nprobe,                       \
-                       (const long long*)group_off, (const long long*)qtile_prefix, qtile, (const long long*)pair_query,   \
+                       (const long long*)row_pos, (const long long*)list_off, (const long long*)list_finite, nlist,        \
+                       tables, nprobe, (const long long*)group_off, (const long long*)qtile_prefix, qtile,                 \
+                       (const long long*)pair_query,                                                                       \
                        (const long long*)pair_probe, (const long long*)pool_base, (unsigned long long*)pool_keys, pool_ld, \
                        pos_offset)
     switch (m) {
@@ -401,6 +416,27 @@ extern "C" int amdrec_ivfpq_scan(const uint8_t* codes, int m, const int64_t* row
 #undef AMDREC_PQ_SCAN
     HIP_TRY(hipGetLastError());
     return AMDREC_OK;
+}
+
+extern "C" int amdrec_ivfpq_scan(const uint8_t* codes, int m, const int64_t* row_pos, const int64_t* list_off, int nlist,
+                                 int64_t max_list_rows, const float* tables, int nprobe, const int64_t* group_off,
+                                 const int64_t* qtile_prefix, int64_t qtile_bound, int qtile, const int64_t* pair_query,
+                                 const int64_t* pair_probe, const int64_t* pool_base, int64_t npairs, uint64_t* pool_keys,
+                                 int64_t pool_ld, int64_t pos_offset, void* stream) {
+    return scan_impl(codes, m, row_pos, list_off, nullptr, nlist, max_list_rows, tables, nprobe, group_off, qtile_prefix,
+                     qtile_bound, qtile, pair_query, pair_probe, pool_base, npairs, pool_keys, pool_ld, pos_offset, stream);
+}
+
+extern "C" int amdrec_ivfpq_scan_finite(const uint8_t* codes, int m, const int64_t* row_pos, const int64_t* list_off,
+                                        const int64_t* list_finite, int nlist, int64_t max_list_rows, const float* tables,
+                                        int nprobe, const int64_t* group_off, const int64_t* qtile_prefix,
+                                        int64_t qtile_bound, int qtile, const int64_t* pair_query, const int64_t* pair_probe,
+                                        const int64_t* pool_base, int64_t npairs, uint64_t* pool_keys, int64_t pool_ld,
+                                        int64_t pos_offset, void* stream) {
+    REQUIRE(list_finite != nullptr, "null pointer: list_finite");
+    return scan_impl(codes, m, row_pos, list_off, list_finite, nlist, max_list_rows, tables, nprobe, group_off,
+                     qtile_prefix, qtile_bound, qtile, pair_query, pair_probe, pool_base, npairs, pool_keys, pool_ld,
+                     pos_offset, stream);
 }
 
 extern "C" int amdrec_ivfpq_distances(const float* scores, int64_t nq, int k, float* distances, void* stream) {

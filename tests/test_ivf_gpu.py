@@ -385,3 +385,28 @@ def test_bf16_prefiltered_second_phase_equals_the_fp32_scan(n, nlist, nprobe, k,
     flat_search(idx._ivf.centroids, nlist, torch.from_numpy(xqn).cuda(), nprobe, cs, pr)
     rD, rI = oracle.search.ivf_search(xbn, assign, cent, xqn, k, nprobe, probes=pr.cpu().numpy())
     oracle.search.check_topk(rD, rI, D_m, ids_m, tau=cases.TOPK_TAU, score_tol=cases.SCORE_ATOL)
+
+
+def test_ivf_nprobe_is_clamped_to_nlist_and_refused_beyond_max_k():
+    """faiss's IndexIVF::search clamps nprobe to nlist: nprobe = nlist + 50 equals nprobe = nlist bit for bit, the stored
+    nprobe stays what the user set.  With nlist > AMDREC_MAX_K, nprobe beyond it is a ValueError naming the limit (not
+    the flat search's refusal of its k)."""
+    from amdrec.index import FAISSIndex
+    xb, xq = _clustered(8_000, 64, 20, 41), _clustered(30, 64, 20, 42)
+    idx = FAISSIndex(64, index_type="IVF", nlist=32, nprobe=32)
+    idx.add(xb)
+    ids, D = idx.search(xq, 100)
+    idx.index.nprobe = 82
+    ids2, D2 = idx.search(xq, 100)
+    assert np.array_equal(ids2, ids) and np.array_equal(D2.view(np.uint32), D.view(np.uint32))
+    assert idx.get_stats()["nprobe"] == 82
+    big = FAISSIndex(64, index_type="IVF", nlist=2100, nprobe=2100)
+    rng = np.random.default_rng(43)
+    c = rng.standard_normal((2100, 64)).astype(np.float32)
+    big.set_trained_centroids(c / np.linalg.norm(c, axis=1, keepdims=True))
+    big.add(xb[:500])
+    with pytest.raises(ValueError, match="AMDREC_MAX_K = 2048"):
+        big.search(xq, 10)
+    big.index.nprobe = 2048
+    ids, D = big.search(xq, 10)
+    assert ids.shape == (30, 10)

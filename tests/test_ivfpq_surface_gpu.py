@@ -1,0 +1,396 @@
+"""IVFPQ across what FAISSIndex accepts, against the float64 oracle (tests/ivfpq_oracle.py) with tolerances that scale with
+the shape (ivfpq_oracle.table_tol / dist_tol): (i) every sub-space width class of the encoder, the tables and the scan,
+one training step; (ii) the leading-dimension arguments of the C ABI; (iii) the query chunks of IVFPQState.search and the
+coarse fallback; (iv) adds in several batches and in odd sizes, k and nprobe at their limits, empty lists; (v) rows and
+queries with non-finite coordinates (they rank after every finite row, at +inf)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import oracle
+from amdrec import _lib
+from tests import ivfpq_oracle
+from tests.test_ivfpq_gpu import CODE_TIE_ATOL, _clustered, _normalized_on_device, _state
+
+pytestmark = pytest.mark.gpu
+
+# (d, m): dsub 4, 12, 24, 48 (partial last staging step of the encoder, twice), 128, 512 (PQ_MAX_DSUB), and m = 32 at a
+# large d (dsub 64)
+SHAPES = [(16, 4), (96, 8), (96, 4), (192, 4), (384, 8), (512, 4), (2048, 4), (2048, 32)]
+
+
+def _index(d, m, n=3000, nlist=16, nprobe=4, seed=1, n_clusters=20):
+    from amdrec.index import FAISSIndex
+    xb = _clustered(n, d, n_clusters, seed)
+    idx = FAISSIndex(d, index_type="IVFPQ", nlist=nlist, nprobe=nprobe, pq_m=m)
+    idx.add(xb)
+    return idx, xb
+
+
+def _code_tie_atol(dsub):
+    """CODE_TIE_ATOL was argued for dsub <= 64; beyond, it grows with the table bound's (dsub + 2)."""
+    return CODE_TIE_ATOL * max(1.0, (dsub + 2) / 66)
+
+
+def _check_scaled(idx, xq, k, nprobe, accuracy=None, case=None, qn=None, finite=None):
+    """The index's search against the oracle given its state (finite: the rows the caller knows to be finite; default
+    all), with dist_tol at the largest finite distance.  -> (positions, distances, oracle distances, oracle positions)."""
+    qn = _normalized_on_device(idx, xq) if qn is None else qn
+    pos, D = idx.search_device(qn, k, normalize=False, return_positions=True)
+    ids, D = pos.cpu().numpy(), D.cpu().numpy()
+    probes = idx._pq.coarse_probes(qn, min(nprobe, idx.nlist)).cpu().numpy()
+    codes, assign, cent, cb = _state(idx)
+    m = cb.shape[0]
+    rD, rI = ivfpq_oracle.adc_search(codes, assign, cent, cb, qn.cpu().numpy(), k, nprobe, probes=probes,
+                                     finite=finite)
+    fin = np.isfinite(rD)
+    assert np.array_equal(fin, np.isfinite(D))
+    if fin.any():
+        tol = float(ivfpq_oracle.dist_tol(rD[fin].max(), idx.dimension, m))
+        err = float(np.abs(D[fin] - rD[fin]).max())
+        assert err <= tol, (err, tol)
+        oracle.search.check_topk(-rD, rI, -D, ids, tau=2 * tol, score_tol=tol)
+        if accuracy is not None:
+            accuracy(case, "ivfpq scan", err / tol, bound=tol)
+    assert (np.diff(D, axis=1)[fin[:, 1:]] >= 0).all()
+    return ids, D, rD, rI
+
+
+def _encode_abi(x, a, cent, cb, m, ld=None, ldc=None):
+    n, d = x.shape[0], cb.shape[0] * cb.shape[2]
+    codes = torch.empty((n, m), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.load().amdrec_ivfpq_encode(_lib.ptr(x), n, ld or x.stride(0), d, _lib.ptr(a), _lib.ptr(cent),
+                                               ldc or cent.stride(0), cent.shape[0], _lib.ptr(cb), m, _lib.ptr(codes),
+                                               _lib.stream_ptr(x.device)))
+    return codes
+
+
+def _train_step_abi(x, a, cent, cb, m, ld=None, ldc=None):
+    """One amdrec_ivfpq_train_step on a copy of cb -> the new codebooks."""
+    n, d = x.shape[0], cb.shape[0] * cb.shape[2]
+    lib = _lib.load()
+    nb = C.c_size_t(0)
+    _lib.check(lib.amdrec_ivfpq_train_workspace(n, d, m, C.byref(nb)))
+    ws = torch.empty(nb.value, dtype=torch.uint8, device=x.device)
+    out = cb.clone()
+    _lib.check(lib.amdrec_ivfpq_train_step(_lib.ptr(x), n, ld or x.stride(0), d, _lib.ptr(a), _lib.ptr(cent),
+                                           ldc or cent.stride(0), cent.shape[0], _lib.ptr(out), m, _lib.ptr(ws), ws.numel(),
+                                           _lib.stream_ptr(x.device)))
+    torch.cuda.synchronize()
+    return out
+
+
+def _tables_abi(q, probes, cent, cb, m, ldq=None, ldp=None, nprobe=None, ldc=None):
+    nq, d = q.shape[0], cb.shape[0] * cb.shape[2]
+    nprobe = nprobe or probes.shape[1]
+    t = torch.empty((nq * nprobe, m, 256), dtype=torch.float32, device=q.device)
+    _lib.check(_lib.load().amdrec_ivfpq_tables(_lib.ptr(q), nq, ldq or q.stride(0), d, _lib.ptr(probes), ldp or probes.stride(0),
+                                               nprobe, _lib.ptr(cent), ldc or cent.stride(0), cent.shape[0], _lib.ptr(cb), m,
+                                               _lib.ptr(t), _lib.stream_ptr(q.device)))
+    torch.cuda.synchronize()
+    return t
+
+
+def _padded(t, ld, fill=float("nan")):
+    """A [rows][ld] buffer whose first t.shape[1] columns are t and the rest ``fill``; 16-byte aligned base."""
+    p = torch.full((t.shape[0], ld), fill, dtype=t.dtype, device=t.device)
+    p[:, :t.shape[1]] = t
+    return p
+
+
+def _sample_codebooks(res, m, step=7):
+    d = res.shape[1]
+    rows = torch.arange(0, 256 * step, step, device=res.device) % res.shape[0]
+    return res[rows].view(256, m, d // m).permute(1, 0, 2).contiguous()
+
+
+# ---- (i) the shape surface ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("d,m", SHAPES)
+def test_ivfpq_shape_surface_against_float64(d, m, accuracy):
+    dsub = d // m
+    idx, xb = _index(d, m)
+    pq = idx._pq
+    xn = _normalized_on_device(idx, xb)
+    codes, assign, cent, cb = _state(idx)
+    xn64 = xn.cpu().numpy()
+    # encoder: the arg-min codes up to near-ties
+    ref = ivfpq_oracle.encode(xn64, assign, cent, cb)
+    same = codes == ref
+    assert same.mean() >= 0.99, same.mean()
+    rows, subs = np.nonzero(~same)
+    worst = 0.0
+    for s in np.unique(subs):
+        r = rows[subs == s]
+        dg = ivfpq_oracle.code_distances(xn64, assign, cent, cb, r, s, codes[r, s].astype(np.int64))
+        dr = ivfpq_oracle.code_distances(xn64, assign, cent, cb, r, s, ref[r, s].astype(np.int64))
+        worst = max(worst, float(np.abs(dg - dr).max()))
+    assert worst <= _code_tie_atol(dsub), (worst, _code_tie_atol(dsub))
+    accuracy(f"ivfpq/encode/d{d}_m{m}", "code near-ties", worst / _code_tie_atol(dsub), mismatch=float(1 - same.mean()))
+    # tables, called directly: every (query, probe) entry against the oracle's float64 table
+    xq = _clustered(9, d, 20, 2)
+    qn = _normalized_on_device(idx, xq)
+    nprobe = 4
+    probes = pq.coarse_probes(qn, nprobe)
+    t = _tables_abi(qn, probes, pq.centroids, pq.codebooks, m).cpu().numpy().astype(np.float64)
+    pr, q64 = probes.cpu().numpy(), qn.cpu().numpy()
+    ratio = 0.0
+    for q in range(qn.shape[0]):
+        for p in range(nprobe):
+            lut = ivfpq_oracle.tables(q64[q], cent[pr[q, p]], cb)
+            tol = ivfpq_oracle.table_tol(lut, dsub)
+            err = np.abs(t[q * nprobe + p] - lut)
+            assert (err <= tol).all(), (q, p, float((err / tol).max()))
+            ratio = max(ratio, float((err / tol).max()))
+    accuracy(f"ivfpq/tables/d{d}_m{m}", "pq_tables_kernel", ratio)
+    # scan, on the index's own state
+    _check_scaled(idx, xq, 200, nprobe, accuracy, f"ivfpq/scan/d{d}_m{m}", qn=qn)
+    # one training step from sampled residual codewords: the float64 Lloyd means of the step's own assignment
+    a = pq.assign
+    res = xn - pq.centroids[a]
+    cb0 = _sample_codebooks(res, m)
+    step_codes = _encode_abi(xn, a, pq.centroids, cb0, m).cpu().numpy()
+    got = _train_step_abi(xn, a, pq.centroids, cb0, m).cpu().numpy()
+    r64 = res.cpu().numpy().astype(np.float64)
+    exp = cb0.cpu().numpy().astype(np.float64)
+    for s in range(m):
+        for j in np.unique(step_codes[:, s]):
+            exp[s, j] = r64[step_codes[:, s] == j, s * dsub:(s + 1) * dsub].mean(0)
+    assert np.abs(got - exp).max() <= 1e-6, float(np.abs(got - exp).max())
+    assert not np.array_equal(got, cb0.cpu().numpy())
+
+
+# ---- (ii) leading dimensions of the C ABI -------------------------------------------------------------------------------
+@pytest.mark.parametrize("d,m", [(192, 4), (96, 8)])
+def test_ivfpq_abi_leading_dimensions_with_nan_padding(d, m):
+    """encode / train_step with ld = d + 4 and ld_centroids = d + 4, tables with ld_queries = d + 1 and ld_probes =
+    nprobe + 3; every padding element NaN.  Codes, codebooks and tables equal the contiguous calls bit for bit."""
+    idx, xb = _index(d, m, n=2000)
+    pq = idx._pq
+    x = _normalized_on_device(idx, xb)
+    a, cent = pq.assign, pq.centroids
+    cb0 = _sample_codebooks(x - cent[a], m)
+    xp, cp = _padded(x, d + 4), _padded(cent, d + 4)
+    assert torch.equal(_encode_abi(xp, a, cp, pq.codebooks, m), _encode_abi(x, a, cent, pq.codebooks, m))
+    assert torch.equal(_train_step_abi(xp, a, cp, cb0, m), _train_step_abi(x, a, cent, cb0, m))
+    qn = _normalized_on_device(idx, _clustered(21, d, 20, 3))
+    nprobe = 5
+    probes = pq.coarse_probes(qn, nprobe)
+    ref = _tables_abi(qn, probes, cent, pq.codebooks, m)
+    qp = _padded(qn, d + 1)
+    pp = _padded(probes, nprobe + 3, fill=-(1 << 40))          # never a list: a stride bug reads one
+    got = _tables_abi(qp, pp, cp, pq.codebooks, m, nprobe=nprobe)
+    assert torch.equal(got.view(torch.int32), ref.view(torch.int32))
+
+
+# ---- (iii) query chunks and the coarse fallback --------------------------------------------------------------------------
+def _bits_equal(a, b):
+    (pa, da), (pb, db) = a, b
+    assert torch.equal(pa, pb)
+    assert torch.equal(da.view(torch.int32), db.view(torch.int32))
+
+
+def test_ivfpq_70001_queries_cross_the_chunk_cap():
+    """nq > 65 535: two chunks of one search; equal bit for bit to searches of 10 000-query slices, and ~200 queries
+    (both chunks) against the oracle."""
+    idx, _ = _index(64, 8, n=3000, nlist=16, nprobe=2)
+    k, nq = 10, 70_001
+    qn = _normalized_on_device(idx, _clustered(nq, 64, 20, 4))
+    full = idx.search_device(qn, k, normalize=False, return_positions=True)
+    parts = [idx.search_device(qn[s:s + 10_000], k, normalize=False, return_positions=True) for s in range(0, nq, 10_000)]
+    _bits_equal(full, (torch.cat([p for p, _ in parts]), torch.cat([d for _, d in parts])))
+    sel = np.unique(np.concatenate([np.arange(0, nq, 350), [65_533, 65_534, 65_535, 65_536, nq - 1]]))
+    sub = qn[torch.from_numpy(sel).to(qn.device)]
+    probes = idx._pq.coarse_probes(sub, 2).cpu().numpy()
+    codes, assign, cent, cb = _state(idx)
+    rD, rI = ivfpq_oracle.adc_search(codes, assign, cent, cb, sub.cpu().numpy(), k, 2, probes=probes)
+    pos, D = full[0].cpu().numpy()[sel], full[1].cpu().numpy()[sel]
+    tol = float(ivfpq_oracle.dist_tol(rD[np.isfinite(rD)].max(), 64, 8))
+    oracle.search.check_topk(-rD, rI, -D, pos, tau=2 * tol, score_tol=tol)
+
+
+def test_ivfpq_small_query_chunks_and_the_coarse_fallback(monkeypatch):
+    """TABLE_BYTES forced to 7 queries per chunk (ragged last chunk, boundaries off the 32-query tile), then POOL_BYTES
+    forced below the coarse key table (the flat-search fallback picks the probes): positions and distance bits equal the
+    unchunked search, and the fallback's probes equal the key table's."""
+    from amdrec import ivfpq
+    idx, _ = _index(64, 8, n=3000, nlist=16, nprobe=3)
+    k, nq, nprobe = 50, 45, 3
+    qn = _normalized_on_device(idx, _clustered(nq, 64, 20, 5))
+    ref = idx.search_device(qn, k, normalize=False, return_positions=True)
+    ref_probes = idx._pq.coarse_probes(qn, nprobe)
+    monkeypatch.setattr(ivfpq, "TABLE_BYTES", 7 * nprobe * 8 * ivfpq.KSUB * 4)
+    _bits_equal(idx.search_device(qn, k, normalize=False, return_positions=True), ref)
+    monkeypatch.undo()
+    coarse_ld = (idx.nlist + 1) // 2 * 2
+    monkeypatch.setattr(ivfpq, "POOL_BYTES", nq * coarse_ld * 8 - 8)
+    assert torch.equal(idx._pq.coarse_probes(qn, nprobe), ref_probes)
+    _bits_equal(idx.search_device(qn, k, normalize=False, return_positions=True), ref)
+
+
+# ---- (iv) adds, limits --------------------------------------------------------------------------------------------------
+def test_ivfpq_add_beyond_one_batch_equals_one_encode_call():
+    """300 001 rows (> ADD_BATCH = 2^18: two encode batches): codes bit-identical to one amdrec_ivfpq_encode over all
+    rows; a query sample against the oracle."""
+    from amdrec.index import ADD_BATCH, FAISSIndex
+    n, d, m = 300_001, 32, 8
+    assert n > ADD_BATCH
+    xb = _clustered(n, d, 40, 6)
+    idx = FAISSIndex(d, index_type="IVFPQ", nlist=64, nprobe=4, pq_m=m)
+    idx.add(xb)
+    pq = idx._pq
+    assert pq.ntotal == n and bool(pq.finite.all())
+    x = _normalized_on_device(idx, xb)
+    assert torch.equal(_encode_abi(x, pq.assign, pq.centroids, pq.codebooks, m), pq.codes)
+    _check_scaled(idx, _clustered(16, d, 40, 7), 100, 4)
+
+
+def test_ivfpq_small_adds_match_the_oracle_and_survive_save_load(tmp_path):
+    """Adds of 2000 (trains), 1, 65 (ends mid 64-row encoder tile) and 0 rows: after each, the scan against the oracle given
+    the state and the new rows' codes against oracle.encode with the trained codebooks; then save / load."""
+    from amdrec.index import FAISSIndex
+    d, m = 64, 8
+    xb, xq = _clustered(2066, d, 20, 8), _clustered(12, d, 20, 9)
+    idx = FAISSIndex(d, index_type="IVFPQ", nlist=16, nprobe=4, pq_m=m)
+    lo = 0
+    for size in (2000, 1, 65, 0):
+        idx.add(xb[lo:lo + size].reshape(size, d))
+        assert idx.index.ntotal == lo + size
+        codes, assign, cent, cb = _state(idx)
+        if lo and size:
+            xn = _normalized_on_device(idx, xb[lo:lo + size]).cpu().numpy()
+            got, ref = codes[lo:lo + size], ivfpq_oracle.encode(xn, assign[lo:lo + size], cent, cb)
+            rows, subs = np.nonzero(got != ref)
+            for r, s in zip(rows, subs):
+                dg = ivfpq_oracle.code_distances(xn, assign[lo:lo + size], cent, cb, [r], s, [int(got[r, s])])
+                dr = ivfpq_oracle.code_distances(xn, assign[lo:lo + size], cent, cb, [r], s, [int(ref[r, s])])
+                assert abs(float(dg[0] - dr[0])) <= CODE_TIE_ATOL
+        lo += size
+        _check_scaled(idx, xq, 300, 4)
+    ids, D = idx.search(xq, 300)
+    p = tmp_path / "pq.bin"
+    idx.save(str(p))
+    idx2 = FAISSIndex(d, index_type="IVFPQ")
+    idx2.load(str(p))
+    ids2, D2 = idx2.search(xq, 300)
+    assert np.array_equal(ids2, ids) and np.array_equal(D2.view(np.uint32), D.view(np.uint32))
+
+
+@pytest.mark.parametrize("k", [1, 2048])
+def test_ivfpq_k_at_its_limits(k):
+    idx, _ = _index(64, 8, n=5000, nlist=8, nprobe=8)
+    pos, D, _, _ = _check_scaled(idx, _clustered(20, 64, 20, 10), k, 8)
+    assert np.isfinite(D).all()
+
+
+def test_ivfpq_many_empty_lists():
+    """Six points repeated 400 times each + 600 clustered rows against nlist 128: most lists are empty; probes of empty
+    lists add nothing."""
+    from amdrec.index import FAISSIndex
+    d, m = 64, 8
+    pts = _clustered(6, d, 6, 11)
+    xb = np.concatenate([np.repeat(pts, 400, axis=0), _clustered(600, d, 10, 12)])
+    idx = FAISSIndex(d, index_type="IVFPQ", nlist=128, nprobe=32, pq_m=m)
+    idx.add(xb)
+    lens = np.bincount(idx._pq.assign.cpu().numpy(), minlength=128)
+    assert (lens == 0).sum() >= 32, (lens == 0).sum()
+    xq = np.concatenate([pts[:3], _clustered(9, d, 10, 13)])
+    _check_scaled(idx, xq, 500, 32)
+
+
+def test_ivfpq_nprobe_is_clamped_to_nlist_at_search_time():
+    """faiss's IndexIVF::search clamps nprobe to nlist: nprobe = nlist + 50 equals nprobe = nlist bit for bit; the stored
+    nprobe stays what the user set."""
+    idx, _ = _index(64, 8, n=3000, nlist=16, nprobe=16)
+    xq = _clustered(40, 64, 20, 14)
+    ids, D = idx.search(xq, 200)
+    idx.index.nprobe = 66
+    ids2, D2 = idx.search(xq, 200)
+    assert np.array_equal(ids2, ids) and np.array_equal(D2.view(np.uint32), D.view(np.uint32))
+    assert idx.get_stats()["nprobe"] == 66 and idx.nprobe == 66
+
+
+# ---- (v) non-finite rows and queries ------------------------------------------------------------------------------------
+def test_ivfpq_non_finite_rows_rank_after_every_finite_row():
+    """A row whose normalised vector has a non-finite coordinate never ranks ahead of a finite row; where it appears its
+    distance is +inf, after every finite slot.  The assignment stays the IVF index's, bit for bit."""
+    from amdrec.index import FAISSIndex
+    d, m, n, nlist = 64, 8, 1500, 8
+    xb = _clustered(n, d, 20, 15)
+    clean = xb.copy()
+    bad = [5, 77, 1400]
+    xb[5] = np.nan
+    xb[77, 3] = np.inf
+    xb[1400, 60] = np.nan
+    idx = FAISSIndex(d, index_type="IVFPQ", nlist=nlist, nprobe=2, pq_m=m)
+    idx.train(clean)                                          # (the coarse quantizer on the clean rows, as for IVF)
+    idx.add(xb)
+    finite = np.ones(n, bool)
+    finite[bad] = False
+    xq = _clustered(24, d, 20, 16)
+    # every list probed, k > n: all rows appear, the non-finite ones last among the filled slots
+    idx.index.nprobe = nlist
+    pos, D, _, _ = _check_scaled(idx, xq, 2048, nlist, finite=finite)
+    nf = n - len(bad)
+    assert np.isfinite(D[:, :nf]).all() and np.isinf(D[:, nf:]).all()
+    assert all(sorted(pos[q, nf:n].tolist()) == bad for q in range(len(xq)))
+    assert (pos[:, n:] == -1).all() and not np.isin(pos[:, :nf], bad).any()
+    # fewer slots than rows: a non-finite row is never among the results
+    idx.index.nprobe = 2
+    pos, D, _, _ = _check_scaled(idx, xq, 100, 2, finite=finite)
+    assert np.isfinite(D).all() and not np.isin(pos, bad).any()
+    ivf = FAISSIndex(d, index_type="IVF", nlist=nlist, nprobe=2)
+    ivf.train(clean)
+    ivf.add(xb)
+    assert torch.equal(idx._pq.assign, ivf._ivf.assign)
+
+
+def test_ivfpq_train_step_ignores_non_finite_rows():
+    """A row with any non-finite coordinate contributes neither sums nor counts: a step on x with an all-NaN row and a row
+    with one NaN coordinate inserted gives codebooks bit-identical to the step on x without them (the fixed-point sums are
+    order-independent)."""
+    d, m = 64, 8
+    idx, xb = _index(d, m, n=3000)
+    pq = idx._pq
+    x = _normalized_on_device(idx, xb)
+    a, cent = pq.assign, pq.centroids
+    cb0 = _sample_codebooks(x - cent[a], m)
+    ref = _train_step_abi(x, a, cent, cb0, m)
+    nan_row = torch.full((1, d), float("nan"), device=x.device)
+    one_nan = x[:1].clone()
+    one_nan[0, 9] = float("nan")
+    xx = torch.cat([x[:10], nan_row, x[10:2000], one_nan, x[2000:]]).contiguous()
+    aa = torch.cat([a[:10], a[:1], a[10:2000], a[:1], a[2000:]]).contiguous()
+    got = _train_step_abi(xx, aa, cent, cb0, m)
+    assert torch.equal(got.view(torch.int32), ref.view(torch.int32))
+
+
+def test_ivfpq_nan_query_leaves_its_batch_unchanged():
+    """A NaN query returns +inf in every slot; every other query of the batch, including those that share its LDS
+    sub-tile of the scan (8 queries at m = 8, 2 lists), is bit-identical to the batch without it."""
+    d, m = 64, 8
+    idx, _ = _index(d, m, n=2000, nlist=2, nprobe=2)
+    qn = _normalized_on_device(idx, _clustered(40, d, 20, 17))
+    ref = idx.search_device(qn, 100, normalize=False, return_positions=True)
+    qq = torch.cat([qn[:5], torch.full((1, d), float("nan"), device=qn.device), qn[5:]]).contiguous()
+    pos, D = idx.search_device(qq, 100, normalize=False, return_positions=True)
+    assert torch.isinf(D[5]).all() and (D[5] > 0).all()
+    keep = torch.tensor([i for i in range(41) if i != 5], device=qn.device)
+    _bits_equal((pos[keep], D[keep]), ref)
+
+
+def test_ivfpq_v12_scan_entry_equals_the_finite_scan_on_finite_rows(monkeypatch):
+    """amdrec_ivfpq_scan (the v12 entry, kept for C callers) treats every row as finite: on an index without non-finite
+    rows, a search whose scan goes through it equals the search through amdrec_ivfpq_scan_finite bit for bit."""
+    idx, _ = _index(64, 8, n=3000, nlist=16, nprobe=4)
+    qn = _normalized_on_device(idx, _clustered(37, 64, 20, 18))
+    ref = idx.search_device(qn, 300, normalize=False, return_positions=True)
+    lib = _lib.load()
+    v12 = lib.amdrec_ivfpq_scan
+
+    def through_v12(codes, m, spos, off, nfin, *rest):
+        return v12(codes, m, spos, off, *rest)
+
+    monkeypatch.setattr(lib, "amdrec_ivfpq_scan_finite", through_v12)
+    _bits_equal(idx.search_device(qn, 300, normalize=False, return_positions=True), ref)

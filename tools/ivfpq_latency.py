@@ -50,10 +50,11 @@ def nbytes(*ts):
 def resident_bytes(idx):
     """Device bytes the index holds once searched: ids, assignment, the list-contiguous copy and its row -> position map,
     and the vectors (IVF-Flat: the fp32 rows, their list-contiguous copy and, if built, its bf16 shadow) or the codes
-    (IVFPQ: in insertion order and list-contiguous).  Centroids, codebooks and workspaces are per index, not per ad."""
+    (IVFPQ: in insertion order and list-contiguous, and the per-row finite flags).  Centroids, codebooks and workspaces are
+    per index, not per ad."""
     if idx._pq is not None:
         lists = idx._pq._lists or ()
-        return nbytes(idx._ids, idx._pq.codes, idx._pq.assign, *lists[:4])
+        return nbytes(idx._ids, idx._pq.codes, idx._pq.finite, idx._pq.assign, *lists[:4])
     lists = idx._ivf._lists or ()
     shadow = getattr(idx._ivf, "_shadow", None) or ()
     return nbytes(idx._ids, idx._xb, idx._ivf.assign, *lists[:4], *shadow)
