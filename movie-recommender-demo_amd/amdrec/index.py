@@ -25,7 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ivf, ivfpq
 
 _MAGIC = b"AMDRECIX1"
 ADD_BATCH = 1 << 18            # IVFPQ add: rows normalised and encoded per batch (256 MB of fp32 at d = 256)
@@ -112,7 +112,6 @@ class FAISSIndex:
         if self.dimension % 4 or not (4 <= self.dimension <= 2048):
             raise ValueError("dimension must be a multiple of 4 in [4, 2048]")
         if self.index_type == "IVFPQ":
-            from . import ivfpq
             ivfpq.check_pq_m(self.dimension, self.pq_m)
             ivfpq.check_nlist(self.nlist)
         _lib.load()
@@ -126,8 +125,10 @@ class FAISSIndex:
         self._identity = True          # ids == arange(n): remap is the identity
         self._host_ids: Optional[list] = None   # only for non-integer ids
         self._trained = self.index_type == "Flat"
-        self._ivf = None               # set by train() for IVF
-        self._pq = None                # set by train() for IVFPQ
+        self._keeps_rows = self.index_type != "IVFPQ"    # IVFPQ: codes only, no fp32 corpus on the device
+        self._state = None             # set by train(): the IVFState / IVFPQState behind ...
+        self._ivf = None               # ... an IVF index, or the coarse level of ...
+        self._pq = None                # ... an IVFPQ index
         self.index = _Handle(self)
         self._log(f"Created {self.index_type} index with dimension {self.dimension}")
 
@@ -155,25 +156,30 @@ class FAISSIndex:
         return t
 
     def _reserve(self, n):
-        cap = self._ids.shape[0] if self.index_type == "IVFPQ" else self._xb.shape[0]
+        cap = self._ids.shape[0]                      # ids and rows grow together
         if n <= cap:
             return
         new_cap = max(n, int(cap * 1.5), 1024)
-        ids = torch.empty((new_cap,), dtype=torch.int64, device=self.device)
-        if self._n:
-            ids[:self._n].copy_(self._ids[:self._n])
-        if self.index_type == "IVFPQ":                # codes only: no fp32 corpus on the device
-            self._ids = ids
-            return
-        xb = torch.empty((new_cap, self.dimension), dtype=torch.float32, device=self.device)
-        if self._n:
-            xb[:self._n].copy_(self._xb[:self._n])
-        self._xb, self._ids = xb, ids
-        if self._mixed:
-            xb16 = torch.empty((new_cap, self.dimension), dtype=torch.bfloat16, device=self.device)
-            if self._n:
-                xb16[:self._n].copy_(self._xb16[:self._n])
-            self._xb16 = xb16
+
+        def grown(t):
+            new = torch.empty((new_cap,) + t.shape[1:], dtype=t.dtype, device=self.device)
+            new[:self._n].copy_(t[:self._n])
+            return new
+        self._ids = grown(self._ids)
+        if self._keeps_rows:
+            self._xb = grown(self._xb)
+            if self._mixed:
+                self._xb16 = grown(self._xb16)
+
+    def _state_class(self):
+        """-> (class of the trained state behind this index type, its train() arguments after nlist); (None, ()) for Flat."""
+        return {"IVF": (ivf.IVFState, ()), "IVFPQ": (ivfpq.IVFPQState, (self.pq_m,))}.get(self.index_type, (None, ()))
+
+    def _set_state(self, state):
+        self._state = state
+        self._pq = None if self._keeps_rows else state
+        self._ivf = state if self._keeps_rows else state.ivf
+        self._trained = True
 
     def _shadow_rows(self, lo, hi):
         """(Re)build rows [lo, hi) of the bf16 shadow from the fp32 rows and fold their norms into _maxnorm."""
@@ -192,14 +198,8 @@ class FAISSIndex:
             return
         t0 = time.time()
         self._log(f"Training index on {len(embeddings)} samples...")
-        if self.index_type == "IVFPQ":
-            from . import ivfpq
-            self._pq = ivfpq.IVFPQState.train(self._to_device_f32(embeddings), self.nlist, self.pq_m)
-            self._ivf = self._pq.ivf
-        else:
-            from . import ivf
-            self._ivf = ivf.IVFState.train(self._to_device_f32(embeddings), self.nlist)
-        self._trained = True
+        cls, extra = self._state_class()
+        self._set_state(cls.train(self._to_device_f32(embeddings), self.nlist, *extra))
         self._log(f"Index trained in {time.time() - t0:.2f}s")
 
     def set_trained_centroids(self, centroids):
@@ -210,12 +210,10 @@ class FAISSIndex:
             raise ValueError("only an IVF index has a coarse quantizer")
         if self._n:
             raise ValueError("set the centroids before adding vectors")
-        from . import ivf
         c = self._to_device_f32(centroids)
         if c.shape[0] != self.nlist:
             raise ValueError(f"expected {self.nlist} centroids, got {c.shape[0]}")
-        self._ivf = ivf.IVFState(c)
-        self._trained = True
+        self._set_state(ivf.IVFState(c))
 
     @property
     def centroids(self):
@@ -237,7 +235,7 @@ class FAISSIndex:
             raise ValueError(f"expected [n, {self.dimension}] embeddings, got {tuple(src.shape)}")
         m = src.shape[0]
         self._reserve(self._n + m)
-        if self.index_type == "IVFPQ":
+        if not self._keeps_rows:
             # normalised and encoded batch by batch: only the codes stay.  Nothing is committed to the PQ state before the
             # ids below are accepted (a rejected add must leave the index as it was)
             pq_new = [self._pq.encode_rows(self._normalize_(
@@ -280,6 +278,10 @@ class FAISSIndex:
         self._log(f"Added embeddings in {time.time() - t0:.2f}s")
         self._log(f"Total index size: {self._n}")
 
+    def resident_tensors(self) -> list:
+        """Every device tensor the index keeps between calls (a captured graph's kernels point at them)."""
+        return [self._xb, self._ids, self._xb16, self._maxnorm] + (self._state.resident_tensors() if self._state else [])
+
     @property
     def id_map(self) -> list:
         if self._host_ids is not None:
@@ -308,22 +310,21 @@ class FAISSIndex:
         nq = q.shape[0]
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         pos = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        off = pos_offset if return_positions else 0
         if self.index_type == "IVF":
-            self._ivf.search(self._xb, self._n, q, k, self.nprobe, scores, pos,
-                             pos_offset=pos_offset if return_positions else 0)
+            self._ivf.search(self._xb, self._n, q, k, self.nprobe, scores, pos, pos_offset=off)
         elif self.index_type == "IVFPQ":                              # scores = squared L2 distances, ascending
-            self._pq.search(q, k, self.nprobe, scores, pos, pos_offset=pos_offset if return_positions else 0)
+            self._pq.search(q, k, self.nprobe, scores, pos, pos_offset=off)
         elif self._mixed:
-            flat_search_mixed(self._xb, self._xb16, self._maxnorm, self._n, q, k, scores, pos,
-                              pos_offset=pos_offset if return_positions else 0)
+            flat_search_mixed(self._xb, self._xb16, self._maxnorm, self._n, q, k, scores, pos, pos_offset=off)
         else:
-            flat_search(self._xb, self._n, q, k, scores, pos, pos_offset=pos_offset if return_positions else 0)
+            flat_search(self._xb, self._n, q, k, scores, pos, pos_offset=off)
         if return_positions or self._identity:
             # identity map: id == position for filled slots; unfilled (-1) slots map to
             # id_map[-1] in the reference (:159) - reproduce that too
             if return_positions:
                 return pos, scores
-            if self._n and (k > self._n or self.index_type in ("IVF", "IVFPQ")):   # only then can a slot be unfilled
+            if self._n and (k > self._n or self._state is not None):   # only then can a slot be unfilled
                 pos = torch.where(pos < 0, pos + self._n, pos)
             return pos, scores
         lib = _lib.load()
@@ -366,12 +367,10 @@ class FAISSIndex:
         d = os.path.dirname(os.path.abspath(filepath))
         os.makedirs(d, exist_ok=True)
         arrays = [("ids", self._ids[:self._n].cpu().numpy())]
-        if self._pq is not None:                                     # codes, centroids, codebooks, assignment: no xb
-            arrays += self._pq.export_arrays()
-        else:
+        if self._keeps_rows:
             arrays.insert(0, ("xb", self._xb[:self._n].cpu().numpy()))
-            if self._ivf is not None:
-                arrays += self._ivf.export_arrays()
+        if self._state is not None:                                  # IVFPQ: codes, centroids, codebooks, assignment
+            arrays += self._state.export_arrays()
         header = {"dimension": self.dimension, "index_type": self.index_type, "nlist": self.nlist,
                   "nprobe": self.nprobe, "ntotal": self._n, "identity_ids": self._identity,
                   "arrays": [{"name": n, "dtype": str(a.dtype), "shape": list(a.shape)} for n, a in arrays]}
@@ -410,7 +409,7 @@ class FAISSIndex:
         self._create_index()
         n = header["ntotal"]
         self._reserve(n)
-        if self.index_type != "IVFPQ":
+        if self._keeps_rows:
             self._xb[:n].copy_(torch.from_numpy(arrays["xb"].copy()))
         self._ids[:n].copy_(torch.from_numpy(arrays["ids"].copy()))
         self._n = n
@@ -418,15 +417,9 @@ class FAISSIndex:
         self._identity = header["identity_ids"]
         hid = header.get("host_ids")
         self._host_ids = None if hid is None else [_decode_id(x) for x in hid]
-        if self.index_type == "IVF":
-            from . import ivf
-            self._ivf = ivf.IVFState.from_arrays(arrays, self.device)
-            self._trained = True
-        elif self.index_type == "IVFPQ":
-            from . import ivfpq
-            self._pq = ivfpq.IVFPQState.from_arrays(arrays, self.device)
-            self._ivf = self._pq.ivf
-            self._trained = True
+        cls, _ = self._state_class()
+        if cls is not None:
+            self._set_state(cls.from_arrays(arrays, self.device))
         self._log(f"Index loaded from {filepath}")
         self._log(f"Index size: {self._n}")
 

@@ -1,6 +1,7 @@
 """IVF-Flat state for ``FAISSIndex(index_type='IVF')`` (faiss_retrieval.py:50-55): coarse centroids,
 list assignment, list-contiguous copy of the corpus, and the search driver over libamdrec's
-``amdrec_flat_search`` (coarse probes) + ``amdrec_ivf_group`` + ``amdrec_ivf_scan[_grouped]`` + ``amdrec_ivf_select``.
+``amdrec_ivf_coarse_keys`` (coarse probes) + ``amdrec_ivf_group`` + ``amdrec_ivf_scan[_grouped]`` + ``amdrec_ivf_select``.
+``InvertedLists`` is the coarse level that IVFPQ shares (amdrec.ivfpq holds one); ``IVFState`` adds the fp32 lists' scans.
 
 Build and search are hand-written HIP: assignment = ``amdrec_ivf_assign`` (fp32-MFMA GEMM with an arg-max epilogue),
 training = ``amdrec_ivf_kmeans_step`` x NITER (assignment + order-independent fixed-point centroid sums: training is
@@ -21,7 +22,8 @@ unsharded scan and the merged top-k is bit-identical to the unsharded IVF result
 from __future__ import annotations
 
 import os
-from typing import Optional
+from collections import namedtuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -118,13 +120,31 @@ def grouped_chunk_limit(nlist: int, nprobe: int) -> int:
     return max(1, (room * min(QTILE, QTILE_SPARSE)) // max(1, nprobe))
 
 
-class IVFState:
+class ListLayout(NamedTuple):
+    """The corpus laid out list-contiguously: rows of a list keep insertion order (flagged rows after the others)."""
+    rows: torch.Tensor          # the owner's per-row payload gathered in list order (IVF: fp32 rows, IVFPQ: codes)
+    spos: torch.Tensor          # [n] corpus position of every list-order row (the stable sort's permutation)
+    off: torch.Tensor           # [nlist + 1] first list-order row of every list
+    lens: torch.Tensor          # [nlist] rows per list
+    max_len: int                # the longest list's rows
+    n: int                      # rows laid out
+
+
+# Views of one search workspace (InvertedLists.workspace): [pool | grouping scratch | pair arrays and offsets | extra]
+ScanWorkspace = namedtuple("ScanWorkspace", "keys pool grp pair_q pair_p goff qtp extra")
+
+
+class InvertedLists:
+    """The coarse level shared by IVF-Flat and IVFPQ: centroids, the per-row list assignment, the list layout, the coarse
+    probes, the pool select and the scan workspace.  The only code that touches any of them."""
+
     def __init__(self, centroids: torch.Tensor):
         self.centroids = centroids.contiguous()                    # [nlist, d], unit rows
         self.nlist, self.dim = centroids.shape
+        self.coarse_ld = (self.nlist + 1) // 2 * 2                  # row pitch of the coarse key table
         self.device = centroids.device
         self.assign = torch.empty(0, dtype=torch.int64, device=self.device)   # list of every position
-        self._lists = None                                          # (xs, spos, list_off, list_len, max_len)
+        self.lists: Optional[ListLayout] = None                     # made by layout(), dropped by extend()
         self._top_rows = None                                       # host: rows of the p longest lists (pool_rows_bound)
         self._nlist_count = None                                    # device: nlist per query (the coarse select's pool sizes)
         self._sel_scratch = None                                    # device: amdrec_ivf_select_split's partial lists and tickets
@@ -132,7 +152,7 @@ class IVFState:
 
     # -- build ----------------------------------------------------------------------------
     @classmethod
-    def train(cls, x: torch.Tensor, nlist: int) -> "IVFState":
+    def train(cls, x: torch.Tensor, nlist: int):
         """x: fp32 device copy of the training embeddings (un-normalised, as FAISSIndex.add passes
         them to train(), faiss_retrieval.py:107-108)."""
         x = _normalize(x.float())
@@ -156,40 +176,31 @@ class IVFState:
                                                   cent.stride(0), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
         return cls(cent)
 
-    def append(self, x_normalised: torch.Tensor, start: int):
-        assert start == self.assign.shape[0]
-        self.assign = torch.cat([self.assign, _assign(x_normalised, self.centroids)])
-        self._lists = None
+    def assign_rows(self, x_normalised: torch.Tensor) -> torch.Tensor:
+        """The list of each L2-normalised row (not yet part of the index: ``extend``)."""
+        return _assign(x_normalised, self.centroids)
+
+    def extend(self, assigns):
+        """Append the lists of new rows (``assign_rows`` results, in order): drops the layout and its bound together."""
+        self.assign = torch.cat([self.assign, *assigns])
+        self.lists = None
         self._top_rows = None
 
-    def _build_lists(self, xb: torch.Tensor, n: int):
-        if self._lists is None or self._lists[5] != n:
-            a = self.assign[:n]
-            order = torch.argsort(a, stable=True)                   # rows of a list keep insertion order
-            counts = torch.bincount(a, minlength=self.nlist)
-            off = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
-            off[1:] = torch.cumsum(counts, 0)
-            xs = xb[:n][order].contiguous()
-            self._lists = (xs, order.contiguous(), off, counts.to(torch.int64), int(counts.max().item()) if n else 0, n)
-            self._shadow = None                                     # bf16 copy of xs + its {M, D}: made on first use
-            # rows of the p longest lists, p = 1 .. nlist: the tight host-side bound of a query's candidate pool
-            # (its nprobe probed lists cannot hold more than the nprobe longest; once per list rebuild, like max above)
-            self._top_rows = np.cumsum(np.sort(counts.cpu().numpy())[::-1].astype(np.int64))
-        return self._lists
-
-    def _list_shadow(self):
-        """bf16 (round-to-nearest) copy of the list-contiguous corpus and max_norm = {largest row norm, largest row
-        rounding-error norm} (amdrec_bf16_rows): the operands of the second-phase prefilter."""
-        if getattr(self, "_shadow", None) is None:
-            xs = self._lists[0]
-            n, d = xs.shape
-            xs16 = torch.empty((n, d), dtype=torch.bfloat16, device=self.device)
-            mx = torch.zeros(2, dtype=torch.float32, device=self.device)
-            if n:
-                _lib.check(_lib.load().amdrec_bf16_rows(_lib.ptr(xs), n, xs.stride(0), d, _lib.ptr(xs16), d, _lib.ptr(mx),
-                                                        _lib.stream_ptr(self.device)))
-            self._shadow = (xs16, mx)
-        return self._shadow
+    def layout(self, n: int, rows: torch.Tensor, last: Optional[torch.Tensor] = None) -> ListLayout:
+        """(Re)build the list layout of rows [0, n): one stable sort by list (rows of a list keep insertion order; those
+        flagged in the bool tensor ``last`` go behind the list's others); ``rows`` is the owner's per-row payload in
+        insertion order.  Callers rebuild when ``lists`` is None (rows were added) or was made for another n."""
+        a = self.assign[:n]
+        order = torch.argsort(a if last is None else a * 2 + last[:n].to(torch.int64), stable=True)
+        counts = torch.bincount(a, minlength=self.nlist)
+        off = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
+        off[1:] = torch.cumsum(counts, 0)
+        self.lists = ListLayout(rows[:n][order].contiguous(), order.contiguous(), off, counts.to(torch.int64),
+                                int(counts.max().item()) if n else 0, n)
+        # rows of the p longest lists, p = 1 .. nlist: the tight host-side bound of a query's candidate pool
+        # (its nprobe probed lists cannot hold more than the nprobe longest; once per list rebuild, like max above)
+        self._top_rows = np.cumsum(np.sort(counts.cpu().numpy())[::-1].astype(np.int64))
+        return self.lists
 
     def pool_rows_bound(self, nprobe: int) -> int:
         """Upper bound of the rows a query's ``nprobe`` probed lists hold = the ``nprobe`` longest lists' rows.  Round 2
@@ -199,13 +210,68 @@ class IVFState:
             return 1
         return max(1, int(self._top_rows[min(int(nprobe), len(self._top_rows)) - 1]))
 
-    def _select(self, lib, pool, pool_ld: int, n_pool, m: int, k: int, out_scores, out_pos, stream_ptr):
+    # -- search steps ---------------------------------------------------------------------
+    def coarse_table_bytes(self, nq: int, nprobe: int) -> int:
+        """Bytes of the dense (score, centroid) key table of ``nq`` queries, or 0 when the table does not fit (more than
+        POOL_BYTES, more probes than a select takes, 2^24 queries): the probes then come from the flat search."""
+        nbytes = nq * self.coarse_ld * 8
+        return nbytes if nbytes <= POOL_BYTES and nprobe <= _lib.MAX_K and nq < (1 << 24) else 0
+
+    def coarse_probes(self, q: torch.Tensor, nprobe: int, keys: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """-> int64 [nq, nprobe]: the nprobe best centroids of each query by inner product (IndexFlatIP quantizer; -1 = none).
+        A dense key table (in ``keys``, else in ``coarse_table_bytes`` of the shared workspace) + the pool select, or, when
+        the table does not fit, the flat search."""
+        nq, nbytes = q.shape[0], self.coarse_table_bytes(q.shape[0], nprobe)
+        cs = torch.empty((nq, nprobe), dtype=torch.float32, device=self.device)
+        probes = torch.empty((nq, nprobe), dtype=torch.int64, device=self.device)
+        if nq and not nbytes:
+            from .index import flat_search
+            flat_search(self.centroids, self.nlist, q, nprobe, cs, probes)
+        elif nq:
+            lib = _lib.load()
+            keys = _lib.WORKSPACE.get(nbytes, self.device) if keys is None else keys
+            if self._nlist_count is None or self._nlist_count.numel() < nq:
+                self._nlist_count = torch.full((max(nq, 512),), self.nlist, dtype=torch.int64, device=self.device)
+            _lib.check(lib.amdrec_ivf_coarse_keys(_lib.ptr(self.centroids), self.nlist, self.centroids.stride(0), self.dim,
+                                                  _lib.ptr(q), nq, q.stride(0), _lib.ptr(keys), self.coarse_ld,
+                                                  _lib.stream_ptr(self.device)))
+            _lib.check(lib.amdrec_ivf_select(_lib.ptr(keys), self.coarse_ld, _lib.ptr(self._nlist_count), nq, nprobe,
+                                             _lib.ptr(cs), _lib.ptr(probes), _lib.stream_ptr(self.device)))
+        return probes
+
+    def workspace(self, chunk: int, nprobe: int, pool_ld: int, coarse_bytes: int, extra_bytes: int = 0) -> ScanWorkspace:
+        """One workspace for a search whose scans take ``chunk`` queries at a time, as byte views (int64 for the pair arrays
+        and the two nlist + 1 offset arrays): ``keys`` = the first ``coarse_bytes`` for the coarse key table (None if 0; it is
+        done with before the first scan writes the pool), ``extra`` = the caller's trailing bytes (IVFPQ's distance tables).
+        The C side trusts these sizes."""
+        pairs, r256 = chunk * nprobe, lambda b: (b + 255) // 256 * 256      # noqa: E731
+        pool_bytes = r256(chunk * pool_ld * 8)
+        arr0 = pool_bytes + r256((self.nlist + 1) * 4) + r256(pairs * 4)
+        extra0 = arr0 + r256(2 * pairs * 8 + 2 * (self.nlist + 1) * 8)
+        ws = _lib.WORKSPACE.get(max(extra0 + extra_bytes + 256, coarse_bytes), self.device)
+        arr = ws[arr0:extra0].view(torch.int64)
+        goff = 2 * pairs
+        return ScanWorkspace(ws[:coarse_bytes] if coarse_bytes else None, ws[:pool_bytes], ws[pool_bytes:arr0],
+                             arr[:pairs], arr[pairs:goff], arr[goff:goff + self.nlist + 1],
+                             arr[goff + self.nlist + 1:goff + 2 * (self.nlist + 1)], ws[extra0:extra0 + extra_bytes])
+
+    def group(self, w: ScanWorkspace, probes: torch.Tensor, probe_ld: int, m: int, ncol: int, base: torch.Tensor,
+              n_out: torch.Tensor, qtile: int):
+        """amdrec_ivf_group: pool slots (``base``, ``n_out``) of the first ``ncol`` probe columns of ``m`` queries and
+        their (query, probe) pairs grouped by list in tiles of ``qtile`` queries (kernels, no host sync)."""
+        _lib.check(_lib.load().amdrec_ivf_group(
+            _lib.ptr(probes), probe_ld, m, ncol, self.nlist, _lib.ptr(self.lists.lens), _lib.ptr(base), _lib.ptr(n_out),
+            _lib.ptr(w.pair_q), _lib.ptr(w.pair_p), _lib.ptr(w.goff), _lib.ptr(w.qtp), qtile, _lib.ptr(w.grp), w.grp.numel(),
+            _lib.stream_ptr(self.device)))
+
+    def select(self, pool, pool_ld: int, n_pool, m: int, k: int, out_scores, out_pos):
         """The k best keys of each query's pool.  Few queries with large pools (one request against nlist 100 / nprobe 10:
         100 000 keys) are selected by several workgroups per query (``amdrec_ivf_select_split``), everything else by one."""
+        lib = _lib.load()
         slices = min(SELECT_MAX_SLICES, pool_ld // SELECT_SLICE_KEYS, 1024 // max(1, m))
         if slices < 4:
             _lib.check(lib.amdrec_ivf_select(_lib.ptr(pool), pool_ld, _lib.ptr(n_pool), m, k, _lib.ptr(out_scores),
-                                             _lib.ptr(out_pos), stream_ptr))
+                                             _lib.ptr(out_pos), _lib.stream_ptr(self.device)))
             return
         need = m * slices * k * 8
         if self._sel_scratch is None or self._sel_scratch.numel() < need:
@@ -214,12 +280,61 @@ class IVFState:
             self._sel_tickets = torch.zeros(max(m, 1024), dtype=torch.int32, device=self.device)   # the kernel leaves them zero
         _lib.check(lib.amdrec_ivf_select_split(_lib.ptr(pool), pool_ld, _lib.ptr(n_pool), m, k, slices, _lib.ptr(out_scores),
                                                _lib.ptr(out_pos), _lib.ptr(self._sel_scratch), self._sel_scratch.numel(),
-                                               _lib.ptr(self._sel_tickets), stream_ptr))
+                                               _lib.ptr(self._sel_tickets), _lib.stream_ptr(self.device)))
+
+    def resident_tensors(self) -> list:
+        """Every device tensor kept between calls (a captured graph's kernels point at them)."""
+        kept = [self.centroids, self.assign, self._nlist_count, self._sel_scratch, self._sel_tickets, *(self.lists or ())]
+        return [t for t in kept if isinstance(t, torch.Tensor)]
+
+    # -- persistence ----------------------------------------------------------------------
+    def export_arrays(self):
+        return [("ivf_centroids", self.centroids.cpu().numpy()), ("ivf_assign", self.assign.cpu().numpy())]
+
+    @classmethod
+    def from_arrays(cls, arrays, device):
+        st = cls(torch.from_numpy(np.array(arrays["ivf_centroids"])).to(device))
+        st.assign = torch.from_numpy(np.array(arrays["ivf_assign"])).to(device)
+        return st
+
+
+class IVFState(InvertedLists):
+    """IVF-Flat: the lists hold the fp32 rows; second phases may run on a bf16 shadow of them."""
+
+    def __init__(self, centroids: torch.Tensor):
+        super().__init__(centroids)
+        self._shadow = None                                         # (bf16 copy of lists.rows, its {M, D}): made on first use
+
+    def append(self, x_normalised: torch.Tensor, start: int):
+        assert start == self.assign.shape[0]
+        self.extend([self.assign_rows(x_normalised)])
+
+    def _build_lists(self, xb: torch.Tensor, n: int) -> ListLayout:
+        if self.lists is None or self.lists.n != n:
+            self.layout(n, xb)
+            self._shadow = None
+        return self.lists
+
+    def _list_shadow(self):
+        """bf16 (round-to-nearest) copy of the list-contiguous corpus and max_norm = {largest row norm, largest row
+        rounding-error norm} (amdrec_bf16_rows): the operands of the second-phase prefilter."""
+        if self._shadow is None:
+            xs = self.lists.rows
+            n, d = xs.shape
+            xs16 = torch.empty((n, d), dtype=torch.bfloat16, device=self.device)
+            mx = torch.zeros(2, dtype=torch.float32, device=self.device)
+            if n:
+                _lib.check(_lib.load().amdrec_bf16_rows(_lib.ptr(xs), n, xs.stride(0), d, _lib.ptr(xs16), d, _lib.ptr(mx),
+                                                        _lib.stream_ptr(self.device)))
+            self._shadow = (xs16, mx)
+        return self._shadow
+
+    def resident_tensors(self) -> list:
+        return super().resident_tensors() + list(self._shadow or ())
 
     # -- search ---------------------------------------------------------------------------
     def search(self, xb: torch.Tensor, n: int, q: torch.Tensor, k: int, nprobe: int, out_scores: torch.Tensor,
                out_pos: torch.Tensor, pos_offset: int = 0):
-        from .index import flat_search
         lib = _lib.load()
         nq = q.shape[0]
         if nq == 0:
@@ -228,13 +343,8 @@ class IVFState:
             out_scores.fill_(float("-inf"))
             out_pos.fill_(-1)
             return
-        xs, spos, off, lens, max_len, _ = self._build_lists(xb, n)
+        xs, spos, off, _, max_len, _ = self._build_lists(xb, n)
         nprobe = search_nprobe(nprobe, self.nlist)
-        # 1. coarse quantizer: nprobe best centroids by inner product (IndexFlatIP quantizer) = a dense (score, centroid)
-        #    key table + the pool select (step 4's kernel); runs below, once the workspace is sized
-        cs = torch.empty((nq, nprobe), dtype=torch.float32, device=self.device)
-        probes = torch.empty((nq, nprobe), dtype=torch.int64, device=self.device)
-        # 2. pool layout + (query, probe) pairs grouped by list: amdrec_ivf_group (kernels, no host sync)
         base = torch.empty((nq, nprobe), dtype=torch.int64, device=self.device)
         n_pool = torch.empty((nq,), dtype=torch.int64, device=self.device)
         pool_ld = self.pool_rows_bound(nprobe)
@@ -243,30 +353,10 @@ class IVFState:
         qtile = QTILE_SPARSE if min(chunk, nq) * nprobe < SPARSE_PAIRS_PER_LIST * self.nlist else QTILE
         if grouped:
             chunk = min(chunk, grouped_chunk_limit(self.nlist, nprobe))
-        # one workspace: [candidate pool | grouping scratch | pair arrays and offsets]
-        pool_bytes = (chunk * pool_ld * 8 + 255) // 256 * 256
-        grp_bytes = ((self.nlist + 1) * 4 + 255) // 256 * 256 + (chunk * nprobe * 4 + 255) // 256 * 256
-        arr_bytes = 2 * chunk * nprobe * 8 + 2 * (self.nlist + 1) * 8
-        coarse_ld = (self.nlist + 1) // 2 * 2
-        coarse = nq * coarse_ld * 8 <= POOL_BYTES and nprobe <= _lib.MAX_K and nq < (1 << 24)
-        wsall = _lib.WORKSPACE.get(max(pool_bytes + grp_bytes + arr_bytes + 256, nq * coarse_ld * 8 if coarse else 0),
-                                   self.device)
-        if coarse:                                     # the key table lives in the pool's memory: the scans come after it
-            if self._nlist_count is None or self._nlist_count.numel() < nq:
-                self._nlist_count = torch.full((max(nq, 512),), self.nlist, dtype=torch.int64, device=self.device)
-            _lib.check(lib.amdrec_ivf_coarse_keys(_lib.ptr(self.centroids), self.nlist, self.centroids.stride(0), self.dim,
-                                                  _lib.ptr(q), nq, q.stride(0), _lib.ptr(wsall), coarse_ld,
-                                                  _lib.stream_ptr(self.device)))
-            _lib.check(lib.amdrec_ivf_select(_lib.ptr(wsall), coarse_ld, _lib.ptr(self._nlist_count), nq, nprobe,
-                                             _lib.ptr(cs), _lib.ptr(probes), _lib.stream_ptr(self.device)))
-        else:
-            flat_search(self.centroids, self.nlist, q, nprobe, cs, probes)
-        ws = wsall[:pool_bytes]
-        grp = wsall[pool_bytes:pool_bytes + grp_bytes]
-        arr = wsall[pool_bytes + grp_bytes:pool_bytes + grp_bytes + arr_bytes].view(torch.int64)
-        pair_q, pair_p = arr[:chunk * nprobe], arr[chunk * nprobe:2 * chunk * nprobe]
-        goff = arr[2 * chunk * nprobe:2 * chunk * nprobe + self.nlist + 1]
-        qtp = arr[2 * chunk * nprobe + self.nlist + 1:]
+        w = self.workspace(chunk, nprobe, pool_ld, self.coarse_table_bytes(nq, nprobe))
+        ws, pair_q, pair_p, goff, qtp = w.pool, w.pair_q, w.pair_p, w.goff, w.qtp
+        # 1. coarse quantizer: nprobe best centroids per query (key table in the workspace, or the flat search)
+        probes = self.coarse_probes(q, nprobe, w.keys)
         st = lambda: _lib.stream_ptr(self.device)      # noqa: E731  (per call: check() ends the call's device scope)
 
         def group_and_scan(s, m, col0, ncol, tau=None, fill=None, n_out=None):
@@ -276,10 +366,8 @@ class IVFState:
             if os.environ.get("AMDREC_IVF_QTILE"):                       # A/B runs: "32", "64", or "first,second" per phase
                 f = os.environ["AMDREC_IVF_QTILE"].split(",")
                 qt = int(f[0] if (tau is None or len(f) == 1) else f[1])
-            pv = probes[s:, col0:]
-            _lib.check(lib.amdrec_ivf_group(_lib.ptr(pv), nprobe, m, ncol, self.nlist, _lib.ptr(lens), _lib.ptr(base[s:]),
-                                            _lib.ptr(n_out), _lib.ptr(pair_q), _lib.ptr(pair_p), _lib.ptr(goff),
-                                            _lib.ptr(qtp), qt, _lib.ptr(grp), grp.numel(), st()))
+            # 2. pool layout + (query, probe) pairs grouped by list
+            self.group(w, probes[s:, col0:], nprobe, m, ncol, base[s:], n_out, qt)
             if tau is not None and mixed:
                 # bf16 prefilter: tau_lo = tau - eps_q, nominate on the bf16 shadow, re-score the nominated rows in fp32
                 _lib.check(lib.amdrec_ivf_filter_bounds(_lib.ptr(q[s:]), m, q.stride(0), self.dim, _lib.ptr(q16[s:]), q16.stride(0),
@@ -313,25 +401,13 @@ class IVFState:
             m = min(chunk, nq - s)
             if two_phase:
                 group_and_scan(s, m, 0, n_first, n_out=n_pool[s:])
-                self._select(lib, ws, pool_ld, n_pool[s:], m, k, out_scores[s:], out_pos[s:], st())
+                self.select(ws, pool_ld, n_pool[s:], m, k, out_scores[s:], out_pos[s:])
                 group_and_scan(s, m, n_first, nprobe - n_first, tau=out_scores[s:, k - 1], fill=n_pool[s:], n_out=scratch_n)
             elif grouped:
                 group_and_scan(s, m, 0, nprobe, n_out=n_pool[s:])
             else:
-                _lib.check(lib.amdrec_ivf_group(_lib.ptr(probes[s:]), nprobe, m, nprobe, self.nlist, _lib.ptr(lens),
-                                                _lib.ptr(base[s:]), _lib.ptr(n_pool[s:]), _lib.ptr(pair_q), _lib.ptr(pair_p),
-                                                _lib.ptr(goff), _lib.ptr(qtp), qtile, _lib.ptr(grp), grp.numel(), st()))
+                self.group(w, probes[s:], nprobe, m, nprobe, base[s:], n_pool[s:], qtile)
                 _lib.check(lib.amdrec_ivf_scan(_lib.ptr(xs), xs.stride(0), self.dim, _lib.ptr(spos), _lib.ptr(off),
                                                _lib.ptr(q[s:]), m, q.stride(0), _lib.ptr(probes[s:]),
                                                _lib.ptr(base[s:]), nprobe, _lib.ptr(ws), pool_ld, pos_offset, st()))
-            self._select(lib, ws, pool_ld, n_pool[s:], m, k, out_scores[s:], out_pos[s:], st())
-
-    # -- persistence ----------------------------------------------------------------------
-    def export_arrays(self):
-        return [("ivf_centroids", self.centroids.cpu().numpy()), ("ivf_assign", self.assign.cpu().numpy())]
-
-    @classmethod
-    def from_arrays(cls, arrays, device) -> "IVFState":
-        st = cls(torch.from_numpy(np.array(arrays["ivf_centroids"])).to(device))
-        st.assign = torch.from_numpy(np.array(arrays["ivf_assign"])).to(device)
-        return st
+            self.select(ws, pool_ld, n_pool[s:], m, k, out_scores[s:], out_pos[s:])

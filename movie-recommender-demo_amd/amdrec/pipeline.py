@@ -423,13 +423,10 @@ class GraphedRecommender:
             with torch.cuda.graph(self._graph):
                 self._out = rec.recommend_device(self._uc, self._un, top_k, stage1_k)
         torch.cuda.synchronize(dev)
-        # pin every device buffer the kernel nodes point at: a later load_state_dict / index.add() then
-        # makes the graph stale (documented) but can never leave it with dangling pointers
-        idx = rec.faiss_index
-        self._pinned = (rec.two_tower_model.user_tower._packed, rec.transformer_ranker._packed, idx._xb, idx._ids,
-                        idx._xb16, idx._maxnorm, rec.ad_features, rec.transformer_ranker._ad_cache, getattr(idx, "_ivf", None) and idx._ivf._lists,
-                        getattr(idx, "_ivf", None) and getattr(idx._ivf, "_shadow", None),
-                        getattr(idx, "_pq", None) and (idx._pq._lists, idx._pq.codebooks))
+        # pin every device buffer the kernel nodes point at: a later load_state_dict / index.add() / larger eager search
+        # then makes the graph stale (documented) but can never leave it with dangling pointers
+        self._pinned = (rec.two_tower_model.user_tower._packed, rec.transformer_ranker._packed, rec.ad_features,
+                        rec.transformer_ranker._ad_cache, *rec.faiss_index.resident_tensors())
 
     @torch.no_grad()
     def __call__(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor):

@@ -216,6 +216,91 @@ def test_ivf_scan_choice_by_pairs_per_list():
     assert ivf.use_grouped_scan(16, 16, 37)
 
 
+@pytest.mark.parametrize("n", [0, 1, 5000])
+@pytest.mark.parametrize("flagged", [False, True])
+def test_inverted_list_layout_is_the_stable_sort_by_list_then_flag(n, flagged):
+    """amdrec.ivf.InvertedLists.layout on CPU tensors against a plain numpy restatement: order = stable sort by (list, flag),
+    offsets / lengths / longest list, the payload gathered in that order, and pool_rows_bound(p) = rows of the p longest
+    lists (at least 1: a pool is never sized 0).  40 lists of which a third stay empty."""
+    from amdrec import ivf
+    nlist, rng = 40, np.random.default_rng(7 + n)
+    assign = rng.choice(np.arange(nlist)[np.arange(nlist) % 3 != 1], size=n).astype(np.int64)
+    flag = rng.random(n) < 0.3
+    rows = rng.integers(0, 255, size=(n, 4)).astype(np.uint8)
+    st = ivf.InvertedLists(torch.zeros((nlist, 8)))
+    st.extend([torch.from_numpy(assign[:n // 2]), torch.from_numpy(assign[n // 2:])])
+    assert st.lists is None and st.pool_rows_bound(3) == 1
+    lay = st.layout(n, torch.from_numpy(rows), last=torch.from_numpy(flag) if flagged else None)
+    assert lay is st.lists and len(lay) == 6 and lay[3] is lay.lens and lay[4] == lay.max_len   # the shape bench.py unpacks
+    order = np.lexsort((np.arange(n), flag if flagged else np.zeros(n, bool), assign))         # last key is the primary one
+    lens = np.bincount(assign, minlength=nlist)
+    assert np.array_equal(lay.spos.numpy(), order) and np.array_equal(lay.rows.numpy(), rows[order])
+    assert np.array_equal(lay.lens.numpy(), lens) and lay.lens.dtype == torch.int64
+    assert np.array_equal(lay.off.numpy(), np.concatenate([[0], np.cumsum(lens)]))
+    assert lay.max_len == (lens.max() if n else 0) and lay.n == n
+    longest = np.sort(lens)[::-1]
+    for p in (1, 2, nlist, nlist + 5):
+        assert st.pool_rows_bound(p) == max(1, int(longest[:p].sum()))
+    st.extend([torch.zeros(3, dtype=torch.int64)])                       # new rows drop the layout and the bound together
+    assert st.lists is None and st.pool_rows_bound(nlist) == 1 and st.assign.shape[0] == n + 3
+
+
+@pytest.mark.parametrize("chunk, nprobe, nlist, pool_ld, nq, extra", [
+    (1, 10, 100, 100_000, 1, None),                 # IVF, one request (pair scan)
+    (64, 10, 100, 100_000, 64, None),               # IVF, grouped
+    (406, 64, 4096, 660_000, 512, None),            # IVF, 10M rows: two chunks of the 2 GB pool
+    (7, 3, 16, 600, 45, 7 * 3 * 8 * 256 * 4),       # IVFPQ, m = 8, small chunks
+    (512, 64, 4096, 20_000, 512, 512 * 64 * 32 * 256 * 4),   # IVFPQ, m = 32: 1 GiB of tables
+    (3, 5, 7, 11, 3000, 0),                         # odd sizes; the key table is the larger request
+])
+def test_scan_workspace_views_sit_where_the_search_drivers_put_them(chunk, nprobe, nlist, pool_ld, nq, extra):
+    """amdrec.ivf.InvertedLists.workspace: views disjoint, inside the allocation, at the byte offsets and with the
+    numel() of the arithmetic both search drivers carried before they shared it (restated below; extra None = IVF-Flat's
+    form, whose pair arrays were not rounded up to 256 bytes and whose last view was the unbounded tail - the same
+    nlist + 1 elements - so its request was up to 248 bytes shorter)."""
+    from amdrec import _lib, ivf
+    st = ivf.InvertedLists(torch.zeros((nlist, 8)))
+    coarse_ld = (nlist + 1) // 2 * 2
+    coarse = nq * coarse_ld * 8
+    assert st.coarse_table_bytes(nq, nprobe) == coarse
+    assert st.coarse_table_bytes(nq, _lib.MAX_K + 1) == 0 and st.coarse_table_bytes(1 << 24, nprobe) == 0
+    assert st.coarse_table_bytes(ivf.POOL_BYTES // (coarse_ld * 8) + 1, nprobe) == 0
+    pool_bytes = (chunk * pool_ld * 8 + 255) // 256 * 256
+    grp_bytes = ((nlist + 1) * 4 + 255) // 256 * 256 + (chunk * nprobe * 4 + 255) // 256 * 256
+    arr_bytes = 2 * chunk * nprobe * 8 + 2 * (nlist + 1) * 8
+    if extra is None:
+        request = max(pool_bytes + grp_bytes + arr_bytes + 256, coarse)
+    else:
+        arr_bytes = (arr_bytes + 255) // 256 * 256
+        request = max(pool_bytes + grp_bytes + arr_bytes + extra + 256, coarse)
+    a0 = pool_bytes + grp_bytes
+    want = {"pool": (0, pool_bytes, 1), "grp": (pool_bytes, grp_bytes, 1),
+            "pair_q": (a0, chunk * nprobe, 8), "pair_p": (a0 + chunk * nprobe * 8, chunk * nprobe, 8),
+            "goff": (a0 + 2 * chunk * nprobe * 8, nlist + 1, 8),
+            "qtp": (a0 + 2 * chunk * nprobe * 8 + (nlist + 1) * 8, nlist + 1, 8),
+            "extra": (a0 + (arr_bytes + 255) // 256 * 256, extra or 0, 1)}
+
+    class Meta:                                                # records the requests; hands out storage-free tensors
+        asked = []
+
+        def get(self, nbytes, device):
+            self.asked.append(nbytes)
+            return torch.empty(nbytes, dtype=torch.uint8, device="meta")
+    arena = Meta()
+    with _lib.WORKSPACE.private(arena):
+        w = st.workspace(chunk, nprobe, pool_ld, coarse, **({} if extra is None else {"extra_bytes": extra}))
+        assert st.workspace(chunk, nprobe, pool_ld, 0).keys is None
+    assert request <= arena.asked[0] < request + 256
+    assert w.keys.storage_offset() == 0 and w.keys.numel() == coarse
+    spans = []
+    for name, (off, numel, size) in want.items():
+        v = getattr(w, name)
+        assert (v.storage_offset() * v.element_size(), v.numel(), v.element_size()) == (off, numel, size), name
+        assert v.is_contiguous()
+        spans.append((off, off + numel * size))
+    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])) and spans[-1][1] <= arena.asked[0]
+
+
 def test_a_replaced_parameter_object_changes_the_packing_cache_key():
     """the drop-ins key their packed weights on the tensors' `_version`s, read from a cached tensor list; a
     Parameter REPLACED without `invalidate()` used to leave the stale list in place for ever (in-place updates of the new

@@ -177,6 +177,30 @@ def test_ivf_pipeline_captures_in_a_hip_graph():
         out = g(uc, un)
         torch.cuda.synchronize()
         assert torch.equal(out["ad_ids"], ids) and torch.equal(out["scores"], sc)
+        assert_replay_survives_a_larger_eager_search(rec, g, uc, un, user, nnum)
+
+
+def assert_replay_survives_a_larger_eager_search(rec, g, uc, un, user, nnum):
+    """The replay object holds every device tensor the index keeps between calls, so an eager search that outgrows (and
+    re-allocates) the coarse level's per-query scratch leaves the captured kernels' buffers alive: replay == eager."""
+    idx = rec.faiss_index
+    held = {t.data_ptr() for t in g._pinned if isinstance(t, torch.Tensor)}
+    resident = idx.resident_tensors()
+    assert resident and all(isinstance(t, torch.Tensor) for t in resident)
+    assert {t.data_ptr() for t in resident} <= held
+    counts = idx._ivf._nlist_count
+    assert counts is not None and counts.data_ptr() in held        # read by the captured coarse select
+    big = counts.numel() + 1
+    bc, bn = synth.user_batch(user, nnum, big, seed=91)
+    rec.recommend_device(torch.from_numpy(bc).cuda(), torch.from_numpy(bn).cuda(), 10, 200)
+    torch.cuda.synchronize()
+    assert idx._ivf._nlist_count.data_ptr() != counts.data_ptr() and idx._ivf._nlist_count.numel() >= big
+    out = g(uc, un)
+    torch.cuda.synchronize()
+    eager = rec.recommend_device(uc, un, 10, 200)
+    assert torch.equal(out["ad_ids"], eager["ad_ids"]) and torch.equal(out["scores"], eager["scores"])
+    assert torch.equal(out["candidate_ids"], eager["candidate_ids"])
+    assert torch.equal(out["candidate_scores"], eager["candidate_scores"])
 
 
 @pytest.mark.parametrize("copies", [1500, 6000])

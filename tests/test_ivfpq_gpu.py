@@ -275,6 +275,7 @@ def _setup_pq(n_ads=20_000):
 
 def test_ivfpq_pipeline_captures_in_a_hip_graph_and_refuses_sharding():
     from amdrec.sharded import ShardedRecommender
+    from tests.test_ivf_gpu import assert_replay_survives_a_larger_eager_search
     rec, _, (user, ad, nnum) = _setup_pq()
     assert rec.faiss_index.index_type == "IVFPQ"
     for B in (4, 32):
@@ -289,6 +290,7 @@ def test_ivfpq_pipeline_captures_in_a_hip_graph_and_refuses_sharding():
         torch.cuda.synchronize()
         assert torch.equal(out["ad_ids"], ids) and torch.equal(out["scores"], sc)
         assert torch.equal(out["candidate_ids"], cids) and torch.equal(out["candidate_scores"], cd)
+        assert_replay_survives_a_larger_eager_search(rec, g, uc, un, user, nnum)
     with pytest.raises(NotImplementedError):
         ShardedRecommender(rec, rank=0, world=1, shard_offset=0)
 

@@ -214,7 +214,7 @@ def test_ivfpq_small_query_chunks_and_the_coarse_fallback(monkeypatch):
     """TABLE_BYTES forced to 7 queries per chunk (ragged last chunk, boundaries off the 32-query tile), then POOL_BYTES
     forced below the coarse key table (the flat-search fallback picks the probes): positions and distance bits equal the
     unchunked search, and the fallback's probes equal the key table's."""
-    from amdrec import ivfpq
+    from amdrec import ivf, ivfpq
     idx, _ = _index(64, 8, n=3000, nlist=16, nprobe=3)
     k, nq, nprobe = 50, 45, 3
     qn = _normalized_on_device(idx, _clustered(nq, 64, 20, 5))
@@ -224,7 +224,8 @@ def test_ivfpq_small_query_chunks_and_the_coarse_fallback(monkeypatch):
     _bits_equal(idx.search_device(qn, k, normalize=False, return_positions=True), ref)
     monkeypatch.undo()
     coarse_ld = (idx.nlist + 1) // 2 * 2
-    monkeypatch.setattr(ivfpq, "POOL_BYTES", nq * coarse_ld * 8 - 8)
+    monkeypatch.setattr(ivf, "POOL_BYTES", nq * coarse_ld * 8 - 8)     # InvertedLists.coarse_table_bytes reads it
+    assert idx._pq.ivf.coarse_table_bytes(nq, nprobe) == 0
     assert torch.equal(idx._pq.coarse_probes(qn, nprobe), ref_probes)
     _bits_equal(idx.search_device(qn, k, normalize=False, return_positions=True), ref)
 

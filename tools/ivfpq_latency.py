@@ -52,12 +52,11 @@ def resident_bytes(idx):
     and the vectors (IVF-Flat: the fp32 rows, their list-contiguous copy and, if built, its bf16 shadow) or the codes
     (IVFPQ: in insertion order and list-contiguous, and the per-row finite flags).  Centroids, codebooks and workspaces are
     per index, not per ad."""
+    lists = idx._ivf.lists
+    per_list = () if lists is None else (lists.rows, lists.spos, lists.off, lists.lens)
     if idx._pq is not None:
-        lists = idx._pq._lists or ()
-        return nbytes(idx._ids, idx._pq.codes, idx._pq.finite, idx._pq.assign, *lists[:4])
-    lists = idx._ivf._lists or ()
-    shadow = getattr(idx._ivf, "_shadow", None) or ()
-    return nbytes(idx._ids, idx._xb, idx._ivf.assign, *lists[:4], *shadow)
+        return nbytes(idx._ids, idx._pq.codes, idx._pq.finite, idx._pq.assign, *per_list)
+    return nbytes(idx._ids, idx._xb, idx._ivf.assign, *per_list, *(idx._ivf._shadow or ()))
 
 
 def recall(ids, ref):
