@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define AMDREC_ABI_VERSION 13
+#define AMDREC_ABI_VERSION 14
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -191,6 +191,20 @@ int amdrec_ivfpq_scan_finite(const uint8_t* codes, int m, const int64_t* row_pos
                              int64_t npairs, uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset, void* stream);
 int amdrec_ivfpq_distances(const float* scores /*[nq][k]*/, int64_t nq, int k, float* distances /*[nq][k], may alias*/,
                            void* stream);
+/* Refine (ABI v14; faiss IndexRefineFlat over the IVFPQ index): re-rank each query's kc candidates (corpus positions as
+ * amdrec_ivf_select writes them, -1 = unfilled, distinct within a query) by the exact squared L2 distance sum_i (q_i - x_i)^2
+ * in fp32 to the kept row x = rows[pos] (fp32, or with rows_bf16 = 1 bf16 widened to fp32), and write the k <= kc best:
+ * out_dist ascending (ties -> lower position), out_pos = position + pos_offset.  A row with finite[pos] == 0 (finite may be
+ * NULL: every row finite), or whose distance is NaN, gets +inf and ranks after every finite row, by position; unfilled
+ * candidates and positions outside [0, nrows) come last as +inf / -1.  A row's distance is evaluated in one fixed order: it
+ * does not depend on nq, on the other candidates or on the launch shape.  1 <= k <= kc <= AMDREC_MAX_K, dim % 4 == 0
+ * (% 8 for bf16 rows), nq <= 65535.  Few queries are split over several workgroups each when the caller gives
+ * `workspace` (>= nq * kc * 8 bytes) and `tickets` (int32 [nq], zero on entry, zero again on return); both may be NULL. */
+int amdrec_ivfpq_rerank(const void* rows, int rows_bf16, int64_t nrows, int64_t ld_rows, int dim,
+                        const uint8_t* finite /*[nrows] or NULL*/, const float* queries, int64_t nq, int64_t ld_queries,
+                        const int64_t* cand_pos /*[nq][kc]*/, int kc, int64_t pos_offset, int k,
+                        float* out_dist /*[nq][k]*/, int64_t* out_pos /*[nq][k]*/, void* workspace, size_t workspace_bytes,
+                        int32_t* tickets, void* stream);
 
 /* Cross-shard merge (absent in the single-device reference): for queries
  * [q0, q0+nq) merge n_lists per-shard top-k lists (scores/positions of list g start

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # AMDREC_LIB_PATH: developer override for A/B runs of two builds of the library in otherwise identical processes
 LIB_PATH = os.environ.get("AMDREC_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "lib", "libamdrec.so")
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 MAX_K = 2048
 
 
@@ -58,6 +58,8 @@ _SIGNATURES = {
     "amdrec_ivfpq_scan_finite": [_vp, _i32, _vp, _vp, _vp, _i32, _i64, _fp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp,
                                  _i64, _i64, _vp],
     "amdrec_ivfpq_distances": [_fp, _i64, _i32, _fp, _vp],
+    "amdrec_ivfpq_rerank": [_vp, _i32, _i64, _i64, _i32, _vp, _fp, _i64, _i64, _vp, _i32, _i64, _i32, _fp, _vp, _vp, _sz, _vp,
+                            _vp],
     "amdrec_topk_merge": [_fp, _vp, _i32, _i64, _i64, _i64, _i32, _fp, _vp, _vp],
     "amdrec_topk_merge_partial": [_fp, _vp, _i32, _i32, _i64, _i64, _i64, _i32, _fp, _vp, _vp, _vp],
     "amdrec_tower_workspace": [_vp, _i64, C.POINTER(_sz)],

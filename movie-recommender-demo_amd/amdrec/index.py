@@ -12,7 +12,8 @@ Layout in HBM: corpus ``[capacity, dimension]`` float32 row-major, rows L2-norma
 ``add`` time, 1 KiB per row at d=256 (1.024 GB per 1M ads: the whole 10M corpus of
 BASELINE config 4 is 10.24 GB, 3.6 % of one MI355X's 288 GB); ids int64 ``[capacity]``.
 An IVFPQ index keeps no fp32 corpus: ``pq_m`` bytes of codes per row plus the row's list (amdrec.ivfpq), and its
-``search`` returns approximate squared L2 distances (ascending), faiss IndexIVFPQ's default metric.
+``search`` returns approximate squared L2 distances (ascending), faiss IndexIVFPQ's default metric.  With ``refine`` it also
+keeps every normalised row (fp32 or bf16, insertion order) and re-ranks the codes' candidates by exact distance.
 """
 from __future__ import annotations
 
@@ -83,12 +84,17 @@ class _Handle:
 
 class FAISSIndex:
     def __init__(self, dimension: int, index_type: str = "IVF", nlist: int = 100, nprobe: int = 10,
-                 use_gpu: bool = False, device=None, verbose: bool = False, prefilter: str = "bf16", pq_m: int = 8):
+                 use_gpu: bool = False, device=None, verbose: bool = False, prefilter: str = "bf16", pq_m: int = 8,
+                 refine: Optional[str] = None, refine_factor: int = 4):
         """``use_gpu`` is accepted for signature compatibility; the index always lives on the
         HIP device (``device`` or the current one) - there is no CPU engine.
         ``prefilter`` (Flat only): "bf16" keeps a bf16 copy of the corpus next to the fp32 one and searches with
         amdrec_flat_search_mixed (bf16 MFMA filter, fp32 re-score, certified exact); "fp32" = amdrec_flat_search.
-        ``pq_m`` (IVFPQ only): sub-quantizers of 8 bits each, 4 / 8 / 16 / 32; 8 is the reference's value."""
+        ``pq_m`` (IVFPQ only): sub-quantizers of 8 bits each, 4 / 8 / 16 / 32; 8 is the reference's value.
+        ``refine`` (IVFPQ only): None = codes only; "fp32" / "bf16" also keep every normalised row in that format (1024 /
+        512 bytes per ad at d = 256; "bf16" needs dimension % 8 == 0) and a search for k re-ranks the
+        min(k * ``refine_factor``, 2048) best candidates of the code scan by their exact squared L2 distance to the kept row
+        (for "bf16": to the bf16-rounded row), as faiss's IndexRefineFlat does.  The clamp to 2048 (AMDREC_MAX_K) is silent."""
         if prefilter not in ("bf16", "fp32"):
             raise ValueError("prefilter must be 'bf16' or 'fp32'")
         self.prefilter = prefilter
@@ -97,6 +103,7 @@ class FAISSIndex:
         self.nlist = int(nlist)
         self.nprobe = int(nprobe)
         self.pq_m = int(pq_m)
+        self.refine, self.refine_factor = refine, refine_factor
         self.use_gpu = use_gpu
         self.verbose = verbose
         self.device = torch.device(device if device is not None else "cuda")
@@ -114,6 +121,7 @@ class FAISSIndex:
         if self.index_type == "IVFPQ":
             ivfpq.check_pq_m(self.dimension, self.pq_m)
             ivfpq.check_nlist(self.nlist)
+        ivfpq.check_refine(self.index_type, self.dimension, self.refine, self.refine_factor)
         _lib.load()
         self._xb = torch.empty((0, self.dimension), dtype=torch.float32, device=self.device)
         self._ids = torch.empty((0,), dtype=torch.int64, device=self.device)
@@ -173,7 +181,8 @@ class FAISSIndex:
 
     def _state_class(self):
         """-> (class of the trained state behind this index type, its train() arguments after nlist); (None, ()) for Flat."""
-        return {"IVF": (ivf.IVFState, ()), "IVFPQ": (ivfpq.IVFPQState, (self.pq_m,))}.get(self.index_type, (None, ()))
+        return {"IVF": (ivf.IVFState, ()),
+                "IVFPQ": (ivfpq.IVFPQState, (self.pq_m, self.refine, self.refine_factor))}.get(self.index_type, (None, ()))
 
     def _set_state(self, state):
         self._state = state
@@ -236,8 +245,9 @@ class FAISSIndex:
         m = src.shape[0]
         self._reserve(self._n + m)
         if not self._keeps_rows:
-            # normalised and encoded batch by batch: only the codes stay.  Nothing is committed to the PQ state before the
-            # ids below are accepted (a rejected add must leave the index as it was)
+            # normalised and encoded batch by batch: only the codes stay (and, with refine, the kept form of the rows).
+            # Nothing is committed to the PQ state before the ids below are accepted (a rejected add must leave the index
+            # as it was)
             pq_new = [self._pq.encode_rows(self._normalize_(
                 src[b:b + ADD_BATCH].to(device=self.device, dtype=torch.float32, copy=True).contiguous()))
                 for b in range(0, m, ADD_BATCH)]
@@ -293,7 +303,7 @@ class FAISSIndex:
         """Device-to-device search, asynchronous on the current stream.
         -> (ids int64 [nq,k], scores float32 [nq,k]) on the device.  ``return_positions``: corpus
         positions (+ ``pos_offset``, the shard's first global row) instead of ids, -1 = unfilled.
-        IVFPQ: the scores are approximate squared L2 distances, ascending (+inf = unfilled)."""
+        IVFPQ: the scores are squared L2 distances, ascending (+inf = unfilled): approximate, or exact with refine."""
         q = _lib.require_gpu(queries, "queries")
         if q.dim() != 2 or q.shape[1] != self.dimension:
             raise ValueError(f"expected [nq, {self.dimension}] queries, got {tuple(q.shape)}")
@@ -376,6 +386,8 @@ class FAISSIndex:
                   "arrays": [{"name": n, "dtype": str(a.dtype), "shape": list(a.shape)} for n, a in arrays]}
         if self.index_type == "IVFPQ":
             header["pq_m"] = self.pq_m
+            if self.refine is not None:                              # (absent: an unrefined index, as every earlier file)
+                header["refine"], header["refine_factor"] = self.refine, int(self.refine_factor)
         if self._host_ids is not None:
             header["host_ids"] = [_encode_id(x) for x in self._host_ids]     # typed: ids round-trip as what they were
         hj = json.dumps(header).encode()
@@ -406,6 +418,7 @@ class FAISSIndex:
         self.nlist = header["nlist"]
         self.nprobe = header["nprobe"]
         self.pq_m = int(header.get("pq_m", self.pq_m))
+        self.refine, self.refine_factor = header.get("refine"), int(header.get("refine_factor", 4))
         self._create_index()
         n = header["ntotal"]
         self._reserve(n)
@@ -417,9 +430,9 @@ class FAISSIndex:
         self._identity = header["identity_ids"]
         hid = header.get("host_ids")
         self._host_ids = None if hid is None else [_decode_id(x) for x in hid]
-        cls, _ = self._state_class()
+        cls, extra = self._state_class()
         if cls is not None:
-            self._set_state(cls.from_arrays(arrays, self.device))
+            self._set_state(cls.from_arrays(arrays, self.device, *extra[1:]))
         self._log(f"Index loaded from {filepath}")
         self._log(f"Index size: {self._n}")
 
