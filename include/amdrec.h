@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define AMDREC_ABI_VERSION 14
+#define AMDREC_ABI_VERSION 14 /* (v14 later gained amdrec_exclude_compact: one added export, nothing else changed) */
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -406,6 +406,22 @@ int amdrec_l2_normalize(const float* in, int64_t ld_in, float* out, int64_t ld_o
  * out[i] = id_map[pos[i]]; pos == -1 reads id_map[n_map-1] exactly like Python's id_map[-1]. */
 int amdrec_remap_ids(const int64_t* pos, const int64_t* id_map, int64_t n_map, int64_t* out,
                      int64_t n, void* stream);
+
+/* Per-request exclusion lists (added to ABI v14 without a version step: a new export, every other entry as it was).  The
+ * search ran unfiltered for kc candidates per query; this drops, per query, every candidate whose key is in the query's
+ * exclusion list exclude[q][0 .. n_exclude) (ad ids or positions, whatever `keys` holds; negative entries are padding and
+ * match nothing; duplicates allowed) and writes the first k survivors in their order: out_keys / out_scores / out_carry
+ * [nq][k].  `carry` (may be NULL, then out_carry is NULL too) is a second int64 block that travels with the keys: the corpus
+ * positions when the keys are remapped ids; out_keys may be NULL when it is given.  A candidate that is already unfilled
+ * (carry < 0, or key < 0 without carry) is never matched and keeps its place.  Slots past the last survivor get fill_key /
+ * fill_score / fill_carry (the index type's unfilled convention: -1, -inf or +inf, -1).  One launch, one workgroup per
+ * query, no workspace.  1 <= k <= kc <= AMDREC_MAX_K, 1 <= n_exclude < AMDREC_MAX_K, ld_exclude >= n_exclude; outputs must
+ * not alias inputs. */
+int amdrec_exclude_compact(const int64_t* keys /*[nq][kc]*/, const float* scores /*[nq][kc]*/,
+                           const int64_t* carry /*[nq][kc] or NULL*/, int64_t nq, int kc,
+                           const int64_t* exclude /*[nq][ld_exclude]*/, int n_exclude, int64_t ld_exclude, int k,
+                           int64_t fill_key, float fill_score, int64_t fill_carry, int64_t* out_keys /*[nq][k]*/,
+                           float* out_scores /*[nq][k]*/, int64_t* out_carry /*[nq][k] or NULL*/, void* stream);
 
 /* Optional per-launch timing: HIP events recorded on the launch stream around every GEMM-shaped
  * kernel launch, accumulated per kernel tag ("<epilogue>_<BP>x<BQ>", DESIGN.md maps tags to

@@ -26,7 +26,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, ivf, ivfpq
+from . import _lib, exclude as _exclude, ivf, ivfpq
 
 _MAGIC = b"AMDRECIX1"
 ADD_BATCH = 1 << 18            # IVFPQ add: rows normalised and encoded per batch (256 MB of fp32 at d = 256)
@@ -132,6 +132,7 @@ class FAISSIndex:
         self._maxnorm = torch.zeros(2, dtype=torch.float32, device=self.device)     # [max row norm, max row rounding-error norm]
         self._identity = True          # ids == arange(n): remap is the identity
         self._host_ids: Optional[list] = None   # only for non-integer ids
+        self._host_pos = None          # (len(_host_ids), {id: [positions]}) for exclusion lists, built on first use
         self._trained = self.index_type == "Flat"
         self._keeps_rows = self.index_type != "IVFPQ"    # IVFPQ: codes only, no fp32 corpus on the device
         self._state = None             # set by train(): the IVFState / IVFPQState behind ...
@@ -299,11 +300,18 @@ class FAISSIndex:
         return self._ids[:self._n].tolist()
 
     def search_device(self, queries: torch.Tensor, k: int, normalize: bool = True,
-                      return_positions: bool = False, pos_offset: int = 0):
+                      return_positions: bool = False, pos_offset: int = 0, exclude: Optional[torch.Tensor] = None,
+                      _exclude_positions: bool = False):
         """Device-to-device search, asynchronous on the current stream.
         -> (ids int64 [nq,k], scores float32 [nq,k]) on the device.  ``return_positions``: corpus
         positions (+ ``pos_offset``, the shard's first global row) instead of ids, -1 = unfilled.
-        IVFPQ: the scores are squared L2 distances, ascending (+inf = unfilled): approximate, or exact with refine."""
+        IVFPQ: the scores are squared L2 distances, ascending (+inf = unfilled): approximate, or exact with refine.
+        ``exclude``: device int64 [nq, E], per query the ad ids that must not be returned (negative = padding): the
+        unfiltered search for k + E with those ids removed, order kept, cut to k (amdrec.exclude has the contract;
+        k + E <= AMDREC_MAX_K).  It applies to ids also under ``return_positions``.  None or E = 0: the plain search, not
+        one launch more."""
+        if exclude is not None and exclude.shape[-1] > 0:
+            return self._search_excluding(queries, k, normalize, return_positions, pos_offset, exclude, _exclude_positions)
         q = _lib.require_gpu(queries, "queries")
         if q.dim() != 2 or q.shape[1] != self.dimension:
             raise ValueError(f"expected [nq, {self.dimension}] queries, got {tuple(q.shape)}")
@@ -343,16 +351,69 @@ class FAISSIndex:
                                         _lib.stream_ptr(self.device)))
         return ids, scores
 
-    def search(self, query_embeddings, k: int = 100, return_distances: bool = True):
-        """faiss_retrieval.py:129-166.  numpy in, numpy out: (ad_ids, distances)."""
+    def _search_excluding(self, queries, k, normalize, return_positions, pos_offset, exclude, exclude_positions):
+        """search_device with an exclusion block: the unfiltered search for kc = k + E, the remap to ids where ids are not
+        positions, amdrec_exclude_compact on the ids, and the id path's treatment of unfilled slots after that."""
+        kc = _exclude.check_exclude(k, exclude.shape[-1])              # (before the library is touched)
+        excl = _lib.require_gpu(exclude, "exclude", torch.int64)
+        pos_c, sc_c = self.search_device(queries, kc, normalize=normalize, return_positions=True)
+        fill = float("inf") if self.index_type == "IVFPQ" else float("-inf")
+        if self._identity or exclude_positions:                      # the keys to match are the positions themselves
+            pos, scores, _ = _exclude.compact(pos_c, sc_c, None, excl, k, fill)
+        else:
+            lib = _lib.load()
+            ids_c = torch.empty_like(pos_c)
+            _lib.check(lib.amdrec_remap_ids(_lib.ptr(pos_c), _lib.ptr(self._ids), self._n, _lib.ptr(ids_c), pos_c.numel(),
+                                            _lib.stream_ptr(self.device)))
+            _, scores, pos = _exclude.compact(ids_c, sc_c, pos_c, excl, k, fill, want_keys=False)
+        if return_positions:
+            if pos_offset:
+                pos = torch.where(pos < 0, pos, pos + pos_offset)
+            return pos, scores
+        if self._identity:
+            # (after the compaction any slot can be unfilled: -1 reads id_map[-1], as in the plain search)
+            return (torch.where(pos < 0, pos + self._n, pos) if self._n else pos), scores
+        ids = torch.empty_like(pos)
+        _lib.check(_lib.load().amdrec_remap_ids(_lib.ptr(pos), _lib.ptr(self._ids), self._n, _lib.ptr(ids), pos.numel(),
+                                                _lib.stream_ptr(self.device)))
+        return ids, scores
+
+    def _exclude_block(self, exclude, nq: int) -> Optional[torch.Tensor]:
+        """The ``exclude`` argument of search / batch_search -> device int64 [nq, E] (None: no list).  With host-side
+        object ids the block holds corpus POSITIONS: every position of each excluded id (ids not in the index are ignored)."""
+        if exclude is None:
+            return None
+        if self._host_ids is None:
+            blk = _exclude.as_block(exclude, nq)
+        else:
+            if len(exclude) != nq:
+                raise ValueError(f"{len(exclude)} exclusion lists for {nq} queries")
+            if self._host_pos is None or self._host_pos[0] != len(self._host_ids):
+                where = {}
+                for p, x in enumerate(self._host_ids):
+                    where.setdefault(x, []).append(p)
+                self._host_pos = (len(self._host_ids), where)
+            where = self._host_pos[1]
+            blk = _exclude.pad_exclusions([[p for x in dict.fromkeys(row) for p in where.get(x, ())] for row in exclude])
+            blk = blk if blk.shape[1] else None
+        return None if blk is None else torch.from_numpy(blk).to(self.device)
+
+    def search(self, query_embeddings, k: int = 100, return_distances: bool = True, exclude=None):
+        """faiss_retrieval.py:129-166.  numpy in, numpy out: (ad_ids, distances).  ``exclude``: one sequence of ad ids per
+        query (or an integer array [nq, E], negative = padding) that must not be returned: see search_device."""
+        return self._search(query_embeddings, k, return_distances, self._exclude_block(exclude, len(query_embeddings)))
+
+    def _search(self, query_embeddings, k, return_distances, excl):
+        """search with the exclusion lists already as a device block (_exclude_block)."""
         q = self._to_device_f32(query_embeddings)
         t0 = time.time()
         if self._host_ids is not None:
-            pos, scores = self.search_device(q, k, normalize=True, return_positions=True)
+            pos, scores = self.search_device(q, k, normalize=True, return_positions=True, exclude=excl,
+                                             _exclude_positions=True)
             idm = np.asarray(self._host_ids, dtype=object)
             ad_ids = idm[pos.cpu().numpy()]                          # pos == -1 -> id_map[-1]
         else:
-            ids, scores = self.search_device(q, k, normalize=True)
+            ids, scores = self.search_device(q, k, normalize=True, exclude=excl)
             ad_ids = ids.cpu().numpy()
         distances = scores.cpu().numpy()
         self._log(f"Search completed in {(time.time() - t0) * 1000:.2f}ms for {len(q)} queries")
@@ -360,11 +421,14 @@ class FAISSIndex:
             return ad_ids, distances
         return ad_ids
 
-    def batch_search(self, query_embeddings, k: int = 100, batch_size: int = 1000):
-        """faiss_retrieval.py:168-194."""
+    def batch_search(self, query_embeddings, k: int = 100, batch_size: int = 1000, exclude=None):
+        """faiss_retrieval.py:168-194.  ``exclude`` (as in search) is padded once, to the longest list of the whole call,
+        and sliced with the queries: the chunking does not change the result."""
         all_ids, all_d = [], []
+        excl = self._exclude_block(exclude, len(query_embeddings))
         for i in range(0, len(query_embeddings), batch_size):
-            ids, d = self.search(query_embeddings[i:i + batch_size], k)
+            ids, d = self._search(query_embeddings[i:i + batch_size], k, True,
+                                  None if excl is None else excl[i:i + batch_size])
             all_ids.append(ids)
             all_d.append(d)
         return np.vstack(all_ids), np.vstack(all_d)

@@ -27,7 +27,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, exclude as _exclude
 from .index import FAISSIndex
 from .ranker import TransformerRanker
 from .towers import TwoTowerModel
@@ -136,11 +136,12 @@ class AdRecommenderInference:
         num = ((num - pp.mean) / pp.scale).astype(np.float32)
         return torch.tensor([cat], dtype=torch.long), torch.from_numpy(num[None, :])
 
-    def preprocess_batch(self, user_data_list: list):
+    def preprocess_batch(self, user_data_list: list, exclude: Optional[np.ndarray] = None):
         """Batch form of preprocess_user_features with the numerical transform on the device: categorical strings
         are label-encoded on the host (dictionary lookups), raw numericals are shipped as one float32 block and
         log1p / standardised by amdrec_prep_numerical.  -> (user_categorical [B,6] int64, user_numerical [B,13]
-        float32), both on the device."""
+        float32), both on the device.  ``exclude`` (int64 [B, E], amdrec.exclude.pad_exclusions) rides in the same
+        staging block and copy; the result is then (user_categorical, user_numerical, exclude on the device)."""
         pp = self.preprocessor
         if pp is None:
             raise ValueError("no preprocessor loaded")
@@ -153,45 +154,54 @@ class AdRecommenderInference:
         # ONE pinned staging block [categorical int64 | raw numerical float32] and ONE H2D copy per call (two pageable
         # copies cost ~25 us of a 0.4 ms request); the block is reused once its previous copy has completed
         cat_bytes = B * nc * 8
-        host, done = self._staging(cat_bytes + B * nn_ * 4)
+        ex_off = (cat_bytes + B * nn_ * 4 + 7) // 8 * 8                 # the int64 exclusion block, 8-byte aligned
+        host, done = self._staging(cat_bytes + B * nn_ * 4 if exclude is None else ex_off + exclude.size * 8)
         hv = host.numpy()
         if nc:
             hv[:cat_bytes].view(np.int64).reshape(B, nc)[:] = [[pp.encode(c, u["categorical"].get(c, "missing")) for c in cols]
                                                                for u in user_data_list]
         if nn_:
-            hv[cat_bytes:].view(np.float32).reshape(B, nn_)[:] = [[float(u["numerical"].get(c, 0)) for c in pp.numerical_cols]
-                                                                  for u in user_data_list]
+            hv[cat_bytes:cat_bytes + B * nn_ * 4].view(np.float32).reshape(B, nn_)[:] = [
+                [float(u["numerical"].get(c, 0)) for c in pp.numerical_cols] for u in user_data_list]
+        if exclude is not None:
+            hv[ex_off:].view(np.int64).reshape(exclude.shape)[:] = exclude
         blk = host.to(dev, non_blocking=True)
         done.record(torch.cuda.current_stream(dev))
         cat = blk[:cat_bytes].view(torch.int64).view(B, nc)
-        x = blk[cat_bytes:].view(torch.float32).view(B, nn_)
+        x = blk[cat_bytes:cat_bytes + B * nn_ * 4].view(torch.float32).view(B, nn_)
         out = torch.empty_like(x)
         lib = _lib.load()
         _lib.check(lib.amdrec_prep_numerical(_lib.ptr(x), _lib.ptr(self._pp_dev[1]), _lib.ptr(self._pp_dev[2]),
                                              _lib.ptr(out), x.shape[0], x.shape[1], _lib.stream_ptr(dev)))
+        if exclude is not None:
+            return cat, out, blk[ex_off:].view(torch.int64).view(exclude.shape)
         return cat, out
 
-    def _staging(self, nbytes: int):
-        """Pinned host block of at least ``nbytes`` + the event of its last use (waited for before it is handed out again)."""
+    def _staging(self, nbytes: int, slot: str = "in"):
+        """Pinned host block of at least ``nbytes`` + the event of its last use (waited for before it is handed out again).
+        ``slot``: blocks of different slots are different memory, so the inputs ("in"), a separately shipped exclusion
+        block ("excl") and the results ("out") of one call never wait for each other."""
         st = self.__dict__.setdefault("_stage_bufs", {})
         size = 256
         while size < nbytes:
             size *= 2
-        ent = st.get(size)
+        ent = st.get((slot, size))
         if ent is None:
-            ent = st[size] = (torch.empty(size, dtype=torch.uint8, pin_memory=True), torch.cuda.Event())
+            ent = st[(slot, size)] = (torch.empty(size, dtype=torch.uint8, pin_memory=True), torch.cuda.Event())
         else:
             ent[1].synchronize()
         return ent[0][:nbytes], ent[1]
 
     # -- the device hot path ------------------------------------------------------------------
-    def _stage1(self, uc, un, stage1_k, check_indices):
+    def _stage1(self, uc, un, stage1_k, check_indices, exclude=None):
         # the tower's launch also applies the search's query normalisation (faiss_retrieval.py:147): one launch fewer
         emb = self.two_tower_model.user_tower.encode(uc, un, check_indices=check_indices, renormalize=True)   # :223-227
+        # exclude (device int64 [B, E] ad ids, or None): removed here, so the ranker only ever sees eligible ads
         return self.faiss_index.search_device(emb, stage1_k, normalize=False,                  # :230-232
-                                              return_positions=True)
+                                              return_positions=True, exclude=exclude)
 
-    def _stage2(self, uc, un, cand_pos, top_k, check_indices, ids_are_positions=False, mark=None, out=None):
+    def _stage2(self, uc, un, cand_pos, top_k, check_indices, ids_are_positions=False, mark=None, out=None,
+                excluded=False):
         lib = _lib.load()
         B, stage1_k = cand_pos.shape
         if self.cache_ad_projection:
@@ -209,7 +219,8 @@ class AdRecommenderInference:
         if ids_are_positions:
             cand_ids = cand_pos
         elif idx._identity:
-            unfilled = idx._n and (stage1_k > idx._n or idx.index_type in ("IVF", "IVFPQ"))   # else every slot is filled
+            # (else every slot is filled)
+            unfilled = idx._n and (stage1_k > idx._n or idx.index_type in ("IVF", "IVFPQ") or excluded)
             # an unfilled slot (-1) reads id_map[-1] like the reference's list indexing (faiss_retrieval.py:159-160): one
             # launch (Python-style remainder: -1 -> n - 1, valid positions unchanged) instead of compare + add + where
             cand_ids = torch.remainder(cand_pos, idx._n) if unfilled else cand_pos
@@ -225,39 +236,60 @@ class AdRecommenderInference:
 
     @torch.no_grad()
     def recommend_device(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor, top_k: int = 10,
-                         stage1_k: int = 500, check_indices: bool = False):
+                         stage1_k: int = 500, check_indices: bool = False,
+                         exclude_ad_ids: Optional[torch.Tensor] = None):
         """[B,6] / [B,13] device tensors -> dict of device tensors, no host synchronisation:
         ad_ids [B,top_k] int64, scores [3,B,top_k] float32 (sigmoid of the logits), candidate_ids
         [B,stage1_k], candidate_scores [B,stage1_k], logits [3, B*stage1_k].  candidate_scores are the index's own
-        scores: inner products (descending) for Flat / IVF, approximate squared L2 distances (ascending) for IVFPQ."""
+        scores: inner products (descending) for Flat / IVF, approximate squared L2 distances (ascending) for IVFPQ.
+        ``exclude_ad_ids``: device int64 [B, E], per user the ad ids that must not be recommended (negative = padding;
+        stage1_k + E <= AMDREC_MAX_K): stage 1 searches stage1_k + E and drops them on the device (FAISSIndex.search_device),
+        so candidate_ids / candidate_scores and everything after them hold eligible ads only."""
         uc = _lib.require_gpu(user_categorical, "user_categorical")
         un = _lib.require_gpu(user_numerical, "user_numerical")
-        cand_pos, cand_scores = self._stage1(uc, un, stage1_k, check_indices)
-        out = self._stage2(uc, un, cand_pos, top_k, check_indices)
+        excluded = exclude_ad_ids is not None and exclude_ad_ids.shape[-1] > 0
+        cand_pos, cand_scores = self._stage1(uc, un, stage1_k, check_indices, exclude_ad_ids if excluded else None)
+        out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded)
         out["candidate_scores"] = cand_scores
         return out
 
-    def capture(self, batch_size: int, top_k: int = 10, stage1_k: int = 500, warmup: int = 2) -> "GraphedRecommender":
+    def capture(self, batch_size: int, top_k: int = 10, stage1_k: int = 500, warmup: int = 2,
+                max_exclude: int = 0) -> "GraphedRecommender":
         """Capture one recommend_device call for a fixed batch shape into a HIP graph (the ~40 kernel
         launches of a request are host-launch-bound at small batch: 1.76 ms eager at B = 1) and return a
-        replayer.  Weights, index and ad table must not change afterwards."""
-        return GraphedRecommender(self, batch_size, top_k, stage1_k, warmup)
+        replayer.  Weights, index and ad table must not change afterwards.  ``max_exclude`` > 0: the graph also holds a
+        static [batch_size, max_exclude] exclusion buffer (stage 1 always searches stage1_k + max_exclude) that the
+        replayer's ``exclude`` argument fills; 0 captures the graph without the exclusion step."""
+        return GraphedRecommender(self, batch_size, top_k, stage1_k, warmup, max_exclude)
 
     # -- reference API ------------------------------------------------------------------------
     def recommend_ads(self, user_data: dict, top_k: int = 10, stage1_k: int = 500,
-                      return_scores: bool = True) -> dict:
-        """inference.py:199-288."""
-        return self.batch_recommend([user_data], top_k=top_k, stage1_k=stage1_k,
-                                    return_scores=return_scores)[0]
+                      return_scores: bool = True, exclude_ad_ids=None) -> dict:
+        """inference.py:199-288.  ``exclude_ad_ids``: the ad ids this user must not be shown (a sequence of integers)."""
+        return self.batch_recommend([user_data], top_k=top_k, stage1_k=stage1_k, return_scores=return_scores,
+                                    exclude_ad_ids=None if exclude_ad_ids is None else [exclude_ad_ids])[0]
 
     def batch_recommend(self, user_data_list: list, top_k: int = 10, stage1_k: int = 500,
-                        return_scores: bool = True) -> list:
+                        return_scores: bool = True, exclude_ad_ids=None) -> list:
         """inference.py:290-331 - but one device pass for the whole list instead of a serial loop.
-        ``timing`` reports the batch's stage times divided by the number of users."""
+        ``timing`` reports the batch's stage times divided by the number of users.  ``exclude_ad_ids``: one sequence of
+        ad ids per user (recommend_device has the meaning); the padded block travels in the input staging block."""
         if not user_data_list:
             return []
-        uc, un = self.preprocess_batch(user_data_list)
-        return self.recommend_tensors(uc, un, top_k, stage1_k, return_scores, _encoded=True)
+        excl = self._host_exclusions(exclude_ad_ids, len(user_data_list), stage1_k)
+        if excl is None:
+            uc, un = self.preprocess_batch(user_data_list)
+        else:
+            uc, un, excl = self.preprocess_batch(user_data_list, excl)
+        return self.recommend_tensors(uc, un, top_k, stage1_k, return_scores, _encoded=True, _exclude_dev=excl)
+
+    @staticmethod
+    def _host_exclusions(exclude_ad_ids, n: int, stage1_k: int) -> Optional[np.ndarray]:
+        """One id list per user -> the padded int64 [n, E] host block (None: no list, or every list empty)."""
+        blk = _exclude.as_block(exclude_ad_ids, n)
+        if blk is not None:
+            _exclude.check_exclude(stage1_k, blk.shape[1])
+        return blk
 
     def _user_limits(self):
         """Per user column, the number of rows of the SMALLER of the tower's and the ranker's embedding tables: an index is
@@ -298,13 +330,14 @@ class AdRecommenderInference:
 
     @torch.no_grad()
     def recommend_tensors(self, user_categorical, user_numerical, top_k=10, stage1_k=500, return_scores=True,
-                          _encoded=False):
+                          _encoded=False, exclude_ad_ids=None, _exclude_dev=None):
         """Tensor-level entry (cf. TwoStageRetriever.retrieve_and_rank, faiss_retrieval.py:283-369); result dicts follow
         inference.py:272-288.  ONE host synchronisation per call (round 3 had four: the tower's index flag, the stage-1
         timing sync, the ranker's index flag, the result copy - each exposing the launch work queued behind it): indices
         are validated without a read-back in the middle (the verdict travels with the results), the stage times come from
         events, ids + scores + verdict come back in one copy.  An out-of-range index raises IndexError like the reference's
-        embedding lookup, before any result is returned."""
+        embedding lookup, before any result is returned.  ``exclude_ad_ids``: one sequence of ad ids per user, shipped as
+        one padded block through pinned memory (no synchronisation of its own)."""
         t0 = time.time()
         dev = self.device
         uc = user_categorical.to(dev)
@@ -312,6 +345,14 @@ class AdRecommenderInference:
         n = uc.shape[0]
         if not n:
             return []
+        excl = _exclude_dev
+        if excl is None and exclude_ad_ids is not None:
+            hb = self._host_exclusions(exclude_ad_ids, n, stage1_k)
+            if hb is not None:
+                host, done = self._staging(hb.size * 8, "excl")
+                host.numpy().view(np.int64).reshape(hb.shape)[:] = hb
+                excl = host.to(dev, non_blocking=True).view(torch.int64).view(hb.shape)
+                done.record(torch.cuda.current_stream(dev))
         tasks = list(self.transformer_ranker.prediction_heads.keys())        # the ranker's task order (= out["tasks"])
         ev = self.__dict__.get("_ev")
         if ev is None:
@@ -333,11 +374,11 @@ class AdRecommenderInference:
             raise IndexError("index out of range in self")                    # (the ad-feature table, transformer_ranker.py:322)
         st = torch.cuda.current_stream(dev)
         ev[0].record(st)
-        cand_pos, _ = self._stage1(uc, un, stage1_k, False)
+        cand_pos, _ = self._stage1(uc, un, stage1_k, False, excl)
         ev[1].record(st)
-        out = self._stage2(uc, un, cand_pos, top_k, False, out=(ad_ids, scores))
+        out = self._stage2(uc, un, cand_pos, top_k, False, out=(ad_ids, scores), excluded=excl is not None)
         assert list(out["tasks"]) == tasks
-        host, done = self._staging(blk.numel())
+        host, done = self._staging(blk.numel(), "out")
         host.copy_(blk, non_blocking=True)
         ev[2].record(st)
         done.record(st)
@@ -381,19 +422,25 @@ class TwoStageRetriever:
 
     @torch.no_grad()
     def retrieve_and_rank(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor, stage1_k: int = 500,
-                          stage2_k: int = 10, ad_features_lookup=None):
+                          stage2_k: int = 10, ad_features_lookup=None, exclude_ad_ids=None):
+        """``exclude_ad_ids``: the ad ids the (first) user must not be shown, a sequence of integers."""
         uc = user_categorical.to(self.device)
         un = user_numerical.to(self.device, dtype=torch.float32)
+        excl = None if exclude_ad_ids is None else [exclude_ad_ids]
         if ad_features_lookup is None:                                            # :329-331
             emb = self.two_tower_model.get_user_embeddings(uc, un)
-            ids, dist = self.faiss_index.search_device(emb, stage1_k)
+            blk = _exclude.as_block(excl, 1)
+            ids, dist = self.faiss_index.search_device(
+                emb[:1] if blk is not None else emb, stage1_k,
+                exclude=None if blk is None else torch.from_numpy(blk).to(self.device))
             return ids[0].tolist(), dist[0].tolist()
         if self._rec is None or self._rec_table is not ad_features_lookup:
             self._rec = AdRecommenderInference(device=str(self.device), two_tower_model=self.two_tower_model,
                                                transformer_ranker=self.transformer_ranker,
                                                faiss_index=self.faiss_index, ad_features=ad_features_lookup)
             self._rec_table = ad_features_lookup
-        r = self._rec.recommend_tensors(uc[:1], un[:1], stage2_k, stage1_k)[0]    # one synchronisation, indices validated
+        r = self._rec.recommend_tensors(uc[:1], un[:1], stage2_k, stage1_k,       # one synchronisation, indices validated
+                                        exclude_ad_ids=excl)[0]
         return r["ad_ids"], r["scores"]["ctr"]                                    # :359-369 (ids, ctr probabilities)
 
 
@@ -402,26 +449,31 @@ class GraphedRecommender:
     The graph owns everything its kernel nodes point at: static input/output tensors (torch's graph
     memory pool) and a private, fixed-size workspace (never the shared grow-only one)."""
 
-    def __init__(self, rec: AdRecommenderInference, batch_size: int, top_k: int, stage1_k: int, warmup: int = 2):
+    def __init__(self, rec: AdRecommenderInference, batch_size: int, top_k: int, stage1_k: int, warmup: int = 2,
+                 max_exclude: int = 0):
         self.rec, self.batch_size, self.top_k, self.stage1_k = rec, batch_size, top_k, stage1_k
+        self.max_exclude = int(max_exclude)
+        _exclude.check_exclude(stage1_k, self.max_exclude)
         dev = rec.ad_features.device
         n_cat = len(rec.two_tower_model.user_tower._names)
         n_num = rec.two_tower_model.user_tower._n_num
         self._uc = torch.zeros((batch_size, n_cat), dtype=torch.int64, device=dev)
         self._un = torch.zeros((batch_size, n_num), dtype=torch.float32, device=dev)
+        # static exclusion block (-1 = padding = nothing excluded); None: the graph has no exclusion step
+        self._ex = torch.full((batch_size, self.max_exclude), -1, dtype=torch.int64, device=dev) if self.max_exclude else None
         # sizing + warm-up pass on the shared workspace (packs weights, sets kernel attributes)
         probe = _lib.MeasuringArena(_lib.Workspace())
         with _lib.WORKSPACE.private(probe):
             for _ in range(max(1, warmup)):
-                rec.recommend_device(self._uc, self._un, top_k, stage1_k)
+                rec.recommend_device(self._uc, self._un, top_k, stage1_k, exclude_ad_ids=self._ex)
         torch.cuda.synchronize(dev)
         self._arena = _lib.FixedArena(probe.high_water, dev)
         with _lib.WORKSPACE.private(self._arena):
-            rec.recommend_device(self._uc, self._un, top_k, stage1_k)          # one eager pass on the private arena
+            rec.recommend_device(self._uc, self._un, top_k, stage1_k, exclude_ad_ids=self._ex)          # one eager pass on the private arena
             torch.cuda.synchronize(dev)
             self._graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._graph):
-                self._out = rec.recommend_device(self._uc, self._un, top_k, stage1_k)
+                self._out = rec.recommend_device(self._uc, self._un, top_k, stage1_k, exclude_ad_ids=self._ex)
         torch.cuda.synchronize(dev)
         # pin every device buffer the kernel nodes point at: a later load_state_dict / index.add() / larger eager search
         # then makes the graph stale (documented) but can never leave it with dangling pointers
@@ -429,11 +481,22 @@ class GraphedRecommender:
                         rec.transformer_ranker._ad_cache, *rec.faiss_index.resident_tensors())
 
     @torch.no_grad()
-    def __call__(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor):
+    def __call__(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor,
+                 exclude: Optional[torch.Tensor] = None):
         """Device tensors [batch_size, ...] -> the same dict as recommend_device (static output buffers,
-        overwritten by the next call)."""
+        overwritten by the next call).  ``exclude``: device int64 [batch_size, E <= max_exclude] ad ids (negative =
+        padding), copied into the graph's block; None = nothing excluded (the block is filled with -1)."""
         if user_categorical.shape[0] != self.batch_size:
             raise ValueError(f"captured for batch {self.batch_size}, got {user_categorical.shape[0]}")
+        if exclude is not None and (self._ex is None or exclude.dim() != 2 or exclude.shape[0] != self.batch_size
+                                    or exclude.shape[1] > self.max_exclude):
+            raise ValueError(f"captured with max_exclude={self.max_exclude} for batch {self.batch_size}, got an exclusion "
+                             f"block of shape {tuple(exclude.shape)}")
+        if self._ex is not None:
+            if exclude is None or exclude.shape[1] < self.max_exclude:
+                self._ex.fill_(-1)
+            if exclude is not None:
+                self._ex[:, :exclude.shape[1]].copy_(exclude)
         self._uc.copy_(user_categorical)
         self._un.copy_(user_numerical)
         self._graph.replay()

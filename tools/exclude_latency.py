@@ -1,0 +1,138 @@
+"""Dev tool: what a per-request exclusion list costs.  Per index type (Flat, IVF 100 / 10, IVFPQ 100 / 10; 1M x 256 randn
+rows), batch B in {1, 32, 512}, k = 500 and E in {0, 64, 512}: search time (HIP events, mean of REPS searches over ROT
+rotating query batches and exclusion blocks) for k, for k + E without a list, and for k with the list; the compaction kernel
+alone (amdrec_profile_* tag exclude_compact); then recommend_device end to end at B = 512 with and without a 64-entry list.
+usage: python tools/exclude_latency.py [--out FILE] [--plain-only] [--pkg DIR] [--n ROWS]
+  --plain-only : only the cells without a list (search at k, recommend_device without exclude_ad_ids): runs on any commit,
+                 for the A/B of the exclude=None path against the parent (--pkg = that commit's movie-recommender-demo_amd)."""
+import argparse
+import json
+import os
+import sys
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--out", default=None)
+ap.add_argument("--plain-only", action="store_true")
+ap.add_argument("--pkg", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "movie-recommender-demo_amd"))
+ap.add_argument("--n", type=int, default=1_000_000)
+ARGS = ap.parse_args()
+sys.path.insert(0, os.path.abspath(ARGS.pkg))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from amdrec import _lib, synth  # noqa: E402
+from amdrec.index import FAISSIndex  # noqa: E402
+
+INDEXES = (("Flat", {}), ("IVF", {"nlist": 100, "nprobe": 10}), ("IVFPQ", {"nlist": 100, "nprobe": 10}))
+BATCHES, K, WIDTHS, REPS, ROT = (1, 32, 512), 500, (0, 64, 512), 20, 4
+
+
+def timed(fn, reps=REPS):
+    """fn(i) is called with a running counter: the caller rotates its inputs on it."""
+    for i in range(3):
+        fn(i)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(reps):
+        fn(i)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def kernel_ms(fn, tag="exclude_compact", reps=10):
+    torch.cuda.synchronize()
+    _lib.profile_enable(True, only=tag)
+    for i in range(reps):
+        fn(i)
+    rep = _lib.profile_report()
+    _lib.profile_enable(False)
+    return rep[tag]["total_ms"] / rep[tag]["launches"]
+
+
+def blocks(idx, qs, E):
+    """Per query batch an exclusion block that hits: E ids drawn from each query's own best K + E."""
+    out = []
+    g = torch.Generator(device=qs[0].device)
+    g.manual_seed(7)
+    for q in qs:
+        ids = idx.search_device(q, K + E)[0]
+        pick = torch.rand(ids.shape, generator=g, device=ids.device).argsort(dim=1)[:, :E]
+        out.append(torch.gather(ids, 1, pick).contiguous())
+    return out
+
+
+def run_searches(x, g, out):
+    dev = x.device
+    for name, kw in INDEXES:
+        idx = FAISSIndex(256, index_type=name, **kw)
+        idx.add(x)
+        for B in BATCHES:
+            qs = [torch.randn((B, 256), generator=g, device=dev) for _ in range(ROT)]
+            rec = {"index": name, "n": x.shape[0], "B": B, "k": K,
+                   "search_k_ms": round(timed(lambda i: idx.search_device(qs[i % ROT], K)), 4)}
+            if not ARGS.plain_only:
+                for E in WIDTHS:
+                    if E == 0:
+                        none = torch.empty((B, 0), dtype=torch.int64, device=dev)
+                        rec["E=0"] = {"search_k_excl_ms": round(timed(lambda i: idx.search_device(qs[i % ROT], K, exclude=none)), 4)}
+                        continue
+                    xs = blocks(idx, qs, E)
+                    rec[f"E={E}"] = {
+                        "search_k_plus_E_ms": round(timed(lambda i: idx.search_device(qs[i % ROT], K + E)), 4),
+                        "search_k_excl_ms": round(timed(lambda i: idx.search_device(qs[i % ROT], K, exclude=xs[i % ROT])), 4),
+                        "compact_kernel_ms": round(kernel_ms(lambda i: idx.search_device(qs[i % ROT], K, exclude=xs[i % ROT])), 4)}
+            print(json.dumps(rec), flush=True)
+            out.append(rec)
+        del idx
+        torch.cuda.empty_cache()
+
+
+def run_pipeline(n, out):
+    """recommend_device at B = 512 over a Flat index of n ads (the demo models, as bench.py's weights)."""
+    from amdrec.pipeline import AdRecommenderInference, build_faiss_index
+    from amdrec.ranker import TransformerRanker
+    from amdrec.towers import TwoTowerModel
+    user, ad, nnum = synth.demo_dims()
+    to_t = lambda sd: {k: torch.from_numpy(np.array(v)) for k, v in sd.items()}   # noqa: E731
+    tt = TwoTowerModel(dict(user), dict(ad), nnum)
+    tt.load_state_dict(to_t(synth.two_tower_state(user, ad, nnum, seed=3)))
+    rk = TransformerRanker(dict(user), dict(ad), nnum)
+    rk.load_state_dict(to_t(synth.ranker_state(user, ad, nnum, seed=4, cross_scale=1.0 / 16)))
+    table = synth.ad_features(ad, n, seed=5)
+    rec = AdRecommenderInference(device="cuda:0", two_tower_model=tt, transformer_ranker=rk,
+                                 faiss_index=build_faiss_index(tt, table, device="cuda:0", index_type="Flat"),
+                                 ad_features=table)
+    B, E = 512, 64
+    users = [tuple(torch.from_numpy(a).cuda() for a in synth.user_batch(user, nnum, B, seed=10 + r)) for r in range(ROT)]
+    row = {"pipeline": "recommend_device", "index": "Flat", "n": n, "B": B, "top_k": 10, "stage1_k": K,
+           "plain_ms": round(timed(lambda i: rec.recommend_device(*users[i % ROT], 10, K)), 4)}
+    if not ARGS.plain_only:
+        xs = []
+        for uc, un in users:                                         # 64 of each user's own candidates, the winners first
+            o = rec.recommend_device(uc, un, 10, K)
+            xs.append(torch.cat([o["ad_ids"], o["candidate_ids"][:, 100:100 + E - 10]], dim=1).contiguous())
+        row["E"] = E
+        row["excl_ms"] = round(timed(lambda i: rec.recommend_device(*users[i % ROT], 10, K, exclude_ad_ids=xs[i % ROT])), 4)
+    print(json.dumps(row), flush=True)
+    out.append(row)
+
+
+def main():
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    out = []
+    x = torch.randn((ARGS.n, 256), generator=g, device=dev)
+    run_searches(x, g, out)
+    del x
+    torch.cuda.empty_cache()
+    run_pipeline(ARGS.n, out)
+    if ARGS.out:
+        with open(ARGS.out, "w") as f:
+            json.dump({"device": torch.cuda.get_device_name(0), "plain_only": ARGS.plain_only, "reps": REPS,
+                       "rotating_inputs": ROT, "rows": out}, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
