@@ -165,7 +165,15 @@ class InvertedLists:
             sel = torch.randperm(n, generator=g)[:MAX_POINTS_PER_CENTROID * nlist].to(x.device)
             x = x[sel]
             n = x.shape[0]
-        cent = x[torch.randperm(n, generator=g)[:nlist].to(x.device)].clone().contiguous()
+        order = torch.randperm(n, generator=g)
+        finite = torch.isfinite(x).all(dim=1).cpu()
+        if not bool(finite.all()):
+            # a row with a non-finite coordinate never becomes a centroid (its scores are NaN: it would win no row, keep
+            # its NaN for every iteration and leave a dead list); with finite rows only, the draw is unchanged
+            order = order[finite[order]]
+            if order.numel() < nlist:
+                raise ValueError(f"need at least nlist={nlist} finite training vectors, got {order.numel()}")
+        cent = x[order[:nlist].to(x.device)].clone().contiguous()
         x = x.contiguous()
         lib = _lib.load()
         nbytes = _lib.C.c_size_t(0)
