@@ -25,7 +25,10 @@
 extern "C" {
 #endif
 
-#define AMDREC_ABI_VERSION 14 /* (v14 later gained amdrec_exclude_compact: one added export, nothing else changed) */
+#define AMDREC_ABI_VERSION 14 /* (v14 later gained amdrec_exclude_compact: one added export, nothing else changed; and the
+                               * first-FFN hidden cache: amdrec_ranker_project_ads_hidden, amdrec_x3_weights.stream_hc ... at the
+                               * struct's end, amdrec_ranker_params.ad_hidden_cache - the number stays, the library and its
+                               * binding ship together and the struct layouts are checked against the compiler, tests/test_abi.py) */
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -327,6 +330,24 @@ typedef struct {
      * and its b_ov is not in the parameter blob.  Only this engine runs such parameters: requires n_layers >= 1 and
      * min_rows == 1 (every pass takes the engine); layers[0] keeps the unfolded W_ov / b_ov (amdrec_ranker_x3_prefix). */
     int64_t fold_attn1;
+    /* Optional (needs fold_attn1 and variant 16): stage 1 of layer 1's FFN served from a per-ad cache.  After the
+     * fold the chain starts with x1 = LN1(z), z = ad_proj_cache[ad] + U[user], and W_1 x1 + b_1 is linear in z once the
+     * row's deviation is known:  W_1 x1 + b_1 = rstd * W_1c z + c,  W_1c = W_1 diag(gamma1) (I - 11^T/256),  c = W_1 beta1
+     * + b_1,  rstd = 1/sqrt(var(z) + eps)  (the centering matrix is folded into W_1c: no mean term).  W_1c z splits into
+     * P[ad] = W_1c a_ad (ad_hidden_cache, built by amdrec_ranker_project_ads_hidden) and Q[user] = W_1c u_user, which the
+     * user-projection launch writes next to U (rows [U | Q] from the stacked w_user_uq / b_user_uq).  The kernel then forms
+     * the hidden tile as relu((P + Q) * rstd + c) from two row loads instead of 256 x 1024 weight elements.
+     *   stream_hc / chunks_hc : the 16-row kernel's stream without layer 1's stage-1 fragment sets
+     *   params_hc             : the parameter blob (n_params floats) with c in the place of layer 1's b_1
+     *   w_user_uq / b_user_uq : [d_model + d_ff][ldw_proj_user] = [w_proj_user ; W_1c w_proj_user], [b_proj ; W_1c b_proj]
+     *   w_hidden_ad           : [d_ff][ldw_proj_ad] = W_1c w_proj_ad    (all composed on the host in float64)
+     * Used only by passes that take the 128-row kernel (> 16384 rows) with both caches set; NULL -> off. */
+    const void* stream_hc;
+    int64_t chunks_hc;
+    const float* params_hc;
+    const float* w_user_uq;
+    const float* b_user_uq;
+    const float* w_hidden_ad;
 } amdrec_x3_weights;
 
 typedef struct {
@@ -361,6 +382,11 @@ typedef struct {
      * the same two addends in the same order as the uncached path (bit-identical). */
     const float* ad_proj_cache;     /* [n_ad_rows][ld_ad_proj_cache] or NULL */
     int64_t ld_ad_proj_cache;
+    /* Optional second candidate-side cache (see amdrec_x3_weights.stream_hc): ad_hidden_cache[a] = w_hidden_ad .
+     * emb(ad_cat[a]), d_ff floats per row of the SAME table as ad_proj_cache.  The per-call user half Q lives in the
+     * workspace next to U (amdrec_ranker_workspace accounts for it while this pointer is set). */
+    const float* ad_hidden_cache;   /* [n_ad_rows][ld_ad_hidden_cache] or NULL */
+    int64_t ld_ad_hidden_cache;
     /* Optional x6 planes (see amdrec_encoder_layer) of cross_wt[i] and head_w1. */
     const uint16_t* cross_wt_x6[AMDREC_MAX_LAYERS];
     const uint16_t* head_w1_x6;
@@ -396,6 +422,12 @@ int amdrec_ranker_x3_prefix(const amdrec_ranker_params* p /*host*/, const float*
 int amdrec_ranker_project_ads(const amdrec_ranker_params* p /*host*/, const int64_t* ad_cat, int64_t n_ads,
                               float* out /*[n_ads][ld_out]*/, int64_t ld_out, void* workspace,
                               size_t workspace_bytes, void* stream);
+
+/* Fills amdrec_ranker_params.ad_hidden_cache: out[a] = x3.w_hidden_ad . emb(ad_cat[a]) (d_ff floats per ad, no bias),
+ * with the tile GEMM of amdrec_ranker_project_ads.  workspace: >= 4*d_ff + 256 bytes. */
+int amdrec_ranker_project_ads_hidden(const amdrec_ranker_params* p /*host*/, const int64_t* ad_cat, int64_t n_ads,
+                                     float* out /*[n_ads][ld_out]*/, int64_t ld_out, void* workspace,
+                                     size_t workspace_bytes, void* stream);
 
 /* faiss.normalize_L2 (faiss_retrieval.py:115, :147): every row scaled by 1/||row||_2, rows of
  * zero norm left as they are.  out may alias in.  dim % 4 == 0. */

@@ -86,6 +86,13 @@ class TransformerRanker(nn.Module):
         # where every pass runs the row-owner kernel (gemm_engine "f16x3" on its architecture, x3_min_rows = 1): one
         # 256 x 256 GEMM less per candidate row.  The fp32 / bf16x6 engines keep the unfolded chain.
         self.fold_first_attention = True
+        # stage 1 of layer 1's FFN served from a second per-ad cache (weights.first_ffn_cache: with the fold,
+        # W_1 LN1(z) + b_1 = rstd * (P[ad] + Q[user]) + c): passes of more than 16384 rows on the folded 16-row kernel read
+        # two rows instead of multiplying with W_1.  ``ensure_ad_cache`` builds P [N, d_ff] fp32 beside the projection
+        # cache while both fit ``hidden_cache_max_bytes`` (N * (d_model + d_ff) * 4: 5 KB per ad at the default widths);
+        # larger tables, smaller passes and the other engines run the uncached program.
+        self.cache_first_ffn = True
+        self.hidden_cache_max_bytes = 8 << 30
         # engine of the big passes (> 8192 rows), all fp32 in / fp32 out with fp32-level error:
         #  "f16x3"  (default) the row-owner kernel (csrc/rowowner.hpp): operands split into two fp16 planes, three
         #           fp16-MFMA products per MAC, everything after the projection in ONE kernel, activations in registers
@@ -155,14 +162,33 @@ class TransformerRanker(nn.Module):
         ws = _lib.WORKSPACE.get(4 * self.d_model + 256, dev)
         _lib.check(lib.amdrec_ranker_project_ads(_lib.C.byref(params), _lib.ptr(table), table.shape[0], _lib.ptr(out),
                                                  out.stride(0), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-        self._ad_cache = (self._packed[0], table.data_ptr(), tuple(table.shape), table._version, out)
+        self._ad_cache = (self._packed[0], table.data_ptr(), tuple(table.shape), table._version, out, None)
         return out
 
     def ensure_ad_cache(self, ad_table):
-        """Build the cache for ``ad_table`` unless a valid one exists (weights or table changed -> rebuilt)."""
-        self._pack(ad_table.device)
+        """Build the cache for ``ad_table`` unless a valid one exists (weights or table changed -> rebuilt) - and, with
+        ``cache_first_ffn`` on weights packed for it, the first-FFN hidden cache P [N, d_ff] beside it while both fit
+        ``hidden_cache_max_bytes``."""
+        params, _ = self._pack(ad_table.device)
         if self._cache_for(ad_table) is None:
             self.cache_ad_projection(ad_table)
+        c = self._ad_cache
+        if c is None or c[5] is not None or not params.x3.w_hidden_ad or self._cache_for(ad_table) is None:
+            return
+        n, d_ff = int(ad_table.shape[0]), int(params.d_ff)
+        if n * (self.d_model + d_ff) * 4 > int(self.hidden_cache_max_bytes):
+            return
+        dev = ad_table.device
+        hid = torch.empty((n, d_ff), dtype=torch.float32, device=dev)
+        ws = _lib.WORKSPACE.get(4 * d_ff + 256, dev)
+        _lib.check(_lib.load().amdrec_ranker_project_ads_hidden(
+            _lib.C.byref(params), _lib.ptr(ad_table), n, _lib.ptr(hid), hid.stride(0), _lib.ptr(ws), ws.numel(),
+            _lib.stream_ptr(dev)))
+        self._ad_cache = (*c[:5], hid)
+
+    def _hidden_cache_for(self, table):
+        """The first-FFN hidden cache that goes with ``_cache_for(table)`` (None: not built)."""
+        return self._ad_cache[5] if self._cache_for(table) is not None else None
 
     def _cache_for(self, table):
         c = getattr(self, "_ad_cache", None)
@@ -177,8 +203,8 @@ class TransformerRanker(nn.Module):
             raise ValueError(f"gemm_engine must be one of {self.ENGINES}")
         # (the key - and with it the ad-projection cache, which is only served for the key it was built under - covers the
         # fold: an engine switch repacks and rebuilds the cache in the other projection form)
-        key = (str(device), self.fuse_attention, bool(self.fold_first_attention), self.gemm_engine, int(self.x3_min_rows),
-               int(self.x3_variant), int(self.x3_cs_max_rows),
+        key = (str(device), self.fuse_attention, bool(self.fold_first_attention), bool(self.cache_first_ffn),
+               self.gemm_engine, int(self.x3_min_rows), int(self.x3_variant), int(self.x3_cs_max_rows),
                _lib.tensor_versions(self))
         if self._packed is None or self._packed[0] != key:
             sd = self.state_dict()
@@ -195,7 +221,8 @@ class TransformerRanker(nn.Module):
                                                       (self.gemm_engine == "f16x3" and not x3),
                                                       x3=x3, x3_min_rows=self.x3_min_rows, x3_variant=self.x3_variant,
                                                       x3_cs_max_rows=self.x3_cs_max_rows,
-                                                      fold_first_attention=bool(self.fold_first_attention))
+                                                      fold_first_attention=bool(self.fold_first_attention),
+                                                      cache_first_ffn=bool(self.cache_first_ffn))
             self._packed = (key, params, keep, tasks)
         return self._packed[1], self._packed[3]
 
@@ -245,6 +272,9 @@ class TransformerRanker(nn.Module):
         cache = self._cache_for(ad_cat) if use_cache else None
         params.ad_proj_cache = cache.data_ptr() if cache is not None else None
         params.ld_ad_proj_cache = cache.stride(0) if cache is not None else 0
+        hidden = self._hidden_cache_for(ad_cat) if cache is not None else None
+        params.ad_hidden_cache = hidden.data_ptr() if hidden is not None else None
+        params.ld_ad_hidden_cache = hidden.stride(0) if hidden is not None else 0
         lib = _lib.load()
         logits = torch.empty((len(tasks), rows), dtype=torch.float32, device=dev)
         if rows == 0:

@@ -609,9 +609,10 @@ extern "C" int amdrec_tower_forward(const amdrec_tower_params* p, const int64_t*
 namespace amdrec {   // ranker_x3.hip: the fp16x3 row-owner engine (everything after the feature projection in one kernel)
 bool ranker_x3_wanted(const amdrec_ranker_params* p, long long rows);
 bool ranker_x3_folded(const amdrec_ranker_params* p);
-int ranker_x3_run(const amdrec_ranker_params* p, const float* X, long long ldx, const float* U, const long long* rowmap,
-                  long long row_base, int rowdiv, long long n_cache, long long rows, float* scratch, float* logits,
-                  long long ld_logits, hipStream_t st);
+bool ranker_x3_hidden_cache(const amdrec_ranker_params* p, long long rows);
+int ranker_x3_run(const amdrec_ranker_params* p, const float* X, long long ldx, const float* U, long long ldu,
+                  const long long* rowmap, long long row_base, int rowdiv, long long n_cache, long long rows, float* scratch,
+                  float* logits, long long ld_logits, hipStream_t st);
 }
 static int ranker_check(const amdrec_ranker_params* p) {
     REQUIRE(p != nullptr, "params is null");
@@ -679,15 +680,15 @@ __global__ __launch_bounds__(256) void proj_gather_kernel(const float* cache, lo
     }
 }
 
-extern "C" int amdrec_ranker_project_ads(const amdrec_ranker_params* p, const int64_t* ad_cat, int64_t n_ads,
-                                         float* out, int64_t ld_out, void* workspace, size_t workspace_bytes,
-                                         void* stream) {
+// out[a] = W . emb(ad_cat[a]) for a [nout][ldw_proj_ad] matrix over the ad embeddings (no bias)
+static int project_ads(const amdrec_ranker_params* p, const float* W, int nout, const int64_t* ad_cat, int64_t n_ads,
+                       float* out, int64_t ld_out, void* workspace, size_t workspace_bytes, void* stream) {
     int rc = ranker_check(p);
     if (rc) return rc;
     if (n_ads <= 0) return AMDREC_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int dm = p->d_model, F0 = p->n_user_feat, F = p->n_user_feat + p->n_ad_feat;
-    REQUIRE(p->w_proj_ad && p->n_ad_feat > 0, "params carry no split projection (w_proj_ad)");
+    const int dm = nout, F0 = p->n_user_feat, F = p->n_user_feat + p->n_ad_feat;
+    REQUIRE(W && p->n_ad_feat > 0, "params carry no split projection (w_proj_ad / x3.w_hidden_ad)");
     REQUIRE(ad_cat && out, "null pointer");
     REQUIRE(ld_out >= dm && ld_out % 4 == 0 && ((uintptr_t)out % 16) == 0, "bad output layout");
     REQUIRE(n_ads < (1ll << 31) - 1024, "n_ads out of range");
@@ -702,9 +703,23 @@ extern "C" int amdrec_ranker_project_ads(const amdrec_ranker_params* p, const in
     ga.row_base = 0; ga.rows = n_ads; ga.rows1 = n_ads; ga.F = F - F0; ga.F0 = 0; ga.E = p->emb_dim;
     ga.eshift = ilog2(p->emb_dim); ga.n_num = 0; ga.cat0_rowdiv = 1;
     // the same GEMM (shape, K order) as the uncached candidate half, with an all-zero "user row"
-    HIP_TRY(linear_wide<EpiRowBiasT>(p->w_proj_ad, nullptr, p->ldw_proj_ad, dm, ga, n_ads, st, (F - F0) * p->emb_dim,
+    HIP_TRY(linear_wide<EpiRowBiasT>(W, nullptr, p->ldw_proj_ad, dm, ga, n_ads, st, (F - F0) * p->emb_dim,
                                      (const float*)zero, out, (long long)ld_out, n_ads, 0ll, 0x7fffffff, dm));
     return AMDREC_OK;
+}
+
+extern "C" int amdrec_ranker_project_ads(const amdrec_ranker_params* p, const int64_t* ad_cat, int64_t n_ads,
+                                         float* out, int64_t ld_out, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+    REQUIRE(p != nullptr, "params is null");
+    return project_ads(p, p->w_proj_ad, p->d_model, ad_cat, n_ads, out, ld_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int amdrec_ranker_project_ads_hidden(const amdrec_ranker_params* p, const int64_t* ad_cat, int64_t n_ads,
+                                                float* out, int64_t ld_out, void* workspace, size_t workspace_bytes,
+                                                void* stream) {
+    REQUIRE(p != nullptr, "params is null");
+    return project_ads(p, p->x3.w_hidden_ad, p->d_ff, ad_cat, n_ads, out, ld_out, workspace, workspace_bytes, stream);
 }
 
 // The user half of the projection for a handful of requests (hoisted form: U[u] = W_user [user emb | numerical] + b).  The tile
@@ -789,6 +804,13 @@ extern "C" int amdrec_ranker_forward(const amdrec_ranker_params* p, const int64_
         }
     }
 
+    // First-FFN hidden cache (amdrec_x3_weights.stream_hc): when the largest pass of this call takes it, the user projection
+    // also writes Q[u] = W_1c U[u] - rows [U | Q] of dm + d_ff floats from the stacked weights, in the same launch.  They
+    // share U's workspace region (rows * dm floats), which holds them from five candidates per user on.
+    const bool with_q = hoist && ranker_x3_hidden_cache(p, w.chunk) && n_users * (long long)(dm + p->d_ff) <= rows * (long long)dm;
+    const int du = with_q ? dm + p->d_ff : dm;                // width and leading dimension of the user rows
+    const float* w_user = with_q ? p->x3.w_user_uq : p->w_proj_user;
+    const float* b_user = with_q ? p->x3.b_user_uq : p->b_proj;
     if (hoist) {
         // U[u] = W_user [user emb(u) | numerical(u)] + b_proj (+ pos[0]): once per user row
         EmbConcatRows gu{};
@@ -798,13 +820,13 @@ extern "C" int amdrec_ranker_forward(const amdrec_ranker_params* p, const int64_
         gu.eshift = ilog2(p->emb_dim); gu.n_num = p->n_num; gu.cat0_rowdiv = 1;
         const int Ku = F0 * p->emb_dim + p->n_num;
         if (n_users <= USER_PROJ_SMALL_MAX && (Ku + 3) / 4 * 4 <= USER_PROJ_SMALL_K && p->ldw_proj_user >= (Ku + 3) / 4 * 4) {
-            ProfScope prof("user_proj_small", 2.0 * n_users * dm * Ku, (double)dm * Ku * 4, st);
-            hipLaunchKernelGGL(user_proj_small_kernel, dim3((unsigned)n_users, (unsigned)((dm + 31) / 32)), dim3(256), 0, st, gu, p->w_proj_user,
-                               (int)p->ldw_proj_user, Ku, p->b_proj, U, dm);
+            ProfScope prof("user_proj_small", 2.0 * n_users * du * Ku, (double)du * Ku * 4, st);
+            hipLaunchKernelGGL(user_proj_small_kernel, dim3((unsigned)n_users, (unsigned)((du + 31) / 32)), dim3(256), 0, st, gu, w_user,
+                               (int)p->ldw_proj_user, Ku, b_user, U, du);
             HIP_TRY(hipGetLastError());
         } else {
-            HIP_TRY(linear_wide<EpiLinearT>(p->w_proj_user, nullptr, p->ldw_proj_user, dm, gu, n_users, st, Ku, p->b_proj, U,
-                                            (long long)dm, n_users, dm, 0));
+            HIP_TRY(linear_wide<EpiLinearT>(w_user, nullptr, p->ldw_proj_user, du, gu, n_users, st, Ku, b_user, U,
+                                            (long long)du, n_users, du, 0));
         }
     }
     for (long long r0 = 0; r0 < rows; r0 += w.chunk) {
@@ -827,7 +849,7 @@ extern "C" int amdrec_ranker_forward(const amdrec_ranker_params* p, const int64_
         REQUIRE(use_x3 || !ranker_x3_folded(p), "x3.fold_attn1 is set but a pass of %lld rows would not run the row-owner "
                                                 "engine (the fold needs n_layers >= 1 and x3.min_rows == 1)", m);
         if (use_x3 && hoist && p->ad_proj_cache) {
-            int rc3 = ranker_x3_run(p, nullptr, 0, (const float*)U, (const long long*)ad_rowmap, r0, (int)user_rowdiv,
+            int rc3 = ranker_x3_run(p, nullptr, 0, (const float*)U, (long long)du, (const long long*)ad_rowmap, r0, (int)user_rowdiv,
                                     (long long)(n_ad_rows > 0 ? n_ad_rows : 1), m, X0, out_logits + r0, (long long)ld_logits, st);
             if (rc3) return rc3;
             continue;
@@ -848,7 +870,7 @@ extern "C" int amdrec_ranker_forward(const amdrec_ranker_params* p, const int64_
                                             p->b_proj, X, (long long)dm, m, dm, 0));
         }
         if (use_x3) {
-            int rc3 = ranker_x3_run(p, (const float*)X, (long long)dm, nullptr, nullptr, 0, 1, 0, m, X0, out_logits + r0,
+            int rc3 = ranker_x3_run(p, (const float*)X, (long long)dm, nullptr, 0, nullptr, 0, 1, 0, m, X0, out_logits + r0,
                                     (long long)ld_logits, st);
             if (rc3) return rc3;
             continue;

@@ -39,8 +39,19 @@ static bool x3c_available(const amdrec_ranker_params* p) {
            (p->n_layers == 0 || p->d_ff % 128 == 0) && p->head_h1 % 128 == 0;
 }
 
-// n_phases < 0: the whole chain; cs: the column-split kernel's stream
-static int x3_build(const amdrec_ranker_params* p, int n_phases, x3::Program& G, bool cs = false) {
+constexpr long long X3B4_MAX_ROWS = 256ll * 64;      // one 64-row workgroup per CU
+
+// the first-FFN hidden cache (amdrec_x3_weights.stream_hc) serves this pass: everything it needs is packed, both caches
+// are set, and the pass takes the 128-row shape of the 16-row kernel
+static bool x3_hidden_cache(const amdrec_ranker_params* p, long long rows, bool cs) {
+    return x3_folded(p) && p->x3.variant == 16 && p->x3.stream_hc != nullptr && p->x3.chunks_hc > 0 &&
+           p->x3.params_hc != nullptr && p->x3.w_user_uq != nullptr && p->x3.b_user_uq != nullptr &&
+           p->ad_proj_cache != nullptr && p->ad_hidden_cache != nullptr && p->ld_ad_hidden_cache >= p->d_ff &&
+           p->d_ff % 64 == 0 && p->d_ff >= 128 && !cs && rows > X3B4_MAX_ROWS;
+}
+
+// n_phases < 0: the whole chain; cs: the column-split kernel's stream; hc: the hidden-cache program (x3_hidden_cache)
+static int x3_build(const amdrec_ranker_params* p, int n_phases, x3::Program& G, bool cs = false, bool hc = false) {
     memset(&G, 0, sizeof(G));
     int n = 0, o = 0;                                               // o: running offset into the parameter blob (floats)
     const bool fold = x3_folded(p);
@@ -55,7 +66,7 @@ static int x3_build(const amdrec_ranker_params* p, int n_phases, x3::Program& G,
             o += 768;
         }
         x3::Phase& F = G.ph[n++];
-        F.type = x3::PH_FFN_LN; F.n_steps = p->d_ff / 32; F.b1 = o; F.b2 = o + p->d_ff; F.gamma = o + p->d_ff + 256;
+        F.type = hc && l == 0 ? x3::PH_FFN_LN_CACHED : x3::PH_FFN_LN; F.n_steps = p->d_ff / 32; F.b1 = o; F.b2 = o + p->d_ff; F.gamma = o + p->d_ff + 256;
         F.beta = o + p->d_ff + 512;
         F.sw1 = p->x3.sw_1[l]; F.sw2 = p->x3.sw_2[l]; F.hn = p->x3.hn[l]; F.hb = p->x3.hb[l]; F.ln_eps = p->ln_eps;
         o += p->d_ff + 768;
@@ -72,7 +83,7 @@ static int x3_build(const amdrec_ranker_params* p, int n_phases, x3::Program& G,
     for (int t = 0; t < p->n_tasks; ++t) { G.hb2[t] = o; G.hw3[t] = o + 64; G.hb3[t] = o + 128; o += 132; }
     REQUIRE(p->x3.n_params == x3_param_floats(p), "x3: parameter blob has %lld floats, the architecture needs %lld",
             (long long)p->x3.n_params, x3_param_floats(p));
-    G.params = p->x3.params;
+    G.params = hc ? p->x3.params_hc : p->x3.params;
     G.n_params = (int)p->x3.n_params;
     // chunks consumed by a prefix of the chain (the ring only needs to know where the stream ends)
     const long long per_layer = 16 + 4ll * (p->d_ff / 32);          // W_ov: 16 chunks; FFN: 64 fragment sets per hidden tile
@@ -80,16 +91,15 @@ static int x3_build(const amdrec_ranker_params* p, int n_phases, x3::Program& G,
     const long long hidden_tiles = (long long)p->n_tasks * (p->head_h1 / 32);
     const long long heads = cs ? hidden_tiles * 3 : hidden_tiles * 40 / 16;
     REQUIRE(cs || hidden_tiles * 40 % 16 == 0, "x3: head stream is not a whole number of chunks");
-    const long long total = p->n_layers * per_layer - (fold ? 16 : 0) + 16ll * p->n_cross + heads;   // fold: no layer-1 W_ov
-    const long long have = cs ? p->x3.chunks_cs : p->x3.chunks;
+    // fold: no layer-1 W_ov; hc: no stage 1 of layer 1's FFN (32 of a hidden tile's 64 fragment sets)
+    const long long total = p->n_layers * per_layer - (fold ? 16 : 0) - (hc ? 2ll * (p->d_ff / 32) : 0) + 16ll * p->n_cross + heads;
+    const long long have = cs ? p->x3.chunks_cs : (hc ? p->x3.chunks_hc : p->x3.chunks);
     REQUIRE(total == have, "x3: stream length %lld chunks does not match the architecture (%lld)", have, total);
     G.n_phases = n_phases < 0 || n_phases > n ? n : n_phases;
     G.total_chunks = (int)total;
-    G.stream = reinterpret_cast<const unsigned char*>(cs ? p->x3.stream_cs : p->x3.stream);
+    G.stream = reinterpret_cast<const unsigned char*>(cs ? p->x3.stream_cs : (hc ? p->x3.stream_hc : p->x3.stream));
     return AMDREC_OK;
 }
-
-constexpr long long X3B4_MAX_ROWS = 256ll * 64;      // one 64-row workgroup per CU
 
 // weight elements a row is multiplied with in the program's phases (the LayerNorm-only phase has none)
 static double x3_weight_elements(const x3::Program& G) {
@@ -98,6 +108,7 @@ static double x3_weight_elements(const x3::Program& G) {
         const x3::Phase& P = G.ph[i];
         if (P.type == x3::PH_ATTN_LN || P.type == x3::PH_CROSS) w += 256.0 * 256.0;
         else if (P.type == x3::PH_FFN_LN) w += 2.0 * 256.0 * 32.0 * P.n_steps;
+        else if (P.type == x3::PH_FFN_LN_CACHED) w += 256.0 * 32.0 * P.n_steps;          // stage 2 only
         else if (P.type == x3::PH_HEADS) w += (double)P.n_tasks * (256.0 * 32.0 * P.n_steps + 64.0 * 32.0 * P.n_steps + 64.0);
     }
     return w;
@@ -143,8 +154,9 @@ static int x3_launch(const x3::Program& G, const x3::Input& in, long long rows, 
     {
         // algorithmic FLOPs: 2 * rows * sum over the phases' weight elements (bench.py prices them against bf16 MFMA / 3)
         const double w = x3_weight_elements(G);
+        const double hidden_bytes = in.hcache != nullptr ? 4.0 * 32.0 * G.ph[1].n_steps : 0.0;   // a row of P (Q: one per user)
         ProfScope prof(small ? "ranker_rowowner16_64_x3" : (variant == 16 ? "ranker_rowowner16_128_x3" : "ranker_rowowner_128_x3"),
-                       2.0 * (double)rows * w, (double)rows * (1024.0 + 12.0), st);
+                       2.0 * (double)rows * w, (double)rows * (1024.0 + 12.0 + hidden_bytes), st);
         if (small)
             hipLaunchKernelGGL(x3b4::ranker_x3b_kernel, dim3(grid), dim3(64 * x3b4::WAVES), x3::RING_BYTES + x3::PARAM_FLOATS * 4, st,
                                G, in, rows, scratch, x_out, ld_xout, logits, ld_logits);
@@ -167,21 +179,31 @@ bool ranker_x3_wanted(const amdrec_ranker_params* p, long long rows) {
 }
 bool ranker_x3_folded(const amdrec_ranker_params* p) { return x3_folded(p); }
 size_t ranker_x3_scratch_bytes(long long rows) { return x3_scratch_bytes(rows); }
-int ranker_x3_run(const amdrec_ranker_params* p, const float* X, long long ldx, const float* U, const long long* rowmap,
-                  long long row_base, int rowdiv, long long n_cache, long long rows, float* scratch, float* logits,
-                  long long ld_logits, hipStream_t st) {
-    // one request's pass (<= 4096 rows by default): the column-split kernel, 16 rows per workgroup
+static bool x3_colsplit(const amdrec_ranker_params* p, long long rows) {
     const long long cs_rows = p->x3.cs_max_rows > 0 ? p->x3.cs_max_rows : (p->x3.cs_max_rows < 0 ? 0 : x3c::MAX_ROWS);
-    const bool cs = x3c_available(p) && rows <= cs_rows;
+    return x3c_available(p) && rows <= cs_rows;
+}
+bool ranker_x3_hidden_cache(const amdrec_ranker_params* p, long long rows) {
+    return x3_eligible(p) && x3_hidden_cache(p, rows, x3_colsplit(p, rows));
+}
+// ldu: leading dimension of U; > 256 = the user projection wrote [U | Q] rows (Q = W_1c u_user at U + 256)
+int ranker_x3_run(const amdrec_ranker_params* p, const float* X, long long ldx, const float* U, long long ldu,
+                  const long long* rowmap, long long row_base, int rowdiv, long long n_cache, long long rows, float* scratch,
+                  float* logits, long long ld_logits, hipStream_t st) {
+    // one request's pass (<= 4096 rows by default): the column-split kernel, 16 rows per workgroup
+    const bool cs = x3_colsplit(p, rows);
+    const bool hc = X == nullptr && ldu >= 256 + p->d_ff && x3_hidden_cache(p, rows, cs);
     x3::Program G;
-    int rc = x3_build(p, -1, G, cs);
+    int rc = x3_build(p, -1, G, cs, hc);
     if (rc) return rc;
     x3::Input in{};
+    in.ldu = 256;
     if (X != nullptr) {
         in.X = X; in.ldx = ldx;
     } else {
         in.cache = p->ad_proj_cache; in.ldc = p->ld_ad_proj_cache; in.n_cache = n_cache; in.rowmap = rowmap; in.U = U;
-        in.row_base = row_base; in.rowdiv = rowdiv;
+        in.row_base = row_base; in.rowdiv = rowdiv; in.ldu = ldu;
+        if (hc) { in.hcache = p->ad_hidden_cache; in.ldh = p->ld_ad_hidden_cache; in.Q = U + 256; }
     }
     return x3_launch(G, in, rows, scratch, nullptr, 0, logits, ld_logits, st, cs ? 160 : (int)p->x3.variant);
 }
@@ -223,7 +245,7 @@ extern "C" int amdrec_ranker_x3_prefix(const amdrec_ranker_params* p, const floa
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     float* scratch = reinterpret_cast<float*>(workspace);
     x3::Input in{};
-    in.X = X; in.ldx = ldx;
+    in.X = X; in.ldx = ldx; in.ldu = 256;
     if (x3_folded(p)) {
         // X is x0; the folded chain wants z = x0 + W_ov x0 + b_ov.  z goes to the scratch rows (row r at r * 256): the
         // 32-row kernel later stores a row's x0 of the cross layers over that same row, after its own lane has read it

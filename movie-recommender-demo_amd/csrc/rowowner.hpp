@@ -64,7 +64,10 @@ constexpr int TARGET_EXP = 12;                   // scaled row / matrix maxima l
 
 // PH_LN: LayerNorm alone (gamma / beta), no weights and no stream chunks - layer 1's LN1 when its attention block is
 // folded into the feature projection (amdrec_x3_weights.fold_attn1: the input rows are z = x0 + W_ov x0 + b_ov already)
-enum PhaseType { PH_ATTN_LN = 0, PH_FFN_LN = 1, PH_CROSS = 2, PH_HEADS = 3, PH_LN = 4 };
+// PH_FFN_LN_CACHED (16-row kernel, 128-row shape only; must follow PH_LN): layer 1's FFN with stage 1 served from the
+// hidden cache - the hidden tile is relu((P[ad] + Q[user]) * rstd + c) from two row loads (Input::hcache / Q, rstd handed
+// on by PH_LN, c in the place of b_1 in the blob), the stream holds the stage-2 groups only (amdrec_x3_weights.stream_hc)
+enum PhaseType { PH_ATTN_LN = 0, PH_FFN_LN = 1, PH_CROSS = 2, PH_HEADS = 3, PH_LN = 4, PH_FFN_LN_CACHED = 5 };
 
 struct Phase {
     int type;
@@ -108,9 +111,13 @@ struct Input {
     const float* cache;        // [n_cache][ldc]
     long long ldc, n_cache;
     const long long* rowmap;   // candidate -> cache row (may be nullptr: identity)
-    const float* U;            // [n_users][256]
+    const float* U;            // [n_users][ldu], 256 used
     long long row_base;        // global index of row 0 of this launch (for the user index)
     int rowdiv;
+    long long ldu;             // 256, or 256 + d_ff when the user projection wrote [U | Q] rows
+    const float* hcache;       // PH_FFN_LN_CACHED: P [n_cache][ldh] (rows as in `cache`) and Q [n_users][ldu] (= U + 256)
+    long long ldh;
+    const float* Q;
 };
 
 // ---- parameters: the 4 values of features f0 + 8 g + 4 h + {0..3} of array `off` = one ds_read_b128 from the LDS copy
@@ -543,7 +550,7 @@ __global__ __launch_bounds__(256, 1) void ranker_x3_kernel(Program G, Input in, 
         long long a = in.rowmap ? in.rowmap[gr] : gr;
         a = a < 0 ? 0 : (a >= in.n_cache ? in.n_cache - 1 : a);     // clamped like the gather loader (reported separately)
         load_rows(x, in.cache + a * in.ldc, h);
-        add_rows(x, in.U + (gr / in.rowdiv) * 256, h);              // cache row + the user's half (same order as proj_gather)
+        add_rows(x, in.U + (gr / in.rowdiv) * in.ldu, h);              // cache row + the user's half (same order as proj_gather)
     }
     float* x0_row = scratch + row * 256;                            // this lane's own row (scratch is padded to whole workgroups)
     bool x0_saved = false;

@@ -151,6 +151,10 @@ struct RingT {
         }
         ++issued;
     }
+    // EXTRA: vector-memory loads of the phase's own (PH_FFN_LN_CACHED: hidden-cache rows) that are known to have been
+    // issued AFTER the DMA pieces of the chunk being certified - they sit in the same in-order counter, so the counted wait
+    // leaves room for them too (an EXTRA below the true number only waits longer; above it would certify too early)
+    template <int EXTRA = 0>
     __device__ __forceinline__ void certify_next() {
         if (DBG & 16) {
             const unsigned long long a = __builtin_amdgcn_s_memtime();
@@ -167,8 +171,9 @@ struct RingT {
             // OPT & 512 with the delayed DMA issue (64): a half whose barrier sits behind the issue group has already
             // issued the pieces of one more chunk when it waits
             constexpr int AHEAD = ((OPT & 512) != 0 && (OPT & 64) != 0) ? int(DMA_G0 < LAG_) + int(DMA_G1 < LAG_) : 0;
+            static_assert(EXTRA == 0 || !(OPT & (128 | 512)), "the extra loads are counted for the plain per-chunk barrier");
             if (OPT & 128) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_WAVE * (DEPTH - 2)) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_WAVE * (DEPTH - 1) + AHEAD) : "memory");
+            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_WAVE * (DEPTH - 1) + AHEAD + EXTRA) : "memory");
         }
         if (!(DBG & 2)) __builtin_amdgcn_s_barrier();
         if (!(OPT & 64)) issue();
@@ -217,14 +222,14 @@ struct RingT {
     // GEMM / FFN step starts on a chunk boundary and its loops are unrolled, so the position inside the chunk is known
     // at compile time: the four reads are one base register + immediate offsets, and the ring bookkeeping (slot
     // wrap-around, barrier, DMA) runs once per chunk instead of the per-group address arithmetic and boundary test.
-    template <int G8>                       // position in a PAIR of chunks (0..7); the group in its chunk is G8 & 3
+    template <int G8, int EXTRA = 0>        // position in a PAIR of chunks (0..7); the group in its chunk is G8 & 3
     __device__ __forceinline__ void read4(f16x8 (&f)[4]) {
         constexpr int G = G8 & 3;
         constexpr bool BAR = (OPT & 512) ? false : ((OPT & 128) ? G8 == 0 : G == 0);      // this group opens a barrier interval
         static_assert(G8 >= 0 && G8 < 8 && CHUNK_FRAGS == 16, "four groups of four fragment sets per chunk");
         static_assert(!(OPT & 128) || ((OPT & 64) && DEPTH == 4), "OPT 128 needs OPT 64, no stagger, DEPTH 4");
         staggered_barrier<G>();
-        if (BAR && !(OPT & 32)) certify_next();
+        if (BAR && !(OPT & 32)) certify_next<EXTRA>();
         if (G == 0) next_chunk();
         // DBG & 64 (diagnostic build only): fragment reads for ONE group in four - the LDS -> VGPR traffic a kernel would
         // have in which a fragment set feeds four row tiles (the hybrid row-tile-owner / column-split proposal)
@@ -236,7 +241,7 @@ struct RingT {
             for (int u = 0; u < 4; ++u)
                 f[u] = *reinterpret_cast<const __attribute__((address_space(3))) f16x8*>(cbase + (4 * G + u) * FRAG_BYTES);
         }
-        if (BAR && (OPT & 32)) certify_next();
+        if (BAR && (OPT & 32)) certify_next<EXTRA>();
         issue_at_group<G>();
     }
     // the same with the group index at run time (heads: 10 groups per hidden tile); align() before the first use
@@ -361,7 +366,8 @@ __device__ __forceinline__ void gemm256(RingX& ring, const f16x8 (&xh)[8], const
     gemm256_from<RingX, 0>(ring, xh, xl, acc);
 }
 
-__device__ __forceinline__ void layer_norm(f32x4 (&y)[16], lds_cfloat* pb, int gamma, int beta, float eps) {
+// (returns the row's 1 / sqrt(var + eps): PH_FFN_LN_CACHED scales the cached hidden rows with it)
+__device__ __forceinline__ float layer_norm(f32x4 (&y)[16], lds_cfloat* pb, int gamma, int beta, float eps) {
     float s = 0.f;
 #pragma unroll
     for (int t = 0; t < 16; ++t)
@@ -383,6 +389,7 @@ __device__ __forceinline__ void layer_norm(f32x4 (&y)[16], lds_cfloat* pb, int g
 #pragma unroll
         for (int r = 0; r < 4; ++r) y[t][r] = (y[t][r] - mean) * rstd * ga[r] + be[r];
     }
+    return rstd;
 }
 
 // LayerNorm of y = acc * un (un a power of two: acc * un is exact, and so is sum(acc) * un == sum(acc * un) barring fp32
@@ -468,27 +475,27 @@ __device__ __forceinline__ void init_pair(f32x4& a0, f32x4& a1, lds_cfloat* pb, 
     }
 }
 
-template <class RingX, bool S1, bool S2, int GI>
+template <class RingX, bool S1, bool S2, int GI, int EXTRA = 0>
 __device__ __forceinline__ void ffn_groups(RingX& ring, f16x8 (&cur)[4], const f16x8 (&xh)[8], const f16x8 (&xl)[8],
                                            f32x4& a10, f32x4& a11, f32x4 (&acc2)[16], const f16x8& hh, const f16x8& hl) {
     constexpr int NG = (S1 ? 8 : 0) + (S2 ? 8 : 0);          // groups in this step (a multiple of 4: whole chunks)
     constexpr bool is1 = S1 && (!S2 || (GI & 1) == 0);
     constexpr int u = (S1 && S2) ? GI >> 1 : GI;
     f16x8 nxt[4];
-    if constexpr (GI < NG - 1) ring.template read4<(GI + 1) & 7>(nxt);
+    if constexpr (GI < NG - 1) ring.template read4<(GI + 1) & 7, EXTRA>(nxt);
     ring.timed_landed(cur);
     if constexpr (is1) group6(cur, xh[u], xl[u], a10, a11);
     else group6(cur, hh, hl, acc2[2 * u], acc2[2 * u + 1]);
-    if constexpr (GI < NG - 1) ffn_groups<RingX, S1, S2, GI + 1>(ring, nxt, xh, xl, a10, a11, acc2, hh, hl);
+    if constexpr (GI < NG - 1) ffn_groups<RingX, S1, S2, GI + 1, EXTRA>(ring, nxt, xh, xl, a10, a11, acc2, hh, hl);
 }
 
 // One FFN step: 8 x { stage-1 group (W_1 tiles 2t, 2t+1 at ks = u), stage-2 group (W_2 tiles 2u, 2u+1 at k-step t-1) }
-template <class RingX, bool S1, bool S2>
+template <class RingX, bool S1, bool S2, int EXTRA = 0>
 __device__ __forceinline__ void ffn_step(RingX& ring, const f16x8 (&xh)[8], const f16x8 (&xl)[8], f32x4& a10, f32x4& a11,
                                          f32x4 (&acc2)[16], const f16x8& hh, const f16x8& hl) {
     f16x8 cur[4];
-    ring.template read4<0>(cur);
-    ffn_groups<RingX, S1, S2, 0>(ring, cur, xh, xl, a10, a11, acc2, hh, hl);
+    ring.template read4<0, EXTRA>(cur);
+    ffn_groups<RingX, S1, S2, 0, EXTRA>(ring, cur, xh, xl, a10, a11, acc2, hh, hl);
 }
 
 template <class RingX>
@@ -521,6 +528,88 @@ __device__ __forceinline__ void phase_ffn_ln(RingX& ring, const Phase& P, f32x4 
 #pragma unroll
         for (int r = 0; r < 4; ++r) x[t][r] = acc2[t][r] * un;
     layer_norm(x, pb, P.gamma, P.beta, P.ln_eps);
+}
+
+// ---- PH_FFN_LN_CACHED: layer 1's FFN with stage 1 from the hidden cache (amdrec_x3_weights.stream_hc) ----
+// W_1 x1 + b_1 = rstd * W_1c z + c with W_1c z = P[ad] + Q[user]: hidden tile t (features 32 t .. 32 t + 31) is two 16-byte
+// groups of each row per lane - floats 32 t + 4 g and 32 t + 16 + 4 g, the accumulator layout of the two stage-1 tiles it
+// replaces (row I/O pattern of load_rows: 64 contiguous bytes per row and instruction).
+struct HiddenRows {
+    f32x4 p0, p1, q0, q1;
+};
+// The loads stay in flight across two steps (and the loop's back edge), where the compiler's own wait insertion falls back
+// to vmcnt(0) - which would also drain the ring's DMA once per step.  So they are issued as inline assembly, invisible to
+// it, and waited for by count (wait_hidden) like the ring's DMA pieces.
+__device__ __forceinline__ void load_hidden(HiddenRows& h, const float* prow, const float* qrow, int t) {
+    const float* pp = prow + 32 * t;
+    const float* qq = qrow + 32 * t;
+    asm volatile("global_load_dwordx4 %0, %4, off\n\t"
+                 "global_load_dwordx4 %1, %4, off offset:64\n\t"
+                 "global_load_dwordx4 %2, %5, off\n\t"
+                 "global_load_dwordx4 %3, %5, off offset:64"
+                 : "=&v"(h.p0), "=&v"(h.p1), "=&v"(h.q0), "=&v"(h.q1)
+                 : "v"(pp), "v"(qq)
+                 : "memory");
+}
+// N = vector-memory operations issued after the four loads of `h` (DMA pieces and younger loads of this phase)
+template <int N>
+__device__ __forceinline__ void wait_hidden(HiddenRows& h) {
+    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(h.p0), "+v"(h.p1), "+v"(h.q0), "+v"(h.q1) : "n"(N) : "memory");
+}
+// step t: hidden tile t from `h` (WAIT: see wait_hidden) -> planes, then (LOAD) h <- the rows of step t + 2, then the 8
+// stage-2 groups (2 chunks).  The four loads are issued in front of the step's first chunk barrier; EXTRA: see
+// RingT::certify_next.
+template <class RingX, int EXTRA, int WAIT, bool LOAD>
+__device__ __forceinline__ void cached_step(RingX& ring, const Phase& P, HiddenRows& h, const float* prow, const float* qrow,
+                                            int t, float rstd, float sh, float lim, lds_cfloat* pb, f32x4 (&acc2)[16]) {
+    const f32x4 c0 = param4(pb, P.b1, 2 * t), c1 = param4(pb, P.b1, 2 * t + 1);
+    wait_hidden<WAIT>(h);
+    f32x4 a0, a1;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        a0[r] = __builtin_fmaf(h.p0[r] + h.q0[r], rstd, c0[r]);
+        a1[r] = __builtin_fmaf(h.p1[r] + h.q1[r], rstd, c1[r]);
+    }
+    f16x8 hh, hl, xh[8], xl[8];               // (no stage 1: the x planes are never read)
+    hidden_planes(a0, a1, sh, lim, hh, hl);
+    if (LOAD) load_hidden(h, prow, qrow, t + 2);
+    ffn_step<RingX, false, true, EXTRA>(ring, xh, xl, a0, a1, acc2, hh, hl);
+}
+// x = LN1's output, rstd = its 1 / sqrt(var(z) + eps).  Two steps' rows are in flight (two register sets, refilled as they
+// are consumed): 4 loads per step beside the ring's 4 DMA pieces (2 per chunk, always issued: past the stream's end the
+// ring re-loads its last chunk).  All of them sit in ONE in-order counter, so every wait of the phase is by count:
+//  * a step's rows (WAIT): issued two steps = 8 DMA pieces and one younger set of loads earlier: 12; the first two sets go
+//    out together at the start of the phase (4, 8), and no set follows the one that the last step consumes (8);
+//  * a chunk's DMA (EXTRA, RingT::certify_next): when chunk k + 1 is certified in front of chunk k of step t = k / 2, the
+//    loads issued at the start of steps t - 1 and t are younger than its DMA pieces, which went out four chunks earlier:
+//    8 while both sets exist, 4 in step T - 2, 0 in step T - 1.
+template <class RingX>
+__device__ __forceinline__ void phase_ffn_ln_cached(RingX& ring, const Phase& P, f32x4 (&x)[16], float rstd, const float* prow,
+                                                    const float* qrow, lds_cfloat* pb) {
+    HiddenRows ha, hb;
+    load_hidden(ha, prow, qrow, 0);
+    load_hidden(hb, prow, qrow, 1);
+    float s, inv;
+    row_scale(x, s, inv);
+    const float sh = x3::hidden_scale(fmaf(P.hn * 8192.0f, inv, P.hb));
+    const float k2 = P.sw2 * sh, lim = 60000.f / sh;
+    f32x4 acc2[16];
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+        const f32x4 b = param4(pb, P.b2, t);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc2[t][r] = (x[t][r] + b[r]) * k2;
+    }
+    const int T = P.n_steps;                   // even, >= 4 (x3_build)
+    cached_step<RingX, 8, 4, true>(ring, P, ha, prow, qrow, 0, rstd, sh, lim, pb, acc2);
+    cached_step<RingX, 8, 8, true>(ring, P, hb, prow, qrow, 1, rstd, sh, lim, pb, acc2);
+    for (int t = 2; t < T - 2; t += 2) {
+        cached_step<RingX, 8, 12, true>(ring, P, ha, prow, qrow, t, rstd, sh, lim, pb, acc2);
+        cached_step<RingX, 8, 12, true>(ring, P, hb, prow, qrow, t + 1, rstd, sh, lim, pb, acc2);
+    }
+    cached_step<RingX, 4, 12, false>(ring, P, ha, prow, qrow, T - 2, rstd, sh, lim, pb, acc2);
+    cached_step<RingX, 0, 8, false>(ring, P, hb, prow, qrow, T - 1, rstd, sh, lim, pb, acc2);
+    layer_norm_scaled(acc2, 1.0f / k2, x, pb, P.gamma, P.beta, P.ln_eps);
 }
 
 // row I/O: lane (q, g) moves the 16-byte groups [16 T + 4 g, +4) of row q (64 contiguous bytes per row and instruction)
@@ -683,18 +772,27 @@ __device__ __forceinline__ void run_chain(const Program& G, const Input& in, lon
         long long a = in.rowmap ? in.rowmap[gr] : gr;
         a = a < 0 ? 0 : (a >= in.n_cache ? in.n_cache - 1 : a);
         load_rows(x, in.cache + a * in.ldc, g);
-        add_rows(x, in.U + (gr / in.rowdiv) * 256, g);
+        add_rows(x, in.U + (gr / in.rowdiv) * in.ldu, g);
     }
     // The chain is [encoder phases] [cross phases] [heads] (ranker_x3.hip x3_build), walked as three loops so that x0 - the
     // trunk's output, 64 registers - is live only across the cross layers.
     int p = 0;
+    float rstd = 0.f;                              // of PH_LN, for the PH_FFN_LN_CACHED that follows it
     for (; p < G.n_phases; ++p) {
         const Phase& P = G.ph[p];
         const int type = __builtin_amdgcn_readfirstlane(P.type);
         if (type == x3::PH_ATTN_LN) phase_attn_ln(ring, P, x, pb);
         else if (type == x3::PH_FFN_LN) phase_ffn_ln(ring, P, x, pb);
-        else if (type == x3::PH_LN) layer_norm(x, pb, P.gamma, P.beta, P.ln_eps);     // folded layer-1 attention
-        else break;
+        else if (type == x3::PH_LN) rstd = layer_norm(x, pb, P.gamma, P.beta, P.ln_eps);     // folded layer-1 attention
+        else if (WAVES == 8 && type == x3::PH_FFN_LN_CACHED) {                         // the 128-row shape only (x3_build)
+            if constexpr (WAVES == 8) {
+                const long long gr = in.row_base + rowc;
+                long long a = in.rowmap ? in.rowmap[gr] : gr;
+                a = a < 0 ? 0 : (a >= in.n_cache ? in.n_cache - 1 : a);            // clamped as for the projection cache
+                phase_ffn_ln_cached(ring, P, x, rstd, in.hcache + a * in.ldh + 4 * g, in.Q + (gr / in.rowdiv) * in.ldu + 4 * g,
+                                    pb);
+            }
+        } else break;
     }
     if (p < G.n_phases && __builtin_amdgcn_readfirstlane(G.ph[p].type) == x3::PH_CROSS) {
         f32x4 x0[16];

@@ -502,7 +502,7 @@ __global__ __launch_bounds__(64 * WAVES) void ranker_x3c_kernel(Program G, Input
         long long a = in.rowmap ? in.rowmap[gr] : gr;
         a = a < 0 ? 0 : (a >= in.n_cache ? in.n_cache - 1 : a);
         load_rows(x, in.cache + a * in.ldc, g);
-        add_rows(x, in.U + (gr / in.rowdiv) * 256, g);
+        add_rows(x, in.U + (gr / in.rowdiv) * in.ldu, g);
     }
     const unsigned long long t_begin = (CDBG & 16) ? __builtin_amdgcn_s_memtime() : 0ull;
     Ring ring;
