@@ -462,15 +462,16 @@ __global__ __launch_bounds__(ShapeIvf::NT, 2) void ivf_group_scan_kernel(
 
 // k largest of keys[q][0..n_q) -> sorted (score desc, position asc); fewer than k -> padded (-inf, -1).
 // The k-th largest SCORE is found by a 3-pass radix select over the keys' high words (11 + 11 + 10 bits); every key at or
-// above it is then gathered (the keys above it plus its ties) and the bitonic sort of the full 64-bit keys settles the
+// above it is then gathered (the keys above it plus its ties) and the sort of the full 64-bit keys settles the
 // ties by position.  Four reads of the pool instead of the seven of a select over the whole 64-bit key; only when the
 // boundary score has so many ties that the gather would not fit (k + ties > 2048) does the kernel fall back to that
 // 6-pass select of the exact k-th key.
-// the k best (by 64-bit key, descending) of row[0 .. n): sorted in buf[0 .. have), have = min(n, k) valid entries first
-// (keys of value 0 = empty slots rank last and are reported invalid by write_result).  All 512 threads call.
-__device__ __forceinline__ int select_sorted_keys(const unsigned long long* row, long long n, int k, int* hist, int* scratch,
-                                                  unsigned long long* buf, unsigned long long* sorted, int* count,
-                                                  int sort_mode) {
+// the k best (by 64-bit key, descending) of row[0 .. n): returns them sorted (in `buf` or in `other`, 2048 keys each),
+// have = min(n, k) valid entries first (keys of value 0 = empty slots rank last and are reported invalid by write_result).
+// All 512 threads call.
+__device__ __forceinline__ const unsigned long long* select_sorted_keys(const unsigned long long* row, long long n, int k,
+                                                                        int* hist, int* scratch, unsigned long long* buf,
+                                                                        unsigned long long* other, int* count, int& have) {
     const int tid = threadIdx.x;
     // A key of value 0 is an EMPTY slot, never a row (make_key of a NaN-free score is non-zero): the split select's partial
     // lists are zero-padded, so a pool may hold S * k > k entries of which fewer than k are rows.  Empty slots are skipped
@@ -479,39 +480,13 @@ __device__ __forceinline__ int select_sorted_keys(const unsigned long long* row,
     // and kept an arbitrary 2048 of them - ADVICE r3.)
     unsigned long long kstar = 1ull;          // gather every row by default (n <= k, or fewer than k non-empty keys)
     if (n > k) {
-        uint32_t prefix = 0u, pmask = 0u;
-        int rr = k;
-        bool all_rows = false;
-        const int shifts[3] = {21, 10, 0};
-        const int bits[3] = {11, 11, 10};
-        for (int pass = 0; pass < 3; ++pass) {
-            for (int i = tid; i < 2048; i += 512) hist[i] = 0;
-            __syncthreads();
-            const uint32_t bm = (1u << bits[pass]) - 1u;
-            for (long long i = tid; i < n; i += 512) {
-                const unsigned long long key = row[i];
-                const uint32_t hi = (uint32_t)(key >> 32);
-                if (key != 0ull && (hi & pmask) == prefix) atomicAdd(&hist[(hi >> shifts[pass]) & bm], 1);
-            }
-            __syncthreads();
-            const int bin = find_bin_desc<2048, 512>(hist, rr, scratch);   // -1: fewer than rr non-empty keys (pass 0 only)
-            if (bin < 0) {                                        // block-uniform: the pool holds fewer than k rows
-                all_rows = true;
-                break;
-            }
-            prefix |= (uint32_t)bin << shifts[pass];
-            pmask |= bm << shifts[pass];
-            // keys at or above this bin's lower edge: the k - rr above the bin (rr = the k-th key's rank inside it) + the bin's
-            // own.  If they fit the sort buffer
-            // the remaining passes are not needed - the gather below takes exactly these and the sort finds the k best.
-            // Typical pools stop after the FIRST pass: two walks over the pool instead of four (the select of a large
-            // pool is bound by those walks: 512 queries x 100 000 keys, 0.46 ms).
-            const int at_or_above = (k - rr) + hist[bin];
-            __syncthreads();                                     // hist is cleared by the next pass
-            if (at_or_above <= 2048) break;                      // block-uniform
-        }
-        // every key at or above the k-th largest score's (partial) prefix
-        kstar = all_rows || prefix == 0u ? 1ull : (unsigned long long)prefix << 32;
+        // every key at or above the k-th largest score's (partial) prefix: the select stops once those fit the sort buffer.
+        // Typical pools stop after the FIRST pass: two walks over the pool instead of four (the select of a large pool is
+        // bound by those walks: 512 queries x 100 000 keys, 0.46 ms).
+        const uint32_t prefix = select_prefix_desc<512, 3, 2048>(hist, scratch, k, [&](auto count_key) {
+            for (long long i = tid; i < n; i += 512) count_key(row[i]);
+        });
+        kstar = prefix == 0u ? 1ull : (unsigned long long)prefix << 32;
     }
     for (int attempt = 0; attempt < 2; ++attempt) {
         if (tid == 0) *count = 0;
@@ -549,77 +524,50 @@ __device__ __forceinline__ int select_sorted_keys(const unsigned long long* row,
         __syncthreads();
     }
     const int have_all = *count < 2048 ? *count : 2048;
-    __syncthreads();
-    // gathered keys -> `sorted`, descending.  sort_mode 0: the all-LDS bitonic network on a power of two >= the gathered count
-    // (cheap for a few hundred keys, 66 stages - most behind a block barrier - for 2048); 1: the per-wave register sort +
-    // cross-run ranking of the flat search's finalize (topk_utils.hpp sort_desc_runs; keys are unique, zeros rank last: a fixed
-    // ~4 us whatever the count); 2 (default): the network up to 512 keys, the runs beyond.
-    if (sort_mode == 0 || (sort_mode == 2 && have_all <= 512)) {
-        int P = 2;
-        while (P < have_all) P <<= 1;             // >= k whenever n >= k (k <= 2048)
-        bitonic_desc(buf, P);
-        for (int i = threadIdx.x; i < have_all; i += 512) sorted[i] = buf[i];
-        __syncthreads();
-    } else if (have_all <= 1024) {
-        sort_desc_runs<2>(buf, sorted, have_all);
-    } else {
-        sort_desc_runs<4>(buf, sorted, have_all);
-    }
-    return have_all < k ? have_all : k;
+    have = have_all < k ? have_all : k;
+    // the network up to 512 keys, the runs beyond (A/B of the two forms: profiles/r04_ivf_sort_ab.log)
+    return sort_keys_desc<512>(buf, other, have_all, 512);
 }
 
 __global__ __launch_bounds__(512) void ivf_select_kernel(const unsigned long long* keys, long long pool_ld,
                                                          const long long* n_pool, int k, float* outD,
-                                                         long long* outI, int sort_mode) {
+                                                         long long* outI) {
     __shared__ int hist[2048];
     __shared__ int scratch[514];
     __shared__ __attribute__((aligned(16))) unsigned long long buf[2048];
-    __shared__ __attribute__((aligned(16))) unsigned long long sorted[2048];
+    __shared__ __attribute__((aligned(16))) unsigned long long other[2048];
     __shared__ int count;
     const long long q = blockIdx.x;
-    const int have = select_sorted_keys(keys + q * pool_ld, n_pool[q], k, hist, scratch, buf, sorted, &count, sort_mode);
+    int have;
+    const unsigned long long* sorted = select_sorted_keys(keys + q * pool_ld, n_pool[q], k, hist, scratch, buf, other, &count, have);
     write_result(sorted, have, k, q, outD, outI, 0);
 }
 
 // Few queries with LARGE pools (one request against nlist 100 / nprobe 10 at 1M ads: 100 000 keys, one workgroup walking
 // them four times: 0.14 ms): gridDim.x workgroups per query each select the k best of a slice of the pool into
-// part[q][slice][k]; the workgroup that draws the query's last ticket (agent-scope release / acquire, as in the flat
-// search's fix-up) selects the k best of those and writes the result.  The k best of the pool are among the k best of
-// the slices, and the order is the key order either way: the same result as ivf_select_kernel.  The ticket returns to 0.
+// part[q][slice][k]; the workgroup that draws the query's last ticket selects the k best of those and writes the result.
+// The k best of the pool are among the k best of the slices, and the order is the key order either way: the same result
+// as ivf_select_kernel.  The ticket returns to 0.
 __global__ __launch_bounds__(512) void ivf_select_split_kernel(const unsigned long long* keys, long long pool_ld,
                                                                const long long* n_pool, int k, unsigned long long* part,
-                                                               int* tickets, float* outD, long long* outI, int sort_mode) {
+                                                               int* tickets, float* outD, long long* outI) {
     __shared__ int hist[2048];
     __shared__ int scratch[514];
     __shared__ __attribute__((aligned(16))) unsigned long long buf[2048];
-    __shared__ __attribute__((aligned(16))) unsigned long long sorted[2048];
-    __shared__ int count, last_sh;
+    __shared__ __attribute__((aligned(16))) unsigned long long other[2048];
+    __shared__ int count;
     const long long q = blockIdx.y;
     const int s = blockIdx.x, S = gridDim.x, tid = threadIdx.x;
     const long long n = n_pool[q];
     const long long per = (n + S - 1) / S;
     const long long lo = s * per < n ? s * per : n, hi = lo + per < n ? lo + per : n;
-    const int have = select_sorted_keys(keys + q * pool_ld + lo, hi - lo, k, hist, scratch, buf, sorted, &count, sort_mode);
+    int have;
+    const unsigned long long* sorted = select_sorted_keys(keys + q * pool_ld + lo, hi - lo, k, hist, scratch, buf, other, &count, have);
     unsigned long long* mine = part + (q * S + s) * k;
     for (int i = tid; i < k; i += 512) mine[i] = i < have ? sorted[i] : 0ull;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int t = __hip_atomic_fetch_add(&tickets[q], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_sh = t == S - 1;
-        if (t == S - 1) {
-            __hip_atomic_store(&tickets[q], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // ready for the next call
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    if (!last_sh) return;                                      // block-uniform
-    __syncthreads();                                           // (`sorted` was read above by every thread)
-    const int have2 = select_sorted_keys(part + q * S * k, (long long)S * k, k, hist, scratch, buf, sorted, &count, sort_mode);
-    write_result(sorted, have2, k, q, outD, outI, 0);
+    if (!last_workgroup(&tickets[q], S, true)) return;
+    sorted = select_sorted_keys(part + q * S * k, (long long)S * k, k, hist, scratch, buf, other, &count, have);
+    write_result(sorted, have, k, q, outD, outI, 0);
 }
 
 // ---- index BUILD: max-inner-product assignment and Lloyd iterations (faiss_retrieval.py:83-95, :118: IndexIVFFlat with an
@@ -1054,11 +1002,6 @@ extern "C" int amdrec_ivf_coarse_keys(const float* centroids, int nlist, int64_t
     return AMDREC_OK;
 }
 
-// sort of the gathered keys in the select kernels: 2 = adaptive (default); AMDREC_IVF_SORT = 0 / 1 force one form (A/B runs)
-static int ivf_sort_mode() {
-    static const int m = [] { const char* v = getenv("AMDREC_IVF_SORT"); return v ? atoi(v) : 2; }();
-    return m;
-}
 
 extern "C" int amdrec_ivf_select(const uint64_t* pool_keys, int64_t pool_ld, const int64_t* pool_count, int64_t nq,
                                  int k, float* out_scores, int64_t* out_pos, void* stream) {
@@ -1068,7 +1011,7 @@ extern "C" int amdrec_ivf_select(const uint64_t* pool_keys, int64_t pool_ld, con
     ProfScope prof("ivf_select", 0.0, 0.0, reinterpret_cast<hipStream_t>(stream));
     hipLaunchKernelGGL(ivf_select_kernel, dim3((unsigned)nq), dim3(512), 0, reinterpret_cast<hipStream_t>(stream),
                        (const unsigned long long*)pool_keys, (long long)pool_ld, (const long long*)pool_count, k,
-                       out_scores, (long long*)out_pos, ivf_sort_mode());
+                       out_scores, (long long*)out_pos);
     HIP_TRY(hipGetLastError());
     return AMDREC_OK;
 }
@@ -1088,7 +1031,7 @@ extern "C" int amdrec_ivf_select_split(const uint64_t* pool_keys, int64_t pool_l
     hipLaunchKernelGGL(ivf_select_split_kernel, dim3((unsigned)slices, (unsigned)nq), dim3(512), 0,
                        reinterpret_cast<hipStream_t>(stream), (const unsigned long long*)pool_keys, (long long)pool_ld,
                        (const long long*)pool_count, k, reinterpret_cast<unsigned long long*>(workspace), tickets, out_scores,
-                       (long long*)out_pos, ivf_sort_mode());
+                       (long long*)out_pos);
     HIP_TRY(hipGetLastError());
     return AMDREC_OK;
 }

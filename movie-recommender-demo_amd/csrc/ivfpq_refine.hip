@@ -26,7 +26,6 @@ __global__ __launch_bounds__(512) void rerank_kernel(const void* rows_, long lon
     __shared__ __attribute__((aligned(16))) float qv[2048];
     __shared__ __attribute__((aligned(16))) unsigned long long keys[2048];
     __shared__ __attribute__((aligned(16))) unsigned long long sorted[2048];
-    __shared__ int last_sh;
     const long long q = blockIdx.y;
     const int s = blockIdx.x, S = gridDim.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int per = (kc + S - 1) / S;
@@ -102,40 +101,12 @@ __global__ __launch_bounds__(512) void rerank_kernel(const void* rows_, long lon
     if (S > 1) {
         unsigned long long* list = part + q * kc;
         for (int i = lo + tid; i < hi; i += 512) list[i] = keys[i];
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const int t = __hip_atomic_fetch_add(&tickets[q], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            last_sh = t == S - 1;
-            if (t == S - 1) {
-                __hip_atomic_store(&tickets[q], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // ready for the next call
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-        }
-        __syncthreads();
-        if (!last_sh) return;                                // block-uniform
+        if (!last_workgroup(&tickets[q], S, true)) return;
         for (int i = tid; i < kc; i += 512) keys[i] = list[i];
         __syncthreads();
     }
     // kc keys, zeros = slots without a key: descending = distance ascending, then -inf keys by position, then the zeros
-    const unsigned long long* res;
-    if (kc <= 512) {
-        int P = 2;
-        while (P < kc) P <<= 1;
-        for (int i = kc + tid; i < P; i += 512) keys[i] = 0ull;
-        __syncthreads();
-        bitonic_desc(keys, P);
-        res = keys;
-    } else {
-        for (int i = tid; i < 2048; i += 512) sorted[i] = 0ull;    // the run sort places no zero key
-        __syncthreads();
-        if (kc <= 1024) sort_desc_runs<2>(keys, sorted, kc);
-        else sort_desc_runs<4>(keys, sorted, kc);
-        res = sorted;
-    }
+    const unsigned long long* res = sort_keys_desc<512>(keys, sorted, kc, 512);
     for (int i = tid; i < k; i += 512) {
         const unsigned long long key = res[i];
         outD[q * k + i] = key != 0ull ? 0.f - key_score(key) : INFINITY;

@@ -185,10 +185,7 @@ __global__ __launch_bounds__(512) void finalize_kernel(const unsigned long long*
     const int q = blockIdx.x;
     const int c = cnt[q];
     const int need = (int)(nrows < k ? nrows : k);
-    if (c < need || c > cap) {
-        if (threadIdx.x == 0) { fail[q] = 1; atomicAdd(&fail[gridDim.x], 1); }
-        return;
-    }
+    if (c < need || c > cap) { give_up(fail, q, gridDim.x); return; }
     int P = 2;
     while (P < c) P <<= 1;
     for (int i = threadIdx.x; i < P; i += blockDim.x) keys[i] = (i < c) ? cand[(long long)q * cap + i] : 0ull;
@@ -198,15 +195,13 @@ __global__ __launch_bounds__(512) void finalize_kernel(const unsigned long long*
 }
 
 // step 5: exact streaming scan of one corpus slice for a failed query; the block that finishes a query's LAST slice (a
-// ticket per query, agent-scope release / acquire around it as in cdna_hip_programming.md "in-launch split-K reduction")
-// merges the slices and writes the result.  One launch: in the common case - no failed query - it is the only cost of the
-// fix-up, and two empty launches cost 8 us of a 140 us single-query search.
+// ticket per query: last_workgroup) merges the slices and writes the result.  One launch: in the common case - no failed
+// query - it is the only cost of the fix-up, and two empty launches cost 8 us of a 140 us single-query search.
 __global__ __launch_bounds__(512) void fixup_kernel(const float* X, long long ldx, long long nrows, int d,
                                                     const float* Q, long long ldq, const int* fail, int nq,
                                                     int k, int nslices, unsigned long long* scratch, int* ticket,
                                                     float* outD, long long* outI, long long pos_offset) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];      // merge: k * nslices keys (<= CAND_CAP)
-    __shared__ int last_sh;
     __shared__ __attribute__((aligned(16))) unsigned long long buf[FIX_BUF];
     __shared__ __attribute__((aligned(16))) float qv[2048];
     __shared__ unsigned long long thr;
@@ -238,34 +233,20 @@ __global__ __launch_bounds__(512) void fixup_kernel(const float* X, long long ld
         __syncthreads();
     };
     for (long long row0 = begin; row0 < end; row0 += NW * U) {
-        float part[U];
+        float a[U];
         const f32x4* xr[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             long long r = row0 + w * U + u;
             r = r < end ? r : end - 1;                         // clamped: branch-free loads, result dropped below
             xr[u] = reinterpret_cast<const f32x4*>(X + r * ldx);
-            part[u] = 0.f;
         }
-        // column chunk outermost so that the U row loads of a chunk are in flight together
-        for (int c = lane; c < d4; c += 64) {
-            const f32x4 y = *reinterpret_cast<const f32x4*>(&qv[4 * c]);
-            f32x4 x[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) x[u] = xr[u][c];
-#pragma unroll
-            for (int u = 0; u < U; ++u)        // explicit fma chain: the same rounding sequence in every slot u
-                part[u] = __builtin_fmaf(x[u][3], y[3], __builtin_fmaf(x[u][2], y[2], __builtin_fmaf(x[u][1], y[1],
-                                         __builtin_fmaf(x[u][0], y[0], part[u]))));
-        }
+        dot_rows<U>(xr, qv, d4, lane, a);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            float a = part[u];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
             long long r = row0 + w * U + u;
-            if (lane == 0 && r < end && a == a) {
-                unsigned long long key = make_key(a, (uint32_t)r);
+            if (lane == 0 && r < end && a[u] == a[u]) {
+                unsigned long long key = make_key(a[u], (uint32_t)r);
                 if (key > thr) {
                     int pos = atomicAdd(&count, 1);
                     buf[pos] = key;   // pos < FIX_BUF guaranteed by the compaction rule below
@@ -280,20 +261,8 @@ __global__ __launch_bounds__(512) void fixup_kernel(const float* X, long long ld
     const int c = count;
     unsigned long long* dst = scratch + ((long long)q * nslices + s) * k;
     for (int i = tid; i < k; i += 512) dst[i] = (i < c) ? buf[i] : 0ull;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's slice stores are out
-    __syncthreads();                                           // ... every wave's; also: before count / thr / buf are reset
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (the fence's own wait may be dropped: keep this one)
-        const int t = __hip_atomic_fetch_add(&ticket[q], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_sh = t == nslices - 1;
-        if (t == nslices - 1) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    if (last_sh) {                                             // block-uniform: merge the query's slices
+    // (last_workgroup's first barrier also stands before count / thr / buf are reset)
+    if (last_workgroup(&ticket[q], nslices, false)) {          // merge the query's slices
         const int total = k * nslices;
         int P = 2;
         while (P < total) P <<= 1;
@@ -959,7 +928,7 @@ __global__ __launch_bounds__(256) void bf16_rows_kernel(const float* x, long lon
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const uint32_t u = __float_as_uint(v[e]);
-            h[e] = (v[e] != v[e]) ? 0x7fc0u : ((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+            h[e] = (v[e] != v[e]) ? 0x7fc0u : bf16_rne(u);
             ss += v[e] * v[e];
             const float dv = v[e] - __uint_as_float(h[e] << 16);       // exact: the rounding error of this component
             ds += dv * dv;
@@ -1026,196 +995,64 @@ __global__ __launch_bounds__(NT, NT == 512 ? 2 : 4) void finalize_mixed_kernel(c
     __shared__ int scratch[NT + 2];
     __shared__ float red[16];
     __shared__ int m_sh;
-    __shared__ int seg_n[256], tot_sh, lost_sh, maxn_sh, fill_sh;
+    __shared__ int seg_n[256], maxn_sh, fill_sh;
     constexpr bool GENERAL = CAPK == CAND_CAP;                // threads read the slot-major candidate area directly
     constexpr int NW = NT / 64;
     constexpr int PER = CAPK / NT;                            // candidate keys per thread
     constexpr int OVP = GENERAL ? 2048 / NT : 0;              // + overflow keys per thread (general shape: up to 2048 per query)
     static_assert(!GENERAL || NT == 512, "the general shape is 512 threads");
-    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int q = blockIdx.x, nq = gridDim.x, tid = threadIdx.x;
     const int need = (int)(nrows < k ? nrows : k);
-    auto give_up = [&]() {
-        if (tid == 0) {
-            fail[q] = 1;
-            atomicAdd(&fail[gridDim.x], 1);
-        }
-    };
-    // segment counts: valid slots per segment, their total, and the hits that did not fit
-    if (tid == 0) { tot_sh = 0; lost_sh = 0; maxn_sh = 0; fill_sh = 0; }
-    __syncthreads();
-    for (int g0 = 0; g0 < nseg; g0 += NT) {                   // (nseg <= 256)
-        int sv = 0, lost = 0;
-        if (g0 + tid < nseg) {
-            const int v = segcnt[(long long)q * nseg + g0 + tid];
-            sv = v < seg_cap ? v : seg_cap;
-            lost = v - sv;
-            seg_n[g0 + tid] = sv;
-            if (!GENERAL && sv) atomicMax(&maxn_sh, sv);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            sv += __shfl_xor(sv, o, 64);
-            lost += __shfl_xor(lost, o, 64);
-        }
-        if (lane == 0) {
-            if (sv) atomicAdd(&tot_sh, sv);
-            if (lost) atomicAdd(&lost_sh, lost);
-        }
-    }
+    if (tid == 0) { maxn_sh = 0; fill_sh = 0; m_sh = 0; }
     const int oc = ocnt[q];
-    __syncthreads();
-    const int c = tot_sh + oc;
-    // every hit must be in a segment or in the overflow block, and the list must be usable (block-uniform tests)
-    if (lost_sh != oc || oc > 2048 || c < need || c > CAPK) { give_up(); return; }
-    float ss = 0.f, ds = 0.f;
-    for (int i = tid; i < d; i += NT) {
-        const float v = Q[(long long)q * ldq + i];
-        qv[i] = v;
-        ss += v * v;
-        const uint32_t u = __float_as_uint(v);                    // the same rounding as bf16_rows_kernel applied to the query
-        const float dv = v - __uint_as_float(((u + 0x7fffu + ((u >> 16) & 1u)) >> 16) << 16);
-        ds += dv * dv;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        ss += __shfl_xor(ss, o, 64);
-        ds += __shfl_xor(ds, o, 64);
-    }
-    if (lane == 0) { red[w] = ss; red[8 + w] = ds; }
-    if (tid == 0) m_sh = 0;
+    const int c = segment_counts<NT>(segcnt + (long long)q * nseg, nseg, seg_cap, oc, need, CAPK, seg_n,
+                                     GENERAL ? nullptr : &maxn_sh);
+    if (c < 0) { give_up(fail, q, nq); return; }
     const unsigned long long* blk = cand + (long long)q * cstride;
-    const int nslots = nseg * seg_cap;
-    const int seg_shift = (nseg & (nseg - 1)) == 0 ? 31 - __builtin_clz((unsigned)nseg) : -1;      // nseg a power of two
     unsigned long long mine[PER + OVP];
     if constexpr (GENERAL) {
-        // the candidates stay where the pass put them: thread <- slots tid + NT j of the segment area, validity from the
-        // segment's count (an empty slot is key 0, which no hit can be: its score would have to be NaN)
+        // the candidates stay where the pass put them: thread <- slots tid + NT j of the segment area
 #pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int s_ = tid + NT * j;                       // slot-major: element (slot, segment) at slot * nseg + segment
-            bool ok = false;
-            if (s_ < nslots) {
-                const int slot = seg_shift >= 0 ? s_ >> seg_shift : s_ / nseg;
-                ok = slot < seg_n[s_ - slot * nseg];
-            }
-            mine[j] = ok ? blk[s_] : 0ull;
-        }
+        for (int j = 0; j < PER; ++j) mine[j] = slot_valid(tid + NT * j, nseg, seg_cap, seg_n) ? blk[tid + NT * j] : 0ull;
 #pragma unroll
-        for (int j = 0; j < OVP; ++j) {
-            const int i = tid + NT * j;
-            mine[PER + j] = (i < oc) ? blk[CAND_CAP + i] : 0ull;
-        }
-        __syncthreads();
+        for (int j = 0; j < OVP; ++j) mine[PER + j] = (tid + NT * j < oc) ? blk[CAND_CAP + tid + NT * j] : 0ull;
     } else {
         // short lists: the occupied prefix of the slot-major area (slots below the fullest segment's count) and the overflow
-        // block are compacted through LDS, then dealt to the threads' registers
+        // block are compacted through LDS, then (behind query_eps' barrier) dealt to the threads' registers
         const int lim = maxn_sh * nseg;
-        for (int s_ = tid; s_ < lim; s_ += NT) {
-            const int slot = seg_shift >= 0 ? s_ >> seg_shift : s_ / nseg;
-            if (slot < seg_n[s_ - slot * nseg]) keys[atomicAdd(&fill_sh, 1)] = blk[s_];
-        }
+        for (int s_ = tid; s_ < lim; s_ += NT)
+            if (slot_valid(s_, nseg, seg_cap, seg_n)) keys[atomicAdd(&fill_sh, 1)] = blk[s_];
         for (int i = tid; i < oc; i += NT) keys[atomicAdd(&fill_sh, 1)] = blk[CAND_CAP + i];
-        __syncthreads();
+    }
+    const float eps = query_eps<NT>(Q + (long long)q * ldq, d, qv, red, max_norm);
+    if constexpr (!GENERAL) {
 #pragma unroll
         for (int j = 0; j < PER; ++j) mine[j] = (tid + NT * j < c) ? keys[tid + NT * j] : 0ull;
         __syncthreads();                                      // keys[] is reused for the survivors
     }
-    float qn = 0.f, dqn = 0.f;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) { qn += red[i]; dqn += red[8 + i]; }
-    const float eps = eps_bound(sqrtf(qn), sqrtf(dqn) * 1.0001f, max_norm[0], max_norm[1], d);
-    if (!(eps < INFINITY)) { give_up(); return; }            // NaN / inf norms: exact path (block-uniform)
+    if (!(eps < INFINITY)) { give_up(fail, q, nq); return; }  // NaN / inf norms: exact path (block-uniform)
     if (need == 0) {
         write_result(keys, 0, k, q, outD, outI, pos_offset);
         return;
     }
-    // a_k = need-th largest approximate score (orderable 32-bit image), radix select 11 + 11 + 10 bits
-    uint32_t prefix = 0u, pmask = 0u;
-    int rr = need;
-    const int shifts[3] = {21, 10, 0};
-    const int nbits[3] = {11, 11, 10};
+    // a_k = need-th largest approximate score (orderable 32-bit image); always found: c >= need
+    const uint32_t a_k = select_prefix_desc<NT, 3>(hist, scratch, need, [&](auto count_key) {
 #pragma unroll
-    for (int pass = 0; pass < 3; ++pass) {
-        for (int i = tid; i < 2048; i += NT) hist[i] = 0;
-        __syncthreads();
-        const uint32_t bm = (1u << nbits[pass]) - 1u;
-#pragma unroll
-        for (int j = 0; j < PER + OVP; ++j) {
-            const uint32_t u = (uint32_t)(mine[j] >> 32);
-            if (mine[j] != 0ull && (u & pmask) == prefix) atomicAdd(&hist[(u >> shifts[pass]) & bm], 1);
-        }
-        __syncthreads();
-        const int bin = find_bin_desc<2048, NT>(hist, rr, scratch);       // always found: c >= need >= rr
-        prefix |= (uint32_t)bin << shifts[pass];
-        pmask |= bm << shifts[pass];
-    }
+        for (int j = 0; j < PER + OVP; ++j) count_key(mine[j]);
+    });
     // prune: a row with approx < a_k - 2 eps has exact < a_k - eps <= exact of each of the k best-by-approx rows
-    const float cut = f32_from_orderable(prefix) - 2.f * eps;
+    const float cut = f32_from_orderable(a_k) - 2.f * eps;
 #pragma unroll
     for (int j = 0; j < PER + OVP; ++j)
         if (mine[j] != 0ull && key_score(mine[j]) >= cut) keys[atomicAdd(&m_sh, 1)] = mine[j];
     __syncthreads();
     const int m = m_sh;                                       // need <= m <= c
-    // fp32 re-score, one wave per candidate, 8 candidates (random 1 KB rows: latency-bound) in flight per wave; two
-    // workgroups per CU (<= 128 VGPRs): with 16 in flight the kernel needed 169 and ran one workgroup per CU, its select
-    // and sort phases - barriers and LDS latency - covered by nothing
-    const int d4 = d >> 2;
-    constexpr int RU = 8;
-    for (int i0 = w; i0 < m; i0 += NW * RU) {
-        float a[RU];
-        uint32_t pos[RU];
-        const f32x4* xr[RU];
-#pragma unroll
-        for (int u = 0; u < RU; ++u) {
-            const int i = i0 + NW * u;
-            a[u] = 0.f;
-            pos[u] = key_pos(keys[i < m ? i : i0]);
-            xr[u] = reinterpret_cast<const f32x4*>(X + (long long)pos[u] * ldx);
-        }
-        // column chunk outermost: the RU row loads of one chunk are independent and go out back to back (with the
-        // row loop outside, each row's load had to return before the next row's was issued: measured 100 ns per row)
-        for (int cc = lane; cc < d4; cc += 64) {
-            const f32x4 y = *reinterpret_cast<const f32x4*>(&qv[4 * cc]);
-            f32x4 x[RU];
-#pragma unroll
-            for (int u = 0; u < RU; ++u) x[u] = xr[u][cc];
-#pragma unroll
-            for (int u = 0; u < RU; ++u)       // explicit fma chain: the same rounding sequence in every slot u
-                a[u] = __builtin_fmaf(x[u][3], y[3], __builtin_fmaf(x[u][2], y[2], __builtin_fmaf(x[u][1], y[1],
-                                      __builtin_fmaf(x[u][0], y[0], a[u]))));
-        }
-#pragma unroll
-        for (int u = 0; u < RU; ++u) {
-            float v = a[u];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            const int i = i0 + NW * u;
-            // a NaN re-score (inf - inf in fp32 that the bf16 pass did not produce) ranks last, as in the fix-up scan
-            if (lane == 0 && i < m) keys[i] = (v == v) ? make_key(v, pos[u]) : 0ull;
-        }
-    }
-    __syncthreads();
-    const unsigned long long* sorted = keys;
-    if (NT == 512 && m <= 2048) {                             // (8192 keys of LDS: source and destination both fit)
-        const int N = m <= 1024 ? 1024 : 2048;
-        for (int i = tid; i < N; i += NT) keys[N + i] = 0ull;    // NaN re-scores (key 0) are not placed by the run sort
-        __syncthreads();
-        if constexpr (NT == 512) {
-            if (m <= 1024) sort_desc_runs<2>(keys, keys + N, m);
-            else sort_desc_runs<4>(keys, keys + N, m);
-        }
-        sorted = keys + N;
-    } else {
-        int P2 = 2;
-        while (P2 < m) P2 <<= 1;
-        for (int i = m + tid; i < P2; i += NT) keys[i] = 0ull;
-        __syncthreads();
-        bitonic_desc(keys, P2);
-    }
-    // certificate (block-uniform): rows outside the list have exact < tau + eps
-    const unsigned long long kth = sorted[need - 1];
-    const bool all_rows = (long long)c >= nrows;
-    if (!all_rows && !(kth != 0ull && key_score(kth) >= tau[q] + eps)) { give_up(); return; }
+    // 8 rows in flight per wave, two workgroups per CU (<= 128 VGPRs): with 16 in flight the kernel needed 169 and ran one
+    // workgroup per CU, its select and sort phases - barriers and LDS latency - covered by nothing
+    rescore_keys<NW, 8>(keys, m, X, ldx, qv, d >> 2);
+    // (8192 keys of LDS: the run sort's source and destination both fit)
+    const unsigned long long* sorted = sort_keys_desc<NT>(keys, keys + (m <= 1024 ? 1024 : 2048), m, 0);
+    if (!certify_or_fail(sorted, need, (long long)c >= nrows, tau[q] + eps, fail, q, nq)) return;
     write_result(sorted, m, k, q, outD, outI, pos_offset);
 }
 
@@ -1224,9 +1061,8 @@ __global__ __launch_bounds__(NT, NT == 512 ? 2 : 4) void finalize_mixed_kernel(c
 // mostly launch-to-drain latency; they are gone).  Every workgroup of a query repeats the select + prune on the query's candidates (the same
 // deterministic result in each: redundant, but in parallel), re-scores the survivors whose corpus position falls to it
 // (pos % gridDim.x: a share that does not depend on the order in which a block's threads compacted the survivors), appends
-// the exact keys to the query's list in the workspace, and takes a ticket; the workgroup that draws the LAST ticket (agent-scope
-// release / acquire around it, as in fixup_kernel) sorts the list - sort_desc_runs for <= 2048 survivors -, certifies and
-// writes the result.  Same per-row re-score arithmetic, same prune rule, same certificate as finalize_mixed_kernel.
+// the exact keys to the query's list in the workspace, and takes a ticket; the workgroup that draws the LAST ticket sorts
+// the list, certifies and writes the result.  Re-score, sort and certificate are finalize_mixed_kernel's: the same helpers.
 __global__ __launch_bounds__(512) void finalize_fused_kernel(const unsigned long long* cand, long long cstride, const int* segcnt,
                                                              int nseg, int seg_cap, const int* ocnt, int cap, int k,
                                                              long long nrows, const float* tau, const float* max_norm,
@@ -1238,89 +1074,34 @@ __global__ __launch_bounds__(512) void finalize_fused_kernel(const unsigned long
     __shared__ int hist[2048];
     __shared__ int scratch[514];
     __shared__ float red[16];
-    __shared__ int m_sh, own_sh, base_sh, last_sh;
-    __shared__ int seg_n[256], tot_sh, lost_sh;
+    __shared__ int m_sh, own_sh, base_sh;
+    __shared__ int seg_n[256];
     constexpr int PER = CAND_CAP / 512;
     constexpr int OVP = 4;
     const int q = blockIdx.y, nq = gridDim.y, s = blockIdx.x, S = gridDim.x;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int need = (int)(nrows < k ? nrows : k);
-    auto give_up = [&]() {                                      // every workgroup of the query reaches the same verdict: one reports
-        if (tid == 0 && s == 0) {
-            fail[q] = 1;
-            atomicAdd(&fail[nq], 1);
-        }
-    };
     // the candidate slots are requested before the segment counts that say which of them are valid have arrived (one
     // global round trip instead of two); validity is applied below
     const unsigned long long* blk = cand + (long long)q * cstride;
-    const int nslots = nseg * seg_cap;
     unsigned long long mine[PER + OVP];
 #pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int s_ = tid + 512 * j;
-        mine[j] = s_ < nslots ? blk[s_] : 0ull;
-    }
+    for (int j = 0; j < PER; ++j) mine[j] = tid + 512 * j < nseg * seg_cap ? blk[tid + 512 * j] : 0ull;
 #pragma unroll
     for (int j = 0; j < OVP; ++j) mine[PER + j] = blk[CAND_CAP + tid + 512 * j];
-    if (tid == 0) { tot_sh = 0; lost_sh = 0; }
-    __syncthreads();
-    int sv = 0, lost = 0;
-    if (tid < nseg) {
-        const int v = segcnt[(long long)q * nseg + tid];
-        sv = v < seg_cap ? v : seg_cap;
-        lost = v - sv;
-        seg_n[tid] = sv;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        sv += __shfl_xor(sv, o, 64);
-        lost += __shfl_xor(lost, o, 64);
-    }
-    if (lane == 0 && w * 64 < nseg) {
-        atomicAdd(&tot_sh, sv);
-        if (lost) atomicAdd(&lost_sh, lost);
-    }
-    const int oc = ocnt[q];
-    __syncthreads();
-    const int c = tot_sh + oc;
-    if (lost_sh != oc || oc > 512 * OVP || c < need || c > cap) { give_up(); return; }
-    float ss = 0.f, ds = 0.f;
-    for (int i = tid; i < d; i += 512) {
-        const float v = Q[(long long)q * ldq + i];
-        qv[i] = v;
-        ss += v * v;
-        const uint32_t u = __float_as_uint(v);                    // the same rounding as bf16_rows_kernel applied to the query
-        const float dv = v - __uint_as_float(((u + 0x7fffu + ((u >> 16) & 1u)) >> 16) << 16);
-        ds += dv * dv;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        ss += __shfl_xor(ss, o, 64);
-        ds += __shfl_xor(ds, o, 64);
-    }
-    if (lane == 0) { red[w] = ss; red[8 + w] = ds; }
     if (tid == 0) { m_sh = 0; own_sh = 0; }
-    const int seg_shift = (nseg & (nseg - 1)) == 0 ? 31 - __builtin_clz((unsigned)nseg) : -1;
+    const int oc = ocnt[q];
+    const int c = segment_counts<512>(segcnt + (long long)q * nseg, nseg, seg_cap, oc, need, cap, seg_n);
+    // every workgroup of the query reaches the same verdict: one reports
+    if (c < 0) { if (s == 0) give_up(fail, q, nq); return; }
 #pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int s_ = tid + 512 * j;
-        bool ok = false;
-        if (s_ < nslots) {
-            const int slot = seg_shift >= 0 ? s_ >> seg_shift : s_ / nseg;
-            ok = slot < seg_n[s_ - slot * nseg];
-        }
-        if (!ok) mine[j] = 0ull;
-    }
+    for (int j = 0; j < PER; ++j)
+        if (!slot_valid(tid + 512 * j, nseg, seg_cap, seg_n)) mine[j] = 0ull;
 #pragma unroll
     for (int j = 0; j < OVP; ++j)
         if (tid + 512 * j >= oc) mine[PER + j] = 0ull;
-    __syncthreads();
-    float qn = 0.f, dqn = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { qn += red[i]; dqn += red[8 + i]; }
-    const float eps = eps_bound(sqrtf(qn), sqrtf(dqn) * 1.0001f, max_norm[0], max_norm[1], d);
-    if (!(eps < INFINITY)) { give_up(); return; }
+    const float eps = query_eps<512>(Q + (long long)q * ldq, d, qv, red, max_norm);
+    if (!(eps < INFINITY)) { if (s == 0) give_up(fail, q, nq); return; }
     if (need == 0) {
         if (s == 0) write_result(keys, 0, k, q, outD, outI, pos_offset);
         return;
@@ -1328,27 +1109,12 @@ __global__ __launch_bounds__(512) void finalize_fused_kernel(const unsigned long
     // a_k to its top 22 bits (two radix passes): the remaining 10 bits cleared give a value <= a_k in the orderable image,
     // i.e. a slightly lower cut - a superset of the survivors of the exact a_k (a relative 2^-13 of the score: no
     // measurable number of extra survivors), never a missing one
-    uint32_t prefix = 0u, pmask = 0u;
-    int rr = need;
-    const int shifts[2] = {21, 10};
-    const int nbits[2] = {11, 11};
+    const uint32_t a_k = select_prefix_desc<512, 2>(hist, scratch, need, [&](auto count_key) {
 #pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        for (int i = tid; i < 2048; i += 512) hist[i] = 0;
-        __syncthreads();
-        const uint32_t bm = (1u << nbits[pass]) - 1u;
-#pragma unroll
-        for (int j = 0; j < PER + OVP; ++j) {
-            const uint32_t u = (uint32_t)(mine[j] >> 32);
-            if (mine[j] != 0ull && (u & pmask) == prefix) atomicAdd(&hist[(u >> shifts[pass]) & bm], 1);
-        }
-        __syncthreads();
-        const int bin = find_bin_desc<2048, 512>(hist, rr, scratch);
-        prefix |= (uint32_t)bin << shifts[pass];
-        pmask |= bm << shifts[pass];
-    }
-    // prune (as in finalize_mixed_kernel); this workgroup keeps the survivors at positions pos % S == s
-    const float cut = f32_from_orderable(prefix) - 2.f * eps;
+        for (int j = 0; j < PER + OVP; ++j) count_key(mine[j]);
+    });
+    // prune (finalize_mixed_kernel's rule); this workgroup keeps the survivors at positions pos % S == s
+    const float cut = f32_from_orderable(a_k) - 2.f * eps;
     int n_surv = 0;
 #pragma unroll
     for (int j = 0; j < PER + OVP; ++j)
@@ -1361,89 +1127,18 @@ __global__ __launch_bounds__(512) void finalize_fused_kernel(const unsigned long
     if (lane == 0 && n_surv) atomicAdd(&m_sh, n_surv);
     __syncthreads();
     const int m = m_sh, own = own_sh;                         // need <= m <= c
-    // fp32 re-score of the own share, one wave per candidate, 8 in flight per wave (finalize_mixed_kernel's arithmetic)
-    const int d4 = d >> 2;
-    constexpr int RU = 8;
-    for (int i0 = w; i0 < own; i0 += 8 * RU) {
-        float a[RU];
-        uint32_t pos[RU];
-        const f32x4* xr[RU];
-#pragma unroll
-        for (int u = 0; u < RU; ++u) {
-            const int i = i0 + 8 * u;
-            a[u] = 0.f;
-            pos[u] = key_pos(keys[i < own ? i : i0]);
-            xr[u] = reinterpret_cast<const f32x4*>(X + (long long)pos[u] * ldx);
-        }
-        for (int cc = lane; cc < d4; cc += 64) {
-            const f32x4 y = *reinterpret_cast<const f32x4*>(&qv[4 * cc]);
-            f32x4 x[RU];
-#pragma unroll
-            for (int u = 0; u < RU; ++u) x[u] = xr[u][cc];
-#pragma unroll
-            for (int u = 0; u < RU; ++u)
-                a[u] = __builtin_fmaf(x[u][3], y[3], __builtin_fmaf(x[u][2], y[2], __builtin_fmaf(x[u][1], y[1],
-                                      __builtin_fmaf(x[u][0], y[0], a[u]))));
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");    // keys[i] of this round were read (pos) before they are rewritten
-#pragma unroll
-        for (int u = 0; u < RU; ++u) {
-            float v = a[u];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            const int i = i0 + 8 * u;
-            if (lane == 0 && i < own) keys[i] = (v == v) ? make_key(v, pos[u]) : 0ull;   // NaN re-score: ranks last (key 0)
-        }
-    }
-    __syncthreads();
+    rescore_keys<8, 8>(keys, own, X, ldx, qv, d >> 2);
     if (tid == 0) base_sh = __hip_atomic_fetch_add(&fcount[q], own, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     unsigned long long* list = exact + (long long)q * cap;
     for (int i = tid; i < own; i += 512) list[base_sh + i] = keys[i];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's stores are out
-    __syncthreads();                                           // ... every wave's
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int t = __hip_atomic_fetch_add(&fticket[q], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_sh = t == S - 1;
-        if (t == S - 1) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
+    if (!last_workgroup(&fticket[q], S, false)) return;
+    // the query's last workgroup: all m exact keys are in the list (NaN re-scores as key 0: they sort last)
+    for (int i = tid; i < m; i += 512) keys[i] = list[i];
     __syncthreads();
-    if (!last_sh) return;                                      // block-uniform
-    // the query's last workgroup: all m exact keys are in the list (NaN re-scores as key 0: they sort last, as before)
-    if (m <= 2048) {
-        const int N = m <= 1024 ? 1024 : 2048;
-        // zero keys (NaN re-scores) are not placed by the run sort: the destination starts cleared
-        for (int i = tid; i < N; i += 512) { keys[i] = i < m ? list[i] : 0ull; keys[N + i] = 0ull; }
-        __syncthreads();
-        if (m <= 1024) sort_desc_runs<2>(keys, keys + N, m);
-        else sort_desc_runs<4>(keys, keys + N, m);
-        const unsigned long long* sorted = keys + N;
-        const unsigned long long kth = sorted[need - 1];
-        const bool all_rows = (long long)c >= nrows;
-        if (!all_rows && !(kth != 0ull && key_score(kth) >= tau[q] + eps)) {
-            if (tid == 0) { fail[q] = 1; atomicAdd(&fail[nq], 1); }
-            return;
-        }
-        write_result(sorted, m, k, q, outD, outI, pos_offset);
-        return;
-    }
-    int P2 = 2;
-    while (P2 < m) P2 <<= 1;
-    for (int i = tid; i < P2; i += 512) keys[i] = i < m ? list[i] : 0ull;
-    __syncthreads();
-    bitonic_desc(keys, P2);
-    const unsigned long long kth = keys[need - 1];
-    const bool all_rows = (long long)c >= nrows;
-    if (!all_rows && !(kth != 0ull && key_score(kth) >= tau[q] + eps)) {
-        if (tid == 0) { fail[q] = 1; atomicAdd(&fail[nq], 1); }
-        return;
-    }
-    write_result(keys, m, k, q, outD, outI, pos_offset);
+    const unsigned long long* sorted = sort_keys_desc<512>(keys, keys + (m <= 1024 ? 1024 : 2048), m, 0);
+    if (!certify_or_fail(sorted, need, (long long)c >= nrows, tau[q] + eps, fail, q, nq)) return;
+    write_result(sorted, m, k, q, outD, outI, pos_offset);
 }
 
 __global__ void fill_f32_kernel(float* p, long long n, float v) {

@@ -40,6 +40,25 @@ def _both(xb, xq, k, ad_ids=None):
     return (ids, D), (rids, rD), ora
 
 
+def _n_fixup(xb, xq, k):
+    """Queries of the search (the C entry point of the current engine on the rows as they are) that took the fix-up scan."""
+    from amdrec import _lib
+    from amdrec.index import flat_search, flat_search_mixed
+    n, d = xb.shape
+    X, Q = torch.from_numpy(xb).cuda(), torch.from_numpy(xq).cuda()
+    D = torch.empty((len(xq), k), dtype=torch.float32, device="cuda")
+    I = torch.empty((len(xq), k), dtype=torch.int64, device="cuda")
+    nfix = torch.zeros(1, dtype=torch.int32, device="cuda")
+    if _PREFILTER == "bf16":
+        X16 = torch.empty((n, d), dtype=torch.bfloat16, device="cuda")
+        mx = torch.zeros(2, dtype=torch.float32, device="cuda")
+        _lib.check(_lib.load().amdrec_bf16_rows(_lib.ptr(X), n, d, d, _lib.ptr(X16), d, _lib.ptr(mx), _lib.stream_ptr(X.device)))
+        flat_search_mixed(X, X16, mx, n, Q, k, D, I, n_fixup=nfix)
+    else:
+        flat_search(X, n, Q, k, D, I, n_fixup=nfix)
+    return int(nfix.item())
+
+
 def _check(got, ref, ora, xq, tau=cases.TOPK_TAU):
     ids, D = got
     rids, rD = ref
@@ -64,11 +83,18 @@ def test_small_corpus_all_candidates(n, nq, k):
 @pytest.mark.parametrize("n,nq,k,d", [(50_000, 37, 500, 256), (120_001, 512, 500, 256), (30_000, 64, 2048, 128),
                                       (20_000, 3, 10, 64), (9_000, 257, 100, 32),
                                       (70_000, 1100, 50, 128),      # three 512-query groups in the streaming filter
-                                      (25_000, 40, 100, 96)])       # dim outside {32,64,128,256}: generic bf16 tiles
+                                      (25_000, 40, 100, 96),        # dim outside {32,64,128,256}: generic bf16 tiles
+                                      # > 128 queries with short lists: the one-workgroup-per-query finalize on its small
+                                      # shapes (twice the planned candidate count, 320 / 840, fits 1024 / 2048 keys)
+                                      (20_000, 256, 64, 64), (20_000, 256, 300, 64)])
 def test_sampled_threshold_path(n, nq, k, d):
     xb, xq = _mk(n, d, 3), _mk(nq, d, 4)
     got, ref, ora = _both(xb, xq, k)
     _check(got, ref, ora, xq)
+    if (n, nq) == (20_000, 256):
+        # ... and the finalize itself gave these results: a finalize that always gave up would pass unseen through the
+        # exact fix-up scan
+        assert _n_fixup(xb, xq, k) == 0
 
 
 def test_unnormalised_inputs_are_renormalised_and_not_mutated():

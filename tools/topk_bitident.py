@@ -1,0 +1,165 @@
+"""Dev tool: one seeded pass over the top-k kernels (flat mixed / fp32 search incl. the fused and the per-query finalize on
+its three shapes and the fix-up, IVF select / split select on crafted pools and a real index, IVFPQ re-rank); prints a sha256
+of (scores, positions) per case and one over everything, as one JSON line.  Run it once per build of the library
+(AMDREC_LIB_PATH, amdrec/_lib.py) in fresh processes and compare: profiles/topk_helpers_bitident.log.
+usage: AMDREC_LIB_PATH=/path/to/libamdrec.so python tools/topk_bitident.py"""
+import hashlib
+import json
+import os
+import sys
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, os.path.join(ROOT, "movie-recommender-demo_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from amdrec import _lib, synth  # noqa: E402
+from amdrec.index import FAISSIndex, flat_search, flat_search_mixed  # noqa: E402
+
+lib = _lib.load()
+dev = torch.device("cuda:0")
+total = hashlib.sha256()
+cases = {}
+
+
+def record(name, scores, pos, extra=None):
+    torch.cuda.synchronize()
+    b = scores.cpu().numpy().tobytes() + pos.cpu().numpy().tobytes()
+    total.update(b)
+    cases[name] = {"sha256": hashlib.sha256(b).hexdigest()[:16]}
+    if extra is not None:
+        cases[name].update(extra)
+
+
+def outs(nq, k):
+    return (torch.empty((nq, k), dtype=torch.float32, device=dev), torch.empty((nq, k), dtype=torch.int64, device=dev),
+            torch.zeros(1, dtype=torch.int32, device=dev))
+
+
+def shadow(X):
+    n, d = X.shape
+    X16 = torch.empty((n, d), dtype=torch.bfloat16, device=dev)
+    mx = torch.zeros(2, dtype=torch.float32, device=dev)
+    _lib.check(lib.amdrec_bf16_rows(_lib.ptr(X), n, d, d, _lib.ptr(X16), d, _lib.ptr(mx), _lib.stream_ptr(dev)))
+    return X16, mx
+
+
+def mixed(name, xb, xq, k):
+    X, Q = torch.from_numpy(xb).to(dev), torch.from_numpy(xq).to(dev)
+    X16, mx = shadow(X)
+    D, I, nf = outs(len(xq), k)
+    flat_search_mixed(X, X16, mx, len(xb), Q, k, D, I, n_fixup=nf)
+    record(name, D, I, {"n_fixup": int(nf.item())})
+
+
+def fp32(name, xb, xq, k):
+    X, Q = torch.from_numpy(xb).to(dev), torch.from_numpy(xq).to(dev)
+    D, I, nf = outs(len(xq), k)
+    flat_search(X, len(xb), Q, k, D, I, n_fixup=nf)
+    record(name, D, I, {"n_fixup": int(nf.item())})
+
+
+rng = np.random.default_rng(7)
+# (a) fused finalize: nq = 1, 8, 100; a clustered case with > 2048 survivors of the prune
+xb = synth.unit_corpus(200_000, 256, seed=31)
+for nq in (1, 8, 100):
+    mixed(f"a_mixed_fused_nq{nq}", xb, synth.unit_corpus(nq, 256, seed=32 + nq), 500)
+n, d = 60_000, 128
+xc = (synth.unit_corpus(n, d, seed=23) * rng.uniform(0.2, 4.0, (n, 1))).astype(np.float32)
+qc = (synth.unit_corpus(70, d, seed=24) * rng.uniform(0.5, 2.0, (70, 1))).astype(np.float32)
+xc[1000:4000] = qc[0] / np.linalg.norm(qc[0]) * 3.0 + rng.standard_normal((3000, d)).astype(np.float32) * 1e-5
+mixed("a_mixed_fused_clustered3000_k500", xc, qc, 500)
+mixed("a_mixed_fused_clustered3000_k100", xc, qc, 100)
+# (b) finalize_mixed_kernel's three shapes at 256 queries
+xs = synth.unit_corpus(20_000, 64, seed=3)
+qs = synth.unit_corpus(256, 64, seed=4)
+mixed("b_mixed_nq256_128x1024", xs, qs, 64)
+mixed("b_mixed_nq256_256x2048", xs, qs, 300)
+mixed("b_mixed_nq256_512x8192", xb[:120_001], synth.unit_corpus(256, 256, seed=5), 500)
+qcc = np.concatenate([qc] * 4)[:256].copy()
+mixed("b_mixed_nq256_clustered3000", xc, qcc, 500)
+# (c) non-streaming dim
+mixed("c_mixed_dim72", synth.unit_corpus(30_000, 72, seed=6), synth.unit_corpus(40, 72, seed=7), 100)
+mixed("c_mixed_dim72_nq200", synth.unit_corpus(30_000, 72, seed=6), synth.unit_corpus(200, 72, seed=8), 100)
+# (d) fp32 engine, and massive ties (fix-up) through both engines
+fp32("d_fp32", xb[:50_000], synth.unit_corpus(37, 256, seed=9), 500)
+ties = np.repeat(synth.unit_corpus(1, 256, seed=11), 20_000, axis=0)
+fp32("d_fp32_ties_fixup", ties, synth.unit_corpus(3, 256, seed=12), 500)
+mixed("d_mixed_ties_fixup", ties, synth.unit_corpus(3, 256, seed=12), 500)
+mixed("d_mixed_ties_fixup_nq200", ties, synth.unit_corpus(200, 256, seed=13), 100)
+
+
+# (e) IVF select on crafted pools (keys as common.hpp make_key) and a real IVF index
+def make_keys(scores, pos):
+    b = scores.astype(np.float32).view(np.uint32).astype(np.uint64)
+    o = np.where(b & np.uint64(0x80000000), (~b) & np.uint64(0xffffffff), b | np.uint64(0x80000000))
+    return (o << np.uint64(32)) | ((~pos.astype(np.uint64)) & np.uint64(0xffffffff))
+
+
+POOL = 100_000
+pools, counts = [], []
+
+
+def pool(scores, zeros=0):
+    nn = len(scores)
+    keys = make_keys(scores, rng.permutation(nn))
+    if zeros:
+        keys[rng.choice(nn, zeros, replace=False)] = 0
+    row = np.zeros(POOL, dtype=np.uint64)
+    row[:nn] = keys
+    pools.append(row)
+    counts.append(nn)
+
+
+pool(rng.standard_normal(400))                       # <= 512 gathered: the network
+pool(rng.uniform(0.5, 0.6, 900))                     # one top bin, 900 gathered: runs of 2
+pool(rng.uniform(0.5, 0.6, 1800))                    # 1800 gathered: runs of 4
+pool(rng.standard_normal(POOL))                      # a large pool: several passes
+pool(rng.uniform(0.5, 0.5001, 60_000))               # dense scores: all three passes
+pool(np.full(5000, 0.25))                            # ties beyond the buffer: the 6-pass select
+pool(rng.standard_normal(3000), zeros=2950)          # fewer than k non-empty keys
+pool(rng.standard_normal(50))                        # n <= k
+K = torch.from_numpy(np.stack(pools).view(np.int64)).to(dev)
+C = torch.tensor(counts, dtype=torch.int64, device=dev)
+for k in (100, 500, 2048):
+    D, I, _ = outs(len(counts), k)
+    _lib.check(lib.amdrec_ivf_select(_lib.ptr(K), POOL, _lib.ptr(C), len(counts), k, _lib.ptr(D), _lib.ptr(I), _lib.stream_ptr(dev)))
+    record(f"e_ivf_select_k{k}", D, I)
+    for slices in (4, 16):
+        ws = torch.zeros(len(counts) * slices * k, dtype=torch.int64, device=dev)
+        tk = torch.zeros(len(counts), dtype=torch.int32, device=dev)
+        D2, I2, _ = outs(len(counts), k)
+        _lib.check(lib.amdrec_ivf_select_split(_lib.ptr(K), POOL, _lib.ptr(C), len(counts), k, slices, _lib.ptr(D2), _lib.ptr(I2),
+                                               _lib.ptr(ws), ws.numel() * 8, _lib.ptr(tk), _lib.stream_ptr(dev)))
+        record(f"e_ivf_select_split_k{k}_s{slices}", D2, I2, {"same_as_select": bool(torch.equal(D, D2) and torch.equal(I, I2)),
+                                                             "tickets_zero": bool((tk == 0).all().item())})
+idx = FAISSIndex(256, index_type="IVF", nlist=100, nprobe=10)
+idx.add(xb)
+for nq in (1, 4, 64, 300):
+    q = torch.from_numpy(synth.unit_corpus(nq, 256, seed=40 + nq)).to(dev)
+    for k in (10, 500):
+        ids, sc = idx.search_device(q, k)
+        record(f"e_ivf_index_nq{nq}_k{k}", sc, ids)
+
+# (f) IVFPQ re-rank: fp32 and bf16 rows, kc = 300 / 800 / 2048, one and several slices
+R = torch.from_numpy(xb[:50_000]).to(dev)
+R16 = R.to(torch.bfloat16)
+for nq in (3, 40):
+    Q = torch.from_numpy(synth.unit_corpus(nq, 256, seed=50 + nq)).to(dev)
+    for kc in (300, 800, 2048):
+        cand = np.stack([rng.choice(50_000, kc, replace=False) for _ in range(nq)]).astype(np.int64)
+        cand[:, -7:] = -1
+        cd = torch.from_numpy(cand).to(dev)
+        for name, rows, b16 in (("fp32", R, 0), ("bf16", R16, 1)):
+            for split in (False, True):
+                k = kc // 2
+                D, I, _ = outs(nq, k)
+                ws = torch.zeros(nq * kc, dtype=torch.int64, device=dev) if split else None
+                tk = torch.zeros(nq, dtype=torch.int32, device=dev) if split else None
+                _lib.check(lib.amdrec_ivfpq_rerank(_lib.ptr(rows), b16, 50_000, 256, 256, None, _lib.ptr(Q), nq, 256, _lib.ptr(cd), kc,
+                                                   0, k, _lib.ptr(D), _lib.ptr(I), _lib.ptr(ws) if split else None,
+                                                   nq * kc * 8 if split else 0, _lib.ptr(tk) if split else None,
+                                                   _lib.stream_ptr(dev)))
+                record(f"f_rerank_{name}_nq{nq}_kc{kc}_{'split' if split else 'one'}", D, I)
+
+print(json.dumps({"lib": os.environ.get("AMDREC_LIB_PATH", "(default: the tree's build)"), "cases": cases,
+                  "sha256_all": total.hexdigest()}))
