@@ -76,6 +76,32 @@ __host__ __device__ inline uint32_t key_pos(unsigned long long k) { return ~(uin
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// ---- caller-provided workspaces -------------------------------------------------------
+// Cuts a workspace into 256-byte-aligned sub-buffers, in the order of the take() calls.  ONE layout (a struct that derives
+// from it and cuts in its constructor, or a function) serves a workspace's *_workspace query (null base: it only measures,
+// its pointers are never dereferenced) and the entry that consumes the workspace: size and carve cannot drift apart.
+struct Carver {
+    char* base;
+    size_t next = 0, used = 0;   // offset of the next sub-buffer; end of the last one, without its padding
+    explicit Carver(void* ws) : base(static_cast<char*>(ws)) {}
+    template <class T> T* take(size_t count) {
+        T* p = base ? reinterpret_cast<T*>(base + next) : nullptr;
+        used = next + count * sizeof(T);
+        next = align_up(used, 256);
+        return p;
+    }
+    size_t bytes() const { return next; }
+    // a run of adjacent sub-buffers that one memset clears: m = bytes() before its first take(), bytes_since(m) after its last
+    size_t bytes_since(size_t m) const { return used - m; }
+};
+
+// the check of every workspace-taking entry: present, large enough and (align > 0) aligned
+inline int require_workspace(const void* ws, size_t have, size_t need, size_t align = 0) {
+    if (!ws || have < need) return set_error(AMDREC_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", need, have);
+    if (align && (uintptr_t)ws % align) return set_error(AMDREC_EINVAL, "workspace must be %zu-byte aligned", align);
+    return AMDREC_OK;
+}
+
 // hipFuncSetAttribute applies to the CURRENT device only, so "done once" must be tracked per device (a process may
 // drive several GPUs; a benign race between threads sets an attribute twice).
 struct PerDeviceOnce {

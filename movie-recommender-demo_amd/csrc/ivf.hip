@@ -741,17 +741,28 @@ extern "C" int amdrec_ivf_assign(const float* x, int64_t rows, int64_t ld, int d
     if (rc) return rc;
     if (rows == 0) return AMDREC_OK;
     REQUIRE(assign != nullptr, "assign is null");
-    const size_t need = align_up((size_t)rows * 8, 256);
-    if (!workspace || workspace_bytes < need)
-        return set_error(AMDREC_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if ((rc = require_workspace(workspace, workspace_bytes, align_up((size_t)rows * 8, 256)))) return rc;
     return assign_impl(x, rows, ld, dim, centroids, nlist, ld_centroids, (long long*)assign, best_score,
-                       reinterpret_cast<unsigned long long*>(workspace), reinterpret_cast<hipStream_t>(stream));
+                       static_cast<unsigned long long*>(workspace), reinterpret_cast<hipStream_t>(stream));
 }
+
+// k-means step: xkeys | assign | sums | counts, the last two cleared together
+struct KmeansWs : Carver {
+    unsigned long long* keys; long long *assign, *sums; int* counts;
+    size_t clear_bytes;
+    KmeansWs(int64_t rows, int dim, int nlist, void* ws) : Carver(ws) {
+        keys = take<unsigned long long>(rows);
+        assign = take<long long>(rows);
+        const size_t m = bytes();
+        sums = take<long long>((size_t)nlist * dim);
+        counts = take<int>(nlist);
+        clear_bytes = bytes_since(m);
+    }
+};
 
 extern "C" int amdrec_ivf_kmeans_workspace(int64_t rows, int dim, int nlist, size_t* bytes) {
     REQUIRE(bytes != nullptr && rows >= 0 && dim >= 4 && nlist >= 1, "bad arguments");
-    *bytes = align_up((size_t)rows * 8, 256) + align_up((size_t)rows * 8, 256) + align_up((size_t)nlist * dim * 8, 256) +
-             align_up((size_t)nlist * 4, 256);
+    *bytes = KmeansWs(rows, dim, nlist, nullptr).bytes();
     return AMDREC_OK;
 }
 
@@ -760,22 +771,15 @@ extern "C" int amdrec_ivf_kmeans_step(const float* x, int64_t rows, int64_t ld, 
     int rc = assign_check(x, rows, ld, dim, centroids, nlist, ld_centroids);
     if (rc) return rc;
     if (rows == 0) return AMDREC_OK;
-    size_t need = 0;
-    amdrec_ivf_kmeans_workspace(rows, dim, nlist, &need);
-    if (!workspace || workspace_bytes < need)
-        return set_error(AMDREC_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    const KmeansWs w(rows, dim, nlist, workspace);
+    if ((rc = require_workspace(workspace, workspace_bytes, w.bytes()))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    char* ws = reinterpret_cast<char*>(workspace);
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws);
-    long long* assign = reinterpret_cast<long long*>(ws + align_up((size_t)rows * 8, 256));
-    long long* sums = reinterpret_cast<long long*>(ws + 2 * align_up((size_t)rows * 8, 256));
-    int* counts = reinterpret_cast<int*>(reinterpret_cast<char*>(sums) + align_up((size_t)nlist * dim * 8, 256));
-    rc = assign_impl(x, rows, ld, dim, centroids, nlist, ld_centroids, assign, nullptr, keys, st);
+    rc = assign_impl(x, rows, ld, dim, centroids, nlist, ld_centroids, w.assign, nullptr, w.keys, st);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(sums, 0, align_up((size_t)nlist * dim * 8, 256) + (size_t)nlist * 4, st));
+    HIP_TRY(hipMemsetAsync(w.sums, 0, w.clear_bytes, st));
     hipLaunchKernelGGL(ivf_accumulate_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, (long long)rows,
-                       (long long)ld, dim, assign, sums, counts);
-    hipLaunchKernelGGL(ivf_finish_centroids_kernel, dim3((unsigned)((nlist + 3) / 4)), dim3(256), 0, st, sums, counts, nlist,
+                       (long long)ld, dim, w.assign, w.sums, w.counts);
+    hipLaunchKernelGGL(ivf_finish_centroids_kernel, dim3((unsigned)((nlist + 3) / 4)), dim3(256), 0, st, w.sums, w.counts, nlist,
                        dim, centroids, (long long)ld_centroids);
     HIP_TRY(hipGetLastError());
     return AMDREC_OK;
@@ -792,12 +796,10 @@ extern "C" int amdrec_ivf_group(const int64_t* probes, int64_t ld_probes, int64_
     REQUIRE(nq * (int64_t)nprobe < (1ll << 31), "too many (query, probe) pairs for one call");
     REQUIRE(probes && list_len && pool_base && pool_count && pair_query && pair_probe && group_off && qtile_prefix, "null pointer");
     const long long npairs = nq * nprobe;
-    const size_t need = align_up((size_t)(nlist + 1) * 4, 256) + align_up((size_t)npairs * 4, 256);
-    if (!workspace || workspace_bytes < need)
-        return set_error(AMDREC_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    Carver c(workspace);
+    int *cnt = c.take<int>((size_t)nlist + 1), *rank = c.take<int>(npairs);
+    if (int rc = require_workspace(workspace, workspace_bytes, c.bytes())) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int* cnt = reinterpret_cast<int*>(workspace);
-    int* rank = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + align_up((size_t)(nlist + 1) * 4, 256));
     HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)(nlist + 1) * 4, st));
     hipLaunchKernelGGL(ivf_group_count_kernel, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st,
                        (const long long*)probes, (long long)ld_probes, nprobe, npairs, nlist, cnt, rank);
@@ -1024,9 +1026,7 @@ extern "C" int amdrec_ivf_select_split(const uint64_t* pool_keys, int64_t pool_l
     if (nq <= 0) return AMDREC_OK;
     REQUIRE(pool_keys && pool_count && out_scores && out_pos && tickets, "null pointer");
     const size_t need = (size_t)nq * slices * k * 8;
-    if (!workspace || workspace_bytes < need)
-        return set_error(AMDREC_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    REQUIRE(((uintptr_t)workspace % 16) == 0, "workspace must be 16-byte aligned");
+    if (int rc = require_workspace(workspace, workspace_bytes, need, 16)) return rc;
     ProfScope prof("ivf_select", 0.0, 0.0, reinterpret_cast<hipStream_t>(stream));
     hipLaunchKernelGGL(ivf_select_split_kernel, dim3((unsigned)slices, (unsigned)nq), dim3(512), 0,
                        reinterpret_cast<hipStream_t>(stream), (const unsigned long long*)pool_keys, (long long)pool_ld,

@@ -318,12 +318,25 @@ extern "C" int amdrec_ivfpq_encode(const float* x, int64_t rows, int64_t ld, int
                        reinterpret_cast<hipStream_t>(stream));
 }
 
+// codebook training step: codes | sums | counts, the last two cleared together
+struct TrainWs : Carver {
+    unsigned char* codes; long long* sums; int* counts;
+    size_t clear_bytes;
+    TrainWs(int64_t rows, int dim, int m, void* ws) : Carver(ws) {
+        codes = take<unsigned char>((size_t)rows * m);
+        const size_t mk = bytes();
+        sums = take<long long>((size_t)PQ_KSUB * dim);
+        counts = take<int>((size_t)m * PQ_KSUB);
+        clear_bytes = bytes_since(mk);
+    }
+};
+
 extern "C" int amdrec_ivfpq_train_workspace(int64_t rows, int dim, int m, size_t* bytes) {
     REQUIRE(bytes != nullptr, "null pointer");
     int rc = pq_check(dim, m);
     if (rc) return rc;
     REQUIRE(rows >= 0 && rows <= (1ll << 20), "rows=%lld out of range [0, 2^20]", (long long)rows);
-    *bytes = align_up((size_t)rows * m, 256) + align_up((size_t)PQ_KSUB * dim * 8, 256) + align_up((size_t)m * PQ_KSUB * 4, 256);
+    *bytes = TrainWs(rows, dim, m, nullptr).bytes();
     return AMDREC_OK;
 }
 
@@ -336,21 +349,17 @@ extern "C" int amdrec_ivfpq_train_step(const float* x, int64_t rows, int64_t ld,
     rc = rows_check(x, rows, ld, dim, assign, centroids, ld_centroids, nlist, codebooks);
     if (rc) return rc;
     if (rows == 0) return AMDREC_OK;
-    if (!workspace || workspace_bytes < need)
-        return set_error(AMDREC_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if ((rc = require_workspace(workspace, workspace_bytes, need))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    char* ws = reinterpret_cast<char*>(workspace);
-    unsigned char* codes = reinterpret_cast<unsigned char*>(ws);
-    long long* sums = reinterpret_cast<long long*>(ws + align_up((size_t)rows * m, 256));
-    int* counts = reinterpret_cast<int*>(reinterpret_cast<char*>(sums) + align_up((size_t)PQ_KSUB * dim * 8, 256));
-    rc = encode_impl(x, rows, ld, dim, (const long long*)assign, centroids, ld_centroids, nlist, codebooks, m, codes, st);
+    const TrainWs w(rows, dim, m, workspace);
+    rc = encode_impl(x, rows, ld, dim, (const long long*)assign, centroids, ld_centroids, nlist, codebooks, m, w.codes, st);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(sums, 0, align_up((size_t)PQ_KSUB * dim * 8, 256) + (size_t)m * PQ_KSUB * 4, st));
+    HIP_TRY(hipMemsetAsync(w.sums, 0, w.clear_bytes, st));
     hipLaunchKernelGGL(pq_accumulate_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, (long long)rows,
-                       (long long)ld, dim, dim / m, m, (const long long*)assign, centroids, (long long)ld_centroids, nlist, codes,
-                       sums, counts);
+                       (long long)ld, dim, dim / m, m, (const long long*)assign, centroids, (long long)ld_centroids, nlist, w.codes,
+                       w.sums, w.counts);
     const long long ncb = (long long)PQ_KSUB * dim;
-    hipLaunchKernelGGL(pq_finish_kernel, dim3((unsigned)((ncb + 255) / 256)), dim3(256), 0, st, sums, counts, m, dim / m,
+    hipLaunchKernelGGL(pq_finish_kernel, dim3((unsigned)((ncb + 255) / 256)), dim3(256), 0, st, w.sums, w.counts, m, dim / m,
                        codebooks);
     HIP_TRY(hipGetLastError());
     return AMDREC_OK;

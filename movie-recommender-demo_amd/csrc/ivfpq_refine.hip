@@ -150,9 +150,7 @@ extern "C" int amdrec_ivfpq_rerank(const void* rows, int rows_bf16, int64_t nrow
     int slices = workspace && tickets ? rerank_slices(nq, kc) : 1;
     if (slices > 1) {
         const size_t need = (size_t)nq * kc * 8;
-        if (workspace_bytes < need)
-            return set_error(AMDREC_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-        REQUIRE(((uintptr_t)workspace % 8) == 0, "workspace must be 8-byte aligned");
+        if (int rc = require_workspace(workspace, workspace_bytes, need, 8)) return rc;
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ProfScope prof("ivfpq_rerank", 3.0 * nq * kc * dim, (double)nq * kc * dim * (rows_bf16 ? 2 : 4), st);

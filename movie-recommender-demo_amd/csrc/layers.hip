@@ -520,18 +520,22 @@ static int tower_check(const amdrec_tower_params* p) {
     return AMDREC_OK;
 }
 
-static size_t tower_ws_bytes(const amdrec_tower_params* p, long long rows) {
-    long long chunk = rows < ROW_CHUNK ? rows : ROW_CHUNK;
-    int wmax = 4;
-    for (int l = 1; l < p->n_layers; ++l) wmax = p->dims[l] > wmax ? p->dims[l] : wmax;
-    return align_up((size_t)chunk * wmax * 4, 256) * 2;
-}
+// two ping-pong buffers of one row chunk at the widest hidden layer
+struct TowerWs : Carver {
+    float* bufs[2]; long long chunk;
+    TowerWs(const amdrec_tower_params* p, long long rows, void* ws) : Carver(ws) {
+        chunk = rows < ROW_CHUNK ? rows : ROW_CHUNK;
+        int wmax = 4;
+        for (int l = 1; l < p->n_layers; ++l) wmax = p->dims[l] > wmax ? p->dims[l] : wmax;
+        for (float*& b : bufs) b = take<float>((size_t)chunk * wmax);
+    }
+};
 
 extern "C" int amdrec_tower_workspace(const amdrec_tower_params* p, int64_t rows, size_t* bytes) {
     int rc = tower_check(p);
     if (rc) return rc;
     REQUIRE(bytes && rows >= 0, "bad arguments");
-    *bytes = tower_ws_bytes(p, rows);
+    *bytes = TowerWs(p, rows, nullptr).bytes();
     return AMDREC_OK;
 }
 
@@ -550,14 +554,8 @@ extern "C" int amdrec_tower_forward(const amdrec_tower_params* p, const int64_t*
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     REQUIRE(cat && out && (num || p->n_num == 0), "null pointer");
     REQUIRE(ld_out % 4 == 0 && ld_out >= p->dims[p->n_layers], "bad ld_out");
-    size_t need = tower_ws_bytes(p, rows);
-    if (!workspace || workspace_bytes < need)
-        return set_error(AMDREC_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    const long long chunk = rows < ROW_CHUNK ? rows : ROW_CHUNK;
-    int wmax = 4;
-    for (int l = 1; l < p->n_layers; ++l) wmax = p->dims[l] > wmax ? p->dims[l] : wmax;
-    float* bufs[2] = {reinterpret_cast<float*>(workspace),
-                      reinterpret_cast<float*>((char*)workspace + align_up((size_t)chunk * wmax * 4, 256))};
+    const TowerWs w(p, rows, workspace);
+    if ((rc = require_workspace(workspace, workspace_bytes, w.bytes()))) return rc;
     if (bad_index_flag) {
         long long n = rows * p->n_feat;
         hipLaunchKernelGGL(check_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
@@ -567,8 +565,8 @@ extern "C" int amdrec_tower_forward(const amdrec_tower_params* p, const int64_t*
         HIP_TRY(tower_small_run(p, (const long long*)cat, num, rows, out, (long long)ld_out, st));
         return AMDREC_OK;
     }
-    for (long long r0 = 0; r0 < rows; r0 += chunk) {
-        const long long m = rows - r0 < chunk ? rows - r0 : chunk;
+    for (long long r0 = 0; r0 < rows; r0 += w.chunk) {
+        const long long m = rows - r0 < w.chunk ? rows - r0 : w.chunk;
         EmbConcatRows g{};
         g.tables = p->tables; g.off = p->table_off; g.card = p->cards;
         g.cat0 = (const long long*)cat; g.cat1 = nullptr; g.rowmap1 = nullptr;
@@ -589,7 +587,7 @@ extern "C" int amdrec_tower_forward(const amdrec_tower_params* p, const int64_t*
                              : linear_wide<EpiL2NormT>(p->w[l], nullptr, p->ldw[l], nout, dense(cur, m, curw, curw), m, st,
                                                        p->dims[l], p->b[l], dst, (long long)ld_out, m, nout, 1e-12f);
             } else {
-                float* dst = bufs[l & 1];
+                float* dst = w.bufs[l & 1];
                 e = (l == 0) ? linear<EpiLinearT>(p->w[l], nullptr, p->ldw[l], nout, g, m, st, p->dims[l], p->b[l], dst,
                                                   (long long)nout, m, nout, 1)
                              : linear<EpiLinearT>(p->w[l], nullptr, p->ldw[l], nout, dense(cur, m, curw, curw), m, st,
@@ -629,34 +627,29 @@ static int ranker_check(const amdrec_ranker_params* p) {
     return AMDREC_OK;
 }
 
-struct RankerWs {
-    size_t off_x, off_t, off_x0, off_h, off_u, bytes;
-    long long chunk;
+struct RankerWs : Carver {
+    float *X, *T, *X0, *H, *U; long long chunk;
+    RankerWs(const amdrec_ranker_params* p, long long rows, void* ws) : Carver(ws) {
+        chunk = rows < ROW_CHUNK ? rows : ROW_CHUNK;
+        if (chunk < 1) chunk = 1;
+        const size_t dm = (size_t)chunk * p->d_model;
+        long long hw = p->d_ff;
+        long long headw = (long long)p->n_tasks * (p->head_h1 + p->head_h2);
+        if (headw > hw) hw = headw;
+        X = take<float>(dm);
+        T = take<float>(dm);
+        // X0 doubles as the row-owner engine's x0 scratch, which is addressed in whole 128-row workgroups
+        X0 = take<float>((size_t)((chunk + 127) / 128 * 128) * p->d_model);
+        H = take<float>((size_t)chunk * hw);
+        U = take<float>((size_t)(rows > 0 ? rows : 0) * p->d_model);   // upper bound: one user row per batch row
+    }
 };
-static RankerWs ranker_ws(const amdrec_ranker_params* p, long long rows, long long n_users) {
-    RankerWs w;
-    w.chunk = rows < ROW_CHUNK ? rows : ROW_CHUNK;
-    if (w.chunk < 1) w.chunk = 1;
-    size_t dm = (size_t)w.chunk * p->d_model * 4;
-    long long hw = p->d_ff;
-    long long headw = (long long)p->n_tasks * (p->head_h1 + p->head_h2);
-    if (headw > hw) hw = headw;
-    size_t o = 0;
-    w.off_x = o;  o = align_up(o + dm, 256);
-    w.off_t = o;  o = align_up(o + dm, 256);
-    // X0 doubles as the row-owner engine's x0 scratch, which is addressed in whole 128-row workgroups
-    w.off_x0 = o; o = align_up(o + (size_t)((w.chunk + 127) / 128 * 128) * p->d_model * 4, 256);
-    w.off_h = o;  o = align_up(o + (size_t)w.chunk * hw * 4, 256);
-    w.off_u = o;  o = align_up(o + (size_t)(n_users > 0 ? n_users : 0) * p->d_model * 4, 256);
-    w.bytes = o;
-    return w;
-}
 
 extern "C" int amdrec_ranker_workspace(const amdrec_ranker_params* p, int64_t rows, size_t* bytes) {
     int rc = ranker_check(p);
     if (rc) return rc;
     REQUIRE(bytes && rows >= 0, "bad arguments");
-    *bytes = ranker_ws(p, rows, rows).bytes;      // upper bound: one user row per batch row
+    *bytes = RankerWs(p, rows, nullptr).bytes();
     return AMDREC_OK;
 }
 
@@ -692,10 +685,8 @@ static int project_ads(const amdrec_ranker_params* p, const float* W, int nout, 
     REQUIRE(ad_cat && out, "null pointer");
     REQUIRE(ld_out >= dm && ld_out % 4 == 0 && ((uintptr_t)out % 16) == 0, "bad output layout");
     REQUIRE(n_ads < (1ll << 31) - 1024, "n_ads out of range");
-    const size_t need = align_up((size_t)dm * 4, 256);
-    if (!workspace || workspace_bytes < need)
-        return set_error(AMDREC_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    float* zero = reinterpret_cast<float*>(workspace);
+    if ((rc = require_workspace(workspace, workspace_bytes, align_up((size_t)dm * 4, 256)))) return rc;
+    float* zero = static_cast<float*>(workspace);
     HIP_TRY(hipMemsetAsync(zero, 0, (size_t)dm * 4, st));
     EmbConcatRows ga{};
     ga.tables = p->tables; ga.off = p->table_off + F0; ga.card = p->cards + F0;
@@ -780,15 +771,9 @@ extern "C" int amdrec_ranker_forward(const amdrec_ranker_params* p, const int64_
     const bool hoist = user_rowdiv > 1 && p->w_proj_user && p->w_proj_ad && p->n_ad_feat > 0 &&
                        (p->n_user_feat > 0 || p->n_num > 0);
     const long long n_users = hoist ? (rows + user_rowdiv - 1) / user_rowdiv : 0;
-    RankerWs w = ranker_ws(p, rows, rows);        // same layout as the workspace query
-    if (!workspace || workspace_bytes < w.bytes)
-        return set_error(AMDREC_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", w.bytes, workspace_bytes);
-    char* ws = reinterpret_cast<char*>(workspace);
-    float* X = reinterpret_cast<float*>(ws + w.off_x);
-    float* T = reinterpret_cast<float*>(ws + w.off_t);
-    float* X0 = reinterpret_cast<float*>(ws + w.off_x0);
-    float* H = reinterpret_cast<float*>(ws + w.off_h);
-    float* U = reinterpret_cast<float*>(ws + w.off_u);
+    const RankerWs w(p, rows, workspace);
+    if ((rc = require_workspace(workspace, workspace_bytes, w.bytes()))) return rc;
+    float *X = w.X, *T = w.T, *X0 = w.X0, *H = w.H, *U = w.U;
     const int dm = p->d_model, F0 = p->n_user_feat, F = p->n_user_feat + p->n_ad_feat;
 
     if (bad_index_flag) {

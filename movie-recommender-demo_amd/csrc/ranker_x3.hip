@@ -240,8 +240,7 @@ extern "C" int amdrec_ranker_x3_prefix(const amdrec_ranker_params* p, const floa
     const bool heads = G.n_phases == 2 * p->n_layers + p->n_cross + 1;
     REQUIRE(!heads || (logits != nullptr && ld_logits >= rows), "the full chain needs a logits buffer");
     const size_t need = x3_scratch_bytes(rows);
-    if (!workspace || workspace_bytes < need)
-        return set_error(AMDREC_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if ((rc = require_workspace(workspace, workspace_bytes, need))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     float* scratch = reinterpret_cast<float*>(workspace);
     x3::Input in{};

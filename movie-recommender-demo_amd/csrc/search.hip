@@ -1153,11 +1153,15 @@ struct SearchPlan {
     int rank;                // r
     int nslices;             // fix-up slices
     long long target;        // expected candidates per query (0: every row is a candidate)
-    size_t off_tau, off_cnt, off_ocnt, off_ticket, off_fcount, off_fticket, off_fail, off_segcnt, off_cand, off_sample, off_fix, off_q16, off_exact, bytes;
+    float *tau, *sample;     // the workspace: make_plan cuts it
+    int *cnt, *ocnt, *ticket, *fcount, *fticket, *fail, *segcnt;   // cnt .. fail are cleared together: clear_bytes from cnt
+    unsigned long long *cand, *fix, *exact;
+    uint16_t* q16; size_t bytes, clear_bytes;
 };
 
-// dim16 > 0: the mixed-precision search, which also keeps a bf16 copy of the queries in the workspace
-static int make_plan(long long nq, long long nrows, int k, SearchPlan& pl, int dim16 = 0) {
+// dim16 > 0: the mixed-precision search, which also keeps a bf16 copy of the queries.  base: the workspace to cut, or nullptr to size it
+static SearchPlan make_plan(long long nq, long long nrows, int k, int dim16, void* base) {
+    SearchPlan pl;
     long long nt = (nrows + SAMPLE_G - 1) / SAMPLE_G;
     // expected candidates per query: far enough above k that an unlucky sample cannot undershoot it (the estimate's
     // sigma is ~target/8: k = 500 -> 1400 = k + 5.1 sigma), small enough that the finalize sort stays at 2048 keys for
@@ -1194,51 +1198,67 @@ static int make_plan(long long nq, long long nrows, int k, SearchPlan& pl, int d
     }
     int ns = CAND_CAP / (k > 0 ? k : 1);
     pl.nslices = ns < 1 ? 1 : (ns > 16 ? 16 : ns);
-    size_t o = 0;
-    pl.off_tau = o;    o = align_up(o + (size_t)nq * 4, 256);
-    pl.off_cnt = o;    o = align_up(o + (size_t)nq * 4, 256);                   // cnt | ocnt | ticket | fail: cleared together
-    pl.off_ocnt = o;   o = align_up(o + (size_t)nq * 4, 256);
-    pl.off_ticket = o; o = align_up(o + (size_t)nq * 4, 256);                   // fix-up: slices finished per query
-    pl.off_fcount = o; o = align_up(o + (size_t)nq * 4, 256);                   // fused finalize (small batches): exact keys appended,
-    pl.off_fticket = o; o = align_up(o + (size_t)nq * 4, 256);                  // blocks finished per query
-    pl.off_fail = o;   o = align_up(o + (size_t)(nq + 1) * 4, 256);
-    pl.off_segcnt = o; o = align_up(o + (size_t)(dim16 ? nq : 0) * 256 * 4, 256);  // streaming pass: hits per (query, segment)
-    pl.off_cand = o;   o = align_up(o + (size_t)nq * CAND_CAP * 8 * (dim16 ? 2 : 1), 256);   // mixed: + overflow block
-    pl.off_sample = o; o = align_up(o + (size_t)nq * (size_t)pl.n_sample * 4, 256);
-    pl.off_fix = o;    o = align_up(o + (size_t)nq * pl.nslices * k * 8, 256);
-    pl.off_q16 = o;    o = align_up(o + (size_t)nq * (size_t)dim16 * 2, 256);
-    pl.off_exact = o;  o = align_up(o + (size_t)(dim16 && nq <= FUSED_MAX_NQ ? nq : 0) * CAND_CAP * 8, 256);   // fused finalize: re-scored keys
-    pl.bytes = o;
-    return 0;
+    Carver c(base);
+    pl.tau = c.take<float>(nq);
+    const size_t m = c.bytes();
+    pl.cnt = c.take<int>(nq);
+    pl.ocnt = c.take<int>(nq);
+    pl.ticket = c.take<int>(nq);                        // fix-up: slices finished per query
+    pl.fcount = c.take<int>(nq);                        // fused finalize (small batches): exact keys appended,
+    pl.fticket = c.take<int>(nq);                       // blocks finished per query
+    pl.fail = c.take<int>(nq + 1);
+    pl.clear_bytes = c.bytes_since(m);
+    pl.segcnt = c.take<int>((size_t)(dim16 ? nq : 0) * 256);                     // streaming pass: hits per (query, segment)
+    pl.cand = c.take<unsigned long long>((size_t)nq * CAND_CAP * (dim16 ? 2 : 1));   // mixed: + overflow block
+    pl.sample = c.take<float>((size_t)nq * (size_t)pl.n_sample);
+    pl.fix = c.take<unsigned long long>((size_t)nq * pl.nslices * k);
+    pl.q16 = c.take<uint16_t>((size_t)nq * (size_t)dim16);
+    pl.exact = c.take<unsigned long long>((size_t)(dim16 && nq <= FUSED_MAX_NQ ? nq : 0) * CAND_CAP);   // fused finalize: re-scored keys
+    pl.bytes = c.bytes();
+    return pl;
 }
 
 // X / Q / ldx / ldq / d are in staged floats: for a BF16 shape the bf16 matrices viewed as float matrices of
 // half the columns (d_alg = the un-halved dimension, for the profiling hook's FLOP count)
 template <class S>
 static hipError_t run_passes(const float* X, long long ldx, long long nrows, int d, const float* Q, long long ldq,
-                             int nq, const SearchPlan& pl, char* ws, hipStream_t st, int d_alg = 0,
+                             int nq, const SearchPlan& pl, hipStream_t st, int d_alg = 0,
                              bool filter = true, long long cand_stride = CAND_CAP) {
     DenseRows lq{Q, nq, (int)ldq, d, 30, 1ll << 30};
-    float* tau = reinterpret_cast<float*>(ws + pl.off_tau);
-    int* cnt = reinterpret_cast<int*>(ws + pl.off_cnt);
     if (pl.n_sample > 0) {
         int gshift = 8;   // SAMPLE_G == 256
         DenseRows lps{X, nrows, (int)ldx, d, gshift, pl.gstride};
-        float* S_ = reinterpret_cast<float*>(ws + pl.off_sample);
-        EpiStoreScores es{S_, pl.n_sample, nq, pl.n_sample, lps};
+        EpiStoreScores es{pl.sample, pl.n_sample, nq, pl.n_sample, lps};
         hipError_t e = launch_gemm<S, false>(lps, lq, es, d, pl.n_sample, nq, st, d_alg);
         if (e != hipSuccess) return e;
         ProfScope prof("search_threshold", 0.0, 4.0 * (double)nq * (double)pl.n_sample, st);
-        hipLaunchKernelGGL(sample_threshold_kernel, dim3(nq), dim3(THR_NT), 0, st, S_, pl.n_sample, pl.n_sample,
-                           pl.rank, tau);
+        hipLaunchKernelGGL(sample_threshold_kernel, dim3(nq), dim3(THR_NT), 0, st, pl.sample, pl.n_sample, pl.n_sample,
+                           pl.rank, pl.tau);
     } else {
-        hipLaunchKernelGGL(fill_f32_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, tau, (long long)nq,
+        hipLaunchKernelGGL(fill_f32_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, pl.tau, (long long)nq,
                            -INFINITY);
     }
     if (!filter) return hipGetLastError();
     DenseRows lp{X, nrows, (int)ldx, d, 30, 1ll << 30};
-    EpiFilter ef{tau, reinterpret_cast<unsigned long long*>(ws + pl.off_cand), cnt, CAND_CAP, nq, nrows, cand_stride};
+    EpiFilter ef{pl.tau, pl.cand, pl.cnt, CAND_CAP, nq, nrows, cand_stride};
     return launch_gemm<S, false>(lp, lq, ef, d, nrows, nq, st, d_alg);
+}
+
+// corpus tile 256 rows x query tile 128 / 64 / 32 (4 waves each): f(Shape<...>{})
+template <bool BF16, class F>
+static hipError_t dispatch_query_tile(long long nq, F&& f) {
+    if (nq > 64) return f(Shape<2, 2, 4, 2, false, BF16>{});
+    if (nq > 32) return f(Shape<4, 1, 2, 2, false, BF16>{});
+    return f(Shape<4, 1, 2, 1, false, BF16>{});
+}
+
+// the streaming kernels' K-steps per row for the dims they are instantiated for (32 / 64 / 128 / 256): f(integral_constant<int, KS>{})
+template <class F>
+static hipError_t dispatch_ks(int dim, F&& f) {
+    if (dim == 256) return f(std::integral_constant<int, 16>{});
+    if (dim == 128) return f(std::integral_constant<int, 8>{});
+    if (dim == 64) return f(std::integral_constant<int, 4>{});
+    return f(std::integral_constant<int, 2>{});
 }
 
 }  // namespace amdrec
@@ -1282,13 +1302,59 @@ extern "C" int amdrec_topk_merge_partial(const float* scores, const int32_t* pos
                            stream);
 }
 
+// both flat-search entries' argument checks (mixed: + the corpus's bf16 shadow and row norms); nq == 0 ends them early
+static int search_check(bool mixed, const float* corpus, int64_t nrows, int64_t ld_corpus, int dim, const uint16_t* corpus_bf16,
+                        int64_t ld_bf16, const float* max_norm, const float* queries, int64_t nq, int64_t ld_queries, int k,
+                        const float* out_scores, const int64_t* out_pos) {
+    const int mult = mixed ? 8 : 4;
+    REQUIRE(k >= 1 && k <= KMAX, "k=%d outside [1,%d]", k, KMAX);
+    REQUIRE(dim >= mult && dim % mult == 0 && dim <= 2048, "dim=%d must be a multiple of %d in [%d,2048]", dim, mult, mult);
+    REQUIRE(nrows >= 0 && nrows < (1ll << 31) - 1024, "nrows out of range");
+    REQUIRE(nq >= 0 && nq < (1ll << 24), "nq out of range");
+    if (nq == 0) return AMDREC_OK;
+    REQUIRE((nrows == 0 || (ld_corpus >= dim && ld_corpus % 4 == 0 &&
+                            (!mixed || (ld_bf16 >= dim && ld_bf16 % 8 == 0 && ld_bf16 < (1 << 20))))) &&
+                ld_queries >= dim && ld_queries % 4 == 0,
+            "%s", mixed ? "leading dimensions must be >= dim; fp32 multiples of 4, bf16 multiples of 8"
+                        : "leading dimensions must be >= dim and multiples of 4");
+    REQUIRE((corpus && (!mixed || corpus_bf16)) || nrows == 0, "corpus is null");
+    REQUIRE(queries && out_scores && out_pos && (!mixed || max_norm), "null pointer");
+    REQUIRE(((uintptr_t)corpus % 16) == 0 && ((uintptr_t)corpus_bf16 % 16) == 0 && ((uintptr_t)queries % 16) == 0,
+            "corpus/queries must be 16-byte aligned");
+    return AMDREC_OK;
+}
+
+// every finalize / fix-up kernel's dynamic LDS limit, once per device
+static int set_lds_limits() {
+    static PerDeviceOnce attr_done;
+    if (!attr_done.pending()) return AMDREC_OK;
+    const struct { const void* kernel; int bytes; } limits[] = {
+        {reinterpret_cast<const void*>(finalize_kernel), CAND_CAP * 8},
+        {reinterpret_cast<const void*>(finalize_mixed_kernel<512, CAND_CAP>), CAND_CAP * 8 + 2048 * 4},
+        {reinterpret_cast<const void*>(finalize_fused_kernel), CAND_CAP * 8 + 2048 * 4},
+        {reinterpret_cast<const void*>(fixup_kernel), CAND_CAP * 8}};
+    for (const auto& l : limits) HIP_TRY(hipFuncSetAttribute(l.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, l.bytes));
+    attr_done.mark();
+    return AMDREC_OK;
+}
+
+// the exact re-scan of the queries that the finalize kernel could not certify, and their count for the caller
+static int launch_fixup(const float* corpus, int64_t ld_corpus, int64_t nrows, int dim, const float* queries, int64_t nq,
+                        int64_t ld_queries, int k, const SearchPlan& pl, float* out_scores, int64_t* out_pos, int64_t pos_offset,
+                        int* n_fixup, hipStream_t st) {
+    hipLaunchKernelGGL(fixup_kernel, dim3((unsigned)(pl.nslices * (nq < FIX_GRID_Q ? nq : FIX_GRID_Q))), dim3(512), CAND_CAP * 8, st,
+                       corpus, (long long)ld_corpus, (long long)nrows, dim, queries, (long long)ld_queries, pl.fail, (int)nq, k,
+                       pl.nslices, pl.fix, pl.ticket, out_scores, (long long*)out_pos, (long long)pos_offset);
+    HIP_TRY(hipGetLastError());
+    if (n_fixup) HIP_TRY(hipMemcpyAsync(n_fixup, pl.fail + nq, sizeof(int), hipMemcpyDeviceToDevice, st));
+    return AMDREC_OK;
+}
+
 extern "C" int amdrec_flat_search_workspace(int64_t nq, int64_t nrows, int k, size_t* bytes) {
     REQUIRE(bytes != nullptr, "bytes is null");
     REQUIRE(nq >= 0 && nrows >= 0, "negative size");
     REQUIRE(k >= 1 && k <= KMAX, "k=%d outside [1,%d]", k, KMAX);
-    SearchPlan pl;
-    make_plan(nq, nrows, k, pl);
-    *bytes = pl.bytes;
+    *bytes = make_plan(nq, nrows, k, 0, nullptr).bytes;
     return AMDREC_OK;
 }
 
@@ -1297,54 +1363,20 @@ extern "C" int amdrec_flat_search(const float* corpus, int64_t nrows, int64_t ld
                                   int64_t pos_offset, float* out_scores, int64_t* out_pos, void* workspace,
                                   size_t workspace_bytes, int* n_fixup, void* stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    REQUIRE(k >= 1 && k <= KMAX, "k=%d outside [1,%d]", k, KMAX);
-    REQUIRE(dim >= 4 && dim % 4 == 0 && dim <= 2048, "dim=%d must be a multiple of 4 in [4,2048]", dim);
-    REQUIRE(nrows >= 0 && nrows < (1ll << 31) - 1024, "nrows out of range");
-    REQUIRE(nq >= 0 && nq < (1ll << 24), "nq out of range");
-    if (nq == 0) return AMDREC_OK;
-    REQUIRE((nrows == 0 || (ld_corpus >= dim && ld_corpus % 4 == 0)) && ld_queries >= dim && ld_queries % 4 == 0,
-            "leading dimensions must be >= dim and multiples of 4");
-    REQUIRE(corpus || nrows == 0, "corpus is null");
-    REQUIRE(queries && out_scores && out_pos, "null pointer");
-    REQUIRE(((uintptr_t)corpus % 16) == 0 && ((uintptr_t)queries % 16) == 0, "corpus/queries must be 16-byte aligned");
-    SearchPlan pl;
-    make_plan(nq, nrows, k, pl);
-    if (workspace_bytes < pl.bytes || workspace == nullptr)
-        return set_error(AMDREC_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", pl.bytes, workspace_bytes);
-    REQUIRE(((uintptr_t)workspace % 256) == 0, "workspace must be 256-byte aligned");
-    char* ws = reinterpret_cast<char*>(workspace);
-    int* cnt = reinterpret_cast<int*>(ws + pl.off_cnt);
-    int* fail = reinterpret_cast<int*>(ws + pl.off_fail);
-    // cnt[nq] and fail[nq + 1] are adjacent in the plan: one fill
-    HIP_TRY(hipMemsetAsync(cnt, 0, (pl.off_fail - pl.off_cnt) + (size_t)(nq + 1) * 4, st));
+    int rc = search_check(false, corpus, nrows, ld_corpus, dim, nullptr, 0, nullptr, queries, nq, ld_queries, k, out_scores, out_pos);
+    if (rc || nq == 0) return rc;
+    const SearchPlan pl = make_plan(nq, nrows, k, 0, workspace);
+    if ((rc = require_workspace(workspace, workspace_bytes, pl.bytes, 256))) return rc;
+    HIP_TRY(hipMemsetAsync(pl.cnt, 0, pl.clear_bytes, st));
 
-    if (nrows > 0) {
-        hipError_t e;
-        // corpus tile 256 rows x query tile 128 / 64 / 32 (4 waves each)
-        if (nq > 64)       e = run_passes<Shape<2, 2, 4, 2>>(corpus, ld_corpus, nrows, dim, queries, ld_queries, (int)nq, pl, ws, st);
-        else if (nq > 32)  e = run_passes<Shape<4, 1, 2, 2>>(corpus, ld_corpus, nrows, dim, queries, ld_queries, (int)nq, pl, ws, st);
-        else               e = run_passes<Shape<4, 1, 2, 1>>(corpus, ld_corpus, nrows, dim, queries, ld_queries, (int)nq, pl, ws, st);
-        HIP_TRY(e);
-    }
-    static PerDeviceOnce attr_done;
-    if (attr_done.pending()) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(finalize_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, CAND_CAP * 8));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fixup_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, CAND_CAP * 8));
-        attr_done.mark();
-    }
-    unsigned long long* cand = reinterpret_cast<unsigned long long*>(ws + pl.off_cand);
-    unsigned long long* fix = reinterpret_cast<unsigned long long*>(ws + pl.off_fix);
-    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)nq), dim3(512), CAND_CAP * 8, st, cand, cnt, CAND_CAP, k,
-                       (long long)nrows, fail, out_scores, (long long*)out_pos, (long long)pos_offset);
-    hipLaunchKernelGGL(fixup_kernel, dim3((unsigned)(pl.nslices * (nq < FIX_GRID_Q ? nq : FIX_GRID_Q))), dim3(512), CAND_CAP * 8, st,
-                       corpus, (long long)ld_corpus, (long long)nrows, dim, queries, (long long)ld_queries, fail, (int)nq, k,
-                       pl.nslices, fix, reinterpret_cast<int*>(ws + pl.off_ticket), out_scores, (long long*)out_pos,
-                       (long long)pos_offset);
-    HIP_TRY(hipGetLastError());
-    if (n_fixup) HIP_TRY(hipMemcpyAsync(n_fixup, fail + nq, sizeof(int), hipMemcpyDeviceToDevice, st));
-    return AMDREC_OK;
+    hipError_t e = nrows <= 0 ? hipSuccess : dispatch_query_tile<false>(nq, [&](auto shape) {
+        return run_passes<decltype(shape)>(corpus, ld_corpus, nrows, dim, queries, ld_queries, (int)nq, pl, st);
+    });
+    HIP_TRY(e);
+    if ((rc = set_lds_limits())) return rc;
+    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)nq), dim3(512), CAND_CAP * 8, st, pl.cand, pl.cnt, CAND_CAP, k,
+                       (long long)nrows, pl.fail, out_scores, (long long*)out_pos, (long long)pos_offset);
+    return launch_fixup(corpus, ld_corpus, nrows, dim, queries, nq, ld_queries, k, pl, out_scores, out_pos, pos_offset, n_fixup, st);
 }
 
 extern "C" int amdrec_bf16_rows(const float* x, int64_t rows, int64_t ld, int dim, uint16_t* out, int64_t ld_out,
@@ -1366,9 +1398,7 @@ extern "C" int amdrec_flat_search_mixed_workspace(int64_t nq, int64_t nrows, int
     REQUIRE(nq >= 0 && nrows >= 0, "negative size");
     REQUIRE(k >= 1 && k <= KMAX, "k=%d outside [1,%d]", k, KMAX);
     REQUIRE(dim >= 8 && dim % 8 == 0 && dim <= 2048, "dim=%d must be a multiple of 8 in [8,2048]", dim);
-    SearchPlan pl;
-    make_plan(nq, nrows, k, pl, dim);
-    *bytes = pl.bytes;
+    *bytes = make_plan(nq, nrows, k, dim, nullptr).bytes;
     return AMDREC_OK;
 }
 
@@ -1378,126 +1408,79 @@ extern "C" int amdrec_flat_search_mixed(const float* corpus, int64_t nrows, int6
                                         int64_t pos_offset, float* out_scores, int64_t* out_pos, void* workspace,
                                         size_t workspace_bytes, int* n_fixup, void* stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    REQUIRE(k >= 1 && k <= KMAX, "k=%d outside [1,%d]", k, KMAX);
-    REQUIRE(dim >= 8 && dim % 8 == 0 && dim <= 2048, "dim=%d must be a multiple of 8 in [8,2048]", dim);
-    REQUIRE(nrows >= 0 && nrows < (1ll << 31) - 1024, "nrows out of range");
-    REQUIRE(nq >= 0 && nq < (1ll << 24), "nq out of range");
-    if (nq == 0) return AMDREC_OK;
-    REQUIRE((nrows == 0 || (ld_corpus >= dim && ld_corpus % 4 == 0 && ld_bf16 >= dim && ld_bf16 % 8 == 0 &&
-                            ld_bf16 < (1 << 20))) &&
-                ld_queries >= dim && ld_queries % 4 == 0,
-            "leading dimensions must be >= dim; fp32 multiples of 4, bf16 multiples of 8");
-    REQUIRE((corpus && corpus_bf16) || nrows == 0, "corpus is null");
-    REQUIRE(queries && out_scores && out_pos && max_norm, "null pointer");
-    REQUIRE(((uintptr_t)corpus % 16) == 0 && ((uintptr_t)corpus_bf16 % 16) == 0 && ((uintptr_t)queries % 16) == 0,
-            "corpus/queries must be 16-byte aligned");
-    SearchPlan pl;
-    make_plan(nq, nrows, k, pl, dim);
-    if (workspace_bytes < pl.bytes || workspace == nullptr)
-        return set_error(AMDREC_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", pl.bytes, workspace_bytes);
-    REQUIRE(((uintptr_t)workspace % 256) == 0, "workspace must be 256-byte aligned");
-    char* ws = reinterpret_cast<char*>(workspace);
-    int* cnt = reinterpret_cast<int*>(ws + pl.off_cnt);
-    int* ocnt = reinterpret_cast<int*>(ws + pl.off_ocnt);
-    int* fail = reinterpret_cast<int*>(ws + pl.off_fail);
-    // cnt[nq], ocnt[nq] and fail[nq + 1] are adjacent in the plan: cleared by the query-conversion kernel below (no
-    // separate fill launch: a launch costs ~5 us, a 32-query search 170)
-    const long long n_zero = (long long)((pl.off_fail - pl.off_cnt) / 4) + nq + 1;
-    if (nrows <= 0) HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)n_zero * 4, st));
+    int rc = search_check(true, corpus, nrows, ld_corpus, dim, corpus_bf16, ld_bf16, max_norm, queries, nq, ld_queries, k,
+                          out_scores, out_pos);
+    if (rc || nq == 0) return rc;
+    const SearchPlan pl = make_plan(nq, nrows, k, dim, workspace);
+    if ((rc = require_workspace(workspace, workspace_bytes, pl.bytes, 256))) return rc;
+    // cnt .. fail are cleared by the query-conversion kernel below (no separate fill launch: a launch costs ~5 us, a
+    // 32-query search 170)
+    const long long n_zero = (long long)(pl.clear_bytes / 4);
+    if (nrows <= 0) HIP_TRY(hipMemsetAsync(pl.cnt, 0, pl.clear_bytes, st));
     constexpr long long CSTRIDE = CAND_STRIDE;
     // corpus pass: the streaming kernel for the power-of-two dims it is instantiated for, else the generic tiles
     const bool streaming = nrows > 0 && (dim == 32 || dim == 64 || dim == 128 || dim == 256);
     const int nseg = streaming ? scan_segments(nrows, nq) : 1;
     const int seg_cap = CAND_CAP / nseg;
-    const int* segcnt = streaming ? reinterpret_cast<int*>(ws + pl.off_segcnt) : cnt;
+    const int* segcnt = streaming ? pl.segcnt : pl.cnt;
 
     if (streaming && pl.n_sample > 0) {
         // conversion + sample in ONE launch (group maxima only), tau from the maxima: inside the corpus pass for <= 8
         // queries (no threshold launch), one wave per query otherwise
-        uint16_t* q16 = reinterpret_cast<uint16_t*>(ws + pl.off_q16);
-        float* gm = reinterpret_cast<float*>(ws + pl.off_sample);
-        float* tau_ = reinterpret_cast<float*>(ws + pl.off_tau);
-        unsigned long long* cand_ = reinterpret_cast<unsigned long long*>(ws + pl.off_cand);
-        int* sc_ = reinterpret_cast<int*>(ws + pl.off_segcnt);
         const SamplePlan sp = sample_plan(nrows, pl.n_sample);
         REQUIRE(sp.cols <= pl.n_sample, "internal: sample maxima do not fit their workspace");
         const bool tau_in_scan = nq <= 8;
-        hipError_t e;
-        auto run = [&](auto ks_tag) -> hipError_t {
+        hipError_t e = dispatch_ks(dim, [&](auto ks_tag) -> hipError_t {
             constexpr int KS = decltype(ks_tag)::value;
-            hipError_t e2 = launch_sample<KS>(corpus_bf16, ld_bf16, sp, queries, ld_queries, (int)nq, q16, gm, cnt, n_zero, st);
+            hipError_t e2 = launch_sample<KS>(corpus_bf16, ld_bf16, sp, queries, ld_queries, (int)nq, pl.q16, pl.sample, pl.cnt, n_zero, st);
             if (e2 != hipSuccess) return e2;
             if (!tau_in_scan) {
                 ProfScope prof("search_threshold", 0.0, 4.0 * (double)nq * (double)sp.cols, st);
-                hipLaunchKernelGGL(tau_from_maxima_kernel, dim3((unsigned)((nq + 7) / 8)), dim3(512), 0, st, (const float*)gm,
-                                   sp.cols, sp.cols, pl.rank, (int)nq, tau_);
+                hipLaunchKernelGGL(tau_from_maxima_kernel, dim3((unsigned)((nq + 7) / 8)), dim3(512), 0, st, pl.sample,
+                                   sp.cols, sp.cols, pl.rank, (int)nq, pl.tau);
             }
-            return launch_scan<KS>(corpus_bf16, ld_bf16, nrows, q16, (int)nq, tau_, cand_, sc_, ocnt, st,
-                                   tau_in_scan ? (const float*)gm : nullptr, sp.cols, sp.cols, pl.rank);
-        };
-        if (dim == 256)      e = run(std::integral_constant<int, 16>{});
-        else if (dim == 128) e = run(std::integral_constant<int, 8>{});
-        else if (dim == 64)  e = run(std::integral_constant<int, 4>{});
-        else                 e = run(std::integral_constant<int, 2>{});
+            return launch_scan<KS>(corpus_bf16, ld_bf16, nrows, pl.q16, (int)nq, pl.tau, pl.cand, pl.segcnt, pl.ocnt, st,
+                                   tau_in_scan ? pl.sample : nullptr, sp.cols, sp.cols, pl.rank);
+        });
         HIP_TRY(e);
     } else if (nrows > 0) {
-        uint16_t* q16 = reinterpret_cast<uint16_t*>(ws + pl.off_q16);
         hipLaunchKernelGGL(bf16_rows_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, queries, (long long)nq,
-                           (long long)ld_queries, dim, q16, (long long)dim, (float*)nullptr, cnt, n_zero);
+                           (long long)ld_queries, dim, pl.q16, (long long)dim, (float*)nullptr, pl.cnt, n_zero);
         // the bf16 matrices as float matrices of dim/2 columns (gemm_core.hpp, Shape::BF16)
         const float* X = reinterpret_cast<const float*>(corpus_bf16);
-        const float* Q = reinterpret_cast<const float*>(q16);
+        const float* Q = reinterpret_cast<const float*>(pl.q16);
         const long long ldx = ld_bf16 / 2, ldq = dim / 2;
         const int dh = dim / 2;
-        hipError_t e;
-        if (nq > 64)       e = run_passes<Shape<2, 2, 4, 2, false, true>>(X, ldx, nrows, dh, Q, ldq, (int)nq, pl, ws, st, dim, !streaming, CSTRIDE);
-        else if (nq > 32)  e = run_passes<Shape<4, 1, 2, 2, false, true>>(X, ldx, nrows, dh, Q, ldq, (int)nq, pl, ws, st, dim, !streaming, CSTRIDE);
-        else               e = run_passes<Shape<4, 1, 2, 1, false, true>>(X, ldx, nrows, dh, Q, ldq, (int)nq, pl, ws, st, dim, !streaming, CSTRIDE);
+        hipError_t e = dispatch_query_tile<true>(nq, [&](auto shape) {
+            return run_passes<decltype(shape)>(X, ldx, nrows, dh, Q, ldq, (int)nq, pl, st, dim, !streaming, CSTRIDE);
+        });
         HIP_TRY(e);
         if (streaming) {
-            float* tau_ = reinterpret_cast<float*>(ws + pl.off_tau);
-            unsigned long long* cand_ = reinterpret_cast<unsigned long long*>(ws + pl.off_cand);
-            int* sc_ = reinterpret_cast<int*>(ws + pl.off_segcnt);
-            if (dim == 256)      e = launch_scan<16>(corpus_bf16, ld_bf16, nrows, q16, (int)nq, tau_, cand_, sc_, ocnt, st);
-            else if (dim == 128) e = launch_scan<8>(corpus_bf16, ld_bf16, nrows, q16, (int)nq, tau_, cand_, sc_, ocnt, st);
-            else if (dim == 64)  e = launch_scan<4>(corpus_bf16, ld_bf16, nrows, q16, (int)nq, tau_, cand_, sc_, ocnt, st);
-            else                 e = launch_scan<2>(corpus_bf16, ld_bf16, nrows, q16, (int)nq, tau_, cand_, sc_, ocnt, st);
+            e = dispatch_ks(dim, [&](auto ks_tag) {
+                return launch_scan<decltype(ks_tag)::value>(corpus_bf16, ld_bf16, nrows, pl.q16, (int)nq, pl.tau, pl.cand,
+                                                            pl.segcnt, pl.ocnt, st);
+            });
             HIP_TRY(e);
         }
     }
-    const size_t fin_lds = (size_t)CAND_CAP * 8 + (size_t)dim * 4;
-    static PerDeviceOnce attr_done;
-    if (attr_done.pending()) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(finalize_mixed_kernel<512, CAND_CAP>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, CAND_CAP * 8 + 2048 * 4));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(finalize_fused_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, CAND_CAP * 8 + 2048 * 4));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fixup_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, CAND_CAP * 8));
-        attr_done.mark();
-    }
-    unsigned long long* cand = reinterpret_cast<unsigned long long*>(ws + pl.off_cand);
-    unsigned long long* fix = reinterpret_cast<unsigned long long*>(ws + pl.off_fix);
-    const float* tau = reinterpret_cast<const float*>(ws + pl.off_tau);
+    if ((rc = set_lds_limits())) return rc;
     {
         ProfScope prof("search_finalize_mixed", 0.0, 0.0, st);
         if (nq <= FUSED_MAX_NQ) {
             int slices = (int)(512 / nq);                           // ~512 workgroups in all: the chip once
             slices = slices < 1 ? 1 : (slices > 16 ? 16 : slices);
-            hipLaunchKernelGGL(finalize_fused_kernel, dim3((unsigned)slices, (unsigned)nq), dim3(512), fin_lds, st,
-                               (const unsigned long long*)cand, CSTRIDE, segcnt, nseg, seg_cap, (const int*)ocnt, CAND_CAP, k,
-                               (long long)nrows, tau, max_norm, corpus, (long long)ld_corpus, dim, queries,
-                               (long long)ld_queries, fail, out_scores, (long long*)out_pos, (long long)pos_offset,
-                               reinterpret_cast<unsigned long long*>(ws + pl.off_exact),
-                               reinterpret_cast<int*>(ws + pl.off_fcount), reinterpret_cast<int*>(ws + pl.off_fticket));
+            hipLaunchKernelGGL(finalize_fused_kernel, dim3((unsigned)slices, (unsigned)nq), dim3(512), (size_t)CAND_CAP * 8 + (size_t)dim * 4, st, pl.cand, CSTRIDE,
+                               segcnt, nseg, seg_cap, pl.ocnt, CAND_CAP, k, (long long)nrows, pl.tau, max_norm, corpus,
+                               (long long)ld_corpus, dim, queries, (long long)ld_queries, pl.fail, out_scores,
+                               (long long*)out_pos, (long long)pos_offset, pl.exact, pl.fcount, pl.fticket);
         } else {
             // one workgroup per query; short lists of many queries (the sharded search) on the small shapes: twice the
             // expected candidate count must fit (10 sigma of the threshold estimate; beyond it the query takes the fix-up scan)
 #define AMDREC_FINALIZE(NT_, CAPK_)                                                                                          \
     hipLaunchKernelGGL((finalize_mixed_kernel<NT_, CAPK_>), dim3((unsigned)nq), dim3(NT_), (size_t)(CAPK_) * 8 + (size_t)dim * 4, \
-                       st, (const unsigned long long*)cand, CSTRIDE, segcnt, nseg, seg_cap, (const int*)ocnt, k,             \
-                       (long long)nrows, tau, max_norm, corpus, (long long)ld_corpus, dim, queries, (long long)ld_queries,    \
-                       fail, out_scores, (long long*)out_pos, (long long)pos_offset)
+                       st, pl.cand, CSTRIDE, segcnt, nseg, seg_cap, pl.ocnt, k, (long long)nrows, pl.tau, max_norm, corpus,  \
+                       (long long)ld_corpus, dim, queries, (long long)ld_queries, pl.fail, out_scores, (long long*)out_pos,  \
+                       (long long)pos_offset)
             if (pl.target > 0 && 2 * pl.target <= 1024 && dim <= 2048) AMDREC_FINALIZE(128, 1024);
             else if (pl.target > 0 && 2 * pl.target <= 2048 && dim <= 2048) AMDREC_FINALIZE(256, 2048);
             else AMDREC_FINALIZE(512, CAND_CAP);
@@ -1505,11 +1488,5 @@ extern "C" int amdrec_flat_search_mixed(const float* corpus, int64_t nrows, int6
         }
     }
     ProfScope prof_fix("search_fixup", 0.0, 0.0, st);
-    hipLaunchKernelGGL(fixup_kernel, dim3((unsigned)(pl.nslices * (nq < FIX_GRID_Q ? nq : FIX_GRID_Q))), dim3(512), CAND_CAP * 8, st,
-                       corpus, (long long)ld_corpus, (long long)nrows, dim, queries, (long long)ld_queries, fail, (int)nq, k,
-                       pl.nslices, fix, reinterpret_cast<int*>(ws + pl.off_ticket), out_scores, (long long*)out_pos,
-                       (long long)pos_offset);
-    HIP_TRY(hipGetLastError());
-    if (n_fixup) HIP_TRY(hipMemcpyAsync(n_fixup, fail + nq, sizeof(int), hipMemcpyDeviceToDevice, st));
-    return AMDREC_OK;
+    return launch_fixup(corpus, ld_corpus, nrows, dim, queries, nq, ld_queries, k, pl, out_scores, out_pos, pos_offset, n_fixup, st);
 }

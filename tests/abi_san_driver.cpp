@@ -126,6 +126,46 @@ int main() {
     rp.d_model = 300;
     EXPECT(amdrec_ranker_workspace(&rp, 10, &b) < 0);                                                            // d_model > 256
 
+    // ---- every workspace-taking entry: one byte short of what it needs is -3 and the message carries both numbers; a
+    // misaligned workspace, where the entry has an alignment rule, is -1 ----
+    auto too_small = [](int rc, size_t need) {
+        char msg[96];
+        snprintf(msg, sizeof msg, "workspace too small: need %zu bytes, got %zu", need, need - 1);
+        return rc == -3 && strcmp(amdrec_last_error(), msg) == 0;
+    };
+    auto misaligned = [](int rc, int align) {
+        char msg[64];
+        snprintf(msg, sizeof msg, "workspace must be %d-byte aligned", align);
+        return rc == -1 && strcmp(amdrec_last_error(), msg) == 0;
+    };
+    uint64_t* kp = reinterpret_cast<uint64_t*>(fake);
+    int32_t* tp32 = reinterpret_cast<int32_t*>(fake);
+    size_t need = 0;
+    EXPECT(amdrec_flat_search_workspace(1, 10, 5, &need) == 0);
+    EXPECT(too_small(amdrec_flat_search(fp, 10, 256, 256, fp, 1, 256, 5, 0, fp, ip, fake, need - 1, nullptr, nullptr), need));
+    EXPECT(misaligned(amdrec_flat_search(fp, 10, 256, 256, fp, 1, 256, 5, 0, fp, ip, fake + 128, need, nullptr, nullptr), 256));
+    EXPECT(amdrec_flat_search_mixed_workspace(1, 10, 5, 256, &need) == 0);
+    EXPECT(too_small(amdrec_flat_search_mixed(fp, 10, 256, 256, reinterpret_cast<uint16_t*>(fake), 256, fp, fp, 1, 256, 5, 0, fp, ip,
+                                              fake, need - 1, nullptr, nullptr), need));
+    EXPECT(misaligned(amdrec_flat_search_mixed(fp, 10, 256, 256, reinterpret_cast<uint16_t*>(fake), 256, fp, fp, 1, 256, 5, 0, fp, ip,
+                                               fake + 128, need, nullptr, nullptr), 256));
+    EXPECT(too_small(amdrec_ivf_assign(fp, 100, 64, 64, fp, 16, 64, ip, nullptr, fake, 1023, nullptr), 1024));       // 100 keys
+    EXPECT(amdrec_ivf_kmeans_workspace(100, 64, 16, &need) == 0 && need == 1024 + 1024 + 8192 + 256);
+    EXPECT(too_small(amdrec_ivf_kmeans_step(fp, 100, 64, 64, fp, 16, 64, fake, need - 1, nullptr), need));
+    EXPECT(too_small(amdrec_ivf_group(ip, 8, 4, 8, 16, ip, ip, ip, ip, ip, ip, ip, 64, fake, 511, nullptr), 512));    // 17 + 32 ints
+    EXPECT(too_small(amdrec_ivf_select_split(kp, 64, ip, 2, 10, 4, fp, ip, fake, 639, tp32, nullptr), 640));          // 2 * 4 * 10 keys
+    EXPECT(misaligned(amdrec_ivf_select_split(kp, 64, ip, 2, 10, 4, fp, ip, fake + 8, 640, tp32, nullptr), 16));
+    EXPECT(amdrec_ivfpq_train_workspace(100, 128, 8, &need) == 0 && need == 1024 + 256 * 128 * 8 + 8 * 256 * 4);
+    EXPECT(too_small(amdrec_ivfpq_train_step(fp, 100, 128, 128, ip, fp, 128, 16, fp, 8, fake, need - 1, nullptr), need));
+    EXPECT(too_small(amdrec_ivfpq_rerank(fp, 0, 100, 64, 64, nullptr, fp, 2, 64, ip, 256, 0, 10, fp, ip, fake, 4095, tp32, nullptr),
+                     4096));                                                                                         // 2 * 256 keys
+    EXPECT(misaligned(amdrec_ivfpq_rerank(fp, 0, 100, 64, 64, nullptr, fp, 2, 64, ip, 256, 0, 10, fp, ip, fake + 4, 4096, tp32, nullptr), 8));
+    rp.d_model = 256;
+    EXPECT(amdrec_ranker_workspace(&rp, 5, &need) == 0);
+    EXPECT(too_small(amdrec_ranker_forward(&rp, ip, fp, 1, ip, nullptr, 5, fp, 5, nullptr, 5, 5, fake, need - 1, nullptr), need));
+    rp.w_proj_ad = fp;
+    EXPECT(too_small(amdrec_ranker_project_ads(&rp, ip, 10, fp, 256, fake, 1023, nullptr), 1024));                    // d_model floats
+
     // ---- profiling plumbing without any launch ----
     amdrec_profile_entry pe[4];
     int n = -1;

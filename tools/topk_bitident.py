@@ -1,6 +1,7 @@
 """Dev tool: one seeded pass over the top-k kernels (flat mixed / fp32 search incl. the fused and the per-query finalize on
-its three shapes and the fix-up, IVF select / split select on crafted pools and a real index, IVFPQ re-rank); prints a sha256
-of (scores, positions) per case and one over everything, as one JSON line.  Run it once per build of the library
+its three shapes and the fix-up, IVF select / split select on crafted pools and a real index, IVFPQ re-rank, IVF / IVFPQ index
+builds and searches at 3000 rows, tower and ranker forwards); prints a sha256 of the outputs per case and one over everything,
+as one JSON line.  Run it once per build of the library
 (AMDREC_LIB_PATH, amdrec/_lib.py) in fresh processes and compare: profiles/topk_helpers_bitident.log.
 usage: AMDREC_LIB_PATH=/path/to/libamdrec.so python tools/topk_bitident.py"""
 import hashlib
@@ -160,6 +161,50 @@ for nq in (3, 40):
                                                    nq * kc * 8 if split else 0, _lib.ptr(tk) if split else None,
                                                    _lib.stream_ptr(dev)))
                 record(f"f_rerank_{name}_nq{nq}_kc{kc}_{'split' if split else 'one'}", D, I)
+
+
+
+def record_t(name, *tensors):
+    torch.cuda.synchronize()
+    b = b"".join(t.cpu().contiguous().view(torch.uint8).numpy().tobytes() for t in tensors)
+    total.update(b)
+    cases[name] = {"sha256": hashlib.sha256(b).hexdigest()[:16]}
+
+
+# (g) index builds at 3000 rows, nlist 16 (k-means centroids, list assignment, PQ codebooks, codes) and IVFPQ searches, plain / refined
+xg = synth.unit_corpus(3000, 256, seed=61)
+qg = torch.from_numpy(synth.unit_corpus(33, 256, seed=62)).to(dev)
+ivf = FAISSIndex(256, index_type="IVF", nlist=16, nprobe=4)
+ivf.add(xg)
+record_t("g_ivf_build_3000", ivf._ivf.centroids, ivf._ivf.assign)
+for refine in (None, "fp32", "bf16"):
+    pq = FAISSIndex(256, index_type="IVFPQ", nlist=16, nprobe=4, refine=refine)
+    pq.add(xg)
+    record_t(f"g_ivfpq_build_3000_refine_{refine}", pq._pq.ivf.centroids, pq._pq.ivf.assign, pq._pq.codebooks, pq._pq.codes)
+    for k in (10, 100):
+        ids, sc = pq.search_device(qg, k)
+        record(f"g_ivfpq_search_refine_{refine}_k{k}", sc, ids)
+
+# (h) the models: demo architecture, 300 and 5000 rows, the ranker on the row-owner engine and on strict fp32
+from amdrec.ranker import TransformerRanker  # noqa: E402
+from amdrec.towers import TwoTowerModel  # noqa: E402
+user, ad, nnum = synth.demo_dims()
+to_t = lambda sd: {k: torch.from_numpy(np.array(v)) for k, v in sd.items()}   # noqa: E731
+tt = TwoTowerModel(dict(user), dict(ad), nnum)
+tt.load_state_dict(to_t(synth.two_tower_state(user, ad, nnum, seed=3)))
+rk = TransformerRanker(dict(user), dict(ad), nnum)
+rk.load_state_dict(to_t(synth.ranker_state(user, ad, nnum, seed=4, cross_scale=1.0 / 16)))
+tt, rk = tt.to(dev).eval(), rk.to(dev).eval()
+table = torch.from_numpy(synth.ad_features(ad, 5000, seed=5)).to(dev)
+uc, un = synth.user_batch(user, nnum, 50, seed=6)
+uc, un = torch.from_numpy(uc).to(dev), torch.from_numpy(un).to(dev)
+cand = torch.from_numpy(rng.integers(0, 5000, (50, 100))).to(dev)
+for rows in (300, 5000):
+    record_t(f"h_ad_tower_rows{rows}", tt.get_ad_embeddings(table[:rows]))
+    record_t(f"h_user_tower_rows{rows // 100}", tt.get_user_embeddings(uc[:rows // 100], un[:rows // 100]))
+    for eng in ("f16x3", "fp32"):
+        rk.gemm_engine = eng
+        record_t(f"h_ranker_{eng}_rows{rows}", rk.score_candidates(uc[:rows // 100], un[:rows // 100], cand[:rows // 100], table, raw=True)[1])
 
 print(json.dumps({"lib": os.environ.get("AMDREC_LIB_PATH", "(default: the tree's build)"), "cases": cases,
                   "sha256_all": total.hexdigest()}))
