@@ -289,13 +289,13 @@ typedef struct {
     const uint16_t *w_o_x6, *w_1_x6, *w_2_x6;
 } amdrec_encoder_layer;
 
-/* Weights of the fp16x3 "row-owner" engine (csrc/rowowner.hpp; optional: stream == NULL -> engine off).  The engine
+/* Weights of the fp16x3 "row-owner" engine (csrc/x3_common.hpp; optional: stream == NULL -> engine off).  The engine
  * runs everything after the feature projection - the encoder layers (transformer_ranker.py:136-155 with the seq-1
  * attention :59-88), the cross layers (:199-202) and the heads (:375-378) - in ONE kernel with the activations in
  * registers; every fp32 operand is split into two fp16 planes (after an exact power-of-two scaling) and a product is
  * three fp16 MFMAs accumulated in fp32: fp32 in, fp32 out, error at the level of an fp32 fma chain.
  * `stream` = all weight matrices as 1 KB MFMA fragment sets in consumption order (the packing, incl. the k permutation
- * inside a 16-wide k-step, is defined by amdrec/weights.py pack_x3_stream and mirrored by rowowner.hpp); `sw_*` = the
+ * inside a 16-wide k-step, is defined by amdrec/weights.py pack_x3_stream and mirrored by csrc/rowowner*.hpp); `sw_*` = the
  * power-of-two scale of each packed matrix; `hn*` / `hb*` = 16 * max_j ||w_j||_2 and max_j |b_j| of the first matrix of
  * each two-stage block (FFN per layer, heads): the kernel bounds a row's hidden activations by hn * max|x| + hb to scale them.
  * Requires d_model == 256, d_ff % 32 == 0, head_h1 % 32 == 0, head_h2 == 64 and the pre-multiplied attention

@@ -327,7 +327,7 @@ def pack_x3_stream(mats: Dict, variant: int = 32, fold_first: bool = False, cach
             "hb_head": float(np.abs(mats["hb1"]).max()), **sc}
 
 
-X3_PARAM_FLOATS = 11264     # LDS parameter area of the kernel (csrc/rowowner.hpp PARAM_FLOATS)
+X3_PARAM_FLOATS = 11264     # LDS parameter area of the kernel (csrc/x3_common.hpp PARAM_FLOATS)
 
 
 def pack_x3_params(layers: List[Dict], cross_b: List, head_b1, heads: List[Dict], fold_first: bool = False) -> np.ndarray:

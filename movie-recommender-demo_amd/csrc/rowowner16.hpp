@@ -1,5 +1,5 @@
-// Row-owner engine, 16-rows-per-wave variant ("x3b"): the same chain, arithmetic, weight-stream ring and parameter blob as
-// rowowner.hpp, re-tiled so that TWO waves share each SIMD.
+// Row-owner engine (x3_common.hpp), 16-rows-per-wave variant ("x3b"): the same chain, arithmetic, weight-stream ring and
+// parameter blob as the 32-row kernel (rowowner.hpp), re-tiled so that TWO waves share each SIMD.
 //
 // WHY.  The 32-row kernel needs ~350 registers per wave (planes 128 + accumulators 128 + ...), i.e. one wave per SIMD, and
 // at one wave per SIMD every non-MFMA instruction is exposed: elimination runs (tools/x3_probe.hip) put its MFMA + VALU
@@ -19,7 +19,7 @@
 //     ffn step t: for u < 8: stage 1 {W_1 tiles 2t, 2t+1 at ks = u}, then stage 2 {W_2 tiles 2u, 2u+1 at k-step t-1}
 //     heads, per task and hidden tile (32): stage 1 as above (8 groups), stage 2 {W_2 tiles 0,1}, {tiles 2,3} at k-step t
 #pragma once
-#include "rowowner.hpp"
+#include "rowowner16_common.hpp"
 
 #define AMDREC_X3B_NAMESPACE x3b
 #define AMDREC_X3B_WAVES 8

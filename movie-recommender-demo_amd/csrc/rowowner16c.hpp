@@ -34,29 +34,14 @@
 //    dropped by the buffer descriptor's bounds check, no clamp).
 //    LDS: ring 64 KB + parameters 44 KB + exchange 16 KB + hidden planes 16 KB = 140 KB.
 #pragma once
-#include "rowowner16.hpp"
+#include "rowowner16_common.hpp"
 
 namespace amdrec {
 namespace x3c {
 
-using x3::CHUNK_BYTES;
-using x3::f16x8;
-using x3::FRAG_BYTES;
-using x3::Input;
-using x3::lds_byte;
-using x3::lds_cfloat;
-using x3::PARAM_FLOATS;
-using x3::Phase;
-using x3::Program;
-using x3b::add_rows;
-using x3b::hidden_planes;
-using x3b::init_pair;
-using x3b::load_rows;
-using x3b::param4;
-using x3b::reduce_sum4;
-using x3b::row_scale;
-using x3b::split8;
-using x3b::store_rows;
+using x3::CHUNK_BYTES, x3::f16x8, x3::FRAG_BYTES, x3::Input, x3::lds_byte, x3::lds_cfloat, x3::PARAM_FLOATS, x3::Phase, x3::Program;
+using x16::add_rows, x16::hidden_planes, x16::init_pair, x16::layer_norm, x16::load_rows, x16::mfma, x16::param4, x16::reduce_sum4,
+    x16::row_scale, x16::split8, x16::store_rows;
 
 // Elimination / stamp switches for tools/x3c_time.py (0 in the product): 1 = no weight DMA and no wait for it, 2 = no MFMAs,
 // 4 = no fragment reads, 16 = cycle stamps (whole kernel, chunk-closing waits + barriers) into the logits buffer's tail.
@@ -158,18 +143,18 @@ __device__ __forceinline__ void chunk(Ring& ring, f16x8 (&cur)[4], int& pos, con
         asm volatile("" : "+v"(c0), "+v"(c1) : "v"(cur[0]), "v"(cur[1]), "v"(cur[2]), "v"(cur[3]), "v"(bh), "v"(bl));
         ring.issue(pos);
     } else {                                  // group6's products in group6's order
-        c0 = x3b::mfma(cur[0], bl, c0);
-        c1 = x3b::mfma(cur[2], bl, c1);
+        c0 = mfma(cur[0], bl, c0);
+        c1 = mfma(cur[2], bl, c1);
         __builtin_amdgcn_sched_barrier(0);
         ring.template issue_piece<0>(pos);
         __builtin_amdgcn_sched_barrier(0);
-        c0 = x3b::mfma(cur[1], bh, c0);
-        c1 = x3b::mfma(cur[3], bh, c1);
+        c0 = mfma(cur[1], bh, c0);
+        c1 = mfma(cur[3], bh, c1);
         __builtin_amdgcn_sched_barrier(0);
         ring.template issue_piece<1>(pos);
         __builtin_amdgcn_sched_barrier(0);
-        c0 = x3b::mfma(cur[0], bh, c0);
-        c1 = x3b::mfma(cur[2], bh, c1);
+        c0 = mfma(cur[0], bh, c0);
+        c1 = mfma(cur[2], bh, c1);
         __builtin_amdgcn_sched_barrier(0);
         ring.template issue_piece<2>(pos);
         ring.template issue_piece<3>(pos);
@@ -240,7 +225,7 @@ __device__ __forceinline__ void prepare(const f32x4 (&x)[16], const f32x4 (&xo)[
     }
 }
 
-// x3b::layer_norm_scaled on the gathered accumulators, plus this wave's own tiles of the result from its own accumulators
+// x16::layer_norm_scaled on the gathered accumulators, plus this wave's own tiles of the result from its own accumulators
 // (the same expressions on the same values: xo[i] == y[4 w + i] bit for bit, without 192 selects to pick them out of y)
 __device__ __forceinline__ void layer_norm_own(const f32x4 (&all)[16], const f32x4 (&acc)[4], float un, f32x4 (&y)[16],
                                                f32x4 (&xo)[4], int w, lds_cfloat* pb, int gamma, int beta, float eps) {
@@ -352,7 +337,7 @@ __device__ __forceinline__ void phase_ffn_ln(Ring& ring, f16x8 (&cur)[4], const 
 // LayerNorm alone (layer 1's LN1 with its attention folded into the projection): no chunks, no exchange - every wave holds
 // the full rows; the 16-row kernel's own function on the same values, then this wave's tiles picked out of the result
 __device__ __forceinline__ void phase_ln(const Phase& P, f32x4 (&x)[16], f32x4 (&xo)[4], int w, lds_cfloat* pb) {
-    x3b::layer_norm(x, pb, P.gamma, P.beta, P.ln_eps);
+    layer_norm(x, pb, P.gamma, P.beta, P.ln_eps);
     own4(x, w, xo);
 }
 

@@ -1,0 +1,89 @@
+"""Dev tool: codegen gate between two builds of one translation unit.  Inputs per side: the device assembly
+(hipcc <product flags> --cuda-device-only -S) and the remarks of -Rpass-analysis=kernel-resource-usage (stderr of that
+compile).  Prints the resource table (parent | branch per kernel) or the per-kernel diff of the instruction streams with
+comments, .loc / .file / .cfi lines, labels' debug suffixes and metadata stripped.
+usage: python tools/isa_diff.py resources parent.remarks branch.remarks
+       python tools/isa_diff.py isa parent.s branch.s"""
+import difflib
+import re
+import subprocess
+import sys
+
+
+def demangle(names):
+    out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
+    return {n: re.sub(r"\(.*", "", d).replace("amdrec::", "") for n, d in zip(names, out)}
+
+
+def resources(path):
+    res, cur = {}, None
+    for line in open(path):
+        m = re.search(r"remark:\s+(.*?): (\S+) \[-Rpass-analysis", line)
+        if not m:
+            continue
+        if m.group(1) == "Function Name":
+            cur = res.setdefault(m.group(2), {})
+        elif cur is not None:
+            cur[m.group(1)] = m.group(2)
+    return res
+
+
+def kernels(path):
+    """kernel name -> its instruction lines (between the kernel's label and its s_endpgm / .Lfunc_end)"""
+    out, cur = {}, None
+    for line in open(path):
+        line = line.split(";")[0].rstrip()
+        s = line.strip()
+        m = re.match(r"^(\w+):$", s)
+        if m and cur is None and not s.startswith(".L"):
+            cur = out.setdefault(m.group(1), [])
+            continue
+        if cur is None:
+            continue
+        if s.startswith(".Lfunc_end"):
+            cur = None
+            continue
+        if not s or s.startswith((".loc", ".file", ".cfi", ".p2align", ".section", ".amdhsa", ".end_amdhsa", ".Ltmp", ".type", ".size")):
+            continue
+        cur.append(s)
+    return {k: v for k, v in out.items() if any(i.startswith("s_endpgm") for i in v)}
+
+
+def main():
+    mode, a, b = sys.argv[1:4]
+    if mode == "resources":
+        ra, rb = resources(a), resources(b)
+        names = demangle(sorted(set(ra) | set(rb)))
+        cols = [("VGPR", "VGPRs"), ("AGPR", "AGPRs"), ("SGPR", "TotalSGPRs"), ("scratch", "ScratchSize [bytes/lane]"),
+                ("spilled VGPRs", "VGPRs Spill"), ("LDS", "LDS Size [bytes/block]"), ("occ", "Occupancy [waves/SIMD]")]
+        print("Kernel resource usage of ranker_x3.hip (product flags + -Rpass-analysis=kernel-resource-usage), parent | branch")
+        print("conditions per kernel: VGPR, AGPR, scratch, spilled VGPRs, LDS and occupancy equal (SGPR shown for information)\n")
+        print("".join(f"{c[0]:>15}" for c in cols) + "  ok  kernel")
+        bad = 0
+        for n in sorted(names, key=names.get):
+            pa, pb = ra.get(n, {}), rb.get(n, {})
+            ok = all(pa.get(k) == pb.get(k) for _, k in cols if k != "TotalSGPRs") and bool(pa) and bool(pb)
+            bad += not ok
+            print("".join(f"{pa.get(k, '-') + '|' + pb.get(k, '-'):>15}" for _, k in cols) + f"  {'yes' if ok else 'NO '} {names[n]}")
+        print(f"\n{len(names)} kernels, {bad} outside the conditions")
+        return 1 if bad else 0
+    ka, kb = kernels(a), kernels(b)
+    names = demangle(sorted(set(ka) | set(kb)))
+    differ = 0
+    print("Instruction streams of ranker_x3.hip's kernels, parent against branch (comments, .loc / .file lines and metadata stripped)\n")
+    for n in sorted(names, key=names.get):
+        ia, ib = ka.get(n, []), kb.get(n, [])
+        cnt = lambda v: (sum(1 for i in v if not i.endswith(":") and not i.startswith(".")), sum(1 for i in v if i.startswith("v_mfma")))
+        same = ia == ib
+        differ += not same
+        print(f"{names[n]}: {'IDENTICAL' if same else 'DIFFERENT'}  instructions {cnt(ia)[0]} | {cnt(ib)[0]}  MFMAs {cnt(ia)[1]} | {cnt(ib)[1]}")
+        if not same:
+            d = list(difflib.unified_diff(ia, ib, "parent", "branch", n=1, lineterm=""))
+            print(f"  {sum(1 for l in d if l[:1] in '+-' and l[:3] not in ('+++', '---'))} changed lines; first hunks:")
+            print("\n".join("  " + l for l in d[:60]))
+    print(f"\n{len(names)} kernels, {differ} with a different instruction stream")
+    return 1 if differ else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,4 +1,5 @@
-// Elimination runs of the row-owner kernel (csrc/rowowner.hpp): the product kernel compiled with AMDREC_X3_DBG switches,
+// Elimination runs of the row-owner kernels (csrc/rowowner.hpp, rowowner16.hpp): the product kernel compiled with AMDREC_X3_DBG
+// switches (csrc/x3_common.hpp),
 // timed on the full chain (3 encoder layers, 3 cross, 3 heads) over 256000 synthetic rows.  Numerics are meaningless
 // here (random fragment bits); only time is read.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -DAMDREC_X3_DBG=<bits> tools/x3_probe.hip -o tools/bin/x3_probe_<bits>
@@ -90,7 +91,7 @@ int main(int argc, char** argv) {
     float ms = 0;
     CK(hipEventElapsedTime(&ms, e0, e1));
     ms /= reps;
-    if (AMDREC_X3_DBG & 16) {              // cycle stamps of every wave (rowowner16.hpp, DBG & 16)
+    if (AMDREC_X3_DBG & 16) {              // cycle stamps of every wave (rowowner16_impl.hpp, DBG & 16)
         std::vector<float> lg((size_t)rows * 4);
         CK(hipMemcpy(lg.data(), dlog, lg.size() * 4, hipMemcpyDeviceToHost));
         const long long nw = (long long)grid * (NTHREADS / 64);

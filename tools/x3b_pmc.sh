@@ -1,6 +1,7 @@
 #!/bin/bash
-# PMC passes over the row-owner probe binary (one counter group per pass; no tracing options besides kernel-trace)
-BIN=${1:-tools/bin/x3b_opt_0}
+# PMC passes over the row-owner probe binary (tools/x3_probe.hip, -DAMDREC_X3_VARIANT=16; one counter group per pass; no tracing
+# options besides kernel-trace)
+BIN=${1:-tools/bin/x3b_dbg0}
 OUT=${2:-gpurun_out/x3b_pmc}
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
