@@ -41,7 +41,11 @@ const char* amdrec_last_error(void);
  * unfilled slots (k > nrows) = -1 / -inf like faiss.  Rows are expected L2-normalised by the
  * caller (amdrec_l2_normalize), as FAISSIndex.add/search do (:114-115, :146-147).
  * n_fixup (device int, may be NULL) receives the number of queries that took the slow
- * exact fix-up path.  dim % 4 == 0, dim <= 2048, 1 <= k <= AMDREC_MAX_K. */
+ * exact fix-up path.  dim % 4 == 0, dim <= 2048, 1 <= k <= AMDREC_MAX_K.
+ * Non-finite input: a row whose score against the query is NaN (a NaN coordinate in the row or in the
+ * query, inf * 0, inf - inf) is never returned; the result is the exact top-k of the other rows, and the
+ * slots they cannot fill are -1 / -inf also when k <= nrows.  The mixed form below gives the same result,
+ * and counts EVERY query in n_fixup when max_norm is non-finite (a NaN or inf in the shadowed corpus). */
 int amdrec_flat_search_workspace(int64_t nq, int64_t nrows, int k, size_t* bytes /*host*/);
 int amdrec_flat_search(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
                        const float* queries, int64_t nq, int64_t ld_queries, int k,

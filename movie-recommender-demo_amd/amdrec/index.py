@@ -131,6 +131,8 @@ class FAISSIndex:
         self._xb16 = torch.empty((0, self.dimension), dtype=torch.bfloat16, device=self.device)
         self._maxnorm = torch.zeros(2, dtype=torch.float32, device=self.device)     # [max row norm, max row rounding-error norm]
         self._identity = True          # ids == arange(n): remap is the identity
+        self._nonfinite = False        # Flat: a stored row holds a NaN, so a search can leave slots unfilled with k <= n
+        self.n_fixup_out: Optional[torch.Tensor] = None    # Flat: device int32[1] that receives the C entry's n_fixup (diagnostics)
         self._host_ids: Optional[list] = None   # only for non-integer ids
         self._host_pos = None          # (len(_host_ids), {id: [positions]}) for exclusion lists, built on first use
         self._trained = self.index_type == "Flat"
@@ -200,6 +202,12 @@ class FAISSIndex:
         _lib.check(lib.amdrec_bf16_rows(_lib.ptr(x), hi - lo, x.stride(0), self.dimension, _lib.ptr(y), y.stride(0),
                                         _lib.ptr(self._maxnorm), _lib.stream_ptr(self.device)))
 
+    def _note_nonfinite(self, x):
+        """Flat: remember whether a stored row is non-finite (one reduction and a host read at add / load time, so that
+        search_device needs neither): such a row scores NaN and is never returned, which leaves slots unfilled."""
+        if self.index_type == "Flat" and not self._nonfinite and x.shape[0]:
+            self._nonfinite = not bool(torch.isfinite(x.sum()))      # normalised rows: a finite sum <=> every entry finite
+
     # -- reference API ----------------------------------------------------------------
     def train(self, embeddings):
         """faiss_retrieval.py:83-95: trains the coarse quantizer of IVF (and the product quantizer of IVFPQ); no-op for
@@ -231,7 +239,8 @@ class FAISSIndex:
         return None if self._ivf is None else self._ivf.centroids
 
     def add(self, embeddings, ad_ids: Optional[List] = None):
-        """faiss_retrieval.py:97-127."""
+        """faiss_retrieval.py:97-127.  A Flat index also checks the added rows for non-finite values (_note_nonfinite: one
+        reduction over them and a host read, i.e. add() synchronises), so that search_device never has to."""
         if not self._trained:
             self.train(embeddings)                                   # :107-108 (un-normalised input)
         t0 = time.time()
@@ -257,6 +266,7 @@ class FAISSIndex:
             x.copy_(src)                                             # casts + moves to the device
             self._normalize_(x)
             self._shadow_rows(self._n, self._n + m)
+            self._note_nonfinite(x)
         if ad_ids is None:                                           # :121-122
             new_ids = torch.arange(self._n, self._n + m, dtype=torch.int64, device=self.device)
             if self._host_ids is not None:
@@ -306,6 +316,13 @@ class FAISSIndex:
         -> (ids int64 [nq,k], scores float32 [nq,k]) on the device.  ``return_positions``: corpus
         positions (+ ``pos_offset``, the shard's first global row) instead of ids, -1 = unfilled.
         IVFPQ: the scores are squared L2 distances, ascending (+inf = unfilled): approximate, or exact with refine.
+        Non-finite input (Flat): a row whose score against the query is NaN - it holds a NaN, or the query does - is never
+        returned; the result is the exact top-k of the other rows and the tail stays unfilled: score -inf, position -1.
+        As an id an unfilled slot reads ``id_map[-1]``, as in the reference, with default and with custom ids alike when
+        the cause is a stored row (known since add / load).  A NaN QUERY on a finite index with default ids is not
+        detected without a launch more per search: its slots come back as -1 there, as ``ids[n - 1]`` with custom ids.
+        With the bf16 prefilter a non-finite row makes the shadow's norms non-finite and every query takes the exact
+        fix-up scan (n_fixup of the C entry = nq).
         ``exclude``: device int64 [nq, E], per query the ad ids that must not be returned (negative = padding): the
         unfiltered search for k + E with those ids removed, order kept, cut to k (amdrec.exclude has the contract;
         k + E <= AMDREC_MAX_K).  It applies to ids also under ``return_positions``.  None or E = 0: the plain search, not
@@ -334,15 +351,17 @@ class FAISSIndex:
         elif self.index_type == "IVFPQ":                              # scores = squared L2 distances, ascending
             self._pq.search(q, k, self.nprobe, scores, pos, pos_offset=off)
         elif self._mixed:
-            flat_search_mixed(self._xb, self._xb16, self._maxnorm, self._n, q, k, scores, pos, pos_offset=off)
+            flat_search_mixed(self._xb, self._xb16, self._maxnorm, self._n, q, k, scores, pos, pos_offset=off,
+                              n_fixup=self.n_fixup_out)
         else:
-            flat_search(self._xb, self._n, q, k, scores, pos, pos_offset=off)
+            flat_search(self._xb, self._n, q, k, scores, pos, pos_offset=off, n_fixup=self.n_fixup_out)
         if return_positions or self._identity:
             # identity map: id == position for filled slots; unfilled (-1) slots map to
             # id_map[-1] in the reference (:159) - reproduce that too
             if return_positions:
                 return pos, scores
-            if self._n and (k > self._n or self._state is not None):   # only then can a slot be unfilled
+            # a slot can be unfilled: k > n, an IVF probe set, a stored NaN row (otherwise only under a NaN query)
+            if self._n and (k > self._n or self._state is not None or self._nonfinite):
                 pos = torch.where(pos < 0, pos + self._n, pos)
             return pos, scores
         lib = _lib.load()
@@ -491,6 +510,8 @@ class FAISSIndex:
         self._ids[:n].copy_(torch.from_numpy(arrays["ids"].copy()))
         self._n = n
         self._shadow_rows(0, n)
+        if self._keeps_rows:
+            self._note_nonfinite(self._xb[:n])
         self._identity = header["identity_ids"]
         hid = header.get("host_ids")
         self._host_ids = None if hid is None else [_decode_id(x) for x in hid]
