@@ -1,0 +1,43 @@
+// What the inverted-list scans share (ivf.hip, ivfpq.hip): the search that takes a workgroup of a grouped scan to its list,
+// and the two scoring rules every path that files a key must agree on.
+#pragma once
+#include "common.hpp"
+
+namespace amdrec {
+
+// NaN scores rank last: filed as -inf, behind every finite row (make_key's order has no place for a NaN)
+__device__ __forceinline__ float rank_last(float sc) {
+    if (!(sc == sc)) sc = -INFINITY;
+    return sc;
+}
+
+// acc + x . y over four elements as ONE explicit fma chain, element 0 innermost.  The order is part of the contract: every
+// path that scores a row in fp32 (the pair scan, the prefilter's quarter-wave re-score and its overflow re-score) must round
+// identically, and a sum of products left to the compiler is contracted differently from one context to the next.
+__device__ __forceinline__ float fma4(f32x4 x, f32x4 y, float acc) {
+    return __builtin_fmaf(x[3], y[3], __builtin_fmaf(x[2], y[2], __builtin_fmaf(x[1], y[1], __builtin_fmaf(x[0], y[0], acc))));
+}
+
+// The list of query tile y of amdrec_ivf_group (blockIdx.y of a grouped scan): l with qt_prefix[l] <= y < qt_prefix[l+1];
+// the caller has returned for y >= qt_prefix[nlist].  The kernels keep the rest of the frame (list_off / group_off / p0 and
+// the second early return) themselves: moved in here as well, in any form tried, it compiled to another instruction stream.
+// A binary search is log2(nlist) DEPENDENT global loads - 12 round trips at nlist 4096, ~10 us in front of a workgroup
+// whose MFMAs take 14 (the per-rank shape of an 8-way sharded 10M index: 305-row lists, tools/shard_step_probe.py --index
+// ivf) - so every wave searches 64-ary: the lanes probe 64 evenly spaced entries of the bracket at once, a ballot counts
+// those at or below y (the prefix is non-decreasing): two or three round trips for any nlist up to 2^18.
+__device__ __forceinline__ int tile_list(long long y, const long long* qt_prefix, int nlist) {
+    int lo = 0, hi = nlist;
+    const int lane = threadIdx.x & 63;
+    while (hi - lo > 1) {                                                  // wave-uniform
+        const int step = (hi - lo + 63) >> 6;
+        const int idx = lo + lane * step;
+        const bool le = idx < hi && qt_prefix[idx] <= y;                   // lane 0 probes lo itself: always true
+        const int c = __builtin_popcountll(__ballot(le));                  // >= 1
+        const int nlo = lo + (c - 1) * step;
+        hi = nlo + step < hi ? nlo + step : hi;
+        lo = nlo;
+    }
+    return lo;
+}
+
+}  // namespace amdrec

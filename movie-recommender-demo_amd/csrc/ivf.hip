@@ -9,6 +9,7 @@
 //                selection is exact and deterministic for every input - no sampling, no fix-up.
 #include "gemm_core.hpp"
 #include "topk_utils.hpp"
+#include "invlists.hpp"
 #include "../../include/amdrec.h"
 
 namespace amdrec {
@@ -58,7 +59,8 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const float* xs, long lon
 #pragma unroll
             for (int u = 0; u < U; ++u) x[u] = xr[u][c];
 #pragma unroll
-            for (int u = 0; u < U; ++u)        // explicit fma chain: the same rounding sequence in every slot u
+            for (int u = 0; u < U; ++u)        // fma4's chain written out (through the helper the eight slots compile to another
+                                               // instruction order): the same rounding sequence in every slot u
                 part[u] = __builtin_fmaf(x[u][3], y[3], __builtin_fmaf(x[u][2], y[2], __builtin_fmaf(x[u][1], y[1],
                                          __builtin_fmaf(x[u][0], y[0], part[u]))));
         }
@@ -68,10 +70,7 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const float* xs, long lon
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
             const long long r = row0 + w * U + u;
-            if (lane == 0 && r < r1) {
-                if (!(a == a)) a = -INFINITY;       // NaN scores rank last
-                dst[r - r0] = make_key(a, (uint32_t)(spos[r] + pos_offset));
-            }
+            if (lane == 0 && r < r1) dst[r - r0] = make_key(rank_last(a), (uint32_t)(spos[r] + pos_offset));
         }
     }
 }
@@ -142,8 +141,7 @@ struct EpiIvfKeys {
                 for (int r = 0; r < 16; ++r) {
 #pragma unroll
                     for (int j = 0; j < TQ; ++j) {
-                        float sc = acc.v[i][j][r];
-                        if (!(sc == sc)) sc = -INFINITY;
+                        const float sc = rank_last(acc.v[i][j][r]);
                         if (sc >= tv[r] && posq[j] >= 0)
                             (keys + qv[r] * pool_ld)[atomicAdd(&fill[qv[r]], 1ull)] = make_key(sc, (uint32_t)posq[j]);
                     }
@@ -165,9 +163,7 @@ struct EpiIvfKeys {
 #pragma unroll
                 for (int j = 0; j < TQ; ++j) {
                     if (posq[j] < 0) continue;
-                    float sc = acc.v[i][j][r];
-                    if (!(sc == sc)) sc = -INFINITY;
-                    dst[rowq[j]] = make_key(sc, (uint32_t)posq[j]);
+                    dst[rowq[j]] = make_key(rank_last(acc.v[i][j][r]), (uint32_t)posq[j]);
                 }
             }
         }
@@ -211,7 +207,7 @@ struct EpiIvfPrefilter {
         float part = 0.f;
         for (int c = sub; c < (d >> 2); c += 16) {
             const f32x4 x = xr[c], y = qr[c];
-            part = __builtin_fmaf(x[3], y[3], __builtin_fmaf(x[2], y[2], __builtin_fmaf(x[1], y[1], __builtin_fmaf(x[0], y[0], part))));
+            part = fma4(x, y, part);
         }
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
@@ -220,7 +216,7 @@ struct EpiIvfPrefilter {
     // the threshold is the k-th score of the first phase, computed by the fp32 MFMA; the re-score sums in another order
     // (1e-7-level differences): a slack towards KEEPING never costs exactness, the select decides
     __device__ __forceinline__ void keep(float sc, long long row, long long q) const {
-        if (!(sc == sc)) sc = -INFINITY;
+        sc = rank_last(sc);
         const float t = tau[q * ld_tau];
         if (sc >= t - 1e-6f * fmaxf(1.f, fabsf(t)) || t == -INFINITY)
             (keys + q * pool_ld)[atomicAdd(&fill[q], 1ull)] = make_key(sc, (uint32_t)(spos[row] + pos_offset));
@@ -273,7 +269,7 @@ struct EpiIvfPrefilter {
                             float sc = 0.f;
                             for (int c = 0; c < (d >> 2); ++c) {
                                 const f32x4 x = xr[c], y = qr[c];
-                                sc = __builtin_fmaf(x[3], y[3], __builtin_fmaf(x[2], y[2], __builtin_fmaf(x[1], y[1], __builtin_fmaf(x[0], y[0], sc))));
+                                sc = fma4(x, y, sc);
                             }
                             keep(sc, rowq[j], qv[i][r]);
                         }
@@ -334,20 +330,7 @@ __global__ __launch_bounds__(S::NT, 2) void ivf_group_scan_mixed_kernel(
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const long long y = blockIdx.y;
     if (y >= qt_prefix[nlist]) return;
-    int lo = 0, hi = nlist;                                                // the tile's list: 64-ary search (ivf_group_scan_kernel)
-    {
-        const int lane = threadIdx.x & 63;
-        while (hi - lo > 1) {
-            const int step = (hi - lo + 63) >> 6;
-            const int idx = lo + lane * step;
-            const bool le = idx < hi && qt_prefix[idx] <= y;
-            const int c = __builtin_popcountll(__ballot(le));
-            const int nlo = lo + (c - 1) * step;
-            hi = nlo + step < hi ? nlo + step : hi;
-            lo = nlo;
-        }
-    }
-    const int l = lo;
+    const int l = tile_list(y, qt_prefix, nlist);
     const long long r0 = list_off[l], len = list_off[l + 1] - r0;
     if ((long long)blockIdx.x * S::BQ >= len) return;
     const long long g0 = goff[l], g = goff[l + 1] - g0;
@@ -393,12 +376,9 @@ struct EpiCoarseKeys {
 #pragma unroll
                     for (int e = 0; e < 4; e += 2) {
                         if (p + e >= nlist) continue;
-                        float s0 = acc.v[i][j][4 * g + e], s1 = acc.v[i][j][4 * g + e + 1];
-                        if (!(s0 == s0)) s0 = -INFINITY;            // NaN scores rank last (as in the list scan)
-                        if (!(s1 == s1)) s1 = -INFINITY;
                         u64x2 kk;
-                        kk[0] = make_key(s0, (uint32_t)(p + e));
-                        kk[1] = make_key(s1, (uint32_t)(p + e + 1)); // p+e+1 == nlist (odd nlist): lands in the ld padding
+                        kk[0] = make_key(rank_last(acc.v[i][j][4 * g + e]), (uint32_t)(p + e));
+                        kk[1] = make_key(rank_last(acc.v[i][j][4 * g + e + 1]), (uint32_t)(p + e + 1));   // p+e+1 == nlist (odd nlist): lands in the ld padding
                         *reinterpret_cast<u64x2*>(dst + p + e) = kk;
                     }
                 }
@@ -406,21 +386,19 @@ struct EpiCoarseKeys {
     }
 };
 
-using ShapeIvf = Shape<2, 2, 1, 4>;     // 64 queries x 256 list rows per workgroup
-using ShapeIvf32 = Shape<1, 4, 1, 2>;   // 32 queries x 256 list rows: for sparse groups (few probing queries per list: 512 x 64
-                                        // probes over 4096 lists is 8 per list, a 64-query tile would be 12 % full)
+// The grouped scans' tiles; BF16: the bf16-prefilter form of the same tile (K-step = 64 bf16)
+template <bool BF16> using ShapeIvf = Shape<2, 2, 1, 4, false, BF16>;     // 64 queries x 256 list rows per workgroup
+// 32 queries x 256 list rows: for sparse groups (few probing queries per list: 512 x 64 probes over 4096 lists is 8 per list,
+// a 64-query tile would be 12 % full)
+template <bool BF16> using ShapeIvf32 = Shape<1, 4, 1, 2, false, BF16>;
 // SHORT lists (round 4): a rank of an 8-way sharded 10M index holds ~305 rows of each of the 4096 lists - two 256-row tiles
 // of which the second is 19 % full (68 % of the MFMAs multiply padding); 128-row tiles pad the same list to 384 rows.
-using ShapeIvfS = Shape<2, 2, 1, 2>;    // 64 queries x 128 list rows
-using ShapeIvf32S = Shape<1, 4, 1, 1>;  // 32 queries x 128 list rows
+template <bool BF16> using ShapeIvfS = Shape<2, 2, 1, 2, false, BF16>;    // 64 queries x 128 list rows
+template <bool BF16> using ShapeIvf32S = Shape<1, 4, 1, 1, false, BF16>;  // 32 queries x 128 list rows
 // (double-buffered staging - one barrier per K-step - measured at the per-rank shape: 0.817 against 0.799 ms, not kept)
-using ShapeIvfB = Shape<2, 2, 1, 4, false, true>;      // the bf16-prefilter forms of the four shapes (K-step = 64 bf16)
-using ShapeIvf32B = Shape<1, 4, 1, 2, false, true>;
-using ShapeIvfSB = Shape<2, 2, 1, 2, false, true>;
-using ShapeIvf32SB = Shape<1, 4, 1, 1, false, true>;
 
-template <class ShapeIvf>
-__global__ __launch_bounds__(ShapeIvf::NT, 2) void ivf_group_scan_kernel(
+template <class S>
+__global__ __launch_bounds__(S::NT, 2) void ivf_group_scan_kernel(
     const float* xs, long long ld, int d, int ksteps, const long long* spos, const long long* list_off,
     const float* Q, long long ldq, const long long* goff, const long long* qt_prefix, int nlist,
     const long long* pair_q, const long long* pair_p, const long long* base, int nprobe, unsigned long long* keys,
@@ -428,36 +406,18 @@ __global__ __launch_bounds__(ShapeIvf::NT, 2) void ivf_group_scan_kernel(
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const long long y = blockIdx.y;
     if (y >= qt_prefix[nlist]) return;
-    // list l with qt_prefix[l] <= y < qt_prefix[l+1].  A binary search is log2(nlist) DEPENDENT global loads - 12 round trips
-    // at nlist 4096, ~10 us in front of a workgroup whose MFMAs take 14 (the per-rank shape of an 8-way sharded 10M index:
-    // 305-row lists, tools/shard_step_probe.py --index ivf) - so every wave searches 64-ary: the lanes probe 64 evenly
-    // spaced entries of the bracket at once, a ballot counts those at or below y (the prefix is non-decreasing): two or
-    // three round trips for any nlist up to 2^18.
-    int lo = 0, hi = nlist;
-    {
-        const int lane = threadIdx.x & 63;
-        while (hi - lo > 1) {                                                  // wave-uniform
-            const int step = (hi - lo + 63) >> 6;
-            const int idx = lo + lane * step;
-            const bool le = idx < hi && qt_prefix[idx] <= y;                   // lane 0 probes lo itself: always true
-            const int c = __builtin_popcountll(__ballot(le));                  // >= 1
-            const int nlo = lo + (c - 1) * step;
-            hi = nlo + step < hi ? nlo + step : hi;
-            lo = nlo;
-        }
-    }
-    const int l = lo;
+    const int l = tile_list(y, qt_prefix, nlist);
     const long long r0 = list_off[l], len = list_off[l + 1] - r0;
-    if ((long long)blockIdx.x * ShapeIvf::BQ >= len) return;
+    if ((long long)blockIdx.x * S::BQ >= len) return;
     const long long g0 = goff[l], g = goff[l + 1] - g0;
     GatherRows lp{Q, pair_q + g0, g, (int)ldq, d};
     DenseRows lq{xs + r0 * ld, len, (int)ld, d, 30, 1ll << 30};
     EpiIvfKeys epi{spos + r0, len, pair_q + g0, pair_p + g0, g, base, nprobe, keys, pool_ld, pos_offset, tau, ld_tau, fill};
-    const long long p0 = (y - qt_prefix[l]) * ShapeIvf::BP;
+    const long long p0 = (y - qt_prefix[l]) * S::BP;
     // gridDim.x workgroups share the list's row tiles (round 4: the host no longer launches one workgroup per row tile of
     // the LONGEST list - on short lists three of four workgroups found no rows after paying for the tile search)
-    for (long long row0 = (long long)blockIdx.x * ShapeIvf::BQ; row0 < len; row0 += (long long)gridDim.x * ShapeIvf::BQ)
-        gemm_block<ShapeIvf>(lp, lq, epi, ksteps, p0, row0, smem);     // (ends behind a barrier: the staging area is free)
+    for (long long row0 = (long long)blockIdx.x * S::BQ; row0 < len; row0 += (long long)gridDim.x * S::BQ)
+        gemm_block<S>(lp, lq, epi, ksteps, p0, row0, smem);     // (ends behind a barrier: the staging area is free)
 }
 
 // k largest of keys[q][0..n_q) -> sorted (score desc, position asc); fewer than k -> padded (-inf, -1).
@@ -836,37 +796,70 @@ extern "C" int amdrec_ivf_scan(const float* lists, int64_t ld, int dim, const in
     return AMDREC_OK;
 }
 
-template <class S>
-static hipError_t launch_group_scan(const char* tag, const float* lists, long long ld, int dim, const long long* row_pos,
-                                    const long long* list_off, int nlist, long long max_list_rows, const float* queries,
-                                    long long ld_queries, const long long* group_off, const long long* qtile_prefix,
-                                    long long qtile_bound, const long long* pair_query, const long long* pair_probe,
-                                    const long long* pool_base, int nprobe, unsigned long long* pool_keys, long long pool_ld,
-                                    long long pos_offset, const float* tau, long long ld_tau, unsigned long long* fill,
-                                    hipStream_t st) {
+// Workgroup columns per (list, query tile): an eighth of the LONGEST list's row tiles, each looping over its share of the
+// list's tiles.  Round 3 launched one workgroup per row tile of the longest list for every (list, query tile): list lengths
+// spread 0 .. 4x the mean, so three of four workgroups found no rows - after paying for the tile search - and at the
+// per-rank shape of an 8-way sharded 10M index (305-row lists) 48 000 of 61 000 workgroups were empty: scan 1.82 ->
+// 0.80 ms (profiles/r04_shard_ivf_g8_after.log).
+constexpr long long scan_columns(long long max_list_rows, int tile_rows) {
+    return ((max_list_rows + tile_rows - 1) / tile_rows + 7) / 8;
+}
+static_assert(scan_columns(305, 128) == 1 && scan_columns(9767, 256) == 5, "the per-rank and the single-GPU shape of the 10M index");
+
+// row tile: 128 rows when even the longest list is short (the tile count of a launch is sized by it), else 256
+constexpr long long SHORT_LIST_ROWS = 1536;
+
+// Both grouped kernels are launched here, so the two phases of one search cannot disagree about geometry; `args`: the
+// kernel's arguments
+template <class S, auto Kernel, class... Args>
+static hipError_t launch_grouped(const char* tag, long long max_list_rows, long long qtile_bound, hipStream_t st, Args... args) {
     static PerDeviceOnce attr_done;
     if (attr_done.pending()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_group_scan_kernel<S>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::LDS_BYTES);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)S::LDS_BYTES);
         if (e != hipSuccess) return e;
         attr_done.mark();
     }
-    // workgroups per (list, query tile): an eighth of the LONGEST list's row tiles, each looping over its share of the list's
-    // tiles.  Round 3 launched one workgroup per row tile of the longest list for every (list, query tile): list lengths
-    // spread 0 .. 4x the mean, so three of four workgroups found no rows - after paying for the tile search - and at the
-    // per-rank shape of an 8-way sharded 10M index (305-row lists) 48 000 of 61 000 workgroups were empty: scan 1.82 ->
-    // 0.80 ms (profiles/r04_shard_ivf_g8_after.log).  AMDREC_IVF_GX overrides for A/B runs.
-    static const long long gx_env = [] { const char* v = getenv("AMDREC_IVF_GX"); return v ? atoll(v) : 0ll; }();
-    long long gxl = (max_list_rows + S::BQ - 1) / S::BQ;
-    const long long cap = gx_env > 0 ? gx_env : (gxl + 7) / 8;
-    if (gxl > cap) gxl = cap;
-    const unsigned gx = (unsigned)gxl;
     ProfScope prof(tag, 0.0, 0.0, st);
-    hipLaunchKernelGGL(ivf_group_scan_kernel<S>, dim3(gx, (unsigned)qtile_bound), dim3(S::NT), S::LDS_BYTES, st, lists, ld, dim,
-                       (dim + BK - 1) / BK, row_pos, list_off, queries, ld_queries, group_off, qtile_prefix, nlist, pair_query,
-                       pair_probe, pool_base, nprobe, pool_keys, pool_ld, pos_offset, tau, ld_tau, fill);
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)scan_columns(max_list_rows, S::BQ), (unsigned)qtile_bound), dim3(S::NT),
+                       S::LDS_BYTES, st, args...);
     return hipGetLastError();
 }
+
+// f(shape, ProfScope tag) for the tile of (qtile, short_lists = the longest list has at most SHORT_LIST_ROWS rows)
+template <bool BF16, class F>
+static hipError_t with_scan_shape(int qtile, bool short_lists, F&& f) {
+    if (qtile == 64)
+        return short_lists ? f(ShapeIvfS<BF16>{}, BF16 ? "ivf_scan_grouped_bf16_64x128" : "ivf_scan_grouped_64x128")
+                           : f(ShapeIvf<BF16>{}, BF16 ? "ivf_scan_grouped_bf16_64x256" : "ivf_scan_grouped_64x256");
+    return short_lists ? f(ShapeIvf32S<BF16>{}, BF16 ? "ivf_scan_grouped_bf16_32x128" : "ivf_scan_grouped_32x128")
+                       : f(ShapeIvf32<BF16>{}, BF16 ? "ivf_scan_grouped_bf16_32x256" : "ivf_scan_grouped_32x256");
+}
+
+// The arguments the two grouped entries have in common and the refusals they share.  Each entry applies them in its own
+// order with its own conditions in between; "null pointer" and "bad leading dimension" are one REQUIRE per entry (its own
+// clauses and-ed to pointers() / leading_dims()), so which of them wins does not depend on the entry.
+struct GroupedArgs {
+    const float* lists; int64_t ld; int dim; const int64_t *row_pos, *list_off; int64_t max_list_rows;
+    const float* queries; int64_t ld_queries; const int64_t *group_off, *qtile_prefix; int64_t qtile_bound; int qtile;
+    const int64_t* pair_query; const uint64_t* pool_keys;
+    int check_dim(int multiple) const {
+        REQUIRE(dim >= multiple && dim % multiple == 0 && dim <= 2048, "dim=%d must be a multiple of %d in [%d,2048]", dim,
+                multiple, multiple);
+        return AMDREC_OK;
+    }
+    int check_qtile() const {
+        REQUIRE(qtile == 32 || qtile == 64, "qtile must be 32 or 64 (the value given to amdrec_ivf_group)");
+        return AMDREC_OK;
+    }
+    bool empty() const { return qtile_bound <= 0 || max_list_rows <= 0; }        // nothing to scan: AMDREC_OK
+    int check_bound() const {
+        REQUIRE(qtile_bound <= 65535, "too many (list, query-tile) groups for one launch: chunk the queries");
+        return AMDREC_OK;
+    }
+    bool pointers() const { return lists && row_pos && list_off && queries && group_off && qtile_prefix && pair_query && pool_keys; }
+    bool leading_dims() const { return ld % 4 == 0 && ld >= dim && ld_queries >= dim && ld_queries % 4 == 0; }
+};
 
 extern "C" int amdrec_ivf_scan_grouped(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
                                        const int64_t* list_off, int nlist, int64_t max_list_rows,
@@ -875,60 +868,27 @@ extern "C" int amdrec_ivf_scan_grouped(const float* lists, int64_t ld, int dim, 
                                        const int64_t* pair_query, const int64_t* pair_probe, const int64_t* pool_base,
                                        int nprobe, uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset,
                                        const float* tau, int64_t ld_tau, int64_t* pool_fill, void* stream) {
-    REQUIRE(dim >= 4 && dim % 4 == 0 && dim <= 2048, "dim=%d must be a multiple of 4 in [4,2048]", dim);
+    const GroupedArgs a{lists, ld, dim, row_pos, list_off, max_list_rows, queries, ld_queries, group_off, qtile_prefix, qtile_bound,
+                        qtile, pair_query, pool_keys};
+    if (int rc = a.check_dim(4)) return rc;
     REQUIRE(nlist >= 1 && nprobe >= 1, "bad nlist/nprobe");
-    REQUIRE(qtile == 32 || qtile == 64, "qtile must be 32 or 64 (the value given to amdrec_ivf_group)");
+    if (int rc = a.check_qtile()) return rc;
     REQUIRE((tau == nullptr) == (pool_fill == nullptr) && (tau == nullptr || ld_tau >= 1), "tau and pool_fill go together");
-    if (qtile_bound <= 0 || max_list_rows <= 0) return AMDREC_OK;
-    REQUIRE(qtile_bound <= 65535, "too many (list, query-tile) groups for one launch: chunk the queries");
-    REQUIRE(lists && row_pos && list_off && queries && group_off && qtile_prefix && pair_query && pair_probe &&
-                (pool_base || tau) && pool_keys, "null pointer");
-    REQUIRE(ld % 4 == 0 && ld >= dim && ld_queries >= dim && ld_queries % 4 == 0, "bad leading dimension");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipError_t e;
-    // row tile: 128 rows when even the longest list is short (the tile count of a launch is sized by it), else 256.
-    // AMDREC_IVF_SHORT_ROWS overrides the limit (0: never) for A/B runs (tools/shard_step_probe.py --index ivf).
-    static const long long short_rows = [] {
-        const char* v = getenv("AMDREC_IVF_SHORT_ROWS");
-        return v ? atoll(v) : 1536ll;
-    }();
-    const bool short_lists = max_list_rows <= short_rows;
-#define AMDREC_IVF_GROUP_SCAN(SHAPE, TAG)                                                                                       \
-    launch_group_scan<SHAPE>(TAG, lists, ld, dim, (const long long*)row_pos, (const long long*)list_off, nlist, max_list_rows, \
-                             queries, ld_queries, (const long long*)group_off, (const long long*)qtile_prefix, qtile_bound,    \
-                             (const long long*)pair_query, (const long long*)pair_probe, (const long long*)pool_base, nprobe,  \
-                             (unsigned long long*)pool_keys, pool_ld, pos_offset, tau, (long long)ld_tau,                      \
-                             (unsigned long long*)pool_fill, st)
-    if (qtile == 64) e = short_lists ? AMDREC_IVF_GROUP_SCAN(ShapeIvfS, "ivf_scan_grouped_64x128") : AMDREC_IVF_GROUP_SCAN(ShapeIvf, "ivf_scan_grouped_64x256");
-    else             e = short_lists ? AMDREC_IVF_GROUP_SCAN(ShapeIvf32S, "ivf_scan_grouped_32x128") : AMDREC_IVF_GROUP_SCAN(ShapeIvf32, "ivf_scan_grouped_32x256");
-#undef AMDREC_IVF_GROUP_SCAN
+    if (a.empty()) return AMDREC_OK;
+    if (int rc = a.check_bound()) return rc;
+    REQUIRE(a.pointers() && pair_probe && (pool_base || tau), "null pointer");
+    REQUIRE(a.leading_dims(), "bad leading dimension");
+    const hipError_t e = with_scan_shape<false>(qtile, max_list_rows <= SHORT_LIST_ROWS, [&](auto shape, const char* tag) {
+        using S = decltype(shape);
+        return launch_grouped<S, ivf_group_scan_kernel<S>>(
+            tag, max_list_rows, qtile_bound, reinterpret_cast<hipStream_t>(stream), lists, ld, dim, (dim + BK - 1) / BK,
+            (const long long*)row_pos, (const long long*)list_off, queries, ld_queries, (const long long*)group_off,
+            (const long long*)qtile_prefix, nlist, (const long long*)pair_query, (const long long*)pair_probe,
+            (const long long*)pool_base, nprobe, (unsigned long long*)pool_keys, pool_ld, pos_offset, tau, ld_tau,
+            (unsigned long long*)pool_fill);
+    });
     HIP_TRY(e);
     return AMDREC_OK;
-}
-
-template <class S>
-static hipError_t launch_group_scan_mixed(const char* tag, const float* lists, long long ld, const uint16_t* lists16, long long ld16,
-                                          int dim, const long long* row_pos, const long long* list_off, int nlist,
-                                          long long max_list_rows, const float* queries, long long ldq, const uint16_t* q16,
-                                          long long ldq16, const long long* group_off, const long long* qtile_prefix,
-                                          long long qtile_bound, const long long* pair_query, unsigned long long* pool_keys,
-                                          long long pool_ld, long long pos_offset, const float* tau, long long ld_tau,
-                                          const float* tau_lo, unsigned long long* fill, hipStream_t st) {
-    static PerDeviceOnce attr_done;
-    if (attr_done.pending()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_group_scan_mixed_kernel<S>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done.mark();
-    }
-    long long gxl = (max_list_rows + S::BQ - 1) / S::BQ;                  // as launch_group_scan
-    const long long cap = (gxl + 7) / 8;
-    if (gxl > cap) gxl = cap;
-    ProfScope prof(tag, 0.0, 0.0, st);
-    hipLaunchKernelGGL(ivf_group_scan_mixed_kernel<S>, dim3((unsigned)gxl, (unsigned)qtile_bound), dim3(S::NT), S::LDS_BYTES, st,
-                       lists, ld, lists16, ld16, dim, (dim / 2 + BK - 1) / BK, row_pos, list_off, queries, ldq, q16, ldq16,
-                       group_off, qtile_prefix, nlist, pair_query, pool_keys, pool_ld, pos_offset, tau, ld_tau, tau_lo, fill);
-    return hipGetLastError();
 }
 
 extern "C" int amdrec_ivf_filter_bounds(const float* queries, int64_t nq, int64_t ld_queries, int dim,
@@ -953,29 +913,26 @@ extern "C" int amdrec_ivf_scan_grouped_mixed(const float* lists, int64_t ld, con
                                              int64_t qtile_bound, int qtile, const int64_t* pair_query, uint64_t* pool_keys,
                                              int64_t pool_ld, int64_t pos_offset, const float* tau, int64_t ld_tau,
                                              const float* tau_lo, int64_t* pool_fill, void* stream) {
-    REQUIRE(dim >= 8 && dim % 8 == 0 && dim <= 2048, "dim=%d must be a multiple of 8 in [8,2048]", dim);
+    const GroupedArgs a{lists, ld, dim, row_pos, list_off, max_list_rows, queries, ld_queries, group_off, qtile_prefix, qtile_bound,
+                        qtile, pair_query, pool_keys};
+    if (int rc = a.check_dim(8)) return rc;
     REQUIRE(nlist >= 1, "bad nlist");
-    REQUIRE(qtile == 32 || qtile == 64, "qtile must be 32 or 64 (the value given to amdrec_ivf_group)");
-    if (qtile_bound <= 0 || max_list_rows <= 0) return AMDREC_OK;
-    REQUIRE(qtile_bound <= 65535, "too many (list, query-tile) groups for one launch: chunk the queries");
-    REQUIRE(lists && lists_bf16 && row_pos && list_off && queries && queries_bf16 && group_off && qtile_prefix && pair_query &&
-                pool_keys && tau && tau_lo && pool_fill, "null pointer");
-    REQUIRE(ld % 4 == 0 && ld >= dim && ld_queries >= dim && ld_queries % 4 == 0 && ld_bf16 >= dim && ld_bf16 % 8 == 0 &&
-                ld_queries_bf16 >= dim && ld_queries_bf16 % 8 == 0 && ld_tau >= 1, "bad leading dimension");
+    if (int rc = a.check_qtile()) return rc;
+    if (a.empty()) return AMDREC_OK;
+    if (int rc = a.check_bound()) return rc;
+    REQUIRE(a.pointers() && lists_bf16 && queries_bf16 && tau && tau_lo && pool_fill, "null pointer");
+    REQUIRE(a.leading_dims() && ld_bf16 >= dim && ld_bf16 % 8 == 0 && ld_queries_bf16 >= dim && ld_queries_bf16 % 8 == 0 &&
+                ld_tau >= 1, "bad leading dimension");
     REQUIRE(((uintptr_t)lists % 16) == 0 && ((uintptr_t)lists_bf16 % 16) == 0 && ((uintptr_t)queries % 16) == 0 &&
                 ((uintptr_t)queries_bf16 % 16) == 0, "lists / queries must be 16-byte aligned");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const bool short_lists = max_list_rows <= 1536;
-    hipError_t e;
-#define AMDREC_IVF_GROUP_SCAN_MIXED(SHAPE, TAG)                                                                                     \
-    launch_group_scan_mixed<SHAPE>(TAG, lists, ld, lists_bf16, ld_bf16, dim, (const long long*)row_pos, (const long long*)list_off, \
-                                   nlist, max_list_rows, queries, ld_queries, queries_bf16, ld_queries_bf16,                         \
-                                   (const long long*)group_off, (const long long*)qtile_prefix, qtile_bound,                         \
-                                   (const long long*)pair_query, (unsigned long long*)pool_keys, pool_ld, pos_offset, tau,           \
-                                   (long long)ld_tau, tau_lo, (unsigned long long*)pool_fill, st)
-    if (qtile == 64) e = short_lists ? AMDREC_IVF_GROUP_SCAN_MIXED(ShapeIvfSB, "ivf_scan_grouped_bf16_64x128") : AMDREC_IVF_GROUP_SCAN_MIXED(ShapeIvfB, "ivf_scan_grouped_bf16_64x256");
-    else             e = short_lists ? AMDREC_IVF_GROUP_SCAN_MIXED(ShapeIvf32SB, "ivf_scan_grouped_bf16_32x128") : AMDREC_IVF_GROUP_SCAN_MIXED(ShapeIvf32B, "ivf_scan_grouped_bf16_32x256");
-#undef AMDREC_IVF_GROUP_SCAN_MIXED
+    const hipError_t e = with_scan_shape<true>(qtile, max_list_rows <= SHORT_LIST_ROWS, [&](auto shape, const char* tag) {
+        using S = decltype(shape);
+        return launch_grouped<S, ivf_group_scan_mixed_kernel<S>>(
+            tag, max_list_rows, qtile_bound, reinterpret_cast<hipStream_t>(stream), lists, ld, lists_bf16, ld_bf16, dim,
+            (dim / 2 + BK - 1) / BK, (const long long*)row_pos, (const long long*)list_off, queries, ld_queries, queries_bf16,
+            ld_queries_bf16, (const long long*)group_off, (const long long*)qtile_prefix, nlist, (const long long*)pair_query,
+            (unsigned long long*)pool_keys, pool_ld, pos_offset, tau, ld_tau, tau_lo, (unsigned long long*)pool_fill);
+    });
     HIP_TRY(e);
     return AMDREC_OK;
 }

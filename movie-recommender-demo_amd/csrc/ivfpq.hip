@@ -9,7 +9,7 @@
 //   pq_scan    : one workgroup per (list, query tile of amdrec_ivf_group) x row range: the tile's tables staged in LDS, one
 //                code load per row, m LDS lookups per (row, query), pool keys (score = -distance) in amdrec_ivf_select's
 //                format - the existing select then yields (distance asc, position asc).
-#include "common.hpp"
+#include "invlists.hpp"
 #include "../../include/amdrec.h"
 
 namespace amdrec {
@@ -197,20 +197,7 @@ __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* codes
     __shared__ long long dst[QS];
     const long long y = blockIdx.y;
     if (y >= qt_prefix[nlist]) return;
-    int lo = 0, hi = nlist;                                              // the list of tile y: 64-ary search (ivf.hip)
-    {
-        const int lane = threadIdx.x & 63;
-        while (hi - lo > 1) {
-            const int step = (hi - lo + 63) >> 6;
-            const int idx = lo + lane * step;
-            const bool le = idx < hi && qt_prefix[idx] <= y;
-            const int c = __builtin_popcountll(__ballot(le));
-            const int nlo = lo + (c - 1) * step;
-            hi = nlo + step < hi ? nlo + step : hi;
-            lo = nlo;
-        }
-    }
-    const int l = lo;
+    const int l = tile_list(y, qt_prefix, nlist);
     const long long r0 = list_off[l], len = list_off[l + 1] - r0, nfin = list_fin ? list_fin[l] : len;
     if ((long long)blockIdx.x * 256 >= len) return;
     const long long g0 = goff[l], g = goff[l + 1] - g0;
@@ -252,9 +239,7 @@ __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* codes
                 float dist = lt[cw[0] & 0xff];
 #pragma unroll
                 for (int s = 1; s < M; ++s) dist += lt[s * PQ_KSUB + ((cw[s >> 2] >> (8 * (s & 3))) & 0xff)];
-                float sc = -dist;
-                if (!(sc == sc)) sc = -INFINITY;                         // NaN distances rank last
-                keys[dst[j] + row] = make_key(sc, pos);
+                keys[dst[j] + row] = make_key(rank_last(-dist), pos);               // NaN distances rank last
             }
         }
         // its rows with a non-finite coordinate (rare; none when list_fin is null): -inf keys, no lookups.  A loop of

@@ -63,6 +63,36 @@ int main() {
     EXPECT(amdrec_ivf_scan_grouped_mixed(fp, 256, nullptr, 256, 256, ip, ip, 16, 100, fp, 256,
                                          reinterpret_cast<uint16_t*>(fake), 256, ip, ip, 8, 64, ip, reinterpret_cast<uint64_t*>(fake),
                                          16, 0, fp, 1, fp, ip, nullptr) < 0);                                      // null shadow
+    // the two grouped scans share one argument check: which refusal wins and what it says (tests/golden/ivf_scan_refusals.json
+    // has the whole table); G / GM: the valid call with dim, nlist, qtile_bound, qtile, the first and the last pointer, ld replaced
+    {
+        uint16_t* hp = reinterpret_cast<uint16_t*>(fake);
+        uint64_t* kp = reinterpret_cast<uint64_t*>(fake);
+        auto refused = [](int rc, const char* msg) { return rc == -1 && strcmp(amdrec_last_error(), msg) == 0; };
+        auto G = [&](int dim, int nlist, int64_t bound, int qtile, const float* lists, const float* tau, int64_t ld) {
+            return amdrec_ivf_scan_grouped(lists, ld, dim, ip, ip, nlist, 100, fp, 256, ip, ip, bound, qtile, ip, ip, ip, 4, kp, 1024,
+                                           0, tau, 1, tau ? ip : nullptr, nullptr);
+        };
+        auto GM = [&](int dim, int nlist, int64_t bound, int qtile, const float* lists, int64_t* fill, int64_t ld) {
+            return amdrec_ivf_scan_grouped_mixed(lists, ld, hp, 256, dim, ip, ip, nlist, 100, fp, 256, hp, 256, ip, ip, bound, qtile,
+                                                 ip, kp, 1024, 0, fp, 1, fp, fill, nullptr);
+        };
+        EXPECT(refused(G(254, 0, 8, 64, fp, nullptr, 256), "dim=254 must be a multiple of 4 in [4,2048]"));        // dim before nlist
+        EXPECT(refused(GM(252, 0, 8, 64, fp, ip, 256), "dim=252 must be a multiple of 8 in [8,2048]"));
+        EXPECT(refused(G(256, 0, 8, 48, fp, nullptr, 256), "bad nlist/nprobe"));                                   // nlist before qtile
+        EXPECT(refused(GM(256, 0, 8, 48, fp, ip, 256), "bad nlist"));
+        EXPECT(refused(G(256, 16, 0, 48, nullptr, nullptr, 0), "qtile must be 32 or 64 (the value given to amdrec_ivf_group)"));
+        EXPECT(refused(amdrec_ivf_scan_grouped(fp, 256, 256, ip, ip, 16, 100, fp, 256, ip, ip, 0, 64, ip, ip, ip, 4, kp, 1024, 0, fp, 1,
+                                               nullptr, nullptr), "tau and pool_fill go together"));                // before the empty call
+        EXPECT(G(256, 16, 0, 64, nullptr, nullptr, 0) == 0 && GM(256, 16, -1, 32, nullptr, nullptr, 0) == 0);       // no tiles
+        EXPECT(refused(G(256, 16, 65536, 64, nullptr, nullptr, 0), "too many (list, query-tile) groups for one launch: chunk the queries"));
+        EXPECT(refused(GM(256, 16, 65536, 64, nullptr, nullptr, 0), "too many (list, query-tile) groups for one launch: chunk the queries"));
+        EXPECT(refused(G(256, 16, 8, 64, nullptr, nullptr, 252), "null pointer"));                                 // null before ld
+        EXPECT(refused(GM(256, 16, 8, 64, fp, nullptr, 252), "null pointer"));
+        EXPECT(refused(G(256, 16, 8, 64, fp, fp, 258), "bad leading dimension"));
+        EXPECT(refused(GM(256, 16, 8, 64, fp + 1, ip, 252), "bad leading dimension"));                             // ld before alignment
+        EXPECT(refused(GM(256, 16, 8, 64, fp + 1, ip, 256), "lists / queries must be 16-byte aligned"));
+    }
     EXPECT(amdrec_l2_normalize(fp, 256, fp, 256, 0, 256, nullptr) == 0);
     EXPECT(amdrec_remap_ids(ip, ip, 10, ip, 0, nullptr) == 0);
     EXPECT(amdrec_prep_numerical(fp, fp, fp, fp, 0, 13, nullptr) == 0);

@@ -104,6 +104,33 @@ def test_host_only_entry_points_validate_arguments_without_a_gpu():
     assert b"n_inexact" in lib.amdrec_last_error()
 
 
+def test_grouped_ivf_scan_refusals_match_the_recorded_table():
+    """amdrec_ivf_scan_grouped / amdrec_ivf_scan_grouped_mixed: return code and amdrec_last_error() text of every bad-argument
+    call of tests/golden/ivf_scan_refusals.json (one per clause of each entry's checks, pairs that pin which refusal wins,
+    the empty calls that return AMDREC_OK with pointers nobody looks at), recorded before the two entries shared their
+    argument check.  Every call returns before the entry's first HIP call."""
+    import json
+    from amdrec import _lib
+    lib = _lib.load()
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "ivf_scan_refusals.json")))
+    raw = ctypes.create_string_buffer(4096 + 256)
+    buf = (ctypes.addressof(raw) + 255) // 256 * 256           # "a non-null, aligned pointer"; never dereferenced
+
+    def value(v):
+        return buf + int(v[3:] or 0) if isinstance(v, str) else v
+
+    assert {c["entry"] for c in table["cases"]} == set(table["entries"]) == {"amdrec_ivf_scan_grouped", "amdrec_ivf_scan_grouped_mixed"}
+    for case in table["cases"]:
+        entry = table["entries"][case["entry"]]
+        assert case["set"] and set(case["set"]) <= set(entry["params"]), case       # the valid call itself would launch
+        assert case["rc"] in (0, -1), case
+        args = [value(case["set"].get(p, v)) for p, v in zip(entry["params"], entry["valid"])]
+        rc = getattr(lib, case["entry"])(*args)
+        assert rc == case["rc"], (case, rc, lib.amdrec_last_error())
+        if rc:
+            assert lib.amdrec_last_error().decode() == case["error"], case
+
+
 def test_model_workspace_queries_follow_the_architecture():
     import ctypes as C
     from amdrec import _lib, synth, weights

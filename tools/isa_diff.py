@@ -2,9 +2,11 @@
 (hipcc <product flags> --cuda-device-only -S) and the remarks of -Rpass-analysis=kernel-resource-usage (stderr of that
 compile).  Prints the resource table (parent | branch per kernel) or the per-kernel diff of the instruction streams with
 comments, .loc / .file / .cfi lines, labels' debug suffixes and metadata stripped.
-usage: python tools/isa_diff.py resources parent.remarks branch.remarks
-       python tools/isa_diff.py isa parent.s branch.s"""
+usage: python tools/isa_diff.py resources parent.remarks branch.remarks [tu]
+       python tools/isa_diff.py isa parent.s branch.s [tu]
+tu: the translation unit's name for the headings (default: the branch file's name up to its first dot + ".hip")"""
 import difflib
+import os
 import re
 import subprocess
 import sys
@@ -51,12 +53,13 @@ def kernels(path):
 
 def main():
     mode, a, b = sys.argv[1:4]
+    tu = sys.argv[4] if len(sys.argv) > 4 else os.path.basename(b).split(".")[0] + ".hip"
     if mode == "resources":
         ra, rb = resources(a), resources(b)
         names = demangle(sorted(set(ra) | set(rb)))
         cols = [("VGPR", "VGPRs"), ("AGPR", "AGPRs"), ("SGPR", "TotalSGPRs"), ("scratch", "ScratchSize [bytes/lane]"),
                 ("spilled VGPRs", "VGPRs Spill"), ("LDS", "LDS Size [bytes/block]"), ("occ", "Occupancy [waves/SIMD]")]
-        print("Kernel resource usage of ranker_x3.hip (product flags + -Rpass-analysis=kernel-resource-usage), parent | branch")
+        print(f"Kernel resource usage of {tu} (product flags + -Rpass-analysis=kernel-resource-usage), parent | branch")
         print("conditions per kernel: VGPR, AGPR, scratch, spilled VGPRs, LDS and occupancy equal (SGPR shown for information)\n")
         print("".join(f"{c[0]:>15}" for c in cols) + "  ok  kernel")
         bad = 0
@@ -70,7 +73,7 @@ def main():
     ka, kb = kernels(a), kernels(b)
     names = demangle(sorted(set(ka) | set(kb)))
     differ = 0
-    print("Instruction streams of ranker_x3.hip's kernels, parent against branch (comments, .loc / .file lines and metadata stripped)\n")
+    print(f"Instruction streams of {tu}'s kernels, parent against branch (comments, .loc / .file lines and metadata stripped)\n")
     for n in sorted(names, key=names.get):
         ia, ib = ka.get(n, []), kb.get(n, [])
         cnt = lambda v: (sum(1 for i in v if not i.endswith(":") and not i.startswith(".")), sum(1 for i in v if i.startswith("v_mfma")))
