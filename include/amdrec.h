@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-#define AMDREC_ABI_VERSION 14 /* (v14 later gained amdrec_exclude_compact: one added export, nothing else changed; and the
+#define AMDREC_ABI_VERSION 14 /* (v14 later gained amdrec_exclude_compact, then amdrec_remove_plan[_workspace] and amdrec_rows_gather:
+                               * added exports, nothing else changed; and the
                                * first-FFN hidden cache: amdrec_ranker_project_ads_hidden, amdrec_x3_weights.stream_hc ... at the
                                * struct's end, amdrec_ranker_params.ad_hidden_cache - the number stays, the library and its
                                * binding ship together and the struct layouts are checked against the compiler, tests/test_abi.py) */
@@ -458,6 +459,29 @@ int amdrec_exclude_compact(const int64_t* keys /*[nq][kc]*/, const float* scores
                            const int64_t* exclude /*[nq][ld_exclude]*/, int n_exclude, int64_t ld_exclude, int k,
                            int64_t fill_key, float fill_score, int64_t fill_carry, int64_t* out_keys /*[nq][k]*/,
                            float* out_scores /*[nq][k]*/, int64_t* out_carry /*[nq][k] or NULL*/, void* stream);
+
+/* Live corpus: removing rows without recomputing any (two more exports added to ABI v14, every other entry as it was).  A
+ * removal is an order-preserving compaction of every per-row array the caller keeps: amdrec_remove_plan says which rows stay,
+ * amdrec_rows_gather moves one array.
+ *
+ * amdrec_remove_plan: row i of n has the key ids[i] (ids == NULL: the key is i itself) and stays unless that key is in
+ * `remove` (n_remove entries, ascending, unique, >= 0; a negative key matches nothing).  kept[0 .. *n_kept) = the old
+ * positions of the rows that stay, ascending; the rest of kept[n] is left as it was; *n_kept is a DEVICE scalar.  Three plain
+ * launches (flag + count per 1024 rows, one workgroup scanning the counts, write); no workgroup waits for another.
+ * 0 <= n <= 2^31 - 1.  n == 0 writes *n_kept = 0 (or nothing, if n_kept is NULL) and needs no other pointer; n_remove == 0
+ * (remove may be NULL) makes kept the identity.  Workspace: amdrec_remove_plan_workspace(n), 256-byte aligned. */
+int amdrec_remove_plan_workspace(int64_t n, size_t* bytes /*host*/);
+int amdrec_remove_plan(const int64_t* ids /*[n] or NULL*/, int64_t n, const int64_t* remove /*[n_remove]*/,
+                       int64_t n_remove, int64_t* kept /*[n]*/, int64_t* n_kept /*device scalar*/, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
+/* dst[j] = src[pos[j]] for j < n_out, byte for byte: rows of row_bytes >= 1 bytes, row pitches ld_*_bytes >= row_bytes (the
+ * padding between rows is neither read nor written).  Out of place: the byte ranges of src (n_src rows) and dst (n_out rows)
+ * must not overlap.  A position outside [0, n_src) is never read: that row of dst is zero-filled.  Accesses are 16 bytes wide
+ * when src, dst, both pitches and row_bytes are all multiples of 16, else the widest of 8 / 4 / 1 that divides them all;
+ * byte offsets are 64-bit; one launch whose capped grid strides over the rows.  n_out == 0 returns at once. */
+int amdrec_rows_gather(const void* src, int64_t ld_src_bytes, int64_t n_src, const int64_t* pos /*[n_out]*/,
+                       int64_t n_out, int64_t row_bytes, void* dst, int64_t ld_dst_bytes, void* stream);
 
 /* Optional per-launch timing: HIP events recorded on the launch stream around every GEMM-shaped
  * kernel launch, accumulated per kernel tag ("<epilogue>_<BP>x<BQ>", DESIGN.md maps tags to

@@ -69,6 +69,9 @@ _SIGNATURES = {
     "amdrec_l2_normalize": [_fp, _i64, _fp, _i64, _i64, _i32, _vp],
     "amdrec_remap_ids": [_vp, _vp, _i64, _vp, _i64, _vp],
     "amdrec_exclude_compact": [_vp, _fp, _vp, _i64, _i32, _vp, _i32, _i64, _i32, _i64, C.c_float, _i64, _vp, _fp, _vp, _vp],
+    "amdrec_remove_plan_workspace": [_i64, C.POINTER(_sz)],
+    "amdrec_remove_plan": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp],
+    "amdrec_rows_gather": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp],
     "amdrec_profile_enable": [_i32],
     "amdrec_profile_only": [C.c_char_p],
     "amdrec_profile_report": [_vp, _i32, C.POINTER(_i32)],

@@ -26,7 +26,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, exclude as _exclude, ivf, ivfpq
+from . import _lib, exclude as _exclude, ivf, ivfpq, rows_edit as _rows_edit
 
 _MAGIC = b"AMDRECIX1"
 ADD_BATCH = 1 << 18            # IVFPQ add: rows normalised and encoded per batch (256 MB of fp32 at d = 256)
@@ -135,6 +135,7 @@ class FAISSIndex:
         self.n_fixup_out: Optional[torch.Tensor] = None    # Flat: device int32[1] that receives the C entry's n_fixup (diagnostics)
         self._host_ids: Optional[list] = None   # only for non-integer ids
         self._host_pos = None          # (len(_host_ids), {id: [positions]}) for exclusion lists, built on first use
+        self._default_ids_ok = True    # False once remove_ids has moved rows: a default id (= position) could repeat a kept id
         self._trained = self.index_type == "Flat"
         self._keeps_rows = self.index_type != "IVFPQ"    # IVFPQ: codes only, no fp32 corpus on the device
         self._state = None             # set by train(): the IVFState / IVFPQState behind ...
@@ -241,6 +242,9 @@ class FAISSIndex:
     def add(self, embeddings, ad_ids: Optional[List] = None):
         """faiss_retrieval.py:97-127.  A Flat index also checks the added rows for non-finite values (_note_nonfinite: one
         reduction over them and a host read, i.e. add() synchronises), so that search_device never has to."""
+        if ad_ids is None and not self._default_ids_ok:
+            raise ValueError("add() without ad_ids after remove_ids(): default ids are corpus positions, and the removal has "
+                             "moved the positions under the ids that stayed; pass ad_ids")
         if not self._trained:
             self.train(embeddings)                                   # :107-108 (un-normalised input)
         t0 = time.time()
@@ -298,6 +302,69 @@ class FAISSIndex:
         self._n += m
         self._log(f"Added embeddings in {time.time() - t0:.2f}s")
         self._log(f"Total index size: {self._n}")
+
+    def remove_ids(self, ad_ids, return_kept: bool = False):
+        """Remove every row whose id is in ``ad_ids`` -> the number of rows removed (``return_kept``: also ``kept``, device
+        int64 [ntotal after the call], the old position of every row that stays).  No counterpart in the reference, whose
+        wrapper can only add.
+
+        Ids need not be unique in the index: every row that carries a listed id goes.  Ids that no row has and duplicates
+        in the list are ignored; an empty list (or one that hits nothing) touches nothing.  The rows that stay keep their
+        relative order - so the tie rule "lower position first" and the insertion order inside IVF lists give what a fresh
+        index over the same rows gives - and they keep their ids: an index with default ids stops being one whose ids are
+        its positions, and the id remap of custom ids takes over.  For that reason ``add`` without ``ad_ids`` raises
+        ValueError from then on (a default id is a position, and the positions have moved under the ids that stayed); with
+        explicit ids it works as before.  Removing every row leaves a trained, empty index in its initial id state.
+        Integer ids are matched on the device; non-integers then raise TypeError and negatives ValueError.  With host-side
+        object ids the list is resolved to positions on the host.
+
+        Nothing is recomputed: IVF centroids, PQ codebooks, list assignments and codes stay as they are, and every stored
+        array (rows, ids, assignments, codes, finite flags, refine rows) is gathered by ``kept`` with amdrec_rows_gather.
+        Only a Flat index's bf16 shadow and its norm bound are rebuilt from the compacted rows (amdrec_bf16_rows), and its
+        "a stored row is non-finite" state is taken again from the rows that stay; IVF lists are laid out again by the next
+        search.  Always out of place: each array is gathered into a NEW tensor that then replaces the old one, which is
+        never written - a search in flight or a captured graph (which pins the tensors it was captured with) keeps reading
+        the index as it was: stale, never half-compacted.  Peak extra memory: one copy of the arrays being rebuilt.
+        The call reads the number of survivors back, i.e. it synchronises with the host."""
+        n = self._n
+        if self._host_ids is not None:
+            where = self._host_positions()
+            remove = np.unique(np.asarray([p for x in dict.fromkeys(ad_ids) for p in where.get(x, ())], dtype=np.int64))
+            keys = None                                              # the list holds positions
+        else:
+            remove = _rows_edit.removal_list(ad_ids)
+            keys = None if self._identity else self._ids
+        removed = 0
+        if n and remove.size:
+            kept, removed = _rows_edit.plan_for(keys, n, remove, self.device)
+        if not removed:
+            return (0, torch.arange(n, dtype=torch.int64, device=self.device)) if return_kept else 0
+        m = n - removed
+
+        def gather(t):
+            return _rows_edit.gather_rows(t, kept, n)
+        if self._host_ids is not None:
+            self._host_ids = [self._host_ids[p] for p in kept.cpu().tolist()]
+        self._host_pos = None                    # (keyed by len(_host_ids) alone: a later add of as many rows would revive it)
+        self._ids = gather(self._ids)
+        if self._keeps_rows:
+            self._xb = gather(self._xb)
+        self._n = m
+        if self._mixed:
+            self._xb16 = torch.empty((m, self.dimension), dtype=torch.bfloat16, device=self.device)
+            self._maxnorm = torch.zeros(2, dtype=torch.float32, device=self.device)
+            self._shadow_rows(0, m)
+        if self.index_type == "Flat":
+            self._nonfinite = False
+            self._note_nonfinite(self._xb[:m])
+        if self._state is not None:
+            self._state.compact(kept)
+        self._identity = False
+        self._default_ids_ok = False
+        if m == 0:                               # empty again: positions restart, no id is left to collide with
+            self._identity, self._default_ids_ok, self._host_ids = True, True, None
+        self._log(f"Removed {removed} vectors; total index size: {self._n}")
+        return (removed, kept) if return_kept else removed
 
     def resident_tensors(self) -> list:
         """Every device tensor the index keeps between calls (a captured graph's kernels point at them)."""
@@ -407,15 +474,20 @@ class FAISSIndex:
         else:
             if len(exclude) != nq:
                 raise ValueError(f"{len(exclude)} exclusion lists for {nq} queries")
-            if self._host_pos is None or self._host_pos[0] != len(self._host_ids):
-                where = {}
-                for p, x in enumerate(self._host_ids):
-                    where.setdefault(x, []).append(p)
-                self._host_pos = (len(self._host_ids), where)
-            where = self._host_pos[1]
+            where = self._host_positions()
             blk = _exclude.pad_exclusions([[p for x in dict.fromkeys(row) for p in where.get(x, ())] for row in exclude])
             blk = blk if blk.shape[1] else None
         return None if blk is None else torch.from_numpy(blk).to(self.device)
+
+    def _host_positions(self) -> dict:
+        """{id: [positions]} of the host-side object ids, built on first use and after every change of their number
+        (remove_ids drops it: the number alone would not show a removal followed by an add of as many rows)."""
+        if self._host_pos is None or self._host_pos[0] != len(self._host_ids):
+            where = {}
+            for p, x in enumerate(self._host_ids):
+                where.setdefault(x, []).append(p)
+            self._host_pos = (len(self._host_ids), where)
+        return self._host_pos[1]
 
     def search(self, query_embeddings, k: int = 100, return_distances: bool = True, exclude=None):
         """faiss_retrieval.py:129-166.  numpy in, numpy out: (ad_ids, distances).  ``exclude``: one sequence of ad ids per

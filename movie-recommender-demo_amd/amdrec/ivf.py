@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .rows_edit import gather_rows
 
 NITER = 10
 MAX_POINTS_PER_CENTROID = 256
@@ -194,6 +195,14 @@ class InvertedLists:
         self.lists = None
         self._top_rows = None
 
+    def compact(self, kept: torch.Tensor):
+        """Rows were removed (FAISSIndex.remove_ids): keep the list of every row in ``kept`` (old positions, ascending), as
+        a NEW tensor, and drop the layout and its bound explicitly - ``lists.n != n`` alone would miss a removal that an
+        add of as many rows follows.  Centroids stay: nothing is re-assigned."""
+        self.assign = gather_rows(self.assign, kept)
+        self.lists = None
+        self._top_rows = None
+
     def layout(self, n: int, rows: torch.Tensor, last: Optional[torch.Tensor] = None) -> ListLayout:
         """(Re)build the list layout of rows [0, n): one stable sort by list (rows of a list keep insertion order; those
         flagged in the bool tensor ``last`` go behind the list's others); ``rows`` is the owner's per-row payload in
@@ -316,6 +325,10 @@ class IVFState(InvertedLists):
     def append(self, x_normalised: torch.Tensor, start: int):
         assert start == self.assign.shape[0]
         self.extend([self.assign_rows(x_normalised)])
+
+    def compact(self, kept: torch.Tensor):
+        super().compact(kept)
+        self._shadow = None
 
     def _build_lists(self, xb: torch.Tensor, n: int) -> ListLayout:
         if self.lists is None or self.lists.n != n:

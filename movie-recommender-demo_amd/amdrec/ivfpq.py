@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .rows_edit import gather_rows
 from .ivf import (POOL_BYTES, MAX_POINTS_PER_CENTROID, MAX_QUERY_TILES, InvertedLists, _normalize, grouped_chunk_limit,
                   search_nprobe)
 
@@ -172,6 +173,17 @@ class IVFPQState:
         self.finite = torch.cat([self.finite] + [b[2] for b in batches])
         if self.rows is not None:                           # (as the codes: an O(n) copy and, for its duration, twice the bytes)
             self.rows = torch.cat([self.rows] + [b[3] for b in batches])
+
+    def compact(self, kept: torch.Tensor):
+        """Rows were removed (FAISSIndex.remove_ids): the assignment, the codes, the finite flags and, with refine, the kept
+        rows of the rows in ``kept`` (old positions, ascending), each gathered into a NEW tensor; the list layout is dropped.
+        Centroids and codebooks stay: nothing is re-assigned or re-encoded."""
+        self.ivf.compact(kept)
+        self.codes = gather_rows(self.codes, kept)
+        self.finite = gather_rows(self.finite, kept)
+        if self.rows is not None:
+            self.rows = gather_rows(self.rows, kept)
+        self._nfin = None
 
     def _build_lists(self):
         """-> (the layout: codes list-contiguous, a list's non-finite rows after its finite ones; finite rows per list)."""

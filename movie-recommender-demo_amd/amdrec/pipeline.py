@@ -27,7 +27,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import _lib, exclude as _exclude
+from . import _lib, exclude as _exclude, rows_edit as _rows_edit
 from .index import FAISSIndex
 from .ranker import TransformerRanker
 from .towers import TwoTowerModel
@@ -261,6 +261,59 @@ class AdRecommenderInference:
         static [batch_size, max_exclude] exclusion buffer (stage 1 always searches stage1_k + max_exclude) that the
         replayer's ``exclude`` argument fills; 0 captures the graph without the exclusion step."""
         return GraphedRecommender(self, batch_size, top_k, stage1_k, warmup, max_exclude)
+
+    # -- live corpus: ads leave and enter without a rebuild of the index or of the ranker's per-ad caches ------------------
+    def remove_ads(self, ad_ids) -> int:
+        """Retire every ad whose id is in ``ad_ids`` -> the number of ads removed.  The index drops their rows
+        (FAISSIndex.remove_ids has the contract), the ad-feature table becomes its gather by the rows that stay, and the
+        ranker's per-ad caches are moved along bit for bit (TransformerRanker.compact_ad_cache): bytes move, nothing is
+        projected again.  Rows of the table beyond the index's old ntotal (a table longer than the corpus) are dropped.
+        Out of place throughout: a graph captured before the call keeps replaying the corpus it was captured with (stale,
+        consistent); capture again to serve the new one.  Synchronises with the host once (the survivor count)."""
+        removed, kept = self.faiss_index.remove_ids(ad_ids, return_kept=True)
+        if not removed:
+            return 0
+        old = self.ad_features
+        new = _rows_edit.gather_rows(old, kept)
+        self.transformer_ranker.compact_ad_cache(old, kept, new)
+        self._swap_ad_table(old, new)
+        return removed
+
+    def add_ads(self, embeddings, ad_features, ad_ids=None) -> None:
+        """Insert ads: ``embeddings`` [m, d] go to the index (FAISSIndex.add: ``ad_ids`` as there; required once ads have been
+        removed), ``ad_features`` [m, n_ad_feat] integer rows are appended to the ad-feature table, and the ranker's per-ad
+        caches grow by projecting the m new rows only (TransformerRanker.extend_ad_cache).  The feature rows are checked
+        against the ranker's ad embedding tables first (IndexError, as an embedding lookup would raise), and a rejected call
+        - bad features, or ids the index refuses - leaves index, table and caches as they were.  Out of place, as
+        remove_ads.  A table that was longer than the corpus is cut to it first (the new rows' positions follow the
+        corpus), and the caches are then rebuilt lazily instead of extended."""
+        idx = self.faiss_index
+        feats = ad_features if isinstance(ad_features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ad_features))
+        if feats.is_floating_point() or feats.dtype == torch.bool:
+            raise TypeError(f"ad_features must be integers, got {feats.dtype}")
+        feats = feats.to(device=self.device, dtype=torch.int64).contiguous()
+        old = self.ad_features
+        if feats.dim() != 2 or feats.shape[1] != old.shape[1] or feats.shape[0] != len(embeddings):
+            raise ValueError(f"ad_features must be [{len(embeddings)}, {old.shape[1]}], got {tuple(feats.shape)}")
+        cards = torch.tensor([e.weight.shape[0] for e in self.transformer_ranker.ad_embeddings.values()],
+                             dtype=torch.int64, device=self.device)
+        if feats.numel() and bool(((feats < 0) | (feats >= cards)).any().item()):
+            raise IndexError("index out of range in self: an ad_features row is outside the ranker's ad embedding tables")
+        n_old = idx.index.ntotal
+        idx.add(embeddings, ad_ids)              # (refuses before it commits anything)
+        new = torch.cat([old[:n_old], feats])
+        if old.shape[0] == n_old:
+            self.transformer_ranker.extend_ad_cache(old, new)
+        self._swap_ad_table(old, new)
+
+    def _swap_ad_table(self, old, new):
+        """Install ``new`` as the ad-feature table.  A "valid" verdict of the once-per-table check (_ad_table_valid) is
+        carried over: rows gathered from a valid table are valid, and add_ads has checked what it appended."""
+        c = self.__dict__.get("_ad_ok")
+        self.ad_features = new
+        if c is not None and c[0][2] is old and c[0][3] == old._version and c[0][0] == _lib._REG_EPOCH[0] and \
+                c[0][1] is self.transformer_ranker and c[1]:
+            self.__dict__["_ad_ok"] = ((c[0][0], c[0][1], new, new._version), c[1])
 
     # -- reference API ------------------------------------------------------------------------
     def recommend_ads(self, user_data: dict, top_k: int = 10, stage1_k: int = 500,

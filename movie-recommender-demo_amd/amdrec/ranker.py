@@ -186,6 +186,57 @@ class TransformerRanker(nn.Module):
             _lib.stream_ptr(dev)))
         self._ad_cache = (*c[:5], hid)
 
+    def compact_ad_cache(self, old_table, kept, new_table):
+        """Rows left the ad table: ``new_table`` = ``old_table[kept]`` (``kept``: device int64, old positions).  If a valid
+        cache exists for ``old_table``, its rows are moved along - the projection cache, and the hidden cache when there is
+        one, gathered by ``kept`` into NEW tensors, bit for bit (amdrec_rows_gather; the old tensors are left as they are
+        for whoever still reads them) - and the cache now belongs to ``new_table``.  Otherwise nothing happens: the cache
+        is built lazily, as ever."""
+        from .rows_edit import gather_rows
+        if not isinstance(old_table, torch.Tensor) or not old_table.is_cuda:
+            return
+        self._pack(old_table.device)
+        if self._cache_for(old_table) is None:
+            return
+        c = self._ad_cache
+        proj = gather_rows(c[4], kept)
+        hid = None if c[5] is None else gather_rows(c[5], kept)
+        self._ad_cache = (c[0], new_table.data_ptr(), tuple(new_table.shape), new_table._version, proj, hid)
+
+    def extend_ad_cache(self, old_table, new_table):
+        """Rows were appended to the ad table: ``new_table[:len(old_table)]`` equals ``old_table``.  If a valid cache exists
+        for ``old_table``, only the appended rows are projected (amdrec_ranker_project_ads, and _hidden when the hidden
+        cache exists and both caches still fit ``hidden_cache_max_bytes`` at the new size - else the hidden cache is
+        dropped), into grown copies of the caches, which then belong to ``new_table``.  Otherwise nothing happens."""
+        from .rows_edit import grown_copy
+        if not isinstance(old_table, torch.Tensor) or not old_table.is_cuda:
+            return
+        dev = old_table.device
+        params, _ = self._pack(dev)
+        if self._cache_for(old_table) is None:
+            return
+        n_old, n_new = int(old_table.shape[0]), int(new_table.shape[0])
+        if n_new < n_old or not new_table.is_contiguous() or new_table.shape[1:] != old_table.shape[1:]:
+            raise ValueError("extend_ad_cache: new_table must be old_table plus appended rows, contiguous")
+        c = self._ad_cache
+        lib = _lib.load()
+        tail = new_table[n_old:]
+        proj = grown_copy(c[4], n_old, n_new)
+        hid = None
+        if c[5] is not None and n_new * (self.d_model + int(params.d_ff)) * 4 <= int(self.hidden_cache_max_bytes):
+            hid = grown_copy(c[5], n_old, n_new)
+        if n_new > n_old:
+            ws = _lib.WORKSPACE.get(4 * max(self.d_model, int(params.d_ff)) + 256, dev)
+            out = proj[n_old:]
+            _lib.check(lib.amdrec_ranker_project_ads(_lib.C.byref(params), _lib.ptr(tail), n_new - n_old, _lib.ptr(out),
+                                                     proj.stride(0), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+            if hid is not None:
+                out = hid[n_old:]
+                _lib.check(lib.amdrec_ranker_project_ads_hidden(
+                    _lib.C.byref(params), _lib.ptr(tail), n_new - n_old, _lib.ptr(out), hid.stride(0), _lib.ptr(ws),
+                    ws.numel(), _lib.stream_ptr(dev)))
+        self._ad_cache = (c[0], new_table.data_ptr(), tuple(new_table.shape), new_table._version, proj, hid)
+
     def _hidden_cache_for(self, table):
         """The first-FFN hidden cache that goes with ``_cache_for(table)`` (None: not built)."""
         return self._ad_cache[5] if self._cache_for(table) is not None else None
