@@ -114,6 +114,13 @@ struct PerDeviceOnce {
         int d = 0;
         if (hipGetDevice(&d) == hipSuccess && d >= 0 && d < 64) done[d] = true;
     }
+    // the dynamic-LDS ceiling of one kernel (`this` is that kernel's static record), set on the first launch per device
+    hipError_t set_dynamic_lds(const void* kern, size_t bytes) {
+        if (!pending()) return hipSuccess;
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e == hipSuccess) mark();
+        return e;
+    }
 };
 
 // ---- optional per-launch timing (amdrec_profile_*): HIP events recorded on the launch stream

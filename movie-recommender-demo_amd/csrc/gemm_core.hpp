@@ -21,6 +21,7 @@
 //    order differs from a sequential loop.
 #pragma once
 #include "common.hpp"
+#include "../../include/amdrec.h"
 
 namespace amdrec {
 
@@ -111,6 +112,38 @@ struct EmbConcatRows {
         if (j + 2 < n_num) z[2] = p[j + 2];
         if (j + 3 < n_num) z[3] = p[j + 3];
         return z;
+    }
+
+    // ---- the row sources of the two models (host).  emb_dim is a power of two (tower_check / ranker_check) ----
+    static int eshift_of(int E) { return 31 - __builtin_clz((unsigned)E); }
+    // One categorical source plus the numerical tail: rows row_base .. row_base + rows of a tower's input.  F0 == F, so cat1
+    // is never read; rows1 = 1 keeps the row state's unused second index at 0.
+    static EmbConcatRows tower_rows(const amdrec_tower_params* p, const long long* cat, const float* num, long long row_base,
+                                    long long rows) {
+        return EmbConcatRows{p->tables, p->table_off, p->cards, cat, nullptr, nullptr, num, row_base, rows, 1, p->n_feat,
+                             p->n_feat, p->emb_dim, eshift_of(p->emb_dim), p->n_num, 1};
+    }
+    // U's rows (hoisted projection): [user emb | numerical], one row per user; one source as for a tower
+    static EmbConcatRows ranker_user_rows(const amdrec_ranker_params* p, const long long* user_cat, const float* numerical,
+                                          long long n_users) {
+        return EmbConcatRows{p->tables, p->table_off, p->cards, user_cat, nullptr, nullptr, numerical, 0, n_users, 1,
+                             p->n_user_feat, p->n_user_feat, p->emb_dim, eshift_of(p->emb_dim), p->n_num, 1};
+    }
+    // full rows [user emb | ad emb | numerical]: the user row is shared by user_rowdiv candidates, the ad row comes through
+    // the optional row map
+    static EmbConcatRows ranker_rows(const amdrec_ranker_params* p, const long long* user_cat, const float* numerical,
+                                     long long user_rowdiv, const long long* ad_cat, const long long* ad_rowmap,
+                                     long long n_ad_rows, long long row_base, long long rows) {
+        return EmbConcatRows{p->tables, p->table_off, p->cards, user_cat, ad_cat, ad_rowmap, numerical, row_base, rows,
+                             n_ad_rows > 0 ? n_ad_rows : 1, p->n_user_feat + p->n_ad_feat, p->n_user_feat, p->emb_dim,
+                             eshift_of(p->emb_dim), p->n_num, (int)user_rowdiv};
+    }
+    // the ad embeddings alone (the candidate half of the split projection; the per-ad caches with row_base 0, no row map)
+    static EmbConcatRows ranker_ad_rows(const amdrec_ranker_params* p, const long long* ad_cat, const long long* ad_rowmap,
+                                        long long n_ad_rows, long long row_base, long long rows) {
+        return EmbConcatRows{p->tables, p->table_off + p->n_user_feat, p->cards + p->n_user_feat, nullptr, ad_cat, ad_rowmap,
+                             nullptr, row_base, rows, n_ad_rows > 0 ? n_ad_rows : 1, p->n_ad_feat, 0, p->emb_dim,
+                             eshift_of(p->emb_dim), 0, 1};
     }
 };
 
@@ -287,37 +320,38 @@ __global__ __launch_bounds__(S::NT, 2) void gemm_nt_kernel(LoadP lp, LoadQ lq, E
     gemm_block<S>(lp, lq, epi, ksteps, (long long)tile_p * S::BP, (long long)tile_q * S::BQ, smem);
 }
 
-// k_alg: the un-padded K (for the algorithmic FLOP/byte count of the profiling hook only)
-template <class S, bool P_IS_SMALL, class LoadP, class LoadQ, class Epi>
-inline hipError_t launch_gemm(const LoadP& lp, const LoadQ& lq, const Epi& epi, int K, long long p_rows,
-                              long long q_rows, hipStream_t stream, int k_alg = 0) {
-    auto kern = gemm_nt_kernel<S, P_IS_SMALL, LoadP, LoadQ, Epi>;
-    // dynamic LDS = the larger of the staging tiles and what the epilogue carves out of the same array
+// The tail of both launchers: the kernel's dynamic-LDS ceiling (the larger of the staging tiles and what the epilogue carves
+// out of the same array; `attr_done` is the calling instantiation's static), the profile scope and the launch.  S gives the
+// geometry; `suffix` marks the engine in the profile tag; ka = the algorithmic K, elem_bytes = bytes per operand element.
+template <class S, class Kern, class LoadP, class LoadQ, class Epi>
+inline hipError_t launch_tiles(Kern kern, PerDeviceOnce& attr_done, const LoadP& lp, const LoadQ& lq, const Epi& epi, int ksteps,
+                               TileMap tm, const char* suffix, double ka, double elem_bytes, long long p_rows,
+                               long long q_rows, hipStream_t stream) {
     constexpr size_t lds_bytes = S::LDS_BYTES > Epi::lds_bytes(S::NT / 64) ? S::LDS_BYTES : Epi::lds_bytes(S::NT / 64);
     static_assert(lds_bytes <= 160 * 1024, "LDS budget");
-    static PerDeviceOnce attr_done;   // per instantiation
-    if (attr_done.pending()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        attr_done.mark();
-    }
-    TileMap tm;
-    int tiles_p = (int)((p_rows + S::BP - 1) / S::BP), tiles_q = (int)((q_rows + S::BQ - 1) / S::BQ);
-    tm.tiles_small = P_IS_SMALL ? tiles_p : tiles_q;
-    tm.tiles_big = P_IS_SMALL ? tiles_q : tiles_p;
+    hipError_t e = attr_done.set_dynamic_lds(reinterpret_cast<const void*>(kern), lds_bytes);
+    if (e != hipSuccess) return e;
     if (tm.tiles_small <= 0 || tm.tiles_big <= 0) return hipSuccess;
-    int ksteps = (K + BK - 1) / BK;
     char tag[64];
-    if (g_prof_on) snprintf(tag, sizeof(tag), "%s_%dx%d%s", Epi::name, S::BP, S::BQ, S::BF16 ? "_bf16" : "");
-    const double ka = k_alg > 0 ? k_alg : (S::BF16 ? 2.0 * K : (double)K);    // elements, not staged floats
-    const double eb = S::BF16 ? 2.0 : 4.0;
+    if (g_prof_on) snprintf(tag, sizeof(tag), "%s_%dx%d%s", Epi::name, S::BP, S::BQ, suffix);
     ProfScope prof(tag, 2.0 * (double)p_rows * (double)q_rows * ka,
-                   eb * ((double)p_rows * ka + (double)q_rows * ka) +
+                   elem_bytes * ((double)p_rows * ka + (double)q_rows * ka) +
                        4.0 * Epi::out_bytes_per_elem * (double)p_rows * (double)q_rows,
                    stream);
     hipLaunchKernelGGL(kern, dim3(tm.grid()), dim3(S::NT), lds_bytes, stream, lp, lq, epi, ksteps, tm);
     return hipGetLastError();
+}
+
+// k_alg: the un-padded K (for the algorithmic FLOP/byte count of the profiling hook only)
+template <class S, bool P_IS_SMALL, class LoadP, class LoadQ, class Epi>
+inline hipError_t launch_gemm(const LoadP& lp, const LoadQ& lq, const Epi& epi, int K, long long p_rows,
+                              long long q_rows, hipStream_t stream, int k_alg = 0) {
+    static PerDeviceOnce attr_done;   // per instantiation
+    const int tiles_p = (int)((p_rows + S::BP - 1) / S::BP), tiles_q = (int)((q_rows + S::BQ - 1) / S::BQ);
+    const TileMap tm{P_IS_SMALL ? tiles_p : tiles_q, P_IS_SMALL ? tiles_q : tiles_p};
+    const double ka = k_alg > 0 ? k_alg : (S::BF16 ? 2.0 * K : (double)K);    // elements, not staged floats
+    return launch_tiles<S>(gemm_nt_kernel<S, P_IS_SMALL, LoadP, LoadQ, Epi>, attr_done, lp, lq, epi, (K + BK - 1) / BK, tm,
+                           S::BF16 ? "_bf16" : "", ka, S::BF16 ? 2.0 : 4.0, p_rows, q_rows, stream);
 }
 
 // ======================================================================================================
@@ -491,31 +525,11 @@ template <class LoadQ, class Epi>
 inline hipError_t launch_gemm_x6(const uint16_t* planes, int p_rows, const LoadQ& lq, const Epi& epi, int K,
                                  long long q_rows, hipStream_t stream, int k_alg = 0) {
     using S = ShapeX6;
-    auto kern = gemm_x6_kernel<LoadQ, Epi>;
-    constexpr size_t lds_bytes = S::LDS_BYTES > Epi::lds_bytes(S::NT / 64) ? S::LDS_BYTES : Epi::lds_bytes(S::NT / 64);
-    static_assert(lds_bytes <= 160 * 1024, "LDS budget");
     static PerDeviceOnce attr_done;   // per instantiation
-    if (attr_done.pending()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        attr_done.mark();
-    }
-    TileMap tm;
-    tm.tiles_small = (p_rows + S::BP - 1) / S::BP;
-    tm.tiles_big = (int)((q_rows + S::BQ - 1) / S::BQ);
-    if (tm.tiles_small <= 0 || tm.tiles_big <= 0) return hipSuccess;
+    const TileMap tm{(p_rows + S::BP - 1) / S::BP, (int)((q_rows + S::BQ - 1) / S::BQ)};
     const int ksteps = K / S::BK16;
-    PlaneRows lp{planes, p_rows, ksteps};
-    char tag[64];
-    if (g_prof_on) snprintf(tag, sizeof(tag), "%s_%dx%d_x6", Epi::name, S::BP, S::BQ);
-    const double ka = k_alg > 0 ? k_alg : K;
-    ProfScope prof(tag, 2.0 * (double)p_rows * (double)q_rows * ka,
-                   4.0 * ((double)p_rows * ka + (double)q_rows * ka) +
-                       4.0 * Epi::out_bytes_per_elem * (double)p_rows * (double)q_rows,
-                   stream);
-    hipLaunchKernelGGL(kern, dim3(tm.grid()), dim3(S::NT), lds_bytes, stream, lp, lq, epi, ksteps, tm);
-    return hipGetLastError();
+    return launch_tiles<S>(gemm_x6_kernel<LoadQ, Epi>, attr_done, PlaneRows{planes, p_rows, ksteps}, lq, epi, ksteps, tm, "_x6",
+                           k_alg > 0 ? k_alg : K, 4.0, p_rows, q_rows, stream);
 }
 
 }  // namespace amdrec

@@ -90,18 +90,29 @@ __device__ __forceinline__ void tile_load(WaveTile& wt, f32x4 (&v)[4], const flo
     wt.get_acc(v);
 }
 
-// out[row][f] = act(acc + bias[f])
-template <bool FULL>
-struct EpiLinearT {
-    static constexpr const char* name = "linear";
+// what launch_gemm asks of these epilogues: each writes one fp32 per output element through the wave tiles above
+struct EpiTiled {
     static constexpr double out_bytes_per_elem = 1.0;
     static constexpr size_t lds_bytes(int nwaves) { return epi_lds_bytes(nwaves); }
+};
+// Every epilogue EpiXT<FULL> derives from a plain struct XArgs: the kernel arguments, which a call site of linear() names
+// field by field (rows and nout apart: the dispatcher fills those in), and the epilogue template the dispatcher instantiates.
+template <bool> struct EpiLinearT;   template <bool> struct EpiRowBiasT;   template <bool> struct EpiCrossT;
+template <bool> struct EpiResidualLNT;   template <bool> struct EpiL2NormT;
+
+struct LinearArgs {
+    template <bool FULL> using Epi = EpiLinearT<FULL>;
     const float* bias;
     float* out;
     long long ldo;
     long long rows;
     int nout;
     int relu;
+};
+// out[row][f] = act(acc + bias[f])
+template <bool FULL>
+struct EpiLinearT : LinearArgs, EpiTiled {
+    static constexpr const char* name = "linear";
     template <class A>
     __device__ void operator()(A& acc, float* smem) const {
         constexpr int TP = A::TP, TQ = A::TQ;
@@ -134,11 +145,8 @@ struct EpiLinearT {
 
 // out[row][f] = acc + ubias[row / rowdiv][f]: the candidate (ad) half of the feature projection plus its
 // user's precomputed half (which already carries the bias and positional row)
-template <bool FULL>
-struct EpiRowBiasT {
-    static constexpr const char* name = "linear";
-    static constexpr double out_bytes_per_elem = 1.0;
-    static constexpr size_t lds_bytes(int nwaves) { return epi_lds_bytes(nwaves); }
+struct RowBiasArgs {
+    template <bool FULL> using Epi = EpiRowBiasT<FULL>;
     const float* ubias;     // [n_users][ld]
     float* out;
     long long ld;
@@ -146,6 +154,10 @@ struct EpiRowBiasT {
     long long row_base;     // global index of the chunk's first row
     int rowdiv;
     int nout;
+};
+template <bool FULL>
+struct EpiRowBiasT : RowBiasArgs, EpiTiled {
+    static constexpr const char* name = "linear";
     template <class A>
     __device__ void operator()(A& acc, float* smem) const {
         constexpr int TP = A::TP, TQ = A::TQ;
@@ -174,11 +186,8 @@ struct EpiRowBiasT {
 };
 
 // out[row][f] = x0[row][f] * (acc + bias[f]) + xl[row][f]     (FeatureInteractionLayer :201)
-template <bool FULL>
-struct EpiCrossT {
-    static constexpr const char* name = "cross";
-    static constexpr double out_bytes_per_elem = 1.0;
-    static constexpr size_t lds_bytes(int nwaves) { return epi_lds_bytes(nwaves); }
+struct CrossArgs {
+    template <bool FULL> using Epi = EpiCrossT<FULL>;
     const float* bias;
     const float* x0;
     const float* xl;
@@ -186,6 +195,10 @@ struct EpiCrossT {
     long long ld;
     long long rows;
     int nout;
+};
+template <bool FULL>
+struct EpiCrossT : CrossArgs, EpiTiled {
+    static constexpr const char* name = "cross";
     template <class A>
     __device__ void operator()(A& acc, float* smem) const {
         constexpr int TP = A::TP, TQ = A::TQ;
@@ -243,11 +256,8 @@ __device__ __forceinline__ void row_allreduce(float (&part)[TQ], float* red, int
 }
 
 // out = LayerNorm(resid + acc + bias) * gamma + beta   (transformer_ranker.py:149, :153; eps 1e-5)
-template <bool FULL>
-struct EpiResidualLNT {
-    static constexpr const char* name = "residual_ln";
-    static constexpr double out_bytes_per_elem = 1.0;
-    static constexpr size_t lds_bytes(int nwaves) { return epi_lds_bytes(nwaves); }
+struct ResidualLNArgs {
+    template <bool FULL> using Epi = EpiResidualLNT<FULL>;
     const float* bias;
     const float* resid;
     const float* gamma;
@@ -257,6 +267,10 @@ struct EpiResidualLNT {
     long long rows;
     int nout;
     float eps;
+};
+template <bool FULL>
+struct EpiResidualLNT : ResidualLNArgs, EpiTiled {
+    static constexpr const char* name = "residual_ln";
     template <class A>
     __device__ void operator()(A& acc, float* smem) const {
         constexpr int TP = A::TP, TQ = A::TQ;
@@ -344,17 +358,18 @@ struct EpiResidualLNT {
 };
 
 // out = (acc + bias) / max(||acc + bias||_2, eps)      (F.normalize, two_tower_model.py:119)
-template <bool FULL>
-struct EpiL2NormT {
-    static constexpr const char* name = "l2norm";
-    static constexpr double out_bytes_per_elem = 1.0;
-    static constexpr size_t lds_bytes(int nwaves) { return epi_lds_bytes(nwaves); }
+struct L2NormArgs {
+    template <bool FULL> using Epi = EpiL2NormT<FULL>;
     const float* bias;
     float* out;
     long long ldo;
     long long rows;
     int nout;
     float eps;
+};
+template <bool FULL>
+struct EpiL2NormT : L2NormArgs, EpiTiled {
+    static constexpr const char* name = "l2norm";
     template <class A>
     __device__ void operator()(A& acc, float* smem) const {
         constexpr int TP = A::TP, TQ = A::TQ;
@@ -433,63 +448,58 @@ __global__ void check_index_kernel(const long long* cat, long long rows, int F, 
     if (v < 0 || v >= card[i % F]) *flag = 1;
 }
 
+static void launch_check_index(const int64_t* cat, long long rows, int F, const int* card, int* flag, hipStream_t st) {
+    hipLaunchKernelGGL(check_index_kernel, dim3((unsigned)((rows * F + 255) / 256)), dim3(256), 0, st, (const long long*)cat,
+                       rows, F, card, flag);
+}
+
 static inline DenseRows dense(const float* p, long long rows, long long ld, int K) {
     return DenseRows{p, rows, (int)ld, K, 30, 1ll << 30};
 }
+// the un-padded K of a row source (the profile hook's FLOP count)
+static inline int k_of(const DenseRows& r) { return r.K; }
+static inline int k_of(const EmbConcatRows& g) { return g.F * g.E + g.n_num; }
 
-// y = epilogue(x W^T): dispatch on the output width; FULL = the width fills whole P tiles, so the
-// epilogue needs no feature-bound checks (true for every layer of the default architecture).
-template <class SW, class SN, bool ALLOW_NARROW, template <bool> class EpiT, class LoadQ, class... EpiArgs>
-static hipError_t linear_shapes(const float* W, int ldw, int nout, const LoadQ& lq, long long rows, hipStream_t st,
-                                int k_alg, EpiArgs... ea) {
-    DenseRows lp = dense(W, nout, ldw, ldw);
-    if constexpr (ALLOW_NARROW) {
-        if (nout <= 64) {
-            if (nout == SN::BP) return launch_gemm<SN, true>(lp, lq, EpiT<true>{ea...}, ldw, nout, rows, st, k_alg);
-            return launch_gemm<SN, true>(lp, lq, EpiT<false>{ea...}, ldw, nout, rows, st, k_alg);
-        }
-    }
-    if (nout % SW::BP == 0) return launch_gemm<SW, true>(lp, lq, EpiT<true>{ea...}, ldw, nout, rows, st, k_alg);
-    return launch_gemm<SW, true>(lp, lq, EpiT<false>{ea...}, ldw, nout, rows, st, k_alg);
-}
-// The error-compensated bf16 path (gemm_core.hpp "x6") for the big passes: needs the host-split weight planes, a dense
-// fp32 row operand and at least one full 256-feature tile.
-template <template <bool> class EpiT, class LoadQ, class... EpiArgs>
-static bool try_x6(hipError_t& e, const uint16_t* Wx6, int ldw, int nout, const LoadQ& lq, long long rows, hipStream_t st,
-                   int k_alg, EpiArgs... ea) {
-    if constexpr (std::is_same<LoadQ, DenseRows>::value) {
-        if (Wx6 == nullptr || rows <= SMALL_ROWS || nout < 256) return false;
-        if (nout % 256 == 0) e = launch_gemm_x6(Wx6, nout, lq, EpiT<true>{ea...}, ldw, rows, st, k_alg);
-        else e = launch_gemm_x6(Wx6, nout, lq, EpiT<false>{ea...}, ldw, rows, st, k_alg);
-        return true;
-    }
-    return false;
-}
-// narrow outputs (<= 64 features) may use the 64-feature shapes
-template <template <bool> class EpiT, class LoadQ, class... EpiArgs>
-static hipError_t linear(const float* W, const uint16_t* Wx6, int ldw, int nout, const LoadQ& lq, long long rows,
-                         hipStream_t st, int k_alg, EpiArgs... ea) {
-    hipError_t e;
-    if (try_x6<EpiT>(e, Wx6, ldw, nout, lq, rows, st, k_alg, ea...)) return e;
-    if (rows <= SMALL_ROWS)
-        return linear_shapes<ShapeSmall, ShapeSmallNarrow, true, EpiT>(W, ldw, nout, lq, rows, st, k_alg, ea...);
-    return linear_shapes<ShapeWide, ShapeNarrow, true, EpiT>(W, ldw, nout, lq, rows, st, k_alg, ea...);
-}
-// epilogues that need a whole 256-feature row in one workgroup (LayerNorm, L2 norm)
-template <template <bool> class EpiT, class LoadQ, class... EpiArgs>
-static hipError_t linear_wide(const float* W, const uint16_t* Wx6, int ldw, int nout, const LoadQ& lq, long long rows,
-                              hipStream_t st, int k_alg, EpiArgs... ea) {
-    hipError_t e;
-    if (try_x6<EpiT>(e, Wx6, ldw, nout, lq, rows, st, k_alg, ea...)) return e;
-    if (rows <= SMALL_ROWS)
-        return linear_shapes<ShapeSmall, ShapeSmallNarrow, false, EpiT>(W, ldw, nout, lq, rows, st, k_alg, ea...);
-    return linear_shapes<ShapeWide, ShapeNarrow, false, EpiT>(W, ldw, nout, lq, rows, st, k_alg, ea...);
-}
+// The weights of one layer, [nout][ld] fp32.  WeightsX6 adds the host-split bf16 planes of the error-compensated path
+// (gemm_core.hpp "x6"; null when the engine is fp32): only a call that passes this type has x6 kernels at all.
+struct Weights { const float* w; int ld; };
+struct WeightsX6 { const float* w; const uint16_t* x6; int ld; };
+// narrow outputs (<= 64 features) may use the 64-feature shapes, unless the call wants a whole 256-feature row in one
+// workgroup whatever nout is (the projections; the LayerNorm and L2-norm epilogues, which need it)
+enum Tiles { ANY_WIDTH, WIDE_ONLY };
 
-static inline int ilog2(int v) {
-    int s = 0;
-    while ((1 << s) < v) ++s;
-    return s;
+// FULL = the width fills whole P tiles, so the epilogue needs no feature-bound checks (true for every layer of the default
+// architecture): launch(EpiXT<full>{a})
+template <class Args, class Launch>
+static hipError_t with_epilogue(bool full, const Args& a, Launch launch) {
+    return full ? launch(typename Args::template Epi<true>{a}) : launch(typename Args::template Epi<false>{a});
+}
+template <class S, class LoadQ, class Args>
+static hipError_t linear_tiles(const float* W, int ldw, const LoadQ& lq, const Args& a, hipStream_t st) {
+    return with_epilogue(a.nout % S::BP == 0, a, [&](const auto& epi) {
+        return launch_gemm<S, true>(dense(W, a.nout, ldw, ldw), lq, epi, ldw, a.nout, a.rows, st, k_of(lq));
+    });
+}
+// y = epilogue(x W^T) for the rows of `lq`: the epilogue's arguments by name, rows and nout filled in here.  Dispatch on the
+// row count (small shapes up to SMALL_ROWS), the output width and - with planes, a dense fp32 row operand and at least one
+// full 256-feature tile - the x6 path for the big passes.
+template <Tiles TILES, class W, class LoadQ, class Args>
+static hipError_t linear(const W& w, int nout, const LoadQ& lq, hipStream_t st, Args a) {
+    a.rows = lq.rows;
+    a.nout = nout;
+    if constexpr (std::is_same<W, WeightsX6>::value) {
+        static_assert(std::is_same<LoadQ, DenseRows>::value, "the x6 kernels stage dense fp32 rows");
+        if (w.x6 != nullptr && a.rows > SMALL_ROWS && nout >= 256)
+            return with_epilogue(nout % 256 == 0, a, [&](const auto& epi) {
+                return launch_gemm_x6(w.x6, nout, lq, epi, w.ld, a.rows, st, k_of(lq));
+            });
+    }
+    if constexpr (TILES == ANY_WIDTH) {
+        if (nout <= 64)
+            return a.rows <= SMALL_ROWS ? linear_tiles<ShapeSmallNarrow>(w.w, w.ld, lq, a, st)
+                                        : linear_tiles<ShapeNarrow>(w.w, w.ld, lq, a, st);
+    }
+    return a.rows <= SMALL_ROWS ? linear_tiles<ShapeSmall>(w.w, w.ld, lq, a, st) : linear_tiles<ShapeWide>(w.w, w.ld, lq, a, st);
 }
 
 // Rows per pass.  A 256-feature layer launches rows/256 workgroups, so a pass must be >= 65536 rows to
@@ -556,46 +566,27 @@ extern "C" int amdrec_tower_forward(const amdrec_tower_params* p, const int64_t*
     REQUIRE(ld_out % 4 == 0 && ld_out >= p->dims[p->n_layers], "bad ld_out");
     const TowerWs w(p, rows, workspace);
     if ((rc = require_workspace(workspace, workspace_bytes, w.bytes()))) return rc;
-    if (bad_index_flag) {
-        long long n = rows * p->n_feat;
-        hipLaunchKernelGGL(check_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                           (const long long*)cat, (long long)rows, p->n_feat, p->cards, bad_index_flag);
-    }
+    if (bad_index_flag) launch_check_index(cat, rows, p->n_feat, p->cards, bad_index_flag, st);
     if (tower_small_ok(p, rows)) {                      // serving batches: one launch for the whole tower
         HIP_TRY(tower_small_run(p, (const long long*)cat, num, rows, out, (long long)ld_out, st));
         return AMDREC_OK;
     }
     for (long long r0 = 0; r0 < rows; r0 += w.chunk) {
         const long long m = rows - r0 < w.chunk ? rows - r0 : w.chunk;
-        EmbConcatRows g{};
-        g.tables = p->tables; g.off = p->table_off; g.card = p->cards;
-        g.cat0 = (const long long*)cat; g.cat1 = nullptr; g.rowmap1 = nullptr;
-        g.num = num;
-        g.row_base = r0;
-        g.rows = m; g.F = p->n_feat; g.F0 = p->n_feat; g.E = p->emb_dim; g.eshift = ilog2(p->emb_dim);
-        g.n_num = p->n_num; g.cat0_rowdiv = 1;
-        const float* cur = nullptr;
-        int curw = 0;
         for (int l = 0; l < p->n_layers; ++l) {
-            const bool last = l == p->n_layers - 1;
             const int nout = p->dims[l + 1];
-            hipError_t e;
-            if (last) {
-                float* dst = out + r0 * ld_out;
-                e = (l == 0) ? linear_wide<EpiL2NormT>(p->w[l], nullptr, p->ldw[l], nout, g, m, st, p->dims[l], p->b[l], dst,
-                                                       (long long)ld_out, m, nout, 1e-12f)
-                             : linear_wide<EpiL2NormT>(p->w[l], nullptr, p->ldw[l], nout, dense(cur, m, curw, curw), m, st,
-                                                       p->dims[l], p->b[l], dst, (long long)ld_out, m, nout, 1e-12f);
-            } else {
-                float* dst = w.bufs[l & 1];
-                e = (l == 0) ? linear<EpiLinearT>(p->w[l], nullptr, p->ldw[l], nout, g, m, st, p->dims[l], p->b[l], dst,
-                                                  (long long)nout, m, nout, 1)
-                             : linear<EpiLinearT>(p->w[l], nullptr, p->ldw[l], nout, dense(cur, m, curw, curw), m, st,
-                                                  p->dims[l], p->b[l], dst, (long long)nout, m, nout, 1);
-                cur = dst;
-                curw = nout;
-            }
-            HIP_TRY(e);
+            const Weights W{p->w[l], p->ldw[l]};
+            // a hidden layer writes relu(.) to its ping-pong buffer, the last layer the normalised rows to `out`
+            auto layer = [&](const auto& in) {
+                if (l == p->n_layers - 1)
+                    return linear<WIDE_ONLY>(W, nout, in, st,
+                                             L2NormArgs{.bias = p->b[l], .out = out + r0 * ld_out, .ldo = ld_out, .eps = 1e-12f});
+                return linear<ANY_WIDTH>(W, nout, in, st,
+                                         LinearArgs{.bias = p->b[l], .out = w.bufs[l & 1], .ldo = nout, .relu = 1});
+            };
+            // layer 0 gathers its rows from the tables, every other layer reads the previous one's buffer
+            if (l == 0) HIP_TRY(layer(EmbConcatRows::tower_rows(p, (const long long*)cat, num, r0, m)));
+            else HIP_TRY(layer(dense(w.bufs[(l - 1) & 1], m, p->dims[l], p->dims[l])));
         }
     }
     if (p->renormalize)                                   // the general path: a second launch (amdrec_l2_normalize in place)
@@ -680,7 +671,7 @@ static int project_ads(const amdrec_ranker_params* p, const float* W, int nout, 
     if (rc) return rc;
     if (n_ads <= 0) return AMDREC_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int dm = nout, F0 = p->n_user_feat, F = p->n_user_feat + p->n_ad_feat;
+    const int dm = nout;
     REQUIRE(W && p->n_ad_feat > 0, "params carry no split projection (w_proj_ad / x3.w_hidden_ad)");
     REQUIRE(ad_cat && out, "null pointer");
     REQUIRE(ld_out >= dm && ld_out % 4 == 0 && ((uintptr_t)out % 16) == 0, "bad output layout");
@@ -688,14 +679,10 @@ static int project_ads(const amdrec_ranker_params* p, const float* W, int nout, 
     if ((rc = require_workspace(workspace, workspace_bytes, align_up((size_t)dm * 4, 256)))) return rc;
     float* zero = static_cast<float*>(workspace);
     HIP_TRY(hipMemsetAsync(zero, 0, (size_t)dm * 4, st));
-    EmbConcatRows ga{};
-    ga.tables = p->tables; ga.off = p->table_off + F0; ga.card = p->cards + F0;
-    ga.cat0 = nullptr; ga.cat1 = (const long long*)ad_cat; ga.rowmap1 = nullptr; ga.num = nullptr;
-    ga.row_base = 0; ga.rows = n_ads; ga.rows1 = n_ads; ga.F = F - F0; ga.F0 = 0; ga.E = p->emb_dim;
-    ga.eshift = ilog2(p->emb_dim); ga.n_num = 0; ga.cat0_rowdiv = 1;
     // the same GEMM (shape, K order) as the uncached candidate half, with an all-zero "user row"
-    HIP_TRY(linear_wide<EpiRowBiasT>(W, nullptr, p->ldw_proj_ad, dm, ga, n_ads, st, (F - F0) * p->emb_dim,
-                                     (const float*)zero, out, (long long)ld_out, n_ads, 0ll, 0x7fffffff, dm));
+    const EmbConcatRows ga = EmbConcatRows::ranker_ad_rows(p, (const long long*)ad_cat, nullptr, n_ads, 0, n_ads);
+    HIP_TRY(linear<WIDE_ONLY>(Weights{W, p->ldw_proj_ad}, dm, ga, st,
+                              RowBiasArgs{.ubias = zero, .out = out, .ld = ld_out, .row_base = 0, .rowdiv = 0x7fffffff}));
     return AMDREC_OK;
 }
 
@@ -752,6 +739,109 @@ __global__ __launch_bounds__(256) void user_proj_small_kernel(EmbConcatRows g, c
     if (j == 0 && n < dm) U[u * dm + n] = a + bias[n];
 }
 
+// What the parts of amdrec_ranker_forward share
+struct RankerCtx {
+    const amdrec_ranker_params* p;
+    hipStream_t st;
+    float *X, *T, *X0, *H, *U;     // RankerWs
+    int dm;
+    bool hoist;                    // split projection: the user half once per user row (U), the ad half per candidate
+    int du;                        // width and leading dimension of U's rows
+};
+
+// U[u] = W_user [user emb(u) | numerical(u)] + b_proj (+ pos[0]): once per user row; rows [U | Q] when du == dm + d_ff
+static int ranker_user_projection(const RankerCtx& c, const int64_t* user_cat, const float* numerical, long long n_users) {
+    const amdrec_ranker_params* p = c.p;
+    const bool with_q = c.du != c.dm;
+    const float* w_user = with_q ? p->x3.w_user_uq : p->w_proj_user;
+    const float* b_user = with_q ? p->x3.b_user_uq : p->b_proj;
+    const EmbConcatRows gu = EmbConcatRows::ranker_user_rows(p, (const long long*)user_cat, numerical, n_users);
+    const int Ku = k_of(gu), K4 = (Ku + 3) / 4 * 4;
+    if (n_users <= USER_PROJ_SMALL_MAX && K4 <= USER_PROJ_SMALL_K && p->ldw_proj_user >= K4) {
+        ProfScope prof("user_proj_small", 2.0 * n_users * c.du * Ku, (double)c.du * Ku * 4, c.st);
+        hipLaunchKernelGGL(user_proj_small_kernel, dim3((unsigned)n_users, (unsigned)((c.du + 31) / 32)), dim3(256), 0, c.st, gu,
+                           w_user, (int)p->ldw_proj_user, Ku, b_user, c.U, c.du);
+        HIP_TRY(hipGetLastError());
+        return AMDREC_OK;
+    }
+    HIP_TRY(linear<WIDE_ONLY>(Weights{w_user, p->ldw_proj_user}, c.du, gu, c.st,
+                              LinearArgs{.bias = b_user, .out = c.U, .ldo = c.du, .relu = 0}));
+    return AMDREC_OK;
+}
+
+// X = the feature projection (+ pos[0], folded into b_proj on the host) of one pass's rows `g`
+static int ranker_project_rows(const RankerCtx& c, const EmbConcatRows& g) {
+    const amdrec_ranker_params* p = c.p;
+    if (c.hoist && p->ad_proj_cache) {
+        hipLaunchKernelGGL(proj_gather_kernel, dim3((unsigned)((g.rows + 3) / 4)), dim3(256), 0, c.st, p->ad_proj_cache,
+                           (long long)p->ld_ad_proj_cache, g.rows1, g.rowmap1, g.row_base, (const float*)c.U, c.dm,
+                           g.cat0_rowdiv, c.X, g.rows);
+    } else if (c.hoist) {
+        // candidate half: ad embeddings only (K = n_ad_feat * emb_dim), plus the user's row of U
+        HIP_TRY(linear<WIDE_ONLY>(Weights{p->w_proj_ad, p->ldw_proj_ad}, c.dm,
+                                  EmbConcatRows::ranker_ad_rows(p, g.cat1, g.rowmap1, g.rows1, g.row_base, g.rows), c.st,
+                                  RowBiasArgs{.ubias = c.U, .out = c.X, .ld = c.dm, .row_base = g.row_base,
+                                              .rowdiv = g.cat0_rowdiv}));
+    } else {
+        HIP_TRY(linear<WIDE_ONLY>(Weights{p->w_proj, p->ldw_proj}, c.dm, g, c.st,
+                                  LinearArgs{.bias = p->b_proj, .out = c.X, .ldo = c.dm, .relu = 0}));
+    }
+    return AMDREC_OK;
+}
+
+// The layer-by-layer engine on the m projected rows in X: encoder layers, cross layers, heads -> logits[t * ld_logits + row]
+static int ranker_layer_chain(const RankerCtx& c, long long m, float* logits, long long ld_logits) {
+    const amdrec_ranker_params* p = c.p;
+    const hipStream_t st = c.st;
+    const int dm = c.dm, dff = p->d_ff;
+    float *X = c.X, *T = c.T;
+    for (int l = 0; l < p->n_layers; ++l) {
+        const amdrec_encoder_layer& L = p->layers[l];
+        const WeightsX6 w_o{L.w_o, L.w_o_x6, L.ldw_dm};
+        ResidualLNArgs ln1{.bias = L.b_o, .resid = X, .gamma = L.ln1_g, .beta = L.ln1_b, .out = X, .ld = dm, .eps = p->ln_eps};
+        if (L.w_v != nullptr) {
+            // T = W_v x + b_v ; X = LN1(X + W_o T + b_o)
+            HIP_TRY(linear<WIDE_ONLY>(Weights{L.w_v, L.ldw_dm}, dm, dense(X, m, dm, dm), st,
+                                      LinearArgs{.bias = L.b_v, .out = T, .ldo = dm, .relu = 0}));
+            HIP_TRY(linear<WIDE_ONLY>(w_o, dm, dense(T, m, dm, dm), st, ln1));
+        } else {
+            // host pre-multiplied W_ov = W_o W_v: LN1(X + W_ov X + b_ov), written to the spare buffer
+            ln1.out = T;
+            HIP_TRY(linear<WIDE_ONLY>(w_o, dm, dense(X, m, dm, dm), st, ln1));
+            float* tmp = X; X = T; T = tmp;
+        }
+        // H = relu(W_1 X + b_1)
+        HIP_TRY(linear<ANY_WIDTH>(WeightsX6{L.w_1, L.w_1_x6, L.ldw_dm}, dff, dense(X, m, dm, dm), st,
+                                  LinearArgs{.bias = L.b_1, .out = c.H, .ldo = dff, .relu = 1}));
+        // X = LN2(X + W_2 H + b_2)
+        HIP_TRY(linear<WIDE_ONLY>(WeightsX6{L.w_2, L.w_2_x6, L.ldw_ff}, dm, dense(c.H, m, dff, dff), st,
+                                  ResidualLNArgs{.bias = L.b_2, .resid = X, .gamma = L.ln2_g, .beta = L.ln2_b, .out = X, .ld = dm,
+                                                 .eps = p->ln_eps}));
+    }
+    // ---- cross layers: xl <- x0 * (xl W_i + b_i) + xl ; x0 = X ----
+    const float* xl = X;
+    for (int i = 0; i < p->n_cross; ++i) {
+        float* dst = (i & 1) ? c.X0 : T;
+        HIP_TRY(linear<WIDE_ONLY>(WeightsX6{p->cross_wt[i], p->cross_wt_x6[i], p->ldw_cross}, dm, dense(xl, m, dm, dm), st,
+                                  CrossArgs{.bias = p->cross_b[i], .x0 = X, .xl = xl, .out = dst, .ld = dm}));
+        xl = dst;
+    }
+    // ---- heads ----
+    const int h1 = p->head_h1, h2 = p->head_h2, nt = p->n_tasks;
+    float* H1 = c.H;                                 // [m][nt*h1]
+    float* H2 = c.H + (size_t)m * nt * h1;           // [m][nt*h2]
+    HIP_TRY(linear<ANY_WIDTH>(WeightsX6{p->head_w1, p->head_w1_x6, p->ldw_head1}, nt * h1, dense(xl, m, dm, dm), st,
+                              LinearArgs{.bias = p->head_b1, .out = H1, .ldo = nt * h1, .relu = 1}));
+    for (int t = 0; t < nt; ++t) {
+        HIP_TRY(linear<ANY_WIDTH>(Weights{p->head_w2[t], p->ldw_head2}, h2, dense(H1 + t * h1, m, (long long)nt * h1, h1), st,
+                                  LinearArgs{.bias = p->head_b2[t], .out = H2 + t * h2, .ldo = nt * h2, .relu = 1}));
+        hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)((m * 16 + 255) / 256)), dim3(256), 0, st, H2 + t * h2, (long long)nt * h2,
+                           h2, p->head_w3[t], p->head_b3[t], logits + (long long)t * ld_logits, m);
+    }
+    HIP_TRY(hipGetLastError());
+    return AMDREC_OK;
+}
+
 extern "C" int amdrec_ranker_forward(const amdrec_ranker_params* p, const int64_t* user_cat, const float* numerical,
                                      int64_t user_rowdiv, const int64_t* ad_cat, const int64_t* ad_rowmap,
                                      int64_t rows, float* out_logits, int64_t ld_logits, int* bad_index_flag,
@@ -773,59 +863,22 @@ extern "C" int amdrec_ranker_forward(const amdrec_ranker_params* p, const int64_
     const long long n_users = hoist ? (rows + user_rowdiv - 1) / user_rowdiv : 0;
     const RankerWs w(p, rows, workspace);
     if ((rc = require_workspace(workspace, workspace_bytes, w.bytes()))) return rc;
-    float *X = w.X, *T = w.T, *X0 = w.X0, *H = w.H, *U = w.U;
     const int dm = p->d_model, F0 = p->n_user_feat, F = p->n_user_feat + p->n_ad_feat;
 
     if (bad_index_flag) {
-        if (F0 && n_user_rows > 0) {
-            long long n = n_user_rows * F0;
-            hipLaunchKernelGGL(check_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                               (const long long*)user_cat, (long long)n_user_rows, F0, p->cards, bad_index_flag);
-        }
-        if (F - F0 && n_ad_rows > 0) {
-            long long n = n_ad_rows * (F - F0);
-            hipLaunchKernelGGL(check_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                               (const long long*)ad_cat, (long long)n_ad_rows, F - F0, p->cards + F0, bad_index_flag);
-        }
+        if (F0 && n_user_rows > 0) launch_check_index(user_cat, n_user_rows, F0, p->cards, bad_index_flag, st);
+        if (F - F0 && n_ad_rows > 0) launch_check_index(ad_cat, n_ad_rows, F - F0, p->cards + F0, bad_index_flag, st);
     }
 
     // First-FFN hidden cache (amdrec_x3_weights.stream_hc): when the largest pass of this call takes it, the user projection
     // also writes Q[u] = W_1c U[u] - rows [U | Q] of dm + d_ff floats from the stacked weights, in the same launch.  They
     // share U's workspace region (rows * dm floats), which holds them from five candidates per user on.
     const bool with_q = hoist && ranker_x3_hidden_cache(p, w.chunk) && n_users * (long long)(dm + p->d_ff) <= rows * (long long)dm;
-    const int du = with_q ? dm + p->d_ff : dm;                // width and leading dimension of the user rows
-    const float* w_user = with_q ? p->x3.w_user_uq : p->w_proj_user;
-    const float* b_user = with_q ? p->x3.b_user_uq : p->b_proj;
-    if (hoist) {
-        // U[u] = W_user [user emb(u) | numerical(u)] + b_proj (+ pos[0]): once per user row
-        EmbConcatRows gu{};
-        gu.tables = p->tables; gu.off = p->table_off; gu.card = p->cards;
-        gu.cat0 = (const long long*)user_cat; gu.cat1 = nullptr; gu.rowmap1 = nullptr; gu.num = numerical;
-        gu.row_base = 0; gu.rows1 = 1; gu.rows = n_users; gu.F = F0; gu.F0 = F0; gu.E = p->emb_dim;
-        gu.eshift = ilog2(p->emb_dim); gu.n_num = p->n_num; gu.cat0_rowdiv = 1;
-        const int Ku = F0 * p->emb_dim + p->n_num;
-        if (n_users <= USER_PROJ_SMALL_MAX && (Ku + 3) / 4 * 4 <= USER_PROJ_SMALL_K && p->ldw_proj_user >= (Ku + 3) / 4 * 4) {
-            ProfScope prof("user_proj_small", 2.0 * n_users * du * Ku, (double)du * Ku * 4, st);
-            hipLaunchKernelGGL(user_proj_small_kernel, dim3((unsigned)n_users, (unsigned)((du + 31) / 32)), dim3(256), 0, st, gu, w_user,
-                               (int)p->ldw_proj_user, Ku, b_user, U, du);
-            HIP_TRY(hipGetLastError());
-        } else {
-            HIP_TRY(linear_wide<EpiLinearT>(w_user, nullptr, p->ldw_proj_user, du, gu, n_users, st, Ku, b_user, U,
-                                            (long long)du, n_users, du, 0));
-        }
-    }
+    const RankerCtx c{p, st, w.X, w.T, w.X0, w.H, w.U, dm, hoist, with_q ? dm + p->d_ff : dm};
+    if (hoist && (rc = ranker_user_projection(c, user_cat, numerical, n_users))) return rc;
+    const long long n_cache = n_ad_rows > 0 ? n_ad_rows : 1;
     for (long long r0 = 0; r0 < rows; r0 += w.chunk) {
         const long long m = rows - r0 < w.chunk ? rows - r0 : w.chunk;
-        // ---- embed + project (+ pos[0], folded into b_proj on the host) ----
-        EmbConcatRows g{};
-        g.tables = p->tables; g.off = p->table_off; g.card = p->cards;
-        g.cat0 = (const long long*)user_cat; g.cat1 = (const long long*)ad_cat;
-        g.rowmap1 = (const long long*)ad_rowmap;
-        g.num = numerical;
-        g.row_base = r0;
-        g.rows1 = n_ad_rows > 0 ? n_ad_rows : 1;
-        g.rows = m; g.F = F; g.F0 = F0; g.E = p->emb_dim; g.eshift = ilog2(p->emb_dim);
-        g.n_num = p->n_num; g.cat0_rowdiv = (int)user_rowdiv;
         // fp16x3 row-owner engine: the rest of the chain is one kernel; with the candidate-side cache it also does the
         // gather (x0 = cache row + user half).  Its x0 scratch is the X0 region (sized in whole 128-row workgroups).
         const bool use_x3 = ranker_x3_wanted(p, m);
@@ -834,79 +887,17 @@ extern "C" int amdrec_ranker_forward(const amdrec_ranker_params* p, const int64_
         REQUIRE(use_x3 || !ranker_x3_folded(p), "x3.fold_attn1 is set but a pass of %lld rows would not run the row-owner "
                                                 "engine (the fold needs n_layers >= 1 and x3.min_rows == 1)", m);
         if (use_x3 && hoist && p->ad_proj_cache) {
-            int rc3 = ranker_x3_run(p, nullptr, 0, (const float*)U, (long long)du, (const long long*)ad_rowmap, r0, (int)user_rowdiv,
-                                    (long long)(n_ad_rows > 0 ? n_ad_rows : 1), m, X0, out_logits + r0, (long long)ld_logits, st);
-            if (rc3) return rc3;
-            continue;
-        }
-        if (hoist && p->ad_proj_cache) {
-            hipLaunchKernelGGL(proj_gather_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, p->ad_proj_cache,
-                               (long long)p->ld_ad_proj_cache, (long long)(n_ad_rows > 0 ? n_ad_rows : 1),
-                               (const long long*)ad_rowmap, r0, (const float*)U, dm, (int)user_rowdiv, X, m);
-        } else if (hoist) {
-            // candidate half: ad embeddings only (K = n_ad_feat * emb_dim), plus the user's row of U
-            EmbConcatRows ga = g;
-            ga.off = p->table_off + F0; ga.card = p->cards + F0;
-            ga.cat0 = nullptr; ga.num = nullptr; ga.n_num = 0; ga.F = F - F0; ga.F0 = 0; ga.cat0_rowdiv = 1;
-            HIP_TRY(linear_wide<EpiRowBiasT>(p->w_proj_ad, nullptr, p->ldw_proj_ad, dm, ga, m, st, (F - F0) * p->emb_dim,
-                                             (const float*)U, X, (long long)dm, m, r0, (int)user_rowdiv, dm));
+            rc = ranker_x3_run(p, nullptr, 0, c.U, c.du, (const long long*)ad_rowmap, r0, (int)user_rowdiv, n_cache, m, c.X0,
+                               out_logits + r0, (long long)ld_logits, st);
         } else {
-            HIP_TRY(linear_wide<EpiLinearT>(p->w_proj, nullptr, p->ldw_proj, dm, g, m, st, F * p->emb_dim + p->n_num,
-                                            p->b_proj, X, (long long)dm, m, dm, 0));
+            rc = ranker_project_rows(c, EmbConcatRows::ranker_rows(p, (const long long*)user_cat, numerical, user_rowdiv,
+                                                                   (const long long*)ad_cat, (const long long*)ad_rowmap,
+                                                                   n_ad_rows, r0, m));
+            if (rc) return rc;
+            rc = use_x3 ? ranker_x3_run(p, c.X, dm, nullptr, 0, nullptr, 0, 1, 0, m, c.X0, out_logits + r0, ld_logits, st)
+                        : ranker_layer_chain(c, m, out_logits + r0, ld_logits);
         }
-        if (use_x3) {
-            int rc3 = ranker_x3_run(p, (const float*)X, (long long)dm, nullptr, 0, nullptr, 0, 1, 0, m, X0, out_logits + r0,
-                                    (long long)ld_logits, st);
-            if (rc3) return rc3;
-            continue;
-        }
-        // ---- encoder layers ----
-        for (int l = 0; l < p->n_layers; ++l) {
-            const amdrec_encoder_layer& L = p->layers[l];
-            if (L.w_v != nullptr) {
-                // T = W_v x + b_v ; X = LN1(X + W_o T + b_o)
-                HIP_TRY(linear_wide<EpiLinearT>(L.w_v, nullptr, L.ldw_dm, dm, dense(X, m, dm, dm), m, st, dm, L.b_v, T,
-                                                (long long)dm, m, dm, 0));
-                HIP_TRY(linear_wide<EpiResidualLNT>(L.w_o, L.w_o_x6, L.ldw_dm, dm, dense(T, m, dm, dm), m, st, dm, L.b_o,
-                                                    (const float*)X, L.ln1_g, L.ln1_b, X, (long long)dm, m, dm,
-                                                    p->ln_eps));
-            } else {
-                // host pre-multiplied W_ov = W_o W_v: LN1(X + W_ov X + b_ov), written to the spare buffer
-                HIP_TRY(linear_wide<EpiResidualLNT>(L.w_o, L.w_o_x6, L.ldw_dm, dm, dense(X, m, dm, dm), m, st, dm, L.b_o,
-                                                    (const float*)X, L.ln1_g, L.ln1_b, T, (long long)dm, m, dm,
-                                                    p->ln_eps));
-                float* tmp = X; X = T; T = tmp;
-            }
-            // H = relu(W_1 X + b_1)
-            HIP_TRY(linear<EpiLinearT>(L.w_1, L.w_1_x6, L.ldw_dm, p->d_ff, dense(X, m, dm, dm), m, st, dm, L.b_1, H,
-                                       (long long)p->d_ff, m, p->d_ff, 1));
-            // X = LN2(X + W_2 H + b_2)
-            HIP_TRY(linear_wide<EpiResidualLNT>(L.w_2, L.w_2_x6, L.ldw_ff, dm, dense(H, m, p->d_ff, p->d_ff), m, st, p->d_ff,
-                                                L.b_2, (const float*)X, L.ln2_g, L.ln2_b, X, (long long)dm, m, dm,
-                                                p->ln_eps));
-        }
-        // ---- cross layers: xl <- x0 * (xl W_i + b_i) + xl ; x0 = X ----
-        const float* xl = X;
-        for (int c = 0; c < p->n_cross; ++c) {
-            float* dst = (c & 1) ? X0 : T;
-            HIP_TRY(linear_wide<EpiCrossT>(p->cross_wt[c], p->cross_wt_x6[c], p->ldw_cross, dm, dense(xl, m, dm, dm), m, st, dm,
-                                           p->cross_b[c], (const float*)X, xl, dst, (long long)dm, m, dm));
-            xl = dst;
-        }
-        // ---- heads ----
-        const int h1 = p->head_h1, h2 = p->head_h2, nt = p->n_tasks;
-        float* H1 = H;                                   // [m][nt*h1]
-        float* H2 = H + (size_t)m * nt * h1;             // [m][nt*h2]
-        HIP_TRY(linear<EpiLinearT>(p->head_w1, p->head_w1_x6, p->ldw_head1, nt * h1, dense(xl, m, dm, dm), m, st, dm, p->head_b1, H1,
-                                   (long long)nt * h1, m, nt * h1, 1));
-        for (int t = 0; t < nt; ++t) {
-            HIP_TRY(linear<EpiLinearT>(p->head_w2[t], nullptr, p->ldw_head2, h2, dense(H1 + t * h1, m, (long long)nt * h1, h1), m,
-                                       st, h1, p->head_b2[t], H2 + t * h2, (long long)nt * h2, m, h2, 1));
-            hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)((m * 16 + 255) / 256)), dim3(256), 0, st,
-                               H2 + t * h2, (long long)nt * h2, h2, p->head_w3[t], p->head_b3[t],
-                               out_logits + (long long)t * ld_logits + r0, m);
-        }
-        HIP_TRY(hipGetLastError());
+        if (rc) return rc;
     }
     return AMDREC_OK;
 }

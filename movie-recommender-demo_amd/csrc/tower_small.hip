@@ -425,15 +425,20 @@ bool tower_small_ok(const amdrec_tower_params* p, long long rows) {
     return true;
 }
 
+// the GEMV kernel at R = 1 / 2 / 4 rows per workgroup (see tower_gemv_kernel)
+template <int K0>
+static void launch_gemv(const TowerSmallArgs& a, long long rows, hipStream_t st) {
+    const int R = rows <= 256 ? 1 : (rows <= 512 ? 2 : 4);
+    const dim3 g((unsigned)((rows + R - 1) / R)), b(512);
+    if (R == 1) hipLaunchKernelGGL((tower_gemv_kernel<K0, 512, 256, 256, 1>), g, b, 0, st, a);
+    else if (R == 2) hipLaunchKernelGGL((tower_gemv_kernel<K0, 512, 256, 256, 2>), g, b, 0, st, a);
+    else hipLaunchKernelGGL((tower_gemv_kernel<K0, 512, 256, 256, 4>), g, b, 0, st, a);
+}
+
 hipError_t tower_small_run(const amdrec_tower_params* p, const long long* cat, const float* num, long long rows, float* out,
                            long long ld_out, hipStream_t st) {
     TowerSmallArgs a{};
-    a.in.tables = p->tables; a.in.off = p->table_off; a.in.card = p->cards;
-    a.in.cat0 = cat; a.in.cat1 = nullptr; a.in.rowmap1 = nullptr; a.in.num = num;
-    a.in.row_base = 0; a.in.rows = rows; a.in.rows1 = rows;
-    a.in.F = p->n_feat; a.in.F0 = p->n_feat; a.in.E = p->emb_dim;
-    a.in.eshift = 31 - __builtin_clz((unsigned)p->emb_dim);                  // emb_dim is a power of two (tower_check)
-    a.in.n_num = p->n_num; a.in.cat0_rowdiv = 1;
+    a.in = EmbConcatRows::tower_rows(p, cat, num, 0, rows);
     a.n_layers = p->n_layers;
     int wmax = (p->dims[0] + 127) & ~127;
     double flops = 0;
@@ -449,42 +454,30 @@ hipError_t tower_small_run(const amdrec_tower_params* p, const long long* cat, c
     a.out = out; a.ld_out = ld_out; a.rows = rows; a.renorm = p->renormalize;
     a.ld_act = wmax + 4;                                  // + 16 bytes: rows of a buffer start on different banks
     const size_t lds = 2ull * TS_ROWS * a.ld_act * sizeof(float);
-    static PerDeviceOnce attr_done;
-    if (attr_done.pending()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tower_small_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TS_ROWS * (TS_MAX_WIDTH + 4) * 4);
-        if (e != hipSuccess) return e;
-        attr_done.mark();
-    }
+    constexpr size_t max_lds = 2 * TS_ROWS * (TS_MAX_WIDTH + 4) * sizeof(float);
+    static PerDeviceOnce attr_fused, attr_pipe128, attr_pipe384;
+    hipError_t e = attr_fused.set_dynamic_lds(reinterpret_cast<const void*>(tower_small_kernel), max_lds);
+    if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((rows + TS_ROWS - 1) / TS_ROWS)), block(64 * TS_WAVES);
+    const double bytes = (double)rows * 4.0 * (p->dims[0] + p->dims[p->n_layers]);
     // the reference's towers (user: 109 -> 512 -> 256 -> 256, ad: 320 -> 512 -> 256 -> 256) as one software pipeline
     if (p->n_layers == 3 && p->dims[1] == 512 && p->dims[2] == 256 && p->dims[3] == 256 && (a.kp[0] == 128 || a.kp[0] == 384)) {
-        static PerDeviceOnce attr_pipe;
-        if (attr_pipe.pending()) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tower_pipe_kernel<128, 512, 256, 256>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TS_ROWS * (TS_MAX_WIDTH + 4) * 4);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(tower_pipe_kernel<384, 512, 256, 256>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TS_ROWS * (TS_MAX_WIDTH + 4) * 4);
-            if (e != hipSuccess) return e;
-            attr_pipe.mark();
-        }
+        e = attr_pipe128.set_dynamic_lds(reinterpret_cast<const void*>(tower_pipe_kernel<128, 512, 256, 256>), max_lds);
+        if (e == hipSuccess)
+            e = attr_pipe384.set_dynamic_lds(reinterpret_cast<const void*>(tower_pipe_kernel<384, 512, 256, 256>), max_lds);
+        if (e != hipSuccess) return e;
         if (rows <= TS_GEMV_MAX_ROWS) {                  // up to four rows per workgroup and one workgroup per CU: no MFMA tile to fill
-            ProfScope prof("tower_gemv_1row", flops * (double)rows, (double)rows * 4.0 * (p->dims[0] + p->dims[p->n_layers]), st);
-            const int R = rows <= 256 ? 1 : (rows <= 512 ? 2 : 4);
-            const dim3 g((unsigned)((rows + R - 1) / R));
-#define AMDREC_GEMV(K0_, R_) hipLaunchKernelGGL((tower_gemv_kernel<K0_, 512, 256, 256, R_>), g, dim3(512), 0, st, a)
-            if (a.kp[0] == 128) { if (R == 1) AMDREC_GEMV(128, 1); else if (R == 2) AMDREC_GEMV(128, 2); else AMDREC_GEMV(128, 4); }
-            else                { if (R == 1) AMDREC_GEMV(384, 1); else if (R == 2) AMDREC_GEMV(384, 2); else AMDREC_GEMV(384, 4); }
-#undef AMDREC_GEMV
+            ProfScope prof("tower_gemv_1row", flops * (double)rows, bytes, st);
+            if (a.kp[0] == 128) launch_gemv<128>(a, rows, st);
+            else launch_gemv<384>(a, rows, st);
             return hipGetLastError();
         }
-        ProfScope prof("tower_pipe_16rows", flops * (double)rows, (double)rows * 4.0 * (p->dims[0] + p->dims[p->n_layers]), st);
+        ProfScope prof("tower_pipe_16rows", flops * (double)rows, bytes, st);
         if (a.kp[0] == 128) hipLaunchKernelGGL((tower_pipe_kernel<128, 512, 256, 256>), grid, block, lds, st, a);
         else hipLaunchKernelGGL((tower_pipe_kernel<384, 512, 256, 256>), grid, block, lds, st, a);
         return hipGetLastError();
     }
-    ProfScope prof("tower_fused_16rows", flops * (double)rows, (double)rows * 4.0 * (p->dims[0] + p->dims[p->n_layers]), st);
+    ProfScope prof("tower_fused_16rows", flops * (double)rows, bytes, st);
     hipLaunchKernelGGL(tower_small_kernel, grid, block, lds, st, a);
     return hipGetLastError();
 }

@@ -131,6 +131,60 @@ def test_grouped_ivf_scan_refusals_match_the_recorded_table():
             assert lib.amdrec_last_error().decode() == case["error"], case
 
 
+def model_refusal_call(lib, table, case, params, buf):
+    """One call of tests/golden/model_refusals.json: the entry's `valid` call on a copy of its packed params, with the
+    fields ("p.<path>") and arguments under `valid_params` / `set` replaced.  -> return code"""
+    entry = table["entries"][case["entry"]]
+
+    def value(v):
+        return buf + int(v[3:] or 0) if isinstance(v, str) else v
+
+    p = params[entry["model"]]
+    p = type(p).from_buffer_copy(p)
+    for path, v in list(entry.get("valid_params", {}).items()) + [(k[2:], v) for k, v in case["set"].items() if k.startswith("p.")]:
+        *head, last = re.findall(r"\w+", path)                  # "n_layers", "dims[1]", "x3.w_hidden_ad"
+        obj = p
+        for t in head:
+            obj = obj[int(t)] if t.isdigit() else getattr(obj, t)
+        if last.isdigit():
+            obj[int(last)] = value(v)
+        else:
+            setattr(obj, last, value(v))
+    out = ctypes.c_size_t(0)
+    args = []
+    for name, v in zip(entry["params"], entry["valid"]):
+        v = case["set"].get(name, v)
+        args.append(ctypes.byref(p) if v == "p" else ctypes.byref(out) if v == "out" else value(v))
+    return getattr(lib, case["entry"])(*args)
+
+
+def test_model_entry_refusals_match_the_recorded_table():
+    """The towers' and the ranker's entries (workspace queries, amdrec_tower_forward, amdrec_ranker_forward,
+    amdrec_ranker_project_ads[_hidden]): return code and amdrec_last_error() text of every bad-argument call of
+    tests/golden/model_refusals.json - one per clause of tower_check and ranker_check, of each entry's pointer / leading
+    dimension / row-count checks and of the workspace-too-small answers, pairs that pin which refusal wins, and the empty
+    calls that return AMDREC_OK - recorded before amdrec_ranker_forward was split and the layer dispatch rewritten.  The
+    params are weights.pack_* of the demo models on "cpu"; every call returns before the entry's first HIP call."""
+    import json
+    from amdrec import _lib, synth, weights
+    lib = _lib.load()
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "model_refusals.json")))
+    user, ad, nnum = synth.demo_dims()
+    tower, keep_t = weights.pack_tower(synth.two_tower_state(user, ad, nnum, seed=1), "user_tower", list(user), nnum, "cpu")
+    ranker, keep_r, _ = weights.pack_ranker(synth.ranker_state(user, ad, nnum, seed=2), list(user), list(ad), nnum, "cpu")
+    raw = ctypes.create_string_buffer(4096 + 256)
+    buf = (ctypes.addressof(raw) + 255) // 256 * 256           # "a non-null, aligned pointer"; never dereferenced
+    assert {c["entry"] for c in table["cases"]} == set(table["entries"]) == {
+        "amdrec_tower_workspace", "amdrec_tower_forward", "amdrec_ranker_workspace", "amdrec_ranker_forward",
+        "amdrec_ranker_project_ads", "amdrec_ranker_project_ads_hidden"}
+    for case in table["cases"]:
+        assert case["set"] and case["rc"] in (0, -1, -3), case      # the valid call itself would launch
+        rc = model_refusal_call(lib, table, case, {"tower": tower, "ranker": ranker}, buf)
+        assert rc == case["rc"], (case, rc, lib.amdrec_last_error())
+        if rc:
+            assert lib.amdrec_last_error().decode() == case["error"], case
+
+
 def test_model_workspace_queries_follow_the_architecture():
     import ctypes as C
     from amdrec import _lib, synth, weights

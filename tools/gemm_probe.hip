@@ -9,9 +9,9 @@
 namespace amdrec {
 thread_local char g_err[512];
 int set_error(int c, const char*, ...) { return c; }
-bool g_prof_on = false;
+std::atomic<bool> g_prof_on{false};
 
-ProfScope::ProfScope(const char*, double, double, hipStream_t s) : slot(-1), st(s) {}
+ProfScope::ProfScope(const char*, double, double, hipStream_t s) : end(nullptr), st(s), gen(0) {}
 ProfScope::~ProfScope() {}
 
 struct NullRows {   // no memory traffic: operand values come from registers

@@ -1,7 +1,7 @@
 """Dev tool: codegen gate between two builds of one translation unit.  Inputs per side: the device assembly
 (hipcc <product flags> --cuda-device-only -S) and the remarks of -Rpass-analysis=kernel-resource-usage (stderr of that
 compile).  Prints the resource table (parent | branch per kernel) or the per-kernel diff of the instruction streams with
-comments, .loc / .file / .cfi lines, labels' debug suffixes and metadata stripped.
+comments, .loc / .file / .cfi lines, labels' debug suffixes, local labels' function ordinals and metadata stripped.
 usage: python tools/isa_diff.py resources parent.remarks branch.remarks [tu]
        python tools/isa_diff.py isa parent.s branch.s [tu]
 tu: the translation unit's name for the headings (default: the branch file's name up to its first dot + ".hip")"""
@@ -31,10 +31,12 @@ def resources(path):
 
 
 def kernels(path):
-    """kernel name -> its instruction lines (between the kernel's label and its s_endpgm / .Lfunc_end)"""
+    """kernel name -> its instruction lines (between the kernel's label and its s_endpgm / .Lfunc_end).  Local labels
+    (.LBB<n>_<m>, .LJTI<n>_<m>, .LCPI<n>_<m>) lose <n>, the function's ordinal in the translation unit: a kernel that joins or
+    leaves the unit renumbers every later function without moving an instruction."""
     out, cur = {}, None
     for line in open(path):
-        line = line.split(";")[0].rstrip()
+        line = re.sub(r"(\.L[A-Za-z]+)\d+_(\d+)", r"\1_\2", line.split(";")[0].rstrip())
         s = line.strip()
         m = re.match(r"^(\w+):$", s)
         if m and cur is None and not s.startswith(".L"):
@@ -65,17 +67,23 @@ def main():
         bad = 0
         for n in sorted(names, key=names.get):
             pa, pb = ra.get(n, {}), rb.get(n, {})
-            ok = all(pa.get(k) == pb.get(k) for _, k in cols if k != "TotalSGPRs") and bool(pa) and bool(pb)
-            bad += not ok
-            print("".join(f"{pa.get(k, '-') + '|' + pb.get(k, '-'):>15}" for _, k in cols) + f"  {'yes' if ok else 'NO '} {names[n]}")
-        print(f"\n{len(names)} kernels, {bad} outside the conditions")
+            ok = all(pa.get(k) == pb.get(k) for _, k in cols if k != "TotalSGPRs")
+            both = bool(pa) and bool(pb)                        # a kernel of one side only is listed, not judged
+            bad += both and not ok
+            mark = ("yes" if ok else "NO ") if both else ("old" if pa else "new")
+            print("".join(f"{pa.get(k, '-') + '|' + pb.get(k, '-'):>15}" for _, k in cols) + f"  {mark} {names[n]}")
+        print(f"\n{len(set(ra) & set(rb))} kernels in both, {bad} outside the conditions; {len(set(ra) - set(rb))} only in the "
+              f"parent (old), {len(set(rb) - set(ra))} only in the branch (new)")
         return 1 if bad else 0
     ka, kb = kernels(a), kernels(b)
     names = demangle(sorted(set(ka) | set(kb)))
     differ = 0
     print(f"Instruction streams of {tu}'s kernels, parent against branch (comments, .loc / .file lines and metadata stripped)\n")
     for n in sorted(names, key=names.get):
-        ia, ib = ka.get(n, []), kb.get(n, [])
+        if n not in ka or n not in kb:                     # left or joined the unit: listed, not compared
+            print(f"{names[n]}: ONLY IN {'PARENT' if n in ka else 'BRANCH'}")
+            continue
+        ia, ib = ka[n], kb[n]
         cnt = lambda v: (sum(1 for i in v if not i.endswith(":") and not i.startswith(".")), sum(1 for i in v if i.startswith("v_mfma")))
         same = ia == ib
         differ += not same
@@ -84,7 +92,8 @@ def main():
             d = list(difflib.unified_diff(ia, ib, "parent", "branch", n=1, lineterm=""))
             print(f"  {sum(1 for l in d if l[:1] in '+-' and l[:3] not in ('+++', '---'))} changed lines; first hunks:")
             print("\n".join("  " + l for l in d[:60]))
-    print(f"\n{len(names)} kernels, {differ} with a different instruction stream")
+    print(f"\n{len(set(ka) & set(kb))} kernels in both, {differ} with a different instruction stream; "
+          f"{len(set(ka) - set(kb))} only in the parent, {len(set(kb) - set(ka))} only in the branch")
     return 1 if differ else 0
 
 

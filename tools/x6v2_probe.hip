@@ -8,8 +8,8 @@
 namespace amdrec {
 thread_local char g_err[512];
 int set_error(int c, const char*, ...) { return c; }
-bool g_prof_on = false;
-ProfScope::ProfScope(const char*, double, double, hipStream_t s) : slot(-1), st(s) {}
+std::atomic<bool> g_prof_on{false};
+ProfScope::ProfScope(const char*, double, double, hipStream_t s) : end(nullptr), st(s), gen(0) {}
 ProfScope::~ProfScope() {}
 
 struct EpiSink {    // keeps the accumulators alive, writes (almost) nothing
