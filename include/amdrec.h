@@ -29,7 +29,8 @@ extern "C" {
                                * added exports, nothing else changed; and the
                                * first-FFN hidden cache: amdrec_ranker_project_ads_hidden, amdrec_x3_weights.stream_hc ... at the
                                * struct's end, amdrec_ranker_params.ad_hidden_cache - the number stays, the library and its
-                               * binding ship together and the struct layouts are checked against the compiler, tests/test_abi.py) */
+                               * binding ship together and the struct layouts are checked against the compiler, tests/test_abi.py;
+                               * amdrec_select_topk then gained its cand_pos argument under the same rule) */
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -404,7 +405,13 @@ int amdrec_ranker_workspace(const amdrec_ranker_params* p /*host*/, int64_t rows
  * Tensor.repeat at inference.py:241-242) and ad_cat row (ad_rowmap ? ad_rowmap[r] : r)
  * (ad_rowmap = candidate ids into a resident ad-feature table: the lookup the reference stubs
  * out at inference.py:244-248).  out_logits[t * ld_logits + r], t = ctr, engagement, revenue.
- * n_user_rows / n_ad_rows = rows of user_cat / ad_cat (for index validation only). */
+ * n_user_rows / n_ad_rows = rows of user_cat / ad_cat (for index validation only).
+ * An ad_rowmap entry outside [0, n_ad_rows) never faults: every gather clamps it into the table.  A NEGATIVE entry means
+ * "no candidate" (an unfilled slot of a search result): its logits are those of ad row 0 - unspecified, finite for finite
+ * weights and features - every other row's logits are what they are with any valid row in its place, bit for bit, and
+ * amdrec_select_topk(cand_pos = ad_rowmap) keeps such a slot out of the result.  bad_index_flag (device int, may be NULL)
+ * is set to 1 when a user_cat / ad_cat index is outside its table or an ad_rowmap entry is >= n_ad_rows (the reference's
+ * ad_table[cand] raises there); negative ad_rowmap entries do not set it. */
 int amdrec_ranker_forward(const amdrec_ranker_params* p /*host*/, const int64_t* user_cat,
                           const float* numerical, int64_t user_rowdiv, const int64_t* ad_cat,
                           const int64_t* ad_rowmap, int64_t rows, float* out_logits, int64_t ld_logits,
@@ -506,9 +513,15 @@ int amdrec_prep_numerical(const float* x, const float* mean /*[cols]*/, const fl
 /* Stage-2 selection (inference.py:258-263: sigmoid -> np.argsort(ctr)[::-1][:top_k]): per user
  * the top_k of its k_c candidates by the LOGIT of task `rank_task` (sigmoid is monotone), order
  * (logit desc, candidate slot asc).  out_ids[u][i] = cand_ids[u][slot], out_scores[t][u][i] =
- * sigmoid(logits[t][u*k_c + slot]), out_slots (optional) = the winning slots. */
+ * sigmoid(logits[t][u*k_c + slot]), out_slots (optional) = the winning slots.  NaN logits rank after every other logit.
+ * cand_pos (device, may be NULL = every slot is a candidate): the candidates' stage-1 corpus positions.  A slot with
+ * cand_pos < 0 was left unfilled by the search and is NOT a candidate, whatever its logit and its cand_ids entry (an id is
+ * the caller's to choose; validity is decided by position): it ranks after every real candidate, NaN logits included.
+ * Where a user has fewer than top_k real candidates (unfilled slots, or top_k > k_c) the tail reads out_ids = -1,
+ * out_scores = 0.0 for every task, out_slots = -1. */
 int amdrec_select_topk(const float* logits /*[n_tasks][ld]*/, int64_t ld_logits, int n_tasks,
-                       int rank_task, const int64_t* cand_ids /*[n_users][k_c]*/, int64_t n_users,
+                       int rank_task, const int64_t* cand_ids /*[n_users][k_c]*/,
+                       const int64_t* cand_pos /*[n_users][k_c] or NULL*/, int64_t n_users,
                        int k_c, int top_k, int64_t* out_ids /*[n_users][top_k]*/,
                        float* out_scores /*[n_tasks][n_users][top_k]*/, int32_t* out_slots, void* stream);
 

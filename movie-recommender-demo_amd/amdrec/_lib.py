@@ -79,7 +79,7 @@ _SIGNATURES = {
     "amdrec_ranker_project_ads_hidden": [_vp, _vp, _i64, _fp, _i64, _vp, _sz, _vp],
     "amdrec_ranker_x3_prefix": [_vp, _fp, _i64, _i64, _i32, _fp, _i64, _fp, _i64, _vp, _sz, _vp],
     "amdrec_prep_numerical": [_fp, _fp, _fp, _fp, _i64, _i32, _vp],
-    "amdrec_select_topk": [_fp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _fp, _vp, _vp],
+    "amdrec_select_topk": [_fp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _fp, _vp, _vp],
 }
 _RESTYPE = {"amdrec_last_error": C.c_char_p}
 

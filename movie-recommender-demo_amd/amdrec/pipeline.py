@@ -202,6 +202,12 @@ class AdRecommenderInference:
 
     def _stage2(self, uc, un, cand_pos, top_k, check_indices, ids_are_positions=False, mark=None, out=None,
                 excluded=False):
+        """Ranker + selection over stage 1's positions ``cand_pos`` [B, stage1_k].  A negative position is a slot the search
+        could not fill: no candidate.  The ranker still computes a (finite, unspecified) logit for it - every gather clamps
+        the row - and the selection, which is handed the positions, ranks it after every real candidate: it is reported only
+        where a user has fewer than ``top_k`` real candidates, as ad id -1 with probability 0.0 for every task.  Validity is
+        decided here, by position: ``candidate_ids`` keeps the search's convention for such a slot (``id_map[-1]``; the
+        position itself with ``ids_are_positions``), from which it can no longer be told."""
         lib = _lib.load()
         B, stage1_k = cand_pos.shape
         if self.cache_ad_projection:
@@ -230,8 +236,8 @@ class AdRecommenderInference:
                                             cand_pos.numel(), _lib.stream_ptr(uc.device)))
         if B:
             _lib.check(lib.amdrec_select_topk(_lib.ptr(logits), logits.stride(0), len(tasks), tasks.index("ctr"),
-                                              _lib.ptr(cand_ids), B, stage1_k, top_k, _lib.ptr(ad_ids),
-                                              _lib.ptr(scores), None, _lib.stream_ptr(uc.device)))
+                                              _lib.ptr(cand_ids), _lib.ptr(cand_pos), B, stage1_k, top_k,
+                                              _lib.ptr(ad_ids), _lib.ptr(scores), None, _lib.stream_ptr(uc.device)))
         return {"ad_ids": ad_ids, "scores": scores, "tasks": tasks, "candidate_ids": cand_ids, "logits": logits}
 
     @torch.no_grad()
@@ -244,7 +250,15 @@ class AdRecommenderInference:
         scores: inner products (descending) for Flat / IVF, approximate squared L2 distances (ascending) for IVFPQ.
         ``exclude_ad_ids``: device int64 [B, E], per user the ad ids that must not be recommended (negative = padding;
         stage1_k + E <= AMDREC_MAX_K): stage 1 searches stage1_k + E and drops them on the device (FAISSIndex.search_device),
-        so candidate_ids / candidate_scores and everything after them hold eligible ads only."""
+        so candidate_ids / candidate_scores and everything after them hold eligible ads only.
+        Short candidate lists: stage 1 leaves a slot unfilled (position -1; candidate_scores -inf, +inf for IVFPQ) when
+        stage1_k exceeds the corpus, with narrow IVF / IVFPQ probes, with a stored NaN row or a NaN query, after exclusions
+        and after remove_ads.  Such a slot is not a candidate: it ranks after every real candidate (those with a NaN logit
+        included) and is reported only where a user has fewer than top_k real candidates, as ad_ids == -1 with scores 0.0
+        for every task - the same tail that top_k > stage1_k gives.  The real ads of a row are distinct and were all
+        retrieved by stage 1.  candidate_ids keeps the search's convention for an unfilled slot (id_map[-1]) and its entry
+        of logits is unspecified but finite (for finite weights and user features): mask them with candidate_scores.
+        ``check_indices``: an out-of-range user index or ad-table row raises IndexError; an unfilled slot does not."""
         uc = _lib.require_gpu(user_categorical, "user_categorical")
         un = _lib.require_gpu(user_numerical, "user_numerical")
         excluded = exclude_ad_ids is not None and exclude_ad_ids.shape[-1] > 0
@@ -318,7 +332,8 @@ class AdRecommenderInference:
     # -- reference API ------------------------------------------------------------------------
     def recommend_ads(self, user_data: dict, top_k: int = 10, stage1_k: int = 500,
                       return_scores: bool = True, exclude_ad_ids=None) -> dict:
-        """inference.py:199-288.  ``exclude_ad_ids``: the ad ids this user must not be shown (a sequence of integers)."""
+        """inference.py:199-288.  ``exclude_ad_ids``: the ad ids this user must not be shown (a sequence of integers).
+        Fewer than ``top_k`` real candidates: as batch_recommend."""
         return self.batch_recommend([user_data], top_k=top_k, stage1_k=stage1_k, return_scores=return_scores,
                                     exclude_ad_ids=None if exclude_ad_ids is None else [exclude_ad_ids])[0]
 
@@ -326,7 +341,10 @@ class AdRecommenderInference:
                         return_scores: bool = True, exclude_ad_ids=None) -> list:
         """inference.py:290-331 - but one device pass for the whole list instead of a serial loop.
         ``timing`` reports the batch's stage times divided by the number of users.  ``exclude_ad_ids``: one sequence of
-        ad ids per user (recommend_device has the meaning); the padded block travels in the input staging block."""
+        ad ids per user (recommend_device has the meaning); the padded block travels in the input staging block.
+        ``ad_ids`` and every list of ``scores`` always have length ``top_k``: where stage 1 retrieved fewer than ``top_k``
+        ads for a user (a corpus smaller than top_k, exclusions, narrow probes, a NaN feature) the tail reads ad id -1
+        with score 0.0 for every task, and no ad appears that stage 1 did not retrieve for that user."""
         if not user_data_list:
             return []
         excl = self._host_exclusions(exclude_ad_ids, len(user_data_list), stage1_k)
@@ -390,7 +408,8 @@ class AdRecommenderInference:
         are validated without a read-back in the middle (the verdict travels with the results), the stage times come from
         events, ids + scores + verdict come back in one copy.  An out-of-range index raises IndexError like the reference's
         embedding lookup, before any result is returned.  ``exclude_ad_ids``: one sequence of ad ids per user, shipped as
-        one padded block through pinned memory (no synchronisation of its own)."""
+        one padded block through pinned memory (no synchronisation of its own).  The lists keep length ``top_k``, with
+        -1 / 0.0 in the tail of a user with fewer real candidates (batch_recommend)."""
         t0 = time.time()
         dev = self.device
         uc = user_categorical.to(dev)
@@ -476,7 +495,8 @@ class TwoStageRetriever:
     @torch.no_grad()
     def retrieve_and_rank(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor, stage1_k: int = 500,
                           stage2_k: int = 10, ad_features_lookup=None, exclude_ad_ids=None):
-        """``exclude_ad_ids``: the ad ids the (first) user must not be shown, a sequence of integers."""
+        """``exclude_ad_ids``: the ad ids the (first) user must not be shown, a sequence of integers.  With a table, the two
+        lists have length ``stage2_k``; a user with fewer real candidates gets -1 / 0.0 in the tail (batch_recommend)."""
         uc = user_categorical.to(self.device)
         un = user_numerical.to(self.device, dtype=torch.float32)
         excl = None if exclude_ad_ids is None else [exclude_ad_ids]

@@ -361,7 +361,13 @@ class TransformerRanker(nn.Module):
         """Pipeline form of inference.py:241-255: user u's features are broadcast over its
         ``k = candidate_rows.shape[1]`` candidates (no .repeat), ad features are gathered from the
         resident ``ad_table [N, n_ad_feat]`` by candidate row.  -> logits dict, each [U*k]
-        (``raw=True``: (task names, one [n_tasks, U*k] tensor))."""
+        (``raw=True``: (task names, one [n_tasks, U*k] tensor)).
+        A NEGATIVE candidate row means "no candidate" (an unfilled slot of a search result): it never faults (every gather
+        clamps it to row 0), its logits are unspecified but finite for finite weights and features, and every other row's
+        logits are, bit for bit, what they are with any valid row in its place.  ``check_indices=True``: a user index or an
+        ad-table entry outside its embedding table, or a candidate row >= ``ad_table.shape[0]``, raises IndexError (as the
+        reference's embedding lookup / ``ad_table[cand]`` would); a negative candidate row does not.  Without the flag a
+        row past the table is clamped to its last row, silently."""
         uc = _lib.require_gpu(user_categorical, "user_categorical").long().contiguous()
         nm = _lib.require_gpu(numerical, "numerical").to(torch.float32).contiguous()
         cand = _lib.require_gpu(candidate_rows, "candidate_rows", torch.int64).contiguous()

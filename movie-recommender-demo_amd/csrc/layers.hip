@@ -453,6 +453,14 @@ static void launch_check_index(const int64_t* cat, long long rows, int F, const 
                        rows, F, card, flag);
 }
 
+// ad_rowmap against the ad table on the checked path: a row >= n_rows is out of range (the reference's ad_table[cand] raises);
+// a negative row means "no candidate" (an unfilled search slot) and is not an error
+__global__ void check_rowmap_kernel(const long long* rowmap, long long n, long long n_rows, int* flag) {
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (rowmap[i] >= n_rows) *flag = 1;
+}
+
 static inline DenseRows dense(const float* p, long long rows, long long ld, int K) {
     return DenseRows{p, rows, (int)ld, K, 30, 1ll << 30};
 }
@@ -654,7 +662,8 @@ __global__ __launch_bounds__(256) void proj_gather_kernel(const float* cache, lo
     if (r >= m) return;
     const long long gr = row_base + r;
     long long a = rowmap ? rowmap[gr] : gr;
-    a = a < 0 ? 0 : (a >= n_cache ? n_cache - 1 : a);        // clamped like the gather loader (reported separately)
+    a = a < 0 ? 0 : (a >= n_cache ? n_cache - 1 : a);        // clamped like the gather loader (a negative row = no candidate:
+                                                             // amdrec_select_topk drops it; >= n_cache: check_rowmap_kernel)
     const f32x4* cp = reinterpret_cast<const f32x4*>(cache + a * ldc);
     const f32x4* up = reinterpret_cast<const f32x4*>(U + (gr / rowdiv) * dm);
     f32x4* xp = reinterpret_cast<f32x4*>(X + r * dm);
@@ -868,6 +877,9 @@ extern "C" int amdrec_ranker_forward(const amdrec_ranker_params* p, const int64_
     if (bad_index_flag) {
         if (F0 && n_user_rows > 0) launch_check_index(user_cat, n_user_rows, F0, p->cards, bad_index_flag, st);
         if (F - F0 && n_ad_rows > 0) launch_check_index(ad_cat, n_ad_rows, F - F0, p->cards + F0, bad_index_flag, st);
+        if (F - F0 && ad_rowmap)
+            hipLaunchKernelGGL(check_rowmap_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st,
+                               (const long long*)ad_rowmap, (long long)rows, (long long)n_ad_rows, bad_index_flag);
     }
 
     // First-FFN hidden cache (amdrec_x3_weights.stream_hc): when the largest pass of this call takes it, the user projection

@@ -438,7 +438,7 @@ __global__ __launch_bounds__(256, 1) void ranker_x3_kernel(Program G, Input in, 
     } else {
         const long long gr = in.row_base + rowc;
         long long a = in.rowmap ? in.rowmap[gr] : gr;
-        a = a < 0 ? 0 : (a >= in.n_cache ? in.n_cache - 1 : a);     // clamped like the gather loader (reported separately)
+        a = a < 0 ? 0 : (a >= in.n_cache ? in.n_cache - 1 : a);     // clamped like the gather loader (amdrec_ranker_forward has the contract)
         load_rows(x, in.cache + a * in.ldc, h);
         add_rows(x, in.U + (gr / in.rowdiv) * in.ldu, h);              // cache row + the user's half (same order as proj_gather)
     }

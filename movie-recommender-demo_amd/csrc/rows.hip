@@ -53,12 +53,15 @@ __global__ void prep_numerical_kernel(const float* x, const float* mean, const f
 // Stage-2 selection (inference.py:258-263, faiss_retrieval.py:355-358): per user, the top_k of
 // its k_c candidates by the ranking task's LOGIT (sigmoid is monotone; ranking on logits avoids
 // the ties of saturated sigmoids), order (logit desc, candidate slot asc); then sigmoid of every
-// task's logit at the winners and the winners' ad ids.  One block per user, bitonic sort of
-// 64-bit (logit, ~slot) keys in LDS.
+// task's logit at the winners and the winners' ad ids.  cand_pos (nullable): the candidates' stage-1 positions; a slot whose
+// position is negative was never filled by the search and is no candidate: it gets the empty key 0 (below every real key,
+// NaN logits included), so it can only appear behind all real candidates, where it reads id -1 / probability 0 like the
+// tail of a list shorter than top_k.  One block per user, bitonic sort of 64-bit (logit, ~slot) keys in LDS.
 __global__ __launch_bounds__(256) void select_topk_kernel(const float* logits, long long ld, int n_tasks,
-                                                          int rank_task, const long long* cand_ids, int k_c,
-                                                          int top_k, long long* out_ids, float* out_scores,
-                                                          int* out_slots, long long n_users) {
+                                                          int rank_task, const long long* cand_ids,
+                                                          const long long* cand_pos, int k_c, int top_k,
+                                                          long long* out_ids, float* out_scores, int* out_slots,
+                                                          long long n_users) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
     const long long u = blockIdx.x;
     int P = 2;
@@ -66,7 +69,7 @@ __global__ __launch_bounds__(256) void select_topk_kernel(const float* logits, l
     const float* lr = logits + (long long)rank_task * ld + u * k_c;
     for (int i = threadIdx.x; i < P; i += blockDim.x) {
         unsigned long long key = 0ull;
-        if (i < k_c) {
+        if (i < k_c && !(cand_pos && cand_pos[u * k_c + i] < 0)) {
             float v = lr[i];
             if (v == v) key = make_key(v, (uint32_t)i);     // NaN logits rank last
             else key = (unsigned long long)(~(uint32_t)i) | (1ull << 32);
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(256) void select_topk_kernel(const float* logits, l
             __syncthreads();
         }
     for (int i = threadIdx.x; i < top_k; i += blockDim.x) {
-        const bool valid = i < k_c;
+        const bool valid = i < k_c && keys[i] != 0ull;           // (0 = empty: padding, or a slot stage 1 left unfilled)
         const int slot = valid ? (int)key_pos(keys[i]) : -1;
         out_ids[u * top_k + i] = valid ? cand_ids[u * k_c + slot] : -1;
         if (out_slots) out_slots[u * top_k + i] = slot;
@@ -104,9 +107,9 @@ __global__ __launch_bounds__(256) void select_topk_kernel(const float* logits, l
 // 512-key bitonic sort above takes ~20 us of barriers whatever the batch; this takes ~3.
 template <int KPL>
 __global__ __launch_bounds__(256) void select_topk_small_kernel(const float* logits, long long ld, int n_tasks, int rank_task,
-                                                                const long long* cand_ids, int k_c, int top_k,
-                                                                long long* out_ids, float* out_scores, int* out_slots,
-                                                                long long n_users) {
+                                                                const long long* cand_ids, const long long* cand_pos,
+                                                                int k_c, int top_k, long long* out_ids, float* out_scores,
+                                                                int* out_slots, long long n_users) {
     const int lane = threadIdx.x & 63;
     const long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (u >= n_users) return;                                  // wave-uniform
@@ -116,7 +119,7 @@ __global__ __launch_bounds__(256) void select_topk_small_kernel(const float* log
     for (int j = 0; j < KPL; ++j) {
         const int i = lane + 64 * j;
         unsigned long long kk = 0ull;
-        if (i < k_c) {
+        if (i < k_c && !(cand_pos && cand_pos[u * k_c + i] < 0)) {
             const float v = lr[i];
             kk = (v == v) ? make_key(v, (uint32_t)i) : ((unsigned long long)(~(uint32_t)i) | (1ull << 32));   // NaN ranks last
         }
@@ -166,8 +169,8 @@ extern "C" int amdrec_prep_numerical(const float* x, const float* mean, const fl
 }
 
 extern "C" int amdrec_select_topk(const float* logits, int64_t ld_logits, int n_tasks, int rank_task,
-                                  const int64_t* cand_ids, int64_t n_users, int k_c, int top_k, int64_t* out_ids,
-                                  float* out_scores, int32_t* out_slots, void* stream) {
+                                  const int64_t* cand_ids, const int64_t* cand_pos, int64_t n_users, int k_c, int top_k,
+                                  int64_t* out_ids, float* out_scores, int32_t* out_slots, void* stream) {
     REQUIRE(n_tasks >= 1 && rank_task >= 0 && rank_task < n_tasks, "bad task index");
     REQUIRE(k_c >= 1 && k_c <= AMDREC_MAX_K, "candidates per user must be in [1,%d]", AMDREC_MAX_K);
     REQUIRE(top_k >= 1 && top_k <= AMDREC_MAX_K, "top_k out of range");
@@ -179,10 +182,10 @@ extern "C" int amdrec_select_topk(const float* logits, int64_t ld_logits, int n_
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);
         if (k_c <= 128)
             hipLaunchKernelGGL(select_topk_small_kernel<2>, grid, dim3(256), 0, st, logits, (long long)ld_logits, n_tasks, rank_task,
-                               (const long long*)cand_ids, k_c, top_k, (long long*)out_ids, out_scores, out_slots, (long long)n_users);
+                               (const long long*)cand_ids, (const long long*)cand_pos, k_c, top_k, (long long*)out_ids, out_scores, out_slots, (long long)n_users);
         else
             hipLaunchKernelGGL(select_topk_small_kernel<8>, grid, dim3(256), 0, st, logits, (long long)ld_logits, n_tasks, rank_task,
-                               (const long long*)cand_ids, k_c, top_k, (long long*)out_ids, out_scores, out_slots, (long long)n_users);
+                               (const long long*)cand_ids, (const long long*)cand_pos, k_c, top_k, (long long*)out_ids, out_scores, out_slots, (long long)n_users);
         HIP_TRY(hipGetLastError());
         return AMDREC_OK;
     }
@@ -190,7 +193,7 @@ extern "C" int amdrec_select_topk(const float* logits, int64_t ld_logits, int n_
     while (P < k_c) P <<= 1;
     hipLaunchKernelGGL(select_topk_kernel, dim3((unsigned)n_users), dim3(256), (size_t)P * 8,
                        reinterpret_cast<hipStream_t>(stream), logits, (long long)ld_logits, n_tasks, rank_task,
-                       (const long long*)cand_ids, k_c, top_k, (long long*)out_ids, out_scores, out_slots,
+                       (const long long*)cand_ids, (const long long*)cand_pos, k_c, top_k, (long long*)out_ids, out_scores, out_slots,
                        (long long)n_users);
     HIP_TRY(hipGetLastError());
     return AMDREC_OK;

@@ -24,6 +24,11 @@
 
 namespace amdrec {
 
+// The hidden layers' ReLU keeps a NaN, as torch.relu does (fmaxf alone returns its other operand, 0): a row with a NaN feature
+// then leaves the tower as a NaN embedding, which the search answers with an empty candidate list, instead of as the
+// embedding of an all-zero first hidden layer.  Every other value, -0.0 included, gives what fmaxf(v, 0) gives.
+__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+
 constexpr int TS_ROWS = 16, TS_WAVES = 8;
 constexpr long long TS_MAX_ROWS = 4096;      // one 16-row workgroup per CU; beyond it the tiled GEMMs have enough work per launch
 constexpr int TS_MAX_WIDTH = 1024;
@@ -192,13 +197,13 @@ __global__ __launch_bounds__(64 * TS_WAVES) void tower_small_kernel(TowerSmallAr
             const f32x4 b0 = *reinterpret_cast<const f32x4*>(bias + 16 * t + 4 * g);
             f32x4 y0;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) y0[e] = last ? acc0[e] + b0[e] : fmaxf(acc0[e] + b0[e], 0.f);
+            for (int e = 0; e < 4; ++e) y0[e] = last ? acc0[e] + b0[e] : relu_keep_nan(acc0[e] + b0[e]);
             *reinterpret_cast<__attribute__((address_space(3))) f32x4*>(dst + n * LD + 16 * t + 4 * g) = y0;
             if (two) {
                 const f32x4 b1 = *reinterpret_cast<const f32x4*>(bias + 16 * (t + 1) + 4 * g);
                 f32x4 y1;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) y1[e] = last ? acc1[e] + b1[e] : fmaxf(acc1[e] + b1[e], 0.f);
+                for (int e = 0; e < 4; ++e) y1[e] = last ? acc1[e] + b1[e] : relu_keep_nan(acc1[e] + b1[e]);
                 *reinterpret_cast<__attribute__((address_space(3))) f32x4*>(dst + n * LD + 16 * (t + 1) + 4 * g) = y1;
             }
         }
@@ -297,8 +302,8 @@ struct TowerPipe {
             f32x4 y0, y1;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                y0[e] = last ? acc0[e] + B0[S][e] : fmaxf(acc0[e] + B0[S][e], 0.f);
-                y1[e] = last ? acc1[e] + B1[S][e] : fmaxf(acc1[e] + B1[S][e], 0.f);
+                y0[e] = last ? acc0[e] + B0[S][e] : relu_keep_nan(acc0[e] + B0[S][e]);
+                y1[e] = last ? acc1[e] + B1[S][e] : relu_keep_nan(acc1[e] + B1[S][e]);
             }
             *reinterpret_cast<__attribute__((address_space(3))) f32x4*>(dst) = y0;
             *reinterpret_cast<__attribute__((address_space(3))) f32x4*>(dst + 16) = y1;
@@ -383,7 +388,7 @@ struct TowerGemv {
             v += __shfl_xor(v, 2, 64);
             v += __shfl_xor(v, 4, 64);
             v += Bv[P & 1];
-            if (j == 0) act[r * 2048 + ((L + 1) & 1) * 1024 + 64 * local(P) + n8] = L == 2 ? v : fmaxf(v, 0.f);
+            if (j == 0) act[r * 2048 + ((L + 1) & 1) * 1024 + 64 * local(P) + n8] = L == 2 ? v : relu_keep_nan(v);
         }
         if constexpr (P + 1 < NP) run<P + 1>();
     }

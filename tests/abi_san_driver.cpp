@@ -96,7 +96,7 @@ int main() {
     EXPECT(amdrec_l2_normalize(fp, 256, fp, 256, 0, 256, nullptr) == 0);
     EXPECT(amdrec_remap_ids(ip, ip, 10, ip, 0, nullptr) == 0);
     EXPECT(amdrec_prep_numerical(fp, fp, fp, fp, 0, 13, nullptr) == 0);
-    EXPECT(amdrec_select_topk(fp, 500, 3, 5, ip, 1, 500, 10, ip, fp, nullptr, nullptr) < 0);                    // rank_task out of range
+    EXPECT(amdrec_select_topk(fp, 500, 3, 5, ip, nullptr, 1, 500, 10, ip, fp, nullptr, nullptr) < 0);                    // rank_task out of range
 
     // ---- towers ----
     amdrec_tower_params tp;

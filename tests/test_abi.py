@@ -97,7 +97,7 @@ def test_host_only_entry_points_validate_arguments_without_a_gpu():
     assert lib.amdrec_flat_search(None, 10, 256, 256, None, 1, 256, 5, 0, None, None, None, 0, None, None) == -1  # nulls
     assert lib.amdrec_l2_normalize(None, 256, None, 256, 0, 256, None) == 0        # rows = 0: nothing to do
     assert lib.amdrec_l2_normalize(None, 256, None, 256, 4, 255, None) == -1
-    assert lib.amdrec_select_topk(None, 0, 3, 5, None, 1, 500, 10, None, None, None, None) == -1   # bad task index
+    assert lib.amdrec_select_topk(None, 0, 3, 5, None, None, 1, 500, 10, None, None, None, None) == -1   # bad task index
     assert lib.amdrec_topk_merge(None, None, 40, 96, 0, 1, 500, None, None, None) == -1            # 40*500 > 16384
     assert lib.amdrec_ivf_select(None, 0, None, 0, 10, None, None, None) == 0                      # nq = 0
     assert lib.amdrec_topk_merge_partial(None, None, 8, 128, 96, 0, 1, 500, None, None, None, None) == -1   # no counter

@@ -78,12 +78,16 @@ def test_corpus_build_1m_rows_through_ad_tower_and_index():
     assert all(np.array_equal(table[ids[i, 0]], table[rows[i]]) for i in range(8))
 
 
-@pytest.mark.parametrize("k_c,top_k", [(500, 10), (100, 10), (500, 32), (7, 10), (500, 64), (600, 10)])
+@pytest.mark.parametrize("k_c,top_k", [(500, 10), (100, 10), (500, 32), (7, 10), (500, 64), (600, 10),
+                                       (128, 10), (129, 10), (512, 32), (513, 10), (2048, 1), (500, 33)])
 def test_select_topk_both_kernels_ties_nan_and_short_lists(k_c, top_k):
     """amdrec_select_topk (np.argsort(ctr)[::-1][:top_k] of inference.py:263, on logits): order (logit desc, candidate slot
     asc) on ties, NaN logits last, sigmoid of every task at the winners, -1 / 0-probability padding when a user has fewer
-    than top_k candidates.  top_k <= 32 with <= 512 candidates takes the one-wave-per-user kernel (no sort), everything
-    else the LDS bitonic sort: both must agree with numpy's lexsort."""
+    than top_k candidates.  top_k <= 32 with <= 512 candidates takes the one-wave-per-user kernel (no sort; two keys per
+    lane up to 128 candidates, eight beyond), everything else the LDS bitonic sort: both must agree with numpy's lexsort.
+    Run twice: with cand_pos = NULL (every slot a candidate), and with stage-1 positions in which user 5 has every third
+    slot negative, user 6 all of them and user 7 an unfilled slot with a huge logit next to a real one with a NaN logit: a
+    negative position is no candidate (behind every real one, NaN logits included; -1 / 0 where it would be reported)."""
     import ctypes as C
     from amdrec import _lib
     lib = _lib.load()
@@ -96,28 +100,43 @@ def test_select_topk_both_kernels_ties_nan_and_short_lists(k_c, top_k):
         lg[2, ::3] = lg[2, 1]                                  # many ties scattered
         lg[3, [0, 4]] = np.nan                                 # NaN ranks last
         lg[4, :] = -np.inf
+        lg[7, 2], lg[7, 3] = np.nan, 1e6                       # (slot 3 is unfilled in the cand_pos run below)
     logits[0] = lg.reshape(-1)
     cand = rng.permutation(10_000_000)[:U * k_c].reshape(U, k_c).astype(np.int64)
     d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()          # noqa: E731
     L, Cd = d(logits), d(cand)
-    ids = torch.full((U, top_k), -7, dtype=torch.int64, device="cuda")
-    sc = torch.full((T, U, top_k), -7.0, dtype=torch.float32, device="cuda")
-    slots = torch.full((U, top_k), -7, dtype=torch.int32, device="cuda")
-    _lib.check(lib.amdrec_select_topk(_lib.ptr(L), L.stride(0), T, 0, _lib.ptr(Cd), U, k_c, top_k, _lib.ptr(ids), _lib.ptr(sc),
-                                      _lib.ptr(slots), _lib.stream_ptr(L.device)))
-    torch.cuda.synchronize()
-    ids, sc, slots = ids.cpu().numpy(), sc.cpu().numpy(), slots.cpu().numpy()
-    n = min(k_c, top_k)
-    for u in range(U):
-        v = lg[u].astype(np.float64)
-        key = np.where(np.isnan(v), -np.inf, v)                # NaN last; among NaNs (and -inf) lower slot first
-        nan_last = np.isnan(v).astype(np.int64)
-        order = np.lexsort((np.arange(k_c), -key, nan_last))[:n]
-        assert slots[u, :n].tolist() == order.tolist(), (u, slots[u], order)
-        assert ids[u, :n].tolist() == cand[u][order].tolist()
-        for t in range(T):
-            x = logits[t].reshape(U, k_c)[u][order].astype(np.float64)
-            want = 1.0 / (1.0 + np.exp(-x))
-            got = sc[t, u, :n]
-            assert np.allclose(got[~np.isnan(x)], want[~np.isnan(x)], atol=1e-6)
-        assert (ids[u, n:] == -1).all() and (slots[u, n:] == -1).all() and (sc[:, u, n:] == 0).all()
+    pos = rng.integers(0, 10_000_000, size=(U, k_c)).astype(np.int64)
+    pos[5, ::3] = -1
+    pos[6, :] = -1
+    if k_c > 5:
+        pos[7, 3] = -1
+    for P in (None, pos):
+        ids = torch.full((U, top_k), -7, dtype=torch.int64, device="cuda")
+        sc = torch.full((T, U, top_k), -7.0, dtype=torch.float32, device="cuda")
+        slots = torch.full((U, top_k), -7, dtype=torch.int32, device="cuda")
+        Pd = None if P is None else d(P)
+        _lib.check(lib.amdrec_select_topk(_lib.ptr(L), L.stride(0), T, 0, _lib.ptr(Cd), _lib.ptr(Pd), U, k_c, top_k, _lib.ptr(ids),
+                                          _lib.ptr(sc), _lib.ptr(slots), _lib.stream_ptr(L.device)))
+        torch.cuda.synchronize()
+        ids, sc, slots = ids.cpu().numpy(), sc.cpu().numpy(), slots.cpu().numpy()
+        for u in range(U):
+            v = lg[u].astype(np.float64)
+            key = np.where(np.isnan(v), -np.inf, v)                # NaN last; among NaNs (and -inf) lower slot first
+            nan_last = np.isnan(v).astype(np.int64)
+            unfilled = np.zeros(k_c, dtype=np.int64) if P is None else (P[u] < 0).astype(np.int64)
+            n = min(k_c - int(unfilled.sum()), top_k)
+            order = np.lexsort((np.arange(k_c), -key, nan_last, unfilled))[:n]
+            assert slots[u, :n].tolist() == order.tolist(), (u, slots[u], order)
+            assert ids[u, :n].tolist() == cand[u][order].tolist()
+            for t in range(T):
+                x = logits[t].reshape(U, k_c)[u][order].astype(np.float64)
+                want = 1.0 / (1.0 + np.exp(-x))
+                got = sc[t, u, :n]
+                assert np.allclose(got[~np.isnan(x)], want[~np.isnan(x)], atol=1e-6)
+            assert (ids[u, n:] == -1).all() and (slots[u, n:] == -1).all() and (sc[:, u, n:] == 0).all()
+        if P is not None:
+            assert (ids[6] == -1).all() and (sc[:, 6] == 0).all()
+            if k_c > 5:
+                assert 3 not in slots[7].tolist()
+                if top_k >= k_c:
+                    assert slots[7, k_c - 2] == 2 and slots[7, k_c - 1] == -1      # the NaN is the last real candidate
