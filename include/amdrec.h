@@ -219,16 +219,26 @@ int amdrec_ivfpq_rerank(const void* rows, int rows_bf16, int64_t nrows, int64_t 
  * [q0, q0+nq) merge n_lists per-shard top-k lists (scores/positions of list g start
  * g*list_stride_bytes after the base pointers; each list is [nq_total][k]; positions are global int32
  * (the exchange format: 8 bytes per candidate on the wire), -1 = unfilled) into the global top-k, same
- * order rule as amdrec_flat_search.  n_lists*k <= 16384. */
+ * order rule as amdrec_flat_search: score descending (-0.0 == +0.0), equal scores -> lower position.  An entry
+ * with a negative position or a NaN score is dropped wherever it stands in its list; slots that cannot be filled
+ * come back as -inf / -1.  Output row i belongs to query q0 + i.  1 <= n_lists*k <= 16384,
+ * list_stride_bytes % 4 == 0, q0 >= 0; nq <= 0 returns AMDREC_OK without reading a pointer. */
 int amdrec_topk_merge(const float* scores, const int32_t* pos, int n_lists, int64_t list_stride_bytes,
                       int64_t q0, int64_t nq, int k, float* out_scores /*[nq][k]*/,
                       int64_t* out_pos /*[nq][k]*/, void* stream);
-/* Same with SHORT lists: every shard sends only its best list_k <= k rows per query (each list is [nq_total][list_k]),
- * which cuts a shard's exact re-scoring and the wire bytes by k / list_k.  The merged top-k is the exact global top-k iff
- * no shard was cut off above the merged k-th score; *n_inexact (device int32, NOT reset: accumulates) is incremented for
- * every query where that cannot be shown - a full list whose last score reaches the merged k-th score (ties included),
- * or fewer than k merged entries while some list is full.  The caller repeats such a batch with list_k = k
- * (amdrec.sharded.ShardedRecommender does).  n_lists*list_k <= 16384. */
+/* Same with SHORT lists: every shard sends only its best list_k rows per query (each list is [nq_total][list_k]), which
+ * cuts a shard's exact re-scoring and the wire bytes by k / list_k.  Every list must be sorted in the search's own order
+ * (score descending, equal scores -> lower position), so that a row a shard did not send is strictly behind its list's
+ * last entry in that order.  A list is FULL when its last entry has a position >= 0 and a score that is not NaN (a NaN or
+ * unfilled last entry: the shard had no more rows, nothing was cut).  The merged top-k is the exact global top-k iff no
+ * FULL list's last entry lies strictly ahead of the merged k-th entry in the (score, position) order; *n_inexact (device
+ * int32, NOT reset: accumulates) is incremented once for every query where that cannot be shown - some FULL list ends
+ * ahead of the merged k-th entry, or fewer than k entries merged while some list is FULL.  A tie in score alone is not
+ * counted: a last entry that IS the merged k-th, or has its score at a higher position, proves the list was cut behind
+ * the boundary; the same score at a lower position is ahead and is counted.  Entries with a negative position or a NaN
+ * score are dropped wherever they stand, as in amdrec_topk_merge.  The caller repeats a counted batch with list_k = k
+ * (amdrec.sharded.ShardedRecommender does).  1 <= n_lists*list_k <= 16384 and 1 <= k <= 16384 (k may exceed
+ * n_lists*list_k: the tail is -inf / -1); n_inexact must not be NULL. */
 int amdrec_topk_merge_partial(const float* scores, const int32_t* pos, int n_lists, int list_k,
                               int64_t list_stride_bytes, int64_t q0, int64_t nq, int k,
                               float* out_scores /*[nq][k]*/, int64_t* out_pos /*[nq][k]*/,

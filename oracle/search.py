@@ -72,12 +72,13 @@ def flat_ip_search(xb, xq, k, chunk=1 << 16, dtype=np.float32):
 
 
 def _merge(D, I, k):
-    """Merge candidate lists: (score desc, id asc), invalid (-1) last."""
+    """Merge candidate lists: (score desc, id asc); an entry with id -1 or a NaN score is dropped (amdrec_topk_merge's
+    contract, and the flat search's: a row whose score is NaN is never returned), unfilled slots (-inf, -1) come last."""
     nq = D.shape[0]
     oD = np.full((nq, k), -np.inf, dtype=np.float32)
     oI = np.full((nq, k), -1, dtype=np.int64)
     for q in range(nq):
-        valid = I[q] >= 0
+        valid = (I[q] >= 0) & ~np.isnan(D[q])
         d, i = D[q][valid], I[q][valid]
         order = np.lexsort((i, -d.astype(np.float64)))[:k]
         oD[q, :len(order)] = d[order]
@@ -98,7 +99,8 @@ def merge_partial(Ds, Is, offsets, k):
     behind its last entry.  The merged top-k is proven exact when no FULL list's last entry lies strictly AHEAD of the
     merged k-th entry in that order; a last entry that IS the merged k-th, or ties with its score at a higher position,
     proves the list was cut at or below the boundary (score ties alone are not failures).  A merged list shorter than k
-    with a full shard list counts as not proven."""
+    with a full shard list counts as not proven.  An entry with position -1 or a NaN score is dropped wherever it stands; a
+    list whose LAST entry is such an entry is not full."""
     D, I = merge_shards(Ds, Is, offsets, k)
     nq = D.shape[0]
     inexact = np.zeros(nq, dtype=bool)

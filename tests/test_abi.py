@@ -102,6 +102,24 @@ def test_host_only_entry_points_validate_arguments_without_a_gpu():
     assert lib.amdrec_ivf_select(None, 0, None, 0, 10, None, None, None) == 0                      # nq = 0
     assert lib.amdrec_topk_merge_partial(None, None, 8, 128, 96, 0, 1, 500, None, None, None, None) == -1   # no counter
     assert b"n_inexact" in lib.amdrec_last_error()
+    # the merge's other refusals (amdrec_topk_merge_partial checks its counter first: a host word nobody dereferences)
+    cnt = C.c_int32(5)
+    cp = C.c_void_p(C.addressof(cnt))
+    assert lib.amdrec_topk_merge(None, None, 8, 98, 0, 1, 500, None, None, None) == -1              # list_stride_bytes % 4
+    assert b"stride" in lib.amdrec_last_error()
+    assert lib.amdrec_topk_merge(None, None, 8, 96, -1, 1, 500, None, None, None) == -1             # q0 < 0
+    assert b"offset" in lib.amdrec_last_error()
+    assert lib.amdrec_topk_merge_partial(None, None, 1, 1, 96, 0, 1, 16385, None, None, cp, None) == -1    # k = 16385
+    assert b"16384" in lib.amdrec_last_error()
+    assert lib.amdrec_topk_merge_partial(None, None, 1, 0, 96, 0, 1, 500, None, None, cp, None) == -1      # list_k = 0
+    assert lib.amdrec_topk_merge(None, None, 0, 96, 0, 1, 500, None, None, None) == -1              # n_lists = 0
+    assert lib.amdrec_topk_merge_partial(None, None, 5, 3277, 96, 0, 1, 500, None, None, cp, None) == -1   # 5 * 3277 = 16385
+    assert b"16384" in lib.amdrec_last_error()
+    assert lib.amdrec_topk_merge_partial(None, None, 4, 4096, 96, 0, 1, 16384, None, None, cp, None) == -1  # the limits pass ...
+    assert b"null pointer" in lib.amdrec_last_error()                                               # ... the nulls do not
+    assert lib.amdrec_topk_merge(None, None, 8, 96, 0, 0, 500, None, None, None) == 0               # nq = 0: nothing to do
+    assert lib.amdrec_topk_merge_partial(None, None, 8, 128, 96, 0, 0, 500, None, None, cp, None) == 0
+    assert cnt.value == 5
 
 
 def test_grouped_ivf_scan_refusals_match_the_recorded_table():
