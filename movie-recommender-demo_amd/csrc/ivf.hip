@@ -179,8 +179,8 @@ struct EpiIvfKeys {
 // with approx >= tau_lo[q] = tau[q] - eps_q is RE-SCORED in fp32 from the fp32 list row - one wave per row, one explicit
 // fma chain per lane and a fixed reduction order, so a row's score does not depend on which workgroup handled it - and
 // appended if that exact score passes tau.  The pool holds exact fp32 keys as before; nothing downstream changes.
-// Hits are collected per chunk of four accumulator rows in LDS (the staging area, free after the K loop; capacity = the
-// chunk's element count: no overflow path), then the workgroup's waves share them.
+// Hits of a whole tile are collected in one list in LDS (the staging area, free after the K loop), then the workgroup's
+// waves share them; a hit that finds the list full is re-scored by its own lane, in the same summation order (rescore1).
 struct EpiIvfPrefilter {
     static constexpr const char* name = "ivf_scan_bf16";
     static constexpr double out_bytes_per_elem = 0.0;
@@ -212,6 +212,32 @@ struct EpiIvfPrefilter {
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
         return part;
+    }
+    // the same score, bit for bit, by ONE lane.  Which nominations of a crowded tile miss the list is decided by a race for
+    // its slots, so the two must agree or a row's score would change from run to run.  rescore16's xor butterfly, seen from
+    // lane 0, is a balanced tree whose leaves in order are the sixteen chains in bit-reversed order: sum them pairwise with
+    // one pending value per level.  Kept a rolled loop: it is expanded once per accumulator element of the caller.
+    __device__ __forceinline__ float rescore1(long long row, long long q) const {
+        const f32x4* xr = reinterpret_cast<const f32x4*>(xs + row * ld);
+        const f32x4* qr = reinterpret_cast<const f32x4*>(Q + q * ldq);
+        float l1 = 0.f, l2 = 0.f, l4 = 0.f, l8 = 0.f, sum = 0.f;          // pending sums of 1, 2, 4, 8 chains
+#pragma clang loop unroll(disable)
+        for (int t = 0; t < 16; ++t) {
+            float v = 0.f;
+            for (int c = (int)(__brev((unsigned)t) >> 28); c < (d >> 2); c += 16) {
+                const f32x4 x = xr[c], y = qr[c];
+                v = fma4(x, y, v);
+            }
+            if (!(t & 1)) { l1 = v; continue; }
+            v = l1 + v;
+            if (!(t & 2)) { l2 = v; continue; }
+            v = l2 + v;
+            if (!(t & 4)) { l4 = v; continue; }
+            v = l4 + v;
+            if (!(t & 8)) { l8 = v; continue; }
+            sum = l8 + v;
+        }
+        return sum;
     }
     // the threshold is the k-th score of the first phase, computed by the fp32 MFMA; the re-score sums in another order
     // (1e-7-level differences): a slack towards KEEPING never costs exactness, the select decides
@@ -264,14 +290,7 @@ struct EpiIvfPrefilter {
                         if (slot < CAP) {
                             hits[slot] = ((unsigned long long)(uint32_t)qv[i][r] << 32) | (unsigned long long)rowq[j];
                         } else {
-                            const f32x4* xr = reinterpret_cast<const f32x4*>(xs + rowq[j] * ld);
-                            const f32x4* qr = reinterpret_cast<const f32x4*>(Q + (long long)qv[i][r] * ldq);
-                            float sc = 0.f;
-                            for (int c = 0; c < (d >> 2); ++c) {
-                                const f32x4 x = xr[c], y = qr[c];
-                                sc = fma4(x, y, sc);
-                            }
-                            keep(sc, rowq[j], qv[i][r]);
+                            keep(rescore1(rowq[j], qv[i][r]), rowq[j], qv[i][r]);
                         }
                     }
                 }

@@ -13,46 +13,9 @@ import pytest
 import torch
 
 from tests import cases
+from tests.guarded import GuardedArena, both_ways
 
 pytestmark = pytest.mark.gpu
-GUARD, FILL, GUARD_FILL = 4096, 0xA5, 0x3C
-
-
-class GuardedArena:
-    def __init__(self):
-        self.served = []            # (whole tensor, offset of the workspace, its bytes)
-
-    def get(self, nbytes, device):
-        nbytes = int(nbytes)
-        buf = torch.full((GUARD + 256 + nbytes + GUARD,), GUARD_FILL, dtype=torch.uint8, device=device)
-        off = GUARD + (-(buf.data_ptr() + GUARD)) % 256
-        buf[off:off + nbytes] = FILL
-        self.served.append((buf, off, nbytes))
-        ws = buf[off:off + nbytes]
-        assert ws.data_ptr() % 256 == 0 and ws.numel() == nbytes
-        return ws
-
-    def check(self, at_least=1):
-        torch.cuda.synchronize()
-        assert len(self.served) >= at_least
-        for buf, off, nbytes in self.served:
-            assert bool((buf[:off] == GUARD_FILL).all()), f"bytes below a {nbytes}-byte workspace were written"
-            assert bool((buf[off + nbytes:] == GUARD_FILL).all()), f"bytes above a {nbytes}-byte workspace were written"
-
-
-def both_ways(run):
-    """run() through the shared workspace, then inside guarded exact-size workspaces: equal outputs, intact guards."""
-    from amdrec import _lib
-    want = run()
-    torch.cuda.synchronize()
-    arena = GuardedArena()
-    with _lib.WORKSPACE.private(arena):
-        got = run()
-        arena.check()
-    assert len(got) == len(want)
-    for g, w in zip(got, want):
-        assert torch.equal(g, w)
-    return arena
 
 
 @pytest.fixture(scope="module")
