@@ -11,7 +11,7 @@ candidates, ad features gathered from a resident table by candidate id.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -57,6 +57,26 @@ class _Cross(nn.Module):
 def _head(d_model, dropout):
     return nn.Sequential(nn.Linear(d_model, 256), nn.ReLU(), nn.Dropout(dropout), nn.Linear(256, 64), nn.ReLU(),
                          nn.Dropout(dropout), nn.Linear(64, 1))
+
+
+class _Packed(NamedTuple):          # TransformerRanker._packed: the weights as packed under ``key`` (``_pack``)
+    key: Tuple
+    params: weights.RankerParams
+    keep: weights.Packed
+    tasks: List[str]
+
+
+class _AdCache(NamedTuple):         # TransformerRanker._ad_cache: one ad table's caches under the pack key they were built with
+    key: Tuple
+    data_ptr: int                   # data_ptr, shape, version: the table's ``_table_key``
+    shape: Tuple
+    version: int
+    proj: torch.Tensor
+    hidden: Optional[torch.Tensor]
+
+
+def _table_key(table):
+    return table.data_ptr(), tuple(table.shape), table._version
 
 
 class TransformerRanker(nn.Module):
@@ -162,7 +182,7 @@ class TransformerRanker(nn.Module):
         ws = _lib.WORKSPACE.get(4 * self.d_model + 256, dev)
         _lib.check(lib.amdrec_ranker_project_ads(_lib.C.byref(params), _lib.ptr(table), table.shape[0], _lib.ptr(out),
                                                  out.stride(0), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-        self._ad_cache = (self._packed[0], table.data_ptr(), tuple(table.shape), table._version, out, None)
+        self._ad_cache = _AdCache(self._packed.key, *_table_key(table), out, None)
         return out
 
     def ensure_ad_cache(self, ad_table):
@@ -170,10 +190,10 @@ class TransformerRanker(nn.Module):
         ``cache_first_ffn`` on weights packed for it, the first-FFN hidden cache P [N, d_ff] beside it while both fit
         ``hidden_cache_max_bytes``."""
         params, _ = self._pack(ad_table.device)
-        if self._cache_for(ad_table) is None:
+        if self._entry_for(ad_table) is None:
             self.cache_ad_projection(ad_table)
-        c = self._ad_cache
-        if c is None or c[5] is not None or not params.x3.w_hidden_ad or self._cache_for(ad_table) is None:
+        c = self._entry_for(ad_table)
+        if c is None or c.hidden is not None or not params.x3.w_hidden_ad:
             return
         n, d_ff = int(ad_table.shape[0]), int(params.d_ff)
         if n * (self.d_model + d_ff) * 4 > int(self.hidden_cache_max_bytes):
@@ -184,7 +204,7 @@ class TransformerRanker(nn.Module):
         _lib.check(_lib.load().amdrec_ranker_project_ads_hidden(
             _lib.C.byref(params), _lib.ptr(ad_table), n, _lib.ptr(hid), hid.stride(0), _lib.ptr(ws), ws.numel(),
             _lib.stream_ptr(dev)))
-        self._ad_cache = (*c[:5], hid)
+        self._ad_cache = c._replace(hidden=hid)
 
     def compact_ad_cache(self, old_table, kept, new_table):
         """Rows left the ad table: ``new_table`` = ``old_table[kept]`` (``kept``: device int64, old positions).  If a valid
@@ -196,12 +216,11 @@ class TransformerRanker(nn.Module):
         if not isinstance(old_table, torch.Tensor) or not old_table.is_cuda:
             return
         self._pack(old_table.device)
-        if self._cache_for(old_table) is None:
+        c = self._entry_for(old_table)
+        if c is None:
             return
-        c = self._ad_cache
-        proj = gather_rows(c[4], kept)
-        hid = None if c[5] is None else gather_rows(c[5], kept)
-        self._ad_cache = (c[0], new_table.data_ptr(), tuple(new_table.shape), new_table._version, proj, hid)
+        hid = None if c.hidden is None else gather_rows(c.hidden, kept)
+        self._ad_cache = _AdCache(c.key, *_table_key(new_table), gather_rows(c.proj, kept), hid)
 
     def extend_ad_cache(self, old_table, new_table):
         """Rows were appended to the ad table: ``new_table[:len(old_table)]`` equals ``old_table``.  If a valid cache exists
@@ -213,18 +232,18 @@ class TransformerRanker(nn.Module):
             return
         dev = old_table.device
         params, _ = self._pack(dev)
-        if self._cache_for(old_table) is None:
+        c = self._entry_for(old_table)
+        if c is None:
             return
         n_old, n_new = int(old_table.shape[0]), int(new_table.shape[0])
         if n_new < n_old or not new_table.is_contiguous() or new_table.shape[1:] != old_table.shape[1:]:
             raise ValueError("extend_ad_cache: new_table must be old_table plus appended rows, contiguous")
-        c = self._ad_cache
         lib = _lib.load()
         tail = new_table[n_old:]
-        proj = grown_copy(c[4], n_old, n_new)
+        proj = grown_copy(c.proj, n_old, n_new)
         hid = None
-        if c[5] is not None and n_new * (self.d_model + int(params.d_ff)) * 4 <= int(self.hidden_cache_max_bytes):
-            hid = grown_copy(c[5], n_old, n_new)
+        if c.hidden is not None and n_new * (self.d_model + int(params.d_ff)) * 4 <= int(self.hidden_cache_max_bytes):
+            hid = grown_copy(c.hidden, n_old, n_new)
         if n_new > n_old:
             ws = _lib.WORKSPACE.get(4 * max(self.d_model, int(params.d_ff)) + 256, dev)
             out = proj[n_old:]
@@ -235,19 +254,22 @@ class TransformerRanker(nn.Module):
                 _lib.check(lib.amdrec_ranker_project_ads_hidden(
                     _lib.C.byref(params), _lib.ptr(tail), n_new - n_old, _lib.ptr(out), hid.stride(0), _lib.ptr(ws),
                     ws.numel(), _lib.stream_ptr(dev)))
-        self._ad_cache = (c[0], new_table.data_ptr(), tuple(new_table.shape), new_table._version, proj, hid)
+        self._ad_cache = _AdCache(c.key, *_table_key(new_table), proj, hid)
+
+    def _entry_for(self, table) -> Optional[_AdCache]:
+        """The cache entry valid for ``table`` - built under the current pack key for this very tensor (same data_ptr, shape
+        and _version) - or None."""
+        c = getattr(self, "_ad_cache", None)
+        if c is None or self._packed is None or c.key != self._packed.key or c[1:4] != _table_key(table):
+            return None
+        return c
+
+    def _cache_for(self, table):
+        return getattr(self._entry_for(table), "proj", None)
 
     def _hidden_cache_for(self, table):
         """The first-FFN hidden cache that goes with ``_cache_for(table)`` (None: not built)."""
-        return self._ad_cache[5] if self._cache_for(table) is not None else None
-
-    def _cache_for(self, table):
-        c = getattr(self, "_ad_cache", None)
-        if c is None or self._packed is None:
-            return None
-        if c[0] != self._packed[0] or c[1] != table.data_ptr() or c[2] != tuple(table.shape) or c[3] != table._version:
-            return None
-        return c[4]
+        return getattr(self._entry_for(table), "hidden", None)
 
     def _pack(self, device):
         if self.gemm_engine not in self.ENGINES:
@@ -257,7 +279,7 @@ class TransformerRanker(nn.Module):
         key = (str(device), self.fuse_attention, bool(self.fold_first_attention), bool(self.cache_first_ffn),
                self.gemm_engine, int(self.x3_min_rows), int(self.x3_variant), int(self.x3_cs_max_rows),
                _lib.tensor_versions(self))
-        if self._packed is None or self._packed[0] != key:
+        if self._packed is None or self._packed.key != key:
             sd = self.state_dict()
             why = weights.x3_ineligible_reason(sd, self.fuse_attention) if self.gemm_engine == "f16x3" else None
             x3 = self.gemm_engine == "f16x3" and why is None
@@ -266,16 +288,12 @@ class TransformerRanker(nn.Module):
                 warnings.warn(f"amdrec TransformerRanker: gemm_engine 'f16x3' is not available for these weights ({why}); "
                               f"running the generic tile GEMMs (bf16x6 above {self.SMALL_ROWS} rows, fp32 MFMA below)",
                               RuntimeWarning, stacklevel=3)
-            params, keep, tasks = weights.pack_ranker(sd, self._user_names, self._ad_names,
-                                                      self._n_num, device, fuse_attention=self.fuse_attention,
-                                                      x6=self.gemm_engine == "bf16x6" or
-                                                      (self.gemm_engine == "f16x3" and not x3),
-                                                      x3=x3, x3_min_rows=self.x3_min_rows, x3_variant=self.x3_variant,
-                                                      x3_cs_max_rows=self.x3_cs_max_rows,
-                                                      fold_first_attention=bool(self.fold_first_attention),
-                                                      cache_first_ffn=bool(self.cache_first_ffn))
-            self._packed = (key, params, keep, tasks)
-        return self._packed[1], self._packed[3]
+            self._packed = _Packed(key, *weights.pack_ranker(
+                sd, self._user_names, self._ad_names, self._n_num, device, fuse_attention=self.fuse_attention,
+                x6=self.gemm_engine == "bf16x6" or (self.gemm_engine == "f16x3" and not x3), x3=x3,
+                x3_min_rows=self.x3_min_rows, x3_variant=self.x3_variant, x3_cs_max_rows=self.x3_cs_max_rows,
+                fold_first_attention=bool(self.fold_first_attention), cache_first_ffn=bool(self.cache_first_ffn)))
+        return self._packed.params, self._packed.tasks
 
     def load_state_dict(self, state_dict, *a, **k):
         r = super().load_state_dict(state_dict, *a, **k)

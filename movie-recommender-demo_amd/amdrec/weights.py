@@ -5,7 +5,7 @@ include/amdrec.h.  Runs once per weight load (float64 on the host, rounded to fl
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List
+from typing import Dict, List, NamedTuple
 
 import numpy as np
 import torch
@@ -282,49 +282,60 @@ def x3c_stream_heads(f1, f2s, tiles_per_task):
     return np.stack(out)
 
 
+# stream kind -> the order in which its kernel reads the fragment sets of (a 256 x 256 GEMM, a cross layer, an FFN, the heads);
+# the hidden-cache stream (amdrec_x3_weights.stream_hc) is kind 16 with layer 1's FFN as x3b_stream_ffn_stage2
+_X3_ORDER = {32: (x3_stream_gemm256, x3_stream_gemm256, x3_stream_ffn, x3_stream_heads),
+             16: (x3b_stream_gemm256, x3b_stream_cross, x3b_stream_ffn, x3b_stream_heads),
+             "16cs": (x3c_stream_gemm256, x3c_stream_gemm256, x3c_stream_ffn, x3c_stream_heads)}
+
+
+def x3_split(mats: Dict, variant: int = 32, fold_first: bool = False):
+    """Scale and plane-split every matrix of ``mats`` (see ``pack_x3_stream``) once -> (fragments {"ov", "w1", "w2", "cross":
+    lists, "h1", "h2", "tiles"}, scales and hidden bounds of amdrec_x3_weights).  Kinds 16 and "16cs" share the fragments of
+    variant 16.  ``fold_first``: layer 1's W_ov is not split (its fragments are None, its scale reads 1.0)."""
+    frags = x3_frags if variant == 32 else x3b_frags
+    fr, sc = {"tiles": mats["h1"].shape[0] // len(mats["h2"]) // 32}, {}
+    for name, dst in (("ov", "sw_ov"), ("w1", "sw_1"), ("w2", "sw_2"), ("cross", "sw_cross")):
+        ws = [None if name == "ov" and fold_first and l == 0 else w for l, w in enumerate(mats[name])]
+        sc[dst] = [1.0 if w is None else x3_pow2_scale(np.abs(w).max()) for w in ws]
+        fr[name] = [None if w is None else frags(w, s) for w, s in zip(ws, sc[dst])]
+    sc["sw_h1"] = x3_pow2_scale(np.abs(mats["h1"]).max())
+    sc["sw_h2"] = x3_pow2_scale(max(np.abs(w).max() for w in mats["h2"]))
+    fr["h1"], fr["h2"] = frags(mats["h1"], sc["sw_h1"]), [frags(w, sc["sw_h2"]) for w in mats["h2"]]
+    # |relu(w_j . x + b_j)| <= ||w_j||_2 ||x||_2 + |b_j| <= (16 max_j ||w_j||_2) max|x| + max_j |b_j|
+    hn = lambda w: float(16.0 * np.linalg.norm(w, axis=1).max() * (1 + 1e-6))     # noqa: E731
+    sc["hn"], sc["hb"] = [hn(w) for w in mats["w1"]], [float(np.abs(b).max()) for b in mats["b1"]]
+    sc["hn_head"], sc["hb_head"] = hn(mats["h1"]), float(np.abs(mats["hb1"]).max())
+    return fr, sc
+
+
+def x3_order(fr: Dict, kind, cache_first_ffn: bool = False) -> np.ndarray:
+    """The fragments of ``x3_split`` in the order stream ``kind`` (32, 16, "16cs") is read -> uint16 [n_frag][64][8]."""
+    s_gemm, s_cross, s_ffn, s_heads = _X3_ORDER[kind]
+    parts = []
+    for l, (ov, f1, f2) in enumerate(zip(fr["ov"], fr["w1"], fr["w2"])):
+        parts += [] if ov is None else [s_gemm(ov)]
+        parts.append(x3b_stream_ffn_stage2(f2) if cache_first_ffn and l == 0 else s_ffn(f1, f2))
+    parts += [s_cross(f) for f in fr["cross"]]
+    parts.append(s_heads(fr["h1"], fr["h2"], fr["tiles"]))
+    stream = np.concatenate(parts)
+    assert stream.shape[0] % 16 == 0
+    return stream
+
+
 def pack_x3_stream(mats: Dict, variant: int = 32, fold_first: bool = False, cache_first_ffn: bool = False) -> Dict:
     """mats: float64 matrices of the chain {"ov": [L x [256][256]], "w1": [L x [d_ff][256]], "b1": [L x [d_ff]], "w2":
     [L x [256][d_ff]], "cross": [C x [256][256] (already [out][in])], "h1": [T*h1][256], "hb1": [T*h1], "h2": [T x
-    [64][h1]]} -> {"stream": uint16 [n_frag][64][8], "chunks", scales and hidden bounds} for amdrec_x3_weights.
+    [64][h1]]} -> {"stream": uint16 [n_frag][64][8], "chunks", scales and hidden bounds} for amdrec_x3_weights: one
+    ``x3_split`` in one ``x3_order`` (pack_ranker orders ONE split up to three ways).
     ``fold_first``: layer 1's attention block is folded into the projection (amdrec_x3_weights.fold_attn1): its W_ov is
     not packed (mats["ov"][0] is not read; its scale reads 1.0).  ``cache_first_ffn`` (variant 16 with ``fold_first``):
     layer 1's stage-1 fragment sets are left out too (amdrec_x3_weights.stream_hc); every scale and bound stays."""
-    assert variant in (16, 32, "16cs")
-    assert not cache_first_ffn or (variant == 16 and fold_first)                  # "16cs": the 16-row fragments in the column-split kernel's order
-    frags, s_gemm, s_ffn, s_heads = {32: (x3_frags, x3_stream_gemm256, x3_stream_ffn, x3_stream_heads),
-                                     16: (x3b_frags, x3b_stream_gemm256, x3b_stream_ffn, x3b_stream_heads),
-                                     "16cs": (x3b_frags, x3c_stream_gemm256, x3c_stream_ffn, x3c_stream_heads)}[variant]
-    s_cross = x3b_stream_cross if variant == 16 else s_gemm
-    parts = []
-    sc = {"sw_ov": [], "sw_1": [], "sw_2": [], "hn": [], "hb": [], "sw_cross": []}
-    for l in range(len(mats["ov"])):
-        s_ov = 1.0
-        if not (fold_first and l == 0):
-            s_ov = x3_pow2_scale(np.abs(mats["ov"][l]).max())
-            parts.append(s_gemm(frags(mats["ov"][l], s_ov)))
-        s1, s2 = x3_pow2_scale(np.abs(mats["w1"][l]).max()), x3_pow2_scale(np.abs(mats["w2"][l]).max())
-        if cache_first_ffn and l == 0:
-            parts.append(x3b_stream_ffn_stage2(frags(mats["w2"][l], s2)))
-        else:
-            parts.append(s_ffn(frags(mats["w1"][l], s1), frags(mats["w2"][l], s2)))
-        sc["sw_ov"].append(s_ov); sc["sw_1"].append(s1); sc["sw_2"].append(s2)
-        # |relu(w_j . x + b_j)| <= ||w_j||_2 ||x||_2 + |b_j| <= (16 max_j ||w_j||_2) max|x| + max_j |b_j|
-        sc["hn"].append(float(16.0 * np.linalg.norm(mats["w1"][l], axis=1).max() * (1 + 1e-6)))
-        sc["hb"].append(float(np.abs(mats["b1"][l]).max()))
-    for w in mats["cross"]:
-        s = x3_pow2_scale(np.abs(w).max())
-        parts.append(s_cross(frags(w, s)))
-        sc["sw_cross"].append(s)
-    sh1 = x3_pow2_scale(np.abs(mats["h1"]).max())
-    sh2 = x3_pow2_scale(max(np.abs(w).max() for w in mats["h2"]))
-    n_tasks = len(mats["h2"])
-    tiles = mats["h1"].shape[0] // n_tasks // 32
-    parts.append(s_heads(frags(mats["h1"], sh1), [frags(w, sh2) for w in mats["h2"]], tiles))
-    stream = np.concatenate(parts)
-    assert stream.shape[0] % 16 == 0
-    return {"stream": stream, "chunks": stream.shape[0] // 16, "sw_h1": sh1, "sw_h2": sh2,
-            "hn_head": float(16.0 * np.linalg.norm(mats["h1"], axis=1).max() * (1 + 1e-6)),
-            "hb_head": float(np.abs(mats["hb1"]).max()), **sc}
+    assert variant in (16, 32, "16cs")                       # "16cs": the 16-row fragments in the column-split kernel's order
+    assert not cache_first_ffn or (variant == 16 and fold_first)
+    fr, sc = x3_split(mats, variant, fold_first)
+    stream = x3_order(fr, variant, cache_first_ffn)
+    return {"stream": stream, "chunks": stream.shape[0] // 16, **sc}
 
 
 X3_PARAM_FLOATS = 11264     # LDS parameter area of the kernel (csrc/x3_common.hpp PARAM_FLOATS)
@@ -343,18 +354,12 @@ def pack_x3_params(layers: List[Dict], cross_b: List, head_b1, heads: List[Dict]
     for h in heads:
         parts += [h["b2"], h["w3"], np.concatenate([np.asarray(h["b3"], dtype=np.float64).reshape(-1), np.zeros(3)])]
     blob = np.concatenate([np.asarray(a, dtype=np.float64).reshape(-1) for a in parts]).astype(np.float32)
-    n = (len(blob) + 1023) // 1024 * 1024
-    out = np.zeros(n, dtype=np.float32)
-    out[:len(blob)] = blob
-    return out
+    return np.pad(blob, (0, -len(blob) % 1024))
 
 
 def _pad_k(w64, mult=32):
-    out_f, k = w64.shape
-    ld = (k + mult - 1) // mult * mult
-    w = np.zeros((out_f, ld), dtype=np.float32)
-    w[:, :k] = w64.astype(np.float32)
-    return w, ld
+    w = np.pad(w64.astype(np.float32), ((0, 0), (0, -w64.shape[1] % mult)))
+    return w, w.shape[1]
 
 
 class Packed:
@@ -364,25 +369,30 @@ class Packed:
         self.device = torch.device(device)
         self._keep: List[torch.Tensor] = []
 
-    def dev(self, arr, dtype=None):
-        t = torch.from_numpy(np.ascontiguousarray(arr))
-        if dtype is not None:
-            t = t.to(dtype)
-        t = t.to(self.device)
+    def ptr(self, arr):
+        t = torch.from_numpy(np.ascontiguousarray(arr)).to(self.device)
         assert t.data_ptr() % 16 == 0
         self._keep.append(t)
-        return t
+        return C.c_void_p(t.data_ptr())
 
-    def ptr(self, arr, dtype=None):
-        return C.c_void_p(self.dev(arr, dtype).data_ptr())
+    def vec(self, v64):
+        return self.ptr(v64.astype(np.float32))
+
+    def mat(self, w64, x6: bool = False):
+        """float64 [out][K] -> pointer to the fp32 matrix (K zero-padded to 32), its leading dimension, pointer to its x6 planes"""
+        w, ld = _pad_k(w64)
+        return self.ptr(w), ld, (self.ptr(split_planes(w)) if x6 else None)
 
 
-def pack_tables(pk: Packed, tables: List, emb_dim: int):
+def pack_tables(pk: Packed, tables: List):
+    emb_dim = int(tables[0].shape[1])
+    if emb_dim < 4 or emb_dim & (emb_dim - 1):
+        raise ValueError("embedding_dim must be a power of two >= 4 for the fused gather")
     cards = [int(t.shape[0]) for t in tables]
     off = np.concatenate([[0], np.cumsum(cards)[:-1]]).astype(np.int32)
     cat = np.concatenate([_np64(t).astype(np.float32) for t in tables], axis=0)
     assert cat.shape[1] == emb_dim
-    return pk.ptr(cat), pk.ptr(off), pk.ptr(np.asarray(cards, dtype=np.int32)), cards
+    return pk.ptr(cat), pk.ptr(off), pk.ptr(np.asarray(cards, dtype=np.int32)), emb_dim
 
 
 def pack_tower(sd: Dict, prefix: str, feature_names: List[str], n_num: int, device, bn_eps=1e-5):
@@ -390,12 +400,9 @@ def pack_tower(sd: Dict, prefix: str, feature_names: List[str], n_num: int, devi
     ``prefix`` ('user_tower' / 'ad_tower').  -> (TowerParams, Packed)"""
     pk = Packed(device)
     tables = [sd[f"{prefix}.embedding_layer.embeddings.{n}.weight"] for n in feature_names]
-    emb_dim = int(tables[0].shape[1])
-    if emb_dim < 4 or emb_dim & (emb_dim - 1):
-        raise ValueError("embedding_dim must be a power of two >= 4 for the fused gather")
     p = TowerParams()
+    p.tables, p.table_off, p.cards, emb_dim = pack_tables(pk, tables)
     p.n_feat, p.emb_dim, p.n_num = len(tables), emb_dim, n_num
-    p.tables, p.table_off, p.cards, _ = pack_tables(pk, tables, emb_dim)
     p.dims[0] = len(tables) * emb_dim + n_num
     idx, l = 0, 0
     while f"{prefix}.mlp.{idx}.weight" in sd:
@@ -416,8 +423,8 @@ def pack_tower(sd: Dict, prefix: str, feature_names: List[str], n_num: int, devi
             raise ValueError("too many layers")
         if w.shape[0] % 4:
             raise ValueError("layer widths must be multiples of 4")
-        wp, ld = _pad_k(w)
-        p.w[l], p.b[l], p.ldw[l], p.dims[l + 1] = pk.ptr(wp), pk.ptr(b.astype(np.float32)), ld, w.shape[0]
+        p.w[l], p.ldw[l], _ = pk.mat(w)
+        p.b[l], p.dims[l + 1] = pk.vec(b), w.shape[0]
         l += 1
     p.n_layers = l
     return p, pk
@@ -434,25 +441,22 @@ def x3_ineligible_reason(sd: Dict, fuse_attention: bool):
     dm = int(sd["feature_projection.weight"].shape[0])
     if dm != 256:
         return f"d_model {dm} != 256"
-    l = 0
-    while f"transformer_layers.{l}.norm1.weight" in sd:
-        dff = int(sd[f"transformer_layers.{l}.feed_forward.fc1.weight"].shape[0])
-        if dff % 32:
-            return f"d_ff {dff} is not a multiple of 32"
-        l += 1
-    c = 0
+    dff, c = [], 0
+    while f"transformer_layers.{len(dff)}.norm1.weight" in sd:
+        dff.append(int(sd[f"transformer_layers.{len(dff)}.feed_forward.fc1.weight"].shape[0]))
+        if dff[-1] % 32:
+            return f"d_ff {dff[-1]} is not a multiple of 32"
     while f"feature_interaction.cross_weights.{c}" in sd:
         c += 1
     tasks = [t for t in TASKS if f"prediction_heads.{t}.0.weight" in sd]
     if not tasks or len(tasks) > MAX_TASKS:
         return f"{len(tasks)} prediction heads (1 .. {MAX_TASKS} supported)"
-    if 2 * l + c + 1 > 20:
-        return f"{2 * l + c + 1} phases (at most 20)"
+    if 2 * len(dff) + c + 1 > 20:
+        return f"{2 * len(dff) + c + 1} phases (at most 20)"
     h1 = int(sd[f"prediction_heads.{tasks[0]}.0.weight"].shape[0])
     h2 = int(sd[f"prediction_heads.{tasks[0]}.3.weight"].shape[0])
     if h1 % 32 or h2 != 64:
         return f"head widths {h1} -> {h2} (multiple of 32 -> 64 supported)"
-    dff = [int(sd[f"transformer_layers.{i}.feed_forward.fc1.weight"].shape[0]) for i in range(l)]
     n_par = sum(6 * 256 + d for d in dff) + 256 * c + len(tasks) * (h1 + 132)
     if (n_par + 1023) // 1024 * 1024 > X3_PARAM_FLOATS:
         return f"{n_par} bias / LayerNorm parameters exceed the kernel's LDS parameter area ({X3_PARAM_FLOATS})"
@@ -463,20 +467,66 @@ def x3_eligible(sd: Dict, fuse_attention: bool) -> bool:
     return x3_ineligible_reason(sd, fuse_attention) is None
 
 
+def x3c_available(p) -> bool:             # stream_cs is packed for: the architecture part of csrc/ranker_x3.hip x3c_available
+    return p.x3.variant == 16 and (p.n_layers == 0 or p.d_ff % 128 == 0) and p.head_h1 % 128 == 0
+
+
+def x3_hidden_cache(p) -> bool:           # stream_hc ... are packed for: the per-pack part of csrc/ranker_x3.hip x3_hidden_cache
+    return bool(p.x3.fold_attn1 and p.x3.variant == 16 and p.w_proj_user and p.d_ff % 64 == 0)
+
+
+# the reference TransformerRanker's eval-mode chain at seq_len 1, in float64 (fields: ``ranker_chain``)
+RankerChain = NamedTuple("RankerChain", [("w_proj", np.ndarray), ("b_proj", np.ndarray), ("layers", List[Dict]), ("cross_wt", List),
+                                         ("cross_b", List), ("head_w1", np.ndarray), ("head_b1", np.ndarray), ("heads", List[Dict]),
+                                         ("tasks", List[str])])
+_LAYER_KEYS = (("wv", "self_attention.W_v.weight"), ("bv", "self_attention.W_v.bias"), ("wo", "self_attention.W_o.weight"),
+               ("bo", "self_attention.W_o.bias"), ("w1", "feed_forward.fc1.weight"), ("b1", "feed_forward.fc1.bias"),
+               ("w2", "feed_forward.fc2.weight"), ("b2", "feed_forward.fc2.bias"), ("g1", "norm1.weight"),
+               ("be1", "norm1.bias"), ("g2", "norm2.weight"), ("be2", "norm2.bias"))
+
+
+def ranker_chain(sd) -> RankerChain:
+    """The one reader of the reference's state dict (torch tensors or numpy): what pack_ranker, the x3 packers,
+    ``folded_projection`` and ``first_ffn_cache`` multiply with (a RankerChain passes through, so those two take either).
+    w_proj [d_model][K], b_proj = bias + positional_encoding[0, 0] (only row 0 is ever read, :361); per encoder layer wv bv wo
+    bo w1 b1 w2 b2 g1 be1 g2 be2 and wov = W_o W_v, b_ov = W_o b_v + b_o (the seq-len-1 attention is exactly W_o (W_v x +
+    b_v) + b_o, transformer_ranker.py:59-88 with :358); per cross layer W^T ([out][in]: xl @ W == xl (W^T)^T) and bias; layer
+    1 of all heads stacked [T * h1][d_model]; per task w2 [h2][h1], b2, w3 [h2], b3 [1]."""
+    if isinstance(sd, RankerChain):
+        return sd
+    layers, n_cross = [], 0
+    while f"transformer_layers.{len(layers)}.norm1.weight" in sd:
+        L = {dst: _np64(sd[f"transformer_layers.{len(layers)}.{src}"]) for dst, src in _LAYER_KEYS}
+        L["wov"], L["b_ov"] = L["wo"] @ L["wv"], L["wo"] @ L["bv"] + L["bo"]
+        layers.append(L)
+    while f"feature_interaction.cross_weights.{n_cross}" in sd:
+        n_cross += 1
+    tasks = [t for t in TASKS if f"prediction_heads.{t}.0.weight" in sd]
+    head = lambda t, k: _np64(sd[f"prediction_heads.{t}.{k}"])     # noqa: E731
+    return RankerChain(
+        _np64(sd["feature_projection.weight"]), _np64(sd["feature_projection.bias"]) + _np64(sd["positional_encoding"])[0, 0],
+        layers, [_np64(sd[f"feature_interaction.cross_weights.{c}"]).T for c in range(n_cross)],
+        [_np64(sd[f"feature_interaction.cross_biases.{c}"]) for c in range(n_cross)],
+        np.concatenate([head(t, "0.weight") for t in tasks], axis=0), np.concatenate([head(t, "0.bias") for t in tasks], axis=0),
+        [{"w2": head(t, "3.weight"), "b2": head(t, "3.bias"), "w3": head(t, "6.weight").reshape(-1),
+          "b3": head(t, "6.bias").reshape(-1)} for t in tasks], tasks)
+
+
+def _user_ad_columns(w, nu: int, na: int):
+    """Projection-like [out][user emb | ad emb | numerical] -> its ([user emb | numerical], [ad emb]) column blocks."""
+    return np.concatenate([w[:, :nu], w[:, nu + na:]], axis=1), w[:, nu:nu + na]
+
+
 def folded_projection(sd: Dict):
     """float64 (W_p', b_p') of the feature projection with encoder layer 1's attention block folded in.  At seq_len 1
     everything of layer 1 before its first LayerNorm is linear in the projection output x0 = W_p f + b_p (b_p incl.
     pos[0]): z = x0 + W_ov x0 + b_ov = (I + W_ov) W_p f + (I + W_ov) b_p + b_ov, W_ov = W_o W_v, b_ov = W_o b_v + b_o."""
-    wp = _np64(sd["feature_projection.weight"])
-    bp = _np64(sd["feature_projection.bias"]) + _np64(sd["positional_encoding"])[0, 0]
-    pre = "transformer_layers.0.self_attention"
-    wv, bv = _np64(sd[f"{pre}.W_v.weight"]), _np64(sd[f"{pre}.W_v.bias"])
-    wo, bo = _np64(sd[f"{pre}.W_o.weight"]), _np64(sd[f"{pre}.W_o.bias"])
-    wov = wo @ wv
-    return wp + wov @ wp, bp + wov @ bp + (wo @ bv + bo)
+    ch = ranker_chain(sd)
+    L = ch.layers[0]
+    return ch.w_proj + L["wov"] @ ch.w_proj, ch.b_proj + L["wov"] @ ch.b_proj + L["b_ov"]
 
 
-def first_ffn_cache(sd: Dict, n_user_cols: int, n_ad_cols: int, ln_eps: float = 1e-5) -> Dict:
+def first_ffn_cache(sd: Dict, n_user_cols: int, n_ad_cols: int, ln_eps: float = 1e-5, folded=None) -> Dict:
     """float64 algebra of the first-FFN hidden cache (amdrec_x3_weights.stream_hc).  With layer 1's attention folded the
     chain starts with x1 = LN1(z), z = a_ad + u_user (the two halves of ``folded_projection``), and stage 1 of layer 1's
     FFN is linear in z once the row's deviation is known:
@@ -487,18 +537,67 @@ def first_ffn_cache(sd: Dict, n_user_cols: int, n_ad_cols: int, ln_eps: float = 
     subtracted: W_1c annihilates the constant vector).  W_1 is the fp32-rounded matrix the engines multiply with.
     -> {"w1c", "c", "w_ad" = W_1c W_p'[:, ad columns], "w_user" = W_1c W_p'[:, user | numerical columns],
         "b" = W_1c b_p'}: the stacked matrices produce P[ad] = w_ad . emb(ad) and Q[user] = w_user . f_user + b straight
-    from the embeddings, composed in float64 (no second fp32 rounding through the cached a_ad)."""
-    pre = "transformer_layers.0"
-    w1 = _np64(sd[f"{pre}.feed_forward.fc1.weight"]).astype(np.float32).astype(np.float64)
-    b1 = _np64(sd[f"{pre}.feed_forward.fc1.bias"])
-    g1, be1 = _np64(sd[f"{pre}.norm1.weight"]), _np64(sd[f"{pre}.norm1.bias"])
-    w1g = w1 * g1[None, :]
+    from the embeddings, composed in float64 (no second fp32 rounding through the cached a_ad).
+    ``folded``: the ``folded_projection`` where the caller already has it."""
+    ch = ranker_chain(sd)
+    L = ch.layers[0]
+    w1 = L["w1"].astype(np.float32).astype(np.float64)
+    w1g = w1 * L["g1"][None, :]
     w1c = w1g - w1g.mean(axis=1, keepdims=True)
-    c = w1 @ be1 + b1
-    wp, bp = folded_projection(sd)
-    nu, na = n_user_cols, n_ad_cols
-    return {"w1c": w1c, "c": c, "w_ad": w1c @ wp[:, nu:nu + na],
-            "w_user": w1c @ np.concatenate([wp[:, :nu], wp[:, nu + na:]], axis=1), "b": w1c @ bp, "ln_eps": ln_eps}
+    wp, bp = folded_projection(ch) if folded is None else folded
+    w_user, w_ad = _user_ad_columns(wp, n_user_cols, n_ad_cols)
+    return {"w1c": w1c, "c": w1 @ L["be1"] + L["b1"], "w_ad": w1c @ w_ad, "w_user": w1c @ w_user, "b": w1c @ bp, "ln_eps": ln_eps}
+
+
+def _pack_encoder_layer(L, pk: Packed, c: Dict, fuse_attention: bool, x6: bool):
+    if fuse_attention:
+        L.w_v, L.b_v = None, None
+        L.w_o, L.ldw_dm, L.w_o_x6 = pk.mat(c["wov"], x6)
+    else:
+        L.b_v = pk.vec(c["bv"])
+        L.w_v, L.ldw_dm, _ = pk.mat(c["wv"])
+        L.w_o, L.ldw_dm, L.w_o_x6 = pk.mat(c["wo"], x6)
+    L.w_1, L.ldw_dm, L.w_1_x6 = pk.mat(c["w1"], x6)
+    L.b_o = pk.vec(c["b_ov"] if fuse_attention else c["bo"])
+    L.w_2, L.ldw_ff, L.w_2_x6 = pk.mat(c["w2"], x6)
+    for dst, src in (("b_1", "b1"), ("b_2", "b2"), ("ln1_g", "g1"), ("ln1_b", "be1"), ("ln2_g", "g2"), ("ln2_b", "be2")):
+        setattr(L, dst, pk.vec(c[src]))
+
+
+def _pack_x3(p: RankerParams, pk: Packed, ch: RankerChain, wproj, bproj, nu: int, na: int, cache_first_ffn: bool):
+    """p.x3 (its variant, fold_attn1, min_rows and cs_max_rows are set): the SAME fp32-rounded matrices the other engines
+    multiply with, split into fp16 planes once and laid out in the order of every stream this packing serves."""
+    f32 = lambda a: a.astype(np.float32).astype(np.float64)   # noqa: E731
+    fold = bool(p.x3.fold_attn1)
+    mats = {"ov": [f32(L["wov"]) for L in ch.layers], "w1": [f32(L["w1"]) for L in ch.layers],
+            "b1": [f32(L["b1"]) for L in ch.layers], "w2": [f32(L["w2"]) for L in ch.layers],
+            "cross": [f32(w) for w in ch.cross_wt], "h1": f32(ch.head_w1), "hb1": f32(ch.head_b1),
+            "h2": [f32(h["w2"]) for h in ch.heads]}
+    fr, sc = x3_split(mats, p.x3.variant, fold)
+
+    def stream(kind, **kw):
+        s = x3_order(fr, kind, **kw)
+        return pk.ptr(s.view(np.int16)), s.shape[0] // 16
+    blob = pack_x3_params(ch.layers, ch.cross_b, ch.head_b1, ch.heads, fold_first=fold)
+    assert len(blob) <= X3_PARAM_FLOATS
+    p.x3.params, p.x3.n_params = pk.ptr(blob), len(blob)
+    p.x3.stream, p.x3.chunks = stream(p.x3.variant)
+    if p.x3.cs_max_rows >= 0 and x3c_available(p):
+        p.x3.stream_cs, p.x3.chunks_cs = stream("16cs")         # the same fragments in the column-split kernel's chunk order
+    if cache_first_ffn and x3_hidden_cache(p):
+        hc = first_ffn_cache(ch, nu, na, folded=(wproj, bproj))
+        p.x3.stream_hc, p.x3.chunks_hc = stream(16, cache_first_ffn=True)
+        blob_hc = blob.copy()                                   # folded layout: [gamma1 | beta1 | b_1 ...] - c in b_1's place
+        blob_hc[512:512 + len(hc["c"])] = hc["c"].astype(np.float32)
+        p.x3.params_hc = pk.ptr(blob_hc)
+        p.x3.w_user_uq, ldu, _ = pk.mat(np.concatenate([_user_ad_columns(wproj, nu, na)[0], hc["w_user"]]))
+        p.x3.b_user_uq = pk.vec(np.concatenate([bproj, hc["b"]]))
+        p.x3.w_hidden_ad, lda, _ = pk.mat(hc["w_ad"])
+        assert ldu == p.ldw_proj_user and lda == p.ldw_proj_ad
+    for dst in ("sw_ov", "sw_1", "sw_2", "hn", "hb", "sw_cross"):
+        for i, v in enumerate(sc[dst]):
+            getattr(p.x3, dst)[i] = v
+    p.x3.sw_h1, p.x3.sw_h2, p.x3.hn_head, p.x3.hb_head = sc["sw_h1"], sc["sw_h2"], sc["hn_head"], sc["hb_head"]
 
 
 def pack_ranker(sd: Dict, user_names: List[str], ad_names: List[str], n_num: int, device, ln_eps=1e-5,
@@ -506,171 +605,52 @@ def pack_ranker(sd: Dict, user_names: List[str], ad_names: List[str], n_num: int
                 x3_variant: int = 32, x3_cs_max_rows: int = 0, fold_first_attention: bool = False,
                 cache_first_ffn: bool = False):
     """state_dict-like of the reference TransformerRanker -> (RankerParams, Packed, task names).
-    ``fuse_attention``: pre-multiply W_ov = W_o W_v, b_ov = W_o b_v + b_o in float64 (the seq-len-1
-    attention is exactly W_o(W_v x + b_v) + b_o, transformer_ranker.py:59-88 with :358), so each
-    encoder layer's attention block is one GEMM instead of two.
-    ``x6``: also upload the bf16 split planes of the big weight matrices (W_ov / W_o, fc1, fc2, cross, stacked head
-    layer 1) so that passes of more than 8192 rows run on the error-compensated bf16-MFMA GEMM.
-    ``fold_first_attention``: when every pass runs the row-owner engine (x3 packed, x3_min_rows == 1, at least one
-    encoder layer), pack the projection as ``folded_projection`` (rounded once to fp32) and the engine's chain without
-    layer 1's W_ov / b_ov (amdrec_x3_weights.fold_attn1); otherwise it has no effect.
+    ``fuse_attention``: pre-multiply W_ov = W_o W_v, b_ov = W_o b_v + b_o in float64 (``ranker_chain``), so each encoder layer's
+    attention block is one GEMM instead of two.
+    ``x6``: also upload the bf16 split planes of the big weight matrices (W_ov / W_o, fc1, fc2, cross, stacked head layer 1) so
+    that passes of more than 8192 rows run on the error-compensated bf16-MFMA GEMM.
+    ``x3``: also pack the row-owner engine's streams where ``x3_ineligible_reason`` is None (else it has no effect).
+    ``fold_first_attention``: when every pass runs the row-owner engine (x3 packed, x3_min_rows == 1, at least one encoder
+    layer), pack the projection as ``folded_projection`` (rounded once to fp32) and the engine's chain without layer 1's
+    W_ov / b_ov (amdrec_x3_weights.fold_attn1); otherwise it has no effect.
     ``cache_first_ffn``: with the fold on the 16-row kernel, also pack what the first-FFN hidden cache needs (``first_ffn_cache``;
     amdrec_x3_weights.stream_hc ...); otherwise it has no effect."""
     pk = Packed(device)
     tables = [sd[f"user_embeddings.{n}.weight"] for n in user_names] + \
              [sd[f"ad_embeddings.{n}.weight"] for n in ad_names]
-    emb_dim = int(tables[0].shape[1])
-    if emb_dim < 4 or emb_dim & (emb_dim - 1):
-        raise ValueError("embedding_dim must be a power of two >= 4 for the fused gather")
     p = RankerParams()
-    p.n_user_feat, p.n_ad_feat, p.emb_dim, p.n_num = len(user_names), len(ad_names), emb_dim, n_num
-    p.tables, p.table_off, p.cards, _ = pack_tables(pk, tables, emb_dim)
-    wproj = _np64(sd["feature_projection.weight"])
-    pos0 = _np64(sd["positional_encoding"])[0, 0]                  # only row 0 is ever read (:361)
-    bproj = _np64(sd["feature_projection.bias"]) + pos0
-    fold = bool(fold_first_attention and x3 and int(x3_min_rows) == 1 and x3_eligible(sd, fuse_attention)
-                and "transformer_layers.0.norm1.weight" in sd)
-    if fold:
-        wproj, bproj = folded_projection(sd)
-    d_model = wproj.shape[0]
+    p.tables, p.table_off, p.cards, emb_dim = pack_tables(pk, tables)
+    ch = ranker_chain(sd)
+    if len(ch.layers) > MAX_LAYERS:
+        raise ValueError(f"at most {MAX_LAYERS} encoder layers are supported (num_layers > {MAX_LAYERS})")
+    x3 = bool(x3) and x3_eligible(sd, fuse_attention)
+    fold = bool(fold_first_attention and x3 and int(x3_min_rows) == 1 and ch.layers)
+    wproj, bproj = folded_projection(ch) if fold else (ch.w_proj, ch.b_proj)
     assert wproj.shape[1] == len(tables) * emb_dim + n_num
-    p.d_model = d_model
-    w, p.ldw_proj = _pad_k(wproj)
-    p.w_proj = pk.ptr(w)
-    # split for the broadcast form: [user emb | numerical] and [ad emb] column blocks
+    p.n_user_feat, p.n_ad_feat, p.emb_dim, p.n_num = len(user_names), len(ad_names), emb_dim, n_num
+    p.d_model, p.ln_eps = wproj.shape[0], ln_eps
+    p.w_proj, p.ldw_proj, _ = pk.mat(wproj)
     nu, na = len(user_names) * emb_dim, len(ad_names) * emb_dim
-    if nu + n_num > 0 and na > 0:
-        w, p.ldw_proj_user = _pad_k(np.concatenate([wproj[:, :nu], wproj[:, nu + na:]], axis=1))
-        p.w_proj_user = pk.ptr(w)
-        w, p.ldw_proj_ad = _pad_k(wproj[:, nu:nu + na])
-        p.w_proj_ad = pk.ptr(w)
-    p.b_proj = pk.ptr(bproj.astype(np.float32))
-    l = 0
-    while f"transformer_layers.{l}.norm1.weight" in sd:
-        if l >= MAX_LAYERS:
-            raise ValueError(f"at most {MAX_LAYERS} encoder layers are supported (num_layers > {MAX_LAYERS})")
-        pre = f"transformer_layers.{l}"
-        L = p.layers[l]
-        wv, bv = _np64(sd[f"{pre}.self_attention.W_v.weight"]), _np64(sd[f"{pre}.self_attention.W_v.bias"])
-        wo, bo = _np64(sd[f"{pre}.self_attention.W_o.weight"]), _np64(sd[f"{pre}.self_attention.W_o.bias"])
-        if fuse_attention:
-            mats = (("w_o", wo @ wv), ("w_1", _np64(sd[f"{pre}.feed_forward.fc1.weight"])))
-            bo = wo @ bv + bo
-            L.w_v, L.b_v = None, None
-        else:
-            mats = (("w_v", wv), ("w_o", wo), ("w_1", _np64(sd[f"{pre}.feed_forward.fc1.weight"])))
-            L.b_v = pk.ptr(bv.astype(np.float32))
-        for dst, mat in mats:
-            w, ld = _pad_k(mat)
-            setattr(L, dst, pk.ptr(w))
-            L.ldw_dm = ld
-            if x6 and dst in ("w_o", "w_1"):
-                setattr(L, dst + "_x6", pk.ptr(split_planes(w)))
-        L.b_o = pk.ptr(bo.astype(np.float32))
-        w, L.ldw_ff = _pad_k(_np64(sd[f"{pre}.feed_forward.fc2.weight"]))
-        L.w_2 = pk.ptr(w)
-        if x6:
-            L.w_2_x6 = pk.ptr(split_planes(w))
-        p.d_ff = int(sd[f"{pre}.feed_forward.fc1.weight"].shape[0])
-        for dst, src in (("b_1", "feed_forward.fc1.bias"), ("b_2", "feed_forward.fc2.bias"),
-                         ("ln1_g", "norm1.weight"), ("ln1_b", "norm1.bias"),
-                         ("ln2_g", "norm2.weight"), ("ln2_b", "norm2.bias")):
-            setattr(L, dst, pk.ptr(_np64(sd[f"{pre}.{src}"]).astype(np.float32)))
-        l += 1
-    p.n_layers = l
-    if l == 0:
-        p.d_ff = 4                  # placeholder (ranker_check wants d_ff >= 4); nothing reads it without encoder layers
-    c = 0
-    while f"feature_interaction.cross_weights.{c}" in sd:
-        w, p.ldw_cross = _pad_k(_np64(sd[f"feature_interaction.cross_weights.{c}"]).T)   # xl @ W == xl (W^T)^T
-        p.cross_wt[c] = pk.ptr(w)
-        if x6:
-            p.cross_wt_x6[c] = pk.ptr(split_planes(w))
-        p.cross_b[c] = pk.ptr(_np64(sd[f"feature_interaction.cross_biases.{c}"]).astype(np.float32))
-        c += 1
-    p.n_cross = c
-    tasks = [t for t in TASKS if f"prediction_heads.{t}.0.weight" in sd]
-    p.n_tasks = len(tasks)
-    w1 = np.concatenate([_np64(sd[f"prediction_heads.{t}.0.weight"]) for t in tasks], axis=0)
-    b1 = np.concatenate([_np64(sd[f"prediction_heads.{t}.0.bias"]) for t in tasks], axis=0)
-    p.head_h1 = int(sd[f"prediction_heads.{tasks[0]}.0.weight"].shape[0])
-    p.head_h2 = int(sd[f"prediction_heads.{tasks[0]}.3.weight"].shape[0])
-    w, p.ldw_head1 = _pad_k(w1)
-    p.head_w1, p.head_b1 = pk.ptr(w), pk.ptr(b1.astype(np.float32))
-    if x6:
-        p.head_w1_x6 = pk.ptr(split_planes(w))
-    for i, t in enumerate(tasks):
-        w, p.ldw_head2 = _pad_k(_np64(sd[f"prediction_heads.{t}.3.weight"]))
-        p.head_w2[i] = pk.ptr(w)
-        p.head_b2[i] = pk.ptr(_np64(sd[f"prediction_heads.{t}.3.bias"]).astype(np.float32))
-        p.head_w3[i] = pk.ptr(_np64(sd[f"prediction_heads.{t}.6.weight"]).reshape(-1).astype(np.float32))
-        p.head_b3[i] = pk.ptr(_np64(sd[f"prediction_heads.{t}.6.bias"]).reshape(-1).astype(np.float32))
-    p.ln_eps = ln_eps
-    if x3 and x3_eligible(sd, fuse_attention):
-        # the SAME fp32-rounded matrices the other engines multiply with, split into fp16 planes in stream order
-        f32 = lambda a: np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64)   # noqa: E731
-        mats = {"ov": [], "w1": [], "b1": [], "w2": [], "cross": [], "h2": []}
-        for li in range(p.n_layers):
-            pre = f"transformer_layers.{li}"
-            wv, wo = _np64(sd[f"{pre}.self_attention.W_v.weight"]), _np64(sd[f"{pre}.self_attention.W_o.weight"])
-            mats["ov"].append(f32(wo @ wv))
-            mats["w1"].append(f32(_np64(sd[f"{pre}.feed_forward.fc1.weight"])))
-            mats["b1"].append(f32(_np64(sd[f"{pre}.feed_forward.fc1.bias"])))
-            mats["w2"].append(f32(_np64(sd[f"{pre}.feed_forward.fc2.weight"])))
-        for ci in range(p.n_cross):
-            mats["cross"].append(f32(_np64(sd[f"feature_interaction.cross_weights.{ci}"]).T))
-        mats["h1"], mats["hb1"] = f32(w1), f32(b1)
-        for t in tasks:
-            mats["h2"].append(f32(_np64(sd[f"prediction_heads.{t}.3.weight"])))
-        x = pack_x3_stream(mats, x3_variant, fold_first=fold)
-        p.x3.variant = x3_variant
-        p.x3.fold_attn1 = int(fold)
-        lay = []
-        for li in range(p.n_layers):
-            pre = f"transformer_layers.{li}"
-            wo = _np64(sd[f"{pre}.self_attention.W_o.weight"])
-            lay.append({"b_ov": wo @ _np64(sd[f"{pre}.self_attention.W_v.bias"]) + _np64(sd[f"{pre}.self_attention.W_o.bias"]),
-                        "g1": _np64(sd[f"{pre}.norm1.weight"]), "be1": _np64(sd[f"{pre}.norm1.bias"]),
-                        "b1": _np64(sd[f"{pre}.feed_forward.fc1.bias"]), "b2": _np64(sd[f"{pre}.feed_forward.fc2.bias"]),
-                        "g2": _np64(sd[f"{pre}.norm2.weight"]), "be2": _np64(sd[f"{pre}.norm2.bias"])})
-        blob = pack_x3_params(lay, [_np64(sd[f"feature_interaction.cross_biases.{ci}"]) for ci in range(p.n_cross)], b1,
-                              [{"b2": _np64(sd[f"prediction_heads.{t}.3.bias"]), "w3": _np64(sd[f"prediction_heads.{t}.6.weight"]),
-                                "b3": _np64(sd[f"prediction_heads.{t}.6.bias"])} for t in tasks], fold_first=fold)
-        assert len(blob) <= X3_PARAM_FLOATS
-        p.x3.params = pk.ptr(blob)
-        p.x3.n_params = len(blob)
-        p.x3.stream = pk.ptr(x["stream"].view(np.int16))
-        p.x3.chunks = x["chunks"]
-        p.x3.min_rows = int(x3_min_rows)
-        if x3_variant == 16 and x3_cs_max_rows >= 0 and (p.n_layers == 0 or p.d_ff % 128 == 0) and p.head_h1 % 128 == 0:
-            xc = pack_x3_stream(mats, "16cs", fold_first=fold)   # same planes and scales, the column-split kernel's chunk order
-            assert all(xc[k] == x[k] for k in ("sw_ov", "sw_1", "sw_2", "sw_cross", "sw_h1", "sw_h2"))
-            p.x3.stream_cs = pk.ptr(xc["stream"].view(np.int16))
-            p.x3.chunks_cs = xc["chunks"]
-        p.x3.cs_max_rows = int(x3_cs_max_rows)
-        if cache_first_ffn and fold and x3_variant == 16 and p.w_proj_user and p.d_ff % 64 == 0:
-            hc = first_ffn_cache(sd, nu, na, ln_eps)
-            xh = pack_x3_stream(mats, 16, fold_first=True, cache_first_ffn=True)
-            p.x3.stream_hc = pk.ptr(xh["stream"].view(np.int16))
-            p.x3.chunks_hc = xh["chunks"]
-            blob_hc = pack_x3_params([dict(lay[0], b1=hc["c"])] + lay[1:],
-                                     [_np64(sd[f"feature_interaction.cross_biases.{ci}"]) for ci in range(p.n_cross)], b1,
-                                     [{"b2": _np64(sd[f"prediction_heads.{t}.3.bias"]),
-                                       "w3": _np64(sd[f"prediction_heads.{t}.6.weight"]),
-                                       "b3": _np64(sd[f"prediction_heads.{t}.6.bias"])} for t in tasks], fold_first=True)
-            assert len(blob_hc) == len(blob)
-            p.x3.params_hc = pk.ptr(blob_hc)
-            wu, ldu = _pad_k(np.concatenate([np.concatenate([wproj[:, :nu], wproj[:, nu + na:]], axis=1), hc["w_user"]]))
-            assert ldu == p.ldw_proj_user
-            p.x3.w_user_uq = pk.ptr(wu)
-            p.x3.b_user_uq = pk.ptr(np.concatenate([bproj, hc["b"]]).astype(np.float32))
-            wa, lda = _pad_k(hc["w_ad"])
-            assert lda == p.ldw_proj_ad
-            p.x3.w_hidden_ad = pk.ptr(wa)
-        for li in range(p.n_layers):
-            p.x3.sw_ov[li], p.x3.sw_1[li], p.x3.sw_2[li] = x["sw_ov"][li], x["sw_1"][li], x["sw_2"][li]
-            p.x3.hn[li], p.x3.hb[li] = x["hn"][li], x["hb"][li]
-        for ci in range(p.n_cross):
-            p.x3.sw_cross[ci] = x["sw_cross"][ci]
-        p.x3.sw_h1, p.x3.sw_h2, p.x3.hn_head, p.x3.hb_head = x["sw_h1"], x["sw_h2"], x["hn_head"], x["hb_head"]
-    return p, pk, tasks
+    if nu + n_num > 0 and na > 0:                                   # split for the broadcast form
+        w_user, w_ad = _user_ad_columns(wproj, nu, na)
+        p.w_proj_user, p.ldw_proj_user, _ = pk.mat(w_user)
+        p.w_proj_ad, p.ldw_proj_ad, _ = pk.mat(w_ad)
+    p.b_proj = pk.vec(bproj)
+    for l, c in enumerate(ch.layers):
+        _pack_encoder_layer(p.layers[l], pk, c, fuse_attention, x6)
+    p.n_layers, p.n_cross, p.n_tasks = len(ch.layers), len(ch.cross_wt), len(ch.tasks)
+    p.d_ff = ch.layers[-1]["w1"].shape[0] if ch.layers else 4      # 4: placeholder (ranker_check wants d_ff >= 4), never read
+    for c, (w, b) in enumerate(zip(ch.cross_wt, ch.cross_b)):
+        p.cross_wt[c], p.ldw_cross, p.cross_wt_x6[c] = pk.mat(w, x6)
+        p.cross_b[c] = pk.vec(b)
+    p.head_h1, p.head_h2 = ch.head_w1.shape[0] // len(ch.tasks), ch.heads[0]["w2"].shape[0]
+    p.head_w1, p.ldw_head1, p.head_w1_x6 = pk.mat(ch.head_w1, x6)
+    p.head_b1 = pk.vec(ch.head_b1)
+    for i, h in enumerate(ch.heads):
+        p.head_w2[i], p.ldw_head2, _ = pk.mat(h["w2"])
+        p.head_b2[i], p.head_w3[i], p.head_b3[i] = pk.vec(h["b2"]), pk.vec(h["w3"]), pk.vec(h["b3"])
+    if x3:
+        p.x3.variant, p.x3.fold_attn1 = x3_variant, int(fold)
+        p.x3.min_rows, p.x3.cs_max_rows = int(x3_min_rows), int(x3_cs_max_rows)
+        _pack_x3(p, pk, ch, wproj, bproj, nu, na, cache_first_ffn)
+    return p, pk, ch.tasks

@@ -391,3 +391,35 @@ def test_column_split_stream_gives_every_wave_its_group_in_every_chunk():
     nz = nz[nz.any(axis=1)]
     key = lambda a: np.sort(np.ascontiguousarray(a).view([("", a.dtype)] * a.shape[1]).ravel())    # noqa: E731
     assert (key(base[base.any(axis=1)]) == key(nz)).all()
+
+
+# ---- one split per matrix, one fold per pack ------------------------------------------------------------------------
+def _count_calls(monkeypatch, name):
+    calls, fn = [], getattr(weights, name)
+    monkeypatch.setattr(weights, name, lambda *a, **k: (calls.append(name), fn(*a, **k))[1])
+    return calls
+
+
+def test_every_matrix_is_plane_split_once_however_many_streams_are_packed(monkeypatch):
+    """The main, column-split and hidden-cache streams are three orderings of ONE set of fragments: a pack splits each of its
+    (L - 1 folded | L) + 2 L + C + 1 + T matrices (W_ov, W_1 and W_2 per layer, cross, stacked head layer 1, head layer 2 per
+    task; L = C = T = 3) exactly once."""
+    user, ad, nnum, sd, _ = cases.ranker_case("demo", "scaled")
+    kw = dict(x6=False, x3=True, x3_variant=16, x3_min_rows=1)
+    calls = _count_calls(monkeypatch, "x3b_frags")
+    p, _, _ = weights.pack_ranker(sd, list(user), list(ad), nnum, "cpu", fold_first_attention=True, cache_first_ffn=True, **kw)
+    assert p.x3.stream and p.x3.stream_cs and p.x3.stream_hc                   # three streams
+    assert len(calls) == (3 - 1) + 2 * 3 + 3 + 1 + 3 == 15
+    del calls[:]
+    p, _, _ = weights.pack_ranker(sd, list(user), list(ad), nnum, "cpu", **kw)
+    assert p.x3.stream and p.x3.stream_cs and not p.x3.stream_hc               # two streams
+    assert len(calls) == 3 + 2 * 3 + 3 + 1 + 3 == 16
+
+
+def test_the_projection_is_folded_once_per_pack(monkeypatch):
+    """The folded projection feeds the packed projection AND the first-FFN hidden cache: computed once, handed on."""
+    user, ad, nnum, sd, _ = cases.ranker_case("demo", "scaled")
+    calls = _count_calls(monkeypatch, "folded_projection")
+    p, _, _ = weights.pack_ranker(sd, list(user), list(ad), nnum, "cpu", x6=False, x3=True, x3_variant=16, x3_min_rows=1,
+                                  fold_first_attention=True, cache_first_ffn=True)
+    assert p.x3.fold_attn1 == 1 and p.x3.stream_hc and len(calls) == 1
