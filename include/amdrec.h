@@ -30,7 +30,8 @@ extern "C" {
                                * first-FFN hidden cache: amdrec_ranker_project_ads_hidden, amdrec_x3_weights.stream_hc ... at the
                                * struct's end, amdrec_ranker_params.ad_hidden_cache - the number stays, the library and its
                                * binding ship together and the struct layouts are checked against the compiler, tests/test_abi.py;
-                               * amdrec_select_topk then gained its cand_pos argument under the same rule) */
+                               * amdrec_select_topk then gained its cand_pos argument under the same rule; so did CTR-first ranking:
+                               * amdrec_ranker_forward_ctr_first ..., amdrec_x3_weights.stream_ctr ... at the struct's end) */
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -364,6 +365,23 @@ typedef struct {
     const float* w_user_uq;
     const float* b_user_uq;
     const float* w_hidden_ad;
+    /* Optional (variant 16, n_tasks >= 2): the streams of CTR-first ranking (amdrec_ranker_forward_ctr_first /
+     * amdrec_ranker_winner_heads).  The SAME fragment sets, from the same split, under the same scales and hidden bounds (sw_h1,
+     * sw_h2, hn_head, hb_head stay the values over the STACKED heads), cut by task:
+     *   stream_ctr / stream_ctr_cs / stream_ctr_hc : `stream` / `stream_cs` / `stream_hc` up to its first heads fragment set,
+     *                                                then the heads of task 0 alone
+     *   stream_win / stream_win_cs                  : the heads of tasks 1 .. n_tasks - 1 alone, in the 16-row / column-split order
+     * A stream that is NULL makes amdrec_ranker_ctr_first_supported answer 0 for the calls that would read it. */
+    const void* stream_ctr;
+    int64_t chunks_ctr;
+    const void* stream_ctr_cs;
+    int64_t chunks_ctr_cs;
+    const void* stream_ctr_hc;
+    int64_t chunks_ctr_hc;
+    const void* stream_win;
+    int64_t chunks_win;
+    const void* stream_win_cs;
+    int64_t chunks_win_cs;
 } amdrec_x3_weights;
 
 typedef struct {
@@ -427,6 +445,44 @@ int amdrec_ranker_forward(const amdrec_ranker_params* p /*host*/, const int64_t*
                           const int64_t* ad_rowmap, int64_t rows, float* out_logits, int64_t ld_logits,
                           int* bad_index_flag, int64_t n_user_rows, int64_t n_ad_rows, void* workspace,
                           size_t workspace_bytes, void* stream);
+
+/* CTR-first ranking (added to ABI v14 without a version step: new exports, new amdrec_x3_weights fields at the struct's end).
+ * The callers of the reference rank a user's candidates by the CTR logit alone and report the other tasks for the winners
+ * only (inference.py:258-288, faiss_retrieval.py:355-369).  Pass 1 runs the projection, the trunk and the head of task 0 on
+ * every candidate and keeps each row's trunk state; the selection runs on that one logit row; pass 2 runs the other heads on
+ * the winners' stored rows.  Every number either pass produces is, bit for bit, the one amdrec_ranker_forward +
+ * amdrec_select_topk produce: a wave owns its rows, and the same fragment sets meet the same fp32 state in the same order
+ * under the same scales.
+ *
+ * amdrec_ranker_forward_ctr_first: the arguments of amdrec_ranker_forward, plus trunk_out [rows][ld_trunk] (ld_trunk >= 256,
+ * % 4 == 0, 16-byte aligned): row r's 256 floats are the state the heads receive.  out_logits[r] = the logit of task 0 (one
+ * row; ld_logits >= rows is still required).  Workspace: amdrec_ranker_ctr_first_workspace.  An error (AMDREC_EINVAL) where
+ * amdrec_ranker_ctr_first_supported(p, rows) is 0: there is no fall-back inside the entry.
+ * amdrec_ranker_ctr_first_supported: non-zero when every pass of a `rows`-row call, and a winner pass of `rows` rows, would
+ * run a 16-row kernel of the fp16x3 engine (x3.variant 16, every pass at least x3.min_rows rows) with the streams it reads
+ * packed, n_tasks >= 2; p's cache pointers count (they select the hidden-cache program).  Otherwise the caller runs
+ * amdrec_ranker_forward.
+ * amdrec_ranker_winner_heads: slots [n_users][top_k] = amdrec_select_topk's out_slots over k_c candidates per user; winner
+ * row i = u * top_k + j reads trunk[u * k_c + slots[i]] (clamped into [0, n_trunk_rows); n_trunk_rows >= n_users * k_c) and
+ * out_scores[t][u][j] = sigmoid(logit of task t), t = 1 .. n_tasks - 1, by the expression amdrec_select_topk uses; 0.0 where
+ * the slot is negative (no winner: the tail of a short list, or top_k > k_c).  Plane 0 of out_scores is not written.  Two
+ * launches: the heads-only program on the kernel its row count selects, and the sigmoid.  n_users * top_k < 2^31.
+ * amdrec_ranker_ctr_first_workspace: the bytes that serve amdrec_ranker_forward_ctr_first on `rows` rows and
+ * amdrec_ranker_winner_heads on n_winner_rows = n_users * top_k rows: the larger of the two needs - amdrec_ranker_workspace's
+ * for `rows` (0 for rows == 0) and (n_tasks - 1) * n_winner_rows floats, rounded up to 256 bytes. */
+int amdrec_ranker_forward_ctr_first(const amdrec_ranker_params* p /*host*/, const int64_t* user_cat,
+                                    const float* numerical, int64_t user_rowdiv, const int64_t* ad_cat,
+                                    const int64_t* ad_rowmap, int64_t rows, float* out_logits /*[rows]*/,
+                                    int64_t ld_logits, int* bad_index_flag, int64_t n_user_rows, int64_t n_ad_rows,
+                                    float* trunk_out /*[rows][ld_trunk]*/, int64_t ld_trunk, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int amdrec_ranker_ctr_first_supported(const amdrec_ranker_params* p /*host*/, int64_t rows);
+int amdrec_ranker_winner_heads(const amdrec_ranker_params* p /*host*/, const float* trunk /*[n_trunk_rows][ld_trunk]*/,
+                               int64_t ld_trunk, int64_t n_trunk_rows, const int32_t* slots /*[n_users][top_k]*/,
+                               int64_t n_users, int k_c, int top_k, float* out_scores /*[n_tasks][n_users][top_k]*/,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int amdrec_ranker_ctr_first_workspace(const amdrec_ranker_params* p /*host*/, int64_t rows, int64_t n_winner_rows,
+                                      size_t* bytes /*host*/);
 
 /* Test / debugging entry of the fp16x3 engine: run the first n_phases phases of the chain (phase order: per encoder
  * layer {attention + LN1, FFN + LN2}, then the cross layers, then the heads; n_phases < 0 = all) on dense projected

@@ -66,6 +66,10 @@ _SIGNATURES = {
     "amdrec_tower_forward": [_vp, _vp, _fp, _i64, _fp, _i64, _vp, _vp, _sz, _vp],
     "amdrec_ranker_workspace": [_vp, _i64, C.POINTER(_sz)],
     "amdrec_ranker_forward": [_vp, _vp, _fp, _i64, _vp, _vp, _i64, _fp, _i64, _vp, _i64, _i64, _vp, _sz, _vp],
+    "amdrec_ranker_forward_ctr_first": [_vp, _vp, _fp, _i64, _vp, _vp, _i64, _fp, _i64, _vp, _i64, _i64, _fp, _i64, _vp, _sz, _vp],
+    "amdrec_ranker_ctr_first_supported": [_vp, _i64],
+    "amdrec_ranker_winner_heads": [_vp, _fp, _i64, _i64, _vp, _i64, _i32, _i32, _fp, _vp, _sz, _vp],
+    "amdrec_ranker_ctr_first_workspace": [_vp, _i64, _i64, C.POINTER(_sz)],
     "amdrec_l2_normalize": [_fp, _i64, _fp, _i64, _i64, _i32, _vp],
     "amdrec_remap_ids": [_vp, _vp, _i64, _vp, _i64, _vp],
     "amdrec_exclude_compact": [_vp, _fp, _vp, _i64, _i32, _vp, _i32, _i64, _i32, _i64, C.c_float, _i64, _vp, _fp, _vp, _vp],

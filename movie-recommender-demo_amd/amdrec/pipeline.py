@@ -80,10 +80,18 @@ class AdRecommenderInference:
                  transformer_ranker: Optional[TransformerRanker] = None,
                  faiss_index: Optional[FAISSIndex] = None, ad_features=None,
                  preprocessor: Optional[Preprocessor] = None, verbose: bool = False,
-                 cache_ad_projection: bool = True):
+                 cache_ad_projection: bool = True, heads: str = "all"):
         """Either ``model_dir`` (files below) or the components directly.
         model_dir: preprocessor.json, two_tower_{best,final}.pt, transformer_ranker_{best,final}.pt,
-        faiss_index.bin (+ .metadata) in this build's format, ad_features.npy [N, 20]."""
+        faiss_index.bin (+ .metadata) in this build's format, ad_features.npy [N, 20].
+        ``heads`` (``heads_mode``): what stage 2 evaluates.  "all": every head on every candidate.  "ctr_first": the
+        candidates are ranked by the CTR logit alone and the other tasks are reported for the winners only
+        (inference.py:258-288), so the trunk and the CTR head run on every candidate and the other heads on the
+        ``B * top_k`` winners' stored trunk rows (TransformerRanker.score_ctr_first / winner_scores).  ad_ids, scores and
+        the CTR logits are bit-identical in both modes; in "ctr_first" ``logits`` holds the CTR row alone.  The mode does
+        what it is told wherever it can run (``heads_mode_effective``); it is no tuning switch - DESIGN.md has the
+        measured batch sizes at which it pays."""
+        self.heads_mode = self._check_heads(heads)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.AmdrecError("AdRecommenderInference needs a HIP device (no CPU fallback)")
@@ -192,6 +200,25 @@ class AdRecommenderInference:
             ent[1].synchronize()
         return ent[0][:nbytes], ent[1]
 
+    HEADS_MODES = ("all", "ctr_first")
+
+    @classmethod
+    def _check_heads(cls, heads):
+        if heads not in cls.HEADS_MODES:
+            raise ValueError(f"heads must be one of {cls.HEADS_MODES}, got {heads!r}")
+        return heads
+
+    def heads_mode_effective(self, heads: Optional[str] = None):
+        """-> (the mode stage 2 runs for ``heads`` (None: ``heads_mode``), why not the requested one or None).  "ctr_first"
+        on a ranker that cannot run it (TransformerRanker.ctr_first_unsupported_reason) runs "all": the results are the
+        same by definition, and no call raises or warns for it."""
+        mode = self._check_heads(self.heads_mode if heads is None else heads)
+        if mode == "ctr_first":
+            why = self.transformer_ranker.ctr_first_unsupported_reason()
+            if why is not None:
+                return "all", why
+        return mode, None
+
     # -- the device hot path ------------------------------------------------------------------
     def _stage1(self, uc, un, stage1_k, check_indices, exclude=None):
         # the tower's launch also applies the search's query normalisation (faiss_retrieval.py:147): one launch fewer
@@ -201,7 +228,7 @@ class AdRecommenderInference:
                                               return_positions=True, exclude=exclude)
 
     def _stage2(self, uc, un, cand_pos, top_k, check_indices, ids_are_positions=False, mark=None, out=None,
-                excluded=False):
+                excluded=False, heads=None):
         """Ranker + selection over stage 1's positions ``cand_pos`` [B, stage1_k].  A negative position is a slot the search
         could not fill: no candidate.  The ranker still computes a (finite, unspecified) logit for it - every gather clamps
         the row - and the selection, which is handed the positions, ranks it after every real candidate: it is reported only
@@ -210,10 +237,22 @@ class AdRecommenderInference:
         position itself with ``ids_are_positions``), from which it can no longer be told."""
         lib = _lib.load()
         B, stage1_k = cand_pos.shape
+        rk = self.transformer_ranker
         if self.cache_ad_projection:
-            self.transformer_ranker.ensure_ad_cache(self.ad_features)
-        tasks, logits = self.transformer_ranker.score_candidates(uc, un, cand_pos, self.ad_features,  # :241-255
-                                                                 check_indices=check_indices, raw=True)
+            rk.ensure_ad_cache(self.ad_features)
+        # "ctr_first" (``heads``: a per-call override of ``heads_mode``): the trunk and the CTR head on every candidate, the
+        # selection on that one logit row, the other heads on the winners.  A ranker or shape that cannot run it takes the
+        # all-heads path below: the same results
+        mode = self.heads_mode if heads is None else heads
+        ctr_first = mode != "all" and self.heads_mode_effective(mode)[0] == "ctr_first" and \
+            rk.ctr_first_ready(self.ad_features, B * stage1_k, B * top_k)
+        if ctr_first:
+            tasks = rk._packed.tasks
+            ctr, trunk = rk.score_ctr_first(uc, un, cand_pos, self.ad_features, check_indices=check_indices, _ready=True)
+            logits = ctr.view(1, -1)
+        else:
+            tasks, logits = rk.score_candidates(uc, un, cand_pos, self.ad_features,                   # :241-255
+                                                check_indices=check_indices, raw=True)
         if mark is not None:                     # amdrec.sharded.StageTimer: the ranker ends here, the selection follows
             mark("ranker")
         if out is not None:                      # (ad_ids, scores) views of one block: the reference API's single D2H copy
@@ -234,20 +273,32 @@ class AdRecommenderInference:
             cand_ids = torch.empty_like(cand_pos)
             _lib.check(lib.amdrec_remap_ids(_lib.ptr(cand_pos), _lib.ptr(idx._ids), idx._n, _lib.ptr(cand_ids),
                                             cand_pos.numel(), _lib.stream_ptr(uc.device)))
-        if B:
+        if B and ctr_first:
+            # the selection as ever, on the one logit row: ad ids, plane 0 of scores and the winning slots; then the winners'
+            # other tasks into planes 1 ..
+            slots = torch.empty((B, top_k), dtype=torch.int32, device=uc.device)
+            _lib.check(lib.amdrec_select_topk(_lib.ptr(logits), logits.stride(0), 1, 0, _lib.ptr(cand_ids), _lib.ptr(cand_pos),
+                                              B, stage1_k, top_k, _lib.ptr(ad_ids), _lib.ptr(scores), _lib.ptr(slots),
+                                              _lib.stream_ptr(uc.device)))
+            rk.winner_scores(trunk, slots, stage1_k, scores)
+        elif B:
             _lib.check(lib.amdrec_select_topk(_lib.ptr(logits), logits.stride(0), len(tasks), tasks.index("ctr"),
                                               _lib.ptr(cand_ids), _lib.ptr(cand_pos), B, stage1_k, top_k,
                                               _lib.ptr(ad_ids), _lib.ptr(scores), None, _lib.stream_ptr(uc.device)))
-        return {"ad_ids": ad_ids, "scores": scores, "tasks": tasks, "candidate_ids": cand_ids, "logits": logits}
+        return {"ad_ids": ad_ids, "scores": scores, "tasks": tasks, "candidate_ids": cand_ids, "logits": logits,
+                "logit_tasks": ("ctr",) if ctr_first else tuple(tasks)}
 
     @torch.no_grad()
     def recommend_device(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor, top_k: int = 10,
                          stage1_k: int = 500, check_indices: bool = False,
-                         exclude_ad_ids: Optional[torch.Tensor] = None):
+                         exclude_ad_ids: Optional[torch.Tensor] = None, heads: Optional[str] = None):
         """[B,6] / [B,13] device tensors -> dict of device tensors, no host synchronisation:
         ad_ids [B,top_k] int64, scores [3,B,top_k] float32 (sigmoid of the logits), candidate_ids
         [B,stage1_k], candidate_scores [B,stage1_k], logits [3, B*stage1_k].  candidate_scores are the index's own
         scores: inner products (descending) for Flat / IVF, approximate squared L2 distances (ascending) for IVFPQ.
+        ``heads``: "all" / "ctr_first" for this call (None: ``heads_mode``).  Where "ctr_first" runs, ``logits`` is
+        [1, B*stage1_k], the CTR row alone; ``logit_tasks`` names the rows of ``logits`` (== ``tasks`` in "all" mode).
+        Everything else - ad_ids, all of scores, the CTR logits - is bit-identical in both modes.
         ``exclude_ad_ids``: device int64 [B, E], per user the ad ids that must not be recommended (negative = padding;
         stage1_k + E <= AMDREC_MAX_K): stage 1 searches stage1_k + E and drops them on the device (FAISSIndex.search_device),
         so candidate_ids / candidate_scores and everything after them hold eligible ads only.
@@ -259,11 +310,13 @@ class AdRecommenderInference:
         retrieved by stage 1.  candidate_ids keeps the search's convention for an unfilled slot (id_map[-1]) and its entry
         of logits is unspecified but finite (for finite weights and user features): mask them with candidate_scores.
         ``check_indices``: an out-of-range user index or ad-table row raises IndexError; an unfilled slot does not."""
+        if heads is not None:
+            self._check_heads(heads)
         uc = _lib.require_gpu(user_categorical, "user_categorical")
         un = _lib.require_gpu(user_numerical, "user_numerical")
         excluded = exclude_ad_ids is not None and exclude_ad_ids.shape[-1] > 0
         cand_pos, cand_scores = self._stage1(uc, un, stage1_k, check_indices, exclude_ad_ids if excluded else None)
-        out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded)
+        out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded, heads=heads)
         out["candidate_scores"] = cand_scores
         return out
 

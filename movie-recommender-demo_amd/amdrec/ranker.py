@@ -140,6 +140,35 @@ class TransformerRanker(nn.Module):
         correct (golden-tested on the tutorial's architecture) but several times slower, and must not be silent."""
         return weights.x3_ineligible_reason(self.state_dict(), self.fuse_attention)
 
+    def ctr_first_unsupported_reason(self):
+        """Why CTR-first ranking (``score_ctr_first`` + ``winner_scores``; AdRecommenderInference ``heads="ctr_first"``) would
+        NOT run for this ranker (None: it runs).  The mode exists on the 16-row kernels of the row-owner engine alone; the
+        pipeline then runs the all-heads path, whose results are the same by definition."""
+        # (asked once per request by the pipeline: the answer is kept while nothing it depends on can have changed - the
+        # switches below, and the architecture, which only a re-registered tensor can change)
+        key = (self.gemm_engine, self.fuse_attention, int(self.x3_variant), int(self.x3_min_rows), _lib._REG_EPOCH[0])
+        c = self.__dict__.get("_ctr_first_why")
+        if c is None or c[0] != key:
+            c = self.__dict__["_ctr_first_why"] = (key, self._ctr_first_unsupported_reason())
+        return c[1]
+
+    def _ctr_first_unsupported_reason(self):
+        if self.gemm_engine != "f16x3":
+            return f"gemm_engine {self.gemm_engine!r} (the mode runs on the f16x3 row-owner kernels only)"
+        why = self.x3_fallback_reason()
+        if why is not None:
+            return f"not the row-owner engine's architecture ({why})"
+        if int(self.x3_variant) != 16:
+            return f"x3_variant {self.x3_variant} (the 32-row kernel has no task window and no gathered input)"
+        if int(self.x3_min_rows) != 1:
+            return f"x3_min_rows {self.x3_min_rows} (every pass, the winners' included, must run the row-owner kernel)"
+        tasks = list(self.prediction_heads.keys())
+        if not tasks or tasks[0] != "ctr":
+            return "the ranking task (ctr) is not task 0"
+        if len(tasks) < 2:
+            return "no task besides the ranking task"
+        return None
+
     def gemm_engine_for(self, rows: int) -> str:
         """The engine a pass of ``rows`` rows actually runs on."""
         eng = self.gemm_engine
@@ -153,6 +182,7 @@ class TransformerRanker(nn.Module):
     def invalidate(self):
         self._packed = None
         self._ad_cache = None
+        self.__dict__.pop("_ctr_first_why", None)
         _lib.drop_tensor_list(self)
 
     def _apply(self, fn, *a, **k):                 # .to() / .cuda() / .float(): tensors may be replaced
@@ -332,18 +362,23 @@ class TransformerRanker(nn.Module):
             xl = fi.dropout(x0 * (torch.matmul(xl, fi.cross_weights[i]) + fi.cross_biases[i]) + xl)   # :201-202
         return {t: head(xl).squeeze(1) for t, head in self.prediction_heads.items()}            # :375-378
 
-    def _run(self, user_cat, numerical, user_rowdiv, ad_cat, ad_rowmap, rows, check_indices=True, raw=False,
-             use_cache=False):
-        if self.training:
-            raise NotImplementedError("score_candidates / the HIP forward implement eval() semantics only; call .eval()")
-        dev = ad_cat.device
-        params, tasks = self._pack(dev)
+    def _bound_params(self, ad_cat, use_cache):
+        """(params, tasks) packed for ``ad_cat``'s device, with the per-ad caches valid for that table (or none) bound."""
+        params, tasks = self._pack(ad_cat.device)
         cache = self._cache_for(ad_cat) if use_cache else None
         params.ad_proj_cache = cache.data_ptr() if cache is not None else None
         params.ld_ad_proj_cache = cache.stride(0) if cache is not None else 0
         hidden = self._hidden_cache_for(ad_cat) if cache is not None else None
         params.ad_hidden_cache = hidden.data_ptr() if hidden is not None else None
         params.ld_ad_hidden_cache = hidden.stride(0) if hidden is not None else 0
+        return params, tasks
+
+    def _run(self, user_cat, numerical, user_rowdiv, ad_cat, ad_rowmap, rows, check_indices=True, raw=False,
+             use_cache=False):
+        if self.training:
+            raise NotImplementedError("score_candidates / the HIP forward implement eval() semantics only; call .eval()")
+        dev = ad_cat.device
+        params, tasks = self._bound_params(ad_cat, use_cache)
         lib = _lib.load()
         logits = torch.empty((len(tasks), rows), dtype=torch.float32, device=dev)
         if rows == 0:
@@ -396,6 +431,90 @@ class TransformerRanker(nn.Module):
         if uc.shape[0] != U or nm.shape[0] != U:
             raise ValueError("one user row per candidate list expected")
         return self._run(uc, nm, k, table, cand.view(-1), U * k, check_indices, raw, use_cache=True)
+
+    # -- CTR-first ranking: pass 1 = trunk + CTR head on every candidate, pass 2 = the other heads on the winners ------
+    def ctr_first_ready(self, ad_table, rows: int, winner_rows: int) -> bool:
+        """Whether ``score_ctr_first`` on ``rows`` candidate rows of ``ad_table`` and ``winner_scores`` on ``winner_rows``
+        winners would both run (amdrec_ranker_ctr_first_supported); packs the mode's weight streams on first use
+        (weights.pack_ctr_first: the pack key and the existing streams are untouched)."""
+        if self.training or rows < 1 or winner_rows < 1 or self.ctr_first_unsupported_reason() is not None:
+            return False
+        params, _ = self._bound_params(ad_table, True)
+        if not weights.pack_ctr_first(params, self._packed.keep):
+            return False
+        lib = _lib.load()
+        return bool(lib.amdrec_ranker_ctr_first_supported(_lib.C.byref(params), rows)) and \
+            bool(lib.amdrec_ranker_ctr_first_supported(_lib.C.byref(params), winner_rows))
+
+    def score_ctr_first(self, user_categorical, numerical, candidate_rows, ad_table, check_indices=False, _ready=False):
+        """Pass 1 of CTR-first ranking, arguments as ``score_candidates``: the projection, the trunk and the CTR head alone.
+        -> (ctr_logits [U*k], trunk [U*k, 256]): bit for bit the CTR row of ``score_candidates`` and, per row, the state its
+        heads receive.  ``trunk`` (rows x 1 KB) is a view of the shared workspace (``_lib.WORKSPACE``), meant for the
+        ``winner_scores`` call that follows: any other workspace-taking call may overwrite it.  Raises where
+        ``ctr_first_ready`` is False: there is no fall-back in here."""
+        uc = _lib.require_gpu(user_categorical, "user_categorical").long().contiguous()
+        nm = _lib.require_gpu(numerical, "numerical").to(torch.float32).contiguous()
+        cand = _lib.require_gpu(candidate_rows, "candidate_rows", torch.int64).contiguous()
+        table = _lib.require_gpu(ad_table, "ad_table", torch.int64)
+        if not table.is_contiguous():
+            raise ValueError("ad_table must be contiguous")
+        U, k = cand.shape
+        if uc.shape[0] != U or nm.shape[0] != U:
+            raise ValueError("one user row per candidate list expected")
+        rows, dev = U * k, table.device
+        if not _ready and not self.ctr_first_ready(table, max(rows, 1), max(rows, 1)):    # (_ready: the caller has asked)
+            raise _lib.AmdrecError("CTR-first ranking is not available for this ranker and shape: " +
+                                   (self.ctr_first_unsupported_reason() or "amdrec_ranker_ctr_first_supported says no"))
+        params, _ = self._bound_params(table, True)
+        lib = _lib.load()
+        nbytes = _lib.C.c_size_t(0)
+        _lib.check(lib.amdrec_ranker_ctr_first_workspace(_lib.C.byref(params), rows, rows, _lib.C.byref(nbytes)))
+        # one block [workspace of both passes | trunk rows]: the winners' pass reads the trunk while it works in the front part
+        off_t = (nbytes.value + 255) // 256 * 256
+        blk = _lib.WORKSPACE.get(off_t + rows * 1024, dev)
+        logits = torch.empty(rows, dtype=torch.float32, device=dev)
+        trunk = blk[off_t:off_t + rows * 1024].view(torch.float32).view(rows, 256)
+        if rows == 0:
+            return logits, trunk
+        flag = torch.zeros(1, dtype=torch.int32, device=dev) if check_indices else None
+        _lib.check(lib.amdrec_ranker_forward_ctr_first(
+            _lib.C.byref(params), _lib.ptr(uc), _lib.ptr(nm), k, _lib.ptr(table), _lib.ptr(cand), rows, _lib.ptr(logits), rows,
+            _lib.ptr(flag), uc.shape[0], table.shape[0], _lib.ptr(trunk), 256, _lib.ptr(blk), off_t, _lib.stream_ptr(dev)))
+        if check_indices and int(flag.item()):
+            raise IndexError("index out of range in self")
+        return logits, trunk
+
+    def winner_scores(self, trunk, slots, k_c: int, out_scores):
+        """Pass 2: ``slots`` int32 [U, top_k] = the winning slots amdrec_select_topk chose among each user's ``k_c`` rows of
+        ``trunk`` ([U * k_c, 256] from ``score_ctr_first``); runs the heads of every task but the first on those rows and
+        writes their probabilities into ``out_scores[1:]`` (contiguous float32 [n_tasks, U, top_k]; plane 0 is the
+        selection's) - 0.0 where the slot is negative.  -> out_scores."""
+        trunk = _lib.require_gpu(trunk, "trunk", torch.float32)
+        slots = _lib.require_gpu(slots, "slots", torch.int32)
+        out_scores = _lib.require_gpu(out_scores, "out_scores", torch.float32)
+        dev = trunk.device
+        params, tasks = self._pack(dev)
+        U, top_k = slots.shape
+        if trunk.dim() != 2 or trunk.shape[1] != 256 or trunk.stride(1) != 1 or not slots.is_contiguous() or \
+                not out_scores.is_contiguous() or tuple(out_scores.shape) != (len(tasks), U, top_k):
+            raise ValueError("winner_scores: trunk [rows, 256], contiguous slots [U, top_k] and out_scores [n_tasks, U, top_k]")
+        if U == 0:
+            return out_scores
+        if not weights.pack_ctr_first(params, self._packed.keep):
+            raise _lib.AmdrecError("CTR-first ranking is not available for this ranker: " +
+                                   str(self.ctr_first_unsupported_reason()))
+        lib = _lib.load()
+        nbytes = _lib.C.c_size_t(0)
+        _lib.check(lib.amdrec_ranker_ctr_first_workspace(_lib.C.byref(params), 0, U * top_k, _lib.C.byref(nbytes)))
+        ws = _lib.WORKSPACE.get(nbytes.value, dev)
+        # the shared workspace may be the very block ``trunk`` lives in (score_ctr_first): work in the part in front of it
+        lo, t0 = ws.data_ptr(), trunk.data_ptr()
+        if lo <= t0 < lo + ws.numel():
+            ws = ws[:t0 - lo] if t0 - lo >= nbytes.value else torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        _lib.check(lib.amdrec_ranker_winner_heads(
+            _lib.C.byref(params), _lib.ptr(trunk), trunk.stride(0), trunk.shape[0], _lib.ptr(slots), U, int(k_c), top_k,
+            _lib.ptr(out_scores), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        return out_scores
 
     def compute_loss(self, predictions, labels, task_weights=None):
         """transformer_ranker.py:382-415: weighted sum of per-task BCE-with-logits -> (total, dict of floats)."""

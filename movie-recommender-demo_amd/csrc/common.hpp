@@ -66,6 +66,10 @@ __device__ __forceinline__ float sumsq4(const f32x4& v) {
     return __builtin_fmaf(v[3], v[3], __builtin_fmaf(v[2], v[2], __builtin_fmaf(v[1], v[1], v[0] * v[0])));
 }
 
+// the probability the stage-2 entries report for a logit (amdrec_select_topk, amdrec_ranker_winner_heads): ONE expression, so
+// that a task's score does not depend on which of them wrote it
+__device__ __forceinline__ float sigmoid_prob(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 __host__ __device__ inline unsigned long long make_key(float score, uint32_t pos) {
     return ((unsigned long long)f32_orderable(score) << 32) | (unsigned long long)(~pos);
 }

@@ -607,9 +607,12 @@ namespace amdrec {   // ranker_x3.hip: the fp16x3 row-owner engine (everything a
 bool ranker_x3_wanted(const amdrec_ranker_params* p, long long rows);
 bool ranker_x3_folded(const amdrec_ranker_params* p);
 bool ranker_x3_hidden_cache(const amdrec_ranker_params* p, long long rows);
+bool ranker_x3_ctr_first_supported(const amdrec_ranker_params* p, long long rows, long long row_chunk);
+size_t ranker_x3_winner_workspace(const amdrec_ranker_params* p, long long rows);
 int ranker_x3_run(const amdrec_ranker_params* p, const float* X, long long ldx, const float* U, long long ldu,
                   const long long* rowmap, long long row_base, int rowdiv, long long n_cache, long long rows, float* scratch,
-                  float* logits, long long ld_logits, hipStream_t st);
+                  float* logits, long long ld_logits, hipStream_t st, bool ctr_first = false, float* x_out = nullptr,
+                  long long ld_xout = 0);
 }
 static int ranker_check(const amdrec_ranker_params* p) {
     REQUIRE(p != nullptr, "params is null");
@@ -851,16 +854,25 @@ static int ranker_layer_chain(const RankerCtx& c, long long m, float* logits, lo
     return AMDREC_OK;
 }
 
-extern "C" int amdrec_ranker_forward(const amdrec_ranker_params* p, const int64_t* user_cat, const float* numerical,
-                                     int64_t user_rowdiv, const int64_t* ad_cat, const int64_t* ad_rowmap,
-                                     int64_t rows, float* out_logits, int64_t ld_logits, int* bad_index_flag,
-                                     int64_t n_user_rows, int64_t n_ad_rows, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
+// amdrec_ranker_forward, and (ctr_first) amdrec_ranker_forward_ctr_first: the same pass loop, hoisted user projection, cached
+// gather and program selection; the CTR-first form runs the trunk and the head of task 0 alone on every pass (out_logits:
+// that one row) and keeps each row's trunk state in trunk_out
+static int ranker_forward(const amdrec_ranker_params* p, const int64_t* user_cat, const float* numerical,
+                          int64_t user_rowdiv, const int64_t* ad_cat, const int64_t* ad_rowmap, int64_t rows,
+                          float* out_logits, int64_t ld_logits, int* bad_index_flag, int64_t n_user_rows, int64_t n_ad_rows,
+                          void* workspace, size_t workspace_bytes, void* stream, bool ctr_first, float* trunk_out,
+                          int64_t ld_trunk) {
     int rc = ranker_check(p);
     if (rc) return rc;
     if (rows <= 0) return AMDREC_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     REQUIRE(user_rowdiv >= 1, "user_rowdiv must be >= 1");
+    if (ctr_first) {
+        REQUIRE(trunk_out != nullptr && ld_trunk >= 256 && ld_trunk % 4 == 0 && ((uintptr_t)trunk_out % 16) == 0,
+                "bad trunk_out layout (ld_trunk >= 256, 16-byte aligned)");
+        REQUIRE(ranker_x3_ctr_first_supported(p, rows, ROW_CHUNK), "these parameters cannot run the CTR-first program on %lld "
+                "rows (amdrec_ranker_ctr_first_supported)", (long long)rows);
+    }
     REQUIRE((user_cat || p->n_user_feat == 0) && (ad_cat || p->n_ad_feat == 0) && out_logits, "null pointer");
     REQUIRE(numerical || p->n_num == 0, "numerical is null");
     REQUIRE(ld_logits >= rows, "ld_logits < rows");
@@ -894,22 +906,56 @@ extern "C" int amdrec_ranker_forward(const amdrec_ranker_params* p, const int64_
         // fp16x3 row-owner engine: the rest of the chain is one kernel; with the candidate-side cache it also does the
         // gather (x0 = cache row + user half).  Its x0 scratch is the X0 region (sized in whole 128-row workgroups).
         const bool use_x3 = ranker_x3_wanted(p, m);
+        float* trunk_r0 = ctr_first ? trunk_out + r0 * ld_trunk : nullptr;
         // the folded projection (x3.fold_attn1) already contains layer 1's attention block: only the engine's chain, which
         // starts with LN1 alone, may follow it
         REQUIRE(use_x3 || !ranker_x3_folded(p), "x3.fold_attn1 is set but a pass of %lld rows would not run the row-owner "
                                                 "engine (the fold needs n_layers >= 1 and x3.min_rows == 1)", m);
         if (use_x3 && hoist && p->ad_proj_cache) {
             rc = ranker_x3_run(p, nullptr, 0, c.U, c.du, (const long long*)ad_rowmap, r0, (int)user_rowdiv, n_cache, m, c.X0,
-                               out_logits + r0, (long long)ld_logits, st);
+                               out_logits + r0, (long long)ld_logits, st, ctr_first, trunk_r0, ld_trunk);
         } else {
             rc = ranker_project_rows(c, EmbConcatRows::ranker_rows(p, (const long long*)user_cat, numerical, user_rowdiv,
                                                                    (const long long*)ad_cat, (const long long*)ad_rowmap,
                                                                    n_ad_rows, r0, m));
             if (rc) return rc;
-            rc = use_x3 ? ranker_x3_run(p, c.X, dm, nullptr, 0, nullptr, 0, 1, 0, m, c.X0, out_logits + r0, ld_logits, st)
+            rc = use_x3 ? ranker_x3_run(p, c.X, dm, nullptr, 0, nullptr, 0, 1, 0, m, c.X0, out_logits + r0, ld_logits, st, ctr_first,
+                                        trunk_r0, ld_trunk)
                         : ranker_layer_chain(c, m, out_logits + r0, ld_logits);
         }
         if (rc) return rc;
     }
+    return AMDREC_OK;
+}
+
+extern "C" int amdrec_ranker_forward(const amdrec_ranker_params* p, const int64_t* user_cat, const float* numerical,
+                                     int64_t user_rowdiv, const int64_t* ad_cat, const int64_t* ad_rowmap,
+                                     int64_t rows, float* out_logits, int64_t ld_logits, int* bad_index_flag,
+                                     int64_t n_user_rows, int64_t n_ad_rows, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    return ranker_forward(p, user_cat, numerical, user_rowdiv, ad_cat, ad_rowmap, rows, out_logits, ld_logits, bad_index_flag,
+                          n_user_rows, n_ad_rows, workspace, workspace_bytes, stream, false, nullptr, 0);
+}
+
+extern "C" int amdrec_ranker_forward_ctr_first(const amdrec_ranker_params* p, const int64_t* user_cat, const float* numerical,
+                                               int64_t user_rowdiv, const int64_t* ad_cat, const int64_t* ad_rowmap,
+                                               int64_t rows, float* out_logits, int64_t ld_logits, int* bad_index_flag,
+                                               int64_t n_user_rows, int64_t n_ad_rows, float* trunk_out, int64_t ld_trunk,
+                                               void* workspace, size_t workspace_bytes, void* stream) {
+    return ranker_forward(p, user_cat, numerical, user_rowdiv, ad_cat, ad_rowmap, rows, out_logits, ld_logits, bad_index_flag,
+                          n_user_rows, n_ad_rows, workspace, workspace_bytes, stream, true, trunk_out, ld_trunk);
+}
+
+extern "C" int amdrec_ranker_ctr_first_supported(const amdrec_ranker_params* p, int64_t rows) {
+    return p != nullptr && ranker_check(p) == AMDREC_OK && rows >= 1 && ranker_x3_ctr_first_supported(p, rows, ROW_CHUNK) ? 1 : 0;
+}
+
+extern "C" int amdrec_ranker_ctr_first_workspace(const amdrec_ranker_params* p, int64_t rows, int64_t n_winner_rows,
+                                                 size_t* bytes) {
+    int rc = ranker_check(p);
+    if (rc) return rc;
+    REQUIRE(bytes && rows >= 0 && n_winner_rows >= 0, "bad arguments");
+    const size_t pass1 = rows > 0 ? RankerWs(p, rows, nullptr).bytes() : 0, pass2 = ranker_x3_winner_workspace(p, n_winner_rows);
+    *bytes = pass1 > pass2 ? pass1 : pass2;
     return AMDREC_OK;
 }

@@ -427,7 +427,7 @@ __device__ __forceinline__ void run_chain(const Program& G, const Input& in, lon
 
     f32x4 x[16];
     if (in.X != nullptr) {
-        load_rows(x, in.X + rowc * in.ldx, g);
+        load_rows(x, in.X + x3::dense_row(in, rowc) * in.ldx, g);
     } else {
         const long long gr = in.row_base + rowc;
         long long a = in.rowmap ? in.rowmap[gr] : gr;

@@ -481,7 +481,7 @@ __global__ __launch_bounds__(64 * WAVES) void ranker_x3c_kernel(Program G, Input
     const long long rowc = row_ok ? row : rows - 1;
     f32x4 x[16];                                                  // every wave loads the workgroup's 16 rows
     if (in.X != nullptr) {
-        load_rows(x, in.X + rowc * in.ldx, g);
+        load_rows(x, in.X + x3::dense_row(in, rowc) * in.ldx, g);
     } else {
         const long long gr = in.row_base + rowc;
         long long a = in.rowmap ? in.rowmap[gr] : gr;

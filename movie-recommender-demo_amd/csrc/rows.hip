@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void select_topk_kernel(const float* logits, l
         if (out_slots) out_slots[u * top_k + i] = slot;
         for (int t = 0; t < n_tasks; ++t) {
             float x = valid ? logits[(long long)t * ld + u * k_c + slot] : -INFINITY;
-            out_scores[((long long)t * n_users + u) * top_k + i] = 1.0f / (1.0f + expf(-x));
+            out_scores[((long long)t * n_users + u) * top_k + i] = sigmoid_prob(x);
         }
     }
 }
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void select_topk_small_kernel(const float* log
         if (out_slots) out_slots[u * top_k + r] = slot;
         for (int t = 0; t < n_tasks; ++t) {
             const float x = valid ? logits[(long long)t * ld + u * k_c + slot] : -INFINITY;
-            out_scores[((long long)t * n_users + u) * top_k + r] = 1.0f / (1.0f + expf(-x));
+            out_scores[((long long)t * n_users + u) * top_k + r] = sigmoid_prob(x);
         }
     }
 }

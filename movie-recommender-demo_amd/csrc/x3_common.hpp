@@ -106,7 +106,21 @@ struct Input {
     const float* hcache;       // PH_FFN_LN_CACHED: P [n_cache][ldh] (rows as in `cache`) and Q [n_users][ldu] (= U + 256)
     long long ldh;
     const float* Q;
+    // gathered dense form (16-row kernels only; X set): row r reads X[(r / top_k) * k_c + slots[r]] - the winners of a
+    // selection (amdrec_select_topk's out_slots) out of the rows it selected from; clamped into [0, n_x), a negative slot
+    // (no winner: its result is discarded) reads row 0.  slots == nullptr: row r reads X[r].
+    const int* slots;          // [rows]
+    int top_k, k_c;
+    long long n_x;             // rows of X
 };
+
+// the row of X that row r of the launch reads (r < 2^31 with slots: amdrec_ranker_winner_heads)
+__device__ __forceinline__ long long dense_row(const Input& in, long long r) {
+    if (in.slots == nullptr) return r;
+    const int s = in.slots[r];
+    const long long a = (long long)((uint32_t)r / (uint32_t)in.top_k) * in.k_c + s;
+    return s < 0 ? 0 : (a >= in.n_x ? in.n_x - 1 : a);
+}
 
 // Elimination switches for tools/x3_probe.hip (0 in the product): 1 = no weight DMA and no wait for it, 2 = no
 // per-chunk barrier, 4 = no fragment reads from LDS (stale registers), 8 = no hidden-tile conversion (stale planes);
