@@ -31,7 +31,8 @@ extern "C" {
                                * struct's end, amdrec_ranker_params.ad_hidden_cache - the number stays, the library and its
                                * binding ship together and the struct layouts are checked against the compiler, tests/test_abi.py;
                                * amdrec_select_topk then gained its cand_pos argument under the same rule; so did CTR-first ranking:
-                               * amdrec_ranker_forward_ctr_first ..., amdrec_x3_weights.stream_ctr ... at the struct's end) */
+                               * amdrec_ranker_forward_ctr_first ..., amdrec_x3_weights.stream_ctr ... at the struct's end; and
+                               * the eligibility masks: amdrec_flat_search_eligible, amdrec_flat_search_mixed_eligible, added exports) */
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -73,6 +74,31 @@ int amdrec_flat_search_mixed(const float* corpus, int64_t nrows, int64_t ld_corp
                              int64_t pos_offset, float* out_scores /*[nq][k]*/,
                              int64_t* out_pos /*[nq][k]*/, void* workspace, size_t workspace_bytes,
                              int* n_fixup, void* stream);
+
+/* Per-request eligibility masks: the same two searches over the rows each query may be shown.  One 64-bit tag per
+ * corpus row (`tags`, exactly nrows words; the library does not interpret the bits), two 64-bit words per query; row r is
+ * eligible for query q iff
+ *     (tags[r] & require_all[q]) == require_all[q]  and  (require_any[q] == 0 or (tags[r] & require_any[q]) != 0),
+ * so require_all = require_any = 0 admits every row.  Result: the exact top-k of the query's ELIGIBLE rows in the search's
+ * own order (score descending, ties -> lower position), the scores the plain search returns for those rows; the NaN rule
+ * above holds; with fewer than k eligible rows the tail is unfilled (-inf / -1) - such a query takes the exact
+ * fix-up scan and is counted in n_fixup.  The predicate is tested inside the corpus pass
+ * where a row enters the candidate pool, so the number of ineligible rows is not limited (unlike an exclusion list).
+ * All three are device pointers and all three are required (tags 64-byte aligned, the masks 8-byte aligned); workspace: the
+ * size the matching *_workspace query gives. */
+int amdrec_flat_search_eligible(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
+                                const float* queries, int64_t nq, int64_t ld_queries, int k,
+                                int64_t pos_offset, float* out_scores /*[nq][k]*/,
+                                int64_t* out_pos /*[nq][k]*/, void* workspace, size_t workspace_bytes,
+                                int* n_fixup, void* stream, const uint64_t* tags /*[nrows]*/,
+                                const uint64_t* require_all /*[nq]*/, const uint64_t* require_any /*[nq]*/);
+int amdrec_flat_search_mixed_eligible(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
+                                      const uint16_t* corpus_bf16, int64_t ld_bf16, const float* max_norm,
+                                      const float* queries, int64_t nq, int64_t ld_queries, int k,
+                                      int64_t pos_offset, float* out_scores /*[nq][k]*/,
+                                      int64_t* out_pos /*[nq][k]*/, void* workspace, size_t workspace_bytes,
+                                      int* n_fixup, void* stream, const uint64_t* tags /*[nrows]*/,
+                                      const uint64_t* require_all /*[nq]*/, const uint64_t* require_any /*[nq]*/);
 
 /* ---- retrieval: IVF-Flat (faiss IndexIVFFlat, METRIC_INNER_PRODUCT, IndexFlatIP quantizer:
  * faiss_retrieval.py:50-55, searched at :150-155 with index.nprobe = nprobe) ---------------------

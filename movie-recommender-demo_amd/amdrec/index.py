@@ -26,7 +26,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, exclude as _exclude, ivf, ivfpq, rows_edit as _rows_edit
+from . import _lib, eligible as _eligible, exclude as _exclude, ivf, ivfpq, rows_edit as _rows_edit
 
 _MAGIC = b"AMDRECIX1"
 ADD_BATCH = 1 << 18            # IVFPQ add: rows normalised and encoded per batch (256 MB of fp32 at d = 256)
@@ -130,6 +130,7 @@ class FAISSIndex:
         self._mixed = self.index_type == "Flat" and self.prefilter == "bf16" and self.dimension % 8 == 0
         self._xb16 = torch.empty((0, self.dimension), dtype=torch.bfloat16, device=self.device)
         self._maxnorm = torch.zeros(2, dtype=torch.float32, device=self.device)     # [max row norm, max row rounding-error norm]
+        self._tags: Optional[torch.Tensor] = None    # int64 [capacity] eligibility tags (amdrec.eligible), allocated on first use
         self._identity = True          # ids == arange(n): remap is the identity
         self._nonfinite = False        # Flat: a stored row holds a NaN, so a search can leave slots unfilled with k <= n
         self.n_fixup_out: Optional[torch.Tensor] = None    # Flat: device int32[1] that receives the C entry's n_fixup (diagnostics)
@@ -178,6 +179,8 @@ class FAISSIndex:
             new[:self._n].copy_(t[:self._n])
             return new
         self._ids = grown(self._ids)
+        if self._tags is not None:
+            self._tags = grown(self._tags)
         if self._keeps_rows:
             self._xb = grown(self._xb)
             if self._mixed:
@@ -202,6 +205,37 @@ class FAISSIndex:
         x, y = self._xb[lo:hi], self._xb16[lo:hi]
         _lib.check(lib.amdrec_bf16_rows(_lib.ptr(x), hi - lo, x.stride(0), self.dimension, _lib.ptr(y), y.stride(0),
                                         _lib.ptr(self._maxnorm), _lib.stream_ptr(self.device)))
+
+    def _check_masks(self, require_all, require_any) -> bool:
+        """Were eligibility masks passed?  Only a Flat index takes them (checked before the library is touched)."""
+        if require_all is None and require_any is None:
+            return False
+        if self.index_type != "Flat":
+            raise NotImplementedError(
+                f"eligibility masks (require_all / require_any) are implemented for the Flat index only; the {self.index_type} "
+                "scan kernels do not test the predicate yet - that is the follow-up (DESIGN.md, 'Per-request eligibility masks')")
+        return True
+
+    def _ensure_tags(self) -> torch.Tensor:
+        """The tag words [capacity], allocated on first use: rows that were never given a tag have tag 0."""
+        if self._tags is None:
+            self._tags = torch.zeros((self._ids.shape[0],), dtype=torch.int64, device=self.device)
+        return self._tags
+
+    def set_tags(self, tags):
+        """Replace the tag word of every row: ``tags`` [ntotal] (anything amdrec.eligible.as_words takes, or a device int64
+        tensor).  Out of place - a new tensor is swapped in and the old one is never written -, so a search in flight or a
+        captured graph keeps the tags it started with."""
+        words = _eligible.device_words(tags, self._n, self.device)
+        new = torch.zeros((self._ids.shape[0],), dtype=torch.int64, device=self.device)
+        new[:self._n].copy_(words)
+        self._tags = new
+
+    def get_tags(self) -> torch.Tensor:
+        """The tag words, device int64 [ntotal] (a copy; zeros for an index that never saw a tag)."""
+        if self._tags is None:
+            return torch.zeros((self._n,), dtype=torch.int64, device=self.device)
+        return self._tags[:self._n].clone()
 
     def _note_nonfinite(self, x):
         """Flat: remember whether a stored row is non-finite (one reduction and a host read at add / load time, so that
@@ -239,9 +273,11 @@ class FAISSIndex:
         """The trained coarse quantizer [nlist, dimension] (device tensor), or None."""
         return None if self._ivf is None else self._ivf.centroids
 
-    def add(self, embeddings, ad_ids: Optional[List] = None):
+    def add(self, embeddings, ad_ids: Optional[List] = None, tags=None):
         """faiss_retrieval.py:97-127.  A Flat index also checks the added rows for non-finite values (_note_nonfinite: one
-        reduction over them and a host read, i.e. add() synchronises), so that search_device never has to."""
+        reduction over them and a host read, i.e. add() synchronises), so that search_device never has to.
+        ``tags``: one 64-bit eligibility word per added row (amdrec.eligible); without it the rows get tag 0, and an index
+        that never sees a tag keeps no tag tensor at all."""
         if ad_ids is None and not self._default_ids_ok:
             raise ValueError("add() without ad_ids after remove_ids(): default ids are corpus positions, and the removal has "
                              "moved the positions under the ids that stayed; pass ad_ids")
@@ -257,6 +293,7 @@ class FAISSIndex:
         if src.dim() != 2 or src.shape[1] != self.dimension:
             raise ValueError(f"expected [n, {self.dimension}] embeddings, got {tuple(src.shape)}")
         m = src.shape[0]
+        new_tags = None if tags is None else _eligible.device_words(tags, m, self.device)    # (refused before anything changes)
         self._reserve(self._n + m)
         if not self._keeps_rows:
             # normalised and encoded batch by batch: only the codes stay (and, with refine, the kept form of the rows).
@@ -295,6 +332,10 @@ class FAISSIndex:
                 self._identity = False
                 new_ids = torch.full((m,), -1, dtype=torch.int64, device=self.device)
         self._ids[self._n:self._n + m].copy_(new_ids)                # :123
+        if new_tags is not None:
+            self._ensure_tags()[self._n:self._n + m].copy_(new_tags)
+        elif self._tags is not None:
+            self._tags[self._n:self._n + m].zero_()
         if self._pq is not None:
             self._pq.commit(pq_new)
         elif self._ivf is not None:
@@ -347,6 +388,8 @@ class FAISSIndex:
             self._host_ids = [self._host_ids[p] for p in kept.cpu().tolist()]
         self._host_pos = None                    # (keyed by len(_host_ids) alone: a later add of as many rows would revive it)
         self._ids = gather(self._ids)
+        if self._tags is not None:
+            self._tags = gather(self._tags)
         if self._keeps_rows:
             self._xb = gather(self._xb)
         self._n = m
@@ -368,7 +411,8 @@ class FAISSIndex:
 
     def resident_tensors(self) -> list:
         """Every device tensor the index keeps between calls (a captured graph's kernels point at them)."""
-        return [self._xb, self._ids, self._xb16, self._maxnorm] + (self._state.resident_tensors() if self._state else [])
+        return ([self._xb, self._ids, self._xb16, self._maxnorm] + ([] if self._tags is None else [self._tags]) +
+                (self._state.resident_tensors() if self._state else []))
 
     @property
     def id_map(self) -> list:
@@ -378,7 +422,8 @@ class FAISSIndex:
 
     def search_device(self, queries: torch.Tensor, k: int, normalize: bool = True,
                       return_positions: bool = False, pos_offset: int = 0, exclude: Optional[torch.Tensor] = None,
-                      _exclude_positions: bool = False):
+                      _exclude_positions: bool = False, require_all: Optional[torch.Tensor] = None,
+                      require_any: Optional[torch.Tensor] = None):
         """Device-to-device search, asynchronous on the current stream.
         -> (ids int64 [nq,k], scores float32 [nq,k]) on the device.  ``return_positions``: corpus
         positions (+ ``pos_offset``, the shard's first global row) instead of ids, -1 = unfilled.
@@ -393,9 +438,15 @@ class FAISSIndex:
         ``exclude``: device int64 [nq, E], per query the ad ids that must not be returned (negative = padding): the
         unfiltered search for k + E with those ids removed, order kept, cut to k (amdrec.exclude has the contract;
         k + E <= AMDREC_MAX_K).  It applies to ids also under ``return_positions``.  None or E = 0: the plain search, not
-        one launch more."""
+        one launch more.
+        ``require_all`` / ``require_any`` (Flat only): device int64 [nq], the queries' eligibility masks against the rows'
+        tags (amdrec.eligible has the contract): the exact top-k of each query's eligible rows, the tail unfilled when
+        fewer than k are eligible.  Where one is given the other defaults to 0; both None: the plain search, not one
+        launch more.  With ``exclude`` the filtered search runs for k + E.  IVF / IVFPQ raise NotImplementedError."""
+        masked = self._check_masks(require_all, require_any)
         if exclude is not None and exclude.shape[-1] > 0:
-            return self._search_excluding(queries, k, normalize, return_positions, pos_offset, exclude, _exclude_positions)
+            return self._search_excluding(queries, k, normalize, return_positions, pos_offset, exclude, _exclude_positions,
+                                          require_all, require_any)
         q = _lib.require_gpu(queries, "queries")
         if q.dim() != 2 or q.shape[1] != self.dimension:
             raise ValueError(f"expected [nq, {self.dimension}] queries, got {tuple(q.shape)}")
@@ -410,6 +461,9 @@ class FAISSIndex:
         else:
             q = q.contiguous()
         nq = q.shape[0]
+        elig = None
+        if masked:
+            elig = (self._ensure_tags(), *_eligible.device_masks(require_all, require_any, nq, self.device))
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         pos = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         off = pos_offset if return_positions else 0
@@ -419,16 +473,17 @@ class FAISSIndex:
             self._pq.search(q, k, self.nprobe, scores, pos, pos_offset=off)
         elif self._mixed:
             flat_search_mixed(self._xb, self._xb16, self._maxnorm, self._n, q, k, scores, pos, pos_offset=off,
-                              n_fixup=self.n_fixup_out)
+                              n_fixup=self.n_fixup_out, elig=elig)
         else:
-            flat_search(self._xb, self._n, q, k, scores, pos, pos_offset=off, n_fixup=self.n_fixup_out)
+            flat_search(self._xb, self._n, q, k, scores, pos, pos_offset=off, n_fixup=self.n_fixup_out, elig=elig)
         if return_positions or self._identity:
             # identity map: id == position for filled slots; unfilled (-1) slots map to
             # id_map[-1] in the reference (:159) - reproduce that too
             if return_positions:
                 return pos, scores
-            # a slot can be unfilled: k > n, an IVF probe set, a stored NaN row (otherwise only under a NaN query)
-            if self._n and (k > self._n or self._state is not None or self._nonfinite):
+            # a slot can be unfilled: k > n, an IVF probe set, a stored NaN row, fewer than k eligible rows (otherwise only
+            # under a NaN query)
+            if self._n and (k > self._n or self._state is not None or self._nonfinite or masked):
                 pos = torch.where(pos < 0, pos + self._n, pos)
             return pos, scores
         lib = _lib.load()
@@ -437,12 +492,14 @@ class FAISSIndex:
                                         _lib.stream_ptr(self.device)))
         return ids, scores
 
-    def _search_excluding(self, queries, k, normalize, return_positions, pos_offset, exclude, exclude_positions):
+    def _search_excluding(self, queries, k, normalize, return_positions, pos_offset, exclude, exclude_positions,
+                          require_all=None, require_any=None):
         """search_device with an exclusion block: the unfiltered search for kc = k + E, the remap to ids where ids are not
         positions, amdrec_exclude_compact on the ids, and the id path's treatment of unfilled slots after that."""
         kc = _exclude.check_exclude(k, exclude.shape[-1])              # (before the library is touched)
         excl = _lib.require_gpu(exclude, "exclude", torch.int64)
-        pos_c, sc_c = self.search_device(queries, kc, normalize=normalize, return_positions=True)
+        pos_c, sc_c = self.search_device(queries, kc, normalize=normalize, return_positions=True, require_all=require_all,
+                                         require_any=require_any)
         fill = float("inf") if self.index_type == "IVFPQ" else float("-inf")
         if self._identity or exclude_positions:                      # the keys to match are the positions themselves
             pos, scores, _ = _exclude.compact(pos_c, sc_c, None, excl, k, fill)
@@ -489,22 +546,28 @@ class FAISSIndex:
             self._host_pos = (len(self._host_ids), where)
         return self._host_pos[1]
 
-    def search(self, query_embeddings, k: int = 100, return_distances: bool = True, exclude=None):
+    def search(self, query_embeddings, k: int = 100, return_distances: bool = True, exclude=None, require_all=None,
+               require_any=None):
         """faiss_retrieval.py:129-166.  numpy in, numpy out: (ad_ids, distances).  ``exclude``: one sequence of ad ids per
-        query (or an integer array [nq, E], negative = padding) that must not be returned: see search_device."""
-        return self._search(query_embeddings, k, return_distances, self._exclude_block(exclude, len(query_embeddings)))
+        query (or an integer array [nq, E], negative = padding) that must not be returned: see search_device.
+        ``require_all`` / ``require_any``: the queries' eligibility masks, one 64-bit word each (one int for all queries, a
+        sequence of ints, a uint64 / int64 array): see search_device."""
+        self._check_masks(require_all, require_any)
+        nq = len(query_embeddings)
+        return self._search(query_embeddings, k, return_distances, self._exclude_block(exclude, nq),
+                            _eligible.device_masks(require_all, require_any, nq, self.device))
 
-    def _search(self, query_embeddings, k, return_distances, excl):
-        """search with the exclusion lists already as a device block (_exclude_block)."""
+    def _search(self, query_embeddings, k, return_distances, excl, masks=(None, None)):
+        """search with the exclusion lists already as a device block (_exclude_block) and the masks as device words."""
         q = self._to_device_f32(query_embeddings)
         t0 = time.time()
         if self._host_ids is not None:
             pos, scores = self.search_device(q, k, normalize=True, return_positions=True, exclude=excl,
-                                             _exclude_positions=True)
+                                             _exclude_positions=True, require_all=masks[0], require_any=masks[1])
             idm = np.asarray(self._host_ids, dtype=object)
             ad_ids = idm[pos.cpu().numpy()]                          # pos == -1 -> id_map[-1]
         else:
-            ids, scores = self.search_device(q, k, normalize=True, exclude=excl)
+            ids, scores = self.search_device(q, k, normalize=True, exclude=excl, require_all=masks[0], require_any=masks[1])
             ad_ids = ids.cpu().numpy()
         distances = scores.cpu().numpy()
         self._log(f"Search completed in {(time.time() - t0) * 1000:.2f}ms for {len(q)} queries")
@@ -512,14 +575,19 @@ class FAISSIndex:
             return ad_ids, distances
         return ad_ids
 
-    def batch_search(self, query_embeddings, k: int = 100, batch_size: int = 1000, exclude=None):
+    def batch_search(self, query_embeddings, k: int = 100, batch_size: int = 1000, exclude=None, require_all=None,
+                     require_any=None):
         """faiss_retrieval.py:168-194.  ``exclude`` (as in search) is padded once, to the longest list of the whole call,
-        and sliced with the queries: the chunking does not change the result."""
+        and sliced with the queries: the chunking does not change the result.  ``require_all`` / ``require_any`` (as in
+        search) are sliced with the queries too."""
         all_ids, all_d = [], []
+        self._check_masks(require_all, require_any)
         excl = self._exclude_block(exclude, len(query_embeddings))
+        ma, my = _eligible.device_masks(require_all, require_any, len(query_embeddings), self.device)
         for i in range(0, len(query_embeddings), batch_size):
             ids, d = self._search(query_embeddings[i:i + batch_size], k, True,
-                                  None if excl is None else excl[i:i + batch_size])
+                                  None if excl is None else excl[i:i + batch_size],
+                                  (None, None) if ma is None else (ma[i:i + batch_size], my[i:i + batch_size]))
             all_ids.append(ids)
             all_d.append(d)
         return np.vstack(all_ids), np.vstack(all_d)
@@ -534,6 +602,8 @@ class FAISSIndex:
         arrays = [("ids", self._ids[:self._n].cpu().numpy())]
         if self._keeps_rows:
             arrays.insert(0, ("xb", self._xb[:self._n].cpu().numpy()))
+        if self._tags is not None:                                   # (absent: an index that never saw a tag, as every earlier file)
+            arrays.append(("tags", self._tags[:self._n].cpu().numpy()))
         if self._state is not None:                                  # IVFPQ: codes, centroids, codebooks, assignment
             arrays += self._state.export_arrays()
         header = {"dimension": self.dimension, "index_type": self.index_type, "nlist": self.nlist,
@@ -580,6 +650,8 @@ class FAISSIndex:
         if self._keeps_rows:
             self._xb[:n].copy_(torch.from_numpy(arrays["xb"].copy()))
         self._ids[:n].copy_(torch.from_numpy(arrays["ids"].copy()))
+        if "tags" in arrays:
+            self._ensure_tags()[:n].copy_(torch.from_numpy(arrays["tags"].copy()))
         self._n = n
         self._shadow_rows(0, n)
         if self._keeps_rows:
@@ -631,9 +703,21 @@ def benchmark_faiss_index(dimension: int = 256, num_vectors: int = 1000000, num_
     return results
 
 
+def _elig_args(elig, n, nq):
+    """(tags [>= n], require_all [nq], require_any [nq]) device int64 -> the three trailing pointers of the *_eligible entries."""
+    tags, ma, my = (_lib.require_gpu(t, name, torch.int64) for t, name in zip(elig, ("tags", "require_all", "require_any")))
+    if tags.dim() != 1 or tags.shape[0] < n or not tags.is_contiguous():
+        raise ValueError(f"tags must be a contiguous int64 vector of at least {n} words, got {tuple(tags.shape)}")
+    for t, name in ((ma, "require_all"), (my, "require_any")):
+        if t.shape != (nq,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int64 [{nq}], got {tuple(t.shape)}")
+    return _lib.ptr(tags), _lib.ptr(ma), _lib.ptr(my)
+
+
 def flat_search(xb: torch.Tensor, n: int, q: torch.Tensor, k: int, out_scores: torch.Tensor,
-                out_pos: torch.Tensor, pos_offset: int = 0, n_fixup: Optional[torch.Tensor] = None):
-    """amdrec_flat_search on device tensors (rows of xb[:n] and q already L2-normalised)."""
+                out_pos: torch.Tensor, pos_offset: int = 0, n_fixup: Optional[torch.Tensor] = None, elig=None):
+    """amdrec_flat_search on device tensors (rows of xb[:n] and q already L2-normalised).  ``elig``: (tags, require_all,
+    require_any) device int64 -> amdrec_flat_search_eligible."""
     lib = _lib.load()
     dev = q.device
     if q.shape[0] == 0:
@@ -641,16 +725,21 @@ def flat_search(xb: torch.Tensor, n: int, q: torch.Tensor, k: int, out_scores: t
     nbytes = _lib.C.c_size_t(0)
     _lib.check(lib.amdrec_flat_search_workspace(q.shape[0], n, k, _lib.C.byref(nbytes)))
     ws = _lib.WORKSPACE.get(nbytes.value, dev)
-    _lib.check(lib.amdrec_flat_search(
-        _lib.ptr(xb), n, xb.stride(0) if xb.dim() == 2 and xb.shape[0] > 0 else xb.shape[-1], xb.shape[-1],
-        _lib.ptr(q), q.shape[0], q.stride(0), k, pos_offset, _lib.ptr(out_scores), _lib.ptr(out_pos),
-        _lib.ptr(ws), ws.numel(), _lib.ptr(n_fixup), _lib.stream_ptr(dev)))
+    args = (_lib.ptr(xb), n, xb.stride(0) if xb.dim() == 2 and xb.shape[0] > 0 else xb.shape[-1], xb.shape[-1],
+            _lib.ptr(q), q.shape[0], q.stride(0), k, pos_offset, _lib.ptr(out_scores), _lib.ptr(out_pos),
+            _lib.ptr(ws), ws.numel(), _lib.ptr(n_fixup))
+    if elig is None:
+        _lib.check(lib.amdrec_flat_search(*args, _lib.stream_ptr(dev)))
+    else:
+        tail = _elig_args(elig, n, q.shape[0])
+        _lib.check(lib.amdrec_flat_search_eligible(*args, _lib.stream_ptr(dev), *tail))
 
 
 def flat_search_mixed(xb: torch.Tensor, xb16: torch.Tensor, max_norm: torch.Tensor, n: int, q: torch.Tensor, k: int,
                       out_scores: torch.Tensor, out_pos: torch.Tensor, pos_offset: int = 0,
-                      n_fixup: Optional[torch.Tensor] = None):
-    """amdrec_flat_search_mixed on device tensors: xb16 = amdrec_bf16_rows(xb), max_norm = its largest row norm."""
+                      n_fixup: Optional[torch.Tensor] = None, elig=None):
+    """amdrec_flat_search_mixed on device tensors: xb16 = amdrec_bf16_rows(xb), max_norm = its largest row norm.  ``elig``:
+    (tags, require_all, require_any) device int64 -> amdrec_flat_search_mixed_eligible."""
     lib = _lib.load()
     dev = q.device
     if q.shape[0] == 0:
@@ -660,7 +749,11 @@ def flat_search_mixed(xb: torch.Tensor, xb16: torch.Tensor, max_norm: torch.Tens
     _lib.check(lib.amdrec_flat_search_mixed_workspace(q.shape[0], n, k, d, _lib.C.byref(nbytes)))
     ws = _lib.WORKSPACE.get(nbytes.value, dev)
     has = xb.dim() == 2 and xb.shape[0] > 0
-    _lib.check(lib.amdrec_flat_search_mixed(
-        _lib.ptr(xb), n, xb.stride(0) if has else d, d, _lib.ptr(xb16), xb16.stride(0) if has else d,
-        _lib.ptr(max_norm), _lib.ptr(q), q.shape[0], q.stride(0), k, pos_offset, _lib.ptr(out_scores),
-        _lib.ptr(out_pos), _lib.ptr(ws), ws.numel(), _lib.ptr(n_fixup), _lib.stream_ptr(dev)))
+    args = (_lib.ptr(xb), n, xb.stride(0) if has else d, d, _lib.ptr(xb16), xb16.stride(0) if has else d,
+            _lib.ptr(max_norm), _lib.ptr(q), q.shape[0], q.stride(0), k, pos_offset, _lib.ptr(out_scores),
+            _lib.ptr(out_pos), _lib.ptr(ws), ws.numel(), _lib.ptr(n_fixup))
+    if elig is None:
+        _lib.check(lib.amdrec_flat_search_mixed(*args, _lib.stream_ptr(dev)))
+    else:
+        tail = _elig_args(elig, n, q.shape[0])
+        _lib.check(lib.amdrec_flat_search_mixed_eligible(*args, _lib.stream_ptr(dev), *tail))

@@ -27,7 +27,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import _lib, exclude as _exclude, rows_edit as _rows_edit
+from . import _lib, eligible as _eligible, exclude as _exclude, rows_edit as _rows_edit
 from .index import FAISSIndex
 from .ranker import TransformerRanker
 from .towers import TwoTowerModel
@@ -144,12 +144,15 @@ class AdRecommenderInference:
         num = ((num - pp.mean) / pp.scale).astype(np.float32)
         return torch.tensor([cat], dtype=torch.long), torch.from_numpy(num[None, :])
 
-    def preprocess_batch(self, user_data_list: list, exclude: Optional[np.ndarray] = None):
+    def preprocess_batch(self, user_data_list: list, exclude: Optional[np.ndarray] = None,
+                         masks: Optional[np.ndarray] = None):
         """Batch form of preprocess_user_features with the numerical transform on the device: categorical strings
         are label-encoded on the host (dictionary lookups), raw numericals are shipped as one float32 block and
         log1p / standardised by amdrec_prep_numerical.  -> (user_categorical [B,6] int64, user_numerical [B,13]
         float32), both on the device.  ``exclude`` (int64 [B, E], amdrec.exclude.pad_exclusions) rides in the same
-        staging block and copy; the result is then (user_categorical, user_numerical, exclude on the device)."""
+        staging block and copy; the result is then (user_categorical, user_numerical, exclude on the device).  ``masks``
+        (int64 [2, B]: the users' require_all and require_any words, amdrec.eligible) ride there too and come back last,
+        as a device [2, B]."""
         pp = self.preprocessor
         if pp is None:
             raise ValueError("no preprocessor loaded")
@@ -163,7 +166,9 @@ class AdRecommenderInference:
         # copies cost ~25 us of a 0.4 ms request); the block is reused once its previous copy has completed
         cat_bytes = B * nc * 8
         ex_off = (cat_bytes + B * nn_ * 4 + 7) // 8 * 8                 # the int64 exclusion block, 8-byte aligned
-        host, done = self._staging(cat_bytes + B * nn_ * 4 if exclude is None else ex_off + exclude.size * 8)
+        m_off = ex_off + (0 if exclude is None else exclude.size * 8)   # the int64 mask words
+        host, done = self._staging(m_off + 2 * B * 8 if masks is not None else
+                                   (cat_bytes + B * nn_ * 4 if exclude is None else m_off))
         hv = host.numpy()
         if nc:
             hv[:cat_bytes].view(np.int64).reshape(B, nc)[:] = [[pp.encode(c, u["categorical"].get(c, "missing")) for c in cols]
@@ -172,7 +177,9 @@ class AdRecommenderInference:
             hv[cat_bytes:cat_bytes + B * nn_ * 4].view(np.float32).reshape(B, nn_)[:] = [
                 [float(u["numerical"].get(c, 0)) for c in pp.numerical_cols] for u in user_data_list]
         if exclude is not None:
-            hv[ex_off:].view(np.int64).reshape(exclude.shape)[:] = exclude
+            hv[ex_off:m_off].view(np.int64).reshape(exclude.shape)[:] = exclude
+        if masks is not None:
+            hv[m_off:m_off + 2 * B * 8].view(np.int64).reshape(2, B)[:] = masks
         blk = host.to(dev, non_blocking=True)
         done.record(torch.cuda.current_stream(dev))
         cat = blk[:cat_bytes].view(torch.int64).view(B, nc)
@@ -181,9 +188,12 @@ class AdRecommenderInference:
         lib = _lib.load()
         _lib.check(lib.amdrec_prep_numerical(_lib.ptr(x), _lib.ptr(self._pp_dev[1]), _lib.ptr(self._pp_dev[2]),
                                              _lib.ptr(out), x.shape[0], x.shape[1], _lib.stream_ptr(dev)))
+        res = (cat, out)
         if exclude is not None:
-            return cat, out, blk[ex_off:].view(torch.int64).view(exclude.shape)
-        return cat, out
+            res += (blk[ex_off:m_off].view(torch.int64).view(exclude.shape),)
+        if masks is not None:
+            res += (blk[m_off:m_off + 2 * B * 8].view(torch.int64).view(2, B),)
+        return res
 
     def _staging(self, nbytes: int, slot: str = "in"):
         """Pinned host block of at least ``nbytes`` + the event of its last use (waited for before it is handed out again).
@@ -220,12 +230,14 @@ class AdRecommenderInference:
         return mode, None
 
     # -- the device hot path ------------------------------------------------------------------
-    def _stage1(self, uc, un, stage1_k, check_indices, exclude=None):
+    def _stage1(self, uc, un, stage1_k, check_indices, exclude=None, masks=(None, None)):
         # the tower's launch also applies the search's query normalisation (faiss_retrieval.py:147): one launch fewer
         emb = self.two_tower_model.user_tower.encode(uc, un, check_indices=check_indices, renormalize=True)   # :223-227
         # exclude (device int64 [B, E] ad ids, or None): removed here, so the ranker only ever sees eligible ads
+        # masks (device int64 [B] require_all / require_any, or None): tested inside the search, likewise
         return self.faiss_index.search_device(emb, stage1_k, normalize=False,                  # :230-232
-                                              return_positions=True, exclude=exclude)
+                                              return_positions=True, exclude=exclude, require_all=masks[0],
+                                              require_any=masks[1])
 
     def _stage2(self, uc, un, cand_pos, top_k, check_indices, ids_are_positions=False, mark=None, out=None,
                 excluded=False, heads=None):
@@ -291,7 +303,8 @@ class AdRecommenderInference:
     @torch.no_grad()
     def recommend_device(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor, top_k: int = 10,
                          stage1_k: int = 500, check_indices: bool = False,
-                         exclude_ad_ids: Optional[torch.Tensor] = None, heads: Optional[str] = None):
+                         exclude_ad_ids: Optional[torch.Tensor] = None, heads: Optional[str] = None,
+                         require_all: Optional[torch.Tensor] = None, require_any: Optional[torch.Tensor] = None):
         """[B,6] / [B,13] device tensors -> dict of device tensors, no host synchronisation:
         ad_ids [B,top_k] int64, scores [3,B,top_k] float32 (sigmoid of the logits), candidate_ids
         [B,stage1_k], candidate_scores [B,stage1_k], logits [3, B*stage1_k].  candidate_scores are the index's own
@@ -302,9 +315,12 @@ class AdRecommenderInference:
         ``exclude_ad_ids``: device int64 [B, E], per user the ad ids that must not be recommended (negative = padding;
         stage1_k + E <= AMDREC_MAX_K): stage 1 searches stage1_k + E and drops them on the device (FAISSIndex.search_device),
         so candidate_ids / candidate_scores and everything after them hold eligible ads only.
+        ``require_all`` / ``require_any``: device int64 [B], per user the eligibility masks against the ads' tags
+        (amdrec.eligible; Flat index): stage 1 is the exact top-stage1_k of the ads the user may be shown, however many
+        are ineligible; a user with fewer eligible ads gets a short candidate list.  Both None: the plain search.
         Short candidate lists: stage 1 leaves a slot unfilled (position -1; candidate_scores -inf, +inf for IVFPQ) when
-        stage1_k exceeds the corpus, with narrow IVF / IVFPQ probes, with a stored NaN row or a NaN query, after exclusions
-        and after remove_ads.  Such a slot is not a candidate: it ranks after every real candidate (those with a NaN logit
+        stage1_k exceeds the corpus, with narrow IVF / IVFPQ probes, with a stored NaN row or a NaN query, after exclusions,
+        under eligibility masks and after remove_ads.  Such a slot is not a candidate: it ranks after every real candidate (those with a NaN logit
         included) and is reported only where a user has fewer than top_k real candidates, as ad_ids == -1 with scores 0.0
         for every task - the same tail that top_k > stage1_k gives.  The real ads of a row are distinct and were all
         retrieved by stage 1.  candidate_ids keeps the search's convention for an unfilled slot (id_map[-1]) and its entry
@@ -315,19 +331,24 @@ class AdRecommenderInference:
         uc = _lib.require_gpu(user_categorical, "user_categorical")
         un = _lib.require_gpu(user_numerical, "user_numerical")
         excluded = exclude_ad_ids is not None and exclude_ad_ids.shape[-1] > 0
-        cand_pos, cand_scores = self._stage1(uc, un, stage1_k, check_indices, exclude_ad_ids if excluded else None)
-        out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded, heads=heads)
+        masked = require_all is not None or require_any is not None
+        cand_pos, cand_scores = self._stage1(uc, un, stage1_k, check_indices, exclude_ad_ids if excluded else None,
+                                             (require_all, require_any))
+        # (excluded: "a slot can be unfilled" - true after a filtered stage 1 as well)
+        out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded or masked, heads=heads)
         out["candidate_scores"] = cand_scores
         return out
 
     def capture(self, batch_size: int, top_k: int = 10, stage1_k: int = 500, warmup: int = 2,
-                max_exclude: int = 0) -> "GraphedRecommender":
+                max_exclude: int = 0, eligibility: bool = False) -> "GraphedRecommender":
         """Capture one recommend_device call for a fixed batch shape into a HIP graph (the ~40 kernel
         launches of a request are host-launch-bound at small batch: 1.76 ms eager at B = 1) and return a
         replayer.  Weights, index and ad table must not change afterwards.  ``max_exclude`` > 0: the graph also holds a
         static [batch_size, max_exclude] exclusion buffer (stage 1 always searches stage1_k + max_exclude) that the
-        replayer's ``exclude`` argument fills; 0 captures the graph without the exclusion step."""
-        return GraphedRecommender(self, batch_size, top_k, stage1_k, warmup, max_exclude)
+        replayer's ``exclude`` argument fills; 0 captures the graph without the exclusion step.  ``eligibility``: the graph
+        holds static [batch_size] mask buffers and runs the filtered search (the replayer's ``require_all`` /
+        ``require_any`` fill them; the tags are those of capture time); False captures the graph as ever."""
+        return GraphedRecommender(self, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility)
 
     # -- live corpus: ads leave and enter without a rebuild of the index or of the ranker's per-ad caches ------------------
     def remove_ads(self, ad_ids) -> int:
@@ -346,9 +367,10 @@ class AdRecommenderInference:
         self._swap_ad_table(old, new)
         return removed
 
-    def add_ads(self, embeddings, ad_features, ad_ids=None) -> None:
+    def add_ads(self, embeddings, ad_features, ad_ids=None, tags=None) -> None:
         """Insert ads: ``embeddings`` [m, d] go to the index (FAISSIndex.add: ``ad_ids`` as there; required once ads have been
-        removed), ``ad_features`` [m, n_ad_feat] integer rows are appended to the ad-feature table, and the ranker's per-ad
+        removed; ``tags``: the ads' 64-bit eligibility words, as there), ``ad_features`` [m, n_ad_feat] integer rows are
+        appended to the ad-feature table, and the ranker's per-ad
         caches grow by projecting the m new rows only (TransformerRanker.extend_ad_cache).  The feature rows are checked
         against the ranker's ad embedding tables first (IndexError, as an embedding lookup would raise), and a rejected call
         - bad features, or ids the index refuses - leaves index, table and caches as they were.  Out of place, as
@@ -367,7 +389,7 @@ class AdRecommenderInference:
         if feats.numel() and bool(((feats < 0) | (feats >= cards)).any().item()):
             raise IndexError("index out of range in self: an ad_features row is outside the ranker's ad embedding tables")
         n_old = idx.index.ntotal
-        idx.add(embeddings, ad_ids)              # (refuses before it commits anything)
+        idx.add(embeddings, ad_ids, tags=tags)   # (refuses before it commits anything)
         new = torch.cat([old[:n_old], feats])
         if old.shape[0] == n_old:
             self.transformer_ranker.extend_ad_cache(old, new)
@@ -384,28 +406,44 @@ class AdRecommenderInference:
 
     # -- reference API ------------------------------------------------------------------------
     def recommend_ads(self, user_data: dict, top_k: int = 10, stage1_k: int = 500,
-                      return_scores: bool = True, exclude_ad_ids=None) -> dict:
+                      return_scores: bool = True, exclude_ad_ids=None, require_all: int = 0, require_any: int = 0) -> dict:
         """inference.py:199-288.  ``exclude_ad_ids``: the ad ids this user must not be shown (a sequence of integers).
-        Fewer than ``top_k`` real candidates: as batch_recommend."""
+        ``require_all`` / ``require_any``: this request's eligibility masks (64-bit integers; 0 and 0: no constraint, the
+        plain search).  Fewer than ``top_k`` real candidates: as batch_recommend."""
+        masked = bool(require_all) or bool(require_any)
         return self.batch_recommend([user_data], top_k=top_k, stage1_k=stage1_k, return_scores=return_scores,
-                                    exclude_ad_ids=None if exclude_ad_ids is None else [exclude_ad_ids])[0]
+                                    exclude_ad_ids=None if exclude_ad_ids is None else [exclude_ad_ids],
+                                    require_all=[require_all] if masked else None,
+                                    require_any=[require_any] if masked else None)[0]
 
     def batch_recommend(self, user_data_list: list, top_k: int = 10, stage1_k: int = 500,
-                        return_scores: bool = True, exclude_ad_ids=None) -> list:
+                        return_scores: bool = True, exclude_ad_ids=None, require_all=None, require_any=None) -> list:
         """inference.py:290-331 - but one device pass for the whole list instead of a serial loop.
         ``timing`` reports the batch's stage times divided by the number of users.  ``exclude_ad_ids``: one sequence of
         ad ids per user (recommend_device has the meaning); the padded block travels in the input staging block.
+        ``require_all`` / ``require_any``: one 64-bit eligibility mask per user each (one int for all, a sequence, a uint64 /
+        int64 array; where one is given the other defaults to 0), in the same staging block: no synchronisation more.
         ``ad_ids`` and every list of ``scores`` always have length ``top_k``: where stage 1 retrieved fewer than ``top_k``
         ads for a user (a corpus smaller than top_k, exclusions, narrow probes, a NaN feature) the tail reads ad id -1
         with score 0.0 for every task, and no ad appears that stage 1 did not retrieve for that user."""
         if not user_data_list:
             return []
-        excl = self._host_exclusions(exclude_ad_ids, len(user_data_list), stage1_k)
-        if excl is None:
-            uc, un = self.preprocess_batch(user_data_list)
-        else:
-            uc, un, excl = self.preprocess_batch(user_data_list, excl)
-        return self.recommend_tensors(uc, un, top_k, stage1_k, return_scores, _encoded=True, _exclude_dev=excl)
+        n = len(user_data_list)
+        excl = self._host_exclusions(exclude_ad_ids, n, stage1_k)
+        masks = self._host_masks(require_all, require_any, n)
+        uc, un, *rest = self.preprocess_batch(user_data_list, excl, masks)
+        excl = rest.pop(0) if excl is not None else None
+        masks = rest.pop(0) if masks is not None else None
+        return self.recommend_tensors(uc, un, top_k, stage1_k, return_scores, _encoded=True, _exclude_dev=excl,
+                                      _masks_dev=masks)
+
+    def _host_masks(self, require_all, require_any, n: int) -> Optional[np.ndarray]:
+        """The two mask arguments of the reference-API calls -> int64 [2, n] on the host (None: neither given)."""
+        if require_all is None and require_any is None:
+            return None
+        self.faiss_index._check_masks(require_all, require_any)
+        return np.stack([_eligible.as_words(0 if require_all is None else require_all, n),
+                         _eligible.as_words(0 if require_any is None else require_any, n)])
 
     @staticmethod
     def _host_exclusions(exclude_ad_ids, n: int, stage1_k: int) -> Optional[np.ndarray]:
@@ -454,14 +492,16 @@ class AdRecommenderInference:
 
     @torch.no_grad()
     def recommend_tensors(self, user_categorical, user_numerical, top_k=10, stage1_k=500, return_scores=True,
-                          _encoded=False, exclude_ad_ids=None, _exclude_dev=None):
+                          _encoded=False, exclude_ad_ids=None, _exclude_dev=None, require_all=None, require_any=None,
+                          _masks_dev=None):
         """Tensor-level entry (cf. TwoStageRetriever.retrieve_and_rank, faiss_retrieval.py:283-369); result dicts follow
         inference.py:272-288.  ONE host synchronisation per call (round 3 had four: the tower's index flag, the stage-1
         timing sync, the ranker's index flag, the result copy - each exposing the launch work queued behind it): indices
         are validated without a read-back in the middle (the verdict travels with the results), the stage times come from
         events, ids + scores + verdict come back in one copy.  An out-of-range index raises IndexError like the reference's
         embedding lookup, before any result is returned.  ``exclude_ad_ids``: one sequence of ad ids per user, shipped as
-        one padded block through pinned memory (no synchronisation of its own).  The lists keep length ``top_k``, with
+        one padded block through pinned memory (no synchronisation of its own).  ``require_all`` / ``require_any``: the
+        users' eligibility masks as in batch_recommend, shipped the same way.  The lists keep length ``top_k``, with
         -1 / 0.0 in the tail of a user with fewer real candidates (batch_recommend)."""
         t0 = time.time()
         dev = self.device
@@ -477,6 +517,14 @@ class AdRecommenderInference:
                 host, done = self._staging(hb.size * 8, "excl")
                 host.numpy().view(np.int64).reshape(hb.shape)[:] = hb
                 excl = host.to(dev, non_blocking=True).view(torch.int64).view(hb.shape)
+                done.record(torch.cuda.current_stream(dev))
+        masks = _masks_dev
+        if masks is None:
+            hm = self._host_masks(require_all, require_any, n)
+            if hm is not None:
+                host, done = self._staging(hm.size * 8, "masks")
+                host.numpy().view(np.int64).reshape(hm.shape)[:] = hm
+                masks = host.to(dev, non_blocking=True).view(torch.int64).view(hm.shape)
                 done.record(torch.cuda.current_stream(dev))
         tasks = list(self.transformer_ranker.prediction_heads.keys())        # the ranker's task order (= out["tasks"])
         ev = self.__dict__.get("_ev")
@@ -499,9 +547,9 @@ class AdRecommenderInference:
             raise IndexError("index out of range in self")                    # (the ad-feature table, transformer_ranker.py:322)
         st = torch.cuda.current_stream(dev)
         ev[0].record(st)
-        cand_pos, _ = self._stage1(uc, un, stage1_k, False, excl)
+        cand_pos, _ = self._stage1(uc, un, stage1_k, False, excl, (None, None) if masks is None else (masks[0], masks[1]))
         ev[1].record(st)
-        out = self._stage2(uc, un, cand_pos, top_k, False, out=(ad_ids, scores), excluded=excl is not None)
+        out = self._stage2(uc, un, cand_pos, top_k, False, out=(ad_ids, scores), excluded=excl is not None or masks is not None)
         assert list(out["tasks"]) == tasks
         host, done = self._staging(blk.numel(), "out")
         host.copy_(blk, non_blocking=True)
@@ -576,7 +624,7 @@ class GraphedRecommender:
     memory pool) and a private, fixed-size workspace (never the shared grow-only one)."""
 
     def __init__(self, rec: AdRecommenderInference, batch_size: int, top_k: int, stage1_k: int, warmup: int = 2,
-                 max_exclude: int = 0):
+                 max_exclude: int = 0, eligibility: bool = False):
         self.rec, self.batch_size, self.top_k, self.stage1_k = rec, batch_size, top_k, stage1_k
         self.max_exclude = int(max_exclude)
         _exclude.check_exclude(stage1_k, self.max_exclude)
@@ -587,19 +635,25 @@ class GraphedRecommender:
         self._un = torch.zeros((batch_size, n_num), dtype=torch.float32, device=dev)
         # static exclusion block (-1 = padding = nothing excluded); None: the graph has no exclusion step
         self._ex = torch.full((batch_size, self.max_exclude), -1, dtype=torch.int64, device=dev) if self.max_exclude else None
+        # static eligibility masks (zeros = no constraint); None: the graph runs the plain search
+        self.eligibility = bool(eligibility)
+        self._masks = torch.zeros((2, batch_size), dtype=torch.int64, device=dev) if self.eligibility else None
+        ma, my = (self._masks[0], self._masks[1]) if self.eligibility else (None, None)
         # sizing + warm-up pass on the shared workspace (packs weights, sets kernel attributes)
         probe = _lib.MeasuringArena(_lib.Workspace())
         with _lib.WORKSPACE.private(probe):
             for _ in range(max(1, warmup)):
-                rec.recommend_device(self._uc, self._un, top_k, stage1_k, exclude_ad_ids=self._ex)
+                rec.recommend_device(self._uc, self._un, top_k, stage1_k, exclude_ad_ids=self._ex, require_all=ma, require_any=my)
         torch.cuda.synchronize(dev)
         self._arena = _lib.FixedArena(probe.high_water, dev)
         with _lib.WORKSPACE.private(self._arena):
-            rec.recommend_device(self._uc, self._un, top_k, stage1_k, exclude_ad_ids=self._ex)          # one eager pass on the private arena
+            rec.recommend_device(self._uc, self._un, top_k, stage1_k, exclude_ad_ids=self._ex, require_all=ma,
+                                 require_any=my)                                                  # one eager pass on the private arena
             torch.cuda.synchronize(dev)
             self._graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._graph):
-                self._out = rec.recommend_device(self._uc, self._un, top_k, stage1_k, exclude_ad_ids=self._ex)
+                self._out = rec.recommend_device(self._uc, self._un, top_k, stage1_k, exclude_ad_ids=self._ex, require_all=ma,
+                                                 require_any=my)
         torch.cuda.synchronize(dev)
         # pin every device buffer the kernel nodes point at: a later load_state_dict / index.add() / larger eager search
         # then makes the graph stale (documented) but can never leave it with dangling pointers
@@ -608,16 +662,28 @@ class GraphedRecommender:
 
     @torch.no_grad()
     def __call__(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor,
-                 exclude: Optional[torch.Tensor] = None):
+                 exclude: Optional[torch.Tensor] = None, require_all: Optional[torch.Tensor] = None,
+                 require_any: Optional[torch.Tensor] = None):
         """Device tensors [batch_size, ...] -> the same dict as recommend_device (static output buffers,
         overwritten by the next call).  ``exclude``: device int64 [batch_size, E <= max_exclude] ad ids (negative =
-        padding), copied into the graph's block; None = nothing excluded (the block is filled with -1)."""
+        padding), copied into the graph's block; None = nothing excluded (the block is filled with -1).  ``require_all`` /
+        ``require_any``: device int64 [batch_size] eligibility masks, copied into the graph's buffers (None = zeros: no
+        constraint); a graph captured without ``eligibility`` raises ValueError for them."""
         if user_categorical.shape[0] != self.batch_size:
             raise ValueError(f"captured for batch {self.batch_size}, got {user_categorical.shape[0]}")
         if exclude is not None and (self._ex is None or exclude.dim() != 2 or exclude.shape[0] != self.batch_size
                                     or exclude.shape[1] > self.max_exclude):
             raise ValueError(f"captured with max_exclude={self.max_exclude} for batch {self.batch_size}, got an exclusion "
                              f"block of shape {tuple(exclude.shape)}")
+        if require_all is not None or require_any is not None:
+            if self._masks is None:
+                raise ValueError("captured without eligibility=True: this graph runs the plain search and takes no masks")
+            for m in (require_all, require_any):
+                if m is not None and (m.dtype != torch.int64 or m.shape != (self.batch_size,)):
+                    raise ValueError(f"masks must be int64 [{self.batch_size}], got {m.dtype} {tuple(m.shape)}")
+        if self._masks is not None:
+            for row, m in zip(self._masks, (require_all, require_any)):
+                row.zero_() if m is None else row.copy_(m)
         if self._ex is not None:
             if exclude is None or exclude.shape[1] < self.max_exclude:
                 self._ex.fill_(-1)

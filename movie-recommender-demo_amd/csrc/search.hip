@@ -28,6 +28,10 @@
 //     value is >= tau + eps nothing outside can enter the top-k.  A query that fails the certificate (or the
 //     count test) goes to the same exact fp32 fix-up scan as before.
 // For dims 32 / 64 / 128 / 256 the corpus pass of this variant is scan_filter_kernel (below), not a generic GEMM tile.
+// Per-request eligibility masks (amdrec_flat_search*_eligible): the same searches over the rows a query may be shown.  The
+// predicate is a compile-time type of every kernel (NoElig / Elig, below): the sample turns ineligible scores into -inf, so
+// tau sits at the quantile that admits ~target ELIGIBLE rows; the filter tests it with the threshold; the fix-up scan, which
+// also answers every query with fewer than k eligible rows, where a key is formed.
 #include <type_traits>
 #include "gemm_core.hpp"
 #include "topk_utils.hpp"
@@ -43,9 +47,30 @@ constexpr int FIX_BUF = 4096;      // fix-up scan buffer (keys)
 constexpr int FIX_GRID_Q = 256;    // queries worked on at a time by the fix-up kernels
 constexpr int SAMPLE_G = 256;      // rows per sample block (== BP of every search shape / divides it)
 
+// ---- per-request eligibility (amdrec_flat_search*_eligible) ----------------------------
+// Row r may be returned to query q iff (tags[r] & all[q]) == all[q] and (any[q] == 0 or (tags[r] & any[q]) != 0); one
+// 64-bit tag per corpus row, two 64-bit masks per query (amdrec.h has the contract).  Every search kernel takes the
+// predicate as a type: NoElig, an empty one, in the searches without masks - their kernels are the ones they were -, Elig
+// in the filtered instantiations.
+__device__ __forceinline__ bool tag_ok(uint64_t t, uint64_t all, uint64_t any) {
+    return (t & all) == all && (any == 0ull || (t & any) != 0ull);
+}
+struct NoElig {
+    static constexpr bool on = false;
+    __device__ __forceinline__ bool ok(long long, int) const { return true; }
+};
+struct Elig {
+    static constexpr bool on = true;
+    const uint64_t* tags;    // [nrows]
+    const uint64_t* all;     // [nq]
+    const uint64_t* any;     // [nq]
+    __device__ __forceinline__ bool ok(long long row, int q) const { return tag_ok(tags[row], all[q], any[q]); }
+};
+
 // ---- epilogues (lane <-> query, registers <-> corpus rows) ---------------------------
-struct EpiStoreScores {
-    static constexpr const char* name = "search_sample";
+template <class EL>
+struct EpiStoreScoresT {
+    static constexpr const char* name = EL::on ? "search_sample_elig" : "search_sample";
     static constexpr double out_bytes_per_elem = 1.0;
     static constexpr size_t lds_bytes(int) { return 0; }
     float* out;          // [nq][ld]
@@ -53,6 +78,7 @@ struct EpiStoreScores {
     int nq;
     long long n_sample;  // sample rows
     DenseRows map;       // to test validity of the mapped row
+    [[no_unique_address]] EL el;   // an ineligible (query, row) element is stored as -inf
     template <class A>
     __device__ void operator()(A& acc, float*) const {
         constexpr int TP = A::TP, TQ = A::TQ;
@@ -71,13 +97,15 @@ struct EpiStoreScores {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float s = acc.v[i][j][4 * g + e];
-                        v[e] = (map.map(p + e) < map.rows) ? s : -INFINITY;
+                        const long long row = map.map(p + e);
+                        v[e] = (row < map.rows && el.ok(row, q)) ? s : -INFINITY;
                     }
                     *reinterpret_cast<f32x4*>(out + (long long)q * ld + p) = v;
                 }
         }
     }
 };
+struct EpiStoreScores : EpiStoreScoresT<NoElig> {};
 
 // Filter epilogue: keys of (score >= tau_q) elements are appended to the per-query candidate lists.  A returning
 // global atomic per hit made the epilogue a chain of ~10 dependent 1-2 us round trips per wave (measured: the bf16
@@ -85,8 +113,9 @@ struct EpiStoreScores {
 // one barrier each hit is appended by its own lane: the global atomics of a block go out together.  Hits beyond the
 // LDS list (threshold-less small corpora, adversarial data) take the direct path.
 constexpr int HIT_CAP = 2048;
-struct EpiFilter {
-    static constexpr const char* name = "search_filter";
+template <class EL>
+struct EpiFilterT {
+    static constexpr const char* name = EL::on ? "search_filter_elig" : "search_filter";
     static constexpr double out_bytes_per_elem = 0.0;
     static constexpr size_t lds_bytes(int) { return 16 + (size_t)HIT_CAP * 12; }
     const float* tau;            // [nq]
@@ -95,6 +124,7 @@ struct EpiFilter {
     int cap, nq;
     long long nrows;
     long long stride;
+    [[no_unique_address]] EL el;   // tested with the threshold: the lists only ever hold eligible rows
     __device__ __forceinline__ void append(int q, unsigned long long key) const {
         const int pos = atomicAdd(&cnt[q], 1);
         if (pos < cap) cand[(long long)q * stride + pos] = key;
@@ -118,7 +148,7 @@ struct EpiFilter {
                 for (int r = 0; r < 16; ++r) {
                     float s = acc.v[i][j][r];
                     int p = acc.p(i, r, lane);
-                    if (s >= t && p < nrows) {
+                    if (s >= t && p < nrows && el.ok(p, q)) {
                         const unsigned long long key = make_key(s, (uint32_t)p);
                         const int slot = atomicAdd(lcount, 1);
                         if (slot < HIT_CAP) { hkey[slot] = key; hq[slot] = q; }
@@ -131,6 +161,7 @@ struct EpiFilter {
         for (int h = threadIdx.x; h < n; h += blockDim.x) append(hq[h], hkey[h]);
     }
 };
+struct EpiFilter : EpiFilterT<NoElig> {};
 
 // Threshold from the sample: tau[q] only has to BOUND the candidate count (any value with
 // k <= #{score >= tau} <= capacity gives the exact result), so instead of an exact radix select of the
@@ -197,10 +228,16 @@ __global__ __launch_bounds__(512) void finalize_kernel(const unsigned long long*
 // step 5: exact streaming scan of one corpus slice for a failed query; the block that finishes a query's LAST slice (a
 // ticket per query: last_workgroup) merges the slices and writes the result.  One launch: in the common case - no failed
 // query - it is the only cost of the fix-up, and two empty launches cost 8 us of a 140 us single-query search.
+// EL: the eligibility predicate, tested where a row's key is formed; EP: its pointers, none for NoElig - fixup_kernel<NoElig>
+// takes the arguments the scan always took and is the code it always was -, (tags, all, any) for Elig.  A filtered query
+// with fewer than k eligible rows always ends here - its candidate count fails the finalize's count test - and gets its
+// eligible rows in order and an unfilled tail.
+template <class EL, class... EP>
 __global__ __launch_bounds__(512) void fixup_kernel(const float* X, long long ldx, long long nrows, int d,
                                                     const float* Q, long long ldq, const int* fail, int nq,
                                                     int k, int nslices, unsigned long long* scratch, int* ticket,
-                                                    float* outD, long long* outI, long long pos_offset) {
+                                                    float* outD, long long* outI, long long pos_offset, EP... elig) {
+    const EL el{elig...};
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];      // merge: k * nslices keys (<= CAND_CAP)
     __shared__ __attribute__((aligned(16))) unsigned long long buf[FIX_BUF];
     __shared__ __attribute__((aligned(16))) float qv[2048];
@@ -245,7 +282,7 @@ __global__ __launch_bounds__(512) void fixup_kernel(const float* X, long long ld
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             long long r = row0 + w * U + u;
-            if (lane == 0 && r < end && a[u] == a[u]) {
+            if (lane == 0 && r < end && a[u] == a[u] && el.ok(r, q)) {
                 unsigned long long key = make_key(a[u], (uint32_t)r);
                 if (key > thr) {
                     int pos = atomicAdd(&count, 1);
@@ -398,6 +435,21 @@ __device__ __forceinline__ void lds_store_hit_opaque(uint32_t key_addr, unsigned
     asm volatile("ds_write_b64 %0, %1\n\tds_write_b32 %2, %3" ::"v"(key_addr), "v"(key), "v"(q_addr), "v"(q) : "memory");
 }
 
+// Two 64-bit words from wave-uniform addresses by SCALAR loads.  Spelled out because the compiler, which cannot prove that
+// the kernel's own stores leave the words alone, reads them with vector loads otherwise - and a vector load's wait
+// (vmcnt counts in order) is also a wait for the LDS-DMA of the next tile.  The scalar loads return on lgkmcnt.
+__device__ __forceinline__ void scalar_load_2x64(const uint64_t* p0, const uint64_t* p1, uint64_t& v0, uint64_t& v1) {
+    asm volatile("s_load_dwordx2 %0, %2, 0x0\n\ts_load_dwordx2 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(v0), "=&s"(v1) : "s"(p0), "s"(p1) : "memory");
+}
+// ... and eight consecutive ones (64 bytes) in one load: w[2 i], w[2 i + 1] = the halves of word i
+typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ u32x16 scalar_load_8x64(const uint64_t* p) {
+    u32x16 w;
+    asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(w) : "s"(p) : "memory");
+    return w;
+}
+
 // 16 bytes from global `g` to LDS `l` by LDS-DMA (the LDS address is wave-uniform: lane i's bytes land at l + 16 i)
 __device__ __forceinline__ void lds_dma16(const unsigned char* g, unsigned char* l) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l,
@@ -428,13 +480,24 @@ struct ScanTile {
     }
 };
 
-template <int KS>                       // KS = dim / 16 in {2, 4, 8, 16}
+// EL (NoElig or Elig): the eligibility predicate.  It is tested in the out-of-line hit path only, never per element: a lane
+// keeps the masks of its two queries beside tq[]; a corpus row belongs to an accumulator register and a lane half (a query
+// to a lane), so the tags a wave needs in one four-element group are those of eight consecutive rows at a wave-uniform
+// address - ONE scalar load per entry of the hit path, which returns on its own counter and so never waits for the LDS-DMA
+// of the next tile that is in flight (a vector load would queue behind it).  The loads stay inside the nrows tags: whole
+// tiles by construction, the last tile by clamping the row.  The predicate is ANDed into `hit` before the ballot, so the
+// wave lists, the segments and the overflow block only ever hold eligible rows, and finalize and certificate need no
+// change: a row outside the list is below tau or ineligible.
+// EP: the predicate's pointers as trailing kernel arguments - none for NoElig, whose instantiation takes the arguments the
+// kernel always took and compiles to the code it always was; (tags, all, any) for Elig.
+template <int KS, class EL = NoElig, class... EP>       // KS = dim / 16 in {2, 4, 8, 16}
 __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __restrict__ X16, long long ld16,
                                                              long long nrows, const uint16_t* __restrict__ Q16, int nq,
                                                              float* __restrict__ tau, unsigned long long* cand,
                                                              int* segcnt, int* ocnt, int seg_cap, int nx,
                                                              const float* __restrict__ gm, long long ldm, long long gm_n,
-                                                             int rank) {
+                                                             int rank, EP... elig) {
+    const EL el{elig...};
     using Tile = ScanTile<KS>;
     constexpr int CPR = Tile::CPR, TILE_CHUNKS = Tile::CHUNKS, AHEAD = Tile::AHEAD;
     constexpr int NSLOT = 2;                                     // ring slots of SCAN_ROWS rows: the DMA runs a tile ahead
@@ -511,8 +574,9 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
     };
     // 32 corpus rows (LDS image at `lb`, fragment k-offset swizzle G) x NJ query tiles: K loop with the A fragments
     // read AHEAD steps before their MFMA, then the threshold scan.  wcount = this wave's hits so far in this tile.
+    uint64_t qall[2] = {0ull, 0ull}, qany[2] = {0ull, 0ull};       // (filtered instantiations only)
     auto quarter = [&](auto nj_tag, auto full_tag, const unsigned char* lb, int G, int prow, uint32_t list_addr,
-                       int& wcount) {
+                       int& wcount, int urow) {                    // urow: the quarter's first corpus row (wave-uniform)
         constexpr int NJ = decltype(nj_tag)::value;
         constexpr bool FULL = decltype(full_tag)::value;           // every row of the tile is a corpus row
         f32x16 acc[NJ];
@@ -553,11 +617,32 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
             for (int g = 0; g < 4; ++g) {
                 const float m4 = fmaxf(fmaxf(acc[j][4 * g], acc[j][4 * g + 1]), fmaxf(acc[j][4 * g + 2], acc[j][4 * g + 3]));
                 if (__builtin_expect(__ballot(m4 >= tq[j]) == 0ull, 1)) continue;
+                // (filtered, whole tile) the tags of the group's eight rows urow + 8 g .. + 7 in one scalar load: one wait per
+                // entry of the hit path, which a wave enters for ~30 % of its groups - some lane of 64 has a hit in 4 elements
+                u32x16 tw = {};
+                if constexpr (EL::on) {
+                    if constexpr (FULL) tw = scalar_load_8x64(el.tags + urow + 8 * g);
+                }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float sc = acc[j][4 * g + e];
                     const int p = prow + e + 8 * g;
-                    const bool hit = sc >= tq[j] && (FULL || p < nrows_i);
+                    bool hit = sc >= tq[j] && (FULL || p < nrows_i);
+                    if constexpr (EL::on) {
+                        // rows urow + e + 8 g (lanes 0-31) and + 4 (lanes 32-63); last tile: clamped into the nrows tags
+                        // (skipping the test for an element no lane has a hit in - one more ballot and branch - was measured
+                        // slower: 0.407 against 0.377 ms per pass at 512 queries, and 17 spilled SGPRs at dim 256)
+                        uint64_t t0, t1;
+                        if constexpr (FULL) {
+                            t0 = tw[2 * e] | ((uint64_t)tw[2 * e + 1] << 32);
+                            t1 = tw[2 * e + 8] | ((uint64_t)tw[2 * e + 9] << 32);
+                        } else {
+                            const int r0 = urow + e + 8 * g, r1 = r0 + 4;
+                            scalar_load_2x64(el.tags + (r0 < nrows_i ? r0 : nrows_i - 1),
+                                             el.tags + (r1 < nrows_i ? r1 : nrows_i - 1), t0, t1);
+                        }
+                        hit = hit && tag_ok(fh ? t1 : t0, qall[j], qany[j]);
+                    }
                     const unsigned long long mask = __ballot(hit);
                     if (mask) {                                    // wave-uniform
                         if (hit) {
@@ -600,6 +685,10 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
     for (int j = 0; j < 2; ++j) {
         const int q = q0 + j * 32 + frow;
         tq[j] = (q < nq) ? (gm != nullptr ? tau_sh[q] : tau[q]) : __builtin_nanf("");
+        if constexpr (EL::on) {
+            qall[j] = el.all[q < nq ? q : nq - 1];
+            qany[j] = el.any[q < nq ? q : nq - 1];
+        }
     }
     int it = 0, wprev = 0;                                         // wprev: hits of the previous tile awaiting their append
     for (; it < my_tiles; ++it) {
@@ -634,7 +723,8 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
 #pragma unroll 1
                 for (int rq = rq_begin; rq < rq_end; ++rq) {
                     asm volatile("" : "+v"(G));
-                    quarter(nj_tag, full_tag, lb + rq * 32 * CPR * 16, G, prow0 + rq * 32 + 4 * fh, list_addr, wcount);
+                    quarter(nj_tag, full_tag, lb + rq * 32 * CPR * 16, G, prow0 + rq * 32 + 4 * fh, list_addr, wcount,
+                            prow0 + rq * 32);
                 }
             };
             using I1 = std::integral_constant<int, 1>;
@@ -671,11 +761,16 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
 //    needs the r-th largest of ~256 group maxima of the sample (see wave_tau), and a maximum of maxima is the maximum.
 // SUB = values per lane, query tile and 32-row quarter: 1 (16-row groups), 4 (4-row groups), 16 (every score: corpora so
 // small that coarser groups would leave fewer than ~1000 columns).  Column of a value: ((tile * 4 + quarter) * 2 + fh) * SUB + i.
-template <int KS, int SUB>
+// EL = Elig: the score of an ineligible (query, row) pair becomes -inf before it enters a group
+// maximum (before it is stored, SUB == 16), so the r-th largest maximum - wave_tau, unchanged - is taken over the query's
+// ELIGIBLE sample rows and sits at the quantile that admits ~target eligible rows whatever fraction of the corpus is
+// eligible; fewer than r eligible sample rows -> fewer than r finite maxima -> tau = -inf.
+template <int KS, int SUB, class EL = NoElig, class... EP>
 __global__ __launch_bounds__(512, 1) void sample_max_kernel(const uint16_t* __restrict__ X16, long long ld16, int tstride,
                                                             int n_tiles, const float* __restrict__ Q, long long ldq, int nq,
                                                             uint16_t* __restrict__ Q16, float* __restrict__ gm, long long ldm,
-                                                            int nx, int* zero, long long n_zero) {
+                                                            int nx, int* zero, long long n_zero, EP... elig) {
+    const EL el{elig...};
     using Tile = ScanTile<KS>;
     constexpr int CPR = Tile::CPR, TILE_CHUNKS = Tile::CHUNKS, PASSES = Tile::PASSES, AHEAD = Tile::AHEAD;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];                      // [2][TILE_CHUNKS * 16]
@@ -716,6 +811,15 @@ __global__ __launch_bounds__(512, 1) void sample_max_kernel(const uint16_t* __re
             const u32x4 pk{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
             qf[j][s_] = __builtin_bit_cast(bf16x8, pk);
             if (wr && q0 + j * 32 < nq) *reinterpret_cast<u32x4*>(Q16 + (long long)q * (16 * KS) + (2 * s_ + fh) * 8) = pk;
+        }
+    }
+    uint64_t qall[2] = {0ull, 0ull}, qany[2] = {0ull, 0ull};       // (filtered instantiations only) masks of the lane's queries
+    if constexpr (EL::on) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int q = q0 + j * 32 + frow;
+            qall[j] = el.all[q < nq ? q : nq - 1];
+            qany[j] = el.any[q < nq ? q : nq - 1];
         }
     }
     // tile DMA (sample tiles are whole tiles: no clamped path)
@@ -775,6 +879,21 @@ __global__ __launch_bounds__(512, 1) void sample_max_kernel(const uint16_t* __re
                         if (s_ + AHEAD < KS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                     }
                     const long long col0 = (((long long)t * 4 + rq) * 2 + fh) * SUB;
+                    if constexpr (EL::on) {
+                        // acc[j][4 g + e] is corpus row (tile row0) + 32 rq + 8 g + 4 fh + e: four tags per g and lane
+                        const uint64_t* tg = el.tags + (long long)t * tstride * SCAN_ROWS + rq * 32 + 4 * fh;
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            uint64_t tw[4];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) tw[e] = tg[8 * g + e];
+#pragma unroll
+                            for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                                for (int e = 0; e < 4; ++e)
+                                    if (!tag_ok(tw[e], qall[j], qany[j])) acc[j][4 * g + e] = -INFINITY;
+                        }
+                    }
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) {
                         const int q = q0 + j * 32 + frow;
@@ -833,11 +952,40 @@ static inline int scan_segments(long long nrows, long long nq) {
     return (int)(nx < 1 ? 1 : nx);
 }
 
-template <int KS>
+template <class EL>
+struct ScanKernels;                      // the streaming and fix-up kernels of a search without (NoElig) / with (Elig) eligibility masks
+template <>
+struct ScanKernels<NoElig> {
+    static constexpr const char *scan_tag = "search_filter_stream128x512_bf16", *sample_tag = "search_sample_max128x512_bf16";
+    template <int KS> static constexpr auto scan() { return scan_filter_kernel<KS>; }
+    template <int KS, int SUB> static constexpr auto sample() { return sample_max_kernel<KS, SUB>; }
+    static auto fixup() { return fixup_kernel<NoElig>; }
+};
+template <>
+struct ScanKernels<Elig> {
+    static constexpr const char *scan_tag = "search_filter_stream128x512_bf16_elig",
+                                *sample_tag = "search_sample_max128x512_bf16_elig";
+#define AMDREC_ELIG_ARGS Elig, const uint64_t*, const uint64_t*, const uint64_t*
+    template <int KS> static constexpr auto scan() { return scan_filter_kernel<KS, AMDREC_ELIG_ARGS>; }
+    template <int KS, int SUB> static constexpr auto sample() { return sample_max_kernel<KS, SUB, AMDREC_ELIG_ARGS>; }
+    static auto fixup() { return fixup_kernel<AMDREC_ELIG_ARGS>; }
+#undef AMDREC_ELIG_ARGS
+};
+// launches `kern` with the eligibility pointers after the arguments every instantiation takes (NoElig: none)
+template <class Kern, class... Args>
+static void launch_with(NoElig, Kern kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+}
+template <class Kern, class... Args>
+static void launch_with(Elig el, Kern kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args..., el.tags, el.all, el.any);
+}
+
+template <int KS, class EL = NoElig>
 static hipError_t launch_scan(const uint16_t* X16, long long ld16, long long nrows, const uint16_t* Q16, int nq,
                               float* tau, unsigned long long* cand, int* segcnt, int* ocnt, hipStream_t st,
-                              const float* gm = nullptr, long long ldm = 0, long long gm_n = 0, int rank = 0) {
-    auto kern = scan_filter_kernel<KS>;
+                              const float* gm = nullptr, long long ldm = 0, long long gm_n = 0, int rank = 0, EL el = EL{}) {
+    auto kern = ScanKernels<EL>::template scan<KS>();
     constexpr size_t lds_bytes = 2ull * SCAN_ROWS * 2 * KS * 16 + SCAN_HIT_BYTES + SCAN_QGROUP * 4;
     static_assert(lds_bytes <= 160 * 1024, "LDS budget");
     static PerDeviceOnce attr_done;
@@ -850,10 +998,10 @@ static hipError_t launch_scan(const uint16_t* X16, long long ld16, long long nro
     const int ny = (nq + SCAN_QGROUP - 1) / SCAN_QGROUP;
     const int nx = scan_segments(nrows, nq);
     const int d = 16 * KS;
-    ProfScope prof("search_filter_stream128x512_bf16", 2.0 * (double)nrows * (double)nq * d,
+    ProfScope prof(ScanKernels<EL>::scan_tag, 2.0 * (double)nrows * (double)nq * d,
                    2.0 * ((double)nrows * d * ny + (double)nq * d), st);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nx * ny)), dim3(512), lds_bytes, st, X16, ld16, nrows, Q16, nq, tau, cand, segcnt,
-                       ocnt, CAND_CAP / nx, nx, gm, ldm, gm_n, rank);
+    launch_with(el, kern, dim3((unsigned)(nx * ny)), dim3(512), lds_bytes, st, X16, ld16, nrows, Q16, nq, tau, cand, segcnt,
+                ocnt, CAND_CAP / nx, nx, gm, ldm, gm_n, rank);
     return hipGetLastError();
 }
 
@@ -875,17 +1023,18 @@ static inline SamplePlan sample_plan(long long nrows, long long n_sample_rows) {
     sp.cols = nt * 8 * sp.sub;
     return sp;
 }
-template <int KS>
+template <int KS, class EL = NoElig>
 static hipError_t launch_sample(const uint16_t* X16, long long ld16, const SamplePlan& sp, const float* Q, long long ldq,
-                                int nq, uint16_t* Q16, float* gm, int* zero, long long n_zero, hipStream_t st) {
+                                int nq, uint16_t* Q16, float* gm, int* zero, long long n_zero, hipStream_t st, EL el = EL{}) {
+    using K = ScanKernels<EL>;
     constexpr size_t lds_bytes = 2ull * SCAN_ROWS * 2 * KS * 16;
     static PerDeviceOnce attr_done;
     if (attr_done.pending()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sample_max_kernel<KS, 1>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K::template sample<KS, 1>()),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(sample_max_kernel<KS, 4>),
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(K::template sample<KS, 4>()),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(sample_max_kernel<KS, 16>),
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(K::template sample<KS, 16>()),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
         attr_done.mark();
@@ -894,18 +1043,18 @@ static hipError_t launch_sample(const uint16_t* X16, long long ld16, const Sampl
     int nx = 256 / ny;
     nx = nx < 1 ? 1 : (nx > sp.n_tiles ? sp.n_tiles : nx);
     const int d = 16 * KS;
-    ProfScope prof("search_sample_max128x512_bf16", 2.0 * (double)sp.n_tiles * SCAN_ROWS * (double)nq * d,
+    ProfScope prof(K::sample_tag, 2.0 * (double)sp.n_tiles * SCAN_ROWS * (double)nq * d,
                    2.0 * (double)sp.n_tiles * SCAN_ROWS * d * ny + 4.0 * (double)nq * d + 4.0 * (double)nq * sp.cols, st);
     const dim3 grid((unsigned)(nx * ny)), block(512);
     if (sp.sub == 1)
-        hipLaunchKernelGGL((sample_max_kernel<KS, 1>), grid, block, lds_bytes, st, X16, ld16, sp.tstride, sp.n_tiles, Q, ldq, nq,
-                           Q16, gm, sp.cols, nx, zero, n_zero);
+        launch_with(el, K::template sample<KS, 1>(), grid, block, lds_bytes, st, X16, ld16, sp.tstride, sp.n_tiles, Q, ldq, nq,
+                    Q16, gm, sp.cols, nx, zero, n_zero);
     else if (sp.sub == 4)
-        hipLaunchKernelGGL((sample_max_kernel<KS, 4>), grid, block, lds_bytes, st, X16, ld16, sp.tstride, sp.n_tiles, Q, ldq, nq,
-                           Q16, gm, sp.cols, nx, zero, n_zero);
+        launch_with(el, K::template sample<KS, 4>(), grid, block, lds_bytes, st, X16, ld16, sp.tstride, sp.n_tiles, Q, ldq, nq,
+                    Q16, gm, sp.cols, nx, zero, n_zero);
     else
-        hipLaunchKernelGGL((sample_max_kernel<KS, 16>), grid, block, lds_bytes, st, X16, ld16, sp.tstride, sp.n_tiles, Q, ldq, nq,
-                           Q16, gm, sp.cols, nx, zero, n_zero);
+        launch_with(el, K::template sample<KS, 16>(), grid, block, lds_bytes, st, X16, ld16, sp.tstride, sp.n_tiles, Q, ldq, nq,
+                    Q16, gm, sp.cols, nx, zero, n_zero);
     return hipGetLastError();
 }
 
@@ -1220,15 +1369,18 @@ static SearchPlan make_plan(long long nq, long long nrows, int k, int dim16, voi
 
 // X / Q / ldx / ldq / d are in staged floats: for a BF16 shape the bf16 matrices viewed as float matrices of
 // half the columns (d_alg = the un-halved dimension, for the profiling hook's FLOP count)
-template <class S>
+template <class S, class EL = NoElig>
 static hipError_t run_passes(const float* X, long long ldx, long long nrows, int d, const float* Q, long long ldq,
                              int nq, const SearchPlan& pl, hipStream_t st, int d_alg = 0,
-                             bool filter = true, long long cand_stride = CAND_CAP) {
+                             bool filter = true, long long cand_stride = CAND_CAP, EL el = EL{}) {
+    using Store = std::conditional_t<EL::on, EpiStoreScoresT<EL>, EpiStoreScores>;
+    using Filter = std::conditional_t<EL::on, EpiFilterT<EL>, EpiFilter>;
     DenseRows lq{Q, nq, (int)ldq, d, 30, 1ll << 30};
     if (pl.n_sample > 0) {
         int gshift = 8;   // SAMPLE_G == 256
         DenseRows lps{X, nrows, (int)ldx, d, gshift, pl.gstride};
-        EpiStoreScores es{pl.sample, pl.n_sample, nq, pl.n_sample, lps};
+        Store es{};
+        static_cast<EpiStoreScoresT<EL>&>(es) = EpiStoreScoresT<EL>{pl.sample, pl.n_sample, nq, pl.n_sample, lps, el};
         hipError_t e = launch_gemm<S, false>(lps, lq, es, d, pl.n_sample, nq, st, d_alg);
         if (e != hipSuccess) return e;
         ProfScope prof("search_threshold", 0.0, 4.0 * (double)nq * (double)pl.n_sample, st);
@@ -1240,7 +1392,8 @@ static hipError_t run_passes(const float* X, long long ldx, long long nrows, int
     }
     if (!filter) return hipGetLastError();
     DenseRows lp{X, nrows, (int)ldx, d, 30, 1ll << 30};
-    EpiFilter ef{pl.tau, pl.cand, pl.cnt, CAND_CAP, nq, nrows, cand_stride};
+    Filter ef{};
+    static_cast<EpiFilterT<EL>&>(ef) = EpiFilterT<EL>{pl.tau, pl.cand, pl.cnt, CAND_CAP, nq, nrows, cand_stride, el};
     return launch_gemm<S, false>(lp, lq, ef, d, nrows, nq, st, d_alg);
 }
 
@@ -1332,19 +1485,22 @@ static int set_lds_limits() {
         {reinterpret_cast<const void*>(finalize_kernel), CAND_CAP * 8},
         {reinterpret_cast<const void*>(finalize_mixed_kernel<512, CAND_CAP>), CAND_CAP * 8 + 2048 * 4},
         {reinterpret_cast<const void*>(finalize_fused_kernel), CAND_CAP * 8 + 2048 * 4},
-        {reinterpret_cast<const void*>(fixup_kernel), CAND_CAP * 8}};
+        {reinterpret_cast<const void*>(ScanKernels<NoElig>::fixup()), CAND_CAP * 8},
+        {reinterpret_cast<const void*>(ScanKernels<Elig>::fixup()), CAND_CAP * 8}};
     for (const auto& l : limits) HIP_TRY(hipFuncSetAttribute(l.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, l.bytes));
     attr_done.mark();
     return AMDREC_OK;
 }
 
 // the exact re-scan of the queries that the finalize kernel could not certify, and their count for the caller
+template <class EL = NoElig>
 static int launch_fixup(const float* corpus, int64_t ld_corpus, int64_t nrows, int dim, const float* queries, int64_t nq,
                         int64_t ld_queries, int k, const SearchPlan& pl, float* out_scores, int64_t* out_pos, int64_t pos_offset,
-                        int* n_fixup, hipStream_t st) {
-    hipLaunchKernelGGL(fixup_kernel, dim3((unsigned)(pl.nslices * (nq < FIX_GRID_Q ? nq : FIX_GRID_Q))), dim3(512), CAND_CAP * 8, st,
-                       corpus, (long long)ld_corpus, (long long)nrows, dim, queries, (long long)ld_queries, pl.fail, (int)nq, k,
-                       pl.nslices, pl.fix, pl.ticket, out_scores, (long long*)out_pos, (long long)pos_offset);
+                        int* n_fixup, hipStream_t st, EL el = EL{}) {
+    launch_with(el, ScanKernels<EL>::fixup(), dim3((unsigned)(pl.nslices * (nq < FIX_GRID_Q ? nq : FIX_GRID_Q))), dim3(512),
+                (size_t)CAND_CAP * 8, st, corpus, (long long)ld_corpus, (long long)nrows, dim, queries, (long long)ld_queries,
+                (const int*)pl.fail, (int)nq, k, pl.nslices, pl.fix, pl.ticket, out_scores, (long long*)out_pos,
+                (long long)pos_offset);
     HIP_TRY(hipGetLastError());
     if (n_fixup) HIP_TRY(hipMemcpyAsync(n_fixup, pl.fail + nq, sizeof(int), hipMemcpyDeviceToDevice, st));
     return AMDREC_OK;
@@ -1358,25 +1514,59 @@ extern "C" int amdrec_flat_search_workspace(int64_t nq, int64_t nrows, int k, si
     return AMDREC_OK;
 }
 
-extern "C" int amdrec_flat_search(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
-                                  const float* queries, int64_t nq, int64_t ld_queries, int k,
-                                  int64_t pos_offset, float* out_scores, int64_t* out_pos, void* workspace,
-                                  size_t workspace_bytes, int* n_fixup, void* stream) {
+// the eligibility pointers of the *_eligible entries: all three are required (checked with the other arguments, before
+// the first HIP call)
+static int elig_check(const uint64_t* tags, const uint64_t* require_all, const uint64_t* require_any, int64_t nrows) {
+    REQUIRE(tags || nrows == 0, "tags is null");
+    REQUIRE(require_all && require_any, "require_all / require_any is null");
+    // (tags: the streaming pass reads the eight tags of a row group with one 64-byte scalar load)
+    REQUIRE(((uintptr_t)tags % 64) == 0 && ((uintptr_t)require_all % 8) == 0 && ((uintptr_t)require_any % 8) == 0,
+            "tags must be 64-byte aligned, require_all / require_any 8-byte aligned");
+    return AMDREC_OK;
+}
+static int elig_check(NoElig, int64_t) { return AMDREC_OK; }
+static int elig_check(Elig el, int64_t nrows) { return elig_check(el.tags, el.all, el.any, nrows); }
+
+template <class EL>
+static int flat_search_impl(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
+                            const float* queries, int64_t nq, int64_t ld_queries, int k,
+                            int64_t pos_offset, float* out_scores, int64_t* out_pos, void* workspace,
+                            size_t workspace_bytes, int* n_fixup, void* stream, EL el) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int rc = search_check(false, corpus, nrows, ld_corpus, dim, nullptr, 0, nullptr, queries, nq, ld_queries, k, out_scores, out_pos);
     if (rc || nq == 0) return rc;
+    if ((rc = elig_check(el, nrows))) return rc;
     const SearchPlan pl = make_plan(nq, nrows, k, 0, workspace);
     if ((rc = require_workspace(workspace, workspace_bytes, pl.bytes, 256))) return rc;
     HIP_TRY(hipMemsetAsync(pl.cnt, 0, pl.clear_bytes, st));
 
     hipError_t e = nrows <= 0 ? hipSuccess : dispatch_query_tile<false>(nq, [&](auto shape) {
-        return run_passes<decltype(shape)>(corpus, ld_corpus, nrows, dim, queries, ld_queries, (int)nq, pl, st);
+        return run_passes<decltype(shape), EL>(corpus, ld_corpus, nrows, dim, queries, ld_queries, (int)nq, pl, st, 0, true,
+                                               CAND_CAP, el);
     });
     HIP_TRY(e);
     if ((rc = set_lds_limits())) return rc;
     hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)nq), dim3(512), CAND_CAP * 8, st, pl.cand, pl.cnt, CAND_CAP, k,
                        (long long)nrows, pl.fail, out_scores, (long long*)out_pos, (long long)pos_offset);
-    return launch_fixup(corpus, ld_corpus, nrows, dim, queries, nq, ld_queries, k, pl, out_scores, out_pos, pos_offset, n_fixup, st);
+    return launch_fixup(corpus, ld_corpus, nrows, dim, queries, nq, ld_queries, k, pl, out_scores, out_pos, pos_offset, n_fixup, st,
+                        el);
+}
+
+extern "C" int amdrec_flat_search(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
+                                  const float* queries, int64_t nq, int64_t ld_queries, int k,
+                                  int64_t pos_offset, float* out_scores, int64_t* out_pos, void* workspace,
+                                  size_t workspace_bytes, int* n_fixup, void* stream) {
+    return flat_search_impl(corpus, nrows, ld_corpus, dim, queries, nq, ld_queries, k, pos_offset, out_scores, out_pos, workspace,
+                            workspace_bytes, n_fixup, stream, NoElig{});
+}
+
+extern "C" int amdrec_flat_search_eligible(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
+                                           const float* queries, int64_t nq, int64_t ld_queries, int k,
+                                           int64_t pos_offset, float* out_scores, int64_t* out_pos, void* workspace,
+                                           size_t workspace_bytes, int* n_fixup, void* stream, const uint64_t* tags,
+                                           const uint64_t* require_all, const uint64_t* require_any) {
+    return flat_search_impl(corpus, nrows, ld_corpus, dim, queries, nq, ld_queries, k, pos_offset, out_scores, out_pos, workspace,
+                            workspace_bytes, n_fixup, stream, Elig{tags, require_all, require_any});
 }
 
 extern "C" int amdrec_bf16_rows(const float* x, int64_t rows, int64_t ld, int dim, uint16_t* out, int64_t ld_out,
@@ -1402,15 +1592,17 @@ extern "C" int amdrec_flat_search_mixed_workspace(int64_t nq, int64_t nrows, int
     return AMDREC_OK;
 }
 
-extern "C" int amdrec_flat_search_mixed(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
-                                        const uint16_t* corpus_bf16, int64_t ld_bf16, const float* max_norm,
-                                        const float* queries, int64_t nq, int64_t ld_queries, int k,
-                                        int64_t pos_offset, float* out_scores, int64_t* out_pos, void* workspace,
-                                        size_t workspace_bytes, int* n_fixup, void* stream) {
+template <class EL>
+static int flat_search_mixed_impl(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
+                                  const uint16_t* corpus_bf16, int64_t ld_bf16, const float* max_norm,
+                                  const float* queries, int64_t nq, int64_t ld_queries, int k,
+                                  int64_t pos_offset, float* out_scores, int64_t* out_pos, void* workspace,
+                                  size_t workspace_bytes, int* n_fixup, void* stream, EL el) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int rc = search_check(true, corpus, nrows, ld_corpus, dim, corpus_bf16, ld_bf16, max_norm, queries, nq, ld_queries, k,
                           out_scores, out_pos);
     if (rc || nq == 0) return rc;
+    if ((rc = elig_check(el, nrows))) return rc;
     const SearchPlan pl = make_plan(nq, nrows, k, dim, workspace);
     if ((rc = require_workspace(workspace, workspace_bytes, pl.bytes, 256))) return rc;
     // cnt .. fail are cleared by the query-conversion kernel below (no separate fill launch: a launch costs ~5 us, a
@@ -1432,15 +1624,16 @@ extern "C" int amdrec_flat_search_mixed(const float* corpus, int64_t nrows, int6
         const bool tau_in_scan = nq <= 8;
         hipError_t e = dispatch_ks(dim, [&](auto ks_tag) -> hipError_t {
             constexpr int KS = decltype(ks_tag)::value;
-            hipError_t e2 = launch_sample<KS>(corpus_bf16, ld_bf16, sp, queries, ld_queries, (int)nq, pl.q16, pl.sample, pl.cnt, n_zero, st);
+            hipError_t e2 = launch_sample<KS, EL>(corpus_bf16, ld_bf16, sp, queries, ld_queries, (int)nq, pl.q16, pl.sample, pl.cnt,
+                                                  n_zero, st, el);
             if (e2 != hipSuccess) return e2;
             if (!tau_in_scan) {
                 ProfScope prof("search_threshold", 0.0, 4.0 * (double)nq * (double)sp.cols, st);
                 hipLaunchKernelGGL(tau_from_maxima_kernel, dim3((unsigned)((nq + 7) / 8)), dim3(512), 0, st, pl.sample,
                                    sp.cols, sp.cols, pl.rank, (int)nq, pl.tau);
             }
-            return launch_scan<KS>(corpus_bf16, ld_bf16, nrows, pl.q16, (int)nq, pl.tau, pl.cand, pl.segcnt, pl.ocnt, st,
-                                   tau_in_scan ? pl.sample : nullptr, sp.cols, sp.cols, pl.rank);
+            return launch_scan<KS, EL>(corpus_bf16, ld_bf16, nrows, pl.q16, (int)nq, pl.tau, pl.cand, pl.segcnt, pl.ocnt, st,
+                                       tau_in_scan ? pl.sample : nullptr, sp.cols, sp.cols, pl.rank, el);
         });
         HIP_TRY(e);
     } else if (nrows > 0) {
@@ -1452,13 +1645,13 @@ extern "C" int amdrec_flat_search_mixed(const float* corpus, int64_t nrows, int6
         const long long ldx = ld_bf16 / 2, ldq = dim / 2;
         const int dh = dim / 2;
         hipError_t e = dispatch_query_tile<true>(nq, [&](auto shape) {
-            return run_passes<decltype(shape)>(X, ldx, nrows, dh, Q, ldq, (int)nq, pl, st, dim, !streaming, CSTRIDE);
+            return run_passes<decltype(shape), EL>(X, ldx, nrows, dh, Q, ldq, (int)nq, pl, st, dim, !streaming, CSTRIDE, el);
         });
         HIP_TRY(e);
         if (streaming) {
             e = dispatch_ks(dim, [&](auto ks_tag) {
-                return launch_scan<decltype(ks_tag)::value>(corpus_bf16, ld_bf16, nrows, pl.q16, (int)nq, pl.tau, pl.cand,
-                                                            pl.segcnt, pl.ocnt, st);
+                return launch_scan<decltype(ks_tag)::value, EL>(corpus_bf16, ld_bf16, nrows, pl.q16, (int)nq, pl.tau, pl.cand,
+                                                                pl.segcnt, pl.ocnt, st, nullptr, 0, 0, 0, el);
             });
             HIP_TRY(e);
         }
@@ -1487,6 +1680,27 @@ extern "C" int amdrec_flat_search_mixed(const float* corpus, int64_t nrows, int6
 #undef AMDREC_FINALIZE
         }
     }
-    ProfScope prof_fix("search_fixup", 0.0, 0.0, st);
-    return launch_fixup(corpus, ld_corpus, nrows, dim, queries, nq, ld_queries, k, pl, out_scores, out_pos, pos_offset, n_fixup, st);
+    ProfScope prof_fix(EL::on ? "search_fixup_elig" : "search_fixup", 0.0, 0.0, st);
+    return launch_fixup(corpus, ld_corpus, nrows, dim, queries, nq, ld_queries, k, pl, out_scores, out_pos, pos_offset, n_fixup, st,
+                        el);
+}
+
+extern "C" int amdrec_flat_search_mixed(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
+                                        const uint16_t* corpus_bf16, int64_t ld_bf16, const float* max_norm,
+                                        const float* queries, int64_t nq, int64_t ld_queries, int k,
+                                        int64_t pos_offset, float* out_scores, int64_t* out_pos, void* workspace,
+                                        size_t workspace_bytes, int* n_fixup, void* stream) {
+    return flat_search_mixed_impl(corpus, nrows, ld_corpus, dim, corpus_bf16, ld_bf16, max_norm, queries, nq, ld_queries, k,
+                                  pos_offset, out_scores, out_pos, workspace, workspace_bytes, n_fixup, stream, NoElig{});
+}
+
+extern "C" int amdrec_flat_search_mixed_eligible(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
+                                                 const uint16_t* corpus_bf16, int64_t ld_bf16, const float* max_norm,
+                                                 const float* queries, int64_t nq, int64_t ld_queries, int k,
+                                                 int64_t pos_offset, float* out_scores, int64_t* out_pos, void* workspace,
+                                                 size_t workspace_bytes, int* n_fixup, void* stream, const uint64_t* tags,
+                                                 const uint64_t* require_all, const uint64_t* require_any) {
+    return flat_search_mixed_impl(corpus, nrows, ld_corpus, dim, corpus_bf16, ld_bf16, max_norm, queries, nq, ld_queries, k,
+                                  pos_offset, out_scores, out_pos, workspace, workspace_bytes, n_fixup, stream,
+                                  Elig{tags, require_all, require_any});
 }
