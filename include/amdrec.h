@@ -32,7 +32,9 @@ extern "C" {
                                * binding ship together and the struct layouts are checked against the compiler, tests/test_abi.py;
                                * amdrec_select_topk then gained its cand_pos argument under the same rule; so did CTR-first ranking:
                                * amdrec_ranker_forward_ctr_first ..., amdrec_x3_weights.stream_ctr ... at the struct's end; and
-                               * the eligibility masks: amdrec_flat_search_eligible, amdrec_flat_search_mixed_eligible, added exports) */
+                               * the eligibility masks: amdrec_flat_search_eligible, amdrec_flat_search_mixed_eligible, added exports; then
+                               * the same masks in the inverted-list scans: amdrec_ivf_scan_eligible, amdrec_ivf_scan_grouped_eligible,
+                               * amdrec_ivf_scan_grouped_mixed_eligible, amdrec_ivfpq_scan_finite_eligible, added exports) */
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -147,6 +149,45 @@ int amdrec_ivf_scan_grouped_mixed(const float* lists, int64_t ld, const uint16_t
                                   int64_t qtile_bound, int qtile, const int64_t* pair_query, uint64_t* pool_keys,
                                   int64_t pool_ld, int64_t pos_offset, const float* tau, int64_t ld_tau,
                                   const float* tau_lo /*[nq]*/, int64_t* pool_fill /*[nq]*/, void* stream);
+/* Per-request eligibility masks in the list scans: the three scans above over the rows each query may be shown (the
+ * contract of amdrec_flat_search_eligible).  Each entry takes the argument list of its plain twin plus three device
+ * pointers, all required and 8-byte aligned (checked with the other arguments, before the first HIP call):
+ *   list_tags   [N]  one 64-bit tag per LIST-ORDER row, list_tags[r] = tag of corpus row row_pos[r]; exactly N words read,
+ *   require_all [nq] / require_any [nq]: indexed by the query numbers of the call - those of `queries` / `probes` /
+ *   pair_query (a driver that passes queries + s per chunk offsets the masks the same way).
+ * Row r is eligible for query q iff (list_tags[r] & require_all[q]) == require_all[q] and (require_any[q] == 0 or
+ * (list_tags[r] & require_any[q]) != 0).  nq == 0 / nothing to scan: AMDREC_OK as the plain twins.
+ * The KEY-0 rule: where a scan writes a slot per (query, row) - amdrec_ivf_scan_eligible, amdrec_ivf_scan_grouped_eligible
+ * with tau == NULL - the slot of an ineligible pair is written as key 0, the value amdrec_ivf_select[_split] treats as
+ * an empty slot (skipped by its histograms and its gather); it is written, not skipped, because the pool is not cleared
+ * between searches, and pool_base / pool_count stay the slot counts of the plain scan.  In filter mode (tau != NULL) the
+ * predicate is and-ed with score >= tau: an ineligible row is not appended.  amdrec_ivf_scan_grouped_mixed_eligible tests
+ * the predicate at nomination, BEFORE the re-score: an ineligible row costs neither a nomination slot nor the fp32 row read.
+ * An eligible row's key is, bit for bit, the key its plain twin writes for it.  With tau[q] = the k-th score of the
+ * ELIGIBLE rows of a subset of the probes (-inf with fewer than k) the two-phase search stays exact. */
+int amdrec_ivf_scan_eligible(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                             const int64_t* list_off, const float* queries, int64_t nq, int64_t ld_queries,
+                             const int64_t* probes, const int64_t* pool_base, int nprobe, uint64_t* pool_keys,
+                             int64_t pool_ld, int64_t pos_offset, void* stream, const uint64_t* list_tags /*[N], list order*/,
+                             const uint64_t* require_all /*[nq]*/, const uint64_t* require_any /*[nq]*/);
+int amdrec_ivf_scan_grouped_eligible(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                                     const int64_t* list_off, int nlist, int64_t max_list_rows, const float* queries,
+                                     int64_t ld_queries, const int64_t* group_off, const int64_t* qtile_prefix,
+                                     int64_t qtile_bound, int qtile, const int64_t* pair_query, const int64_t* pair_probe,
+                                     const int64_t* pool_base, int nprobe, uint64_t* pool_keys, int64_t pool_ld,
+                                     int64_t pos_offset, const float* tau /*or NULL*/, int64_t ld_tau,
+                                     int64_t* pool_fill /*[nq] or NULL*/, void* stream,
+                                     const uint64_t* list_tags /*[N], list order*/, const uint64_t* require_all /*[nq]*/,
+                                     const uint64_t* require_any /*[nq]*/);
+int amdrec_ivf_scan_grouped_mixed_eligible(const float* lists, int64_t ld, const uint16_t* lists_bf16, int64_t ld_bf16, int dim,
+                                           const int64_t* row_pos, const int64_t* list_off, int nlist, int64_t max_list_rows,
+                                           const float* queries, int64_t ld_queries, const uint16_t* queries_bf16,
+                                           int64_t ld_queries_bf16, const int64_t* group_off, const int64_t* qtile_prefix,
+                                           int64_t qtile_bound, int qtile, const int64_t* pair_query, uint64_t* pool_keys,
+                                           int64_t pool_ld, int64_t pos_offset, const float* tau, int64_t ld_tau,
+                                           const float* tau_lo /*[nq]*/, int64_t* pool_fill /*[nq]*/, void* stream,
+                                           const uint64_t* list_tags /*[N], list order*/, const uint64_t* require_all /*[nq]*/,
+                                           const uint64_t* require_any /*[nq]*/);
 /* Step 1 as a dense key table (replaces the `index.search` of faiss's IndexFlatIP quantizer inside IndexIVFFlat.search,
  * faiss_retrieval.py:50-55, :150-155): keys[q][c] = 64-bit (score of query q against centroid c, ~c) for every centroid -
  * the pool format of amdrec_ivf_select, which then yields the nprobe best centroids per query (score desc, lower centroid
@@ -225,6 +266,16 @@ int amdrec_ivfpq_scan_finite(const uint8_t* codes, int m, const int64_t* row_pos
                              int nprobe, const int64_t* group_off, const int64_t* qtile_prefix, int64_t qtile_bound,
                              int qtile, const int64_t* pair_query, const int64_t* pair_probe, const int64_t* pool_base,
                              int64_t npairs, uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset, void* stream);
+/* amdrec_ivfpq_scan_finite over the rows each query may be shown: list_tags / require_all / require_any and the key-0 rule
+ * as amdrec_ivf_scan_grouped_eligible above (both loops, the finite rows and the -inf tail, store key 0 for an ineligible
+ * (query, row) pair); an eligible row's key is the plain scan's. */
+int amdrec_ivfpq_scan_finite_eligible(const uint8_t* codes, int m, const int64_t* row_pos, const int64_t* list_off,
+                                      const int64_t* list_finite /*[nlist]*/, int nlist, int64_t max_list_rows,
+                                      const float* tables, int nprobe, const int64_t* group_off, const int64_t* qtile_prefix,
+                                      int64_t qtile_bound, int qtile, const int64_t* pair_query, const int64_t* pair_probe,
+                                      const int64_t* pool_base, int64_t npairs, uint64_t* pool_keys, int64_t pool_ld,
+                                      int64_t pos_offset, void* stream, const uint64_t* list_tags /*[N], list order*/,
+                                      const uint64_t* require_all /*[nq]*/, const uint64_t* require_any /*[nq]*/);
 int amdrec_ivfpq_distances(const float* scores /*[nq][k]*/, int64_t nq, int k, float* distances /*[nq][k], may alias*/,
                            void* stream);
 /* Refine (ABI v14; faiss IndexRefineFlat over the IVFPQ index): re-rank each query's kc candidates (corpus positions as

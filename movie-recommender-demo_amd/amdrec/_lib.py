@@ -45,6 +45,14 @@ _SIGNATURES = {
     "amdrec_ivf_filter_bounds": [_fp, _i64, _i64, _i32, _vp, _i64, _fp, _fp, _i64, _fp, _vp],
     "amdrec_ivf_scan_grouped_mixed": [_fp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i64, _fp, _i64, _vp, _i64, _vp, _vp, _i64,
                                       _i32, _vp, _vp, _i64, _i64, _fp, _i64, _fp, _vp, _vp],
+    # the *_eligible list scans: their plain twin's arguments + (list_tags, require_all, require_any)
+    "amdrec_ivf_scan_eligible": [_fp, _i64, _i32, _vp, _vp, _fp, _i64, _i64, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    "amdrec_ivf_scan_grouped_eligible": [_fp, _i64, _i32, _vp, _vp, _i32, _i64, _fp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp,
+                                         _i32, _vp, _i64, _i64, _fp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "amdrec_ivf_scan_grouped_mixed_eligible": [_fp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i64, _fp, _i64, _vp, _i64, _vp, _vp,
+                                               _i64, _i32, _vp, _vp, _i64, _i64, _fp, _i64, _fp, _vp, _vp, _vp, _vp, _vp],
+    "amdrec_ivfpq_scan_finite_eligible": [_vp, _i32, _vp, _vp, _vp, _i32, _i64, _fp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp,
+                                          _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
     "amdrec_ivf_select": [_vp, _i64, _vp, _i64, _i32, _fp, _vp, _vp],
     "amdrec_ivf_select_split": [_vp, _i64, _vp, _i64, _i32, _i32, _fp, _vp, _vp, _sz, _vp, _vp],
     "amdrec_ivf_coarse_keys": [_fp, _i32, _i64, _i32, _fp, _i64, _i64, _vp, _i64, _vp],

@@ -1,7 +1,8 @@
 """Per-request eligibility masks ("only the ads this request may be shown": geo, device and placement targeting, paused
 campaigns, brand-safety classes).
 
-Contract (Flat index, both engines, every dimension).  Every ad carries one 64-bit TAG word; the library does not interpret
+Contract (Flat index, both engines, every dimension; an IVF / IVFPQ index constructed with ``list_tags=True`` applies the same
+predicate inside its list scans and returns its own result restricted to eligible rows).  Every ad carries one 64-bit TAG word; the library does not interpret
 it, the caller assigns the bits; an ad that was never given a tag has tag 0.  Every query carries two 64-bit words,
 ``require_all`` and ``require_any``.  Row ``r`` is eligible for query ``q`` iff
 

@@ -85,7 +85,7 @@ class _Handle:
 class FAISSIndex:
     def __init__(self, dimension: int, index_type: str = "IVF", nlist: int = 100, nprobe: int = 10,
                  use_gpu: bool = False, device=None, verbose: bool = False, prefilter: str = "bf16", pq_m: int = 8,
-                 refine: Optional[str] = None, refine_factor: int = 4):
+                 refine: Optional[str] = None, refine_factor: int = 4, list_tags: bool = False):
         """``use_gpu`` is accepted for signature compatibility; the index always lives on the
         HIP device (``device`` or the current one) - there is no CPU engine.
         ``prefilter`` (Flat only): "bf16" keeps a bf16 copy of the corpus next to the fp32 one and searches with
@@ -94,7 +94,11 @@ class FAISSIndex:
         ``refine`` (IVFPQ only): None = codes only; "fp32" / "bf16" also keep every normalised row in that format (1024 /
         512 bytes per ad at d = 256; "bf16" needs dimension % 8 == 0) and a search for k re-ranks the
         min(k * ``refine_factor``, 2048) best candidates of the code scan by their exact squared L2 distance to the kept row
-        (for "bf16": to the bf16-rounded row), as faiss's IndexRefineFlat does.  The clamp to 2048 (AMDREC_MAX_K) is silent."""
+        (for "bf16": to the bf16-rounded row), as faiss's IndexRefineFlat does.  The clamp to 2048 (AMDREC_MAX_K) is silent.
+        ``list_tags`` (IVF / IVFPQ; ignored for Flat, which takes masks anyway): the index also keeps its tag words in list
+        order (8 bytes per ad next to the lists, rebuilt with the list layout) and its searches take ``require_all`` /
+        ``require_any``: the predicate is tested inside the list scans.  Without it an IVF / IVFPQ index refuses masks;
+        ``enable_list_tags()`` opts in an index that is already built or loaded."""
         if prefilter not in ("bf16", "fp32"):
             raise ValueError("prefilter must be 'bf16' or 'fp32'")
         self.prefilter = prefilter
@@ -104,6 +108,7 @@ class FAISSIndex:
         self.nprobe = int(nprobe)
         self.pq_m = int(pq_m)
         self.refine, self.refine_factor = refine, refine_factor
+        self.list_tags = bool(list_tags)
         self.use_gpu = use_gpu
         self.verbose = verbose
         self.device = torch.device(device if device is not None else "cuda")
@@ -196,6 +201,17 @@ class FAISSIndex:
         self._pq = None if self._keeps_rows else state
         self._ivf = state if self._keeps_rows else state.ivf
         self._trained = True
+        if getattr(self, "list_tags", False):
+            self._ivf.tag_source = self._ensure_tags
+
+    def enable_list_tags(self):
+        """Opt an IVF / IVFPQ index that is already built (or was loaded from a file saved without the flag) into eligibility
+        masks: from now on it keeps its tags in list order (made here when the lists are laid out, else with the layout) and
+        its searches take ``require_all`` / ``require_any``.  The flag is saved with the index.  Nothing to do for Flat."""
+        self.list_tags = True
+        if self._ivf is not None:
+            self._ivf.tag_source = self._ensure_tags
+            self._ivf.refresh_list_tags()
 
     def _shadow_rows(self, lo, hi):
         """(Re)build rows [lo, hi) of the bf16 shadow from the fp32 rows and fold their norms into _maxnorm."""
@@ -207,13 +223,16 @@ class FAISSIndex:
                                         _lib.ptr(self._maxnorm), _lib.stream_ptr(self.device)))
 
     def _check_masks(self, require_all, require_any) -> bool:
-        """Were eligibility masks passed?  Only a Flat index takes them (checked before the library is touched)."""
+        """Were eligibility masks passed?  A Flat index takes them, an IVF / IVFPQ index only when it keeps list-order tags
+        (``list_tags=True`` / ``enable_list_tags()``); checked before the library is touched."""
         if require_all is None and require_any is None:
             return False
-        if self.index_type != "Flat":
+        if self.index_type != "Flat" and not getattr(self, "list_tags", False):
             raise NotImplementedError(
-                f"eligibility masks (require_all / require_any) are implemented for the Flat index only; the {self.index_type} "
-                "scan kernels do not test the predicate yet - that is the follow-up (DESIGN.md, 'Per-request eligibility masks')")
+                f"eligibility masks (require_all / require_any) on an {self.index_type} index need its list-order tags: construct "
+                "it with list_tags=True or call enable_list_tags().  Without them only the Flat index takes masks; the "
+                "list scans are the follow-up that this opt-in switches on (DESIGN.md, 'Eligibility masks in the "
+                "inverted-list scans')")
         return True
 
     def _ensure_tags(self) -> torch.Tensor:
@@ -230,6 +249,8 @@ class FAISSIndex:
         new = torch.zeros((self._ids.shape[0],), dtype=torch.int64, device=self.device)
         new[:self._n].copy_(words)
         self._tags = new
+        if self._ivf is not None:                                    # list_tags: the list-order copy follows the swap
+            self._ivf.refresh_list_tags()
 
     def get_tags(self) -> torch.Tensor:
         """The tag words, device int64 [ntotal] (a copy; zeros for an index that never saw a tag)."""
@@ -439,10 +460,12 @@ class FAISSIndex:
         unfiltered search for k + E with those ids removed, order kept, cut to k (amdrec.exclude has the contract;
         k + E <= AMDREC_MAX_K).  It applies to ids also under ``return_positions``.  None or E = 0: the plain search, not
         one launch more.
-        ``require_all`` / ``require_any`` (Flat only): device int64 [nq], the queries' eligibility masks against the rows'
-        tags (amdrec.eligible has the contract): the exact top-k of each query's eligible rows, the tail unfilled when
+        ``require_all`` / ``require_any`` (Flat; IVF / IVFPQ with ``list_tags``): device int64 [nq], the queries' eligibility
+        masks against the rows' tags (amdrec.eligible has the contract): the exact top-k of each query's eligible rows, the tail unfilled when
         fewer than k are eligible.  Where one is given the other defaults to 0; both None: the plain search, not one
-        launch more.  With ``exclude`` the filtered search runs for k + E.  IVF / IVFPQ raise NotImplementedError."""
+        launch more.  With ``exclude`` the filtered search runs for k + E.  IVF / IVFPQ: the index's own result restricted
+        to eligible rows - the exact top-k, in its own order and with its own scores, of the eligible rows of the probed
+        lists (IVFPQ refine re-ranks the best eligible candidates); without ``list_tags`` they raise NotImplementedError."""
         masked = self._check_masks(require_all, require_any)
         if exclude is not None and exclude.shape[-1] > 0:
             return self._search_excluding(queries, k, normalize, return_positions, pos_offset, exclude, _exclude_positions,
@@ -461,16 +484,17 @@ class FAISSIndex:
         else:
             q = q.contiguous()
         nq = q.shape[0]
-        elig = None
+        elig = masks = None
         if masked:
-            elig = (self._ensure_tags(), *_eligible.device_masks(require_all, require_any, nq, self.device))
+            masks = _eligible.device_masks(require_all, require_any, nq, self.device)
+            elig = (self._ensure_tags(), *masks)
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         pos = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         off = pos_offset if return_positions else 0
         if self.index_type == "IVF":
-            self._ivf.search(self._xb, self._n, q, k, self.nprobe, scores, pos, pos_offset=off)
+            self._ivf.search(self._xb, self._n, q, k, self.nprobe, scores, pos, pos_offset=off, elig=masks)
         elif self.index_type == "IVFPQ":                              # scores = squared L2 distances, ascending
-            self._pq.search(q, k, self.nprobe, scores, pos, pos_offset=off)
+            self._pq.search(q, k, self.nprobe, scores, pos, pos_offset=off, elig=masks)
         elif self._mixed:
             flat_search_mixed(self._xb, self._xb16, self._maxnorm, self._n, q, k, scores, pos, pos_offset=off,
                               n_fixup=self.n_fixup_out, elig=elig)
@@ -613,6 +637,8 @@ class FAISSIndex:
             header["pq_m"] = self.pq_m
             if self.refine is not None:                              # (absent: an unrefined index, as every earlier file)
                 header["refine"], header["refine_factor"] = self.refine, int(self.refine_factor)
+        if self.index_type != "Flat" and self.list_tags:             # (absent: no list-order tags, as every earlier file)
+            header["list_tags"] = True
         if self._host_ids is not None:
             header["host_ids"] = [_encode_id(x) for x in self._host_ids]     # typed: ids round-trip as what they were
         hj = json.dumps(header).encode()
@@ -644,6 +670,7 @@ class FAISSIndex:
         self.nprobe = header["nprobe"]
         self.pq_m = int(header.get("pq_m", self.pq_m))
         self.refine, self.refine_factor = header.get("refine"), int(header.get("refine_factor", 4))
+        self.list_tags = bool(header.get("list_tags", False))
         self._create_index()
         n = header["ntotal"]
         self._reserve(n)

@@ -15,6 +15,8 @@ Trainer: spherical Lloyd, max-inner-product assignment (the quantizer is IndexFl
 training points per centroid, 10 iterations, seed 1234 (faiss' documented defaults).
 Search = coarse probes -> [nearest eighth of the probes: grouped scan -> select -> tau] -> [other probes: grouped scan keeping
 score >= tau] -> select (exact: tau is the k-th score over a subset of the candidates, hence a lower bound of the final one).
+Eligibility masks (opt-in, ``FAISSIndex(list_tags=True)``): ``InvertedLists`` also keeps the tag words in list order and every
+scan of a masked search is its ``*_eligible`` twin ("Eligibility masks in the inverted-list scans").
 Sharding: the centroids are SHARED by all ranks (``amdrec.sharded.share_ivf_centroids``); a rank
 files its own rows under them and holds its slice of every list, so the union of the ranks' scans is exactly the
 unsharded scan and the merged top-k is bit-identical to the unsharded IVF result.
@@ -150,6 +152,12 @@ class InvertedLists:
         self._nlist_count = None                                    # device: nlist per query (the coarse select's pool sizes)
         self._sel_scratch = None                                    # device: amdrec_ivf_select_split's partial lists and tickets
         self._sel_tickets = None
+        # Eligibility masks in the list scans (FAISSIndex(list_tags=True)): tag_source() -> the owner's tag words in
+        # insertion order (int64 [>= n]); list_tags = those words in LIST order (tags[spos], 8 bytes per row), made with the
+        # layout and again when the owner swaps its tag tensor (_list_tags_of: the tensor list_tags was gathered from)
+        self.tag_source = None
+        self.list_tags: Optional[torch.Tensor] = None
+        self._list_tags_of = None
 
     # -- build ----------------------------------------------------------------------------
     @classmethod
@@ -217,7 +225,36 @@ class InvertedLists:
         # rows of the p longest lists, p = 1 .. nlist: the tight host-side bound of a query's candidate pool
         # (its nprobe probed lists cannot hold more than the nprobe longest; once per list rebuild, like max above)
         self._top_rows = np.cumsum(np.sort(counts.cpu().numpy())[::-1].astype(np.int64))
+        self.list_tags = self._list_tags_of = None
+        self.refresh_list_tags()
         return self.lists
+
+    def refresh_list_tags(self) -> Optional[torch.Tensor]:
+        """list_tags of the current layout from the owner's current tag tensor (amdrec_rows_gather, out of place: a search in
+        flight or a captured graph keeps the copy it started with).  Nothing to do without ``tag_source``, before the first
+        layout, or while the copy made from this very tensor for this very layout stands (the owner writes a tag tensor in
+        place only for rows that no layout holds yet)."""
+        if self.tag_source is None or self.lists is None:
+            return None
+        tags = self.tag_source()
+        if self.list_tags is None or self._list_tags_of is not tags:
+            self.list_tags = gather_rows(tags, self.lists.spos, self.lists.n)
+            self._list_tags_of = tags
+        return self.list_tags
+
+    def elig_tail(self, elig, nq: int):
+        """``elig`` = (require_all, require_any) device int64 [nq] -> f(s): the three trailing pointers of an *_eligible scan
+        for the queries from s on (the masks are offset with the queries)."""
+        if self.tag_source is None:
+            raise ValueError("eligibility masks need list-order tags: FAISSIndex(list_tags=True) or enable_list_tags()")
+        lt = self.refresh_list_tags()
+        ma, my = (_lib.require_gpu(t, name, torch.int64) for t, name in zip(elig, ("require_all", "require_any")))
+        for t, name in ((ma, "require_all"), (my, "require_any")):
+            if t.shape != (nq,) or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous int64 [{nq}], got {tuple(t.shape)}")
+        if lt.shape != (self.lists.n,):
+            raise ValueError("list_tags does not match the list layout")
+        return lambda s: (_lib.ptr(lt), _lib.ptr(ma[s:]), _lib.ptr(my[s:]))
 
     def pool_rows_bound(self, nprobe: int) -> int:
         """Upper bound of the rows a query's ``nprobe`` probed lists hold = the ``nprobe`` longest lists' rows.  Round 2
@@ -301,7 +338,8 @@ class InvertedLists:
 
     def resident_tensors(self) -> list:
         """Every device tensor kept between calls (a captured graph's kernels point at them)."""
-        kept = [self.centroids, self.assign, self._nlist_count, self._sel_scratch, self._sel_tickets, *(self.lists or ())]
+        kept = [self.centroids, self.assign, self._nlist_count, self._sel_scratch, self._sel_tickets, self.list_tags,
+                *(self.lists or ())]
         return [t for t in kept if isinstance(t, torch.Tensor)]
 
     # -- persistence ----------------------------------------------------------------------
@@ -355,7 +393,10 @@ class IVFState(InvertedLists):
 
     # -- search ---------------------------------------------------------------------------
     def search(self, xb: torch.Tensor, n: int, q: torch.Tensor, k: int, nprobe: int, out_scores: torch.Tensor,
-               out_pos: torch.Tensor, pos_offset: int = 0):
+               out_pos: torch.Tensor, pos_offset: int = 0, elig=None):
+        """``elig``: (require_all, require_any) device int64 [nq] -> every scan of the search is its *_eligible twin over
+        ``list_tags`` (same probes, same phases, same tiles; the first phase's tau is the k-th ELIGIBLE score); None: the
+        plain scans, nothing else."""
         lib = _lib.load()
         nq = q.shape[0]
         if nq == 0:
@@ -365,6 +406,8 @@ class IVFState(InvertedLists):
             out_pos.fill_(-1)
             return
         xs, spos, off, _, max_len, _ = self._build_lists(xb, n)
+        tail = (lambda s: ()) if elig is None else self.elig_tail(elig, nq)      # noqa: E731
+        sfx = "" if elig is None else "_eligible"
         nprobe = search_nprobe(nprobe, self.nlist)
         base = torch.empty((nq, nprobe), dtype=torch.int64, device=self.device)
         n_pool = torch.empty((nq,), dtype=torch.int64, device=self.device)
@@ -393,17 +436,17 @@ class IVFState(InvertedLists):
                 # bf16 prefilter: tau_lo = tau - eps_q, nominate on the bf16 shadow, re-score the nominated rows in fp32
                 _lib.check(lib.amdrec_ivf_filter_bounds(_lib.ptr(q[s:]), m, q.stride(0), self.dim, _lib.ptr(q16[s:]), q16.stride(0),
                                                         _lib.ptr(mx16), _lib.ptr(tau), tau.stride(0), _lib.ptr(tau_lo[s:]), st()))
-                _lib.check(lib.amdrec_ivf_scan_grouped_mixed(
+                _lib.check(getattr(lib, "amdrec_ivf_scan_grouped_mixed" + sfx)(
                     _lib.ptr(xs), xs.stride(0), _lib.ptr(xs16), xs16.stride(0), self.dim, _lib.ptr(spos), _lib.ptr(off),
                     self.nlist, max_len, _lib.ptr(q[s:]), q.stride(0), _lib.ptr(q16[s:]), q16.stride(0), _lib.ptr(goff),
                     _lib.ptr(qtp), (m * ncol) // qt + self.nlist, qt, _lib.ptr(pair_q), _lib.ptr(ws), pool_ld, pos_offset,
-                    _lib.ptr(tau), tau.stride(0), _lib.ptr(tau_lo[s:]), _lib.ptr(fill), st()))
+                    _lib.ptr(tau), tau.stride(0), _lib.ptr(tau_lo[s:]), _lib.ptr(fill), st(), *tail(s)))
                 return
-            _lib.check(lib.amdrec_ivf_scan_grouped(
+            _lib.check(getattr(lib, "amdrec_ivf_scan_grouped" + sfx)(
                 _lib.ptr(xs), xs.stride(0), self.dim, _lib.ptr(spos), _lib.ptr(off), self.nlist, max_len,
                 _lib.ptr(q[s:]), q.stride(0), _lib.ptr(goff), _lib.ptr(qtp), (m * ncol) // qt + self.nlist, qt,
                 _lib.ptr(pair_q), _lib.ptr(pair_p), _lib.ptr(base[s:]), ncol, _lib.ptr(ws), pool_ld, pos_offset,
-                _lib.ptr(tau), 0 if tau is None else tau.stride(0), _lib.ptr(fill), st()))
+                _lib.ptr(tau), 0 if tau is None else tau.stride(0), _lib.ptr(fill), st(), *tail(s)))
 
         # Exact two-phase scan (batches that take the grouped scan, >= TWO_PHASE_MIN_PROBES probes): the nearest eighth of
         # the probes unfiltered -> select -> tau = that subset's k-th score, a LOWER bound of the final k-th score -> the other
@@ -428,7 +471,7 @@ class IVFState(InvertedLists):
                 group_and_scan(s, m, 0, nprobe, n_out=n_pool[s:])
             else:
                 self.group(w, probes[s:], nprobe, m, nprobe, base[s:], n_pool[s:], qtile)
-                _lib.check(lib.amdrec_ivf_scan(_lib.ptr(xs), xs.stride(0), self.dim, _lib.ptr(spos), _lib.ptr(off),
-                                               _lib.ptr(q[s:]), m, q.stride(0), _lib.ptr(probes[s:]),
-                                               _lib.ptr(base[s:]), nprobe, _lib.ptr(ws), pool_ld, pos_offset, st()))
+                _lib.check(getattr(lib, "amdrec_ivf_scan" + sfx)(
+                    _lib.ptr(xs), xs.stride(0), self.dim, _lib.ptr(spos), _lib.ptr(off), _lib.ptr(q[s:]), m, q.stride(0),
+                    _lib.ptr(probes[s:]), _lib.ptr(base[s:]), nprobe, _lib.ptr(ws), pool_ld, pos_offset, st(), *tail(s)))
             self.select(ws, pool_ld, n_pool[s:], m, k, out_scores[s:], out_pos[s:])

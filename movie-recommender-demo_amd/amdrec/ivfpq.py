@@ -199,8 +199,10 @@ class IVFPQState:
         return self.ivf.coarse_probes(q, nprobe)
 
     def search(self, q: torch.Tensor, k: int, nprobe: int, out_dist: torch.Tensor, out_pos: torch.Tensor,
-               pos_offset: int = 0):
-        """q: L2-normalised queries.  -> out_dist [nq, k] squared L2 distances (ascending, +inf = unfilled): approximate
+               pos_offset: int = 0, elig=None):
+        """``elig``: (require_all, require_any) device int64 [nq] -> the code scan is amdrec_ivfpq_scan_finite_eligible over the
+        coarse level's ``list_tags``; with refine the re-rank then orders the best ELIGIBLE candidates and needs no masks.
+        q: L2-normalised queries.  -> out_dist [nq, k] squared L2 distances (ascending, +inf = unfilled): approximate
         (from the codes), or with refine exact for the kept rows; out_pos [nq, k] positions + pos_offset (-1 = unfilled)."""
         nq = q.shape[0]
         if nq == 0:
@@ -210,14 +212,14 @@ class IVFPQState:
             out_pos.fill_(-1)
             return
         if self.rows is None:
-            self._search_codes(q, k, nprobe, out_dist, out_pos, pos_offset)
+            self._search_codes(q, k, nprobe, out_dist, out_pos, pos_offset, elig=elig)
             return
         # steps 1-4 for k' candidates (scores = -approximate distance: only their order matters), then
         # 5. the exact re-rank of those candidates from the kept rows
         kc = refine_candidates(k, self.refine_factor)
         cand_score = torch.empty((nq, kc), dtype=torch.float32, device=self.device)
         cand_pos = torch.empty((nq, kc), dtype=torch.int64, device=self.device)
-        self._search_codes(q, kc, nprobe, cand_score, cand_pos, 0, distances=False)
+        self._search_codes(q, kc, nprobe, cand_score, cand_pos, 0, distances=False, elig=elig)
         self.rerank(q, cand_pos, k, out_dist, out_pos, pos_offset)
 
     def rerank(self, q: torch.Tensor, cand_pos: torch.Tensor, k: int, out_dist: torch.Tensor, out_pos: torch.Tensor,
@@ -242,13 +244,15 @@ class IVFPQState:
                 _lib.ptr(self._rr_tickets) if split else None, _lib.stream_ptr(self.device)))
 
     def _search_codes(self, q: torch.Tensor, k: int, nprobe: int, out_dist: torch.Tensor, out_pos: torch.Tensor,
-                      pos_offset: int = 0, distances: bool = True):
+                      pos_offset: int = 0, distances: bool = True, elig=None):
         """Steps 1-4: the k best rows of the probed lists by the codes' table-lookup distance (``distances`` False: out_dist
         keeps the select's scores, -distance)."""
         lib = _lib.load()
         nq = q.shape[0]
         (codes, spos, off, _, max_len, _), nfin = self._build_lists()
         ivf = self.ivf
+        tail = (lambda s: ()) if elig is None else ivf.elig_tail(elig, nq)      # noqa: E731
+        scan = lib.amdrec_ivfpq_scan_finite if elig is None else lib.amdrec_ivfpq_scan_finite_eligible
         nprobe = search_nprobe(nprobe, self.nlist)
         st = lambda: _lib.stream_ptr(self.device)      # noqa: E731  (per call: check() ends the call's device scope)
         base = torch.empty((nq, nprobe), dtype=torch.int64, device=self.device)
@@ -270,11 +274,11 @@ class IVFPQState:
                                                _lib.ptr(tables), st()))
             # 3. pool layout + (query, probe) pairs grouped by list, then the table-lookup scan of every probed list
             ivf.group(w, probes[s:], nprobe, m, nprobe, base[s:], n_pool[s:], QTILE)
-            _lib.check(lib.amdrec_ivfpq_scan_finite(_lib.ptr(codes), self.m, _lib.ptr(spos), _lib.ptr(off), _lib.ptr(nfin),
-                                                    self.nlist, max_len, _lib.ptr(tables), nprobe, _lib.ptr(w.goff),
-                                                    _lib.ptr(w.qtp), (m * nprobe) // QTILE + self.nlist, QTILE,
-                                                    _lib.ptr(w.pair_q), _lib.ptr(w.pair_p), _lib.ptr(base[s:]), m * nprobe,
-                                                    _lib.ptr(w.pool), pool_ld, pos_offset, st()))
+            _lib.check(scan(_lib.ptr(codes), self.m, _lib.ptr(spos), _lib.ptr(off), _lib.ptr(nfin),
+                            self.nlist, max_len, _lib.ptr(tables), nprobe, _lib.ptr(w.goff),
+                            _lib.ptr(w.qtp), (m * nprobe) // QTILE + self.nlist, QTILE,
+                            _lib.ptr(w.pair_q), _lib.ptr(w.pair_p), _lib.ptr(base[s:]), m * nprobe,
+                            _lib.ptr(w.pool), pool_ld, pos_offset, st(), *tail(s)))
             # 4. the k best keys (score = -distance) -> distances
             ivf.select(w.pool, pool_ld, n_pool[s:], m, k, out_dist[s:], out_pos[s:])
         if distances:

@@ -18,6 +18,35 @@ __device__ __forceinline__ float fma4(f32x4 x, f32x4 y, float acc) {
     return __builtin_fmaf(x[3], y[3], __builtin_fmaf(x[2], y[2], __builtin_fmaf(x[1], y[1], __builtin_fmaf(x[0], y[0], acc))));
 }
 
+// ---- per-request eligibility in the list scans (the *_eligible scan entries; amdrec.h has the contract) ----------------------
+// The flat search's predicate (search.hip) over LIST-ORDER tags: list_tags[r] is the tag word of list-order row r (the
+// index keeps list_tags = tags[row_pos] next to its lists), so a scan reads a row's tag where it reads the row's position,
+// coalesced.  Every scan kernel and epilogue takes the predicate as a type: ListNoElig, an empty one, in the scans without
+// masks - their kernels are the ones they were -, ListElig in the filtered instantiations.  A scan reads a tag once per row
+// (tag) and a query's two words once per accumulator register (mask), then tests them per (query, row) element (ok).
+struct ListNoElig {
+    static constexpr bool on = false;
+    struct Tag {};
+    struct Mask {};
+    __device__ __forceinline__ ListNoElig at(long long) const { return {}; }
+    __device__ __forceinline__ Tag tag(long long) const { return {}; }
+    __device__ __forceinline__ Mask mask(long long) const { return {}; }
+    static __device__ __forceinline__ bool ok(Tag, Mask) { return true; }
+};
+struct ListElig {
+    static constexpr bool on = true;
+    const uint64_t* tags;    // [N], list order
+    const uint64_t* all;     // [nq]
+    const uint64_t* any;     // [nq]
+    using Tag = uint64_t;
+    struct Mask { uint64_t all, any; };
+    __device__ __forceinline__ ListElig at(long long r0) const { return {tags + r0, all, any}; }   // rows counted from r0
+    __device__ __forceinline__ Tag tag(long long row) const { return tags[row]; }
+    // q < 0: no query in this accumulator register (nothing is loaded; the caller drops the register's elements)
+    __device__ __forceinline__ Mask mask(long long q) const { return q >= 0 ? Mask{all[q], any[q]} : Mask{0ull, 0ull}; }
+    static __device__ __forceinline__ bool ok(Tag t, Mask m) { return (t & m.all) == m.all && (m.any == 0ull || (t & m.any) != 0ull); }
+};
+
 // The list of query tile y of amdrec_ivf_group (blockIdx.y of a grouped scan): l with qt_prefix[l] <= y < qt_prefix[l+1];
 // the caller has returned for y >= qt_prefix[nlist].  The kernels keep the rest of the frame (list_off / group_off / p0 and
 // the second early return) themselves: moved in here as well, in any form tried, it compiled to another instruction stream.

@@ -14,12 +14,19 @@
 
 namespace amdrec {
 
+// EL (ListNoElig or ListElig, invlists.hpp): the eligibility predicate; EP: its pointers as trailing kernel arguments - none
+// for ListNoElig, whose instantiation takes the arguments the kernel always took and compiles to the code it always was;
+// (list_tags, all, any) for ListElig.  The scans below take them the same way.  This scan is a slot mode: an ineligible
+// (query, row) slot is stored as key 0, the select's EMPTY-slot value - stored, not skipped: the pool is not cleared
+// between searches.
+template <class EL = ListNoElig, class... EP>
 __global__ __launch_bounds__(256) void ivf_scan_kernel(const float* xs, long long ld, int d, const long long* spos,
                                                        const long long* list_off, const float* Q, long long ldq,
                                                        const long long* probes, const long long* base, int nprobe,
                                                        unsigned long long* keys, long long pool_ld,
-                                                       long long pos_offset) {
+                                                       long long pos_offset, EP... elig) {
     __shared__ __attribute__((aligned(16))) float qv[2048];
+    const EL el{elig...};
     const int q = blockIdx.y, p = blockIdx.x;
     const long long l = probes[(long long)q * nprobe + p];
     if (l < 0) return;
@@ -41,6 +48,7 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const float* xs, long lon
     unsigned long long* dst = keys + (long long)q * pool_ld + base[(long long)q * nprobe + p];
     const int d4 = d >> 2;
     constexpr int NW = 4, U = 8;
+    const typename EL::Mask mq = el.mask(q);
     for (long long row0 = rb; row0 < r1; row0 += NW * U) {
         float part[U];
         const f32x4* xr[U];
@@ -70,7 +78,12 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const float* xs, long lon
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
             const long long r = row0 + w * U + u;
-            if (lane == 0 && r < r1) dst[r - r0] = make_key(rank_last(a), (uint32_t)(spos[r] + pos_offset));
+            if constexpr (EL::on) {
+                if (lane == 0 && r < r1)
+                    dst[r - r0] = EL::ok(el.tag(r), mq) ? make_key(rank_last(a), (uint32_t)(spos[r] + pos_offset)) : 0ull;
+            } else {
+                if (lane == 0 && r < r1) dst[r - r0] = make_key(rank_last(a), (uint32_t)(spos[r] + pos_offset));
+            }
         }
     }
 }
@@ -93,8 +106,9 @@ struct GatherRows {
     }
 };
 
-struct EpiIvfKeys {
-    static constexpr const char* name = "ivf_scan";
+template <class EL>
+struct EpiIvfKeysT {
+    static constexpr const char* name = EL::on ? "ivf_scan_elig" : "ivf_scan";
     static constexpr double out_bytes_per_elem = 2.0;
     static constexpr size_t lds_bytes(int) { return 0; }
     const long long* spos;      // positions of this list's rows
@@ -111,6 +125,9 @@ struct EpiIvfKeys {
     const float* tau;
     long long ld_tau;
     unsigned long long* fill;
+    // eligibility (rows counted from the list's first, as spos): slot mode stores key 0, the select's empty-slot value, for
+    // an ineligible (query, row) element; filter mode tests the predicate with the threshold and does not append the row
+    [[no_unique_address]] EL el;
     template <class A>
     __device__ void operator()(A& acc, float*) const {
         constexpr int TP = A::TP, TQ = A::TQ;
@@ -120,10 +137,12 @@ struct EpiIvfKeys {
         // pair_q -> tau / pair_p -> base row by row inside the store loop: 32-48 dependent round trips per workgroup,
         // longer than the tile's MFMAs on short lists.
         long long rowq[TQ], posq[TQ];
+        typename EL::Tag tagq[TQ];
 #pragma unroll
         for (int j = 0; j < TQ; ++j) {
             rowq[j] = acc.q(j, lane);                             // row inside the list
             posq[j] = rowq[j] < list_rows ? spos[rowq[j]] + pos_offset : -1;
+            tagq[j] = rowq[j] < list_rows ? el.tag(rowq[j]) : typename EL::Tag{};
         }
 #pragma unroll
         for (int i = 0; i < TP; ++i) {
@@ -133,6 +152,21 @@ struct EpiIvfKeys {
                 const long long jj = acc.p(i, r, lane);          // member of the group (depends on the lane half)
                 qv[r] = jj < g ? pair_q[jj] : -1;
             }
+            // the queries' two mask words, fetched with the tau / base loads, folded with the rows' tags into one bit per
+            // element (r * TQ + j) at once: the sixteen mask pairs are dead before the store loop (held through it they
+            // took the 64 x 256 tiles to the register limit)
+            uint64_t okb = 0ull;
+            if constexpr (EL::on) {
+                static_assert(16 * TQ <= 64, "one eligibility bit per accumulator element of a tile row");
+                typename EL::Mask mv[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) mv[r] = el.mask(qv[r]);
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+#pragma unroll
+                    for (int j = 0; j < TQ; ++j) okb |= (uint64_t)EL::ok(tagq[j], mv[r]) << (r * TQ + j);
+            }
+            (void)okb;
             if (tau != nullptr) {
                 float tv[16];
 #pragma unroll
@@ -142,7 +176,7 @@ struct EpiIvfKeys {
 #pragma unroll
                     for (int j = 0; j < TQ; ++j) {
                         const float sc = rank_last(acc.v[i][j][r]);
-                        if (sc >= tv[r] && posq[j] >= 0)
+                        if (sc >= tv[r] && posq[j] >= 0 && (!EL::on || ((okb >> (r * TQ + j)) & 1ull)))
                             (keys + qv[r] * pool_ld)[atomicAdd(&fill[qv[r]], 1ull)] = make_key(sc, (uint32_t)posq[j]);
                     }
                 }
@@ -163,7 +197,10 @@ struct EpiIvfKeys {
 #pragma unroll
                 for (int j = 0; j < TQ; ++j) {
                     if (posq[j] < 0) continue;
-                    dst[rowq[j]] = make_key(rank_last(acc.v[i][j][r]), (uint32_t)posq[j]);
+                    if constexpr (EL::on)
+                        dst[rowq[j]] = ((okb >> (r * TQ + j)) & 1ull) ? make_key(rank_last(acc.v[i][j][r]), (uint32_t)posq[j]) : 0ull;
+                    else
+                        dst[rowq[j]] = make_key(rank_last(acc.v[i][j][r]), (uint32_t)posq[j]);
                 }
             }
         }
@@ -181,8 +218,9 @@ struct EpiIvfKeys {
 // appended if that exact score passes tau.  The pool holds exact fp32 keys as before; nothing downstream changes.
 // Hits of a whole tile are collected in one list in LDS (the staging area, free after the K loop), then the workgroup's
 // waves share them; a hit that finds the list full is re-scored by its own lane, in the same summation order (rescore1).
-struct EpiIvfPrefilter {
-    static constexpr const char* name = "ivf_scan_bf16";
+template <class EL>
+struct EpiIvfPrefilterT {
+    static constexpr const char* name = EL::on ? "ivf_scan_bf16_elig" : "ivf_scan_bf16";
     static constexpr double out_bytes_per_elem = 0.0;
     static constexpr size_t lds_bytes(int) { return 0; }        // reuses the staging tiles (checked against their size below)
     const long long* spos;      // positions of this list's rows
@@ -200,6 +238,10 @@ struct EpiIvfPrefilter {
     const float* Q;             // fp32 queries
     long long ldq;
     int d;
+    // eligibility (rows counted from the list's first, as spos): tested at nomination, BEFORE the hit enters the LDS list -
+    // an ineligible row costs neither a list slot nor the fp32 row read of the re-score; rescore16 / rescore1 / keep only
+    // ever see eligible rows
+    [[no_unique_address]] EL el;
     // fp32 score of (list row, query) by the 16 lanes of a quarter wave (sub = lane & 15); every lane returns the sum
     __device__ __forceinline__ float rescore16(long long row, long long q, int sub) const {
         const f32x4* xr = reinterpret_cast<const f32x4*>(xs + row * ld);
@@ -253,13 +295,20 @@ struct EpiIvfPrefilter {
         constexpr int NWAVES = A::WP * A::WQ;
         // the nominations of the whole tile in ONE list over the staging tiles; a nomination that does not fit is re-scored
         // by its own lane on the spot (a tile with thousands of nominations: tau is not selective there)
-        constexpr int CAP = (int)(((size_t)(A::WP * TP + A::WQ * TQ) * 32 * BK * sizeof(float) - 16) / 8);
+        constexpr int BP = A::WP * TP * 32;
+        constexpr size_t STAGE_BYTES = (size_t)(A::WP * TP + A::WQ * TQ) * 32 * BK * sizeof(float);
+        constexpr int CAP = (int)((STAGE_BYTES - 16 - (EL::on ? (size_t)BP * 16 : 0)) / 8);
+        static_assert(BP <= NWAVES * 64 && CAP >= 256, "one query's masks per thread; room for a tile's nominations");
         const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
         int* cnt = reinterpret_cast<int*>(smem);
         unsigned long long* hits = reinterpret_cast<unsigned long long*>(smem + 4);     // (query << 32) | row in the list
         long long rowq[TQ];
+        typename EL::Tag tagq[TQ];
 #pragma unroll
-        for (int j = 0; j < TQ; ++j) rowq[j] = acc.q(j, lane);
+        for (int j = 0; j < TQ; ++j) {
+            rowq[j] = acc.q(j, lane);
+            tagq[j] = rowq[j] < list_rows ? el.tag(rowq[j]) : typename EL::Tag{};
+        }
         // member -> query -> prefilter threshold for all of this lane's accumulator rows at once: two dependent round
         // trips per tile (fetched round by round they were eight)
         int qv[TP][16];
@@ -275,6 +324,22 @@ struct EpiIvfPrefilter {
         for (int i = 0; i < TP; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) tv[i][r] = qv[i][r] >= 0 ? tau_lo[qv[i][r]] : __builtin_nanf("");
+        // eligibility: the two mask words of the tile's BP queries go to the END of the staging area (one query per thread:
+        // pair_q -> all / any, in flight with the pair_q -> tau_lo loads above; the nomination list gives up BP * 16 bytes)
+        // and a hit reads its query's pair from there.  Held in registers - sixteen pairs per lane, or folded into a bit
+        // per accumulator element - they spilled the 64 x 256 tile.
+        const uint64_t* lmask = nullptr;
+        if constexpr (EL::on) {
+            uint64_t* lm = reinterpret_cast<uint64_t*>(smem) + (STAGE_BYTES / 8 - 2 * BP);
+            const long long jj = (long long)(acc.p0 - acc.wp * TP * 32) + tid;
+            if (tid < BP) {
+                const typename EL::Mask m = el.mask(jj < g ? pair_q[jj] : -1);
+                lm[2 * tid] = m.all;
+                lm[2 * tid + 1] = m.any;
+            }
+            lmask = lm;
+        }
+        (void)lmask;
         if (tid == 0) *cnt = 0;
         __syncthreads();                                                  // (also: every wave has left the staging tiles)
 #pragma unroll
@@ -286,6 +351,10 @@ struct EpiIvfPrefilter {
                     const float a = acc.v[i][j][r];
                     // NaN approx (NaN rows / queries): re-score, the exact path decides; NaN threshold: member absent
                     if ((a >= tv[i][r] || (!(a == a) && tv[i][r] == tv[i][r])) && rowq[j] < list_rows) {
+                        if constexpr (EL::on) {
+                            const int m = acc.wp * TP * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);   // acc.p() inside the tile
+                            if (!EL::ok(tagq[j], typename EL::Mask{lmask[2 * m], lmask[2 * m + 1]})) continue;
+                        }
                         const int slot = atomicAdd(cnt, 1);
                         if (slot < CAP) {
                             hits[slot] = ((unsigned long long)(uint32_t)qv[i][r] << 32) | (unsigned long long)rowq[j];
@@ -340,13 +409,14 @@ __global__ __launch_bounds__(256) void ivf_filter_bounds_kernel(const float* Q, 
     }
 }
 
-template <class S>
+template <class S, class EL = ListNoElig, class... EP>
 __global__ __launch_bounds__(S::NT, 2) void ivf_group_scan_mixed_kernel(
     const float* xs, long long ld, const uint16_t* xs16, long long ld16, int d, int ksteps, const long long* spos,
     const long long* list_off, const float* Q, long long ldq, const uint16_t* Q16, long long ldq16, const long long* goff,
     const long long* qt_prefix, int nlist, const long long* pair_q, unsigned long long* keys, long long pool_ld,
-    long long pos_offset, const float* tau, long long ld_tau, const float* tau_lo, unsigned long long* fill) {
+    long long pos_offset, const float* tau, long long ld_tau, const float* tau_lo, unsigned long long* fill, EP... elig) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    const EL el{elig...};
     const long long y = blockIdx.y;
     if (y >= qt_prefix[nlist]) return;
     const int l = tile_list(y, qt_prefix, nlist);
@@ -356,8 +426,8 @@ __global__ __launch_bounds__(S::NT, 2) void ivf_group_scan_mixed_kernel(
     // the bf16 matrices as float matrices of d / 2 columns (gemm_core.hpp, Shape::BF16)
     GatherRows lp{reinterpret_cast<const float*>(Q16), pair_q + g0, g, (int)(ldq16 / 2), d / 2};
     DenseRows lq{reinterpret_cast<const float*>(xs16 + r0 * ld16), len, (int)(ld16 / 2), d / 2, 30, 1ll << 30};
-    EpiIvfPrefilter epi{spos + r0, len, pair_q + g0, g, keys, pool_ld, pos_offset, tau, ld_tau, tau_lo, fill,
-                        xs + r0 * ld, ld, Q, ldq, d};
+    EpiIvfPrefilterT<EL> epi{spos + r0, len, pair_q + g0, g, keys, pool_ld, pos_offset, tau, ld_tau, tau_lo, fill,
+                             xs + r0 * ld, ld, Q, ldq, d, el.at(r0)};
     const long long p0 = (y - qt_prefix[l]) * S::BP;
     for (long long row0 = (long long)blockIdx.x * S::BQ; row0 < len; row0 += (long long)gridDim.x * S::BQ)
         gemm_block<S>(lp, lq, epi, ksteps, p0, row0, smem);
@@ -416,13 +486,14 @@ template <bool BF16> using ShapeIvfS = Shape<2, 2, 1, 2, false, BF16>;    // 64 
 template <bool BF16> using ShapeIvf32S = Shape<1, 4, 1, 1, false, BF16>;  // 32 queries x 128 list rows
 // (double-buffered staging - one barrier per K-step - measured at the per-rank shape: 0.817 against 0.799 ms, not kept)
 
-template <class S>
+template <class S, class EL = ListNoElig, class... EP>
 __global__ __launch_bounds__(S::NT, 2) void ivf_group_scan_kernel(
     const float* xs, long long ld, int d, int ksteps, const long long* spos, const long long* list_off,
     const float* Q, long long ldq, const long long* goff, const long long* qt_prefix, int nlist,
     const long long* pair_q, const long long* pair_p, const long long* base, int nprobe, unsigned long long* keys,
-    long long pool_ld, long long pos_offset, const float* tau, long long ld_tau, unsigned long long* fill) {
+    long long pool_ld, long long pos_offset, const float* tau, long long ld_tau, unsigned long long* fill, EP... elig) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    const EL el{elig...};
     const long long y = blockIdx.y;
     if (y >= qt_prefix[nlist]) return;
     const int l = tile_list(y, qt_prefix, nlist);
@@ -431,7 +502,8 @@ __global__ __launch_bounds__(S::NT, 2) void ivf_group_scan_kernel(
     const long long g0 = goff[l], g = goff[l + 1] - g0;
     GatherRows lp{Q, pair_q + g0, g, (int)ldq, d};
     DenseRows lq{xs + r0 * ld, len, (int)ld, d, 30, 1ll << 30};
-    EpiIvfKeys epi{spos + r0, len, pair_q + g0, pair_p + g0, g, base, nprobe, keys, pool_ld, pos_offset, tau, ld_tau, fill};
+    EpiIvfKeysT<EL> epi{spos + r0, len, pair_q + g0, pair_p + g0, g, base, nprobe, keys, pool_ld, pos_offset, tau, ld_tau, fill,
+                        el.at(r0)};
     const long long p0 = (y - qt_prefix[l]) * S::BP;
     // gridDim.x workgroups share the list's row tiles (round 4: the host no longer launches one workgroup per row tile of
     // the LONGEST list - on short lists three of four workgroups found no rows after paying for the tile search)
@@ -794,25 +866,73 @@ extern "C" int amdrec_ivf_group(const int64_t* probes, int64_t ld_probes, int64_
     return AMDREC_OK;
 }
 
-extern "C" int amdrec_ivf_scan(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
-                               const int64_t* list_off, const float* queries, int64_t nq, int64_t ld_queries,
-                               const int64_t* probes, const int64_t* pool_base, int nprobe, uint64_t* pool_keys,
-                               int64_t pool_ld, int64_t pos_offset, void* stream) {
+// ---- the eligibility pointers of the *_eligible scans ----
+// All three are required and 8-byte aligned, checked with the other arguments before the first HIP call.  A scan entry
+// and its *_eligible twin are ONE host template over the predicate: ListNoElig checks and passes nothing.
+static int elig_check(ListNoElig) { return AMDREC_OK; }
+static int elig_check(ListElig el) {
+    REQUIRE(el.tags != nullptr, "list_tags is null");
+    REQUIRE(el.all != nullptr, "require_all is null");
+    REQUIRE(el.any != nullptr, "require_any is null");
+    REQUIRE(((uintptr_t)el.tags % 8) == 0, "list_tags must be 8-byte aligned");
+    REQUIRE(((uintptr_t)el.all % 8) == 0, "require_all must be 8-byte aligned");
+    REQUIRE(((uintptr_t)el.any % 8) == 0, "require_any must be 8-byte aligned");
+    return AMDREC_OK;
+}
+// the kernel instantiation of a predicate: K<ListNoElig>, or K<ListElig, its three pointers>
+#define AMDREC_LIST_ELIG_ARGS ListElig, const uint64_t*, const uint64_t*, const uint64_t*
+// launches `kern` with the eligibility pointers after the arguments every instantiation takes (ListNoElig: none)
+template <class Kern, class... Args>
+static void launch_with(ListNoElig, Kern kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+}
+template <class Kern, class... Args>
+static void launch_with(ListElig el, Kern kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args..., el.tags, el.all, el.any);
+}
+
+template <class EL>
+static int ivf_scan_impl(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                         const int64_t* list_off, const float* queries, int64_t nq, int64_t ld_queries,
+                         const int64_t* probes, const int64_t* pool_base, int nprobe, uint64_t* pool_keys,
+                         int64_t pool_ld, int64_t pos_offset, void* stream, EL el) {
     REQUIRE(dim >= 4 && dim % 4 == 0 && dim <= 2048, "dim=%d must be a multiple of 4 in [4,2048]", dim);
     REQUIRE(nprobe >= 1 && nprobe <= 65535, "nprobe out of range");
     if (nq <= 0) return AMDREC_OK;
     REQUIRE(nq <= 65535, "at most 65535 queries per call");
     REQUIRE(lists && row_pos && list_off && queries && probes && pool_base && pool_keys, "null pointer");
     REQUIRE(ld % 4 == 0 && ld >= dim && ld_queries >= dim, "bad leading dimension");
+    if (int rc = elig_check(el)) return rc;
     long long splits = 2048 / ((long long)nprobe * nq);            // ~2048 workgroups in all
     splits = splits < 1 ? 1 : (splits > 64 ? 64 : splits);
-    ProfScope prof("ivf_scan_pairs", 0.0, 0.0, reinterpret_cast<hipStream_t>(stream));
-    hipLaunchKernelGGL(ivf_scan_kernel, dim3(nprobe, (unsigned)nq, (unsigned)splits), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       lists, (long long)ld, dim, (const long long*)row_pos, (const long long*)list_off, queries,
-                       (long long)ld_queries, (const long long*)probes, (const long long*)pool_base, nprobe,
-                       (unsigned long long*)pool_keys, (long long)pool_ld, (long long)pos_offset);
+    ProfScope prof(EL::on ? "ivf_scan_pairs_elig" : "ivf_scan_pairs", 0.0, 0.0, reinterpret_cast<hipStream_t>(stream));
+    auto kern = [] {
+        if constexpr (EL::on) return ivf_scan_kernel<AMDREC_LIST_ELIG_ARGS>;
+        else return ivf_scan_kernel<>;
+    }();
+    launch_with(el, kern, dim3(nprobe, (unsigned)nq, (unsigned)splits), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                lists, (long long)ld, dim, (const long long*)row_pos, (const long long*)list_off, queries,
+                (long long)ld_queries, (const long long*)probes, (const long long*)pool_base, nprobe,
+                (unsigned long long*)pool_keys, (long long)pool_ld, (long long)pos_offset);
     HIP_TRY(hipGetLastError());
     return AMDREC_OK;
+}
+
+extern "C" int amdrec_ivf_scan(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                               const int64_t* list_off, const float* queries, int64_t nq, int64_t ld_queries,
+                               const int64_t* probes, const int64_t* pool_base, int nprobe, uint64_t* pool_keys,
+                               int64_t pool_ld, int64_t pos_offset, void* stream) {
+    return ivf_scan_impl(lists, ld, dim, row_pos, list_off, queries, nq, ld_queries, probes, pool_base, nprobe, pool_keys,
+                         pool_ld, pos_offset, stream, ListNoElig{});
+}
+
+extern "C" int amdrec_ivf_scan_eligible(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                                        const int64_t* list_off, const float* queries, int64_t nq, int64_t ld_queries,
+                                        const int64_t* probes, const int64_t* pool_base, int nprobe, uint64_t* pool_keys,
+                                        int64_t pool_ld, int64_t pos_offset, void* stream, const uint64_t* list_tags,
+                                        const uint64_t* require_all, const uint64_t* require_any) {
+    return ivf_scan_impl(lists, ld, dim, row_pos, list_off, queries, nq, ld_queries, probes, pool_base, nprobe, pool_keys,
+                         pool_ld, pos_offset, stream, ListElig{list_tags, require_all, require_any});
 }
 
 // Workgroup columns per (list, query tile): an eighth of the LONGEST list's row tiles, each looping over its share of the
@@ -830,8 +950,8 @@ constexpr long long SHORT_LIST_ROWS = 1536;
 
 // Both grouped kernels are launched here, so the two phases of one search cannot disagree about geometry; `args`: the
 // kernel's arguments
-template <class S, auto Kernel, class... Args>
-static hipError_t launch_grouped(const char* tag, long long max_list_rows, long long qtile_bound, hipStream_t st, Args... args) {
+template <class S, auto Kernel, class EL, class... Args>
+static hipError_t launch_grouped(EL el, const char* tag, long long max_list_rows, long long qtile_bound, hipStream_t st, Args... args) {
     static PerDeviceOnce attr_done;
     if (attr_done.pending()) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -840,19 +960,22 @@ static hipError_t launch_grouped(const char* tag, long long max_list_rows, long 
         attr_done.mark();
     }
     ProfScope prof(tag, 0.0, 0.0, st);
-    hipLaunchKernelGGL(Kernel, dim3((unsigned)scan_columns(max_list_rows, S::BQ), (unsigned)qtile_bound), dim3(S::NT),
-                       S::LDS_BYTES, st, args...);
+    launch_with(el, Kernel, dim3((unsigned)scan_columns(max_list_rows, S::BQ), (unsigned)qtile_bound), dim3(S::NT),
+                S::LDS_BYTES, st, args...);
     return hipGetLastError();
 }
 
 // f(shape, ProfScope tag) for the tile of (qtile, short_lists = the longest list has at most SHORT_LIST_ROWS rows)
-template <bool BF16, class F>
+// (ELIG: the tags of the filtered instantiations end in _elig)
+template <bool BF16, bool ELIG, class F>
 static hipError_t with_scan_shape(int qtile, bool short_lists, F&& f) {
+#define AMDREC_SCAN_TAG(tile) \
+    (BF16 ? (ELIG ? "ivf_scan_grouped_bf16_" tile "_elig" : "ivf_scan_grouped_bf16_" tile) \
+          : (ELIG ? "ivf_scan_grouped_" tile "_elig" : "ivf_scan_grouped_" tile))
     if (qtile == 64)
-        return short_lists ? f(ShapeIvfS<BF16>{}, BF16 ? "ivf_scan_grouped_bf16_64x128" : "ivf_scan_grouped_64x128")
-                           : f(ShapeIvf<BF16>{}, BF16 ? "ivf_scan_grouped_bf16_64x256" : "ivf_scan_grouped_64x256");
-    return short_lists ? f(ShapeIvf32S<BF16>{}, BF16 ? "ivf_scan_grouped_bf16_32x128" : "ivf_scan_grouped_32x128")
-                       : f(ShapeIvf32<BF16>{}, BF16 ? "ivf_scan_grouped_bf16_32x256" : "ivf_scan_grouped_32x256");
+        return short_lists ? f(ShapeIvfS<BF16>{}, AMDREC_SCAN_TAG("64x128")) : f(ShapeIvf<BF16>{}, AMDREC_SCAN_TAG("64x256"));
+    return short_lists ? f(ShapeIvf32S<BF16>{}, AMDREC_SCAN_TAG("32x128")) : f(ShapeIvf32<BF16>{}, AMDREC_SCAN_TAG("32x256"));
+#undef AMDREC_SCAN_TAG
 }
 
 // The arguments the two grouped entries have in common and the refusals they share.  Each entry applies them in its own
@@ -880,13 +1003,14 @@ struct GroupedArgs {
     bool leading_dims() const { return ld % 4 == 0 && ld >= dim && ld_queries >= dim && ld_queries % 4 == 0; }
 };
 
-extern "C" int amdrec_ivf_scan_grouped(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
-                                       const int64_t* list_off, int nlist, int64_t max_list_rows,
-                                       const float* queries, int64_t ld_queries, const int64_t* group_off,
-                                       const int64_t* qtile_prefix, int64_t qtile_bound, int qtile,
-                                       const int64_t* pair_query, const int64_t* pair_probe, const int64_t* pool_base,
-                                       int nprobe, uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset,
-                                       const float* tau, int64_t ld_tau, int64_t* pool_fill, void* stream) {
+template <class EL>
+static int scan_grouped_impl(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                             const int64_t* list_off, int nlist, int64_t max_list_rows,
+                             const float* queries, int64_t ld_queries, const int64_t* group_off,
+                             const int64_t* qtile_prefix, int64_t qtile_bound, int qtile,
+                             const int64_t* pair_query, const int64_t* pair_probe, const int64_t* pool_base,
+                             int nprobe, uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset,
+                             const float* tau, int64_t ld_tau, int64_t* pool_fill, void* stream, EL el) {
     const GroupedArgs a{lists, ld, dim, row_pos, list_off, max_list_rows, queries, ld_queries, group_off, qtile_prefix, qtile_bound,
                         qtile, pair_query, pool_keys};
     if (int rc = a.check_dim(4)) return rc;
@@ -897,10 +1021,15 @@ extern "C" int amdrec_ivf_scan_grouped(const float* lists, int64_t ld, int dim, 
     if (int rc = a.check_bound()) return rc;
     REQUIRE(a.pointers() && pair_probe && (pool_base || tau), "null pointer");
     REQUIRE(a.leading_dims(), "bad leading dimension");
-    const hipError_t e = with_scan_shape<false>(qtile, max_list_rows <= SHORT_LIST_ROWS, [&](auto shape, const char* tag) {
+    if (int rc = elig_check(el)) return rc;
+    const hipError_t e = with_scan_shape<false, EL::on>(qtile, max_list_rows <= SHORT_LIST_ROWS, [&](auto shape, const char* tag) {
         using S = decltype(shape);
-        return launch_grouped<S, ivf_group_scan_kernel<S>>(
-            tag, max_list_rows, qtile_bound, reinterpret_cast<hipStream_t>(stream), lists, ld, dim, (dim + BK - 1) / BK,
+        constexpr auto kern = [] {
+            if constexpr (EL::on) return ivf_group_scan_kernel<S, AMDREC_LIST_ELIG_ARGS>;
+            else return ivf_group_scan_kernel<S>;
+        }();
+        return launch_grouped<S, kern>(
+            el, tag, max_list_rows, qtile_bound, reinterpret_cast<hipStream_t>(stream), lists, ld, dim, (dim + BK - 1) / BK,
             (const long long*)row_pos, (const long long*)list_off, queries, ld_queries, (const long long*)group_off,
             (const long long*)qtile_prefix, nlist, (const long long*)pair_query, (const long long*)pair_probe,
             (const long long*)pool_base, nprobe, (unsigned long long*)pool_keys, pool_ld, pos_offset, tau, ld_tau,
@@ -908,6 +1037,32 @@ extern "C" int amdrec_ivf_scan_grouped(const float* lists, int64_t ld, int dim, 
     });
     HIP_TRY(e);
     return AMDREC_OK;
+}
+
+extern "C" int amdrec_ivf_scan_grouped(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                                       const int64_t* list_off, int nlist, int64_t max_list_rows,
+                                       const float* queries, int64_t ld_queries, const int64_t* group_off,
+                                       const int64_t* qtile_prefix, int64_t qtile_bound, int qtile,
+                                       const int64_t* pair_query, const int64_t* pair_probe, const int64_t* pool_base,
+                                       int nprobe, uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset,
+                                       const float* tau, int64_t ld_tau, int64_t* pool_fill, void* stream) {
+    return scan_grouped_impl(lists, ld, dim, row_pos, list_off, nlist, max_list_rows, queries, ld_queries, group_off,
+                             qtile_prefix, qtile_bound, qtile, pair_query, pair_probe, pool_base, nprobe, pool_keys, pool_ld,
+                             pos_offset, tau, ld_tau, pool_fill, stream, ListNoElig{});
+}
+
+extern "C" int amdrec_ivf_scan_grouped_eligible(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                                                const int64_t* list_off, int nlist, int64_t max_list_rows,
+                                                const float* queries, int64_t ld_queries, const int64_t* group_off,
+                                                const int64_t* qtile_prefix, int64_t qtile_bound, int qtile,
+                                                const int64_t* pair_query, const int64_t* pair_probe,
+                                                const int64_t* pool_base, int nprobe, uint64_t* pool_keys, int64_t pool_ld,
+                                                int64_t pos_offset, const float* tau, int64_t ld_tau, int64_t* pool_fill,
+                                                void* stream, const uint64_t* list_tags, const uint64_t* require_all,
+                                                const uint64_t* require_any) {
+    return scan_grouped_impl(lists, ld, dim, row_pos, list_off, nlist, max_list_rows, queries, ld_queries, group_off,
+                             qtile_prefix, qtile_bound, qtile, pair_query, pair_probe, pool_base, nprobe, pool_keys, pool_ld,
+                             pos_offset, tau, ld_tau, pool_fill, stream, ListElig{list_tags, require_all, require_any});
 }
 
 extern "C" int amdrec_ivf_filter_bounds(const float* queries, int64_t nq, int64_t ld_queries, int dim,
@@ -925,13 +1080,14 @@ extern "C" int amdrec_ivf_filter_bounds(const float* queries, int64_t nq, int64_
     return AMDREC_OK;
 }
 
-extern "C" int amdrec_ivf_scan_grouped_mixed(const float* lists, int64_t ld, const uint16_t* lists_bf16, int64_t ld_bf16, int dim,
-                                             const int64_t* row_pos, const int64_t* list_off, int nlist, int64_t max_list_rows,
-                                             const float* queries, int64_t ld_queries, const uint16_t* queries_bf16,
-                                             int64_t ld_queries_bf16, const int64_t* group_off, const int64_t* qtile_prefix,
-                                             int64_t qtile_bound, int qtile, const int64_t* pair_query, uint64_t* pool_keys,
-                                             int64_t pool_ld, int64_t pos_offset, const float* tau, int64_t ld_tau,
-                                             const float* tau_lo, int64_t* pool_fill, void* stream) {
+template <class EL>
+static int scan_grouped_mixed_impl(const float* lists, int64_t ld, const uint16_t* lists_bf16, int64_t ld_bf16, int dim,
+                                   const int64_t* row_pos, const int64_t* list_off, int nlist, int64_t max_list_rows,
+                                   const float* queries, int64_t ld_queries, const uint16_t* queries_bf16,
+                                   int64_t ld_queries_bf16, const int64_t* group_off, const int64_t* qtile_prefix,
+                                   int64_t qtile_bound, int qtile, const int64_t* pair_query, uint64_t* pool_keys,
+                                   int64_t pool_ld, int64_t pos_offset, const float* tau, int64_t ld_tau,
+                                   const float* tau_lo, int64_t* pool_fill, void* stream, EL el) {
     const GroupedArgs a{lists, ld, dim, row_pos, list_off, max_list_rows, queries, ld_queries, group_off, qtile_prefix, qtile_bound,
                         qtile, pair_query, pool_keys};
     if (int rc = a.check_dim(8)) return rc;
@@ -944,16 +1100,47 @@ extern "C" int amdrec_ivf_scan_grouped_mixed(const float* lists, int64_t ld, con
                 ld_tau >= 1, "bad leading dimension");
     REQUIRE(((uintptr_t)lists % 16) == 0 && ((uintptr_t)lists_bf16 % 16) == 0 && ((uintptr_t)queries % 16) == 0 &&
                 ((uintptr_t)queries_bf16 % 16) == 0, "lists / queries must be 16-byte aligned");
-    const hipError_t e = with_scan_shape<true>(qtile, max_list_rows <= SHORT_LIST_ROWS, [&](auto shape, const char* tag) {
+    if (int rc = elig_check(el)) return rc;
+    const hipError_t e = with_scan_shape<true, EL::on>(qtile, max_list_rows <= SHORT_LIST_ROWS, [&](auto shape, const char* tag) {
         using S = decltype(shape);
-        return launch_grouped<S, ivf_group_scan_mixed_kernel<S>>(
-            tag, max_list_rows, qtile_bound, reinterpret_cast<hipStream_t>(stream), lists, ld, lists_bf16, ld_bf16, dim,
+        constexpr auto kern = [] {
+            if constexpr (EL::on) return ivf_group_scan_mixed_kernel<S, AMDREC_LIST_ELIG_ARGS>;
+            else return ivf_group_scan_mixed_kernel<S>;
+        }();
+        return launch_grouped<S, kern>(
+            el, tag, max_list_rows, qtile_bound, reinterpret_cast<hipStream_t>(stream), lists, ld, lists_bf16, ld_bf16, dim,
             (dim / 2 + BK - 1) / BK, (const long long*)row_pos, (const long long*)list_off, queries, ld_queries, queries_bf16,
             ld_queries_bf16, (const long long*)group_off, (const long long*)qtile_prefix, nlist, (const long long*)pair_query,
             (unsigned long long*)pool_keys, pool_ld, pos_offset, tau, ld_tau, tau_lo, (unsigned long long*)pool_fill);
     });
     HIP_TRY(e);
     return AMDREC_OK;
+}
+
+extern "C" int amdrec_ivf_scan_grouped_mixed(const float* lists, int64_t ld, const uint16_t* lists_bf16, int64_t ld_bf16, int dim,
+                                             const int64_t* row_pos, const int64_t* list_off, int nlist, int64_t max_list_rows,
+                                             const float* queries, int64_t ld_queries, const uint16_t* queries_bf16,
+                                             int64_t ld_queries_bf16, const int64_t* group_off, const int64_t* qtile_prefix,
+                                             int64_t qtile_bound, int qtile, const int64_t* pair_query, uint64_t* pool_keys,
+                                             int64_t pool_ld, int64_t pos_offset, const float* tau, int64_t ld_tau,
+                                             const float* tau_lo, int64_t* pool_fill, void* stream) {
+    return scan_grouped_mixed_impl(lists, ld, lists_bf16, ld_bf16, dim, row_pos, list_off, nlist, max_list_rows, queries,
+                                   ld_queries, queries_bf16, ld_queries_bf16, group_off, qtile_prefix, qtile_bound, qtile,
+                                   pair_query, pool_keys, pool_ld, pos_offset, tau, ld_tau, tau_lo, pool_fill, stream,
+                                   ListNoElig{});
+}
+
+extern "C" int amdrec_ivf_scan_grouped_mixed_eligible(
+    const float* lists, int64_t ld, const uint16_t* lists_bf16, int64_t ld_bf16, int dim, const int64_t* row_pos,
+    const int64_t* list_off, int nlist, int64_t max_list_rows, const float* queries, int64_t ld_queries,
+    const uint16_t* queries_bf16, int64_t ld_queries_bf16, const int64_t* group_off, const int64_t* qtile_prefix,
+    int64_t qtile_bound, int qtile, const int64_t* pair_query, uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset,
+    const float* tau, int64_t ld_tau, const float* tau_lo, int64_t* pool_fill, void* stream, const uint64_t* list_tags,
+    const uint64_t* require_all, const uint64_t* require_any) {
+    return scan_grouped_mixed_impl(lists, ld, lists_bf16, ld_bf16, dim, row_pos, list_off, nlist, max_list_rows, queries,
+                                   ld_queries, queries_bf16, ld_queries_bf16, group_off, qtile_prefix, qtile_bound, qtile,
+                                   pair_query, pool_keys, pool_ld, pos_offset, tau, ld_tau, tau_lo, pool_fill, stream,
+                                   ListElig{list_tags, require_all, require_any});
 }
 
 extern "C" int amdrec_ivf_coarse_keys(const float* centroids, int nlist, int64_t ld_centroids, int dim, const float* queries,

@@ -186,15 +186,22 @@ __global__ __launch_bounds__(256) void pq_tables_kernel(const float* Q, long lon
 // sub-space order and one 8-byte key store (consecutive rows: consecutive keys of the query's pool row).  A list keeps its
 // rows with a non-finite coordinate after its list_fin[l] finite ones: their keys are -inf (after every finite row).
 // list_fin == nullptr: every row is finite.
-template <int M>
+// EL (ListNoElig or ListElig, invlists.hpp): the eligibility predicate; EP: its pointers as trailing kernel arguments (none
+// for ListNoElig: the kernel it always was).  A thread reads its row's tag once, next to the code word, and stores key 0 -
+// the select's empty-slot value - for an ineligible (query, row) in both loops: stored, not skipped, the pool is not cleared
+// between searches.  The sub-tile's mask words sit in LDS next to its pool offsets.
+template <int M, class EL = ListNoElig, class... EP>
 __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* codes, const long long* spos,
                                                       const long long* list_off, const long long* list_fin, int nlist, const float* tables, int nprobe,
                                                       const long long* goff, const long long* qt_prefix, int qtile,
                                                       const long long* pair_q, const long long* pair_p, const long long* base,
-                                                      unsigned long long* keys, long long pool_ld, long long pos_offset) {
+                                                      unsigned long long* keys, long long pool_ld, long long pos_offset,
+                                                      EP... elig) {
     constexpr int QS = 64 / M;                                           // queries per LDS sub-tile
     __shared__ __attribute__((aligned(16))) float lut[QS * M * PQ_KSUB];
     __shared__ long long dst[QS];
+    __shared__ typename EL::Mask msk[QS];
+    const EL el{elig...};
     const long long y = blockIdx.y;
     if (y >= qt_prefix[nlist]) return;
     const int l = tile_list(y, qt_prefix, nlist);
@@ -215,6 +222,7 @@ __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* codes
         if (t < nsub) {
             const long long q = pair_q[g0 + sp + t];
             dst[t] = q * pool_ld + base[q * nprobe + pair_p[g0 + sp + t]];
+            if constexpr (EL::on) msk[t] = el.mask(q);
         }
         __syncthreads();
         const long long stride = (long long)gridDim.x * 256, row0 = (long long)blockIdx.x * 256 + t;
@@ -234,12 +242,16 @@ __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* codes
                 }
             }
             const uint32_t pos = (uint32_t)(spos[r0 + row] + pos_offset);
+            const typename EL::Tag tg = el.tag(r0 + row);
             for (int j = 0; j < nsub; ++j) {
                 const float* lt = lut + j * (M * PQ_KSUB);
                 float dist = lt[cw[0] & 0xff];
 #pragma unroll
                 for (int s = 1; s < M; ++s) dist += lt[s * PQ_KSUB + ((cw[s >> 2] >> (8 * (s & 3))) & 0xff)];
-                keys[dst[j] + row] = make_key(rank_last(-dist), pos);               // NaN distances rank last
+                if constexpr (EL::on)
+                    keys[dst[j] + row] = EL::ok(tg, msk[j]) ? make_key(rank_last(-dist), pos) : 0ull;
+                else
+                    keys[dst[j] + row] = make_key(rank_last(-dist), pos);           // NaN distances rank last
             }
         }
         // its rows with a non-finite coordinate (rare; none when list_fin is null): -inf keys, no lookups.  A loop of
@@ -247,7 +259,12 @@ __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* codes
         const long long skip = row0 < nfin ? (nfin - row0 + stride - 1) / stride : 0;
         for (long long row = row0 + skip * stride; row < len; row += stride) {
             const uint32_t pos = (uint32_t)(spos[r0 + row] + pos_offset);
-            for (int j = 0; j < nsub; ++j) keys[dst[j] + row] = make_key(-INFINITY, pos);
+            if constexpr (EL::on) {
+                const typename EL::Tag tg = el.tag(r0 + row);
+                for (int j = 0; j < nsub; ++j) keys[dst[j] + row] = EL::ok(tg, msk[j]) ? make_key(-INFINITY, pos) : 0ull;
+            } else {
+                for (int j = 0; j < nsub; ++j) keys[dst[j] + row] = make_key(-INFINITY, pos);
+            }
         }
     }
 }
@@ -371,11 +388,38 @@ extern "C" int amdrec_ivfpq_tables(const float* queries, int64_t nq, int64_t ld_
     return AMDREC_OK;
 }
 
+// The eligibility pointers of amdrec_ivfpq_scan_finite_eligible: all three required and 8-byte aligned, checked with the other
+// arguments before the first HIP call.  The plain scans and the eligible one are ONE host template over the predicate.
+static int elig_check(ListNoElig) { return AMDREC_OK; }
+static int elig_check(ListElig el) {
+    REQUIRE(el.tags != nullptr, "list_tags is null");
+    REQUIRE(el.all != nullptr, "require_all is null");
+    REQUIRE(el.any != nullptr, "require_any is null");
+    REQUIRE(((uintptr_t)el.tags % 8) == 0, "list_tags must be 8-byte aligned");
+    REQUIRE(((uintptr_t)el.all % 8) == 0, "require_all must be 8-byte aligned");
+    REQUIRE(((uintptr_t)el.any % 8) == 0, "require_any must be 8-byte aligned");
+    return AMDREC_OK;
+}
+template <class Kern, class... Args>
+static void launch_with(ListNoElig, Kern kern, dim3 grid, dim3 block, hipStream_t st, Args... args) {
+    hipLaunchKernelGGL(kern, grid, block, 0, st, args...);
+}
+template <class Kern, class... Args>
+static void launch_with(ListElig el, Kern kern, dim3 grid, dim3 block, hipStream_t st, Args... args) {
+    hipLaunchKernelGGL(kern, grid, block, 0, st, args..., el.tags, el.all, el.any);
+}
+template <int M, class EL>
+static constexpr auto pq_scan_for() {
+    if constexpr (EL::on) return pq_scan_kernel<M, ListElig, const uint64_t*, const uint64_t*, const uint64_t*>;
+    else return pq_scan_kernel<M>;
+}
+
+template <class EL>
 static int scan_impl(const uint8_t* codes, int m, const int64_t* row_pos, const int64_t* list_off,
                      const int64_t* list_finite, int nlist, int64_t max_list_rows, const float* tables, int nprobe,
                      const int64_t* group_off, const int64_t* qtile_prefix, int64_t qtile_bound, int qtile,
                      const int64_t* pair_query, const int64_t* pair_probe, const int64_t* pool_base, int64_t npairs,
-                     uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset, void* stream) {
+                     uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset, void* stream, EL el) {
     REQUIRE(pq_m_ok(m), "m=%d must be 4, 8, 16 or 32", m);
     REQUIRE(nlist >= 1 && nprobe >= 1, "bad nlist/nprobe");
     REQUIRE(qtile == 32 || qtile == 64, "qtile must be 32 or 64 (the value given to amdrec_ivf_group)");
@@ -384,6 +428,7 @@ static int scan_impl(const uint8_t* codes, int m, const int64_t* row_pos, const 
     REQUIRE(codes && row_pos && list_off && tables && group_off && qtile_prefix && pair_query && pair_probe && pool_base &&
                 pool_keys, "null pointer");
     REQUIRE(((uintptr_t)codes % 16) == 0 && ((uintptr_t)tables % 16) == 0, "codes / tables must be 16-byte aligned");
+    if (int rc = elig_check(el)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     // row shares per (list, tile): ~2048 workgroups in all over the tiles that can be non-empty, but at least ~1024 rows each
     // of the longest list: every share re-stages its tile's tables (64 KiB per sub-tile).  One 256-row share per 256-row block
@@ -393,14 +438,14 @@ static int scan_impl(const uint8_t* codes, int m, const int64_t* row_pos, const 
     const long long gmax = (max_list_rows + 1023) / 1024;
     gx = gx > gmax ? gmax : gx;
     gx = gx < 1 ? 1 : gx;
-    ProfScope prof("ivfpq_scan", 0.0, 0.0, st);
+    ProfScope prof(EL::on ? "ivfpq_scan_elig" : "ivfpq_scan", 0.0, 0.0, st);
 #define AMDREC_PQ_SCAN(MM)                                                                                                  \
-    hipLaunchKernelGGL(pq_scan_kernel<MM>, dim3((unsigned)gx, (unsigned)qtile_bound), dim3(256), 0, st, codes,              \
-                       (const long long*)row_pos, (const long long*)list_off, (const long long*)list_finite, nlist,        \
-                       tables, nprobe, (const long long*)group_off, (const long long*)qtile_prefix, qtile,                 \
-                       (const long long*)pair_query,                                                                       \
-                       (const long long*)pair_probe, (const long long*)pool_base, (unsigned long long*)pool_keys, pool_ld, \
-                       pos_offset)
+    launch_with(el, pq_scan_for<MM, EL>(), dim3((unsigned)gx, (unsigned)qtile_bound), dim3(256), st, codes,                 \
+                (const long long*)row_pos, (const long long*)list_off, (const long long*)list_finite, nlist,               \
+                tables, nprobe, (const long long*)group_off, (const long long*)qtile_prefix, qtile,                        \
+                (const long long*)pair_query,                                                                              \
+                (const long long*)pair_probe, (const long long*)pool_base, (unsigned long long*)pool_keys, (long long)pool_ld, \
+                (long long)pos_offset)
     switch (m) {
         case 4: AMDREC_PQ_SCAN(4); break;
         case 8: AMDREC_PQ_SCAN(8); break;
@@ -418,7 +463,8 @@ extern "C" int amdrec_ivfpq_scan(const uint8_t* codes, int m, const int64_t* row
                                  const int64_t* pair_probe, const int64_t* pool_base, int64_t npairs, uint64_t* pool_keys,
                                  int64_t pool_ld, int64_t pos_offset, void* stream) {
     return scan_impl(codes, m, row_pos, list_off, nullptr, nlist, max_list_rows, tables, nprobe, group_off, qtile_prefix,
-                     qtile_bound, qtile, pair_query, pair_probe, pool_base, npairs, pool_keys, pool_ld, pos_offset, stream);
+                     qtile_bound, qtile, pair_query, pair_probe, pool_base, npairs, pool_keys, pool_ld, pos_offset, stream,
+                     ListNoElig{});
 }
 
 extern "C" int amdrec_ivfpq_scan_finite(const uint8_t* codes, int m, const int64_t* row_pos, const int64_t* list_off,
@@ -430,7 +476,22 @@ extern "C" int amdrec_ivfpq_scan_finite(const uint8_t* codes, int m, const int64
     REQUIRE(list_finite != nullptr, "null pointer: list_finite");
     return scan_impl(codes, m, row_pos, list_off, list_finite, nlist, max_list_rows, tables, nprobe, group_off,
                      qtile_prefix, qtile_bound, qtile, pair_query, pair_probe, pool_base, npairs, pool_keys, pool_ld,
-                     pos_offset, stream);
+                     pos_offset, stream, ListNoElig{});
+}
+
+extern "C" int amdrec_ivfpq_scan_finite_eligible(const uint8_t* codes, int m, const int64_t* row_pos, const int64_t* list_off,
+                                                 const int64_t* list_finite, int nlist, int64_t max_list_rows,
+                                                 const float* tables, int nprobe, const int64_t* group_off,
+                                                 const int64_t* qtile_prefix, int64_t qtile_bound, int qtile,
+                                                 const int64_t* pair_query, const int64_t* pair_probe,
+                                                 const int64_t* pool_base, int64_t npairs, uint64_t* pool_keys,
+                                                 int64_t pool_ld, int64_t pos_offset, void* stream,
+                                                 const uint64_t* list_tags, const uint64_t* require_all,
+                                                 const uint64_t* require_any) {
+    REQUIRE(list_finite != nullptr, "null pointer: list_finite");
+    return scan_impl(codes, m, row_pos, list_off, list_finite, nlist, max_list_rows, tables, nprobe, group_off,
+                     qtile_prefix, qtile_bound, qtile, pair_query, pair_probe, pool_base, npairs, pool_keys, pool_ld,
+                     pos_offset, stream, ListElig{list_tags, require_all, require_any});
 }
 
 extern "C" int amdrec_ivfpq_distances(const float* scores, int64_t nq, int k, float* distances, void* stream) {

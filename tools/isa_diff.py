@@ -4,7 +4,10 @@ compile).  Prints the resource table (parent | branch per kernel) or the per-ker
 comments, .loc / .file / .cfi lines, labels' debug suffixes, local labels' function ordinals and metadata stripped.
 usage: python tools/isa_diff.py resources parent.remarks branch.remarks [tu]
        python tools/isa_diff.py isa parent.s branch.s [tu]
-tu: the translation unit's name for the headings (default: the branch file's name up to its first dot + ".hip")"""
+tu: the translation unit's name for the headings (default: the branch file's name up to its first dot + ".hip")
+--same NAME (repeatable, after the other arguments): a template argument that the branch added with a default, e.g.
+ListNoElig - kernels are paired by demangled name with ", NAME" / "<NAME>" removed, so f<S, NAME> (or f<NAME>) of the branch
+is judged against the parent's f<S> (or f)."""
 import difflib
 import os
 import re
@@ -12,9 +15,24 @@ import subprocess
 import sys
 
 
+SAME = []           # --same: template arguments dropped from the demangled names
+
+
 def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-    return {n: re.sub(r"\(.*", "", d).replace("amdrec::", "") for n, d in zip(names, out)}
+    res = {}
+    for n, d in zip(names, out):
+        d = re.sub(r"\(.*", "", d).replace("amdrec::", "")
+        for t in SAME:
+            d = d.replace(", " + t + ">", ">").replace(", " + t + " >", " >").replace("<" + t + ">", "")
+        res[n] = re.sub(r"^void (\w+)$", r"\1", d.replace("> >", ">>"))
+    return res
+
+
+def by_name(table):
+    """mangled name -> value  =>  demangled (and --same-normalised) name -> value"""
+    names = demangle(sorted(table))
+    return {names[n]: v for n, v in table.items()}
 
 
 def resources(path):
@@ -47,18 +65,23 @@ def kernels(path):
         if s.startswith(".Lfunc_end"):
             cur = None
             continue
-        if not s or s.startswith((".loc", ".file", ".cfi", ".p2align", ".section", ".amdhsa", ".end_amdhsa", ".Ltmp", ".type", ".size")):
+        if not s or s.startswith((".loc", ".file", ".cfi", ".p2align", ".section", ".amdhsa", ".end_amdhsa", ".Ltmp", ".type", ".size", ".text")):
             continue
         cur.append(s)
     return {k: v for k, v in out.items() if any(i.startswith("s_endpgm") for i in v)}
 
 
 def main():
-    mode, a, b = sys.argv[1:4]
-    tu = sys.argv[4] if len(sys.argv) > 4 else os.path.basename(b).split(".")[0] + ".hip"
+    argv = sys.argv[1:]
+    while "--same" in argv:
+        i = argv.index("--same")
+        SAME.append(argv[i + 1])
+        del argv[i:i + 2]
+    mode, a, b = argv[:3]
+    tu = argv[3] if len(argv) > 3 else os.path.basename(b).split(".")[0] + ".hip"
     if mode == "resources":
-        ra, rb = resources(a), resources(b)
-        names = demangle(sorted(set(ra) | set(rb)))
+        ra, rb = by_name(resources(a)), by_name(resources(b))
+        names = {n: n for n in set(ra) | set(rb)}
         cols = [("VGPR", "VGPRs"), ("AGPR", "AGPRs"), ("SGPR", "TotalSGPRs"), ("scratch", "ScratchSize [bytes/lane]"),
                 ("spilled VGPRs", "VGPRs Spill"), ("LDS", "LDS Size [bytes/block]"), ("occ", "Occupancy [waves/SIMD]")]
         print(f"Kernel resource usage of {tu} (product flags + -Rpass-analysis=kernel-resource-usage), parent | branch")
@@ -75,8 +98,8 @@ def main():
         print(f"\n{len(set(ra) & set(rb))} kernels in both, {bad} outside the conditions; {len(set(ra) - set(rb))} only in the "
               f"parent (old), {len(set(rb) - set(ra))} only in the branch (new)")
         return 1 if bad else 0
-    ka, kb = kernels(a), kernels(b)
-    names = demangle(sorted(set(ka) | set(kb)))
+    ka, kb = by_name(kernels(a)), by_name(kernels(b))
+    names = {n: n for n in set(ka) | set(kb)}
     differ = 0
     print(f"Instruction streams of {tu}'s kernels, parent against branch (comments, .loc / .file lines and metadata stripped)\n")
     for n in sorted(names, key=names.get):
