@@ -34,7 +34,8 @@ extern "C" {
                                * amdrec_ranker_forward_ctr_first ..., amdrec_x3_weights.stream_ctr ... at the struct's end; and
                                * the eligibility masks: amdrec_flat_search_eligible, amdrec_flat_search_mixed_eligible, added exports; then
                                * the same masks in the inverted-list scans: amdrec_ivf_scan_eligible, amdrec_ivf_scan_grouped_eligible,
-                               * amdrec_ivf_scan_grouped_mixed_eligible, amdrec_ivfpq_scan_finite_eligible, added exports) */
+                               * amdrec_ivf_scan_grouped_mixed_eligible, amdrec_ivfpq_scan_finite_eligible, added exports; then
+                               * the per-group caps: amdrec_select_topk_capped, amdrec_group_cap_compact, added exports) */
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -667,6 +668,39 @@ int amdrec_select_topk(const float* logits /*[n_tasks][ld]*/, int64_t ld_logits,
                        const int64_t* cand_pos /*[n_users][k_c] or NULL*/, int64_t n_users,
                        int k_c, int top_k, int64_t* out_ids /*[n_users][top_k]*/,
                        float* out_scores /*[n_tasks][n_users][top_k]*/, int32_t* out_slots, void* stream);
+
+/* Per-group caps ("at most c ads of one advertiser"; two more exports added to ABI v14, every other entry as it was).  The
+ * rule is greedy in rank order: an entry is accepted while fewer than max_per_group accepted entries share its group - which
+ * equals "keep an entry iff fewer than max_per_group BETTER-RANKED entries have its group, then cut", so every entry is
+ * decided from its own group's prefix alone.  A group key is an int64 per corpus row, group_of[n_group_rows], read at an
+ * entry's corpus position; a negative key means ungrouped (never capped), and a position outside [0, n_group_rows) is never
+ * read and counts as ungrouped.  1 <= max_per_group <= AMDREC_MAX_K.
+ *
+ * amdrec_select_topk_capped: amdrec_select_topk under the cap - its arguments in the same order, then the groups.  The
+ * candidates are amdrec_select_topk's (a slot with cand_pos < 0 is none; cand_pos is REQUIRED here) and are visited in its
+ * order (logit desc, slot asc, NaN logits after every other logit); a candidate's group is group_of[cand_pos].  A candidate
+ * of group g >= 0 is accepted iff fewer than max_per_group earlier candidates in that order have group g (NaN-logit
+ * candidates count and are capped like any other); ungrouped candidates are always accepted.  The first top_k accepted
+ * candidates are the result, in order; the tail past the last one reads out_ids = -1, out_scores = 0.0, out_slots = -1 as
+ * amdrec_select_topk's short-list tail.  out_scores, out_slots and the probability expression are amdrec_select_topk's.
+ * One launch, no workspace; every argument is validated before the first HIP call. */
+int amdrec_select_topk_capped(const float* logits /*[n_tasks][ld]*/, int64_t ld_logits, int n_tasks,
+                              int rank_task, const int64_t* cand_ids /*[n_users][k_c]*/,
+                              const int64_t* cand_pos /*[n_users][k_c]*/, int64_t n_users,
+                              int k_c, int top_k, int64_t* out_ids /*[n_users][top_k]*/,
+                              float* out_scores /*[n_tasks][n_users][top_k]*/, int32_t* out_slots,
+                              const int64_t* group_of /*[n_group_rows], indexed by cand_pos*/, int64_t n_group_rows,
+                              int max_per_group, void* stream);
+
+/* amdrec_group_cap_compact: the same rule on a search result.  pos / scores [nq][kc] are a search's positions and scores in
+ * the index's own order; an entry is kept iff fewer than max_per_group earlier FILLED entries of its row share its
+ * non-negative group group_of[pos].  An unfilled entry (pos < 0) is never counted and never dropped: it keeps its place
+ * behind the filled ones.  out_pos / out_scores [nq][k] receive the first k kept entries in their order; the slots past the
+ * last one get -1 / fill_score (the index type's unfilled convention: -inf, or +inf for IVFPQ).  One launch, one workgroup
+ * per query, no workspace.  1 <= k <= kc <= AMDREC_MAX_K; outputs must not alias inputs. */
+int amdrec_group_cap_compact(const int64_t* pos /*[nq][kc]*/, const float* scores /*[nq][kc]*/, int64_t nq, int kc,
+                             const int64_t* group_of /*[n_group_rows]*/, int64_t n_group_rows, int max_per_group, int k,
+                             float fill_score, int64_t* out_pos /*[nq][k]*/, float* out_scores /*[nq][k]*/, void* stream);
 
 #ifdef __cplusplus
 }

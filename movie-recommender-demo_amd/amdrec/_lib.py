@@ -95,6 +95,9 @@ _SIGNATURES = {
     "amdrec_ranker_x3_prefix": [_vp, _fp, _i64, _i64, _i32, _fp, _i64, _fp, _i64, _vp, _sz, _vp],
     "amdrec_prep_numerical": [_fp, _fp, _fp, _fp, _i64, _i32, _vp],
     "amdrec_select_topk": [_fp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _fp, _vp, _vp],
+    # amdrec_select_topk's arguments up to out_slots + (group_of, n_group_rows, max_per_group, stream)
+    "amdrec_select_topk_capped": [_fp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _fp, _vp, _vp, _i64, _i32, _vp],
+    "amdrec_group_cap_compact": [_vp, _fp, _i64, _i32, _vp, _i64, _i32, _i32, C.c_float, _vp, _fp, _vp],
 }
 _RESTYPE = {"amdrec_last_error": C.c_char_p}
 

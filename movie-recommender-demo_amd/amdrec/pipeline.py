@@ -230,23 +230,26 @@ class AdRecommenderInference:
         return mode, None
 
     # -- the device hot path ------------------------------------------------------------------
-    def _stage1(self, uc, un, stage1_k, check_indices, exclude=None, masks=(None, None)):
+    def _stage1(self, uc, un, stage1_k, check_indices, exclude=None, masks=(None, None), max_per_group=None):
         # the tower's launch also applies the search's query normalisation (faiss_retrieval.py:147): one launch fewer
         emb = self.two_tower_model.user_tower.encode(uc, un, check_indices=check_indices, renormalize=True)   # :223-227
         # exclude (device int64 [B, E] ad ids, or None): removed here, so the ranker only ever sees eligible ads
         # masks (device int64 [B] require_all / require_any, or None): tested inside the search, likewise
+        # max_per_group (stage1_max_per_group, or None): the per-group cap on the candidate list (FAISSIndex.search_device)
         return self.faiss_index.search_device(emb, stage1_k, normalize=False,                  # :230-232
                                               return_positions=True, exclude=exclude, require_all=masks[0],
-                                              require_any=masks[1])
+                                              require_any=masks[1], max_per_group=max_per_group)
 
     def _stage2(self, uc, un, cand_pos, top_k, check_indices, ids_are_positions=False, mark=None, out=None,
-                excluded=False, heads=None):
+                excluded=False, heads=None, max_per_group=None):
         """Ranker + selection over stage 1's positions ``cand_pos`` [B, stage1_k].  A negative position is a slot the search
         could not fill: no candidate.  The ranker still computes a (finite, unspecified) logit for it - every gather clamps
         the row - and the selection, which is handed the positions, ranks it after every real candidate: it is reported only
         where a user has fewer than ``top_k`` real candidates, as ad id -1 with probability 0.0 for every task.  Validity is
         decided here, by position: ``candidate_ids`` keeps the search's convention for such a slot (``id_map[-1]``; the
-        position itself with ``ids_are_positions``), from which it can no longer be told."""
+        position itself with ``ids_are_positions``), from which it can no longer be told.
+        ``max_per_group`` (validated by the caller, None: no cap): the selection is amdrec_select_topk_capped over the index's
+        group keys - at most that many winners of one group per user, greedy in the selection's order."""
         lib = _lib.load()
         B, stage1_k = cand_pos.shape
         rk = self.transformer_ranker
@@ -285,18 +288,22 @@ class AdRecommenderInference:
             cand_ids = torch.empty_like(cand_pos)
             _lib.check(lib.amdrec_remap_ids(_lib.ptr(cand_pos), _lib.ptr(idx._ids), idx._n, _lib.ptr(cand_ids),
                                             cand_pos.numel(), _lib.stream_ptr(uc.device)))
+        if max_per_group is None:
+            select, groups = lib.amdrec_select_topk, ()
+        else:                                    # the same arguments, then the groups: the cap runs inside the selection
+            select, groups = lib.amdrec_select_topk_capped, (_lib.ptr(idx._groups), idx._n, max_per_group)
         if B and ctr_first:
             # the selection as ever, on the one logit row: ad ids, plane 0 of scores and the winning slots; then the winners'
             # other tasks into planes 1 ..
             slots = torch.empty((B, top_k), dtype=torch.int32, device=uc.device)
-            _lib.check(lib.amdrec_select_topk(_lib.ptr(logits), logits.stride(0), 1, 0, _lib.ptr(cand_ids), _lib.ptr(cand_pos),
-                                              B, stage1_k, top_k, _lib.ptr(ad_ids), _lib.ptr(scores), _lib.ptr(slots),
-                                              _lib.stream_ptr(uc.device)))
+            _lib.check(select(_lib.ptr(logits), logits.stride(0), 1, 0, _lib.ptr(cand_ids), _lib.ptr(cand_pos),
+                              B, stage1_k, top_k, _lib.ptr(ad_ids), _lib.ptr(scores), _lib.ptr(slots), *groups,
+                              _lib.stream_ptr(uc.device)))
             rk.winner_scores(trunk, slots, stage1_k, scores)
         elif B:
-            _lib.check(lib.amdrec_select_topk(_lib.ptr(logits), logits.stride(0), len(tasks), tasks.index("ctr"),
-                                              _lib.ptr(cand_ids), _lib.ptr(cand_pos), B, stage1_k, top_k,
-                                              _lib.ptr(ad_ids), _lib.ptr(scores), None, _lib.stream_ptr(uc.device)))
+            _lib.check(select(_lib.ptr(logits), logits.stride(0), len(tasks), tasks.index("ctr"),
+                              _lib.ptr(cand_ids), _lib.ptr(cand_pos), B, stage1_k, top_k,
+                              _lib.ptr(ad_ids), _lib.ptr(scores), None, *groups, _lib.stream_ptr(uc.device)))
         return {"ad_ids": ad_ids, "scores": scores, "tasks": tasks, "candidate_ids": cand_ids, "logits": logits,
                 "logit_tasks": ("ctr",) if ctr_first else tuple(tasks)}
 
@@ -304,7 +311,8 @@ class AdRecommenderInference:
     def recommend_device(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor, top_k: int = 10,
                          stage1_k: int = 500, check_indices: bool = False,
                          exclude_ad_ids: Optional[torch.Tensor] = None, heads: Optional[str] = None,
-                         require_all: Optional[torch.Tensor] = None, require_any: Optional[torch.Tensor] = None):
+                         require_all: Optional[torch.Tensor] = None, require_any: Optional[torch.Tensor] = None,
+                         max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None):
         """[B,6] / [B,13] device tensors -> dict of device tensors, no host synchronisation:
         ad_ids [B,top_k] int64, scores [3,B,top_k] float32 (sigmoid of the logits), candidate_ids
         [B,stage1_k], candidate_scores [B,stage1_k], logits [3, B*stage1_k].  candidate_scores are the index's own
@@ -325,30 +333,43 @@ class AdRecommenderInference:
         for every task - the same tail that top_k > stage1_k gives.  The real ads of a row are distinct and were all
         retrieved by stage 1.  candidate_ids keeps the search's convention for an unfilled slot (id_map[-1]) and its entry
         of logits is unspecified but finite (for finite weights and user features): mask them with candidate_scores.
+        ``max_per_group`` (None: no cap, the launches of ever): at most that many of a user's ``top_k`` ads share one group
+        key of the index (FAISSIndex.add(groups=) / set_groups; amdrec.group_cap has the rule: greedy in the selection's
+        order, ungrouped ads never capped).  The cap runs inside the selection, on the device; a user whose candidates hold
+        fewer than ``top_k`` ads that it lets through gets the -1 / 0.0 tail.  ``stage1_max_per_group``: the same rule on the
+        candidate list (FAISSIndex.search_device(max_per_group=): the cap applied to the index's own top
+        2 * stage1_k), so that one advertiser's near-duplicate creatives cannot fill the candidates; slots the cap
+        leaves empty are unfilled slots as above.  Either on an index without group keys, or <= 0: ValueError.
         ``check_indices``: an out-of-range user index or ad-table row raises IndexError; an unfilled slot does not."""
         if heads is not None:
             self._check_heads(heads)
+        cap, cap1 = self._check_caps(max_per_group, stage1_max_per_group)          # (before the library is touched)
         uc = _lib.require_gpu(user_categorical, "user_categorical")
         un = _lib.require_gpu(user_numerical, "user_numerical")
         excluded = exclude_ad_ids is not None and exclude_ad_ids.shape[-1] > 0
         masked = require_all is not None or require_any is not None
         cand_pos, cand_scores = self._stage1(uc, un, stage1_k, check_indices, exclude_ad_ids if excluded else None,
-                                             (require_all, require_any))
+                                             (require_all, require_any), cap1)
         # (excluded: "a slot can be unfilled" - true after a filtered stage 1 as well)
-        out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded or masked, heads=heads)
+        out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded or masked or cap1 is not None,
+                           heads=heads, max_per_group=cap)
         out["candidate_scores"] = cand_scores
         return out
 
     def capture(self, batch_size: int, top_k: int = 10, stage1_k: int = 500, warmup: int = 2,
-                max_exclude: int = 0, eligibility: bool = False) -> "GraphedRecommender":
+                max_exclude: int = 0, eligibility: bool = False, max_per_group: Optional[int] = None,
+                stage1_max_per_group: Optional[int] = None) -> "GraphedRecommender":
         """Capture one recommend_device call for a fixed batch shape into a HIP graph (the ~40 kernel
         launches of a request are host-launch-bound at small batch: 1.76 ms eager at B = 1) and return a
         replayer.  Weights, index and ad table must not change afterwards.  ``max_exclude`` > 0: the graph also holds a
         static [batch_size, max_exclude] exclusion buffer (stage 1 always searches stage1_k + max_exclude) that the
         replayer's ``exclude`` argument fills; 0 captures the graph without the exclusion step.  ``eligibility``: the graph
         holds static [batch_size] mask buffers and runs the filtered search (the replayer's ``require_all`` /
-        ``require_any`` fill them; the tags are those of capture time); False captures the graph as ever."""
-        return GraphedRecommender(self, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility)
+        ``require_any`` fill them; the tags are those of capture time); False captures the graph as ever.
+        ``max_per_group`` / ``stage1_max_per_group`` (recommend_device): scalars fixed at capture; the group keys are those
+        of capture time."""
+        return GraphedRecommender(self, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group,
+                                  stage1_max_per_group)
 
     # -- live corpus: ads leave and enter without a rebuild of the index or of the ranker's per-ad caches ------------------
     def remove_ads(self, ad_ids) -> int:
@@ -367,9 +388,9 @@ class AdRecommenderInference:
         self._swap_ad_table(old, new)
         return removed
 
-    def add_ads(self, embeddings, ad_features, ad_ids=None, tags=None) -> None:
+    def add_ads(self, embeddings, ad_features, ad_ids=None, tags=None, groups=None) -> None:
         """Insert ads: ``embeddings`` [m, d] go to the index (FAISSIndex.add: ``ad_ids`` as there; required once ads have been
-        removed; ``tags``: the ads' 64-bit eligibility words, as there), ``ad_features`` [m, n_ad_feat] integer rows are
+        removed; ``tags``: the ads' 64-bit eligibility words, ``groups``: their int64 group keys, as there), ``ad_features`` [m, n_ad_feat] integer rows are
         appended to the ad-feature table, and the ranker's per-ad
         caches grow by projecting the m new rows only (TransformerRanker.extend_ad_cache).  The feature rows are checked
         against the ranker's ad embedding tables first (IndexError, as an embedding lookup would raise), and a rejected call
@@ -389,7 +410,7 @@ class AdRecommenderInference:
         if feats.numel() and bool(((feats < 0) | (feats >= cards)).any().item()):
             raise IndexError("index out of range in self: an ad_features row is outside the ranker's ad embedding tables")
         n_old = idx.index.ntotal
-        idx.add(embeddings, ad_ids, tags=tags)   # (refuses before it commits anything)
+        idx.add(embeddings, ad_ids, tags=tags, groups=groups)   # (refuses before it commits anything)
         new = torch.cat([old[:n_old], feats])
         if old.shape[0] == n_old:
             self.transformer_ranker.extend_ad_cache(old, new)
@@ -406,18 +427,22 @@ class AdRecommenderInference:
 
     # -- reference API ------------------------------------------------------------------------
     def recommend_ads(self, user_data: dict, top_k: int = 10, stage1_k: int = 500,
-                      return_scores: bool = True, exclude_ad_ids=None, require_all: int = 0, require_any: int = 0) -> dict:
+                      return_scores: bool = True, exclude_ad_ids=None, require_all: int = 0, require_any: int = 0,
+                      max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None) -> dict:
         """inference.py:199-288.  ``exclude_ad_ids``: the ad ids this user must not be shown (a sequence of integers).
         ``require_all`` / ``require_any``: this request's eligibility masks (64-bit integers; 0 and 0: no constraint, the
-        plain search).  Fewer than ``top_k`` real candidates: as batch_recommend."""
+        plain search).  ``max_per_group`` / ``stage1_max_per_group``: the per-group caps of recommend_device.  Fewer than
+        ``top_k`` real candidates: as batch_recommend."""
         masked = bool(require_all) or bool(require_any)
         return self.batch_recommend([user_data], top_k=top_k, stage1_k=stage1_k, return_scores=return_scores,
                                     exclude_ad_ids=None if exclude_ad_ids is None else [exclude_ad_ids],
                                     require_all=[require_all] if masked else None,
-                                    require_any=[require_any] if masked else None)[0]
+                                    require_any=[require_any] if masked else None, max_per_group=max_per_group,
+                                    stage1_max_per_group=stage1_max_per_group)[0]
 
     def batch_recommend(self, user_data_list: list, top_k: int = 10, stage1_k: int = 500,
-                        return_scores: bool = True, exclude_ad_ids=None, require_all=None, require_any=None) -> list:
+                        return_scores: bool = True, exclude_ad_ids=None, require_all=None, require_any=None,
+                        max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None) -> list:
         """inference.py:290-331 - but one device pass for the whole list instead of a serial loop.
         ``timing`` reports the batch's stage times divided by the number of users.  ``exclude_ad_ids``: one sequence of
         ad ids per user (recommend_device has the meaning); the padded block travels in the input staging block.
@@ -425,7 +450,10 @@ class AdRecommenderInference:
         int64 array; where one is given the other defaults to 0), in the same staging block: no synchronisation more.
         ``ad_ids`` and every list of ``scores`` always have length ``top_k``: where stage 1 retrieved fewer than ``top_k``
         ads for a user (a corpus smaller than top_k, exclusions, narrow probes, a NaN feature) the tail reads ad id -1
-        with score 0.0 for every task, and no ad appears that stage 1 did not retrieve for that user."""
+        with score 0.0 for every task, and no ad appears that stage 1 did not retrieve for that user.
+        ``max_per_group`` / ``stage1_max_per_group``: the per-group caps of recommend_device, for every user of the list (a
+        user with fewer than ``top_k`` ads that the cap lets through gets the same tail)."""
+        self._check_caps(max_per_group, stage1_max_per_group)
         if not user_data_list:
             return []
         n = len(user_data_list)
@@ -435,7 +463,13 @@ class AdRecommenderInference:
         excl = rest.pop(0) if excl is not None else None
         masks = rest.pop(0) if masks is not None else None
         return self.recommend_tensors(uc, un, top_k, stage1_k, return_scores, _encoded=True, _exclude_dev=excl,
-                                      _masks_dev=masks)
+                                      _masks_dev=masks, max_per_group=max_per_group,
+                                      stage1_max_per_group=stage1_max_per_group)
+
+    def _check_caps(self, max_per_group, stage1_max_per_group):
+        """The two cap arguments -> (cap or None, stage-1 cap or None); refusals before the library is touched."""
+        idx = self.faiss_index
+        return idx._check_group_cap(max_per_group), idx._check_group_cap(stage1_max_per_group, "stage1_max_per_group")
 
     def _host_masks(self, require_all, require_any, n: int) -> Optional[np.ndarray]:
         """The two mask arguments of the reference-API calls -> int64 [2, n] on the host (None: neither given)."""
@@ -493,7 +527,7 @@ class AdRecommenderInference:
     @torch.no_grad()
     def recommend_tensors(self, user_categorical, user_numerical, top_k=10, stage1_k=500, return_scores=True,
                           _encoded=False, exclude_ad_ids=None, _exclude_dev=None, require_all=None, require_any=None,
-                          _masks_dev=None):
+                          _masks_dev=None, max_per_group=None, stage1_max_per_group=None):
         """Tensor-level entry (cf. TwoStageRetriever.retrieve_and_rank, faiss_retrieval.py:283-369); result dicts follow
         inference.py:272-288.  ONE host synchronisation per call (round 3 had four: the tower's index flag, the stage-1
         timing sync, the ranker's index flag, the result copy - each exposing the launch work queued behind it): indices
@@ -502,7 +536,9 @@ class AdRecommenderInference:
         embedding lookup, before any result is returned.  ``exclude_ad_ids``: one sequence of ad ids per user, shipped as
         one padded block through pinned memory (no synchronisation of its own).  ``require_all`` / ``require_any``: the
         users' eligibility masks as in batch_recommend, shipped the same way.  The lists keep length ``top_k``, with
-        -1 / 0.0 in the tail of a user with fewer real candidates (batch_recommend)."""
+        -1 / 0.0 in the tail of a user with fewer real candidates (batch_recommend).  ``max_per_group`` /
+        ``stage1_max_per_group``: the per-group caps of recommend_device."""
+        cap, cap1 = self._check_caps(max_per_group, stage1_max_per_group)
         t0 = time.time()
         dev = self.device
         uc = user_categorical.to(dev)
@@ -547,9 +583,10 @@ class AdRecommenderInference:
             raise IndexError("index out of range in self")                    # (the ad-feature table, transformer_ranker.py:322)
         st = torch.cuda.current_stream(dev)
         ev[0].record(st)
-        cand_pos, _ = self._stage1(uc, un, stage1_k, False, excl, (None, None) if masks is None else (masks[0], masks[1]))
+        cand_pos, _ = self._stage1(uc, un, stage1_k, False, excl, (None, None) if masks is None else (masks[0], masks[1]), cap1)
         ev[1].record(st)
-        out = self._stage2(uc, un, cand_pos, top_k, False, out=(ad_ids, scores), excluded=excl is not None or masks is not None)
+        out = self._stage2(uc, un, cand_pos, top_k, False, out=(ad_ids, scores),
+                           excluded=excl is not None or masks is not None or cap1 is not None, max_per_group=cap)
         assert list(out["tasks"]) == tasks
         host, done = self._staging(blk.numel(), "out")
         host.copy_(blk, non_blocking=True)
@@ -595,9 +632,14 @@ class TwoStageRetriever:
 
     @torch.no_grad()
     def retrieve_and_rank(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor, stage1_k: int = 500,
-                          stage2_k: int = 10, ad_features_lookup=None, exclude_ad_ids=None):
+                          stage2_k: int = 10, ad_features_lookup=None, exclude_ad_ids=None,
+                          max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None):
         """``exclude_ad_ids``: the ad ids the (first) user must not be shown, a sequence of integers.  With a table, the two
-        lists have length ``stage2_k``; a user with fewer real candidates gets -1 / 0.0 in the tail (batch_recommend)."""
+        lists have length ``stage2_k``; a user with fewer real candidates gets -1 / 0.0 in the tail (batch_recommend).
+        ``stage1_max_per_group`` / ``max_per_group``: the per-group caps on the candidates and on the ranked result
+        (AdRecommenderInference.recommend_device); without a table only the first applies (there is no stage 2)."""
+        idx = self.faiss_index
+        cap, cap1 = idx._check_group_cap(max_per_group), idx._check_group_cap(stage1_max_per_group, "stage1_max_per_group")
         uc = user_categorical.to(self.device)
         un = user_numerical.to(self.device, dtype=torch.float32)
         excl = None if exclude_ad_ids is None else [exclude_ad_ids]
@@ -606,7 +648,7 @@ class TwoStageRetriever:
             blk = _exclude.as_block(excl, 1)
             ids, dist = self.faiss_index.search_device(
                 emb[:1] if blk is not None else emb, stage1_k,
-                exclude=None if blk is None else torch.from_numpy(blk).to(self.device))
+                exclude=None if blk is None else torch.from_numpy(blk).to(self.device), max_per_group=cap1)
             return ids[0].tolist(), dist[0].tolist()
         if self._rec is None or self._rec_table is not ad_features_lookup:
             self._rec = AdRecommenderInference(device=str(self.device), two_tower_model=self.two_tower_model,
@@ -614,7 +656,7 @@ class TwoStageRetriever:
                                                faiss_index=self.faiss_index, ad_features=ad_features_lookup)
             self._rec_table = ad_features_lookup
         r = self._rec.recommend_tensors(uc[:1], un[:1], stage2_k, stage1_k,       # one synchronisation, indices validated
-                                        exclude_ad_ids=excl)[0]
+                                        exclude_ad_ids=excl, max_per_group=cap, stage1_max_per_group=cap1)[0]
         return r["ad_ids"], r["scores"]["ctr"]                                    # :359-369 (ids, ctr probabilities)
 
 
@@ -624,8 +666,12 @@ class GraphedRecommender:
     memory pool) and a private, fixed-size workspace (never the shared grow-only one)."""
 
     def __init__(self, rec: AdRecommenderInference, batch_size: int, top_k: int, stage1_k: int, warmup: int = 2,
-                 max_exclude: int = 0, eligibility: bool = False):
+                 max_exclude: int = 0, eligibility: bool = False, max_per_group: Optional[int] = None,
+                 stage1_max_per_group: Optional[int] = None):
         self.rec, self.batch_size, self.top_k, self.stage1_k = rec, batch_size, top_k, stage1_k
+        # the per-group caps: scalars fixed at capture (the group keys are those of capture time, pinned below)
+        self.max_per_group, self.stage1_max_per_group = rec._check_caps(max_per_group, stage1_max_per_group)
+        caps = dict(max_per_group=self.max_per_group, stage1_max_per_group=self.stage1_max_per_group)
         self.max_exclude = int(max_exclude)
         _exclude.check_exclude(stage1_k, self.max_exclude)
         dev = rec.ad_features.device
@@ -643,17 +689,18 @@ class GraphedRecommender:
         probe = _lib.MeasuringArena(_lib.Workspace())
         with _lib.WORKSPACE.private(probe):
             for _ in range(max(1, warmup)):
-                rec.recommend_device(self._uc, self._un, top_k, stage1_k, exclude_ad_ids=self._ex, require_all=ma, require_any=my)
+                rec.recommend_device(self._uc, self._un, top_k, stage1_k, exclude_ad_ids=self._ex, require_all=ma, require_any=my,
+                                     **caps)
         torch.cuda.synchronize(dev)
         self._arena = _lib.FixedArena(probe.high_water, dev)
         with _lib.WORKSPACE.private(self._arena):
             rec.recommend_device(self._uc, self._un, top_k, stage1_k, exclude_ad_ids=self._ex, require_all=ma,
-                                 require_any=my)                                                  # one eager pass on the private arena
+                                 require_any=my, **caps)                                               # one eager pass on the private arena
             torch.cuda.synchronize(dev)
             self._graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._graph):
                 self._out = rec.recommend_device(self._uc, self._un, top_k, stage1_k, exclude_ad_ids=self._ex, require_all=ma,
-                                                 require_any=my)
+                                                 require_any=my, **caps)
         torch.cuda.synchronize(dev)
         # pin every device buffer the kernel nodes point at: a later load_state_dict / index.add() / larger eager search
         # then makes the graph stale (documented) but can never leave it with dangling pointers

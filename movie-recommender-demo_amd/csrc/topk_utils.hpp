@@ -384,6 +384,57 @@ __device__ inline bool certify_or_fail(const unsigned long long* sorted, int nee
     return false;
 }
 
+// ---- per-group caps (amdrec_select_topk_capped, amdrec_group_cap_compact) -----------------------------------------
+// The group key of corpus position pos: group_of[pos], or -1 (ungrouped) for a position outside [0, n_rows), which is never read.
+__device__ __forceinline__ long long group_at(const long long* group_of, long long n_rows, long long pos) {
+    return (pos >= 0 && pos < n_rows) ? group_of[pos] : -1ll;
+}
+
+// grp[0 .. n) in LDS: the group keys of a query's entries in rank order (negative = ungrouped, or no entry at all).  Does
+// entry i of group g >= 0 have fewer than `cap` earlier entries of its group, i.e. does the greedy pass accept it?  The scan
+// stops once cap earlier ones are seen: a row that is all one group costs ~cap reads per entry, a row of distinct groups i reads
+// (every lane of a wave reads the same words: LDS broadcasts).  Blocks of 8 entries between two looks at the count: their
+// reads are independent and go out together (one entry per trip waited a whole LDS latency for each: 135 us against 40 for
+// amdrec_group_cap_compact at 512 x 1000 -> 500).
+__device__ __forceinline__ bool below_group_cap(const long long* grp, int i, long long g, int cap) {
+    int seen = 0, j = 0;
+    for (; j + 8 <= i && seen < cap; j += 8) {
+        int hit = 0;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) hit += grp[j + t] == g;
+        seen += hit;
+    }
+    for (; j < i && seen < cap; ++j) seen += grp[j] == g;
+    return seen < cap;
+}
+
+// Order-preserving compaction by a block of NT threads whose thread t owns entries t, t + NT, ... (ROUNDS of them): slot[r]
+// = the number of kept entries before entry r * NT + t, returns the number kept in all.  Wave ballot + popcount of the lower
+// lanes, the wave totals of every round through LDS behind ONE block barrier.  All threads call.
+template <int NT, int ROUNDS>
+__device__ inline int compact_slots(const bool (&keep)[ROUNDS], int (&slot)[ROUNDS], int (*wave_total)[NT / 64]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+        const unsigned long long m = __ballot(keep[r]);
+        slot[r] = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_total[r][w] = __popcll(m);
+    }
+    __syncthreads();
+    int base = 0;
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+        slot[r] += base;
+#pragma unroll
+        for (int x = 0; x < NT / 64; ++x) {
+            const int t = wave_total[r][x];
+            if (x < w) slot[r] += t;
+            base += t;
+        }
+    }
+    return base;
+}
+
 __device__ inline void write_result(const unsigned long long* buf, int have, int k, long long q, float* outD,
                                     long long* outI, long long pos_offset) {
     for (int i = threadIdx.x; i < k; i += blockDim.x) {
