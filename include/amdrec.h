@@ -35,7 +35,8 @@ extern "C" {
                                * the eligibility masks: amdrec_flat_search_eligible, amdrec_flat_search_mixed_eligible, added exports; then
                                * the same masks in the inverted-list scans: amdrec_ivf_scan_eligible, amdrec_ivf_scan_grouped_eligible,
                                * amdrec_ivf_scan_grouped_mixed_eligible, amdrec_ivfpq_scan_finite_eligible, added exports; then
-                               * the per-group caps: amdrec_select_topk_capped, amdrec_group_cap_compact, added exports) */
+                               * the per-group caps: amdrec_select_topk_capped, amdrec_group_cap_compact, added exports; then
+                               * auction ranking: amdrec_select_topk_auction, an added export) */
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -701,6 +702,31 @@ int amdrec_select_topk_capped(const float* logits /*[n_tasks][ld]*/, int64_t ld_
 int amdrec_group_cap_compact(const int64_t* pos /*[nq][kc]*/, const float* scores /*[nq][kc]*/, int64_t nq, int kc,
                              const int64_t* group_of /*[n_group_rows]*/, int64_t n_group_rows, int max_per_group, int k,
                              float fill_score, int64_t* out_pos /*[nq][k]*/, float* out_scores /*[nq][k]*/, void* stream);
+
+/* Auction ranking (one more export added to ABI v14, every other entry as it was): amdrec_select_topk ordered by expected
+ * revenue, with an optional per-user reserve, the per-group cap of amdrec_select_topk_capped and generalised second prices.
+ * For candidate slot i of user u (a candidate iff cand_pos >= 0; cand_pos is REQUIRED):
+ *   p = the probability amdrec_select_topk reports for logits[rank_task], b = bid_of[cand_pos] (1.0 for a position >=
+ *   n_bid_rows, which is never read; bids are finite and >= +0.0), e = b * p, one fp32 multiply.
+ * Order: e descending, slot ascending, a NaN e (NaN logit) after every other candidate.  reserve (device [n_users], may be
+ * NULL): a candidate is dropped iff !(e >= reserve[u]) - a NaN e too - and is then no candidate: it cannot win, does not
+ * count towards a cap and sets nobody's price.  max_per_group > 0: the greedy cap over group_of[cand_pos] in that order on
+ * the candidates that pass the reserve; 0: no cap, group_of is not looked at and may be NULL.
+ * The first top_k accepted candidates win.  With next(r) = the candidate the same selection would report at rank r + 1 (for
+ * the last rank the (top_k + 1)-th accepted one, if any) and floor = max(reserve[u] or 0, e of next(r), a missing or NaN one
+ * counting 0): out_price = NaN where the winner's e is NaN, 0.0 where floor == 0, else min(b, floor / p) with the correctly
+ * rounded fp32 division - the smallest bid that keeps the rank, never above the winner's own.  out_ecpm = e.  NaN outputs
+ * are the canonical quiet NaN (0x7fc00000).  out_ids / out_scores / out_slots as amdrec_select_topk; the unfilled tail reads
+ * id -1, slot -1, probability 0.0, eCPM 0.0, price 0.0.  One launch, no workspace; every argument is validated before the
+ * first HIP call. */
+int amdrec_select_topk_auction(const float* logits /*[n_tasks][ld]*/, int64_t ld_logits, int n_tasks, int rank_task,
+                               const int64_t* cand_ids /*[n_users][k_c]*/, const int64_t* cand_pos /*[n_users][k_c]*/,
+                               int64_t n_users, int k_c, int top_k, const float* bid_of /*[n_bid_rows], by cand_pos*/,
+                               int64_t n_bid_rows, const float* reserve /*[n_users] or NULL*/,
+                               const int64_t* group_of /*[n_group_rows]; NULL without a cap*/, int64_t n_group_rows,
+                               int max_per_group /*0: no cap*/, int64_t* out_ids /*[n_users][top_k]*/,
+                               float* out_scores /*[n_tasks][n_users][top_k]*/, int32_t* out_slots /*or NULL*/,
+                               float* out_ecpm /*[n_users][top_k]*/, float* out_price /*[n_users][top_k]*/, void* stream);
 
 #ifdef __cplusplus
 }

@@ -26,7 +26,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, eligible as _eligible, exclude as _exclude, group_cap as _group_cap, ivf, ivfpq, rows_edit as _rows_edit
+from . import _lib, auction as _auction, eligible as _eligible, exclude as _exclude, group_cap as _group_cap, ivf, ivfpq, rows_edit as _rows_edit
 
 _MAGIC = b"AMDRECIX1"
 ADD_BATCH = 1 << 18            # IVFPQ add: rows normalised and encoded per batch (256 MB of fp32 at d = 256)
@@ -137,6 +137,7 @@ class FAISSIndex:
         self._maxnorm = torch.zeros(2, dtype=torch.float32, device=self.device)     # [max row norm, max row rounding-error norm]
         self._tags: Optional[torch.Tensor] = None    # int64 [capacity] eligibility tags (amdrec.eligible), allocated on first use
         self._groups: Optional[torch.Tensor] = None  # int64 [capacity] group keys (amdrec.group_cap), allocated on first use
+        self._bids: Optional[torch.Tensor] = None    # float32 [capacity] bids (amdrec.auction), allocated on first use
         self._identity = True          # ids == arange(n): remap is the identity
         self._nonfinite = False        # Flat: a stored row holds a NaN, so a search can leave slots unfilled with k <= n
         self.n_fixup_out: Optional[torch.Tensor] = None    # Flat: device int32[1] that receives the C entry's n_fixup (diagnostics)
@@ -189,6 +190,8 @@ class FAISSIndex:
             self._tags = grown(self._tags)
         if self._groups is not None:
             self._groups = grown(self._groups)
+        if getattr(self, "_bids", None) is not None:
+            self._bids = grown(self._bids)
         if self._keeps_rows:
             self._xb = grown(self._xb)
             if self._mixed:
@@ -282,6 +285,36 @@ class FAISSIndex:
             return torch.full((self._n,), -1, dtype=torch.int64, device=self.device)
         return self._groups[:self._n].clone()
 
+    def _ensure_bids(self) -> torch.Tensor:
+        """The bids [capacity], allocated on first use: rows that were never given a bid have 1.0."""
+        if getattr(self, "_bids", None) is None:
+            self._bids = torch.ones((self._ids.shape[0],), dtype=torch.float32, device=self.device)
+        return self._bids
+
+    def set_bids(self, bids):
+        """Replace the bid of every row: ``bids`` [ntotal] numbers (amdrec.auction: finite, >= 0, the unit is the caller's).
+        Out of place - a new tensor is swapped in and the old one is never written -, so a selection in flight or a captured
+        graph keeps the bids it started with."""
+        vals = _auction.device_bids(bids, self._n, self.device)
+        new = torch.ones((self._ids.shape[0],), dtype=torch.float32, device=self.device)
+        new[:self._n].copy_(vals)
+        self._bids = new
+
+    def get_bids(self) -> torch.Tensor:
+        """The bids, device float32 [ntotal] (a copy; 1.0 everywhere for an index that never saw a bid)."""
+        if getattr(self, "_bids", None) is None:
+            return torch.ones((self._n,), dtype=torch.float32, device=self.device)
+        return self._bids[:self._n].clone()
+
+    def _check_auction(self, rank_by, reserve):
+        """The ``rank_by`` / ``reserve`` arguments -> (does the auction run, the reserve as amdrec.auction.check_reserve
+        returns it).  Refused before the library is touched: an unknown rank_by, "ecpm" on an index that holds no bids, a
+        reserve without "ecpm", a negative or non-finite scalar reserve."""
+        auction = _auction.check_rank_by(rank_by)
+        if auction and getattr(self, "_bids", None) is None:
+            raise ValueError('rank_by="ecpm" on an index without bids: give them with add(..., bids=) or set_bids()')
+        return auction, _auction.check_reserve(reserve, auction=auction)
+
     def _check_group_cap(self, max_per_group, what: str = "max_per_group"):
         """A ``max_per_group`` argument -> the cap as the entries take it, or None for "no cap".  Refused before the library
         is touched: a cap of 0 or below, and a cap on an index that holds no group keys."""
@@ -328,13 +361,15 @@ class FAISSIndex:
         """The trained coarse quantizer [nlist, dimension] (device tensor), or None."""
         return None if self._ivf is None else self._ivf.centroids
 
-    def add(self, embeddings, ad_ids: Optional[List] = None, tags=None, groups=None):
+    def add(self, embeddings, ad_ids: Optional[List] = None, tags=None, groups=None, bids=None):
         """faiss_retrieval.py:97-127.  A Flat index also checks the added rows for non-finite values (_note_nonfinite: one
         reduction over them and a host read, i.e. add() synchronises), so that search_device never has to.
         ``tags``: one 64-bit eligibility word per added row (amdrec.eligible); without it the rows get tag 0, and an index
         that never sees a tag keeps no tag tensor at all.
         ``groups``: one int64 group key per added row (amdrec.group_cap; negative = ungrouped); without it the rows get -1,
-        and an index that never sees a group keeps no group tensor at all."""
+        and an index that never sees a group keeps no group tensor at all.
+        ``bids``: one float32 bid per added row (amdrec.auction; finite, >= 0); without it the rows get 1.0, and an index
+        that never sees a bid keeps no bid tensor at all."""
         if ad_ids is None and not self._default_ids_ok:
             raise ValueError("add() without ad_ids after remove_ids(): default ids are corpus positions, and the removal has "
                              "moved the positions under the ids that stayed; pass ad_ids")
@@ -352,6 +387,7 @@ class FAISSIndex:
         m = src.shape[0]
         new_tags = None if tags is None else _eligible.device_words(tags, m, self.device)    # (refused before anything changes)
         new_groups = None if groups is None else _group_cap.device_keys(groups, m, self.device)
+        new_bids = None if bids is None else _auction.device_bids(bids, m, self.device)
         self._reserve(self._n + m)
         if not self._keeps_rows:
             # normalised and encoded batch by batch: only the codes stay (and, with refine, the kept form of the rows).
@@ -398,6 +434,10 @@ class FAISSIndex:
             self._ensure_groups()[self._n:self._n + m].copy_(new_groups)
         elif self._groups is not None:
             self._groups[self._n:self._n + m].fill_(-1)
+        if new_bids is not None:
+            self._ensure_bids()[self._n:self._n + m].copy_(new_bids)
+        elif getattr(self, "_bids", None) is not None:
+            self._bids[self._n:self._n + m].fill_(1.0)
         if self._pq is not None:
             self._pq.commit(pq_new)
         elif self._ivf is not None:
@@ -454,6 +494,8 @@ class FAISSIndex:
             self._tags = gather(self._tags)
         if self._groups is not None:
             self._groups = gather(self._groups)
+        if getattr(self, "_bids", None) is not None:
+            self._bids = gather(self._bids)
         if self._keeps_rows:
             self._xb = gather(self._xb)
         self._n = m
@@ -477,6 +519,7 @@ class FAISSIndex:
         """Every device tensor the index keeps between calls (a captured graph's kernels point at them)."""
         return ([self._xb, self._ids, self._xb16, self._maxnorm] + ([] if self._tags is None else [self._tags]) +
                 ([] if self._groups is None else [self._groups]) +
+                ([] if getattr(self, "_bids", None) is None else [self._bids]) +
                 (self._state.resident_tensors() if self._state else []))
 
     @property
@@ -711,6 +754,8 @@ class FAISSIndex:
             arrays.append(("groups", self._groups[:self._n].cpu().numpy()))
         if self._state is not None:                                  # IVFPQ: codes, centroids, codebooks, assignment
             arrays += self._state.export_arrays()
+        if getattr(self, "_bids", None) is not None:                 # (absent: an index that never saw a bid, as every earlier file)
+            arrays.append(("bids", self._bids[:self._n].cpu().numpy()))
         header = {"dimension": self.dimension, "index_type": self.index_type, "nlist": self.nlist,
                   "nprobe": self.nprobe, "ntotal": self._n, "identity_ids": self._identity,
                   "arrays": [{"name": n, "dtype": str(a.dtype), "shape": list(a.shape)} for n, a in arrays]}
@@ -762,6 +807,8 @@ class FAISSIndex:
             self._ensure_tags()[:n].copy_(torch.from_numpy(arrays["tags"].copy()))
         if "groups" in arrays:
             self._ensure_groups()[:n].copy_(torch.from_numpy(arrays["groups"].copy()))
+        if "bids" in arrays:
+            self._ensure_bids()[:n].copy_(torch.from_numpy(arrays["bids"].copy()))
         self._n = n
         self._shadow_rows(0, n)
         if self._keeps_rows:

@@ -27,7 +27,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import _lib, eligible as _eligible, exclude as _exclude, rows_edit as _rows_edit
+from . import _lib, auction as _auction, eligible as _eligible, exclude as _exclude, rows_edit as _rows_edit
 from .index import FAISSIndex
 from .ranker import TransformerRanker
 from .towers import TwoTowerModel
@@ -241,7 +241,7 @@ class AdRecommenderInference:
                                               require_any=masks[1], max_per_group=max_per_group)
 
     def _stage2(self, uc, un, cand_pos, top_k, check_indices, ids_are_positions=False, mark=None, out=None,
-                excluded=False, heads=None, max_per_group=None):
+                excluded=False, heads=None, max_per_group=None, auction=None):
         """Ranker + selection over stage 1's positions ``cand_pos`` [B, stage1_k].  A negative position is a slot the search
         could not fill: no candidate.  The ranker still computes a (finite, unspecified) logit for it - every gather clamps
         the row - and the selection, which is handed the positions, ranks it after every real candidate: it is reported only
@@ -249,7 +249,9 @@ class AdRecommenderInference:
         decided here, by position: ``candidate_ids`` keeps the search's convention for such a slot (``id_map[-1]``; the
         position itself with ``ids_are_positions``), from which it can no longer be told.
         ``max_per_group`` (validated by the caller, None: no cap): the selection is amdrec_select_topk_capped over the index's
-        group keys - at most that many winners of one group per user, greedy in the selection's order."""
+        group keys - at most that many winners of one group per user, greedy in the selection's order.
+        ``auction`` (validated by the caller, None: rank by CTR): ``(reserve,)`` - the selection is amdrec_select_topk_auction
+        over the index's bids (amdrec.auction has the rule), the cap inside it, and the result gains ``ecpm`` / ``prices``."""
         lib = _lib.load()
         B, stage1_k = cand_pos.shape
         rk = self.transformer_ranker
@@ -271,7 +273,7 @@ class AdRecommenderInference:
         if mark is not None:                     # amdrec.sharded.StageTimer: the ranker ends here, the selection follows
             mark("ranker")
         if out is not None:                      # (ad_ids, scores) views of one block: the reference API's single D2H copy
-            ad_ids, scores = out
+            ad_ids, scores = out[0], out[1]      # (under the auction the block also holds ecpm and prices: out[2], out[3])
         else:
             ad_ids = torch.empty((B, top_k), dtype=torch.int64, device=uc.device)
             scores = torch.empty((len(tasks), B, top_k), dtype=torch.float32, device=uc.device)
@@ -288,31 +290,49 @@ class AdRecommenderInference:
             cand_ids = torch.empty_like(cand_pos)
             _lib.check(lib.amdrec_remap_ids(_lib.ptr(cand_pos), _lib.ptr(idx._ids), idx._n, _lib.ptr(cand_ids),
                                             cand_pos.numel(), _lib.stream_ptr(uc.device)))
-        if max_per_group is None:
-            select, groups = lib.amdrec_select_topk, ()
+        mid, ecpm, prices = (), None, None       # mid / tail: what an entry takes between top_k and out_ids / behind out_slots
+        if auction is not None:
+            # the auction entry: the selection's arguments with the bids, the reserve and the groups in the middle and two
+            # outputs more; the cap (0: none) rides in the same launch
+            select = lib.amdrec_select_topk_auction
+            reserve = _auction.reserve_tensor(_auction.check_reserve(auction[0], B), B, uc.device)
+            mid = (_lib.ptr(idx._bids), idx._n, _lib.ptr(reserve), _lib.ptr(idx._groups) if max_per_group else None,
+                   idx._n if max_per_group else 0, max_per_group or 0)
+            if out is not None and len(out) == 4:
+                ecpm, prices = out[2], out[3]
+            else:
+                ecpm = torch.empty((B, top_k), dtype=torch.float32, device=uc.device)
+                prices = torch.empty((B, top_k), dtype=torch.float32, device=uc.device)
+            tail = (_lib.ptr(ecpm), _lib.ptr(prices))
+        elif max_per_group is None:
+            select, tail = lib.amdrec_select_topk, ()
         else:                                    # the same arguments, then the groups: the cap runs inside the selection
-            select, groups = lib.amdrec_select_topk_capped, (_lib.ptr(idx._groups), idx._n, max_per_group)
+            select, tail = lib.amdrec_select_topk_capped, (_lib.ptr(idx._groups), idx._n, max_per_group)
         if B and ctr_first:
             # the selection as ever, on the one logit row: ad ids, plane 0 of scores and the winning slots; then the winners'
             # other tasks into planes 1 ..
             slots = torch.empty((B, top_k), dtype=torch.int32, device=uc.device)
             _lib.check(select(_lib.ptr(logits), logits.stride(0), 1, 0, _lib.ptr(cand_ids), _lib.ptr(cand_pos),
-                              B, stage1_k, top_k, _lib.ptr(ad_ids), _lib.ptr(scores), _lib.ptr(slots), *groups,
+                              B, stage1_k, top_k, *mid, _lib.ptr(ad_ids), _lib.ptr(scores), _lib.ptr(slots), *tail,
                               _lib.stream_ptr(uc.device)))
             rk.winner_scores(trunk, slots, stage1_k, scores)
         elif B:
             _lib.check(select(_lib.ptr(logits), logits.stride(0), len(tasks), tasks.index("ctr"),
-                              _lib.ptr(cand_ids), _lib.ptr(cand_pos), B, stage1_k, top_k,
-                              _lib.ptr(ad_ids), _lib.ptr(scores), None, *groups, _lib.stream_ptr(uc.device)))
-        return {"ad_ids": ad_ids, "scores": scores, "tasks": tasks, "candidate_ids": cand_ids, "logits": logits,
-                "logit_tasks": ("ctr",) if ctr_first else tuple(tasks)}
+                              _lib.ptr(cand_ids), _lib.ptr(cand_pos), B, stage1_k, top_k, *mid,
+                              _lib.ptr(ad_ids), _lib.ptr(scores), None, *tail, _lib.stream_ptr(uc.device)))
+        res = {"ad_ids": ad_ids, "scores": scores, "tasks": tasks, "candidate_ids": cand_ids, "logits": logits,
+               "logit_tasks": ("ctr",) if ctr_first else tuple(tasks)}
+        if auction is not None:
+            res["ecpm"], res["prices"] = ecpm, prices
+        return res
 
     @torch.no_grad()
     def recommend_device(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor, top_k: int = 10,
                          stage1_k: int = 500, check_indices: bool = False,
                          exclude_ad_ids: Optional[torch.Tensor] = None, heads: Optional[str] = None,
                          require_all: Optional[torch.Tensor] = None, require_any: Optional[torch.Tensor] = None,
-                         max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None):
+                         max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
+                         rank_by: Optional[str] = None, reserve=None):
         """[B,6] / [B,13] device tensors -> dict of device tensors, no host synchronisation:
         ad_ids [B,top_k] int64, scores [3,B,top_k] float32 (sigmoid of the logits), candidate_ids
         [B,stage1_k], candidate_scores [B,stage1_k], logits [3, B*stage1_k].  candidate_scores are the index's own
@@ -340,10 +360,18 @@ class AdRecommenderInference:
         candidate list (FAISSIndex.search_device(max_per_group=): the cap applied to the index's own top
         2 * stage1_k), so that one advertiser's near-duplicate creatives cannot fill the candidates; slots the cap
         leaves empty are unfilled slots as above.  Either on an index without group keys, or <= 0: ValueError.
+        ``rank_by`` (None / "ctr": the CTR order, the launches of ever): "ecpm" ranks a user's candidates by bid x pCTR over
+        the index's bids (FAISSIndex.add(bids=) / set_bids; amdrec.auction has the rule), inside the selection launch, with
+        ``max_per_group`` applied in that order; the dict gains ``ecpm`` and ``prices``, float32 [B, top_k]: each winner's
+        expected revenue and its generalised second price (0.0 in the unfilled tail).  ``reserve`` (needs "ecpm"): a Python
+        float >= 0 for every user, or a device float32 [B]; candidates whose eCPM does not reach it are dropped and it is
+        every price's floor.  "ecpm" on an index without bids, an unknown ``rank_by``, a reserve without "ecpm" and a
+        negative or non-finite scalar reserve: ValueError.
         ``check_indices``: an out-of-range user index or ad-table row raises IndexError; an unfilled slot does not."""
         if heads is not None:
             self._check_heads(heads)
         cap, cap1 = self._check_caps(max_per_group, stage1_max_per_group)          # (before the library is touched)
+        auction = self._check_auction(rank_by, reserve)
         uc = _lib.require_gpu(user_categorical, "user_categorical")
         un = _lib.require_gpu(user_numerical, "user_numerical")
         excluded = exclude_ad_ids is not None and exclude_ad_ids.shape[-1] > 0
@@ -352,13 +380,14 @@ class AdRecommenderInference:
                                              (require_all, require_any), cap1)
         # (excluded: "a slot can be unfilled" - true after a filtered stage 1 as well)
         out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded or masked or cap1 is not None,
-                           heads=heads, max_per_group=cap)
+                           heads=heads, max_per_group=cap, auction=auction)
         out["candidate_scores"] = cand_scores
         return out
 
     def capture(self, batch_size: int, top_k: int = 10, stage1_k: int = 500, warmup: int = 2,
                 max_exclude: int = 0, eligibility: bool = False, max_per_group: Optional[int] = None,
-                stage1_max_per_group: Optional[int] = None) -> "GraphedRecommender":
+                stage1_max_per_group: Optional[int] = None, rank_by: Optional[str] = None,
+                reserve: bool = False) -> "GraphedRecommender":
         """Capture one recommend_device call for a fixed batch shape into a HIP graph (the ~40 kernel
         launches of a request are host-launch-bound at small batch: 1.76 ms eager at B = 1) and return a
         replayer.  Weights, index and ad table must not change afterwards.  ``max_exclude`` > 0: the graph also holds a
@@ -367,9 +396,11 @@ class AdRecommenderInference:
         holds static [batch_size] mask buffers and runs the filtered search (the replayer's ``require_all`` /
         ``require_any`` fill them; the tags are those of capture time); False captures the graph as ever.
         ``max_per_group`` / ``stage1_max_per_group`` (recommend_device): scalars fixed at capture; the group keys are those
-        of capture time."""
+        of capture time.  ``rank_by`` (recommend_device) is fixed at capture too, and the bids are those of capture time;
+        ``reserve=True`` (needs "ecpm") gives the graph a static [batch_size] float32 reserve buffer that the replayer's
+        ``reserve`` argument fills."""
         return GraphedRecommender(self, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group,
-                                  stage1_max_per_group)
+                                  stage1_max_per_group, rank_by, reserve)
 
     # -- live corpus: ads leave and enter without a rebuild of the index or of the ranker's per-ad caches ------------------
     def remove_ads(self, ad_ids) -> int:
@@ -388,9 +419,9 @@ class AdRecommenderInference:
         self._swap_ad_table(old, new)
         return removed
 
-    def add_ads(self, embeddings, ad_features, ad_ids=None, tags=None, groups=None) -> None:
+    def add_ads(self, embeddings, ad_features, ad_ids=None, tags=None, groups=None, bids=None) -> None:
         """Insert ads: ``embeddings`` [m, d] go to the index (FAISSIndex.add: ``ad_ids`` as there; required once ads have been
-        removed; ``tags``: the ads' 64-bit eligibility words, ``groups``: their int64 group keys, as there), ``ad_features`` [m, n_ad_feat] integer rows are
+        removed; ``tags``: the ads' 64-bit eligibility words, ``groups``: their int64 group keys, ``bids``: their float32 bids, as there), ``ad_features`` [m, n_ad_feat] integer rows are
         appended to the ad-feature table, and the ranker's per-ad
         caches grow by projecting the m new rows only (TransformerRanker.extend_ad_cache).  The feature rows are checked
         against the ranker's ad embedding tables first (IndexError, as an embedding lookup would raise), and a rejected call
@@ -410,7 +441,7 @@ class AdRecommenderInference:
         if feats.numel() and bool(((feats < 0) | (feats >= cards)).any().item()):
             raise IndexError("index out of range in self: an ad_features row is outside the ranker's ad embedding tables")
         n_old = idx.index.ntotal
-        idx.add(embeddings, ad_ids, tags=tags, groups=groups)   # (refuses before it commits anything)
+        idx.add(embeddings, ad_ids, tags=tags, groups=groups, bids=bids)   # (refuses before it commits anything)
         new = torch.cat([old[:n_old], feats])
         if old.shape[0] == n_old:
             self.transformer_ranker.extend_ad_cache(old, new)
@@ -428,21 +459,24 @@ class AdRecommenderInference:
     # -- reference API ------------------------------------------------------------------------
     def recommend_ads(self, user_data: dict, top_k: int = 10, stage1_k: int = 500,
                       return_scores: bool = True, exclude_ad_ids=None, require_all: int = 0, require_any: int = 0,
-                      max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None) -> dict:
+                      max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
+                      rank_by: Optional[str] = None, reserve=None) -> dict:
         """inference.py:199-288.  ``exclude_ad_ids``: the ad ids this user must not be shown (a sequence of integers).
         ``require_all`` / ``require_any``: this request's eligibility masks (64-bit integers; 0 and 0: no constraint, the
-        plain search).  ``max_per_group`` / ``stage1_max_per_group``: the per-group caps of recommend_device.  Fewer than
+        plain search).  ``max_per_group`` / ``stage1_max_per_group``: the per-group caps of recommend_device.  ``rank_by`` /
+        ``reserve``: the auction of recommend_device (the dict gains ``ecpm`` and ``prices``).  Fewer than
         ``top_k`` real candidates: as batch_recommend."""
         masked = bool(require_all) or bool(require_any)
         return self.batch_recommend([user_data], top_k=top_k, stage1_k=stage1_k, return_scores=return_scores,
                                     exclude_ad_ids=None if exclude_ad_ids is None else [exclude_ad_ids],
                                     require_all=[require_all] if masked else None,
                                     require_any=[require_any] if masked else None, max_per_group=max_per_group,
-                                    stage1_max_per_group=stage1_max_per_group)[0]
+                                    stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve)[0]
 
     def batch_recommend(self, user_data_list: list, top_k: int = 10, stage1_k: int = 500,
                         return_scores: bool = True, exclude_ad_ids=None, require_all=None, require_any=None,
-                        max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None) -> list:
+                        max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
+                        rank_by: Optional[str] = None, reserve=None) -> list:
         """inference.py:290-331 - but one device pass for the whole list instead of a serial loop.
         ``timing`` reports the batch's stage times divided by the number of users.  ``exclude_ad_ids``: one sequence of
         ad ids per user (recommend_device has the meaning); the padded block travels in the input staging block.
@@ -452,8 +486,11 @@ class AdRecommenderInference:
         ads for a user (a corpus smaller than top_k, exclusions, narrow probes, a NaN feature) the tail reads ad id -1
         with score 0.0 for every task, and no ad appears that stage 1 did not retrieve for that user.
         ``max_per_group`` / ``stage1_max_per_group``: the per-group caps of recommend_device, for every user of the list (a
-        user with fewer than ``top_k`` ads that the cap lets through gets the same tail)."""
+        user with fewer than ``top_k`` ads that the cap lets through gets the same tail).  ``rank_by`` / ``reserve``: the
+        auction of recommend_device; every user's dict gains ``"ecpm"`` and ``"prices"`` lists of length ``top_k``, which travel
+        in the same result block: no copy and no synchronisation more."""
         self._check_caps(max_per_group, stage1_max_per_group)
+        self._check_auction(rank_by, reserve)
         if not user_data_list:
             return []
         n = len(user_data_list)
@@ -464,12 +501,18 @@ class AdRecommenderInference:
         masks = rest.pop(0) if masks is not None else None
         return self.recommend_tensors(uc, un, top_k, stage1_k, return_scores, _encoded=True, _exclude_dev=excl,
                                       _masks_dev=masks, max_per_group=max_per_group,
-                                      stage1_max_per_group=stage1_max_per_group)
+                                      stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve)
 
     def _check_caps(self, max_per_group, stage1_max_per_group):
         """The two cap arguments -> (cap or None, stage-1 cap or None); refusals before the library is touched."""
         idx = self.faiss_index
         return idx._check_group_cap(max_per_group), idx._check_group_cap(stage1_max_per_group, "stage1_max_per_group")
+
+    def _check_auction(self, rank_by, reserve):
+        """The ``rank_by`` / ``reserve`` arguments -> None (rank by CTR) or ``(reserve or None,)``; refusals before the library
+        is touched (FAISSIndex._check_auction)."""
+        auction, reserve = self.faiss_index._check_auction(rank_by, reserve)
+        return (reserve,) if auction else None
 
     def _host_masks(self, require_all, require_any, n: int) -> Optional[np.ndarray]:
         """The two mask arguments of the reference-API calls -> int64 [2, n] on the host (None: neither given)."""
@@ -527,7 +570,7 @@ class AdRecommenderInference:
     @torch.no_grad()
     def recommend_tensors(self, user_categorical, user_numerical, top_k=10, stage1_k=500, return_scores=True,
                           _encoded=False, exclude_ad_ids=None, _exclude_dev=None, require_all=None, require_any=None,
-                          _masks_dev=None, max_per_group=None, stage1_max_per_group=None):
+                          _masks_dev=None, max_per_group=None, stage1_max_per_group=None, rank_by=None, reserve=None):
         """Tensor-level entry (cf. TwoStageRetriever.retrieve_and_rank, faiss_retrieval.py:283-369); result dicts follow
         inference.py:272-288.  ONE host synchronisation per call (round 3 had four: the tower's index flag, the stage-1
         timing sync, the ranker's index flag, the result copy - each exposing the launch work queued behind it): indices
@@ -537,8 +580,10 @@ class AdRecommenderInference:
         one padded block through pinned memory (no synchronisation of its own).  ``require_all`` / ``require_any``: the
         users' eligibility masks as in batch_recommend, shipped the same way.  The lists keep length ``top_k``, with
         -1 / 0.0 in the tail of a user with fewer real candidates (batch_recommend).  ``max_per_group`` /
-        ``stage1_max_per_group``: the per-group caps of recommend_device."""
+        ``stage1_max_per_group``: the per-group caps of recommend_device.  ``rank_by`` / ``reserve``: its auction; ``ecpm`` and
+        ``prices`` ride in the same result block and copy."""
         cap, cap1 = self._check_caps(max_per_group, stage1_max_per_group)
+        auction = self._check_auction(rank_by, reserve)
         t0 = time.time()
         dev = self.device
         uc = user_categorical.to(dev)
@@ -567,10 +612,15 @@ class AdRecommenderInference:
         if ev is None:
             ev = self.__dict__["_ev"] = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ids_b, sc_b = n * top_k * 8, len(tasks) * n * top_k * 4
-        blk = torch.empty(ids_b + sc_b + 8, dtype=torch.uint8, device=dev)
+        au_b = 0 if auction is None else n * top_k * 4                       # ecpm, then prices, behind the scores
+        blk = torch.empty(ids_b + sc_b + 2 * au_b + 8, dtype=torch.uint8, device=dev)
         ad_ids = blk[:ids_b].view(torch.int64).view(n, top_k)
         scores = blk[ids_b:ids_b + sc_b].view(torch.float32).view(len(tasks), n, top_k)
-        verdict = blk[ids_b + sc_b:].view(torch.int32)                       # [2]: nonzero = an index out of range
+        outs = (ad_ids, scores)
+        if auction is not None:
+            outs += tuple(blk[ids_b + sc_b + i * au_b:ids_b + sc_b + (i + 1) * au_b].view(torch.float32).view(n, top_k)
+                          for i in range(2))
+        verdict = blk[ids_b + sc_b + 2 * au_b:].view(torch.int32)            # [2]: nonzero = an index out of range
         trusted = _encoded and self.preprocessor is not None and self._encoder_fits()
         if trusted:
             verdict.zero_()
@@ -585,8 +635,9 @@ class AdRecommenderInference:
         ev[0].record(st)
         cand_pos, _ = self._stage1(uc, un, stage1_k, False, excl, (None, None) if masks is None else (masks[0], masks[1]), cap1)
         ev[1].record(st)
-        out = self._stage2(uc, un, cand_pos, top_k, False, out=(ad_ids, scores),
-                           excluded=excl is not None or masks is not None or cap1 is not None, max_per_group=cap)
+        out = self._stage2(uc, un, cand_pos, top_k, False, out=outs,
+                           excluded=excl is not None or masks is not None or cap1 is not None, max_per_group=cap,
+                           auction=auction)
         assert list(out["tasks"]) == tasks
         host, done = self._staging(blk.numel(), "out")
         host.copy_(blk, non_blocking=True)
@@ -594,10 +645,11 @@ class AdRecommenderInference:
         done.record(st)
         ev[2].synchronize()
         hv = host.numpy()
-        if int(hv[ids_b + sc_b:].view(np.int32)[0]):
+        if int(hv[ids_b + sc_b + 2 * au_b:].view(np.int32)[0]):
             raise IndexError("index out of range in self")                    # torch.nn.Embedding's message
         ids = hv[:ids_b].view(np.int64).reshape(n, top_k).tolist()
         sc = hv[ids_b:ids_b + sc_b].view(np.float32).reshape(len(tasks), n, top_k).tolist() if return_scores else None
+        au = None if auction is None else hv[ids_b + sc_b:ids_b + sc_b + 2 * au_b].view(np.float32).reshape(2, n, top_k).tolist()
         t2 = time.time()
         # stage 1 = its GPU time (tower + search, as the reference brackets them); stage 2 = the rest of the call's wall time
         # (ranker, selection, the copy back and the list conversion: what the reference's second bracket holds)
@@ -609,6 +661,8 @@ class AdRecommenderInference:
                  "timing": {"stage1_ms": stage1_ms, "stage2_ms": total_ms - stage1_ms, "total_ms": total_ms}}
             if return_scores:
                 r["scores"] = {t: sc[i][b] for i, t in enumerate(tasks)}
+            if au is not None:
+                r["ecpm"], r["prices"] = au[0][b], au[1][b]
             res.append(r)
         return res
 
@@ -633,13 +687,17 @@ class TwoStageRetriever:
     @torch.no_grad()
     def retrieve_and_rank(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor, stage1_k: int = 500,
                           stage2_k: int = 10, ad_features_lookup=None, exclude_ad_ids=None,
-                          max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None):
+                          max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
+                          rank_by: Optional[str] = None, reserve=None):
         """``exclude_ad_ids``: the ad ids the (first) user must not be shown, a sequence of integers.  With a table, the two
         lists have length ``stage2_k``; a user with fewer real candidates gets -1 / 0.0 in the tail (batch_recommend).
         ``stage1_max_per_group`` / ``max_per_group``: the per-group caps on the candidates and on the ranked result
-        (AdRecommenderInference.recommend_device); without a table only the first applies (there is no stage 2)."""
+        (AdRecommenderInference.recommend_device); without a table only the first applies (there is no stage 2).
+        ``rank_by`` / ``reserve``: the auction of recommend_device for the ranked result (the tuple is as ever: ids and CTR
+        probabilities, in eCPM order); without a table they are checked and change nothing."""
         idx = self.faiss_index
         cap, cap1 = idx._check_group_cap(max_per_group), idx._check_group_cap(stage1_max_per_group, "stage1_max_per_group")
+        idx._check_auction(rank_by, reserve)
         uc = user_categorical.to(self.device)
         un = user_numerical.to(self.device, dtype=torch.float32)
         excl = None if exclude_ad_ids is None else [exclude_ad_ids]
@@ -656,7 +714,8 @@ class TwoStageRetriever:
                                                faiss_index=self.faiss_index, ad_features=ad_features_lookup)
             self._rec_table = ad_features_lookup
         r = self._rec.recommend_tensors(uc[:1], un[:1], stage2_k, stage1_k,       # one synchronisation, indices validated
-                                        exclude_ad_ids=excl, max_per_group=cap, stage1_max_per_group=cap1)[0]
+                                        exclude_ad_ids=excl, max_per_group=cap, stage1_max_per_group=cap1,
+                                        rank_by=rank_by, reserve=reserve)[0]
         return r["ad_ids"], r["scores"]["ctr"]                                    # :359-369 (ids, ctr probabilities)
 
 
@@ -667,11 +726,16 @@ class GraphedRecommender:
 
     def __init__(self, rec: AdRecommenderInference, batch_size: int, top_k: int, stage1_k: int, warmup: int = 2,
                  max_exclude: int = 0, eligibility: bool = False, max_per_group: Optional[int] = None,
-                 stage1_max_per_group: Optional[int] = None):
+                 stage1_max_per_group: Optional[int] = None, rank_by: Optional[str] = None, reserve: bool = False):
         self.rec, self.batch_size, self.top_k, self.stage1_k = rec, batch_size, top_k, stage1_k
         # the per-group caps: scalars fixed at capture (the group keys are those of capture time, pinned below)
         self.max_per_group, self.stage1_max_per_group = rec._check_caps(max_per_group, stage1_max_per_group)
         caps = dict(max_per_group=self.max_per_group, stage1_max_per_group=self.stage1_max_per_group)
+        # the auction: rank_by fixed at capture (the bids are those of capture time, pinned below); reserve=True: a static
+        # [batch_size] reserve buffer, zeros = every non-NaN eCPM passes
+        self.rank_by = rank_by
+        auction = rec._check_auction(rank_by, 0.0 if reserve else None) is not None
+        self._reserve = None
         self.max_exclude = int(max_exclude)
         _exclude.check_exclude(stage1_k, self.max_exclude)
         dev = rec.ad_features.device
@@ -685,6 +749,10 @@ class GraphedRecommender:
         self.eligibility = bool(eligibility)
         self._masks = torch.zeros((2, batch_size), dtype=torch.int64, device=dev) if self.eligibility else None
         ma, my = (self._masks[0], self._masks[1]) if self.eligibility else (None, None)
+        if auction:
+            if reserve:
+                self._reserve = torch.zeros((batch_size,), dtype=torch.float32, device=dev)
+            caps.update(rank_by=rank_by, reserve=self._reserve)
         # sizing + warm-up pass on the shared workspace (packs weights, sets kernel attributes)
         probe = _lib.MeasuringArena(_lib.Workspace())
         with _lib.WORKSPACE.private(probe):
@@ -710,12 +778,14 @@ class GraphedRecommender:
     @torch.no_grad()
     def __call__(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor,
                  exclude: Optional[torch.Tensor] = None, require_all: Optional[torch.Tensor] = None,
-                 require_any: Optional[torch.Tensor] = None):
+                 require_any: Optional[torch.Tensor] = None, reserve=None):
         """Device tensors [batch_size, ...] -> the same dict as recommend_device (static output buffers,
         overwritten by the next call).  ``exclude``: device int64 [batch_size, E <= max_exclude] ad ids (negative =
         padding), copied into the graph's block; None = nothing excluded (the block is filled with -1).  ``require_all`` /
         ``require_any``: device int64 [batch_size] eligibility masks, copied into the graph's buffers (None = zeros: no
-        constraint); a graph captured without ``eligibility`` raises ValueError for them."""
+        constraint); a graph captured without ``eligibility`` raises ValueError for them.  ``reserve``: a float >= 0 or a
+        device float32 [batch_size], copied into the graph's reserve buffer (None = zeros); a graph captured without
+        ``reserve=True`` raises ValueError for it."""
         if user_categorical.shape[0] != self.batch_size:
             raise ValueError(f"captured for batch {self.batch_size}, got {user_categorical.shape[0]}")
         if exclude is not None and (self._ex is None or exclude.dim() != 2 or exclude.shape[0] != self.batch_size
@@ -728,6 +798,15 @@ class GraphedRecommender:
             for m in (require_all, require_any):
                 if m is not None and (m.dtype != torch.int64 or m.shape != (self.batch_size,)):
                     raise ValueError(f"masks must be int64 [{self.batch_size}], got {m.dtype} {tuple(m.shape)}")
+        if reserve is not None:
+            if self._reserve is None:
+                raise ValueError("captured without reserve=True: this graph holds no reserve buffer")
+            reserve = _auction.check_reserve(reserve, self.batch_size)
+        if self._reserve is not None:
+            if isinstance(reserve, torch.Tensor):
+                self._reserve.copy_(reserve)
+            else:
+                self._reserve.fill_(0.0 if reserve is None else reserve)
         if self._masks is not None:
             for row, m in zip(self._masks, (require_all, require_any)):
                 row.zero_() if m is None else row.copy_(m)

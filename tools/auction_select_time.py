@@ -1,0 +1,96 @@
+"""Dev tool: what the auction costs inside the stage-2 selection.  In ONE process, after a warm-up, alternating over REPS
+repeats (each a HIP-event pair around ITERS back-to-back launches, divided by ITERS), at 512 x 500 -> 10 and 1 x 500 -> 10:
+  amdrec_select_topk and amdrec_select_topk_capped (cap 2) - csrc/rows.hip, which the auction does not touch, so these are the
+  parent commit's kernels - against amdrec_select_topk_auction without a cap and with cap 2, both with a per-user reserve,
+  over bids and group keys of a million ads.
+The spread is (max - min) / median over the repeats of one cell.
+usage: python tools/auction_select_time.py [--out FILE] [--reps R] [--iters N]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--out", default=None)
+ap.add_argument("--reps", type=int, default=9)
+ap.add_argument("--iters", type=int, default=50)
+ARGS = ap.parse_args()
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "movie-recommender-demo_amd"))
+import torch  # noqa: E402
+from amdrec import _lib  # noqa: E402
+
+
+def stats(us):
+    med = statistics.median(us)
+    return {"median_us": round(med, 3), "min_us": round(min(us), 3), "max_us": round(max(us), 3),
+            "spread": round((max(us) - min(us)) / med, 4), "repeats": len(us)}
+
+
+def event_us(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / iters
+
+
+def alternate(cells):
+    """{name: launch} -> {name: stats}: one warm-up round, then REPS rounds that visit every cell in turn."""
+    for name, fn in cells.items():
+        assert fn() == 0, (name, _lib.load().amdrec_last_error())
+        event_us(fn, 3)
+    times = {name: [] for name in cells}
+    for _ in range(ARGS.reps):
+        for name, fn in cells.items():
+            times[name].append(event_us(fn, ARGS.iters))
+    return {name: stats(t) for name, t in times.items()}
+
+
+def select_cells(lib, users, k_c, top_k, cap, n_ads=1_000_000, n_groups=60):
+    dev = "cuda"
+    g = torch.Generator(device=dev)
+    g.manual_seed(users + k_c)
+    logits = torch.randn((3, users * k_c), generator=g, device=dev)
+    pos = torch.randint(0, n_ads, (users, k_c), generator=g, device=dev)
+    groups = torch.randint(0, n_groups, (n_ads,), generator=g, device=dev)
+    bids = torch.rand((n_ads,), generator=g, device=dev) * 4
+    reserve = torch.full((users,), 0.25, device=dev)                  # drops roughly a fifth of the eCPMs
+    ids = torch.empty((users, top_k), dtype=torch.int64, device=dev)
+    sc = torch.empty((3, users, top_k), dtype=torch.float32, device=dev)
+    ecpm = torch.empty((users, top_k), dtype=torch.float32, device=dev)
+    price = torch.empty((users, top_k), dtype=torch.float32, device=dev)
+    st = _lib.stream_ptr(dev)
+    head = (_lib.ptr(logits), logits.stride(0), 3, 0, _lib.ptr(pos), _lib.ptr(pos), users, k_c, top_k)
+    outs = (_lib.ptr(ids), _lib.ptr(sc), None)
+    bid = (_lib.ptr(bids), n_ads, _lib.ptr(reserve))
+    tail = (_lib.ptr(ecpm), _lib.ptr(price), st)
+    cells = {
+        "select_topk": lambda: lib.amdrec_select_topk(*head, *outs, st),
+        "select_topk_capped": lambda: lib.amdrec_select_topk_capped(*head, *outs, _lib.ptr(groups), n_ads, cap, st),
+        "select_topk_auction": lambda: lib.amdrec_select_topk_auction(*head, *bid, None, 0, 0, *outs, *tail),
+        "select_topk_auction_capped": lambda: lib.amdrec_select_topk_auction(*head, *bid, _lib.ptr(groups), n_ads, cap, *outs, *tail),
+    }
+    res = alternate(cells)
+    res["auction_over_capped"] = round(res["select_topk_auction"]["median_us"] / res["select_topk_capped"]["median_us"], 3)
+    res["auction_capped_over_capped"] = round(res["select_topk_auction_capped"]["median_us"] /
+                                              res["select_topk_capped"]["median_us"], 3)
+    res["shape"] = {"users": users, "candidates": k_c, "top_k": top_k, "cap": cap, "groups": n_groups}
+    return res
+
+
+def main():
+    lib = _lib.load()
+    res = {"device": torch.cuda.get_device_name(0), "repeats": ARGS.reps, "launches_per_repeat": ARGS.iters,
+           "users_512": select_cells(lib, 512, 500, 10, 2), "users_1": select_cells(lib, 1, 500, 10, 2)}
+    print(json.dumps(res, indent=1))
+    if ARGS.out:
+        with open(ARGS.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
