@@ -4,7 +4,7 @@
 //   group_cap_compact : one workgroup of 512 per query, built like exclude_compact.  Thread t owns columns t, t + 512, ...;
 //            the columns' groups go to LDS (an unfilled column as -1, so that it is never counted), each thread decides its
 //            columns with below_group_cap and the survivors' output slots come from compact_slots - the two pieces the capped
-//            stage-2 selection (rows.hip) uses as well.  An unfilled column (position < 0) is never dropped and keeps its
+//            stage-2 selection (select.hip) uses as well.  An unfilled column (position < 0) is never dropped and keeps its
 //            place: behind every filled one, as the searches write them.  Slots past the last survivor get -1 / fill_score.
 #include "common.hpp"
 #include "topk_utils.hpp"

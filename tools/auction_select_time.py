@@ -1,11 +1,15 @@
-"""Dev tool: what the auction costs inside the stage-2 selection.  In ONE process, after a warm-up, alternating over REPS
-repeats (each a HIP-event pair around ITERS back-to-back launches, divided by ITERS), at 512 x 500 -> 10 and 1 x 500 -> 10:
-  amdrec_select_topk and amdrec_select_topk_capped (cap 2) - csrc/rows.hip, which the auction does not touch, so these are the
-  parent commit's kernels - against amdrec_select_topk_auction without a cap and with cap 2, both with a per-user reserve,
-  over bids and group keys of a million ads.
+"""Dev tool: what the stage-2 selection family (csrc/select.hip) costs.  In ONE process, after a warm-up, alternating over REPS
+repeats (each a HIP-event pair around ITERS back-to-back launches, divided by ITERS), on the wave shape (512 x 500 -> 10 and
+1 x 500 -> 10) and on the sort shape (512 x 2048 -> 100 and 1 x 2048 -> 100):
+  amdrec_select_topk and amdrec_select_topk_capped (cap 2) against amdrec_select_topk_auction without a cap and with cap 2,
+  both with a per-user reserve, over bids and group keys of a million ads.
+--parent-lib PATH loads a second build of the library (the parent commit's) next to this one: every cell then has a
+"<cell>_parent_build" neighbour that alternates with it, and "branch_over_parent" / "inside_parent_spread" per cell say whether
+this build's median lies within the parent's own spread above the parent's median.
 The spread is (max - min) / median over the repeats of one cell.
-usage: python tools/auction_select_time.py [--out FILE] [--reps R] [--iters N]"""
+usage: python tools/auction_select_time.py [--out FILE] [--parent-lib PATH] [--reps R] [--iters N]"""
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -13,6 +17,7 @@ import sys
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
+ap.add_argument("--parent-lib", default=None)
 ap.add_argument("--reps", type=int, default=9)
 ap.add_argument("--iters", type=int, default=50)
 ARGS = ap.parse_args()
@@ -50,7 +55,10 @@ def alternate(cells):
     return {name: stats(t) for name, t in times.items()}
 
 
-def select_cells(lib, users, k_c, top_k, cap, n_ads=1_000_000, n_groups=60):
+ENTRIES = ("amdrec_select_topk", "amdrec_select_topk_capped", "amdrec_select_topk_auction")
+
+
+def select_cells(lib, parent, users, k_c, top_k, cap, n_ads=1_000_000, n_groups=60):
     dev = "cuda"
     g = torch.Generator(device=dev)
     g.manual_seed(users + k_c)
@@ -68,13 +76,23 @@ def select_cells(lib, users, k_c, top_k, cap, n_ads=1_000_000, n_groups=60):
     outs = (_lib.ptr(ids), _lib.ptr(sc), None)
     bid = (_lib.ptr(bids), n_ads, _lib.ptr(reserve))
     tail = (_lib.ptr(ecpm), _lib.ptr(price), st)
-    cells = {
-        "select_topk": lambda: lib.amdrec_select_topk(*head, *outs, st),
-        "select_topk_capped": lambda: lib.amdrec_select_topk_capped(*head, *outs, _lib.ptr(groups), n_ads, cap, st),
-        "select_topk_auction": lambda: lib.amdrec_select_topk_auction(*head, *bid, None, 0, 0, *outs, *tail),
-        "select_topk_auction_capped": lambda: lib.amdrec_select_topk_auction(*head, *bid, _lib.ptr(groups), n_ads, cap, *outs, *tail),
-    }
+    def of(build):
+        return {
+            "select_topk": lambda: build.amdrec_select_topk(*head, *outs, st),
+            "select_topk_capped": lambda: build.amdrec_select_topk_capped(*head, *outs, _lib.ptr(groups), n_ads, cap, st),
+            "select_topk_auction": lambda: build.amdrec_select_topk_auction(*head, *bid, None, 0, 0, *outs, *tail),
+            "select_topk_auction_capped": lambda: build.amdrec_select_topk_auction(*head, *bid, _lib.ptr(groups), n_ads, cap, *outs, *tail),
+        }
+    cells = of(lib)
+    if parent is not None:                                            # each cell next to its parent-build neighbour
+        theirs = of(parent)
+        cells = {k: v for name in cells for k, v in ((name, cells[name]), (name + "_parent_build", theirs[name]))}
     res = alternate(cells)
+    if parent is not None:
+        for name in of(lib):
+            mine, base = res[name], res[name + "_parent_build"]
+            mine["branch_over_parent"] = round(mine["median_us"] / base["median_us"], 4)
+            mine["inside_parent_spread"] = mine["median_us"] <= base["median_us"] * (1 + base["spread"])
     res["auction_over_capped"] = round(res["select_topk_auction"]["median_us"] / res["select_topk_capped"]["median_us"], 3)
     res["auction_capped_over_capped"] = round(res["select_topk_auction_capped"]["median_us"] /
                                               res["select_topk_capped"]["median_us"], 3)
@@ -84,8 +102,17 @@ def select_cells(lib, users, k_c, top_k, cap, n_ads=1_000_000, n_groups=60):
 
 def main():
     lib = _lib.load()
+    parent = None
+    if ARGS.parent_lib:
+        parent = C.CDLL(os.path.abspath(ARGS.parent_lib))
+        for name in ENTRIES:
+            getattr(parent, name).argtypes = _lib._SIGNATURES[name]
+            getattr(parent, name).restype = C.c_int
     res = {"device": torch.cuda.get_device_name(0), "repeats": ARGS.reps, "launches_per_repeat": ARGS.iters,
-           "users_512": select_cells(lib, 512, 500, 10, 2), "users_1": select_cells(lib, 1, 500, 10, 2)}
+           "parent_build": bool(parent),
+           "users_512": select_cells(lib, parent, 512, 500, 10, 2), "users_1": select_cells(lib, parent, 1, 500, 10, 2),
+           "sort_users_512": select_cells(lib, parent, 512, 2048, 100, 2),
+           "sort_users_1": select_cells(lib, parent, 1, 2048, 100, 2)}
     print(json.dumps(res, indent=1))
     if ARGS.out:
         with open(ARGS.out, "w") as f:
