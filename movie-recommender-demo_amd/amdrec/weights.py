@@ -307,10 +307,82 @@ _X3_ORDER = {32: (x3_stream_gemm256, x3_stream_gemm256, x3_stream_ffn, x3_stream
              "16cs": (x3c_stream_gemm256, x3c_stream_gemm256, x3c_stream_ffn, x3c_stream_heads)}
 
 
+# ---- per-unit rebalancing of the hidden layers ------------------------------------------------------------------------
+# The engine has ONE power-of-two scale per weight matrix and ONE per row for a whole hidden tile, taken from the worst-case
+# bound of ``x3_hidden_bound``.  A hidden unit whose [w_j | b_j] lies many binades under the layer's largest therefore lands
+# in fp16 subnormals twice: its W_1 row under sw_1 and its hidden value under the bound - while its W_2 column, which a
+# trained net makes correspondingly large, sets sw_2 for everybody else.  relu(a t) / a == relu(t) exactly for a power of two
+# a, so such a unit is lifted at pack time: row j of W_1 and b_1[j] times 2^k, column j of W_2 divided by it.  A unit within
+# X3_REBALANCE_BINADES of the largest keeps the factor 1: i.i.d. weights pack to the bytes they always had.  The threshold
+# comes from the sweep in tests/test_x3_model_cpu.py (None: no rebalancing, the packing before it existed).
+X3_REBALANCE_BINADES = 4
+
+
+def _binade(v):
+    return np.floor(np.log2(v)).astype(np.int64)
+
+
+def _lifts_to(size: np.ndarray) -> np.ndarray:
+    """Per entry of ``size`` (>= 0) the power of two >= 1 that brings it to X3_REBALANCE_BINADES binades under the largest
+    (1.0 for entries that are there already, for zeros and non-finite sizes, and for all when rebalancing is off)."""
+    size = np.asarray(size, dtype=np.float64)
+    f = np.ones(size.shape)
+    ok = np.isfinite(size) & (size > 0)
+    if X3_REBALANCE_BINADES is None or not ok.any():
+        return f
+    f[ok] = 2.0 ** np.maximum(0, _binade(size[ok].max()) - X3_REBALANCE_BINADES - _binade(size[ok]))
+    return f
+
+
+def x3_unit_lifts(w1: np.ndarray, b1: np.ndarray) -> np.ndarray:
+    """Hidden layer W_1 [n][k], b_1 [n] -> the power of two per hidden unit by which its W_1 row and bias are multiplied
+    (and its W_2 column divided): units measured by ||[w_j | b_j]||_2."""
+    return _lifts_to(np.sqrt((np.asarray(w1, dtype=np.float64) ** 2).sum(axis=1) + np.asarray(b1, dtype=np.float64) ** 2))
+
+
+def _scaled(a, f):
+    return a if (f == 1.0).all() else a * f       # (the common case returns the very array)
+
+
+def x3_rebalance_heads(h1, hb1, h2):
+    """Stacked head layer 1 [T * n1][256], its bias, per task layer 2 [64][n1] -> (h1', hb1', h2', per-unit lifts of layer 1,
+    per-task lifts of layer 2).  Layer 1 per unit as in an FFN (all tasks share sw_h1 and one hidden bound, so a task whose
+    units are small as a whole is lifted as a whole); then a task whose layer 2 - after its columns took layer 1's lifts -
+    lies more than X3_REBALANCE_BINADES under the largest task's in max |w| is lifted as a whole under the shared sw_h2: its
+    b_2 goes with it and its w_3 (fp32, in the parameter blob) is divided."""
+    f1 = x3_unit_lifts(h1, hb1)
+    n1 = h1.shape[0] // len(h2)
+    h2 = [_scaled(w, 1.0 / f1[None, t * n1:(t + 1) * n1]) for t, w in enumerate(h2)]
+    f2 = _lifts_to(np.array([np.abs(w).max() for w in h2]))
+    return _scaled(h1, f1[:, None]), _scaled(hb1, f1), [_scaled(w, f) for w, f in zip(h2, f2)], f1, f2
+
+
+def x3_rebalance(mats: Dict):
+    """``mats`` of ``pack_x3_stream`` -> (the same network with every FFN's and the heads' hidden units rebalanced,
+    {"w1": per layer the unit lifts, "h1": the stacked head layer 1's, "h2": per task}).  Whatever else multiplies with
+    these hidden units takes the same factors: b_1 / head b_1, b_2 and w_3 in ``pack_x3_params`` and the rows of
+    ``first_ffn_cache``."""
+    lift = {"w1": [x3_unit_lifts(w, b) for w, b in zip(mats["w1"], mats["b1"])]}
+    out = dict(mats)
+    out["w1"] = [_scaled(w, f[:, None]) for w, f in zip(mats["w1"], lift["w1"])]
+    out["b1"] = [_scaled(b, f) for b, f in zip(mats["b1"], lift["w1"])]
+    out["w2"] = [_scaled(w, 1.0 / f[None, :]) for w, f in zip(mats["w2"], lift["w1"])]
+    out["h1"], out["hb1"], out["h2"], lift["h1"], lift["h2"] = x3_rebalance_heads(mats["h1"], mats["hb1"], mats["h2"])
+    return out, lift
+
+
+def x3_hidden_bound(w1: np.ndarray, b1: np.ndarray):
+    """(hn, hb) of amdrec_x3_weights: |relu(w_j . x + b_j)| <= ||w_j||_2 ||x||_2 + |b_j| <= (16 max_j ||w_j||_2) max|x| +
+    max_j |b_j| for 256-wide x."""
+    return float(16.0 * np.linalg.norm(w1, axis=1).max() * (1 + 1e-6)), float(np.abs(b1).max())
+
+
 def x3_split(mats: Dict, variant: int = 32, fold_first: bool = False):
     """Scale and plane-split every matrix of ``mats`` (see ``pack_x3_stream``) once -> (fragments {"ov", "w1", "w2", "cross":
-    lists, "h1", "h2", "tiles"}, scales and hidden bounds of amdrec_x3_weights).  Kinds 16 and "16cs" share the fragments of
-    variant 16.  ``fold_first``: layer 1's W_ov is not split (its fragments are None, its scale reads 1.0)."""
+    lists, "h1", "h2", "tiles"}, scales and hidden bounds of amdrec_x3_weights and "lift": the factors of ``x3_rebalance``,
+    which is applied first).  Kinds 16 and "16cs" share the fragments of variant 16.  ``fold_first``: layer 1's W_ov is not
+    split (its fragments are None, its scale reads 1.0)."""
+    mats, lift = x3_rebalance(mats)
     frags = x3_frags if variant == 32 else x3b_frags
     fr, sc = {"tiles": mats["h1"].shape[0] // len(mats["h2"]) // 32}, {}
     for name, dst in (("ov", "sw_ov"), ("w1", "sw_1"), ("w2", "sw_2"), ("cross", "sw_cross")):
@@ -320,10 +392,10 @@ def x3_split(mats: Dict, variant: int = 32, fold_first: bool = False):
     sc["sw_h1"] = x3_pow2_scale(np.abs(mats["h1"]).max())
     sc["sw_h2"] = x3_pow2_scale(max(np.abs(w).max() for w in mats["h2"]))
     fr["h1"], fr["h2"] = frags(mats["h1"], sc["sw_h1"]), [frags(w, sc["sw_h2"]) for w in mats["h2"]]
-    # |relu(w_j . x + b_j)| <= ||w_j||_2 ||x||_2 + |b_j| <= (16 max_j ||w_j||_2) max|x| + max_j |b_j|
-    hn = lambda w: float(16.0 * np.linalg.norm(w, axis=1).max() * (1 + 1e-6))     # noqa: E731
-    sc["hn"], sc["hb"] = [hn(w) for w in mats["w1"]], [float(np.abs(b).max()) for b in mats["b1"]]
-    sc["hn_head"], sc["hb_head"] = hn(mats["h1"]), float(np.abs(mats["hb1"]).max())
+    bounds = [x3_hidden_bound(w, b) for w, b in zip(mats["w1"], mats["b1"])]
+    sc["hn"], sc["hb"] = [n for n, _ in bounds], [b for _, b in bounds]
+    sc["hn_head"], sc["hb_head"] = x3_hidden_bound(mats["h1"], mats["hb1"])
+    sc["lift"] = lift
     return fr, sc
 
 
@@ -363,8 +435,9 @@ def x3_ctr_first_orders(n_tasks: int, column_split: bool, cache_first_ffn: bool)
 def pack_x3_stream(mats: Dict, variant: int = 32, fold_first: bool = False, cache_first_ffn: bool = False) -> Dict:
     """mats: float64 matrices of the chain {"ov": [L x [256][256]], "w1": [L x [d_ff][256]], "b1": [L x [d_ff]], "w2":
     [L x [256][d_ff]], "cross": [C x [256][256] (already [out][in])], "h1": [T*h1][256], "hb1": [T*h1], "h2": [T x
-    [64][h1]]} -> {"stream": uint16 [n_frag][64][8], "chunks", scales and hidden bounds} for amdrec_x3_weights: one
-    ``x3_split`` in one ``x3_order`` (pack_ranker orders ONE split up to three ways).
+    [64][h1]]} -> {"stream": uint16 [n_frag][64][8], "chunks", scales and hidden bounds, "lift"} for amdrec_x3_weights: one
+    ``x3_split`` in one ``x3_order`` (pack_ranker orders ONE split up to three ways).  "lift": the factors of
+    ``x3_rebalance`` that the caller's parameter blob has to carry too.
     ``fold_first``: layer 1's attention block is folded into the projection (amdrec_x3_weights.fold_attn1): its W_ov is
     not packed (mats["ov"][0] is not read; its scale reads 1.0).  ``cache_first_ffn`` (variant 16 with ``fold_first``):
     layer 1's stage-1 fragment sets are left out too (amdrec_x3_weights.stream_hc); every scale and bound stays."""
@@ -563,7 +636,7 @@ def folded_projection(sd: Dict):
     return ch.w_proj + L["wov"] @ ch.w_proj, ch.b_proj + L["wov"] @ ch.b_proj + L["b_ov"]
 
 
-def first_ffn_cache(sd: Dict, n_user_cols: int, n_ad_cols: int, ln_eps: float = 1e-5, folded=None) -> Dict:
+def first_ffn_cache(sd: Dict, n_user_cols: int, n_ad_cols: int, ln_eps: float = 1e-5, folded=None, lift=None) -> Dict:
     """float64 algebra of the first-FFN hidden cache (amdrec_x3_weights.stream_hc).  With layer 1's attention folded the
     chain starts with x1 = LN1(z), z = a_ad + u_user (the two halves of ``folded_projection``), and stage 1 of layer 1's
     FFN is linear in z once the row's deviation is known:
@@ -575,7 +648,9 @@ def first_ffn_cache(sd: Dict, n_user_cols: int, n_ad_cols: int, ln_eps: float = 
     -> {"w1c", "c", "w_ad" = W_1c W_p'[:, ad columns], "w_user" = W_1c W_p'[:, user | numerical columns],
         "b" = W_1c b_p'}: the stacked matrices produce P[ad] = w_ad . emb(ad) and Q[user] = w_user . f_user + b straight
     from the embeddings, composed in float64 (no second fp32 rounding through the cached a_ad).
-    ``folded``: the ``folded_projection`` where the caller already has it."""
+    ``folded``: the ``folded_projection`` where the caller already has it.  ``lift``: layer 1's unit lifts of
+    ``x3_rebalance`` [d_ff] - every row of the result is a hidden unit's and is multiplied with its power of two (exact), so
+    that rstd * (P + Q) + c is the lifted hidden value the stream's W_2 columns were divided for."""
     ch = ranker_chain(sd)
     L = ch.layers[0]
     w1 = L["w1"].astype(np.float32).astype(np.float64)
@@ -583,7 +658,10 @@ def first_ffn_cache(sd: Dict, n_user_cols: int, n_ad_cols: int, ln_eps: float = 
     w1c = w1g - w1g.mean(axis=1, keepdims=True)
     wp, bp = folded_projection(ch) if folded is None else folded
     w_user, w_ad = _user_ad_columns(wp, n_user_cols, n_ad_cols)
-    return {"w1c": w1c, "c": w1 @ L["be1"] + L["b1"], "w_ad": w1c @ w_ad, "w_user": w1c @ w_user, "b": w1c @ bp, "ln_eps": ln_eps}
+    hc = {"w1c": w1c, "c": w1 @ L["be1"] + L["b1"], "w_ad": w1c @ w_ad, "w_user": w1c @ w_user, "b": w1c @ bp}
+    if lift is not None:
+        hc = {k: _scaled(v, lift if v.ndim == 1 else lift[:, None]) for k, v in hc.items()}
+    return {**hc, "ln_eps": ln_eps}
 
 
 def _pack_encoder_layer(L, pk: Packed, c: Dict, fuse_attention: bool, x6: bool):
@@ -616,14 +694,18 @@ def _pack_x3(p: RankerParams, pk: Packed, ch: RankerChain, wproj, bproj, nu: int
     def stream(kind, **kw):
         s = x3_order(fr, kind, **kw)
         return pk.ptr(s.view(np.int16)), s.shape[0] // 16
-    blob = pack_x3_params(ch.layers, ch.cross_b, ch.head_b1, ch.heads, fold_first=fold)
+    # the parameters that multiply with rebalanced hidden units take the units' factors (``x3_rebalance``)
+    lift = sc["lift"]
+    layers = [dict(L, b1=_scaled(L["b1"], f)) for L, f in zip(ch.layers, lift["w1"])]
+    heads = [dict(h, b2=_scaled(h["b2"], f), w3=_scaled(h["w3"], 1.0 / f)) for h, f in zip(ch.heads, lift["h2"])]
+    blob = pack_x3_params(layers, ch.cross_b, _scaled(ch.head_b1, lift["h1"]), heads, fold_first=fold)
     assert len(blob) <= X3_PARAM_FLOATS
     p.x3.params, p.x3.n_params = pk.ptr(blob), len(blob)
     p.x3.stream, p.x3.chunks = stream(p.x3.variant)
     if p.x3.cs_max_rows >= 0 and x3c_available(p):
         p.x3.stream_cs, p.x3.chunks_cs = stream("16cs")         # the same fragments in the column-split kernel's chunk order
     if cache_first_ffn and x3_hidden_cache(p):
-        hc = first_ffn_cache(ch, nu, na, folded=(wproj, bproj))
+        hc = first_ffn_cache(ch, nu, na, folded=(wproj, bproj), lift=lift["w1"][0])
         p.x3.stream_hc, p.x3.chunks_hc = stream(16, cache_first_ffn=True)
         blob_hc = blob.copy()                                   # folded layout: [gamma1 | beta1 | b_1 ...] - c in b_1's place
         blob_hc[512:512 + len(hc["c"])] = hc["c"].astype(np.float32)
