@@ -11,8 +11,8 @@
 namespace amdrec {
 namespace AMDREC_X3B_NAMESPACE {
 
-using x3::CHUNK_BYTES, x3::CHUNK_FRAGS, x3::DBG, x3::DEPTH, x3::f16x8, x3::FRAG_BYTES, x3::Input, x3::lds_byte, x3::lds_cfloat,
-    x3::NBUF, x3::Phase, x3::Program, x3::RING_BYTES;
+using x3::CHUNK_BYTES, x3::CHUNK_FRAGS, x3::DBG, x3::f16x8, x3::FRAG_BYTES, x3::Input, x3::lds_byte, x3::lds_cfloat, x3::Phase,
+    x3::Program, x3::RING_BYTES;
 using x16::add_rows, x16::group6, x16::hidden_planes, x16::init_pair, x16::layer_norm, x16::layer_norm_scaled, x16::load_rows,
     x16::param4, x16::prepare, x16::reduce_sum4, x16::row_scale, x16::split8, x16::store_rows;
 
@@ -21,6 +21,13 @@ using x16::add_rows, x16::group6, x16::hidden_planes, x16::init_pair, x16::layer
 #endif
 constexpr int WAVES = AMDREC_X3B_WAVES, ROWS_PER_WAVE = 16, ROWS_PER_WG = WAVES * ROWS_PER_WAVE;
 constexpr int DMA_PER_WAVE = CHUNK_FRAGS / WAVES;     // 2 fragment sets per wave and chunk
+// The 128-row shape runs PH_FFN_LN split by STAGE over pairs of waves (phase_ffn_ln_role_a, phase_ffn_ln_role_b below).  Its hand-off area is
+// the ring's last slot: the ring is one chunk shorter there (NBUF 6 and 7 measured the same,
+// profiles/x3_paired_ffn_bound.log), the parameter blob stays where it is and the host's LDS size does not change.
+// (DBG & 256 / 512: the unpaired phase with its elimination switches, on the unshortened ring.)
+constexpr bool PAIRED = WAVES == 8 && !(DBG & (256 | 512));
+constexpr int NBUF = PAIRED ? x3::NBUF - 1 : x3::NBUF, DEPTH = NBUF - 3;
+constexpr int PAIR_BYTES = CHUNK_BYTES / 4;           // per pair of waves: 4 KB = four 16-byte pieces per lane
 // A chunk's DMA pieces are issued behind the fragment reads of this group of the chunk in front of it (not at the chunk's
 // barrier, group 0): the matrix pipe has the first group's MFMAs queued while the waves of a SIMD sit in the
 // memory-instruction issue.
@@ -115,17 +122,21 @@ struct Ring {
     // wrap-around, barrier, DMA) runs once per chunk instead of the per-group address arithmetic and boundary test.
     // Group 0 certifies the chunk after this one and moves to this chunk's slot; group DMA_GROUP refills a free slot
     // (chunk + DEPTH + 1 into the slot of chunk - 2, which every wave has left).
-    template <int G, int EXTRA = 0>
-    __device__ __forceinline__ void read4(f16x8 (&f)[4]) {
+    // the chunk's barrier: certify the chunk after this one, move to this chunk's slot
+    template <int EXTRA = 0>
+    __device__ __forceinline__ void advance() {
+        certify_next<EXTRA>();
+        slot = slot + 1 == NBUF ? 0 : slot + 1;
+        cbase = lds_rd + (uint32_t)slot * CHUNK_BYTES;
+    }
+    // HALF (PH_FFN_LN, diagnostic build only, DBG & 256 / 512): no reads for the odd groups - the stage-2 groups there
+    template <int G, bool HALF = false>
+    __device__ __forceinline__ void frag4(f16x8 (&f)[4]) {
         static_assert(G >= 0 && G < 4 && CHUNK_FRAGS == 16, "four groups of four fragment sets per chunk");
-        if (G == 0) {
-            certify_next<EXTRA>();
-            slot = slot + 1 == NBUF ? 0 : slot + 1;
-            cbase = lds_rd + (uint32_t)slot * CHUNK_BYTES;
-        }
         // DBG & 64 (diagnostic build only): fragment reads for ONE group in four - the LDS -> VGPR traffic a kernel would
         // have in which a fragment set feeds four row tiles (the hybrid row-tile-owner / column-split proposal)
-        if ((DBG & 4) || ((DBG & 64) && G != 0) || ((DBG & 128) && (G & 1))) {       // 128: one group in TWO (pairs of waves sharing)
+        if ((DBG & 4) || ((DBG & 64) && G != 0) || ((DBG & 128) && (G & 1)) ||        // 128: one group in TWO (pairs of waves sharing)
+            (HALF && (DBG & (256 | 512)) && (G & 1))) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) asm volatile("" : "+v"(f[u]));
         } else {
@@ -133,6 +144,11 @@ struct Ring {
             for (int u = 0; u < 4; ++u)
                 f[u] = *reinterpret_cast<const __attribute__((address_space(3))) f16x8*>(cbase + (4 * G + u) * FRAG_BYTES);
         }
+    }
+    template <int G, int EXTRA = 0, bool HALF = false>
+    __device__ __forceinline__ void read4(f16x8 (&f)[4]) {
+        if (G == 0) advance<EXTRA>();
+        frag4<G, HALF>(f);
         if (G == DMA_GROUP) issue();
     }
     __device__ __forceinline__ void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
@@ -169,29 +185,34 @@ __device__ __forceinline__ void phase_attn_ln(Ring& ring, const Phase& P, f32x4 
     layer_norm_scaled(acc, inv / P.sw1, x, pb, P.gamma, P.beta, P.ln_eps);
 }
 
-template <bool S1, bool S2, int GI, int EXTRA = 0>
+template <bool S1, bool S2, int GI, int EXTRA = 0, bool HALF = false>
 __device__ __forceinline__ void ffn_groups(Ring& ring, f16x8 (&cur)[4], const f16x8 (&xh)[8], const f16x8 (&xl)[8],
                                            f32x4& a10, f32x4& a11, f32x4 (&acc2)[16], const f16x8& hh, const f16x8& hl) {
     constexpr int NG = (S1 ? 8 : 0) + (S2 ? 8 : 0);          // groups in this step (a multiple of 4: whole chunks)
     constexpr bool is1 = S1 && (!S2 || (GI & 1) == 0);
     constexpr int u = (S1 && S2) ? GI >> 1 : GI;
     f16x8 nxt[4];
-    if constexpr (GI < NG - 1) ring.read4<(GI + 1) & 3, EXTRA>(nxt);
+    if constexpr (GI < NG - 1) ring.read4<(GI + 1) & 3, EXTRA, HALF>(nxt);
     ring.timed_landed(cur);
     if constexpr (is1) group6(cur, xh[u], xl[u], a10, a11);
     else group6(cur, hh, hl, acc2[2 * u], acc2[2 * u + 1]);
-    if constexpr (GI < NG - 1) ffn_groups<S1, S2, GI + 1, EXTRA>(ring, nxt, xh, xl, a10, a11, acc2, hh, hl);
+    if constexpr (GI < NG - 1) ffn_groups<S1, S2, GI + 1, EXTRA, HALF>(ring, nxt, xh, xl, a10, a11, acc2, hh, hl);
 }
 
 // One FFN step: 8 x { stage-1 group (W_1 tiles 2t, 2t+1 at ks = u), stage-2 group (W_2 tiles 2u, 2u+1 at k-step t-1) }
-template <bool S1, bool S2, int EXTRA = 0>
+template <bool S1, bool S2, int EXTRA = 0, bool HALF = false>
 __device__ __forceinline__ void ffn_step(Ring& ring, const f16x8 (&xh)[8], const f16x8 (&xl)[8], f32x4& a10, f32x4& a11,
                                          f32x4 (&acc2)[16], const f16x8& hh, const f16x8& hl) {
     f16x8 cur[4];
-    ring.read4<0, EXTRA>(cur);
-    ffn_groups<S1, S2, 0, EXTRA>(ring, cur, xh, xl, a10, a11, acc2, hh, hl);
+    ring.read4<0, EXTRA, HALF>(cur);
+    ffn_groups<S1, S2, 0, EXTRA, HALF>(ring, cur, xh, xl, a10, a11, acc2, hh, hl);
 }
 
+// (diagnostic build only, DBG & 512: PH_FFN_LN without its hidden-tile conversions - stale planes)
+__device__ __forceinline__ void ffn_hidden(const f32x4& a0, const f32x4& a1, float c, float lim, f16x8& hh, f16x8& hl) {
+    if (DBG & 512) asm volatile("" : "+v"(hh), "+v"(hl) : "v"(a0), "v"(a1));
+    else hidden_planes(a0, a1, c, lim, hh, hl);
+}
 __device__ __forceinline__ void phase_ffn_ln(Ring& ring, const Phase& P, f32x4 (&x)[16], lds_cfloat* pb) {
     float s, inv;
     row_scale(x, s, inv);
@@ -203,15 +224,257 @@ __device__ __forceinline__ void phase_ffn_ln(Ring& ring, const Phase& P, f32x4 (
     f32x4 a10, a11;
     f16x8 hh, hl;
     init_pair(a10, a11, pb, P.b1, 0, b1s);
-    ffn_step<true, false>(ring, xh, xl, a10, a11, acc2, hh, hl);
+    ffn_step<true, false, 0, true>(ring, xh, xl, a10, a11, acc2, hh, hl);
     for (int t = 1; t < P.n_steps; ++t) {
-        hidden_planes(a10, a11, c1, lim1, hh, hl);
+        ffn_hidden(a10, a11, c1, lim1, hh, hl);
         init_pair(a10, a11, pb, P.b1, 2 * t, b1s);
-        ffn_step<true, true>(ring, xh, xl, a10, a11, acc2, hh, hl);
+        ffn_step<true, true, 0, true>(ring, xh, xl, a10, a11, acc2, hh, hl);
     }
-    hidden_planes(a10, a11, c1, lim1, hh, hl);
-    ffn_step<false, true>(ring, xh, xl, a10, a11, acc2, hh, hl);
+    ffn_hidden(a10, a11, c1, lim1, hh, hl);
+    ffn_step<false, true, 0, true>(ring, xh, xl, a10, a11, acc2, hh, hl);
     layer_norm_scaled(acc2, 1.0f / (P.sw2 * sh), x, pb, P.gamma, P.beta, P.ln_eps);
+}
+
+// ---- PH_FFN_LN split by STAGE over pairs of waves (the 128-row shape) ----
+// Waves w ("role A") and w + 4 ("role B") share a SIMD and form a pair; tile 0 is A's 16 rows, tile 1 B's.  A holds the x
+// planes of BOTH tiles and runs every stage-1 group against both; B holds the stage-2 accumulators of both tiles and runs
+// every stage-2 group against both: a fragment set read from LDS feeds 12 MFMAs instead of 6, every wave reads the
+// fragments of half the groups (the stream alternates stage-1 and stage-2 groups: A reads groups 0 and 2 of a chunk, B 1
+// and 3), and the two waves of a SIMD no longer convert their hidden tiles at the same moment (pair_publish).
+// Every output element sees the MFMAs it sees in phase_ffn_ln, in the same order and scaled alike: results are bit-identical.
+//  * hidden tiles: A writes the planes of its tile and the finished accumulators of B's (4 x 16 bytes per lane: the
+//    accumulator layout IS the B-operand layout, so lane l writes what lane l of B reads) into the pair's area, waits lgkmcnt(0) and passes the next chunk's barrier
+//    (Ring::advance); B reads them behind that barrier.  One buffer is enough: B's reads have landed before the MFMAs of
+//    its first group, i.e. before its next barrier, and A writes again three barriers later.
+//  * phase entry / exit: B's planes and stage-1 bias scale go to A, A's initial stage-2 accumulator and hidden scale to B, and at
+//    the end A's LayerNorm output comes back - 16 KB each through the 4 KB area, in slices of { write, wait, barrier, read,
+//    wait, barrier }: 18 barriers at entry, 8 at exit, beside the phase's 4 n_steps.
+//  * workgroup barriers only, and both roles pass the same number on every path: a role without groups in a step (B in the
+//    first, A in the last) still passes every chunk's barrier and issues its DMA pieces.
+template <int K, class V>
+__device__ __forceinline__ void pair_put(lds_byte* box, const V& v) {
+    static_assert(sizeof(V) == 16 && K >= 0 && K < PAIR_BYTES / FRAG_BYTES, "a 16-byte piece per lane");
+    *reinterpret_cast<__attribute__((address_space(3))) V*>(box + K * FRAG_BYTES) = v;
+}
+template <int K, class V>
+__device__ __forceinline__ void pair_get(const lds_byte* box, V& v) {
+    static_assert(sizeof(V) == 16 && K >= 0 && K < PAIR_BYTES / FRAG_BYTES, "a 16-byte piece per lane");
+    v = *reinterpret_cast<const __attribute__((address_space(3))) V*>(box + K * FRAG_BYTES);
+}
+__device__ __forceinline__ void pair_landed() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+__device__ __forceinline__ void pair_sync() {        // my accesses to the area are done; everyone's behind the barrier
+    pair_landed();
+    __builtin_amdgcn_s_barrier();
+}
+// one fragment set against one B k-step of both tiles: per accumulator the MFMAs of group6, in its order
+__device__ __forceinline__ void group12(const f16x8 (&a)[4], const f16x8& bh0, const f16x8& bl0, const f16x8& bh1,
+                                        const f16x8& bl1, f32x4& c00, f32x4& c01, f32x4& c10, f32x4& c11) {
+    c00 = x16::mfma(a[0], bl0, c00);
+    c01 = x16::mfma(a[2], bl0, c01);
+    c10 = x16::mfma(a[0], bl1, c10);
+    c11 = x16::mfma(a[2], bl1, c11);
+    c00 = x16::mfma(a[1], bh0, c00);
+    c01 = x16::mfma(a[3], bh0, c01);
+    c10 = x16::mfma(a[1], bh1, c10);
+    c11 = x16::mfma(a[3], bh1, c11);
+    c00 = x16::mfma(a[0], bh0, c00);
+    c01 = x16::mfma(a[2], bh0, c01);
+    c10 = x16::mfma(a[0], bh1, c10);
+    c11 = x16::mfma(a[2], bh1, c11);
+}
+// A role's J-th group of a step.  MODE 0: a single-stage step, all four groups of its 2 chunks are this role's;
+// MODE 1: role A in a full step (groups 0 and 2 of its 4 chunks); MODE 2: role B there (groups 1 and 3).
+// The role's first group of a chunk passes the chunk's barrier, one of its groups issues the wave's DMA pieces.
+template <int MODE, int J>
+__device__ __forceinline__ void pair_read(Ring& ring, f16x8 (&f)[4]) {
+    constexpr int G = MODE == 0 ? (J & 3) : 2 * (J & 1) + (MODE == 2 ? 1 : 0);
+    if constexpr (G == (MODE == 2 ? 1 : 0)) ring.advance();
+    ring.frag4<G>(f);
+    if constexpr (G == (MODE == 1 ? 2 : DMA_GROUP)) ring.issue();
+}
+template <int MODE, int J>
+__device__ __forceinline__ void pair_groups1(Ring& ring, f16x8 (&cur)[4], const f16x8 (&xh)[2][8], const f16x8 (&xl)[2][8],
+                                             f32x4 (&a)[2][2]) {
+    f16x8 nxt[4];
+    if constexpr (J < 7) pair_read<MODE, J + 1>(ring, nxt);
+    ring.timed_landed(cur);
+    group12(cur, xh[0][J], xl[0][J], xh[1][J], xl[1][J], a[0][0], a[0][1], a[1][0], a[1][1]);
+    if constexpr (J < 7) pair_groups1<MODE, J + 1>(ring, nxt, xh, xl, a);
+}
+template <int MODE, int J>
+__device__ __forceinline__ void pair_groups2(Ring& ring, f16x8 (&cur)[4], const f16x8 (&hh)[2], const f16x8 (&hl)[2],
+                                             f32x4 (&acc2)[2][16]) {
+    f16x8 nxt[4];
+    if constexpr (J < 7) pair_read<MODE, J + 1>(ring, nxt);
+    ring.timed_landed(cur);
+    group12(cur, hh[0], hl[0], hh[1], hl[1], acc2[0][2 * J], acc2[0][2 * J + 1], acc2[1][2 * J], acc2[1][2 * J + 1]);
+    if constexpr (J < 7) pair_groups2<MODE, J + 1>(ring, nxt, hh, hl, acc2);
+}
+// the 2 chunks of a single-stage step for the role without groups in it
+__device__ __forceinline__ void pair_idle_step(Ring& ring) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        ring.advance();
+        ring.issue();
+    }
+}
+
+// A: the finished hidden tile goes to the pair's area - its own tile's as planes, B's tile's as the two accumulators it
+// is (B converts that one: each wave converts one tile per step, as in the unpaired phase, but not at the same time - A in
+// front of the barrier, under B's last MFMAs of the step, B behind it, under A's first); the next chunk's barrier hands
+// them to B
+__device__ __forceinline__ void pair_publish(const f32x4 (&a)[2][2], float c1, float lim1, lds_byte* box) {
+    f16x8 hh, hl;
+    hidden_planes(a[0][0], a[0][1], c1, lim1, hh, hl);
+    pair_put<0>(box, hh);
+    pair_put<1>(box, hl);
+    pair_put<2>(box, a[1][0]);
+    pair_put<3>(box, a[1][1]);
+    pair_landed();
+}
+// B, behind a step's first barrier: what A published in front of it
+__device__ __forceinline__ void pair_fetch(const lds_byte* box, float c1, float lim1, f16x8 (&hh)[2], f16x8 (&hl)[2]) {
+    f32x4 a0, a1;
+    pair_get<0>(box, hh[0]);
+    pair_get<1>(box, hl[0]);
+    pair_get<2>(box, a0);
+    pair_get<3>(box, a1);
+    hidden_planes(a0, a1, c1, lim1, hh[1], hl[1]);
+}
+
+__device__ __forceinline__ void phase_ffn_ln_role_a(Ring& ring, const Phase& P, f32x4 (&x)[16], lds_cfloat* pb, lds_byte* box) {
+    float s, inv;
+    row_scale(x, s, inv);
+    const float sh = x3::hidden_scale(fmaf(P.hn * 8192.0f, inv, P.hb));
+    float b1s[2];
+    b1s[0] = s * P.sw1;
+    const float c1 = sh * inv / P.sw1, lim1 = 60000.f / c1;
+    f16x8 xh[2][8], xl[2][8];
+    {
+        f32x4 acc2[16];
+        prepare<true>(x, s, pb, P.b2, P.sw2 * sh, xh[0], xl[0], acc2);
+        // pieces 0, 1: B -> A; pieces 2, 3: A -> B
+        f32x4 sc = {P.sw2 * sh, 0.f, 0.f, 0.f};
+        if (DBG & 1024) {           // diagnostic build only: no exchange at the phase's ends (its cost by difference)
+            sc[0] = b1s[0];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                asm volatile("" ::"v"(acc2[2 * i]), "v"(acc2[2 * i + 1]));
+                xh[1][i] = xh[0][i], xl[1][i] = xl[0][i];
+                asm volatile("" : "+v"(xh[1][i]), "+v"(xl[1][i]));
+            }
+        } else {
+            pair_put<2>(box, sc);
+            pair_sync();
+            pair_get<0>(box, sc);
+            pair_sync();
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                pair_put<2>(box, acc2[2 * i]);
+                pair_put<3>(box, acc2[2 * i + 1]);
+                pair_sync();
+                pair_get<0>(box, xh[1][i]);
+                pair_get<1>(box, xl[1][i]);
+                pair_sync();
+            }
+        }
+        b1s[1] = sc[0];
+    }
+    f32x4 a[2][2];
+    f16x8 cur[4];
+    init_pair(a[0][0], a[0][1], pb, P.b1, 0, b1s[0]);
+    init_pair(a[1][0], a[1][1], pb, P.b1, 0, b1s[1]);
+    pair_read<0, 0>(ring, cur);
+    pair_groups1<0, 0>(ring, cur, xh, xl, a);
+    for (int t = 1; t < P.n_steps; ++t) {
+        pair_publish(a, c1, lim1, box);         // tile t - 1
+        init_pair(a[0][0], a[0][1], pb, P.b1, 2 * t, b1s[0]);
+        init_pair(a[1][0], a[1][1], pb, P.b1, 2 * t, b1s[1]);
+        pair_read<1, 0>(ring, cur);
+        pair_groups1<1, 0>(ring, cur, xh, xl, a);
+    }
+    pair_publish(a, c1, lim1, box);
+    pair_idle_step(ring);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (DBG & 1024) {
+            asm volatile("" : "+v"(x[4 * k]), "+v"(x[4 * k + 1]), "+v"(x[4 * k + 2]), "+v"(x[4 * k + 3]));
+            continue;
+        }
+        pair_sync();
+        pair_get<0>(box, x[4 * k]);
+        pair_get<1>(box, x[4 * k + 1]);
+        pair_get<2>(box, x[4 * k + 2]);
+        pair_get<3>(box, x[4 * k + 3]);
+        pair_sync();
+    }
+}
+
+__device__ __forceinline__ void phase_ffn_ln_role_b(Ring& ring, const Phase& P, f32x4 (&x)[16], lds_cfloat* pb, lds_byte* box) {
+    float s, inv;
+    row_scale(x, s, inv);
+    const float sh = x3::hidden_scale(fmaf(P.hn * 8192.0f, inv, P.hb));
+    float k2[2];
+    k2[1] = P.sw2 * sh;
+    const float c1 = sh * inv / P.sw1, lim1 = 60000.f / c1;
+    f32x4 acc2[2][16];
+    {
+        f16x8 xh[8], xl[8];
+        prepare<true>(x, s, pb, P.b2, k2[1], xh, xl, acc2[1]);
+        f32x4 sc = {s * P.sw1, 0.f, 0.f, 0.f};
+        if (DBG & 1024) {
+            sc[0] = k2[1];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                asm volatile("" ::"v"(xh[i]), "v"(xl[i]));
+                acc2[0][2 * i] = acc2[1][2 * i], acc2[0][2 * i + 1] = acc2[1][2 * i + 1];
+                asm volatile("" : "+v"(acc2[0][2 * i]), "+v"(acc2[0][2 * i + 1]));
+            }
+        } else {
+            pair_put<0>(box, sc);
+            pair_sync();
+            pair_get<2>(box, sc);
+            pair_sync();
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                pair_put<0>(box, xh[i]);
+                pair_put<1>(box, xl[i]);
+                pair_sync();
+                pair_get<2>(box, acc2[0][2 * i]);
+                pair_get<3>(box, acc2[0][2 * i + 1]);
+                pair_sync();
+            }
+        }
+        k2[0] = sc[0];
+    }
+    pair_idle_step(ring);
+    f16x8 hh[2], hl[2], cur[4];
+    for (int t = 1; t < P.n_steps; ++t) {
+        pair_read<2, 0>(ring, cur);
+        pair_fetch(box, c1, lim1, hh, hl);                // tile t - 1
+        pair_groups2<2, 0>(ring, cur, hh, hl, acc2);
+    }
+    pair_read<0, 0>(ring, cur);
+    pair_fetch(box, c1, lim1, hh, hl);
+    pair_groups2<0, 0>(ring, cur, hh, hl, acc2);
+    {
+        f32x4 y[16];
+        layer_norm_scaled(acc2[0], 1.0f / k2[0], y, pb, P.gamma, P.beta, P.ln_eps);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (DBG & 1024) {
+                asm volatile("" ::"v"(y[4 * k]), "v"(y[4 * k + 1]), "v"(y[4 * k + 2]), "v"(y[4 * k + 3]));
+                continue;
+            }
+            pair_put<0>(box, y[4 * k]);
+            pair_put<1>(box, y[4 * k + 1]);
+            pair_put<2>(box, y[4 * k + 2]);
+            pair_put<3>(box, y[4 * k + 3]);
+            pair_sync();
+            pair_sync();
+        }
+    }
+    layer_norm_scaled(acc2[1], 1.0f / k2[1], x, pb, P.gamma, P.beta, P.ln_eps);
 }
 
 // ---- PH_FFN_LN_CACHED: layer 1's FFN with stage 1 from the hidden cache (amdrec_x3_weights.stream_hc) ----
@@ -443,7 +706,15 @@ __device__ __forceinline__ void run_chain(const Program& G, const Input& in, lon
         const Phase& P = G.ph[p];
         const int type = __builtin_amdgcn_readfirstlane(P.type);
         if (type == x3::PH_ATTN_LN) phase_attn_ln(ring, P, x, pb);
-        else if (type == x3::PH_FFN_LN) phase_ffn_ln(ring, P, x, pb);
+        else if (type == x3::PH_FFN_LN) {
+            if constexpr (PAIRED) {
+                lds_byte* box = (lds_byte*)smem + NBUF * CHUNK_BYTES + (wave & 3) * PAIR_BYTES + lane * 16;
+                if (wave < 4) phase_ffn_ln_role_a(ring, P, x, pb, box);
+                else phase_ffn_ln_role_b(ring, P, x, pb, box);
+            } else {
+                phase_ffn_ln(ring, P, x, pb);
+            }
+        }
         else if (type == x3::PH_LN) rstd = layer_norm(x, pb, P.gamma, P.beta, P.ln_eps);     // folded layer-1 attention
         else if (WAVES == 8 && type == x3::PH_FFN_LN_CACHED) {                         // the 128-row shape only (x3_build)
             if constexpr (WAVES == 8) {

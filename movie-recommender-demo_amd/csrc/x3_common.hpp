@@ -44,7 +44,8 @@ constexpr int CHUNK_BYTES = CHUNK_FRAGS * FRAG_BYTES;
 #ifndef AMDREC_X3_NBUF
 #define AMDREC_X3_NBUF 7
 #endif
-constexpr int NBUF = AMDREC_X3_NBUF;             // ring chunks (7 x 16 KB = 112 KB; 6, 8 and 9 measured the same)
+constexpr int NBUF = AMDREC_X3_NBUF;             // ring chunks (7 x 16 KB = 112 KB; 6, 8 and 9 measured the same; the 16-row kernel's
+                                                 // 128-row shape runs on NBUF - 1 and hands hidden tiles over in the last slot)
 constexpr int PARAM_FLOATS = 11264;              // LDS parameter area behind the ring: 44 KB (the reference architecture needs 41.5)
 constexpr int RING_BYTES = NBUF * CHUNK_BYTES;
 constexpr int DEPTH = NBUF - 3;                  // chunks in flight beyond the certified one (NBUF >= DEPTH + 3)
@@ -125,7 +126,10 @@ __device__ __forceinline__ long long dense_row(const Input& in, long long r) {
 // Elimination switches for tools/x3_probe.hip (0 in the product): 1 = no weight DMA and no wait for it, 2 = no
 // per-chunk barrier, 4 = no fragment reads from LDS (stale registers), 8 = no hidden-tile conversion (stale planes);
 // 16-row kernels only: 16 = cycle stamps (DMA wait / barrier) per wave into the logits buffer's tail, 32 (with 16) =
-// stamps of the waits for a group's fragments instead, 64 / 128 = fragment reads for one group in four / in two.
+// stamps of the waits for a group's fragments instead, 64 / 128 = fragment reads for one group in four / in two;
+// 128-row shape of the 16-row kernel only (rowowner16_impl.hpp, profiles/x3_paired_ffn_bound.log): 256 = PH_FFN_LN as the
+// UNPAIRED phase on the 7-slot ring, without the fragment reads of its odd groups, 512 = that and without its hidden-tile
+// conversions (the two bound the paired phase from below), 1024 = the paired phase without the exchanges at its ends.
 #ifndef AMDREC_X3_DBG
 #define AMDREC_X3_DBG 0
 #endif
