@@ -66,6 +66,13 @@ __device__ __forceinline__ float sumsq4(const f32x4& v) {
     return __builtin_fmaf(v[3], v[3], __builtin_fmaf(v[2], v[2], __builtin_fmaf(v[1], v[1], v[0] * v[0])));
 }
 
+// ReLU that keeps a NaN, as torch.relu does (fmaxf alone returns its other operand, 0): a row with a NaN feature then leaves a
+// tower as a NaN embedding, which the search answers with an empty candidate list, and a ranker as NaN logits, instead of as
+// the output of an all-zero hidden layer.  Every other value, -0.0 included, gives what fmaxf(v, 0) gives.  Used by every
+// Linear+ReLU epilogue (tower_small.hip, layers.hip EpiLinearT); the row-owner ranker kernels keep their one-instruction
+// ReLUs and restore the NaN per row at the logit store (x3_common.hpp keep_nan).
+__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+
 // the probability the stage-2 entries report for a logit (amdrec_select_topk, amdrec_ranker_winner_heads): ONE expression, so
 // that a task's score does not depend on which of them wrote it
 __device__ __forceinline__ float sigmoid_prob(float x) { return 1.0f / (1.0f + expf(-x)); }

@@ -135,7 +135,7 @@ struct EpiLinearT : LinearArgs, EpiTiled {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float x = acc.v[i][j][4 * g + e] + b[g][e];
-                        v[g][e] = relu ? fmaxf(x, 0.f) : x;
+                        v[g][e] = relu ? relu_keep_nan(x) : x;
                     }
                 tile_store<FULL>(wt, v, out, ldo, (long long)acc.q0 + j * 32, rows, acc.p0 + i * 32, nout);
             }

@@ -369,6 +369,7 @@ __device__ __forceinline__ void phase_heads(Ring& ring, const Program& G, const 
     split_rows(x, s, xh, xl);
     const float sh = hidden_scale(fmaf(P.hn * 8192.0f, inv, P.hb));
     const float b1s = s * P.sw1, c1 = sh * inv / P.sw1, un2 = 1.0f / (P.sw2 * sh);
+    float probe = 0.f;                                              // NaN iff the row's state is not finite (x3_common.hpp keep_nan)
     for (int task = 0; task < P.n_tasks; ++task) {
         f32x16 acc2[2];
 #pragma unroll
@@ -384,6 +385,7 @@ __device__ __forceinline__ void phase_heads(Ring& ring, const Program& G, const 
                 mac3(acc1, cur[0], cur[1], xh[u], xl[u]);
                 if (u < 15) { cur[0] = nxt[0]; cur[1] = nxt[1]; }
             }
+            probe = acc1[0];
             f16x8 hh[2], hl[2];
             hidden_planes(acc1, c1, hh, hl);
             f16x8 a2[4];
@@ -404,7 +406,7 @@ __device__ __forceinline__ void phase_heads(Ring& ring, const Program& G, const 
                 for (int e = 0; e < 4; ++e) dot += fmaxf(acc2[i][4 * g + e] * un2, 0.f) * w[e];
             }
         dot += __shfl_xor(dot, 32, 64);
-        if (h == 0 && row_ok) out[(long long)task * ld_out + row] = dot + pb[G.hb3[task] - 4 * h];   // b_3 (h == 0 here)
+        if (h == 0 && row_ok) out[(long long)task * ld_out + row] = keep_nan(dot + pb[G.hb3[task] - 4 * h], probe);   // b_3 (h == 0 here)
     }
 }
 

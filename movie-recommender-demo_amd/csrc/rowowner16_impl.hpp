@@ -647,6 +647,7 @@ __device__ __forceinline__ void phase_heads(Ring& ring, const Program& G, const 
     init_pair(acc2[2], acc2[3], pb, G.hb2[0], 2, P.sw2 * sh);
     init_pair(a10, a11, pb, P.b1, 0, b1s);
     heads_step<true, false, 0>(ring, xh, xl, a10, a11, acc2, hh, hl);                   // tile 0: stage 1 only
+    const float probe = a10[0];                                // NaN iff the row's state is not finite (x3_common.hpp keep_nan)
     int task = 0, t_in = 0;                                    // task / index of the tile whose stage 2 runs in step tt
     for (int tt = 1; tt <= NT; ++tt) {
         hidden_planes(a10, a11, c1, lim1, hh, hl);             // tile tt - 1
@@ -666,7 +667,7 @@ __device__ __forceinline__ void phase_heads(Ring& ring, const Program& G, const 
                 for (int r = 0; r < 4; ++r) dot += fmaxf(acc2[t][r] * un2, 0.f) * w[r];
             }
             dot = reduce_sum4(dot);
-            if (g == 0 && row_ok) out[(long long)task * ld_out + row] = dot + pb[G.hb3[task]];  // g == 0: pb carries no offset
+            if (g == 0 && row_ok) out[(long long)task * ld_out + row] = x3::keep_nan(dot + pb[G.hb3[task]], probe);  // g == 0: pb carries no offset
             t_in = 0;
             if (++task < P.n_tasks) {
                 init_pair(acc2[0], acc2[1], pb, G.hb2[task], 0, P.sw2 * sh);

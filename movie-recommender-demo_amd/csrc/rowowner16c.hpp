@@ -373,6 +373,7 @@ __device__ __forceinline__ void phase_heads(Ring& ring, f16x8 (&cur)[4], const E
     f32x4 a2[2], a10, a11;
     f16x8 hh0, hl0, hh1, hl1;
     int task = 0, done = 0;                                      // hidden steps of `task` whose stage 2 has run
+    float probe = 0.f;                                           // set after super-step 0, before the first store
     init_pair(a2[0], a2[1], pb, G.hb2[0], 2 * pr, P.sw2 * sh);
     // a task's 64 outputs are complete once the stage 2 of all its hidden steps has run: waves 0, 1 publish them
     auto stage2_done = [&]() {
@@ -389,7 +390,7 @@ __device__ __forceinline__ void phase_heads(Ring& ring, f16x8 (&cur)[4], const E
             for (int r = 0; r < 4; ++r) dot += fmaxf(o[r] * un2, 0.f) * wv[r];
         }
         dot = reduce_sum4(dot);
-        if (store) out[(long long)task * ld_out + row] = dot + pb[G.hb3[task]];               // store: wave 0, g == 0, row valid
+        if (store) out[(long long)task * ld_out + row] = x3::keep_nan(dot + pb[G.hb3[task]], probe);   // store: wave 0, g == 0, row valid
         done = 0;
         if (++task < P.n_tasks) init_pair(a2[0], a2[1], pb, G.hb2[task], 2 * pr, P.sw2 * sh);
     };
@@ -401,6 +402,7 @@ __device__ __forceinline__ void phase_heads(Ring& ring, f16x8 (&cur)[4], const E
 #pragma unroll
         for (int i = 0; i < 8; ++i) chunk(ring, cur, pos, xh[i], xl[i], a10, a11);
     }
+    probe = a10[0];                                              // NaN iff the row's state is not finite (x3_common.hpp keep_nan)
     hidden_planes(a10, a11, c1, lim1, ph, pl);
     E.put_hidden(0, w, ph, pl);
     // super-steps 1 .. S - 1: 8 stage-1 chunks with the 4 stage-2 chunks of super-step ss - 1 behind chunks 3 and 7

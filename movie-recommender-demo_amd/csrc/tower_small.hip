@@ -24,10 +24,7 @@
 
 namespace amdrec {
 
-// The hidden layers' ReLU keeps a NaN, as torch.relu does (fmaxf alone returns its other operand, 0): a row with a NaN feature
-// then leaves the tower as a NaN embedding, which the search answers with an empty candidate list, instead of as the
-// embedding of an all-zero first hidden layer.  Every other value, -0.0 included, gives what fmaxf(v, 0) gives.
-__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+// (the hidden layers' ReLU is common.hpp relu_keep_nan: a row with a NaN feature leaves the tower as a NaN embedding)
 
 constexpr int TS_ROWS = 16, TS_WAVES = 8;
 constexpr long long TS_MAX_ROWS = 4096;      // one 16-row workgroup per CU; beyond it the tiled GEMMs have enough work per launch

@@ -123,6 +123,17 @@ __device__ __forceinline__ long long dense_row(const Input& in, long long r) {
     return s < 0 ? 0 : (a >= in.n_x ? in.n_x - 1 : a);
 }
 
+// The heads' ReLUs (med3 in hidden_planes, fmaxf before w_3) are one instruction per element and drop a NaN, and unlike the
+// FFN no residual carries it past them: a row whose trunk state is NaN or infinite would leave with finite logits built from
+// the biases, where the reference's torch.relu keeps the NaN.  So every heads phase takes ONE value per row, `probe` - an
+// element of the row's first stage-1 accumulator, which the MFMA makes NaN exactly when the row's planes hold a NaN (a NaN
+// anywhere in the row; an infinity gives a NaN low plane) - and applies it where a logit is stored: one select per row and
+// task, nothing per hidden element, and the bits of every finite row stay what they were.
+__device__ __forceinline__ float keep_nan(float logit, float probe) {
+    const float z = probe * 0.f;                 // 0 for a finite probe, NaN for a NaN or infinite one
+    return z != z ? z : logit;
+}
+
 // Elimination switches for tools/x3_probe.hip (0 in the product): 1 = no weight DMA and no wait for it, 2 = no
 // per-chunk barrier, 4 = no fragment reads from LDS (stale registers), 8 = no hidden-tile conversion (stale planes);
 // 16-row kernels only: 16 = cycle stamps (DMA wait / barrier) per wave into the logits buffer's tail, 32 (with 16) =
