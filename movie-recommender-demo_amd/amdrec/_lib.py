@@ -242,6 +242,21 @@ def drop_tensor_list(module):
     module.__dict__.pop("_amdrec_tensor_list", None)
 
 
+def copyable_state(module, derived=("_packed", "_ad_cache")) -> dict:
+    """``__getstate__`` of the drop-ins: the module's ``__dict__`` without its derived state.  The packed weights hold a
+    ctypes structure of raw device pointers (not picklable, and a copy must not point into the original's buffers), the
+    per-ad caches belong to the original's pack, and the cached tensor list names the ORIGINAL's tensors: a copy
+    (``copy.deepcopy``, ``pickle``, ``torch.save`` of the whole module) starts with none of them and packs for itself on
+    first use."""
+    state = dict(module.__dict__)
+    for name in ("_amdrec_tensor_list", "_amdrec_tensor_epoch", "_amdrec_tensor_ids", "_ctr_first_why"):
+        state.pop(name, None)
+    for name in derived:
+        if name in state:
+            state[name] = None
+    return state
+
+
 class Workspace:
     """Grow-only per-device scratch buffer handed to the C ABI (caller-owned workspace).
 

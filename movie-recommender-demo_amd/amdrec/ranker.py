@@ -8,9 +8,16 @@ argument order (ad_categorical is SECOND, unlike TwoTowerModel) and returns the 
 length fixed at 1 (:358) softmax over a single key is 1.0 whatever the mask says.
 ``score_candidates`` is the pipeline entry: one user row broadcast over its stage-1
 candidates, ad features gathered from a resident table by candidate id.
+
+Writes the framework cannot see: the packed weights and the per-ad caches are keyed by tensor identity and ``_version``.
+A write through ``.data`` (``p.data.copy_(w)``, ``p.data = t``), a raw pointer or a DLPack alias changes neither and is
+outside the keys: call ``invalidate()`` after such a write to a weight, and replace the ad table by a new tensor after
+such a write to its rows.  A copy of the module (``copy.deepcopy``, ``pickle``, ``torch.save(model)``) carries no
+derived state and packs for itself on first use.
 """
 from __future__ import annotations
 
+import weakref
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
@@ -73,10 +80,15 @@ class _AdCache(NamedTuple):         # TransformerRanker._ad_cache: one ad table'
     version: int
     proj: torch.Tensor
     hidden: Optional[torch.Tensor]
+    table: "weakref.ref"            # the table itself: address, shape and version all repeat once a table has been freed
 
 
 def _table_key(table):
     return table.data_ptr(), tuple(table.shape), table._version
+
+
+def _entry(key, table, proj, hidden) -> _AdCache:
+    return _AdCache(key, *_table_key(table), proj, hidden, weakref.ref(table))
 
 
 class TransformerRanker(nn.Module):
@@ -180,10 +192,20 @@ class TransformerRanker(nn.Module):
 
     # -- packing ----------------------------------------------------------------------
     def invalidate(self):
+        """Drop the packed weights and the per-ad caches: the next eval-mode call packs (and caches) again.  Both are keyed
+        by what torch shows of a change - the device, the engine switches, every parameter's and buffer's ``_version`` and
+        identity; the caches also by the ad table's identity, address, shape and ``_version``.  A write it cannot see
+        (``p.data.copy_(w)``, ``p.data = t``, a raw pointer, a DLPack alias) changes none of them, so the HIP path would keep
+        serving the old weights while the ATen path (``autograd_forward``, train mode) already shows the new ones: call
+        this after such a write to a weight.  After such a write to the ad table, hand the ranker a new tensor (the
+        pipeline: assign it to ``rec.ad_features``)."""
         self._packed = None
         self._ad_cache = None
         self.__dict__.pop("_ctr_first_why", None)
         _lib.drop_tensor_list(self)
+
+    def __getstate__(self):                        # deepcopy / pickle / torch.save(module): a copy packs for itself
+        return _lib.copyable_state(self)
 
     def _apply(self, fn, *a, **k):                 # .to() / .cuda() / .float(): tensors may be replaced
         r = super()._apply(fn, *a, **k)
@@ -212,21 +234,27 @@ class TransformerRanker(nn.Module):
         ws = _lib.WORKSPACE.get(4 * self.d_model + 256, dev)
         _lib.check(lib.amdrec_ranker_project_ads(_lib.C.byref(params), _lib.ptr(table), table.shape[0], _lib.ptr(out),
                                                  out.stride(0), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-        self._ad_cache = _AdCache(self._packed.key, *_table_key(table), out, None)
+        self._ad_cache = _entry(self._packed.key, table, out, None)
         return out
 
     def ensure_ad_cache(self, ad_table):
         """Build the cache for ``ad_table`` unless a valid one exists (weights or table changed -> rebuilt) - and, with
         ``cache_first_ffn`` on weights packed for it, the first-FFN hidden cache P [N, d_ff] beside it while both fit
-        ``hidden_cache_max_bytes``."""
+        ``hidden_cache_max_bytes``.  The cap holds for a hidden cache that exists already: one built under a larger cap is
+        dropped here (the projection cache stays), as a fresh ranker under the same cap would have none."""
         params, _ = self._pack(ad_table.device)
         if self._entry_for(ad_table) is None:
             self.cache_ad_projection(ad_table)
         c = self._entry_for(ad_table)
-        if c is None or c.hidden is not None or not params.x3.w_hidden_ad:
+        if c is None or not params.x3.w_hidden_ad:
             return
         n, d_ff = int(ad_table.shape[0]), int(params.d_ff)
-        if n * (self.d_model + d_ff) * 4 > int(self.hidden_cache_max_bytes):
+        fits = n * (self.d_model + d_ff) * 4 <= int(self.hidden_cache_max_bytes)
+        if c.hidden is not None:
+            if not fits:                                    # the cap was lowered under a cache built before: the uncached program
+                self._ad_cache = c._replace(hidden=None)
+            return
+        if not fits:
             return
         dev = ad_table.device
         hid = torch.empty((n, d_ff), dtype=torch.float32, device=dev)
@@ -250,7 +278,7 @@ class TransformerRanker(nn.Module):
         if c is None:
             return
         hid = None if c.hidden is None else gather_rows(c.hidden, kept)
-        self._ad_cache = _AdCache(c.key, *_table_key(new_table), gather_rows(c.proj, kept), hid)
+        self._ad_cache = _entry(c.key, new_table, gather_rows(c.proj, kept), hid)
 
     def extend_ad_cache(self, old_table, new_table):
         """Rows were appended to the ad table: ``new_table[:len(old_table)]`` equals ``old_table``.  If a valid cache exists
@@ -284,13 +312,16 @@ class TransformerRanker(nn.Module):
                 _lib.check(lib.amdrec_ranker_project_ads_hidden(
                     _lib.C.byref(params), _lib.ptr(tail), n_new - n_old, _lib.ptr(out), hid.stride(0), _lib.ptr(ws),
                     ws.numel(), _lib.stream_ptr(dev)))
-        self._ad_cache = _AdCache(c.key, *_table_key(new_table), proj, hid)
+        self._ad_cache = _entry(c.key, new_table, proj, hid)
 
     def _entry_for(self, table) -> Optional[_AdCache]:
-        """The cache entry valid for ``table`` - built under the current pack key for this very tensor (same data_ptr, shape
-        and _version) - or None."""
+        """The cache entry valid for ``table`` - built under the current pack key for this very tensor OBJECT at its current
+        data_ptr, shape and _version - or None.  The object itself is compared (through a weak reference): the caching
+        allocator hands a freed table's block to the next table of its shape, and a loader that runs the same code gives
+        that one the same _version."""
         c = getattr(self, "_ad_cache", None)
-        if c is None or self._packed is None or c.key != self._packed.key or c[1:4] != _table_key(table):
+        if c is None or self._packed is None or c.key != self._packed.key or c.table() is not table or \
+                c[1:4] != _table_key(table):
             return None
         return c
 

@@ -11,6 +11,11 @@ Training: in ``train()`` mode the forward is the re
 PyTorch autograd on the module's device (BatchNorm batch statistics, Dropout active) - the hand-written HIP
 kernels are the eval-mode hot path only; ``compute_loss`` is two_tower_model.py:256-285 and the trainers live in
 ``amdrec.training``.  A weight update re-packs the HIP weights on the next eval-mode call (parameter versions).
+
+Writes the framework cannot see: the packed weights are keyed by tensor identity and ``_version``.  A write through
+``.data`` (``p.data.copy_(w)``, ``p.data = t``), a raw pointer or a DLPack alias changes neither and is outside the key:
+call ``invalidate()`` (on a tower, or on the model for both) after such a write.  A copy of the module
+(``copy.deepcopy``, ``pickle``, ``torch.save(model)``) carries no derived state and packs for itself on first use.
 """
 from __future__ import annotations
 
@@ -53,8 +58,16 @@ class _Tower(nn.Module):
         self._packed = None
 
     def invalidate(self):
+        """Drop the packed weights: the next eval-mode call packs again.  The packing is keyed by what torch shows of a
+        change - the device, every parameter's and buffer's ``_version`` and identity.  A write it cannot see
+        (``p.data.copy_(w)``, ``p.data = t``, a raw pointer, a DLPack alias) changes neither, so the HIP path would keep
+        serving the old weights while the ATen path (``autograd_forward``, train mode) already shows the new ones: call
+        this after such a write."""
         self._packed = None
         _lib.drop_tensor_list(self)
+
+    def __getstate__(self):                        # deepcopy / pickle / torch.save(module): a copy packs for itself
+        return _lib.copyable_state(self)
 
     def _apply(self, fn, *a, **k):                 # .to() / .cuda() / .float(): tensors may be replaced
         r = super()._apply(fn, *a, **k)
@@ -167,8 +180,13 @@ class TwoTowerModel(nn.Module):
         sim = torch.matmul(user_embeddings, ad_embeddings.T) / self.temperature
         return torch.nn.functional.cross_entropy(sim.view(-1, sim.size(1)), torch.arange(sim.size(0), device=sim.device))
 
-    def load_state_dict(self, state_dict, *a, **k):
-        r = super().load_state_dict(state_dict, *a, **k)
+    def invalidate(self):
+        """Both towers' ``invalidate``: the remedy after a weight write that torch's version counters do not see
+        (``.data``, raw pointers, DLPack aliases)."""
         self.user_tower.invalidate()
         self.ad_tower.invalidate()
+
+    def load_state_dict(self, state_dict, *a, **k):
+        r = super().load_state_dict(state_dict, *a, **k)
+        self.invalidate()
         return r
