@@ -186,13 +186,16 @@ def share_ivf_centroids(index, train_rows, rank: int, world: int, group=None, sr
 
 def all_gather_bytes(out: torch.Tensor, inp: torch.Tensor, group=None):
     """all_gather_into_tensor; device tensors under a gloo group (rehearsal of the multi-rank
-    path on a box with fewer GPUs than ranks) are staged through the host."""
+    path on a box with fewer GPUs than ranks) are staged through the host.  ``out`` (contiguous) receives the ranks' ``inp``
+    one behind the other, whatever its shape: both go to the collective as flat views, because gloo takes the concatenated
+    form alone - a stacked ``out`` [world, *inp.shape], which RCCL accepts, it refuses (recommend_all's scores)."""
+    flat_in, flat_out = inp.reshape(-1), out.view(-1)
     if inp.is_cuda and dist.get_backend(group) == "gloo":
-        h_in, h_out = inp.cpu(), torch.empty(out.shape, dtype=out.dtype)
+        h_in, h_out = flat_in.cpu(), torch.empty(flat_out.shape, dtype=out.dtype)
         dist.all_gather_into_tensor(h_out, h_in, group=group)
-        out.copy_(h_out)
+        flat_out.copy_(h_out)
     else:
-        dist.all_gather_into_tensor(out, inp, group=group)
+        dist.all_gather_into_tensor(flat_out, flat_in, group=group)
 
 
 def all_to_all_bytes(out: torch.Tensor, inp: torch.Tensor, group=None):

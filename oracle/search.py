@@ -31,14 +31,18 @@ def normalize_l2(x):
 
 
 def topk_desc(scores, k):
-    """Exact k largest per row, sorted (score desc, position asc). -> (D, I)."""
+    """Exact k largest per row, sorted (score desc, position asc). -> (D, I).  A NaN score is never returned (the flat
+    search's contract): a row of them, a NaN query's, leaves every slot unfilled (-inf, -1)."""
     nq, n = scores.shape
-    kk = min(k, n)
     D = np.full((nq, k), -np.inf, dtype=np.float32)
     I = np.full((nq, k), -1, dtype=np.int64)
     for q in range(nq):
         s = scores[q]
-        if kk < n:
+        kk = min(k, n)
+        if np.isnan(s).any():
+            cand = np.nonzero(~np.isnan(s))[0]
+            kk = min(kk, len(cand))
+        elif kk < n:
             kth = np.partition(s, n - kk)[n - kk]
             cand = np.nonzero(s >= kth)[0]
         else:
