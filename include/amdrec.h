@@ -728,6 +728,32 @@ int amdrec_select_topk_auction(const float* logits /*[n_tasks][ld]*/, int64_t ld
                                float* out_scores /*[n_tasks][n_users][top_k]*/, int32_t* out_slots /*or NULL*/,
                                float* out_ecpm /*[n_users][top_k]*/, float* out_price /*[n_users][top_k]*/, void* stream);
 
+/* Diversified selection (one more export added to ABI v14, every other entry as it was): amdrec_select_topk re-ordered by
+ * relevance discounted by similarity to what is already chosen - a multiplicative MMR.  Per user:
+ *   candidates and relevance order are amdrec_select_topk's (cand_pos is REQUIRED; logit desc, slot asc, NaN logits last);
+ *   max_per_group > 0: a candidate is accepted iff fewer than max_per_group better-ranked candidates share its non-negative
+ *   group group_of[cand_pos] (amdrec_select_topk_capped's acceptance); 0: every candidate is accepted, group_of may be NULL;
+ *   the POOL is the first `pool` accepted candidates.  Member i has rel_i = the probability amdrec_select_topk reports for
+ *   logits[rank_task], and m_i = 0.  For rank r = 0 .. top_k - 1 the untaken member with the largest
+ *   v_i = rel_i * fmaf(-lam, m_i, 1.0f) (fp32) wins; equal values go to the member earlier in the relevance order, a NaN value
+ *   ranks after every other (among NaNs the earlier member).  After winner w, every remaining i: m_i = fminf(1, fmaxf(m_i,
+ *   s_iw)), s_iw = the fp32 inner product of rows cand_pos[i] and cand_pos[w] of `rows` (accumulation order unspecified; a NaN
+ *   s_iw leaves m_i as it was; a negative one does not discount).  A position >= n_rows is never read: similarity 0.
+ * Winners go out in pick order as amdrec_select_topk writes them; out_values[u][r] = the winning v.  The tail past the last
+ * winner (a pool shorter than top_k) reads id -1, slot -1, probabilities 0.0, value 0.0.  With lam == 0 the result equals
+ * amdrec_select_topk's (amdrec_select_topk_capped's under a cap) bit for bit.
+ * 1 <= top_k <= pool <= 128, 1 <= k_c <= AMDREC_MAX_K, 1 <= dim <= ld_rows, pool * dim <= 32768 (the pool's rows are staged
+ * in one workgroup's LDS), lam finite in [0, 1].  One launch, one workgroup per user, no workspace; every argument is
+ * validated before the first HIP call; n_users <= 0 returns OK without looking at a pointer. */
+int amdrec_select_topk_diverse(const float* logits /*[n_tasks][ld]*/, int64_t ld_logits, int n_tasks, int rank_task,
+                               const int64_t* cand_ids /*[n_users][k_c]*/, const int64_t* cand_pos /*[n_users][k_c]*/,
+                               int64_t n_users, int k_c, int top_k, const float* rows /*[n_rows][ld_rows]*/, int64_t n_rows,
+                               int64_t ld_rows, int dim, float lam, int pool,
+                               const int64_t* group_of /*[n_group_rows]; NULL without a cap*/, int64_t n_group_rows,
+                               int max_per_group /*0: no cap*/, int64_t* out_ids /*[n_users][top_k]*/,
+                               float* out_scores /*[n_tasks][n_users][top_k]*/, int32_t* out_slots /*or NULL*/,
+                               float* out_values /*[n_users][top_k]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

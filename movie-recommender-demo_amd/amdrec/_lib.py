@@ -101,6 +101,10 @@ _SIGNATURES = {
     # its outputs + (out_ecpm, out_price, stream)
     "amdrec_select_topk_auction": [_fp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _fp, _i64, _fp, _vp, _i64, _i32, _vp, _fp,
                                    _vp, _fp, _fp, _vp],
+    # amdrec_select_topk's arguments up to top_k + (rows, n_rows, ld_rows, dim, lam, pool, group_of, n_group_rows,
+    # max_per_group), its outputs + (out_values, stream)
+    "amdrec_select_topk_diverse": [_fp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _fp, _i64, _i64, _i32, C.c_float, _i32,
+                                   _vp, _i64, _i32, _vp, _fp, _vp, _fp, _vp],
     "amdrec_group_cap_compact": [_vp, _fp, _i64, _i32, _vp, _i64, _i32, _i32, C.c_float, _vp, _fp, _vp],
 }
 _RESTYPE = {"amdrec_last_error": C.c_char_p}

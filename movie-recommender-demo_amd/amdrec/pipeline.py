@@ -27,7 +27,8 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import _lib, auction as _auction, eligible as _eligible, exclude as _exclude, rows_edit as _rows_edit
+from . import _lib, auction as _auction, diversity as _diversity, eligible as _eligible, exclude as _exclude, \
+    rows_edit as _rows_edit
 from .index import FAISSIndex
 from .ranker import TransformerRanker
 from .towers import TwoTowerModel
@@ -241,7 +242,7 @@ class AdRecommenderInference:
                                               require_any=masks[1], max_per_group=max_per_group)
 
     def _stage2(self, uc, un, cand_pos, top_k, check_indices, ids_are_positions=False, mark=None, out=None,
-                excluded=False, heads=None, max_per_group=None, auction=None):
+                excluded=False, heads=None, max_per_group=None, auction=None, diversity=None):
         """Ranker + selection over stage 1's positions ``cand_pos`` [B, stage1_k].  A negative position is a slot the search
         could not fill: no candidate.  The ranker still computes a (finite, unspecified) logit for it - every gather clamps
         the row - and the selection, which is handed the positions, ranks it after every real candidate: it is reported only
@@ -251,7 +252,10 @@ class AdRecommenderInference:
         ``max_per_group`` (validated by the caller, None: no cap): the selection is amdrec_select_topk_capped over the index's
         group keys - at most that many winners of one group per user, greedy in the selection's order.
         ``auction`` (validated by the caller, None: rank by CTR): ``(reserve,)`` - the selection is amdrec_select_topk_auction
-        over the index's bids (amdrec.auction has the rule), the cap inside it, and the result gains ``ecpm`` / ``prices``."""
+        over the index's bids (amdrec.auction has the rule), the cap inside it, and the result gains ``ecpm`` / ``prices``.
+        ``diversity`` (validated by the caller, None: the selections above): ``(lam, pool)`` - the selection is
+        amdrec_select_topk_diverse over the index's rows as they are at this call (amdrec.diversity has the rule), the cap
+        inside it, and the result gains ``diversity_values``."""
         lib = _lib.load()
         B, stage1_k = cand_pos.shape
         rk = self.transformer_ranker
@@ -290,7 +294,8 @@ class AdRecommenderInference:
             cand_ids = torch.empty_like(cand_pos)
             _lib.check(lib.amdrec_remap_ids(_lib.ptr(cand_pos), _lib.ptr(idx._ids), idx._n, _lib.ptr(cand_ids),
                                             cand_pos.numel(), _lib.stream_ptr(uc.device)))
-        mid, ecpm, prices = (), None, None       # mid / tail: what an entry takes between top_k and out_ids / behind out_slots
+        # mid / tail: what an entry takes between top_k and out_ids / behind out_slots
+        mid, ecpm, prices, values = (), None, None, None
         if auction is not None:
             # the auction entry: the selection's arguments with the bids, the reserve and the groups in the middle and two
             # outputs more; the cap (0: none) rides in the same launch
@@ -304,6 +309,15 @@ class AdRecommenderInference:
                 ecpm = torch.empty((B, top_k), dtype=torch.float32, device=uc.device)
                 prices = torch.empty((B, top_k), dtype=torch.float32, device=uc.device)
             tail = (_lib.ptr(ecpm), _lib.ptr(prices))
+        elif diversity is not None:
+            # the diversified entry: the rows, lam, the pool and the groups in the middle, one output more; the cap (0: none)
+            # rides in the same launch.  The rows are read from the index now: nothing is cached across corpus edits
+            select = lib.amdrec_select_topk_diverse
+            mid = (_lib.ptr(idx._xb), idx._n, idx._xb.stride(0), idx.dimension, diversity[0], diversity[1],
+                   _lib.ptr(idx._groups) if max_per_group else None, idx._n if max_per_group else 0, max_per_group or 0)
+            values = out[2] if out is not None and len(out) == 3 else \
+                torch.empty((B, top_k), dtype=torch.float32, device=uc.device)
+            tail = (_lib.ptr(values),)
         elif max_per_group is None:
             select, tail = lib.amdrec_select_topk, ()
         else:                                    # the same arguments, then the groups: the cap runs inside the selection
@@ -324,6 +338,8 @@ class AdRecommenderInference:
                "logit_tasks": ("ctr",) if ctr_first else tuple(tasks)}
         if auction is not None:
             res["ecpm"], res["prices"] = ecpm, prices
+        if diversity is not None:
+            res["diversity_values"] = values
         return res
 
     @torch.no_grad()
@@ -332,7 +348,8 @@ class AdRecommenderInference:
                          exclude_ad_ids: Optional[torch.Tensor] = None, heads: Optional[str] = None,
                          require_all: Optional[torch.Tensor] = None, require_any: Optional[torch.Tensor] = None,
                          max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
-                         rank_by: Optional[str] = None, reserve=None):
+                         rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
+                         diversity_pool: int = 64):
         """[B,6] / [B,13] device tensors -> dict of device tensors, no host synchronisation:
         ad_ids [B,top_k] int64, scores [3,B,top_k] float32 (sigmoid of the logits), candidate_ids
         [B,stage1_k], candidate_scores [B,stage1_k], logits [3, B*stage1_k].  candidate_scores are the index's own
@@ -367,11 +384,19 @@ class AdRecommenderInference:
         float >= 0 for every user, or a device float32 [B]; candidates whose eCPM does not reach it are dropped and it is
         every price's floor.  "ecpm" on an index without bids, an unknown ``rank_by``, a reserve without "ecpm" and a
         negative or non-finite scalar reserve: ValueError.
+        ``diversity`` (None: the selections above, the launches of ever): ``lam`` in [0, 1] re-orders the best
+        ``diversity_pool`` accepted candidates greedily by pCTR x (1 - lam x the largest similarity to an ad already chosen),
+        similarities being inner products of the index's own rows (amdrec.diversity has the rule; Flat and IVF), inside one
+        selection launch, after ``max_per_group`` where that is given; the dict gains ``diversity_values``, float32 [B, top_k]:
+        each winner's discounted value (0.0 in the unfilled tail).  ``lam == 0`` is the plain (or capped) result bit for bit.
+        A non-number ``lam``: TypeError; ``lam`` outside [0, 1], a pool below ``top_k``, above 128 or with pool x dimension >
+        32768, a pool without ``diversity``, and ``diversity`` with "ecpm": ValueError; on an IVFPQ index: NotImplementedError.
         ``check_indices``: an out-of-range user index or ad-table row raises IndexError; an unfilled slot does not."""
         if heads is not None:
             self._check_heads(heads)
         cap, cap1 = self._check_caps(max_per_group, stage1_max_per_group)          # (before the library is touched)
         auction = self._check_auction(rank_by, reserve)
+        div = self._check_diversity(diversity, diversity_pool, top_k, auction)
         uc = _lib.require_gpu(user_categorical, "user_categorical")
         un = _lib.require_gpu(user_numerical, "user_numerical")
         excluded = exclude_ad_ids is not None and exclude_ad_ids.shape[-1] > 0
@@ -380,14 +405,15 @@ class AdRecommenderInference:
                                              (require_all, require_any), cap1)
         # (excluded: "a slot can be unfilled" - true after a filtered stage 1 as well)
         out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded or masked or cap1 is not None,
-                           heads=heads, max_per_group=cap, auction=auction)
+                           heads=heads, max_per_group=cap, auction=auction, diversity=div)
         out["candidate_scores"] = cand_scores
         return out
 
     def capture(self, batch_size: int, top_k: int = 10, stage1_k: int = 500, warmup: int = 2,
                 max_exclude: int = 0, eligibility: bool = False, max_per_group: Optional[int] = None,
                 stage1_max_per_group: Optional[int] = None, rank_by: Optional[str] = None,
-                reserve: bool = False) -> "GraphedRecommender":
+                reserve: bool = False, diversity: Optional[float] = None,
+                diversity_pool: int = 64) -> "GraphedRecommender":
         """Capture one recommend_device call for a fixed batch shape into a HIP graph (the ~40 kernel
         launches of a request are host-launch-bound at small batch: 1.76 ms eager at B = 1) and return a
         replayer.  Weights, index and ad table must not change afterwards.  ``max_exclude`` > 0: the graph also holds a
@@ -398,9 +424,10 @@ class AdRecommenderInference:
         ``max_per_group`` / ``stage1_max_per_group`` (recommend_device): scalars fixed at capture; the group keys are those
         of capture time.  ``rank_by`` (recommend_device) is fixed at capture too, and the bids are those of capture time;
         ``reserve=True`` (needs "ecpm") gives the graph a static [batch_size] float32 reserve buffer that the replayer's
-        ``reserve`` argument fills."""
+        ``reserve`` argument fills.  ``diversity`` / ``diversity_pool`` (recommend_device): scalars fixed at capture, like
+        ``max_per_group``; the rows are those of capture time."""
         return GraphedRecommender(self, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group,
-                                  stage1_max_per_group, rank_by, reserve)
+                                  stage1_max_per_group, rank_by, reserve, diversity, diversity_pool)
 
     # -- live corpus: ads leave and enter without a rebuild of the index or of the ranker's per-ad caches ------------------
     def remove_ads(self, ad_ids) -> int:
@@ -460,23 +487,27 @@ class AdRecommenderInference:
     def recommend_ads(self, user_data: dict, top_k: int = 10, stage1_k: int = 500,
                       return_scores: bool = True, exclude_ad_ids=None, require_all: int = 0, require_any: int = 0,
                       max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
-                      rank_by: Optional[str] = None, reserve=None) -> dict:
+                      rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
+                      diversity_pool: int = 64) -> dict:
         """inference.py:199-288.  ``exclude_ad_ids``: the ad ids this user must not be shown (a sequence of integers).
         ``require_all`` / ``require_any``: this request's eligibility masks (64-bit integers; 0 and 0: no constraint, the
         plain search).  ``max_per_group`` / ``stage1_max_per_group``: the per-group caps of recommend_device.  ``rank_by`` /
-        ``reserve``: the auction of recommend_device (the dict gains ``ecpm`` and ``prices``).  Fewer than
+        ``reserve``: the auction of recommend_device (the dict gains ``ecpm`` and ``prices``).  ``diversity`` /
+        ``diversity_pool``: its diversified selection (the dict gains ``diversity_values``).  Fewer than
         ``top_k`` real candidates: as batch_recommend."""
         masked = bool(require_all) or bool(require_any)
         return self.batch_recommend([user_data], top_k=top_k, stage1_k=stage1_k, return_scores=return_scores,
                                     exclude_ad_ids=None if exclude_ad_ids is None else [exclude_ad_ids],
                                     require_all=[require_all] if masked else None,
                                     require_any=[require_any] if masked else None, max_per_group=max_per_group,
-                                    stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve)[0]
+                                    stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve,
+                                    diversity=diversity, diversity_pool=diversity_pool)[0]
 
     def batch_recommend(self, user_data_list: list, top_k: int = 10, stage1_k: int = 500,
                         return_scores: bool = True, exclude_ad_ids=None, require_all=None, require_any=None,
                         max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
-                        rank_by: Optional[str] = None, reserve=None) -> list:
+                        rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
+                        diversity_pool: int = 64) -> list:
         """inference.py:290-331 - but one device pass for the whole list instead of a serial loop.
         ``timing`` reports the batch's stage times divided by the number of users.  ``exclude_ad_ids``: one sequence of
         ad ids per user (recommend_device has the meaning); the padded block travels in the input staging block.
@@ -488,9 +519,11 @@ class AdRecommenderInference:
         ``max_per_group`` / ``stage1_max_per_group``: the per-group caps of recommend_device, for every user of the list (a
         user with fewer than ``top_k`` ads that the cap lets through gets the same tail).  ``rank_by`` / ``reserve``: the
         auction of recommend_device; every user's dict gains ``"ecpm"`` and ``"prices"`` lists of length ``top_k``, which travel
-        in the same result block: no copy and no synchronisation more."""
+        in the same result block: no copy and no synchronisation more.  ``diversity`` / ``diversity_pool``: the diversified
+        selection of recommend_device; every user's dict gains a ``"diversity_values"`` list of length ``top_k``, in the same
+        block."""
         self._check_caps(max_per_group, stage1_max_per_group)
-        self._check_auction(rank_by, reserve)
+        self._check_diversity(diversity, diversity_pool, top_k, self._check_auction(rank_by, reserve))
         if not user_data_list:
             return []
         n = len(user_data_list)
@@ -501,7 +534,8 @@ class AdRecommenderInference:
         masks = rest.pop(0) if masks is not None else None
         return self.recommend_tensors(uc, un, top_k, stage1_k, return_scores, _encoded=True, _exclude_dev=excl,
                                       _masks_dev=masks, max_per_group=max_per_group,
-                                      stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve)
+                                      stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve,
+                                      diversity=diversity, diversity_pool=diversity_pool)
 
     def _check_caps(self, max_per_group, stage1_max_per_group):
         """The two cap arguments -> (cap or None, stage-1 cap or None); refusals before the library is touched."""
@@ -513,6 +547,11 @@ class AdRecommenderInference:
         is touched (FAISSIndex._check_auction)."""
         auction, reserve = self.faiss_index._check_auction(rank_by, reserve)
         return (reserve,) if auction else None
+
+    def _check_diversity(self, diversity, diversity_pool, top_k, auction):
+        """The ``diversity`` / ``diversity_pool`` arguments -> None (today's selection) or ``(lam, pool)``; refusals before the
+        library is touched (amdrec.diversity.check_diversity).  ``auction``: _check_auction's result."""
+        return _diversity.check_index_diversity(self.faiss_index, diversity, diversity_pool, top_k, auction is not None)
 
     def _host_masks(self, require_all, require_any, n: int) -> Optional[np.ndarray]:
         """The two mask arguments of the reference-API calls -> int64 [2, n] on the host (None: neither given)."""
@@ -570,7 +609,8 @@ class AdRecommenderInference:
     @torch.no_grad()
     def recommend_tensors(self, user_categorical, user_numerical, top_k=10, stage1_k=500, return_scores=True,
                           _encoded=False, exclude_ad_ids=None, _exclude_dev=None, require_all=None, require_any=None,
-                          _masks_dev=None, max_per_group=None, stage1_max_per_group=None, rank_by=None, reserve=None):
+                          _masks_dev=None, max_per_group=None, stage1_max_per_group=None, rank_by=None, reserve=None,
+                          diversity=None, diversity_pool=64):
         """Tensor-level entry (cf. TwoStageRetriever.retrieve_and_rank, faiss_retrieval.py:283-369); result dicts follow
         inference.py:272-288.  ONE host synchronisation per call (round 3 had four: the tower's index flag, the stage-1
         timing sync, the ranker's index flag, the result copy - each exposing the launch work queued behind it): indices
@@ -581,9 +621,11 @@ class AdRecommenderInference:
         users' eligibility masks as in batch_recommend, shipped the same way.  The lists keep length ``top_k``, with
         -1 / 0.0 in the tail of a user with fewer real candidates (batch_recommend).  ``max_per_group`` /
         ``stage1_max_per_group``: the per-group caps of recommend_device.  ``rank_by`` / ``reserve``: its auction; ``ecpm`` and
-        ``prices`` ride in the same result block and copy."""
+        ``prices`` ride in the same result block and copy.  ``diversity`` / ``diversity_pool``: its diversified selection;
+        ``diversity_values`` rides there too."""
         cap, cap1 = self._check_caps(max_per_group, stage1_max_per_group)
         auction = self._check_auction(rank_by, reserve)
+        div = self._check_diversity(diversity, diversity_pool, top_k, auction)
         t0 = time.time()
         dev = self.device
         uc = user_categorical.to(dev)
@@ -613,14 +655,17 @@ class AdRecommenderInference:
             ev = self.__dict__["_ev"] = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ids_b, sc_b = n * top_k * 8, len(tasks) * n * top_k * 4
         au_b = 0 if auction is None else n * top_k * 4                       # ecpm, then prices, behind the scores
-        blk = torch.empty(ids_b + sc_b + 2 * au_b + 8, dtype=torch.uint8, device=dev)
+        dv_b = 0 if div is None else n * top_k * 4                           # diversity_values, there instead (never both)
+        blk = torch.empty(ids_b + sc_b + 2 * au_b + dv_b + 8, dtype=torch.uint8, device=dev)
         ad_ids = blk[:ids_b].view(torch.int64).view(n, top_k)
         scores = blk[ids_b:ids_b + sc_b].view(torch.float32).view(len(tasks), n, top_k)
         outs = (ad_ids, scores)
         if auction is not None:
             outs += tuple(blk[ids_b + sc_b + i * au_b:ids_b + sc_b + (i + 1) * au_b].view(torch.float32).view(n, top_k)
                           for i in range(2))
-        verdict = blk[ids_b + sc_b + 2 * au_b:].view(torch.int32)            # [2]: nonzero = an index out of range
+        if div is not None:
+            outs += (blk[ids_b + sc_b:ids_b + sc_b + dv_b].view(torch.float32).view(n, top_k),)
+        verdict = blk[ids_b + sc_b + 2 * au_b + dv_b:].view(torch.int32)     # [2]: nonzero = an index out of range
         trusted = _encoded and self.preprocessor is not None and self._encoder_fits()
         if trusted:
             verdict.zero_()
@@ -637,7 +682,7 @@ class AdRecommenderInference:
         ev[1].record(st)
         out = self._stage2(uc, un, cand_pos, top_k, False, out=outs,
                            excluded=excl is not None or masks is not None or cap1 is not None, max_per_group=cap,
-                           auction=auction)
+                           auction=auction, diversity=div)
         assert list(out["tasks"]) == tasks
         host, done = self._staging(blk.numel(), "out")
         host.copy_(blk, non_blocking=True)
@@ -645,11 +690,12 @@ class AdRecommenderInference:
         done.record(st)
         ev[2].synchronize()
         hv = host.numpy()
-        if int(hv[ids_b + sc_b + 2 * au_b:].view(np.int32)[0]):
+        if int(hv[ids_b + sc_b + 2 * au_b + dv_b:].view(np.int32)[0]):
             raise IndexError("index out of range in self")                    # torch.nn.Embedding's message
         ids = hv[:ids_b].view(np.int64).reshape(n, top_k).tolist()
         sc = hv[ids_b:ids_b + sc_b].view(np.float32).reshape(len(tasks), n, top_k).tolist() if return_scores else None
         au = None if auction is None else hv[ids_b + sc_b:ids_b + sc_b + 2 * au_b].view(np.float32).reshape(2, n, top_k).tolist()
+        dv = None if div is None else hv[ids_b + sc_b:ids_b + sc_b + dv_b].view(np.float32).reshape(n, top_k).tolist()
         t2 = time.time()
         # stage 1 = its GPU time (tower + search, as the reference brackets them); stage 2 = the rest of the call's wall time
         # (ranker, selection, the copy back and the list conversion: what the reference's second bracket holds)
@@ -663,6 +709,8 @@ class AdRecommenderInference:
                 r["scores"] = {t: sc[i][b] for i, t in enumerate(tasks)}
             if au is not None:
                 r["ecpm"], r["prices"] = au[0][b], au[1][b]
+            if dv is not None:
+                r["diversity_values"] = dv[b]
             res.append(r)
         return res
 
@@ -688,16 +736,19 @@ class TwoStageRetriever:
     def retrieve_and_rank(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor, stage1_k: int = 500,
                           stage2_k: int = 10, ad_features_lookup=None, exclude_ad_ids=None,
                           max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
-                          rank_by: Optional[str] = None, reserve=None):
+                          rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
+                          diversity_pool: int = 64):
         """``exclude_ad_ids``: the ad ids the (first) user must not be shown, a sequence of integers.  With a table, the two
         lists have length ``stage2_k``; a user with fewer real candidates gets -1 / 0.0 in the tail (batch_recommend).
         ``stage1_max_per_group`` / ``max_per_group``: the per-group caps on the candidates and on the ranked result
         (AdRecommenderInference.recommend_device); without a table only the first applies (there is no stage 2).
         ``rank_by`` / ``reserve``: the auction of recommend_device for the ranked result (the tuple is as ever: ids and CTR
-        probabilities, in eCPM order); without a table they are checked and change nothing."""
+        probabilities, in eCPM order); without a table they are checked and change nothing.  ``diversity`` /
+        ``diversity_pool``: the diversified selection of recommend_device for the ranked result (ids and CTR probabilities, in
+        pick order); without a table they are checked and change nothing."""
         idx = self.faiss_index
         cap, cap1 = idx._check_group_cap(max_per_group), idx._check_group_cap(stage1_max_per_group, "stage1_max_per_group")
-        idx._check_auction(rank_by, reserve)
+        _diversity.check_index_diversity(idx, diversity, diversity_pool, stage2_k, idx._check_auction(rank_by, reserve)[0])
         uc = user_categorical.to(self.device)
         un = user_numerical.to(self.device, dtype=torch.float32)
         excl = None if exclude_ad_ids is None else [exclude_ad_ids]
@@ -715,7 +766,8 @@ class TwoStageRetriever:
             self._rec_table = ad_features_lookup
         r = self._rec.recommend_tensors(uc[:1], un[:1], stage2_k, stage1_k,       # one synchronisation, indices validated
                                         exclude_ad_ids=excl, max_per_group=cap, stage1_max_per_group=cap1,
-                                        rank_by=rank_by, reserve=reserve)[0]
+                                        rank_by=rank_by, reserve=reserve, diversity=diversity,
+                                        diversity_pool=diversity_pool)[0]
         return r["ad_ids"], r["scores"]["ctr"]                                    # :359-369 (ids, ctr probabilities)
 
 
@@ -726,7 +778,8 @@ class GraphedRecommender:
 
     def __init__(self, rec: AdRecommenderInference, batch_size: int, top_k: int, stage1_k: int, warmup: int = 2,
                  max_exclude: int = 0, eligibility: bool = False, max_per_group: Optional[int] = None,
-                 stage1_max_per_group: Optional[int] = None, rank_by: Optional[str] = None, reserve: bool = False):
+                 stage1_max_per_group: Optional[int] = None, rank_by: Optional[str] = None, reserve: bool = False,
+                 diversity: Optional[float] = None, diversity_pool: int = 64):
         self.rec, self.batch_size, self.top_k, self.stage1_k = rec, batch_size, top_k, stage1_k
         # the per-group caps: scalars fixed at capture (the group keys are those of capture time, pinned below)
         self.max_per_group, self.stage1_max_per_group = rec._check_caps(max_per_group, stage1_max_per_group)
@@ -735,6 +788,10 @@ class GraphedRecommender:
         # [batch_size] reserve buffer, zeros = every non-NaN eCPM passes
         self.rank_by = rank_by
         auction = rec._check_auction(rank_by, 0.0 if reserve else None) is not None
+        # the diversified selection: lam and the pool fixed at capture (the rows are those of capture time, pinned below)
+        self.diversity, self.diversity_pool = diversity, diversity_pool
+        if rec._check_diversity(diversity, diversity_pool, top_k, () if auction else None) is not None:
+            caps.update(diversity=diversity, diversity_pool=diversity_pool)
         self._reserve = None
         self.max_exclude = int(max_exclude)
         _exclude.check_exclude(stage1_k, self.max_exclude)

@@ -5,6 +5,8 @@
 // expected revenue e = bid * pCTR with an optional per-user reserve, the cap, and generalised second prices,
 // amdrec/auction.py): a key function, a winner write-out and two kernel shapes, templated on AUCTION and CAPPED.
 // Order everywhere: (key desc, candidate slot asc), a NaN score last, a slot that is no candidate never.
+// amdrec_select_topk_diverse (amdrec/diversity.py) builds on the same key function, cap helpers and winner write-out with a
+// kernel of its own further down: the plain order gives it a pool, which it re-orders by similarity-discounted relevance.
 #include <optional>
 #include "../../include/amdrec.h"
 #include "common.hpp"
@@ -243,6 +245,244 @@ __global__ __launch_bounds__(SORT_NT) void select_sort_kernel(SelectArgs a) {
     }
 }
 
+// ---- diversified selection (amdrec_select_topk_diverse, amdrec/diversity.py has the rule) ---------------------------------
+// One workgroup of 512 per user, one dynamic LDS area used twice.  Phase A: the plain selection's keys, sorted (the cap's
+// below_group_cap filter and compaction on the sorted entries, as in the sort shape above), the first `pool` accepted ones
+// are the pool, in relevance order.  Phase B: the pool's rows are gathered over the sort's LDS (a position beyond the row
+// array, and an empty pool slot, is a row of zeros: similarity 0 or NaN, neither of which discounts).  Phase C: top_k
+// rounds.  Every wave finds the round's winner for itself from the members' (rel, m) in LDS - 64-bit keys (value image,
+// ~pool index; a NaN value in the plane below, as candidate_key's) and a wave maximum, so the choice is workgroup-uniform
+// without a barrier - then takes its share of the remaining members (DIV_RU at a time: their LDS reads are independent),
+// dots them with the winner's row and writes the new m into the OTHER of two m arrays: a wave that is still reading this
+// round's m is never overtaken, and one barrier per round suffices.  Every loop bound is top_k, pool or dim.
+constexpr int DIV_NT = SORT_NT, DIV_NW = DIV_NT / 64, DIV_RU = 4, DIV_GU = 8;
+constexpr int DIV_MAX_POOL = 128, DIV_MAX_FLOATS = 32768;
+constexpr size_t DIV_SORT_BYTES = 3ull * AMDREC_MAX_K * 8;     // keys, the run sort's second array, the groups
+constexpr size_t DIV_MAX_LDS = DIV_MAX_FLOATS * sizeof(float);
+static_assert(DIV_SORT_BYTES <= DIV_MAX_LDS, "the sort phase fits the largest row area");
+
+struct DiverseArgs {
+    const float* rows;
+    long long n_rows, ld_rows;
+    int dim;
+    float lam;
+    int pool;
+    float* out_values;
+};
+
+__device__ __forceinline__ float dot_acc(float x, float y, float acc) { return __builtin_fmaf(x, y, acc); }
+__device__ __forceinline__ float dot_acc(const f32x4& x, const f32x4& y, float acc) {
+    return __builtin_fmaf(x[3], y[3], __builtin_fmaf(x[2], y[2], __builtin_fmaf(x[1], y[1], __builtin_fmaf(x[0], y[0], acc))));
+}
+
+// One round's similarity update by one wave: members i = wv, wv + DIV_NW, ... of the pool that are still alive (bit i of
+// alive_lo / alive_hi; the winner w is not) get m_next[i] = min(1, maxNum(m_cur[i], <row i, row w>)).  T = f32x4 (dim % 4 ==
+// 0, n = dim / 4) or float (n = dim): rows of n elements of T in LDS.
+template <class T>
+__device__ __forceinline__ void diverse_update(const T* rowbuf, int n, int pool, int w, unsigned long long alive_lo,
+                                               unsigned long long alive_hi, const float* m_cur, float* m_next) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const T* rw = rowbuf + (long long)w * n;
+    for (int i0 = wv; i0 < pool; i0 += DIV_NW * DIV_RU) {
+        bool act[DIV_RU];
+        const T* ri[DIV_RU];
+        float acc[DIV_RU];
+        bool any = false;
+#pragma unroll
+        for (int u = 0; u < DIV_RU; ++u) {
+            const int i = i0 + DIV_NW * u;
+            act[u] = i < pool && (((i < 64 ? alive_lo >> i : alive_hi >> (i - 64)) & 1ull) != 0ull);
+            ri[u] = act[u] ? rowbuf + (long long)i * n : rw;
+            acc[u] = 0.0f;
+            any = any || act[u];
+        }
+        if (!any) continue;                                    // wave-uniform
+        for (int c = lane; c < n; c += 64) {
+            const T y = rw[c];
+            T x[DIV_RU];
+#pragma unroll
+            for (int u = 0; u < DIV_RU; ++u) x[u] = ri[u][c];
+#pragma unroll
+            for (int u = 0; u < DIV_RU; ++u) acc[u] = dot_acc(x[u], y, acc[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < DIV_RU; ++u)
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) acc[u] += __shfl_xor(acc[u], o, 64);
+#pragma unroll
+        for (int u = 0; u < DIV_RU; ++u) {
+            const int i = i0 + DIV_NW * u;
+            // fmaxf is maxNum: a NaN similarity leaves m as it was; m itself is never NaN
+            if (lane == 0 && act[u]) m_next[i] = fminf(1.0f, fmaxf(m_cur[i], acc[u]));
+        }
+    }
+}
+
+template <bool CAPPED>
+__global__ __launch_bounds__(DIV_NT) void select_diverse_kernel(SelectArgs a, DiverseArgs d) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char div_lds[];
+    __shared__ unsigned long long pool_key[DIV_MAX_POOL];      // the pool in relevance order; 0: no member
+    __shared__ long long pool_pos[DIV_MAX_POOL];               // the members' row positions; -1: a row of zeros
+    __shared__ float pool_rel[DIV_MAX_POOL];
+    __shared__ float pool_m[2][DIV_MAX_POOL];
+    __shared__ int win_idx[DIV_MAX_POOL];                      // per rank: the winner's pool index, -1: none
+    __shared__ float win_val[DIV_MAX_POOL];
+    const long long u = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63;
+
+    // ---- phase A: the relevance order, the cap, the pool
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(div_lds);
+    unsigned long long* other = keys + AMDREC_MAX_K;
+    for (int i = tid; i < a.k_c; i += DIV_NT) keys[i] = candidate_key<false>(a, u, i, candidate_pos(a, u, i), 0.0f);
+    if (tid < DIV_MAX_POOL) {
+        pool_key[tid] = 0ull;
+        win_idx[tid] = -1;
+    }
+    __syncthreads();
+    // the all-LDS network up to 128 keys, the per-wave run sort beyond: 512 x 500 -> 10 at pool 64 takes 64.3 us with the
+    // 500 keys through the network (a block barrier per stage) and an update in the last round, 59.7 through the runs
+    // without that update (the two were changed together)
+    const unsigned long long* sorted = sort_keys_desc<DIV_NT>(keys, other, a.k_c, 128);    // (ends behind a block barrier)
+    if constexpr (!CAPPED) {
+        if (tid < d.pool && tid < a.k_c) pool_key[tid] = sorted[tid];
+    } else {
+        long long* grp = reinterpret_cast<long long*>(other + AMDREC_MAX_K);
+        __shared__ int wave_total[SORT_ROUNDS][DIV_NW];
+        unsigned long long key[SORT_ROUNDS];
+        long long g[SORT_ROUNDS];
+#pragma unroll
+        for (int r = 0; r < SORT_ROUNDS; ++r) {
+            const int i = r * DIV_NT + tid;
+            key[r] = i < a.k_c ? sorted[i] : 0ull;
+            g[r] = key[r] != 0ull ? group_at(a.group_of, a.n_group_rows, a.cand_pos[u * a.k_c + key_pos(key[r])]) : -1ll;
+            if (i < a.k_c) grp[i] = g[r];
+        }
+        __syncthreads();
+        bool keep[SORT_ROUNDS];
+        int slot[SORT_ROUNDS];
+#pragma unroll
+        for (int r = 0; r < SORT_ROUNDS; ++r)
+            keep[r] = key[r] != 0ull && (g[r] < 0 || below_group_cap(grp, r * DIV_NT + tid, g[r], a.cap));
+        compact_slots<DIV_NT, SORT_ROUNDS>(keep, slot, wave_total);
+#pragma unroll
+        for (int r = 0; r < SORT_ROUNDS; ++r)
+            if (keep[r] && slot[r] < d.pool) pool_key[slot[r]] = key[r];
+    }
+    __syncthreads();                                           // the pool is complete, and the sort's LDS is free
+
+    // ---- phase B: relevance, and the pool's rows into LDS
+    float* rowbuf = reinterpret_cast<float*>(div_lds);
+    if (tid < DIV_MAX_POOL) {
+        // a member's row position, -1 for "a row of zeros": no member, or a position beyond the rows.  Through LDS, so that
+        // the gather's loads depend on nothing but LDS and go out back to back (with the cand_pos load inside the gather loop
+        // every row load waited for one: 512 x 500 -> 10 took 59.7 us against 58.4 at pool 64, 136.7 against 125.1 at 128)
+        const unsigned long long pk = pool_key[tid];
+        long long pos = -1ll;
+        float rel = 0.0f;
+        if (pk != 0ull) {
+            pos = a.cand_pos[u * a.k_c + key_pos(pk)];
+            rel = sigmoid_prob(a.logits[(long long)a.rank_task * a.ld + u * a.k_c + key_pos(pk)]);
+        }
+        pool_pos[tid] = pos < d.n_rows ? pos : -1ll;
+        pool_rel[tid] = rel;
+        pool_m[0][tid] = 0.0f;
+        pool_m[1][tid] = 0.0f;
+    }
+    __syncthreads();
+    const bool vec_lds = (d.dim & 3) == 0;
+    const bool vec_glb = vec_lds && (d.ld_rows & 3) == 0 && (reinterpret_cast<uintptr_t>(d.rows) & 15) == 0;
+    if (vec_glb) {
+        const int d4 = d.dim >> 2, total = d.pool * d4;
+        f32x4* rb4 = reinterpret_cast<f32x4*>(rowbuf);
+        for (int e0 = tid; e0 < total; e0 += DIV_GU * DIV_NT) {
+            f32x4 v[DIV_GU];
+#pragma unroll
+            for (int k = 0; k < DIV_GU; ++k) {
+                const int e = e0 + k * DIV_NT;
+                v[k] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                if (e < total) {
+                    const int i = e / d4, c = e - i * d4;
+                    const long long pos = pool_pos[i];
+                    if (pos >= 0) v[k] = reinterpret_cast<const f32x4*>(d.rows + pos * d.ld_rows)[c];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < DIV_GU; ++k)
+                if (e0 + k * DIV_NT < total) rb4[e0 + k * DIV_NT] = v[k];
+        }
+    } else {
+        const int total = d.pool * d.dim;
+        for (int e0 = tid; e0 < total; e0 += DIV_GU * DIV_NT) {
+            float v[DIV_GU];
+#pragma unroll
+            for (int k = 0; k < DIV_GU; ++k) {
+                const int e = e0 + k * DIV_NT;
+                v[k] = 0.0f;
+                if (e < total) {
+                    const int i = e / d.dim, c = e - i * d.dim;
+                    const long long pos = pool_pos[i];
+                    if (pos >= 0) v[k] = d.rows[pos * d.ld_rows + c];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < DIV_GU; ++k)
+                if (e0 + k * DIV_NT < total) rowbuf[e0 + k * DIV_NT] = v[k];
+        }
+    }
+    __syncthreads();
+
+    // ---- phase C: the greedy rounds.  Lane l of every wave looks after members l and l + 64
+    const float rel0 = pool_rel[lane], rel1 = pool_rel[lane + 64];
+    bool alive0 = lane < d.pool && pool_key[lane] != 0ull, alive1 = lane + 64 < d.pool && pool_key[lane + 64] != 0ull;
+    for (int r = 0; r < a.top_k; ++r) {
+        const float* m_cur = pool_m[r & 1];
+        float* m_next = pool_m[(r + 1) & 1];
+        const float m0 = m_cur[lane], m1 = m_cur[lane + 64];
+        const float v0 = rel0 * __builtin_fmaf(-d.lam, m0, 1.0f), v1 = rel1 * __builtin_fmaf(-d.lam, m1, 1.0f);
+        const unsigned long long k0 =
+            !alive0 ? 0ull : (v0 == v0) ? make_key(v0, (uint32_t)lane) : ((unsigned long long)(~(uint32_t)lane) | (1ull << 32));
+        const unsigned long long k1 =
+            !alive1 ? 0ull : (v1 == v1) ? make_key(v1, (uint32_t)(lane + 64))
+                                        : ((unsigned long long)(~(uint32_t)(lane + 64)) | (1ull << 32));
+        unsigned long long best = k0 > k1 ? k0 : k1;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long x = __shfl_xor(best, o, 64);
+            best = x > best ? x : best;
+        }
+        if (best == 0ull) break;                               // workgroup-uniform: the pool is used up, the tail stays empty
+        const int w = (int)key_pos(best);
+        if (tid == (w & 63)) {                                 // (wave 0's lane that looks after w)
+            win_idx[r] = w;
+            win_val[r] = w < 64 ? v0 : v1;
+        }
+        if (r + 1 == a.top_k) break;                           // the last winner discounts nobody
+        if (lane == (w & 63)) {
+            if (w < 64) alive0 = false;
+            else alive1 = false;
+        }
+        const unsigned long long alive_lo = __ballot(alive0), alive_hi = __ballot(alive1);
+        // members that sit this round out keep their m: a taken one is never read again, and the winner's is in win_val
+        // (lane l copies this wave's l-th member, one LDS instruction for all of them; lane 0 writes a member's updated m in a
+        // later instruction, and a wave's LDS operations execute in order)
+        {
+            const int i = (tid >> 6) + DIV_NW * lane;
+            if (i < d.pool) m_next[i] = m_cur[i];
+        }
+        if (vec_lds)
+            diverse_update<f32x4>(reinterpret_cast<const f32x4*>(rowbuf), d.dim >> 2, d.pool, w, alive_lo, alive_hi, m_cur, m_next);
+        else
+            diverse_update<float>(rowbuf, d.dim, d.pool, w, alive_lo, alive_hi, m_cur, m_next);
+        __syncthreads();
+    }
+    __syncthreads();                                           // (wave 0's win_idx / win_val)
+    for (int r = tid; r < a.top_k; r += DIV_NT) {
+        const int w = win_idx[r];
+        write_winner<false>(a, w >= 0 ? pool_key[w] : 0ull, u, r, 0.0f);
+        d.out_values[u * a.top_k + r] = w >= 0 ? win_val[r] : 0.0f;
+    }
+}
+
 template <bool AUCTION, bool CAPPED>
 static void launch_select(const SelectArgs& a, hipStream_t st) {
     if (a.top_k <= 32 && a.k_c <= 512) {                       // one wave per user, no sort
@@ -329,4 +569,50 @@ extern "C" int amdrec_select_topk_auction(const float* logits, int64_t ld_logits
                        bid_of, (long long)n_bid_rows, reserve, out_ecpm, out_price,
                        capped ? (const long long*)group_of : nullptr, capped ? (long long)n_group_rows : 0, max_per_group};
     return select_any(a, true, "select_topk_auction", (double)n_users * k_c * (capped ? 24.0 : 16.0), stream);
+}
+
+extern "C" int amdrec_select_topk_diverse(const float* logits, int64_t ld_logits, int n_tasks, int rank_task,
+                                          const int64_t* cand_ids, const int64_t* cand_pos, int64_t n_users, int k_c, int top_k,
+                                          const float* rows, int64_t n_rows, int64_t ld_rows, int dim, float lam, int pool,
+                                          const int64_t* group_of, int64_t n_group_rows, int max_per_group, int64_t* out_ids,
+                                          float* out_scores, int32_t* out_slots, float* out_values, void* stream) {
+    REQUIRE(n_tasks >= 1 && rank_task >= 0 && rank_task < n_tasks, "bad task index");
+    REQUIRE(k_c >= 1 && k_c <= AMDREC_MAX_K, "candidates per user must be in [1,%d]", AMDREC_MAX_K);
+    REQUIRE(pool >= 1 && pool <= DIV_MAX_POOL, "pool=%d out of range [1, %d]", pool, DIV_MAX_POOL);
+    REQUIRE(top_k >= 1 && top_k <= pool, "top_k=%d out of range [1, pool=%d]", top_k, pool);
+    REQUIRE(dim >= 1, "dim=%d must be >= 1", dim);
+    REQUIRE(ld_rows >= dim, "ld_rows=%lld is smaller than dim=%d", (long long)ld_rows, dim);
+    REQUIRE((long long)pool * dim <= DIV_MAX_FLOATS, "pool * dim = %lld exceeds %d (the pool's rows must fit one workgroup's LDS)",
+            (long long)pool * dim, DIV_MAX_FLOATS);
+    REQUIRE(lam >= 0.0f && lam <= 1.0f, "lam=%g must be finite and in [0, 1]", (double)lam);      // (refuses a NaN as well)
+    REQUIRE(n_rows >= 0, "n_rows=%lld is negative", (long long)n_rows);
+    REQUIRE(max_per_group >= 0 && max_per_group <= AMDREC_MAX_K, "max_per_group=%d out of range [0, %d] (0: no cap)",
+            max_per_group, AMDREC_MAX_K);
+    REQUIRE(n_group_rows >= 0, "n_group_rows=%lld is negative", (long long)n_group_rows);
+    if (n_users <= 0) return AMDREC_OK;                        // (no user: nothing to do, and no pointer is looked at)
+    const bool capped = max_per_group > 0;
+    REQUIRE(n_users <= 2147483647ll, "n_users=%lld: at most 2^31 - 1 users per call", (long long)n_users);
+    REQUIRE(cand_pos != nullptr, "null pointer: cand_pos (the diversified selection reads every pool member's row through it)");
+    REQUIRE(rows != nullptr || n_rows == 0, "null pointer: rows");
+    REQUIRE(!capped || group_of != nullptr || n_group_rows == 0, "null pointer: group_of");
+    REQUIRE(logits && cand_ids && out_ids && out_scores && out_values, "null pointer");
+    REQUIRE(ld_logits >= n_users * k_c, "ld_logits too small");
+    const SelectArgs a{logits, (long long)ld_logits, n_tasks, rank_task, (const long long*)cand_ids, (const long long*)cand_pos,
+                       k_c, top_k, (long long)n_users, (long long*)out_ids, out_scores, out_slots,
+                       nullptr, 0, nullptr, nullptr, nullptr,
+                       capped ? (const long long*)group_of : nullptr, capped ? (long long)n_group_rows : 0, max_per_group};
+    const DiverseArgs d{rows, (long long)n_rows, (long long)ld_rows, dim, lam, pool, out_values};
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const size_t row_bytes = (size_t)pool * dim * sizeof(float);
+    const size_t lds = row_bytes > DIV_SORT_BYTES ? row_bytes : DIV_SORT_BYTES;
+    static PerDeviceOnce attr_plain, attr_capped;
+    HIP_TRY((capped ? attr_capped : attr_plain)
+                .set_dynamic_lds(capped ? reinterpret_cast<const void*>(select_diverse_kernel<true>)
+                                        : reinterpret_cast<const void*>(select_diverse_kernel<false>), DIV_MAX_LDS));
+    ProfScope prof("select_topk_diverse", 2.0 * n_users * top_k * pool * dim,
+                   (double)n_users * (k_c * 20.0 + (double)row_bytes), st);
+    if (capped) hipLaunchKernelGGL(select_diverse_kernel<true>, dim3((unsigned)n_users), dim3(DIV_NT), lds, st, a, d);
+    else hipLaunchKernelGGL(select_diverse_kernel<false>, dim3((unsigned)n_users), dim3(DIV_NT), lds, st, a, d);
+    HIP_TRY(hipGetLastError());
+    return AMDREC_OK;
 }
