@@ -461,6 +461,15 @@ typedef struct {
     int64_t chunks_win;
     const void* stream_win_cs;
     int64_t chunks_win_cs;
+    /* Products per MAC (added to ABI v14 without a version step: a new field at the struct's end, 0 in zero-initialised
+     * parameters).  0 or 3: the fp16x3 arithmetic above.  1: the single-product engine - a product is ah*bh alone, ONE fp16
+     * MFMA per MAC on the high planes of the SAME streams, scales, bounds and parameter blobs (nothing else is packed for it;
+     * the low fragment sets travel with the chunks and are never read).  Opt-in reduced precision: operands carry 11
+     * significant bits, logits come out with a relative error near 1e-4 of the row maximum instead of fp32's 1e-7.  Needs
+     * variant 16; every pass runs the 64-row (<= 16384 rows) or the 128-row shape of the 16-row kernel - never the
+     * column-split or the 32-row kernel - with the fold, the hidden cache and the CTR-first streams as under 3.  Any other
+     * value makes the parameters ineligible for the engine. */
+    int64_t products;
 } amdrec_x3_weights;
 
 typedef struct {

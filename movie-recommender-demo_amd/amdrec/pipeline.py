@@ -81,7 +81,7 @@ class AdRecommenderInference:
                  transformer_ranker: Optional[TransformerRanker] = None,
                  faiss_index: Optional[FAISSIndex] = None, ad_features=None,
                  preprocessor: Optional[Preprocessor] = None, verbose: bool = False,
-                 cache_ad_projection: bool = True, heads: str = "all"):
+                 cache_ad_projection: bool = True, heads: str = "all", ranker_engine: Optional[str] = None):
         """Either ``model_dir`` (files below) or the components directly.
         model_dir: preprocessor.json, two_tower_{best,final}.pt, transformer_ranker_{best,final}.pt,
         faiss_index.bin (+ .metadata) in this build's format, ad_features.npy [N, 20].
@@ -91,7 +91,11 @@ class AdRecommenderInference:
         ``B * top_k`` winners' stored trunk rows (TransformerRanker.score_ctr_first / winner_scores).  ad_ids, scores and
         the CTR logits are bit-identical in both modes; in "ctr_first" ``logits`` holds the CTR row alone.  The mode does
         what it is told wherever it can run (``heads_mode_effective``); it is no tuning switch - DESIGN.md has the
-        measured batch sizes at which it pays."""
+        measured batch sizes at which it pays.
+        ``ranker_engine``: the ranker's ``gemm_engine`` (TransformerRanker.ALL_ENGINES), set before its first pack; None leaves
+        the ranker as it is.  "f16" is the opt-in single-product fp16 engine (reduced precision: DESIGN.md)."""
+        if ranker_engine is not None and ranker_engine not in TransformerRanker.ALL_ENGINES:
+            raise ValueError(f"ranker_engine must be None or one of {TransformerRanker.ALL_ENGINES}")
         self.heads_mode = self._check_heads(heads)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -127,6 +131,8 @@ class AdRecommenderInference:
             self.two_tower_model = two_tower_model.to(self.device).eval()
             self.transformer_ranker = transformer_ranker.to(self.device).eval()
             self.faiss_index = faiss_index
+        if ranker_engine is not None:
+            self.transformer_ranker.gemm_engine = ranker_engine
         if isinstance(ad_features, torch.Tensor):
             self.ad_features = ad_features.to(device=self.device, dtype=torch.int64).contiguous()
         else:

@@ -115,7 +115,7 @@ class TransformerRanker(nn.Module):
         self.fuse_attention = True
         # encoder layer 1's attention block folded into the feature projection (exact algebra at seq_len 1: x0 + W_ov x0 +
         # b_ov is linear in the projection's input; weights.folded_projection).  Needs fuse_attention and applies only
-        # where every pass runs the row-owner kernel (gemm_engine "f16x3" on its architecture, x3_min_rows = 1): one
+        # where every pass runs the row-owner kernel (gemm_engine "f16x3" or "f16" on its architecture, x3_min_rows = 1): one
         # 256 x 256 GEMM less per candidate row.  The fp32 / bf16x6 engines keep the unfolded chain.
         self.fold_first_attention = True
         # stage 1 of layer 1's FFN served from a second per-ad cache (weights.first_ffn_cache: with the fold,
@@ -131,6 +131,13 @@ class TransformerRanker(nn.Module):
         #  "bf16x6" the round-1 tile GEMMs on three bf16 planes, six products per MAC (also the fallback of "f16x3" for
         #           architectures the row-owner kernel is not written for)
         #  "fp32"   fp32 MFMA everywhere
+        # and one opt-in engine of REDUCED precision:
+        #  "f16"    the row-owner 16-row kernels with ONE fp16-MFMA product per MAC on the high planes of the streams that
+        #           "f16x3" packs (csrc/rowowner16.hpp "SINGLE PRODUCT"): operands carry 11 significant bits, logits differ
+        #           from fp32's by about 1e-4 of a row's largest activation (DESIGN.md "Ranker: single-product fp16
+        #           engine").  Every pass runs it - fold, hidden cache, CTR-first and graph capture as under "f16x3" - so it
+        #           needs x3_variant 16 and x3_min_rows 1 (ValueError at pack time otherwise); on an architecture the
+        #           row-owner kernels are not written for it falls back as "f16x3" does, to the fp32-accurate tile GEMMs
         self.gemm_engine = "f16x3"
         # smallest pass that takes the row-owner kernel.  1 = every batch: one launch (~0.35 ms per 128-row round, bound by
         # one CU's weight-stream rate) matches the ~25 small launches of the fp32 path at a single request (0.60 ms end to
@@ -142,7 +149,12 @@ class TransformerRanker(nn.Module):
         # 500 candidates), -1 = never
         self.x3_cs_max_rows = 0
 
+    # ENGINES: the engines of fp32-level error - accuracy sweeps iterate this tuple and hold every member to the fp32 engine's
+    # error.  REDUCED_ENGINES: the opt-in engines that trade accuracy for speed; ``gemm_engine`` takes a name of either.
     ENGINES = ("f16x3", "bf16x6", "fp32")
+    REDUCED_ENGINES = ("f16",)
+    ALL_ENGINES = ENGINES + REDUCED_ENGINES
+    ROW_OWNER_ENGINES = ("f16x3", "f16")      # the engines of csrc/ranker_x3.hip: three products per MAC, or one
     SMALL_ROWS = 8192       # passes of at most this many rows run the fp32-MFMA small shapes (csrc/layers.hip)
 
     def x3_fallback_reason(self):
@@ -165,7 +177,7 @@ class TransformerRanker(nn.Module):
         return c[1]
 
     def _ctr_first_unsupported_reason(self):
-        if self.gemm_engine != "f16x3":
+        if self.gemm_engine not in self.ROW_OWNER_ENGINES:
             return f"gemm_engine {self.gemm_engine!r} (the mode runs on the f16x3 row-owner kernels only)"
         why = self.x3_fallback_reason()
         if why is not None:
@@ -184,10 +196,10 @@ class TransformerRanker(nn.Module):
     def gemm_engine_for(self, rows: int) -> str:
         """The engine a pass of ``rows`` rows actually runs on."""
         eng = self.gemm_engine
-        if eng == "f16x3":
+        if eng in self.ROW_OWNER_ENGINES:
             if weights.x3_eligible(self.state_dict(), self.fuse_attention):
-                return "f16x3" if rows >= self.x3_min_rows else "fp32"
-            eng = "bf16x6"
+                return eng if rows >= self.x3_min_rows else "fp32"       # ("f16": x3_min_rows is 1, _pack refuses others)
+            eng = "bf16x6"                                                # no reduced-precision fallback
         return eng if rows > self.SMALL_ROWS else "fp32"
 
     # -- packing ----------------------------------------------------------------------
@@ -333,8 +345,8 @@ class TransformerRanker(nn.Module):
         return getattr(self._entry_for(table), "hidden", None)
 
     def _pack(self, device):
-        if self.gemm_engine not in self.ENGINES:
-            raise ValueError(f"gemm_engine must be one of {self.ENGINES}")
+        if self.gemm_engine not in self.ALL_ENGINES:
+            raise ValueError(f"gemm_engine must be one of {self.ALL_ENGINES}")
         # (the key - and with it the ad-projection cache, which is only served for the key it was built under - covers the
         # fold: an engine switch repacks and rebuilds the cache in the other projection form)
         key = (str(device), self.fuse_attention, bool(self.fold_first_attention), bool(self.cache_first_ffn),
@@ -342,16 +354,23 @@ class TransformerRanker(nn.Module):
                _lib.tensor_versions(self))
         if self._packed is None or self._packed.key != key:
             sd = self.state_dict()
-            why = weights.x3_ineligible_reason(sd, self.fuse_attention) if self.gemm_engine == "f16x3" else None
-            x3 = self.gemm_engine == "f16x3" and why is None
+            row_owner = self.gemm_engine in self.ROW_OWNER_ENGINES
+            if self.gemm_engine == "f16" and int(self.x3_variant) != 16:
+                raise ValueError(f"gemm_engine 'f16' runs on the 16-row kernels only (x3_variant {self.x3_variant})")
+            if self.gemm_engine == "f16" and int(self.x3_min_rows) != 1:
+                raise ValueError(f"gemm_engine 'f16' runs every pass or none: x3_min_rows must be 1, not {self.x3_min_rows} "
+                                 "(fp16 for some batch sizes and fp32 for others is a trap)")
+            why = weights.x3_ineligible_reason(sd, self.fuse_attention) if row_owner else None
+            x3 = row_owner and why is None
             if why is not None:
                 import warnings
-                warnings.warn(f"amdrec TransformerRanker: gemm_engine 'f16x3' is not available for these weights ({why}); "
+                warnings.warn(f"amdrec TransformerRanker: gemm_engine {self.gemm_engine!r} is not available for these weights ({why}); "
                               f"running the generic tile GEMMs (bf16x6 above {self.SMALL_ROWS} rows, fp32 MFMA below)",
                               RuntimeWarning, stacklevel=3)
             self._packed = _Packed(key, *weights.pack_ranker(
                 sd, self._user_names, self._ad_names, self._n_num, device, fuse_attention=self.fuse_attention,
-                x6=self.gemm_engine == "bf16x6" or (self.gemm_engine == "f16x3" and not x3), x3=x3,
+                x6=self.gemm_engine == "bf16x6" or (row_owner and not x3), x3=x3,
+                x3_products=1 if self.gemm_engine == "f16" else 3,
                 x3_min_rows=self.x3_min_rows, x3_variant=self.x3_variant, x3_cs_max_rows=self.x3_cs_max_rows,
                 fold_first_attention=bool(self.fold_first_attention), cache_first_ffn=bool(self.cache_first_ffn)))
         return self._packed.params, self._packed.tasks

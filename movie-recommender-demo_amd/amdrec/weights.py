@@ -30,6 +30,7 @@ class EncoderLayer(C.Structure):
 
 
 class X3Weights(C.Structure):
+    # (amdrec_x3_weights up to its CTR-first streams; what the header appended since is in X3WeightsP below)
     _fields_ = [("stream", _FP), ("chunks", C.c_int64), ("min_rows", C.c_int64), ("params", _FP), ("n_params", C.c_int64),
                 ("variant", C.c_int64),
                 ("sw_ov", C.c_float * MAX_LAYERS), ("sw_1", C.c_float * MAX_LAYERS), ("sw_2", C.c_float * MAX_LAYERS),
@@ -41,6 +42,12 @@ class X3Weights(C.Structure):
                 ("stream_ctr", _FP), ("chunks_ctr", C.c_int64), ("stream_ctr_cs", _FP), ("chunks_ctr_cs", C.c_int64),
                 ("stream_ctr_hc", _FP), ("chunks_ctr_hc", C.c_int64), ("stream_win", _FP), ("chunks_win", C.c_int64),
                 ("stream_win_cs", _FP), ("chunks_win_cs", C.c_int64)]
+
+
+class X3WeightsP(X3Weights):
+    """amdrec_x3_weights as the header has it now: ctypes lays a subclass's fields behind its base's, which is where the
+    header appended ``products`` (0 / 3: the fp16x3 arithmetic, 1: the single-product engine)."""
+    _fields_ = [("products", C.c_int64)]
 
 
 class RankerParams(C.Structure):
@@ -58,7 +65,7 @@ class RankerParams(C.Structure):
                 ("head_w3", _FP * MAX_TASKS), ("head_b3", _FP * MAX_TASKS),
                 ("ad_proj_cache", _FP), ("ld_ad_proj_cache", C.c_int64),
                 ("ad_hidden_cache", _FP), ("ld_ad_hidden_cache", C.c_int64),
-                ("cross_wt_x6", _FP * MAX_LAYERS), ("head_w1_x6", _FP), ("x3", X3Weights)]
+                ("cross_wt_x6", _FP * MAX_LAYERS), ("head_w1_x6", _FP), ("x3", X3WeightsP)]
 
 
 def _np64(t):
@@ -747,7 +754,7 @@ def pack_ctr_first(p: RankerParams, pk: Packed) -> bool:
 def pack_ranker(sd: Dict, user_names: List[str], ad_names: List[str], n_num: int, device, ln_eps=1e-5,
                 fuse_attention: bool = True, x6: bool = True, x3: bool = False, x3_min_rows: int = 0,
                 x3_variant: int = 32, x3_cs_max_rows: int = 0, fold_first_attention: bool = False,
-                cache_first_ffn: bool = False):
+                cache_first_ffn: bool = False, x3_products: int = 3):
     """state_dict-like of the reference TransformerRanker -> (RankerParams, Packed, task names).
     ``fuse_attention``: pre-multiply W_ov = W_o W_v, b_ov = W_o b_v + b_o in float64 (``ranker_chain``), so each encoder layer's
     attention block is one GEMM instead of two.
@@ -758,7 +765,16 @@ def pack_ranker(sd: Dict, user_names: List[str], ad_names: List[str], n_num: int
     layer), pack the projection as ``folded_projection`` (rounded once to fp32) and the engine's chain without layer 1's
     W_ov / b_ov (amdrec_x3_weights.fold_attn1); otherwise it has no effect.
     ``cache_first_ffn``: with the fold on the 16-row kernel, also pack what the first-FFN hidden cache needs (``first_ffn_cache``;
-    amdrec_x3_weights.stream_hc ...); otherwise it has no effect."""
+    amdrec_x3_weights.stream_hc ...); otherwise it has no effect.
+    ``x3_products``: 3, or 1 for the single-product engine (amdrec_x3_weights.products): the same streams, scales and blobs,
+    read by the kernels that multiply the high planes alone.  Needs ``x3_variant`` 16 and ``x3_min_rows`` 1 - a ranker that
+    is half precision for some batch sizes and fp32 for others is a trap - and changes nothing where x3 is not packed."""
+    if int(x3_products) not in (1, 3):
+        raise ValueError("x3_products must be 3 or 1")
+    if x3 and int(x3_products) == 1 and int(x3_variant) != 16:
+        raise ValueError(f"the single-product engine runs on the 16-row kernels only (x3_variant {x3_variant})")
+    if x3 and int(x3_products) == 1 and int(x3_min_rows) != 1:
+        raise ValueError(f"the single-product engine runs every pass or none (x3_min_rows {x3_min_rows}, must be 1)")
     pk = Packed(device)
     tables = [sd[f"user_embeddings.{n}.weight"] for n in user_names] + \
              [sd[f"ad_embeddings.{n}.weight"] for n in ad_names]
@@ -797,4 +813,5 @@ def pack_ranker(sd: Dict, user_names: List[str], ad_names: List[str], n_num: int
         p.x3.variant, p.x3.fold_attn1 = x3_variant, int(fold)
         p.x3.min_rows, p.x3.cs_max_rows = int(x3_min_rows), int(x3_cs_max_rows)
         _pack_x3(p, pk, ch, wproj, bproj, nu, na, cache_first_ffn)
+        p.x3.products = int(x3_products) if int(x3_products) == 1 else 0      # (0: what packs have always carried)
     return p, pk, ch.tasks

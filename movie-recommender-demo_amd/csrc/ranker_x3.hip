@@ -23,6 +23,8 @@ static long long x3_param_floats(const amdrec_ranker_params* p) {
 static bool x3_eligible(const amdrec_ranker_params* p) {
     if (p->x3.stream == nullptr || p->x3.chunks <= 0 || p->x3.params == nullptr) return false;
     if (p->x3.variant != 16 && p->x3.variant != 32) return false;
+    if (p->x3.products != 0 && p->x3.products != 1 && p->x3.products != 3) return false;
+    if (p->x3.products == 1 && p->x3.variant != 16) return false;     // the single-product kernels are 16-row kernels
     if (x3_param_floats(p) > x3::PARAM_FLOATS) return false;      // the parameter blob must fit its LDS area
     // d_ff is a placeholder without encoder layers (amdrec/weights.py pack_ranker)
     if (p->d_model != 256 || (p->n_layers > 0 && p->d_ff % 32 != 0) || p->head_h1 % 32 != 0 || p->head_h2 != 64) return false;
@@ -45,8 +47,12 @@ constexpr long long X3B4_MAX_ROWS = 256ll * 64;      // one 64-row workgroup per
 // rows by default.  16-row variant otherwise: 64-row workgroups of four waves (one per SIMD) while the pass fits the chip
 // once in that shape (<= 256 CUs x 64 rows) - it finishes in ~0.7 of the 128-row shape's time (one request's 500 rows: 0.20
 // against 0.28 ms, profiles/r03_x3b_waves.log); beyond it the 128-row shape's two waves per SIMD win.
+// amdrec_x3_weights.products == 1 (the single-product engine: x1b / x1b4 of rowowner16.hpp) has the two row-owner shapes of
+// the 16-row kernel and nothing else: never ColSplit, never Rows32x128 (x3_eligible).
 enum class X3Shape { Rows32x128, Rows16x128, Rows16x64, ColSplit };
+static bool x3_single_product(const amdrec_ranker_params* p) { return p->x3.products == 1; }
 static X3Shape x3_shape(const amdrec_ranker_params* p, long long rows) {
+    if (x3_single_product(p)) return rows <= X3B4_MAX_ROWS ? X3Shape::Rows16x64 : X3Shape::Rows16x128;
     const long long cs_rows = p->x3.cs_max_rows > 0 ? p->x3.cs_max_rows : (p->x3.cs_max_rows < 0 ? 0 : x3c::MAX_ROWS);
     if (x3c_available(p) && rows <= cs_rows) return X3Shape::ColSplit;
     if (p->x3.variant != 16) return X3Shape::Rows32x128;
@@ -168,10 +174,11 @@ static size_t x3_scratch_bytes(long long rows) {
     return (size_t)((rows + x3::ROWS_PER_WG - 1) / x3::ROWS_PER_WG) * x3::ROWS_PER_WG * 256 * 4;
 }
 
-// tag: the launch's profile tag, where it is not the kernel shape's own
+// tag: the launch's profile tag, where it is not the kernel shape's own; single: the single-product kernels (Rows16x128 /
+// Rows16x64 only)
 static int x3_launch(const x3::Program& G, const x3::Input& in, long long rows, float* scratch, float* x_out,
                      long long ld_xout, float* logits, long long ld_logits, hipStream_t st, X3Shape shape,
-                     const char* tag = nullptr) {
+                     const char* tag = nullptr, bool single = false) {
     static PerDeviceOnce attr_done;
     if (attr_done.pending()) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(x3::ranker_x3_kernel),
@@ -181,6 +188,18 @@ static int x3_launch(const x3::Program& G, const x3::Input& in, long long rows, 
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(x3b4::ranker_x3b_kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, x3::RING_BYTES + x3::PARAM_FLOATS * 4));
         attr_done.mark();
+    }
+    if (single) {
+        REQUIRE(shape == X3Shape::Rows16x128 || shape == X3Shape::Rows16x64, "x3: the single-product engine has the 16-row "
+                "row-owner shapes only");
+        static PerDeviceOnce attr_single;
+        if (attr_single.pending()) {
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(x1b::ranker_x3b_kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, x3::RING_BYTES + x3::PARAM_FLOATS * 4));
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(x1b4::ranker_x3b_kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, x3::RING_BYTES + x3::PARAM_FLOATS * 4));
+            attr_single.mark();
+        }
     }
     if (shape == X3Shape::ColSplit) {                  // (the caller built G on that kernel's stream)
         static PerDeviceOnce attr_cs;
@@ -204,9 +223,16 @@ static int x3_launch(const x3::Program& G, const x3::Input& in, long long rows, 
         // algorithmic FLOPs: 2 * rows * sum over the phases' weight elements (bench.py prices them against bf16 MFMA / 3)
         const double w = x3_weight_elements(G);
         const double hidden_bytes = in.hcache != nullptr ? 4.0 * 32.0 * G.ph[1].n_steps : 0.0;   // a row of P (Q: one per user)
-        ProfScope prof(tag ? tag : small ? "ranker_rowowner16_64_x3" : (shape == X3Shape::Rows16x128 ? "ranker_rowowner16_128_x3" : "ranker_rowowner_128_x3"),
+        ProfScope prof(tag ? tag : single ? (small ? "ranker_rowowner16_64_f16" : "ranker_rowowner16_128_f16")
+                       : small ? "ranker_rowowner16_64_x3" : (shape == X3Shape::Rows16x128 ? "ranker_rowowner16_128_x3" : "ranker_rowowner_128_x3"),
                        2.0 * (double)rows * w, (double)rows * (1024.0 + 12.0 + hidden_bytes), st);
-        if (small)
+        if (single && small)
+            hipLaunchKernelGGL(x1b4::ranker_x3b_kernel, dim3(grid), dim3(64 * x1b4::WAVES), x3::RING_BYTES + x3::PARAM_FLOATS * 4, st,
+                               G, in, rows, scratch, x_out, ld_xout, logits, ld_logits);
+        else if (single)
+            hipLaunchKernelGGL(x1b::ranker_x3b_kernel, dim3(grid), dim3(512), x3::RING_BYTES + x3::PARAM_FLOATS * 4, st, G, in,
+                               rows, scratch, x_out, ld_xout, logits, ld_logits);
+        else if (small)
             hipLaunchKernelGGL(x3b4::ranker_x3b_kernel, dim3(grid), dim3(64 * x3b4::WAVES), x3::RING_BYTES + x3::PARAM_FLOATS * 4, st,
                                G, in, rows, scratch, x_out, ld_xout, logits, ld_logits);
         else if (shape == X3Shape::Rows16x128)
@@ -269,7 +295,7 @@ int ranker_x3_run(const amdrec_ranker_params* p, const float* X, long long ldx, 
         in.row_base = row_base; in.rowdiv = rowdiv; in.ldu = ldu;
         if (hc) { in.hcache = p->ad_hidden_cache; in.ldh = p->ld_ad_hidden_cache; in.Q = U + 256; }
     }
-    return x3_launch(G, in, rows, scratch, x_out, ld_xout, logits, ld_logits, st, shape);
+    return x3_launch(G, in, rows, scratch, x_out, ld_xout, logits, ld_logits, st, shape, nullptr, x3_single_product(p));
 }
 }  // namespace amdrec
 
@@ -322,7 +348,8 @@ extern "C" int amdrec_ranker_winner_heads(const amdrec_ranker_params* p, const f
     x3::Input in{};
     in.X = trunk; in.ldx = ld_trunk; in.ldu = 256;
     in.slots = slots; in.top_k = top_k; in.k_c = k_c; in.n_x = n_trunk_rows;
-    if ((rc = x3_launch(G, in, rows, nullptr, nullptr, 0, w.logits, rows, st, shape, "ranker_winner_heads_x3"))) return rc;
+    if ((rc = x3_launch(G, in, rows, nullptr, nullptr, 0, w.logits, rows, st, shape,
+                        x3_single_product(p) ? "ranker_winner_heads_f16" : "ranker_winner_heads_x3", x3_single_product(p)))) return rc;
     hipLaunchKernelGGL(winner_scores_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, w.logits, slots, rows,
                        p->n_tasks - 1, out_scores);
     HIP_TRY(hipGetLastError());
@@ -374,5 +401,5 @@ extern "C" int amdrec_ranker_x3_prefix(const amdrec_ranker_params* p, const floa
         HIP_TRY(hipGetLastError());
         in.X = scratch; in.ldx = 256;
     }
-    return x3_launch(G, in, rows, scratch, x_out, ld_out, logits, ld_logits, st, shape);
+    return x3_launch(G, in, rows, scratch, x_out, ld_out, logits, ld_logits, st, shape, nullptr, x3_single_product(p));
 }

@@ -18,11 +18,21 @@
 //     gemm256 : for ks < 8: for tile pair tp < 8: {A_h(2tp, ks), A_l(2tp, ks), A_h(2tp+1, ks), A_l(2tp+1, ks)}
 //     ffn step t: for u < 8: stage 1 {W_1 tiles 2t, 2t+1 at ks = u}, then stage 2 {W_2 tiles 2u, 2u+1 at k-step t-1}
 //     heads, per task and hidden tile (32): stage 1 as above (8 groups), stage 2 {W_2 tiles 0,1}, {tiles 2,3} at k-step t
+//
+// SINGLE PRODUCT (x1b / x1b4, amdrec_x3_weights.products == 1: the opt-in half-precision engine).  The same kernel on the
+// same streams with the two correction products left out: a product a*b is ah*bh alone, one fp16 MFMA per MAC - a relative
+// error of 2^-12 per operand where the three products leave 2^-22.  The scaling above still rules out fp16 overflow, so the
+// high planes alone are a well-conditioned fp16 operand; no low plane is formed (half the plane-split vector work), a
+// group's low fragment sets stay unread in LDS (half the fragment reads) and the paired FFN exchanges no low planes.
+// Ring, DMA pieces, vmcnt counts, barriers, scales, bounds, the 60000 clamp, LayerNorm, epilogues and keep_nan are the
+// three-product kernel's (an infinite row: its high plane is infinite, and inf * w summed over both signs of w - or met by
+// a zero weight - is NaN or infinite in the probe accumulator, which keep_nan maps to NaN alike).
 #pragma once
 #include "rowowner16_common.hpp"
 
 #define AMDREC_X3B_NAMESPACE x3b
 #define AMDREC_X3B_WAVES 8
+#define AMDREC_X3B_PRODUCTS 3
 #include "rowowner16_impl.hpp"
 #undef AMDREC_X3B_NAMESPACE
 #undef AMDREC_X3B_WAVES
@@ -32,3 +42,19 @@
 #include "rowowner16_impl.hpp"
 #undef AMDREC_X3B_NAMESPACE
 #undef AMDREC_X3B_WAVES
+#undef AMDREC_X3B_PRODUCTS
+
+// x1b (128 rows, paired FFN, cached first FFN), x1b4 (64 rows): the single-product engine
+#define AMDREC_X3B_PRODUCTS 1
+#define AMDREC_X3B_NAMESPACE x1b
+#define AMDREC_X3B_WAVES 8
+#include "rowowner16_impl.hpp"
+#undef AMDREC_X3B_NAMESPACE
+#undef AMDREC_X3B_WAVES
+
+#define AMDREC_X3B_NAMESPACE x1b4
+#define AMDREC_X3B_WAVES 4
+#include "rowowner16_impl.hpp"
+#undef AMDREC_X3B_NAMESPACE
+#undef AMDREC_X3B_WAVES
+#undef AMDREC_X3B_PRODUCTS

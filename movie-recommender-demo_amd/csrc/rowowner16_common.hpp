@@ -13,11 +13,17 @@ __device__ __forceinline__ f32x4 mfma(const f16x8& a, const f16x8& b, const f32x
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 // one group of 4 fragment sets {Ah(t0), Al(t0), Ah(t1), Al(t1)} against one B k-step (bh, bl): 6 MFMAs, two accumulators interleaved
+// NP (here and below): products per MAC.  3 = the fp16x3 arithmetic; 1 = the single-product engine (rowowner16.hpp): the
+// high-by-high MFMAs alone, no low plane is formed (`bl` / `l` are never written) and a[1], a[3] are never read
+template <int NP = 3>
 __device__ __forceinline__ void group6(const f16x8 (&a)[4], const f16x8& bh, const f16x8& bl, f32x4& c0, f32x4& c1) {
-    c0 = mfma(a[0], bl, c0);
-    c1 = mfma(a[2], bl, c1);
-    c0 = mfma(a[1], bh, c0);
-    c1 = mfma(a[3], bh, c1);
+    static_assert(NP == 3 || NP == 1, "three products or one");
+    if constexpr (NP == 3) {
+        c0 = mfma(a[0], bl, c0);
+        c1 = mfma(a[2], bl, c1);
+        c0 = mfma(a[1], bh, c0);
+        c1 = mfma(a[3], bh, c1);
+    }
     c0 = mfma(a[0], bh, c0);
     c1 = mfma(a[2], bh, c1);
 }
@@ -45,13 +51,14 @@ __device__ __forceinline__ void row_scale(const f32x4 (&x)[16], float& s, float&
 }
 
 // planes of one k-step from two adjacent tiles (elements 0..3 from `a`, 4..7 from `b`), scaled by s
+template <int NP = 3>
 __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, float s, f16x8& h, f16x8& l) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float v = (j < 4 ? a[j & 3] : b[j & 3]) * s;
         const _Float16 hh = (_Float16)v;
         h[j] = hh;
-        l[j] = (_Float16)(v - (float)hh);
+        if constexpr (NP == 3) l[j] = (_Float16)(v - (float)hh);
     }
 }
 
@@ -60,12 +67,12 @@ __device__ __forceinline__ f32x4 param4(lds_cfloat* pb, int off, int tile) {    
 }
 
 // planes + initial accumulators, tile pair by tile pair (x[2ks], x[2ks+1] die as they are consumed)
-template <bool WITH_X>
+template <bool WITH_X, int NP = 3>
 __device__ __forceinline__ void prepare(const f32x4 (&x)[16], float s, lds_cfloat* pb, int bias, float scale,
                                         f16x8 (&xh)[8], f16x8 (&xl)[8], f32x4 (&acc)[16]) {
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
-        split8(x[2 * ks], x[2 * ks + 1], s, xh[ks], xl[ks]);
+        split8<NP>(x[2 * ks], x[2 * ks + 1], s, xh[ks], xl[ks]);
 #pragma unroll
         for (int t = 2 * ks; t < 2 * ks + 2; ++t) {
             const f32x4 b = param4(pb, bias, t);
@@ -131,6 +138,7 @@ __device__ __forceinline__ void layer_norm_scaled(const f32x4 (&acc)[16], float 
 
 // hidden tile (two 16-feature accumulators = one k-step of stage 2) -> planes
 // `lim` = 60000 / c (exact: c is a power of two)
+template <int NP = 3>
 __device__ __forceinline__ void hidden_planes(const f32x4& a0, const f32x4& a1, float c, float lim, f16x8& hh, f16x8& hl) {
     if (DBG & 8) {
         asm volatile("" : "+v"(hh), "+v"(hl) : "v"(a0), "v"(a1));
@@ -144,7 +152,7 @@ __device__ __forceinline__ void hidden_planes(const f32x4& a0, const f32x4& a1, 
         t0[r] = __builtin_amdgcn_fmed3f(a0[r], 0.f, lim);
         t1[r] = __builtin_amdgcn_fmed3f(a1[r], 0.f, lim);
     }
-    split8(t0, t1, c, hh, hl);
+    split8<NP>(t0, t1, c, hh, hl);
 }
 __device__ __forceinline__ void init_pair(f32x4& a0, f32x4& a1, lds_cfloat* pb, int bias, int tile0, float scale) {
     const f32x4 b0 = param4(pb, bias, tile0), b1 = param4(pb, bias, tile0 + 1);

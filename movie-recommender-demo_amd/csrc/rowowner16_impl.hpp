@@ -1,8 +1,10 @@
 // Body of the 16-rows-per-wave row-owner kernel (design and geometry: rowowner16.hpp; helpers that do not depend on the
 // workgroup shape: rowowner16_common.hpp): the ring, the step and phase drivers and the kernel, included once per
-// workgroup shape with AMDREC_X3B_NAMESPACE / AMDREC_X3B_WAVES set - x3b: 8 waves = 128 rows per workgroup (two waves per
-// SIMD, the throughput shape), x3b4: 4 waves = 64 rows (one wave per SIMD: a pass of <= 16384 rows spreads over twice the
-// CUs and a wave has its SIMD to itself - 0.20 instead of 0.28 ms for one request's 500 rows, tools/x3_probe.hip).
+// workgroup shape and product count with AMDREC_X3B_NAMESPACE / AMDREC_X3B_WAVES / AMDREC_X3B_PRODUCTS set - x3b: 8 waves =
+// 128 rows per workgroup (two waves per SIMD, the throughput shape), x3b4: 4 waves = 64 rows (one wave per SIMD: a pass
+// of <= 16384 rows spreads over twice the CUs and a wave has its SIMD to itself - 0.20 instead of 0.28 ms for one
+// request's 500 rows, tools/x3_probe.hip);
+// x1b / x1b4: the same two shapes with ONE product per MAC (rowowner16.hpp "SINGLE PRODUCT").
 // No include guard.  What was tried here and not adopted: profiles/HISTORY.md "Row-owner 16-row kernel: switches".
 
 // (a step without stage 2 is passed the not-yet-written hidden planes by reference and never reads them)
@@ -13,13 +15,32 @@ namespace AMDREC_X3B_NAMESPACE {
 
 using x3::CHUNK_BYTES, x3::CHUNK_FRAGS, x3::DBG, x3::f16x8, x3::FRAG_BYTES, x3::Input, x3::lds_byte, x3::lds_cfloat, x3::Phase,
     x3::Program, x3::RING_BYTES;
-using x16::add_rows, x16::group6, x16::hidden_planes, x16::init_pair, x16::layer_norm, x16::layer_norm_scaled, x16::load_rows,
-    x16::param4, x16::prepare, x16::reduce_sum4, x16::row_scale, x16::split8, x16::store_rows;
+using x16::add_rows, x16::init_pair, x16::layer_norm, x16::layer_norm_scaled, x16::load_rows, x16::param4, x16::reduce_sum4,
+    x16::row_scale, x16::store_rows;
 
-#if !defined(AMDREC_X3B_WAVES) || !defined(AMDREC_X3B_NAMESPACE)
+#if !defined(AMDREC_X3B_WAVES) || !defined(AMDREC_X3B_NAMESPACE) || !defined(AMDREC_X3B_PRODUCTS)
 #error "include rowowner16.hpp, not this file"
 #endif
 constexpr int WAVES = AMDREC_X3B_WAVES, ROWS_PER_WAVE = 16, ROWS_PER_WG = WAVES * ROWS_PER_WAVE;
+// Products per MAC: 3, or 1 = high planes only.  With 1 no low plane exists: the `xl` / `hl` / `bl` operands below are
+// declared and handed on as before but never written, read, or exchanged between the waves of a pair, and a group's low
+// fragment sets (1 and 3) are never read from LDS.  Ring, DMA, waits and barriers do not depend on it.
+constexpr int PRODUCTS = AMDREC_X3B_PRODUCTS;
+constexpr bool LOW = PRODUCTS == 3;
+__device__ __forceinline__ void group6(const f16x8 (&a)[4], const f16x8& bh, const f16x8& bl, f32x4& c0, f32x4& c1) {
+    x16::group6<PRODUCTS>(a, bh, bl, c0, c1);
+}
+__device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, float s, f16x8& h, f16x8& l) {
+    x16::split8<PRODUCTS>(a, b, s, h, l);
+}
+template <bool WITH_X>
+__device__ __forceinline__ void prepare(const f32x4 (&x)[16], float s, lds_cfloat* pb, int bias, float scale, f16x8 (&xh)[8],
+                                        f16x8 (&xl)[8], f32x4 (&acc)[16]) {
+    x16::prepare<WITH_X, PRODUCTS>(x, s, pb, bias, scale, xh, xl, acc);
+}
+__device__ __forceinline__ void hidden_planes(const f32x4& a0, const f32x4& a1, float c, float lim, f16x8& hh, f16x8& hl) {
+    x16::hidden_planes<PRODUCTS>(a0, a1, c, lim, hh, hl);
+}
 constexpr int DMA_PER_WAVE = CHUNK_FRAGS / WAVES;     // 2 fragment sets per wave and chunk
 // The 128-row shape runs PH_FFN_LN split by STAGE over pairs of waves (phase_ffn_ln_role_a, phase_ffn_ln_role_b below).  Its hand-off area is
 // the ring's last slot: the ring is one chunk shorter there (NBUF 6 and 7 measured the same,
@@ -49,7 +70,8 @@ struct Ring {
     __device__ __forceinline__ void timed_landed(f16x8 (&f)[4]) {
         if (!(DBG & 32)) return;
         const unsigned long long a = __builtin_amdgcn_s_memtime();
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]));
+        if constexpr (LOW) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]));
+        else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[2]));
         const unsigned long long b = __builtin_amdgcn_s_memtime();
         t_lds += b - a;
     }
@@ -138,10 +160,11 @@ struct Ring {
         if ((DBG & 4) || ((DBG & 64) && G != 0) || ((DBG & 128) && (G & 1)) ||        // 128: one group in TWO (pairs of waves sharing)
             (HALF && (DBG & (256 | 512)) && (G & 1))) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u) asm volatile("" : "+v"(f[u]));
+            for (int u = 0; u < 4; u += LOW ? 1 : 2) asm volatile("" : "+v"(f[u]));
         } else {
+            // (one product: the high sets 0 and 2 alone - the low sets arrive with the chunk and stay in LDS)
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
+            for (int u = 0; u < 4; u += LOW ? 1 : 2)
                 f[u] = *reinterpret_cast<const __attribute__((address_space(3))) f16x8*>(cbase + (4 * G + u) * FRAG_BYTES);
         }
     }
@@ -269,14 +292,16 @@ __device__ __forceinline__ void pair_sync() {        // my accesses to the area 
 // one fragment set against one B k-step of both tiles: per accumulator the MFMAs of group6, in its order
 __device__ __forceinline__ void group12(const f16x8 (&a)[4], const f16x8& bh0, const f16x8& bl0, const f16x8& bh1,
                                         const f16x8& bl1, f32x4& c00, f32x4& c01, f32x4& c10, f32x4& c11) {
-    c00 = x16::mfma(a[0], bl0, c00);
-    c01 = x16::mfma(a[2], bl0, c01);
-    c10 = x16::mfma(a[0], bl1, c10);
-    c11 = x16::mfma(a[2], bl1, c11);
-    c00 = x16::mfma(a[1], bh0, c00);
-    c01 = x16::mfma(a[3], bh0, c01);
-    c10 = x16::mfma(a[1], bh1, c10);
-    c11 = x16::mfma(a[3], bh1, c11);
+    if constexpr (LOW) {
+        c00 = x16::mfma(a[0], bl0, c00);
+        c01 = x16::mfma(a[2], bl0, c01);
+        c10 = x16::mfma(a[0], bl1, c10);
+        c11 = x16::mfma(a[2], bl1, c11);
+        c00 = x16::mfma(a[1], bh0, c00);
+        c01 = x16::mfma(a[3], bh0, c01);
+        c10 = x16::mfma(a[1], bh1, c10);
+        c11 = x16::mfma(a[3], bh1, c11);
+    }
     c00 = x16::mfma(a[0], bh0, c00);
     c01 = x16::mfma(a[2], bh0, c01);
     c10 = x16::mfma(a[0], bh1, c10);
@@ -327,7 +352,7 @@ __device__ __forceinline__ void pair_publish(const f32x4 (&a)[2][2], float c1, f
     f16x8 hh, hl;
     hidden_planes(a[0][0], a[0][1], c1, lim1, hh, hl);
     pair_put<0>(box, hh);
-    pair_put<1>(box, hl);
+    if constexpr (LOW) pair_put<1>(box, hl);
     pair_put<2>(box, a[1][0]);
     pair_put<3>(box, a[1][1]);
     pair_landed();
@@ -336,7 +361,7 @@ __device__ __forceinline__ void pair_publish(const f32x4 (&a)[2][2], float c1, f
 __device__ __forceinline__ void pair_fetch(const lds_byte* box, float c1, float lim1, f16x8 (&hh)[2], f16x8 (&hl)[2]) {
     f32x4 a0, a1;
     pair_get<0>(box, hh[0]);
-    pair_get<1>(box, hl[0]);
+    if constexpr (LOW) pair_get<1>(box, hl[0]);
     pair_get<2>(box, a0);
     pair_get<3>(box, a1);
     hidden_planes(a0, a1, c1, lim1, hh[1], hl[1]);
@@ -374,7 +399,7 @@ __device__ __forceinline__ void phase_ffn_ln_role_a(Ring& ring, const Phase& P, 
                 pair_put<3>(box, acc2[2 * i + 1]);
                 pair_sync();
                 pair_get<0>(box, xh[1][i]);
-                pair_get<1>(box, xl[1][i]);
+                if constexpr (LOW) pair_get<1>(box, xl[1][i]);
                 pair_sync();
             }
         }
@@ -438,7 +463,7 @@ __device__ __forceinline__ void phase_ffn_ln_role_b(Ring& ring, const Phase& P, 
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 pair_put<0>(box, xh[i]);
-                pair_put<1>(box, xl[i]);
+                if constexpr (LOW) pair_put<1>(box, xl[i]);
                 pair_sync();
                 pair_get<2>(box, acc2[0][2 * i]);
                 pair_get<3>(box, acc2[0][2 * i + 1]);
