@@ -36,7 +36,8 @@ extern "C" {
                                * the same masks in the inverted-list scans: amdrec_ivf_scan_eligible, amdrec_ivf_scan_grouped_eligible,
                                * amdrec_ivf_scan_grouped_mixed_eligible, amdrec_ivfpq_scan_finite_eligible, added exports; then
                                * the per-group caps: amdrec_select_topk_capped, amdrec_group_cap_compact, added exports; then
-                               * auction ranking: amdrec_select_topk_auction, an added export) */
+                               * auction ranking: amdrec_select_topk_auction, an added export; then
+                               * per-ad score boosts: amdrec_flat_search_boosted, amdrec_flat_search_mixed_boosted, added exports) */
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -103,6 +104,31 @@ int amdrec_flat_search_mixed_eligible(const float* corpus, int64_t nrows, int64_
                                       int64_t* out_pos /*[nq][k]*/, void* workspace, size_t workspace_bytes,
                                       int* n_fixup, void* stream, const uint64_t* tags /*[nrows]*/,
                                       const uint64_t* require_all /*[nq]*/, const uint64_t* require_any /*[nq]*/);
+
+/* Per-ad score boosts: the same two searches under the retrieval key
+ *     s(q, r) = ip(q, r) + weight[q] * boost[r],
+ * one float per corpus row (`boost`, exactly nrows values, finite), one float per query (`weight`).  ip is the score the
+ * matching plain entry returns for the row; t = weight[q] * boost[r] is one rounded fp32 multiply and s = ip + t one rounded
+ * fp32 add - two roundings, never a fused multiply-add.  Result: the exact top-k under s (s descending, ties -> lower
+ * position), s returned as the score; a row whose ip is NaN is never returned; unfilled slots as above; a query with
+ * weight 0 gets the plain search's positions.  The key is evaluated inside the corpus pass (sample, filter, re-score and
+ * fix-up scan all see it), so a boost can lift a row from any rank.  `boost_max`: a host upper bound of max |boost|, used by
+ * the mixed form's error bound only (a bound that is too small can cost exactness, one that is too large only speed).
+ * Both pointers are device pointers and required (boost 64-byte aligned); workspace: the size the matching *_workspace
+ * query gives. */
+int amdrec_flat_search_boosted(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
+                               const float* queries, int64_t nq, int64_t ld_queries, int k,
+                               int64_t pos_offset, float* out_scores /*[nq][k]*/,
+                               int64_t* out_pos /*[nq][k]*/, void* workspace, size_t workspace_bytes,
+                               int* n_fixup, void* stream, const float* boost /*[nrows]*/,
+                               const float* weight /*[nq]*/, float boost_max);
+int amdrec_flat_search_mixed_boosted(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
+                                     const uint16_t* corpus_bf16, int64_t ld_bf16, const float* max_norm,
+                                     const float* queries, int64_t nq, int64_t ld_queries, int k,
+                                     int64_t pos_offset, float* out_scores /*[nq][k]*/,
+                                     int64_t* out_pos /*[nq][k]*/, void* workspace, size_t workspace_bytes,
+                                     int* n_fixup, void* stream, const float* boost /*[nrows]*/,
+                                     const float* weight /*[nq]*/, float boost_max);
 
 /* ---- retrieval: IVF-Flat (faiss IndexIVFFlat, METRIC_INNER_PRODUCT, IndexFlatIP quantizer:
  * faiss_retrieval.py:50-55, searched at :150-155 with index.nprobe = nprobe) ---------------------

@@ -39,6 +39,11 @@ _SIGNATURES = {
     "amdrec_flat_search_eligible": [_fp, _i64, _i64, _i32, _fp, _i64, _i64, _i32, _i64, _fp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
     "amdrec_flat_search_mixed_eligible": [_fp, _i64, _i64, _i32, _vp, _i64, _fp, _fp, _i64, _i64, _i32, _i64, _fp, _vp, _vp,
                                           _sz, _vp, _vp, _vp, _vp, _vp],
+    # the *_boosted searches: their plain twin's arguments + (boost, weight, boost_max)
+    "amdrec_flat_search_boosted": [_fp, _i64, _i64, _i32, _fp, _i64, _i64, _i32, _i64, _fp, _vp, _vp, _sz, _vp, _vp, _fp, _fp,
+                                   C.c_float],
+    "amdrec_flat_search_mixed_boosted": [_fp, _i64, _i64, _i32, _vp, _i64, _fp, _fp, _i64, _i64, _i32, _i64, _fp, _vp, _vp,
+                                         _sz, _vp, _vp, _fp, _fp, C.c_float],
     "amdrec_ivf_scan": [_fp, _i64, _i32, _vp, _vp, _fp, _i64, _i64, _vp, _vp, _i32, _vp, _i64, _i64, _vp],
     "amdrec_ivf_scan_grouped": [_fp, _i64, _i32, _vp, _vp, _i32, _i64, _fp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32,
                                 _vp, _i64, _i64, _fp, _i64, _vp, _vp],

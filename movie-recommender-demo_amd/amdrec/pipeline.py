@@ -27,7 +27,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import _lib, auction as _auction, diversity as _diversity, eligible as _eligible, exclude as _exclude, \
+from . import _lib, boost as _boost, auction as _auction, diversity as _diversity, eligible as _eligible, exclude as _exclude, \
     rows_edit as _rows_edit
 from .index import FAISSIndex
 from .ranker import TransformerRanker
@@ -152,14 +152,15 @@ class AdRecommenderInference:
         return torch.tensor([cat], dtype=torch.long), torch.from_numpy(num[None, :])
 
     def preprocess_batch(self, user_data_list: list, exclude: Optional[np.ndarray] = None,
-                         masks: Optional[np.ndarray] = None):
+                         masks: Optional[np.ndarray] = None, weights: Optional[np.ndarray] = None):
         """Batch form of preprocess_user_features with the numerical transform on the device: categorical strings
         are label-encoded on the host (dictionary lookups), raw numericals are shipped as one float32 block and
         log1p / standardised by amdrec_prep_numerical.  -> (user_categorical [B,6] int64, user_numerical [B,13]
         float32), both on the device.  ``exclude`` (int64 [B, E], amdrec.exclude.pad_exclusions) rides in the same
         staging block and copy; the result is then (user_categorical, user_numerical, exclude on the device).  ``masks``
         (int64 [2, B]: the users' require_all and require_any words, amdrec.eligible) ride there too and come back last,
-        as a device [2, B]."""
+        as a device [2, B].  ``weights`` (float32 [B]: the users' stage-1 boost weights, amdrec.boost) ride behind them and
+        come back after them, as a device float32 [B]."""
         pp = self.preprocessor
         if pp is None:
             raise ValueError("no preprocessor loaded")
@@ -174,8 +175,9 @@ class AdRecommenderInference:
         cat_bytes = B * nc * 8
         ex_off = (cat_bytes + B * nn_ * 4 + 7) // 8 * 8                 # the int64 exclusion block, 8-byte aligned
         m_off = ex_off + (0 if exclude is None else exclude.size * 8)   # the int64 mask words
-        host, done = self._staging(m_off + 2 * B * 8 if masks is not None else
-                                   (cat_bytes + B * nn_ * 4 if exclude is None else m_off))
+        w_off = m_off + (0 if masks is None else 2 * B * 8)             # the float32 boost weights
+        host, done = self._staging(w_off + B * 4 if weights is not None else (m_off + 2 * B * 8 if masks is not None else
+                                   (cat_bytes + B * nn_ * 4 if exclude is None else m_off)))
         hv = host.numpy()
         if nc:
             hv[:cat_bytes].view(np.int64).reshape(B, nc)[:] = [[pp.encode(c, u["categorical"].get(c, "missing")) for c in cols]
@@ -187,6 +189,8 @@ class AdRecommenderInference:
             hv[ex_off:m_off].view(np.int64).reshape(exclude.shape)[:] = exclude
         if masks is not None:
             hv[m_off:m_off + 2 * B * 8].view(np.int64).reshape(2, B)[:] = masks
+        if weights is not None:
+            hv[w_off:w_off + B * 4].view(np.float32)[:] = weights
         blk = host.to(dev, non_blocking=True)
         done.record(torch.cuda.current_stream(dev))
         cat = blk[:cat_bytes].view(torch.int64).view(B, nc)
@@ -200,6 +204,8 @@ class AdRecommenderInference:
             res += (blk[ex_off:m_off].view(torch.int64).view(exclude.shape),)
         if masks is not None:
             res += (blk[m_off:m_off + 2 * B * 8].view(torch.int64).view(2, B),)
+        if weights is not None:
+            res += (blk[w_off:w_off + B * 4].view(torch.float32),)
         return res
 
     def _staging(self, nbytes: int, slot: str = "in"):
@@ -237,15 +243,16 @@ class AdRecommenderInference:
         return mode, None
 
     # -- the device hot path ------------------------------------------------------------------
-    def _stage1(self, uc, un, stage1_k, check_indices, exclude=None, masks=(None, None), max_per_group=None):
+    def _stage1(self, uc, un, stage1_k, check_indices, exclude=None, masks=(None, None), max_per_group=None, boost_weight=None):
         # the tower's launch also applies the search's query normalisation (faiss_retrieval.py:147): one launch fewer
         emb = self.two_tower_model.user_tower.encode(uc, un, check_indices=check_indices, renormalize=True)   # :223-227
         # exclude (device int64 [B, E] ad ids, or None): removed here, so the ranker only ever sees eligible ads
         # masks (device int64 [B] require_all / require_any, or None): tested inside the search, likewise
         # max_per_group (stage1_max_per_group, or None): the per-group cap on the candidate list (FAISSIndex.search_device)
+        # boost_weight (stage1_boost: a number or device float32 [B], or None): the retrieval key ip + w * boost[ad], likewise
         return self.faiss_index.search_device(emb, stage1_k, normalize=False,                  # :230-232
                                               return_positions=True, exclude=exclude, require_all=masks[0],
-                                              require_any=masks[1], max_per_group=max_per_group)
+                                              require_any=masks[1], max_per_group=max_per_group, boost_weight=boost_weight)
 
     def _stage2(self, uc, un, cand_pos, top_k, check_indices, ids_are_positions=False, mark=None, out=None,
                 excluded=False, heads=None, max_per_group=None, auction=None, diversity=None):
@@ -355,7 +362,7 @@ class AdRecommenderInference:
                          require_all: Optional[torch.Tensor] = None, require_any: Optional[torch.Tensor] = None,
                          max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                          rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                         diversity_pool: int = 64):
+                         diversity_pool: int = 64, stage1_boost=None):
         """[B,6] / [B,13] device tensors -> dict of device tensors, no host synchronisation:
         ad_ids [B,top_k] int64, scores [3,B,top_k] float32 (sigmoid of the logits), candidate_ids
         [B,stage1_k], candidate_scores [B,stage1_k], logits [3, B*stage1_k].  candidate_scores are the index's own
@@ -397,9 +404,16 @@ class AdRecommenderInference:
         each winner's discounted value (0.0 in the unfilled tail).  ``lam == 0`` is the plain (or capped) result bit for bit.
         A non-number ``lam``: TypeError; ``lam`` outside [0, 1], a pool below ``top_k``, above 128 or with pool x dimension >
         32768, a pool without ``diversity``, and ``diversity`` with "ecpm": ValueError; on an IVFPQ index: NotImplementedError.
+        ``stage1_boost`` (None: the plain search, the launches of ever): a number or a device float32 [B], the users' weights
+        on the index's per-ad boosts (FAISSIndex.add(boosts=) / set_boosts; amdrec.boost has the rule; Flat index): stage 1
+        is the exact top-stage1_k under similarity + w x boost[ad], so an ad with a large bid (boost = beta x log(bid)) reaches
+        the ranker - and the auction - from any similarity rank; candidate_scores are the boosted scores.  Stage 2 never
+        reads them and is unchanged.  On an index without boosts, a non-finite number: ValueError; with masks, on IVF / IVFPQ:
+        NotImplementedError.
         ``check_indices``: an out-of-range user index or ad-table row raises IndexError; an unfilled slot does not."""
         if heads is not None:
             self._check_heads(heads)
+        self.faiss_index._check_boost(stage1_boost, require_all is not None or require_any is not None)
         cap, cap1 = self._check_caps(max_per_group, stage1_max_per_group)          # (before the library is touched)
         auction = self._check_auction(rank_by, reserve)
         div = self._check_diversity(diversity, diversity_pool, top_k, auction)
@@ -408,7 +422,7 @@ class AdRecommenderInference:
         excluded = exclude_ad_ids is not None and exclude_ad_ids.shape[-1] > 0
         masked = require_all is not None or require_any is not None
         cand_pos, cand_scores = self._stage1(uc, un, stage1_k, check_indices, exclude_ad_ids if excluded else None,
-                                             (require_all, require_any), cap1)
+                                             (require_all, require_any), cap1, stage1_boost)
         # (excluded: "a slot can be unfilled" - true after a filtered stage 1 as well)
         out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded or masked or cap1 is not None,
                            heads=heads, max_per_group=cap, auction=auction, diversity=div)
@@ -419,7 +433,7 @@ class AdRecommenderInference:
                 max_exclude: int = 0, eligibility: bool = False, max_per_group: Optional[int] = None,
                 stage1_max_per_group: Optional[int] = None, rank_by: Optional[str] = None,
                 reserve: bool = False, diversity: Optional[float] = None,
-                diversity_pool: int = 64) -> "GraphedRecommender":
+                diversity_pool: int = 64, stage1_boost: bool = False) -> "GraphedRecommender":
         """Capture one recommend_device call for a fixed batch shape into a HIP graph (the ~40 kernel
         launches of a request are host-launch-bound at small batch: 1.76 ms eager at B = 1) and return a
         replayer.  Weights, index and ad table must not change afterwards.  ``max_exclude`` > 0: the graph also holds a
@@ -431,9 +445,11 @@ class AdRecommenderInference:
         of capture time.  ``rank_by`` (recommend_device) is fixed at capture too, and the bids are those of capture time;
         ``reserve=True`` (needs "ecpm") gives the graph a static [batch_size] float32 reserve buffer that the replayer's
         ``reserve`` argument fills.  ``diversity`` / ``diversity_pool`` (recommend_device): scalars fixed at capture, like
-        ``max_per_group``; the rows are those of capture time."""
+        ``max_per_group``; the rows are those of capture time.  ``stage1_boost=True``: the graph holds a static
+        [batch_size] float32 weight buffer and runs the boosted search (the replayer's ``stage1_boost`` fills it, zeros
+        without one; the boosts are those of capture time); False captures the graph as ever."""
         return GraphedRecommender(self, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group,
-                                  stage1_max_per_group, rank_by, reserve, diversity, diversity_pool)
+                                  stage1_max_per_group, rank_by, reserve, diversity, diversity_pool, stage1_boost)
 
     # -- live corpus: ads leave and enter without a rebuild of the index or of the ranker's per-ad caches ------------------
     def remove_ads(self, ad_ids) -> int:
@@ -452,9 +468,9 @@ class AdRecommenderInference:
         self._swap_ad_table(old, new)
         return removed
 
-    def add_ads(self, embeddings, ad_features, ad_ids=None, tags=None, groups=None, bids=None) -> None:
+    def add_ads(self, embeddings, ad_features, ad_ids=None, tags=None, groups=None, bids=None, boosts=None) -> None:
         """Insert ads: ``embeddings`` [m, d] go to the index (FAISSIndex.add: ``ad_ids`` as there; required once ads have been
-        removed; ``tags``: the ads' 64-bit eligibility words, ``groups``: their int64 group keys, ``bids``: their float32 bids, as there), ``ad_features`` [m, n_ad_feat] integer rows are
+        removed; ``tags``: the ads' 64-bit eligibility words, ``groups``: their int64 group keys, ``bids``: their float32 bids, ``boosts``: their stage-1 score boosts, as there), ``ad_features`` [m, n_ad_feat] integer rows are
         appended to the ad-feature table, and the ranker's per-ad
         caches grow by projecting the m new rows only (TransformerRanker.extend_ad_cache).  The feature rows are checked
         against the ranker's ad embedding tables first (IndexError, as an embedding lookup would raise), and a rejected call
@@ -474,7 +490,7 @@ class AdRecommenderInference:
         if feats.numel() and bool(((feats < 0) | (feats >= cards)).any().item()):
             raise IndexError("index out of range in self: an ad_features row is outside the ranker's ad embedding tables")
         n_old = idx.index.ntotal
-        idx.add(embeddings, ad_ids, tags=tags, groups=groups, bids=bids)   # (refuses before it commits anything)
+        idx.add(embeddings, ad_ids, tags=tags, groups=groups, bids=bids, boosts=boosts)   # (refuses before it commits anything)
         new = torch.cat([old[:n_old], feats])
         if old.shape[0] == n_old:
             self.transformer_ranker.extend_ad_cache(old, new)
@@ -494,12 +510,13 @@ class AdRecommenderInference:
                       return_scores: bool = True, exclude_ad_ids=None, require_all: int = 0, require_any: int = 0,
                       max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                       rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                      diversity_pool: int = 64) -> dict:
+                      diversity_pool: int = 64, stage1_boost=None) -> dict:
         """inference.py:199-288.  ``exclude_ad_ids``: the ad ids this user must not be shown (a sequence of integers).
         ``require_all`` / ``require_any``: this request's eligibility masks (64-bit integers; 0 and 0: no constraint, the
         plain search).  ``max_per_group`` / ``stage1_max_per_group``: the per-group caps of recommend_device.  ``rank_by`` /
         ``reserve``: the auction of recommend_device (the dict gains ``ecpm`` and ``prices``).  ``diversity`` /
-        ``diversity_pool``: its diversified selection (the dict gains ``diversity_values``).  Fewer than
+        ``diversity_pool``: its diversified selection (the dict gains ``diversity_values``).  ``stage1_boost``: this request's
+        weight on the per-ad boosts in stage 1 (a number; recommend_device).  Fewer than
         ``top_k`` real candidates: as batch_recommend."""
         masked = bool(require_all) or bool(require_any)
         return self.batch_recommend([user_data], top_k=top_k, stage1_k=stage1_k, return_scores=return_scores,
@@ -507,13 +524,13 @@ class AdRecommenderInference:
                                     require_all=[require_all] if masked else None,
                                     require_any=[require_any] if masked else None, max_per_group=max_per_group,
                                     stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve,
-                                    diversity=diversity, diversity_pool=diversity_pool)[0]
+                                    diversity=diversity, diversity_pool=diversity_pool, stage1_boost=stage1_boost)[0]
 
     def batch_recommend(self, user_data_list: list, top_k: int = 10, stage1_k: int = 500,
                         return_scores: bool = True, exclude_ad_ids=None, require_all=None, require_any=None,
                         max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                         rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                        diversity_pool: int = 64) -> list:
+                        diversity_pool: int = 64, stage1_boost=None) -> list:
         """inference.py:290-331 - but one device pass for the whole list instead of a serial loop.
         ``timing`` reports the batch's stage times divided by the number of users.  ``exclude_ad_ids``: one sequence of
         ad ids per user (recommend_device has the meaning); the padded block travels in the input staging block.
@@ -527,7 +544,9 @@ class AdRecommenderInference:
         auction of recommend_device; every user's dict gains ``"ecpm"`` and ``"prices"`` lists of length ``top_k``, which travel
         in the same result block: no copy and no synchronisation more.  ``diversity`` / ``diversity_pool``: the diversified
         selection of recommend_device; every user's dict gains a ``"diversity_values"`` list of length ``top_k``, in the same
-        block."""
+        block.  ``stage1_boost``: the stage-1 boost weight of recommend_device, one number for every user or a sequence of
+        one per user; the weights travel in the input staging block: no copy and no synchronisation more."""
+        self.faiss_index._check_boost(stage1_boost, require_all is not None or require_any is not None)
         self._check_caps(max_per_group, stage1_max_per_group)
         self._check_diversity(diversity, diversity_pool, top_k, self._check_auction(rank_by, reserve))
         if not user_data_list:
@@ -535,11 +554,13 @@ class AdRecommenderInference:
         n = len(user_data_list)
         excl = self._host_exclusions(exclude_ad_ids, n, stage1_k)
         masks = self._host_masks(require_all, require_any, n)
-        uc, un, *rest = self.preprocess_batch(user_data_list, excl, masks)
+        wts = None if stage1_boost is None else _boost.as_weights(stage1_boost, n)
+        uc, un, *rest = self.preprocess_batch(user_data_list, excl, masks, wts)
         excl = rest.pop(0) if excl is not None else None
         masks = rest.pop(0) if masks is not None else None
+        wts = rest.pop(0) if wts is not None else None
         return self.recommend_tensors(uc, un, top_k, stage1_k, return_scores, _encoded=True, _exclude_dev=excl,
-                                      _masks_dev=masks, max_per_group=max_per_group,
+                                      _masks_dev=masks, _boost_dev=wts, max_per_group=max_per_group,
                                       stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve,
                                       diversity=diversity, diversity_pool=diversity_pool)
 
@@ -616,7 +637,7 @@ class AdRecommenderInference:
     def recommend_tensors(self, user_categorical, user_numerical, top_k=10, stage1_k=500, return_scores=True,
                           _encoded=False, exclude_ad_ids=None, _exclude_dev=None, require_all=None, require_any=None,
                           _masks_dev=None, max_per_group=None, stage1_max_per_group=None, rank_by=None, reserve=None,
-                          diversity=None, diversity_pool=64):
+                          diversity=None, diversity_pool=64, stage1_boost=None, _boost_dev=None):
         """Tensor-level entry (cf. TwoStageRetriever.retrieve_and_rank, faiss_retrieval.py:283-369); result dicts follow
         inference.py:272-288.  ONE host synchronisation per call (round 3 had four: the tower's index flag, the stage-1
         timing sync, the ranker's index flag, the result copy - each exposing the launch work queued behind it): indices
@@ -628,7 +649,10 @@ class AdRecommenderInference:
         -1 / 0.0 in the tail of a user with fewer real candidates (batch_recommend).  ``max_per_group`` /
         ``stage1_max_per_group``: the per-group caps of recommend_device.  ``rank_by`` / ``reserve``: its auction; ``ecpm`` and
         ``prices`` ride in the same result block and copy.  ``diversity`` / ``diversity_pool``: its diversified selection;
-        ``diversity_values`` rides there too."""
+        ``diversity_values`` rides there too.  ``stage1_boost``: the users' stage-1 boost weights as in batch_recommend,
+        shipped through pinned memory like the masks."""
+        if _boost_dev is None:
+            self.faiss_index._check_boost(stage1_boost, require_all is not None or require_any is not None)
         cap, cap1 = self._check_caps(max_per_group, stage1_max_per_group)
         auction = self._check_auction(rank_by, reserve)
         div = self._check_diversity(diversity, diversity_pool, top_k, auction)
@@ -655,6 +679,13 @@ class AdRecommenderInference:
                 host.numpy().view(np.int64).reshape(hm.shape)[:] = hm
                 masks = host.to(dev, non_blocking=True).view(torch.int64).view(hm.shape)
                 done.record(torch.cuda.current_stream(dev))
+        wts = _boost_dev
+        if wts is None and stage1_boost is not None:
+            hw = _boost.as_weights(stage1_boost, n)
+            host, done = self._staging(hw.size * 4, "boost")
+            host.numpy().view(np.float32)[:] = hw
+            wts = host.to(dev, non_blocking=True).view(torch.float32)
+            done.record(torch.cuda.current_stream(dev))
         tasks = list(self.transformer_ranker.prediction_heads.keys())        # the ranker's task order (= out["tasks"])
         ev = self.__dict__.get("_ev")
         if ev is None:
@@ -684,7 +715,8 @@ class AdRecommenderInference:
             raise IndexError("index out of range in self")                    # (the ad-feature table, transformer_ranker.py:322)
         st = torch.cuda.current_stream(dev)
         ev[0].record(st)
-        cand_pos, _ = self._stage1(uc, un, stage1_k, False, excl, (None, None) if masks is None else (masks[0], masks[1]), cap1)
+        cand_pos, _ = self._stage1(uc, un, stage1_k, False, excl, (None, None) if masks is None else (masks[0], masks[1]), cap1,
+                                   wts)
         ev[1].record(st)
         out = self._stage2(uc, un, cand_pos, top_k, False, out=outs,
                            excluded=excl is not None or masks is not None or cap1 is not None, max_per_group=cap,
@@ -743,7 +775,7 @@ class TwoStageRetriever:
                           stage2_k: int = 10, ad_features_lookup=None, exclude_ad_ids=None,
                           max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                           rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                          diversity_pool: int = 64):
+                          diversity_pool: int = 64, stage1_boost=None):
         """``exclude_ad_ids``: the ad ids the (first) user must not be shown, a sequence of integers.  With a table, the two
         lists have length ``stage2_k``; a user with fewer real candidates gets -1 / 0.0 in the tail (batch_recommend).
         ``stage1_max_per_group`` / ``max_per_group``: the per-group caps on the candidates and on the ranked result
@@ -751,8 +783,10 @@ class TwoStageRetriever:
         ``rank_by`` / ``reserve``: the auction of recommend_device for the ranked result (the tuple is as ever: ids and CTR
         probabilities, in eCPM order); without a table they are checked and change nothing.  ``diversity`` /
         ``diversity_pool``: the diversified selection of recommend_device for the ranked result (ids and CTR probabilities, in
-        pick order); without a table they are checked and change nothing."""
+        pick order); without a table they are checked and change nothing.  ``stage1_boost``: the (first) user's weight on the
+        per-ad boosts in stage 1, a number (recommend_device), with or without a table."""
         idx = self.faiss_index
+        idx._check_boost(stage1_boost)
         cap, cap1 = idx._check_group_cap(max_per_group), idx._check_group_cap(stage1_max_per_group, "stage1_max_per_group")
         _diversity.check_index_diversity(idx, diversity, diversity_pool, stage2_k, idx._check_auction(rank_by, reserve)[0])
         uc = user_categorical.to(self.device)
@@ -763,7 +797,8 @@ class TwoStageRetriever:
             blk = _exclude.as_block(excl, 1)
             ids, dist = self.faiss_index.search_device(
                 emb[:1] if blk is not None else emb, stage1_k,
-                exclude=None if blk is None else torch.from_numpy(blk).to(self.device), max_per_group=cap1)
+                exclude=None if blk is None else torch.from_numpy(blk).to(self.device), max_per_group=cap1,
+                boost_weight=stage1_boost)
             return ids[0].tolist(), dist[0].tolist()
         if self._rec is None or self._rec_table is not ad_features_lookup:
             self._rec = AdRecommenderInference(device=str(self.device), two_tower_model=self.two_tower_model,
@@ -773,7 +808,7 @@ class TwoStageRetriever:
         r = self._rec.recommend_tensors(uc[:1], un[:1], stage2_k, stage1_k,       # one synchronisation, indices validated
                                         exclude_ad_ids=excl, max_per_group=cap, stage1_max_per_group=cap1,
                                         rank_by=rank_by, reserve=reserve, diversity=diversity,
-                                        diversity_pool=diversity_pool)[0]
+                                        diversity_pool=diversity_pool, stage1_boost=stage1_boost)[0]
         return r["ad_ids"], r["scores"]["ctr"]                                    # :359-369 (ids, ctr probabilities)
 
 
@@ -785,7 +820,7 @@ class GraphedRecommender:
     def __init__(self, rec: AdRecommenderInference, batch_size: int, top_k: int, stage1_k: int, warmup: int = 2,
                  max_exclude: int = 0, eligibility: bool = False, max_per_group: Optional[int] = None,
                  stage1_max_per_group: Optional[int] = None, rank_by: Optional[str] = None, reserve: bool = False,
-                 diversity: Optional[float] = None, diversity_pool: int = 64):
+                 diversity: Optional[float] = None, diversity_pool: int = 64, stage1_boost: bool = False):
         self.rec, self.batch_size, self.top_k, self.stage1_k = rec, batch_size, top_k, stage1_k
         # the per-group caps: scalars fixed at capture (the group keys are those of capture time, pinned below)
         self.max_per_group, self.stage1_max_per_group = rec._check_caps(max_per_group, stage1_max_per_group)
@@ -816,6 +851,11 @@ class GraphedRecommender:
             if reserve:
                 self._reserve = torch.zeros((batch_size,), dtype=torch.float32, device=dev)
             caps.update(rank_by=rank_by, reserve=self._reserve)
+        # static stage-1 boost weights (zeros = the plain search's positions); None: the graph runs the plain search
+        self._boost_w = torch.zeros((batch_size,), dtype=torch.float32, device=dev) if stage1_boost else None
+        if stage1_boost:
+            rec.faiss_index._check_boost(self._boost_w, self.eligibility)
+            caps.update(stage1_boost=self._boost_w)
         # sizing + warm-up pass on the shared workspace (packs weights, sets kernel attributes)
         probe = _lib.MeasuringArena(_lib.Workspace())
         with _lib.WORKSPACE.private(probe):
@@ -841,14 +881,29 @@ class GraphedRecommender:
     @torch.no_grad()
     def __call__(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor,
                  exclude: Optional[torch.Tensor] = None, require_all: Optional[torch.Tensor] = None,
-                 require_any: Optional[torch.Tensor] = None, reserve=None):
+                 require_any: Optional[torch.Tensor] = None, reserve=None, stage1_boost=None):
         """Device tensors [batch_size, ...] -> the same dict as recommend_device (static output buffers,
         overwritten by the next call).  ``exclude``: device int64 [batch_size, E <= max_exclude] ad ids (negative =
         padding), copied into the graph's block; None = nothing excluded (the block is filled with -1).  ``require_all`` /
         ``require_any``: device int64 [batch_size] eligibility masks, copied into the graph's buffers (None = zeros: no
         constraint); a graph captured without ``eligibility`` raises ValueError for them.  ``reserve``: a float >= 0 or a
         device float32 [batch_size], copied into the graph's reserve buffer (None = zeros); a graph captured without
-        ``reserve=True`` raises ValueError for it."""
+        ``reserve=True`` raises ValueError for it.  ``stage1_boost``: a number or a device float32 [batch_size], copied into
+        the graph's weight buffer (None = zeros); a graph captured without ``stage1_boost=True`` raises ValueError for it."""
+        if stage1_boost is not None:
+            if self._boost_w is None:
+                raise ValueError("captured without stage1_boost=True: this graph runs the plain search and takes no boost weight")
+            if isinstance(stage1_boost, torch.Tensor):
+                if stage1_boost.dtype != torch.float32 or stage1_boost.shape != (self.batch_size,):
+                    raise ValueError(f"stage1_boost must be float32 [{self.batch_size}], got {stage1_boost.dtype} "
+                                     f"{tuple(stage1_boost.shape)}")
+            else:
+                stage1_boost = _boost.check_weight(stage1_boost)
+        if self._boost_w is not None:
+            if isinstance(stage1_boost, torch.Tensor):
+                self._boost_w.copy_(stage1_boost)
+            else:
+                self._boost_w.fill_(0.0 if stage1_boost is None else stage1_boost)
         if user_categorical.shape[0] != self.batch_size:
             raise ValueError(f"captured for batch {self.batch_size}, got {user_categorical.shape[0]}")
         if exclude is not None and (self._ex is None or exclude.dim() != 2 or exclude.shape[0] != self.batch_size

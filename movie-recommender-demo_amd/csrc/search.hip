@@ -56,21 +56,59 @@ __device__ __forceinline__ bool tag_ok(uint64_t t, uint64_t all, uint64_t any) {
     return (t & all) == all && (any == 0ull || (t & any) != 0ull);
 }
 struct NoElig {
-    static constexpr bool on = false;
+    static constexpr bool on = false, boosted = false;
     __device__ __forceinline__ bool ok(long long, int) const { return true; }
 };
 struct Elig {
-    static constexpr bool on = true;
+    static constexpr bool on = true, boosted = false;
     const uint64_t* tags;    // [nrows]
     const uint64_t* all;     // [nq]
     const uint64_t* any;     // [nq]
     __device__ __forceinline__ bool ok(long long row, int q) const { return tag_ok(tags[row], all[q], any[q]); }
 };
 
+// ---- per-ad score boosts (amdrec_flat_search*_boosted) ----------------------------------
+// key(q, r) = <q, x_r> + w_q * boost[r]: one float per corpus row, one weight per query (amdrec.h has the contract).  The
+// third alternative of the same compile-time type: every kernel that forms a score takes Boosted where the other searches
+// take NoElig / Elig, and the code it adds sits behind `if constexpr (EL::boosted)` - the other instantiations are the code
+// they were.  The returned score is TWO rounded fp32 operations, t = w * b and s = ip + t, never a fused multiply-add
+// (the translation unit is compiled with contraction on): boost_term / boost_add (topk_utils.hpp) are the only places that form them.
+struct Boosted {
+    static constexpr bool on = false, boosted = true;
+    const float* boost;      // [nrows]
+    const float* weight;     // [nq]
+    float boost_max = 0.f;   // >= max |boost| (the finalize kernels' error bound; the other kernels do not take it)
+    __device__ __forceinline__ bool ok(long long, int) const { return true; }
+    __device__ __forceinline__ float term(long long row, int q) const { return boost_term(weight[q], boost[row]); }
+    // the score of row `row` for query q from its inner product
+    __device__ __forceinline__ float score(float ip, long long row, int q) const { return boost_add(ip, term(row, q)); }
+};
+#define AMDREC_BOOST_FIN Boosted, const float*, const float*, float
+// finalize_mixed_kernel takes the boost as BO (NoElig: none; Boosted) with its arguments behind the ones it always took.
+// eps: with t in both chains the bf16 pass's bound grows by the fp32 slack of the larger partial sums (derivation above
+// finalize_mixed_kernel); term: what rescore_keys adds to a re-scored inner product.
+template <class BO>
+__device__ __forceinline__ float fin_eps(float eps, int d, int q, const BO& bo) {
+    if constexpr (BO::boosted)
+        return eps * (1.f + 2.f / (float)d) + (float)(d + 1) * 1.2e-7f * (fabsf(bo.weight[q]) * bo.boost_max * 1.0001f);
+    else
+        return eps;
+}
+template <class BO>
+__device__ __forceinline__ auto fin_term(const BO& bo, int q) {
+    if constexpr (BO::boosted) return RowBoost{bo.boost, bo.weight[q]};
+    else return NoTerm{};
+}
+// profile tag of a kernel family for the predicate type
+template <class EL>
+constexpr const char* tag_for(const char* plain, const char* elig, const char* boost) {
+    return EL::boosted ? boost : (EL::on ? elig : plain);
+}
+
 // ---- epilogues (lane <-> query, registers <-> corpus rows) ---------------------------
 template <class EL>
 struct EpiStoreScoresT {
-    static constexpr const char* name = EL::on ? "search_sample_elig" : "search_sample";
+    static constexpr const char* name = tag_for<EL>("search_sample", "search_sample_elig", "search_sample_boost");
     static constexpr double out_bytes_per_elem = 1.0;
     static constexpr size_t lds_bytes(int) { return 0; }
     float* out;          // [nq][ld]
@@ -98,6 +136,7 @@ struct EpiStoreScoresT {
                     for (int e = 0; e < 4; ++e) {
                         float s = acc.v[i][j][4 * g + e];
                         const long long row = map.map(p + e);
+                        if constexpr (EL::boosted) s = el.score(s, row < map.rows ? row : 0, q);   // tau: a quantile of the BOOSTED scores
                         v[e] = (row < map.rows && el.ok(row, q)) ? s : -INFINITY;
                     }
                     *reinterpret_cast<f32x4*>(out + (long long)q * ld + p) = v;
@@ -115,7 +154,7 @@ struct EpiStoreScores : EpiStoreScoresT<NoElig> {};
 constexpr int HIT_CAP = 2048;
 template <class EL>
 struct EpiFilterT {
-    static constexpr const char* name = EL::on ? "search_filter_elig" : "search_filter";
+    static constexpr const char* name = tag_for<EL>("search_filter", "search_filter_elig", "search_filter_boost");
     static constexpr double out_bytes_per_elem = 0.0;
     static constexpr size_t lds_bytes(int) { return 16 + (size_t)HIT_CAP * 12; }
     const float* tau;            // [nq]
@@ -148,6 +187,7 @@ struct EpiFilterT {
                 for (int r = 0; r < 16; ++r) {
                     float s = acc.v[i][j][r];
                     int p = acc.p(i, r, lane);
+                    if constexpr (EL::boosted) s = el.score(s, p < nrows ? p : 0, q < nq ? q : 0);   // (NaN stays NaN)
                     if (s >= t && p < nrows && el.ok(p, q)) {
                         const unsigned long long key = make_key(s, (uint32_t)p);
                         const int slot = atomicAdd(lcount, 1);
@@ -283,6 +323,7 @@ __global__ __launch_bounds__(512) void fixup_kernel(const float* X, long long ld
         for (int u = 0; u < U; ++u) {
             long long r = row0 + w * U + u;
             if (lane == 0 && r < end && a[u] == a[u] && el.ok(r, q)) {
+                if constexpr (EL::boosted) a[u] = el.score(a[u], r, q);
                 unsigned long long key = make_key(a[u], (uint32_t)r);
                 if (key > thr) {
                     int pos = atomicAdd(&count, 1);
@@ -450,6 +491,52 @@ __device__ __forceinline__ u32x16 scalar_load_8x64(const uint64_t* p) {
     return w;
 }
 
+// ... and 32 consecutive floats (128 bytes, the boosts of one 32-row quarter) in two loads behind one wait
+__device__ __forceinline__ void scalar_load_32xf32(const float* p, u32x16& lo, u32x16& hi) {
+    asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx16 %1, %2, 0x40\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(lo), "=&s"(hi) : "s"(p));
+}
+// The boosts of a 32-row quarter as the streaming kernels' accumulators see them: bt[4 g + e] = boost of corpus row
+// urow + 8 g + 4 fh + e (fh: the lane's half).  The 32 values are wave-uniform, like the eligibility tags: two scalar
+// loads, which return on their own counter and never queue behind the LDS-DMA in flight, then one select per value by
+// the lane half.  FULL: all 32 rows are corpus rows (urow is a multiple of 32 and the array 64-byte aligned, so the loads
+// stay inside it).  In the corpus's last, partial tile a quarter that lies inside the corpus takes the same two loads, one
+// beyond its end reads nothing, and the one quarter the corpus ends in (at most one per search, none when nrows % 32 == 0)
+// loads the two candidates of each value on their own from clamped rows - 16 pairs of scalar loads, each behind its own
+// wait: what the eligibility path does for its tags there.
+__device__ __forceinline__ void scalar_load_2xf32(const float* p0, const float* p1, uint32_t& v0, uint32_t& v1) {
+    asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(v0), "=&s"(v1) : "s"(p0), "s"(p1));
+}
+template <bool FULL>
+__device__ __forceinline__ void quarter_boosts(const float* boost, int urow, int fh, int nrows, float (&bt)[16]) {
+    if (FULL || urow + 32 <= nrows) {                          // (wave-uniform) every row of the quarter is a corpus row
+        u32x16 lo, hi;
+        scalar_load_32xf32(boost + urow, lo, hi);
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t b0 = g < 2 ? lo[8 * g + e] : hi[8 * (g - 2) + e];
+                const uint32_t b1 = g < 2 ? lo[8 * g + 4 + e] : hi[8 * (g - 2) + 4 + e];
+                bt[4 * g + e] = __uint_as_float(fh ? b1 : b0);
+            }
+    } else if (urow >= nrows) {                                // no row of the quarter is: nothing is read
+#pragma unroll
+        for (int r = 0; r < 16; ++r) bt[r] = 0.f;
+    } else {                                                   // the one quarter the corpus ends in: row by row, clamped
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int r0 = urow + 8 * g + e, r1 = r0 + 4;
+                uint32_t b0, b1;
+                scalar_load_2xf32(boost + (r0 < nrows ? r0 : nrows - 1), boost + (r1 < nrows ? r1 : nrows - 1), b0, b1);
+                bt[4 * g + e] = __uint_as_float(fh ? b1 : b0);
+            }
+    }
+}
+
 // 16 bytes from global `g` to LDS `l` by LDS-DMA (the LDS address is wave-uniform: lane i's bytes land at l + 16 i)
 __device__ __forceinline__ void lds_dma16(const unsigned char* g, unsigned char* l) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l,
@@ -575,15 +662,27 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
     // 32 corpus rows (LDS image at `lb`, fragment k-offset swizzle G) x NJ query tiles: K loop with the A fragments
     // read AHEAD steps before their MFMA, then the threshold scan.  wcount = this wave's hits so far in this tile.
     uint64_t qall[2] = {0ull, 0ull}, qany[2] = {0ull, 0ull};       // (filtered instantiations only)
+    float wq[2] = {0.f, 0.f};                                      // (boosted instantiations only) weights of the lane's queries
     auto quarter = [&](auto nj_tag, auto full_tag, const unsigned char* lb, int G, int prow, uint32_t list_addr,
                        int& wcount, int urow) {                    // urow: the quarter's first corpus row (wave-uniform)
         constexpr int NJ = decltype(nj_tag)::value;
         constexpr bool FULL = decltype(full_tag)::value;           // every row of the tile is a corpus row
         f32x16 acc[NJ];
+        if constexpr (EL::boosted) {
+            // the accumulators start at t = w_q * boost[row] where the plain pass zeroes them: the threshold test, the hit
+            // lists and the keys see the boosted approximate score and nothing downstream of the MFMAs changes
+            float bt[16];
+            quarter_boosts<FULL>(el.boost, urow, fh, nrows_i, bt);
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
+            for (int j = 0; j < NJ; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+                for (int r = 0; r < 16; ++r) acc[j][r] = boost_term(wq[j], bt[r]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+        }
         bf16x8 a[AHEAD];
 #pragma unroll
         for (int s_ = 0; s_ < AHEAD; ++s_) a[s_] = *reinterpret_cast<const bf16x8*>(lb + ((32 * s_) ^ G));
@@ -689,6 +788,7 @@ __global__ __launch_bounds__(512, 1) void scan_filter_kernel(const uint16_t* __r
             qall[j] = el.all[q < nq ? q : nq - 1];
             qany[j] = el.any[q < nq ? q : nq - 1];
         }
+        if constexpr (EL::boosted) wq[j] = el.weight[q < nq ? q : nq - 1];
     }
     int it = 0, wprev = 0;                                         // wprev: hits of the previous tile awaiting their append
     for (; it < my_tiles; ++it) {
@@ -822,6 +922,14 @@ __global__ __launch_bounds__(512, 1) void sample_max_kernel(const uint16_t* __re
             qany[j] = el.any[q < nq ? q : nq - 1];
         }
     }
+    float wq[2] = {0.f, 0.f};                                      // (boosted instantiations only) weights of the lane's queries
+    if constexpr (EL::boosted) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int q = q0 + j * 32 + frow;
+            wq[j] = el.weight[q < nq ? q : nq - 1];
+        }
+    }
     // tile DMA (sample tiles are whole tiles: no clamped path)
     const uint32_t lane_off = Tile::lane_off(tid, ld16);
     auto dma = [&](int st_, int buf) {
@@ -857,10 +965,21 @@ __global__ __launch_bounds__(512, 1) void sample_max_kernel(const uint16_t* __re
                     asm volatile("" : "+v"(G));
                     const unsigned char* lq = lb + rq * 32 * CPR * 16;
                     f32x16 acc[NJ];
+                    if constexpr (EL::boosted) {
+                        // as in the corpus pass: the sample's scores are the boosted ones, so tau lands on THEIR quantile
+                        const int urow = (int)((long long)t * tstride * SCAN_ROWS) + rq * 32;      // < 2^31 (entry point)
+                        float bt[16];
+                        quarter_boosts<true>(el.boost, urow, fh, 0, bt);
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j)
+                        for (int j = 0; j < NJ; ++j)
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+                            for (int r = 0; r < 16; ++r) acc[j][r] = boost_term(wq[j], bt[r]);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+                    }
                     bf16x8 a[AHEAD];
 #pragma unroll
                     for (int s_ = 0; s_ < AHEAD; ++s_) a[s_] = *reinterpret_cast<const bf16x8*>(lq + ((32 * s_) ^ G));
@@ -971,7 +1090,17 @@ struct ScanKernels<Elig> {
     static auto fixup() { return fixup_kernel<AMDREC_ELIG_ARGS>; }
 #undef AMDREC_ELIG_ARGS
 };
-// launches `kern` with the eligibility pointers after the arguments every instantiation takes (NoElig: none)
+template <>
+struct ScanKernels<Boosted> {
+    static constexpr const char *scan_tag = "search_filter_stream128x512_bf16_boost",
+                                *sample_tag = "search_sample_max128x512_bf16_boost";
+#define AMDREC_BOOST_ARGS Boosted, const float*, const float*
+    template <int KS> static constexpr auto scan() { return scan_filter_kernel<KS, AMDREC_BOOST_ARGS>; }
+    template <int KS, int SUB> static constexpr auto sample() { return sample_max_kernel<KS, SUB, AMDREC_BOOST_ARGS>; }
+    static auto fixup() { return fixup_kernel<AMDREC_BOOST_ARGS>; }
+#undef AMDREC_BOOST_ARGS
+};
+// launches `kern` with the predicate's pointers after the arguments every instantiation takes (NoElig: none)
 template <class Kern, class... Args>
 static void launch_with(NoElig, Kern kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
     hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
@@ -979,6 +1108,10 @@ static void launch_with(NoElig, Kern kern, dim3 grid, dim3 block, size_t lds, hi
 template <class Kern, class... Args>
 static void launch_with(Elig el, Kern kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
     hipLaunchKernelGGL(kern, grid, block, lds, st, args..., el.tags, el.all, el.any);
+}
+template <class Kern, class... Args>
+static void launch_with(Boosted bo, Kern kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args..., bo.boost, bo.weight);
 }
 
 template <int KS, class EL = NoElig>
@@ -1113,6 +1246,17 @@ __global__ __launch_bounds__(256) void bf16_rows_kernel(const float* x, long lon
 // (2u + u^2) ||q|| M with u = 2^-8 (every component half an ulp off: tests/test_search_gpu.py::
 // test_mixed_worst_case_rounding, where round 1's u = 2^-9 constant returned a wrong top-k); on random unit vectors
 // ||dq|| ~ ||dx|| ~ 0.0008, i.e. eps ~ 0.0018 instead of 0.0078: half as many candidates survive the prune and are re-scored.
+// With a boost (fin_eps): the two numbers compared are a = fl(t (+) q~.x~), the MFMA chain STARTED at t = fl(w b) (generic
+// tiles: fl(fl(q~.x~) + t)), and s = fl(fl(q.x) + t).  t is the same number on both sides and adds no error of its own; what
+// grows is the fp32 slack, because every partial sum of the approximate chain is now bounded by P = |w| B + ||q|| (M + D)
+// (B >= max |boost|) instead of ||q|| (M + D), and s carries one more rounding of a value <= P.  With u = 2^-24:
+//   approximate chain  d u P  (generic tiles: d u ||q|| (M + D) + u P),   exact side  d u ||q|| M + u P,
+// so beyond the plain bound's 2 d u ||q|| (M + D) the slack is at most (d + 1) u |w| B + 2 u ||q|| (M + D).  The last term is
+// <= eps_plain / d (eps_plain contains d * 1.2e-7 ||q|| (M + D) and 1.2e-7 > 2 u); fin_eps takes
+//   eps = eps_plain (1 + 2 / d) + (d + 1) * 1.2e-7 * |w| B * 1.0001        (twice the terms above)
+// and uses it wherever eps_plain was: the prune a_k - 2 eps, the certificate tau + eps, in both finalize kernels.  A query
+// with w = 0 pays the factor 1 + 2 / d only; |w| B = 256 at d = 256 gives eps ~ 0.008 + eps_plain, i.e. the worst case of
+// the bf16 bound again: more survivors to re-score, never a wrong result.  A non-finite w makes eps non-finite: fix-up scan.
 // (eps_bound itself lives in topk_utils.hpp: the IVF scan's bf16 prefilter uses the same bound)
 
 // step 4 of the mixed-precision search: select a_k -> prune -> fp32 re-score -> exact sort -> certificate, one workgroup per
@@ -1131,13 +1275,19 @@ constexpr int FUSED_MAX_NQ = 128;
 // s * nseg + g) [+ an overflow block at CAND_CAP when the streaming pass produced it]; segcnt[q][nseg] = hits each segment
 // saw (may exceed seg_cap: the excess went to the overflow block, ocnt[q] entries).  The generic GEMM pass writes one
 // segment (nseg = 1, seg_cap = CAND_CAP, no overflow).
-template <int NT, int CAPK>
+// BO / BP: the boost and its arguments (boost, weight, boost_max) - NoElig and none in the kernel every search without
+// boosts launches, Boosted in the boosted searches.  (The module's LDS lowering numbers the kernels that reach LDS variables
+// through a call in NAME order and each kernel loads its number as a constant: `Boosted` sorts behind `NoElig`, so the
+// boosted instantiations take numbers after this kernel's and leave its constant alone.)
+template <int NT, int CAPK, class BO = NoElig, class... BP>
 __global__ __launch_bounds__(NT, NT == 512 ? 2 : 4) void finalize_mixed_kernel(const unsigned long long* cand, long long cstride,
                                                                        const int* segcnt, int nseg, int seg_cap, const int* ocnt,
                                                                        int k, long long nrows, const float* tau,
                                                                        const float* max_norm, const float* X, long long ldx,
                                                                        int d, const float* Q, long long ldq, int* fail,
-                                                                       float* outD, long long* outI, long long pos_offset) {
+                                                                       float* outD, long long* outI, long long pos_offset,
+                                                                       BP... bp) {
+    const BO bo{bp...};
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];      // [CAPK] then qv[d]
     float* qv = reinterpret_cast<float*>(keys + CAPK);
     __shared__ int hist[2048];
@@ -1173,7 +1323,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 2 : 4) void finalize_mixed_kernel(c
             if (slot_valid(s_, nseg, seg_cap, seg_n)) keys[atomicAdd(&fill_sh, 1)] = blk[s_];
         for (int i = tid; i < oc; i += NT) keys[atomicAdd(&fill_sh, 1)] = blk[CAND_CAP + i];
     }
-    const float eps = query_eps<NT>(Q + (long long)q * ldq, d, qv, red, max_norm);
+    const float eps = fin_eps(query_eps<NT>(Q + (long long)q * ldq, d, qv, red, max_norm), d, q, bo);
     if constexpr (!GENERAL) {
 #pragma unroll
         for (int j = 0; j < PER; ++j) mine[j] = (tid + NT * j < c) ? keys[tid + NT * j] : 0ull;
@@ -1198,7 +1348,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 2 : 4) void finalize_mixed_kernel(c
     const int m = m_sh;                                       // need <= m <= c
     // 8 rows in flight per wave, two workgroups per CU (<= 128 VGPRs): with 16 in flight the kernel needed 169 and ran one
     // workgroup per CU, its select and sort phases - barriers and LDS latency - covered by nothing
-    rescore_keys<NW, 8>(keys, m, X, ldx, qv, d >> 2);
+    rescore_keys<NW, 8>(keys, m, X, ldx, qv, d >> 2, fin_term(bo, q));
     // (8192 keys of LDS: the run sort's source and destination both fit)
     const unsigned long long* sorted = sort_keys_desc<NT>(keys, keys + (m <= 1024 ? 1024 : 2048), m, 0);
     if (!certify_or_fail(sorted, need, (long long)c >= nrows, tau[q] + eps, fail, q, nq)) return;
@@ -1212,83 +1362,30 @@ __global__ __launch_bounds__(NT, NT == 512 ? 2 : 4) void finalize_mixed_kernel(c
 // (pos % gridDim.x: a share that does not depend on the order in which a block's threads compacted the survivors), appends
 // the exact keys to the query's list in the workspace, and takes a ticket; the workgroup that draws the LAST ticket sorts
 // the list, certifies and writes the result.  Re-score, sort and certificate are finalize_mixed_kernel's: the same helpers.
-__global__ __launch_bounds__(512) void finalize_fused_kernel(const unsigned long long* cand, long long cstride, const int* segcnt,
-                                                             int nseg, int seg_cap, const int* ocnt, int cap, int k,
-                                                             long long nrows, const float* tau, const float* max_norm,
-                                                             const float* X, long long ldx, int d, const float* Q, long long ldq,
-                                                             int* fail, float* outD, long long* outI, long long pos_offset,
-                                                             unsigned long long* exact, int* fcount, int* fticket) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];      // [cap] then qv[d]
-    float* qv = reinterpret_cast<float*>(keys + cap);
-    __shared__ int hist[2048];
-    __shared__ int scratch[514];
-    __shared__ float red[16];
-    __shared__ int m_sh, own_sh, base_sh;
-    __shared__ int seg_n[256];
-    constexpr int PER = CAND_CAP / 512;
-    constexpr int OVP = 4;
-    const int q = blockIdx.y, nq = gridDim.y, s = blockIdx.x, S = gridDim.x;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int need = (int)(nrows < k ? nrows : k);
-    // the candidate slots are requested before the segment counts that say which of them are valid have arrived (one
-    // global round trip instead of two); validity is applied below
-    const unsigned long long* blk = cand + (long long)q * cstride;
-    unsigned long long mine[PER + OVP];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) mine[j] = tid + 512 * j < nseg * seg_cap ? blk[tid + 512 * j] : 0ull;
-#pragma unroll
-    for (int j = 0; j < OVP; ++j) mine[PER + j] = blk[CAND_CAP + tid + 512 * j];
-    if (tid == 0) { m_sh = 0; own_sh = 0; }
-    const int oc = ocnt[q];
-    const int c = segment_counts<512>(segcnt + (long long)q * nseg, nseg, seg_cap, oc, need, cap, seg_n);
-    // every workgroup of the query reaches the same verdict: one reports
-    if (c < 0) { if (s == 0) give_up(fail, q, nq); return; }
-#pragma unroll
-    for (int j = 0; j < PER; ++j)
-        if (!slot_valid(tid + 512 * j, nseg, seg_cap, seg_n)) mine[j] = 0ull;
-#pragma unroll
-    for (int j = 0; j < OVP; ++j)
-        if (tid + 512 * j >= oc) mine[PER + j] = 0ull;
-    const float eps = query_eps<512>(Q + (long long)q * ldq, d, qv, red, max_norm);
-    if (!(eps < INFINITY)) { if (s == 0) give_up(fail, q, nq); return; }
-    if (need == 0) {
-        if (s == 0) write_result(keys, 0, k, q, outD, outI, pos_offset);
-        return;
-    }
-    // a_k to its top 22 bits (two radix passes): the remaining 10 bits cleared give a value <= a_k in the orderable image,
-    // i.e. a slightly lower cut - a superset of the survivors of the exact a_k (a relative 2^-13 of the score: no
-    // measurable number of extra survivors), never a missing one
-    const uint32_t a_k = select_prefix_desc<512, 2>(hist, scratch, need, [&](auto count_key) {
-#pragma unroll
-        for (int j = 0; j < PER + OVP; ++j) count_key(mine[j]);
-    });
-    // prune (finalize_mixed_kernel's rule); this workgroup keeps the survivors at positions pos % S == s
-    const float cut = f32_from_orderable(a_k) - 2.f * eps;
-    int n_surv = 0;
-#pragma unroll
-    for (int j = 0; j < PER + OVP; ++j)
-        if (mine[j] != 0ull && key_score(mine[j]) >= cut) {
-            ++n_surv;
-            if ((int)(key_pos(mine[j]) % (uint32_t)S) == s) keys[atomicAdd(&own_sh, 1)] = mine[j];
-        }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n_surv += __shfl_xor(n_surv, o, 64);
-    if (lane == 0 && n_surv) atomicAdd(&m_sh, n_surv);
-    __syncthreads();
-    const int m = m_sh, own = own_sh;                         // need <= m <= c
-    rescore_keys<8, 8>(keys, own, X, ldx, qv, d >> 2);
-    if (tid == 0) base_sh = __hip_atomic_fetch_add(&fcount[q], own, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    unsigned long long* list = exact + (long long)q * cap;
-    for (int i = tid; i < own; i += 512) list[base_sh + i] = keys[i];
-    if (!last_workgroup(&fticket[q], S, false)) return;
-    // the query's last workgroup: all m exact keys are in the list (NaN re-scores as key 0: they sort last)
-    for (int i = tid; i < m; i += 512) keys[i] = list[i];
-    __syncthreads();
-    const unsigned long long* sorted = sort_keys_desc<512>(keys, keys + (m <= 1024 ? 1024 : 2048), m, 0);
-    if (!certify_or_fail(sorted, need, (long long)c >= nrows, tau[q] + eps, fail, q, nq)) return;
-    write_result(sorted, m, k, q, outD, outI, pos_offset);
-}
+#define AMDREC_FUSED_KERNEL finalize_fused_kernel
+#define AMDREC_FUSED_PARAMS
+#define AMDREC_FUSED_BOOST
+#define AMDREC_FUSED_EPS(e) e
+#define AMDREC_FUSED_TERM
+#include "search_finalize_fused.hpp"
+#undef AMDREC_FUSED_KERNEL
+#undef AMDREC_FUSED_PARAMS
+#undef AMDREC_FUSED_BOOST
+#undef AMDREC_FUSED_EPS
+#undef AMDREC_FUSED_TERM
+// ... and its boosted sibling: fin_eps where eps is formed, fin_term in the re-score.  The name sorts behind every kernel
+// the module already had (search_finalize_fused.hpp says why that matters).
+#define AMDREC_FUSED_KERNEL finalize_fused_boosted_kernel
+#define AMDREC_FUSED_PARAMS , const float* boost, const float* weight, float boost_max
+#define AMDREC_FUSED_BOOST const Boosted bo{boost, weight, boost_max};
+#define AMDREC_FUSED_EPS(e) fin_eps(e, d, q, bo)
+#define AMDREC_FUSED_TERM , fin_term(bo, q)
+#include "search_finalize_fused.hpp"
+#undef AMDREC_FUSED_KERNEL
+#undef AMDREC_FUSED_PARAMS
+#undef AMDREC_FUSED_BOOST
+#undef AMDREC_FUSED_EPS
+#undef AMDREC_FUSED_TERM
 
 __global__ void fill_f32_kernel(float* p, long long n, float v) {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1373,8 +1470,8 @@ template <class S, class EL = NoElig>
 static hipError_t run_passes(const float* X, long long ldx, long long nrows, int d, const float* Q, long long ldq,
                              int nq, const SearchPlan& pl, hipStream_t st, int d_alg = 0,
                              bool filter = true, long long cand_stride = CAND_CAP, EL el = EL{}) {
-    using Store = std::conditional_t<EL::on, EpiStoreScoresT<EL>, EpiStoreScores>;
-    using Filter = std::conditional_t<EL::on, EpiFilterT<EL>, EpiFilter>;
+    using Store = std::conditional_t<EL::on || EL::boosted, EpiStoreScoresT<EL>, EpiStoreScores>;
+    using Filter = std::conditional_t<EL::on || EL::boosted, EpiFilterT<EL>, EpiFilter>;
     DenseRows lq{Q, nq, (int)ldq, d, 30, 1ll << 30};
     if (pl.n_sample > 0) {
         int gshift = 8;   // SAMPLE_G == 256
@@ -1486,7 +1583,10 @@ static int set_lds_limits() {
         {reinterpret_cast<const void*>(finalize_mixed_kernel<512, CAND_CAP>), CAND_CAP * 8 + 2048 * 4},
         {reinterpret_cast<const void*>(finalize_fused_kernel), CAND_CAP * 8 + 2048 * 4},
         {reinterpret_cast<const void*>(ScanKernels<NoElig>::fixup()), CAND_CAP * 8},
-        {reinterpret_cast<const void*>(ScanKernels<Elig>::fixup()), CAND_CAP * 8}};
+        {reinterpret_cast<const void*>(ScanKernels<Elig>::fixup()), CAND_CAP * 8},
+        {reinterpret_cast<const void*>(ScanKernels<Boosted>::fixup()), CAND_CAP * 8},
+        {reinterpret_cast<const void*>(finalize_mixed_kernel<512, CAND_CAP, AMDREC_BOOST_FIN>), CAND_CAP * 8 + 2048 * 4},
+        {reinterpret_cast<const void*>(finalize_fused_boosted_kernel), CAND_CAP * 8 + 2048 * 4}};
     for (const auto& l : limits) HIP_TRY(hipFuncSetAttribute(l.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, l.bytes));
     attr_done.mark();
     return AMDREC_OK;
@@ -1526,6 +1626,31 @@ static int elig_check(const uint64_t* tags, const uint64_t* require_all, const u
 }
 static int elig_check(NoElig, int64_t) { return AMDREC_OK; }
 static int elig_check(Elig el, int64_t nrows) { return elig_check(el.tags, el.all, el.any, nrows); }
+// ... and the boost arguments of the *_boosted entries: both pointers are required
+static int elig_check(Boosted bo, int64_t nrows) {
+    REQUIRE(bo.boost || nrows == 0, "boost is null");
+    REQUIRE(bo.weight, "weight is null");
+    // (boost: the streaming passes read the 32 boosts of a row quarter with two 64-byte scalar loads)
+    REQUIRE(((uintptr_t)bo.boost % 64) == 0 && ((uintptr_t)bo.weight % 4) == 0,
+            "boost must be 64-byte aligned, weight 4-byte aligned");
+    REQUIRE(bo.boost_max >= 0.f && bo.boost_max < INFINITY, "boost_max must be a finite bound of max |boost|");
+    return AMDREC_OK;
+}
+
+// finalize_mixed_kernel with the boost's arguments after the ones every instantiation takes
+template <int NT, int CAPK, class... A>
+static void launch_finalize_mixed(NoElig, dim3 grid, size_t lds, hipStream_t st, A... a) {
+    hipLaunchKernelGGL((finalize_mixed_kernel<NT, CAPK>), grid, dim3(NT), lds, st, a...);
+}
+template <int NT, int CAPK, class... A>
+static void launch_finalize_mixed(Elig, dim3 grid, size_t lds, hipStream_t st, A... a) {
+    hipLaunchKernelGGL((finalize_mixed_kernel<NT, CAPK>), grid, dim3(NT), lds, st, a...);
+}
+template <int NT, int CAPK, class... A>
+static void launch_finalize_mixed(Boosted bo, dim3 grid, size_t lds, hipStream_t st, A... a) {
+    hipLaunchKernelGGL((finalize_mixed_kernel<NT, CAPK, AMDREC_BOOST_FIN>), grid, dim3(NT), lds, st, a..., bo.boost, bo.weight,
+                       bo.boost_max);
+}
 
 template <class EL>
 static int flat_search_impl(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
@@ -1658,10 +1783,17 @@ static int flat_search_mixed_impl(const float* corpus, int64_t nrows, int64_t ld
     }
     if ((rc = set_lds_limits())) return rc;
     {
-        ProfScope prof("search_finalize_mixed", 0.0, 0.0, st);
+        ProfScope prof(EL::boosted ? "search_finalize_mixed_boost" : "search_finalize_mixed", 0.0, 0.0, st);
         if (nq <= FUSED_MAX_NQ) {
             int slices = (int)(512 / nq);                           // ~512 workgroups in all: the chip once
             slices = slices < 1 ? 1 : (slices > 16 ? 16 : slices);
+            if constexpr (EL::boosted)
+                hipLaunchKernelGGL(finalize_fused_boosted_kernel, dim3((unsigned)slices, (unsigned)nq), dim3(512),
+                                   (size_t)CAND_CAP * 8 + (size_t)dim * 4, st, pl.cand, CSTRIDE, segcnt, nseg, seg_cap, pl.ocnt,
+                                   CAND_CAP, k, (long long)nrows, pl.tau, max_norm, corpus, (long long)ld_corpus, dim, queries,
+                                   (long long)ld_queries, pl.fail, out_scores, (long long*)out_pos, (long long)pos_offset,
+                                   pl.exact, pl.fcount, pl.fticket, el.boost, el.weight, el.boost_max);
+            else
             hipLaunchKernelGGL(finalize_fused_kernel, dim3((unsigned)slices, (unsigned)nq), dim3(512), (size_t)CAND_CAP * 8 + (size_t)dim * 4, st, pl.cand, CSTRIDE,
                                segcnt, nseg, seg_cap, pl.ocnt, CAND_CAP, k, (long long)nrows, pl.tau, max_norm, corpus,
                                (long long)ld_corpus, dim, queries, (long long)ld_queries, pl.fail, out_scores,
@@ -1670,17 +1802,18 @@ static int flat_search_mixed_impl(const float* corpus, int64_t nrows, int64_t ld
             // one workgroup per query; short lists of many queries (the sharded search) on the small shapes: twice the
             // expected candidate count must fit (10 sigma of the threshold estimate; beyond it the query takes the fix-up scan)
 #define AMDREC_FINALIZE(NT_, CAPK_)                                                                                          \
-    hipLaunchKernelGGL((finalize_mixed_kernel<NT_, CAPK_>), dim3((unsigned)nq), dim3(NT_), (size_t)(CAPK_) * 8 + (size_t)dim * 4, \
-                       st, pl.cand, CSTRIDE, segcnt, nseg, seg_cap, pl.ocnt, k, (long long)nrows, pl.tau, max_norm, corpus,  \
-                       (long long)ld_corpus, dim, queries, (long long)ld_queries, pl.fail, out_scores, (long long*)out_pos,  \
-                       (long long)pos_offset)
+    launch_finalize_mixed<NT_, CAPK_>(el, dim3((unsigned)nq), (size_t)(CAPK_) * 8 + (size_t)dim * 4, st,                      \
+                                      (const unsigned long long*)pl.cand, CSTRIDE, segcnt, nseg, seg_cap, (const int*)pl.ocnt, k, \
+                                      (long long)nrows, (const float*)pl.tau, max_norm, corpus, (long long)ld_corpus, dim,     \
+                                      queries, (long long)ld_queries, pl.fail, out_scores, (long long*)out_pos,                \
+                                      (long long)pos_offset)
             if (pl.target > 0 && 2 * pl.target <= 1024 && dim <= 2048) AMDREC_FINALIZE(128, 1024);
             else if (pl.target > 0 && 2 * pl.target <= 2048 && dim <= 2048) AMDREC_FINALIZE(256, 2048);
             else AMDREC_FINALIZE(512, CAND_CAP);
 #undef AMDREC_FINALIZE
         }
     }
-    ProfScope prof_fix(EL::on ? "search_fixup_elig" : "search_fixup", 0.0, 0.0, st);
+    ProfScope prof_fix(tag_for<EL>("search_fixup", "search_fixup_elig", "search_fixup_boost"), 0.0, 0.0, st);
     return launch_fixup(corpus, ld_corpus, nrows, dim, queries, nq, ld_queries, k, pl, out_scores, out_pos, pos_offset, n_fixup, st,
                         el);
 }
@@ -1704,3 +1837,24 @@ extern "C" int amdrec_flat_search_mixed_eligible(const float* corpus, int64_t nr
                                   pos_offset, out_scores, out_pos, workspace, workspace_bytes, n_fixup, stream,
                                   Elig{tags, require_all, require_any});
 }
+
+extern "C" int amdrec_flat_search_boosted(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
+                                          const float* queries, int64_t nq, int64_t ld_queries, int k,
+                                          int64_t pos_offset, float* out_scores, int64_t* out_pos, void* workspace,
+                                          size_t workspace_bytes, int* n_fixup, void* stream, const float* boost,
+                                          const float* weight, float boost_max) {
+    return flat_search_impl(corpus, nrows, ld_corpus, dim, queries, nq, ld_queries, k, pos_offset, out_scores, out_pos, workspace,
+                            workspace_bytes, n_fixup, stream, Boosted{boost, weight, boost_max});
+}
+
+extern "C" int amdrec_flat_search_mixed_boosted(const float* corpus, int64_t nrows, int64_t ld_corpus, int dim,
+                                                const uint16_t* corpus_bf16, int64_t ld_bf16, const float* max_norm,
+                                                const float* queries, int64_t nq, int64_t ld_queries, int k,
+                                                int64_t pos_offset, float* out_scores, int64_t* out_pos, void* workspace,
+                                                size_t workspace_bytes, int* n_fixup, void* stream, const float* boost,
+                                                const float* weight, float boost_max) {
+    return flat_search_mixed_impl(corpus, nrows, ld_corpus, dim, corpus_bf16, ld_bf16, max_norm, queries, nq, ld_queries, k,
+                                  pos_offset, out_scores, out_pos, workspace, workspace_bytes, n_fixup, stream,
+                                  Boosted{boost, weight, boost_max});
+}
+#undef AMDREC_BOOST_FIN

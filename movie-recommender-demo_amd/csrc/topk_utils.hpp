@@ -267,8 +267,29 @@ __device__ __forceinline__ void dot_rows(const f32x4* (&xr)[RU], const float* qv
 // keys[0 .. n) in LDS (approximate score, corpus position) -> (exact fp32 score, position), by a block of NW waves: one
 // wave per key, RU rows (random 1 KB reads: latency-bound) in flight per wave.  A NaN score (inf - inf in fp32 that the bf16
 // pass did not produce) becomes key 0 and ranks last, as in the fix-up scan.  Ends with a block barrier.
-template <int NW, int RU>
-__device__ inline void rescore_keys(unsigned long long* keys, int n, const float* X, long long ldx, const float* qv, int d4) {
+// `term`: what is added to a row's inner product to form its score.  NoTerm: nothing - the plain searches.  RowBoost: the
+// boosted flat search's t = w * boost[pos], as TWO rounded fp32 operations, t = w * b and s = ip + t, whatever the
+// translation unit's contraction setting (a fused multiply-add would round once and differ from the scan's key in the last bit).
+__device__ __forceinline__ float boost_term(float w, float b) {
+#pragma clang fp contract(off)
+    return w * b;
+}
+__device__ __forceinline__ float boost_add(float ip, float t) {
+#pragma clang fp contract(off)
+    return ip + t;
+}
+struct NoTerm {
+    static constexpr bool boosted = false;
+};
+struct RowBoost {
+    static constexpr bool boosted = true;
+    const float* boost;      // [nrows]
+    float w;                 // the query's weight
+    __device__ __forceinline__ float operator()(float ip, uint32_t pos) const { return boost_add(ip, boost_term(w, boost[pos])); }
+};
+template <int NW, int RU, class Term = NoTerm>
+__device__ inline void rescore_keys(unsigned long long* keys, int n, const float* X, long long ldx, const float* qv, int d4,
+                                    Term term = Term{}) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     for (int i0 = w; i0 < n; i0 += NW * RU) {
         float a[RU];
@@ -285,7 +306,11 @@ __device__ inline void rescore_keys(unsigned long long* keys, int n, const float
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
             const int i = i0 + NW * u;
-            if (lane == 0 && i < n) keys[i] = (a[u] == a[u]) ? make_key(a[u], pos[u]) : 0ull;
+            if constexpr (Term::boosted) {
+                if (lane == 0 && i < n) keys[i] = (a[u] == a[u]) ? make_key(term(a[u], pos[u]), pos[u]) : 0ull;
+            } else {
+                if (lane == 0 && i < n) keys[i] = (a[u] == a[u]) ? make_key(a[u], pos[u]) : 0ull;
+            }
         }
     }
     __syncthreads();
