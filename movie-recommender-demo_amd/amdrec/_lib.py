@@ -333,3 +333,83 @@ class MeasuringArena:
 
 
 WORKSPACE = Workspace()
+
+
+class Gate:
+    """What threads that share the library must agree on, process-wide like the workspace it protects.
+
+    ``enqueue`` (a re-entrant lock): held while a call enqueues its device work.  The launches of one call write and read
+    the shared workspace one after the other on one stream; launches of two calling threads interleaved on that stream would
+    read each other's intermediate results.  Lazily built state (packed weights, per-ad caches, limits) is built under it
+    too.  The serving entry points of ``AdRecommenderInference`` take it themselves - around the enqueue only, not around
+    their host work or their wait for the device; whoever drives models or an index directly from several threads takes it
+    around each call.
+
+    ``serving()`` / ``capturing()``: a graph capture swaps the workspace for a private arena (``Workspace.private``) and
+    puts the runtime into its global capture mode, in which another thread's event wait or copy invalidates the capture: it
+    cannot run beside serving calls of other threads.  Neither waits for the other; the one that comes second raises
+    AmdrecError, before it has touched the device."""
+
+    def __init__(self):
+        self.enqueue = threading.RLock()
+        self._mu = threading.Lock()
+        self._calls = {}              # thread ident -> depth of its serving calls in flight
+        self._capturer = None         # thread ident of the capturing thread, and ...
+        self._capture_depth = 0       # ... the depth of its captures
+        # (the scopes hold no state of their own: one object each serves every call - the serving path pays no allocation)
+        self._serving, self._capturing = _Scope(self._enter_call, self._exit_call), _Scope(self._enter_capture, self._exit_capture)
+
+    def serving(self):
+        return self._serving
+
+    def capturing(self):
+        return self._capturing
+
+    def _enter_call(self):
+        me = threading.get_ident()
+        with self._mu:
+            if self._capturer is not None and self._capturer != me:
+                raise AmdrecError("a graph capture is in progress on another thread: serving calls cannot run beside capture() "
+                                  "(INTEGRATION.md, threads)")
+            self._calls[me] = self._calls.get(me, 0) + 1
+
+    def _exit_call(self):
+        me = threading.get_ident()
+        with self._mu:
+            left = self._calls[me] - 1
+            if left:
+                self._calls[me] = left
+            else:
+                del self._calls[me]
+
+    def _enter_capture(self):
+        me = threading.get_ident()
+        with self._mu:
+            if (self._capturer is not None and self._capturer != me) or any(t != me for t in self._calls):
+                raise AmdrecError("capture() while other threads are serving or capturing: a graph capture swaps the process-wide "
+                                  "workspace and the runtime's capture mode is global (INTEGRATION.md, threads)")
+            self._capturer = me
+            self._capture_depth += 1
+
+    def _exit_capture(self):
+        with self._mu:
+            self._capture_depth -= 1
+            if not self._capture_depth:
+                self._capturer = None
+
+
+class _Scope:
+    __slots__ = ("_enter", "_exit")
+
+    def __init__(self, enter, exit_):
+        self._enter, self._exit = enter, exit_
+
+    def __enter__(self):
+        self._enter()
+
+    def __exit__(self, *exc):
+        self._exit()
+        return False
+
+
+GATE = Gate()

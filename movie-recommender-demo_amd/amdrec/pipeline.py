@@ -20,6 +20,7 @@ Deviations, each forced by a reference defect:
 from __future__ import annotations
 
 import json
+import threading
 import time
 from pathlib import Path
 from typing import Dict, List, Optional
@@ -167,11 +168,9 @@ class AdRecommenderInference:
         cols = [c for c in USER_COLS if c in pp.classes]
         B, nc, nn_ = len(user_data_list), len(cols), len(pp.numerical_cols)
         dev = self.ad_features.device
-        if getattr(self, "_pp_dev", (None,))[0] is not pp:
-            self._pp_dev = (pp, torch.from_numpy(pp.mean.astype(np.float32)).to(dev),
-                            torch.from_numpy(pp.scale.astype(np.float32)).to(dev))
         # ONE pinned staging block [categorical int64 | raw numerical float32] and ONE H2D copy per call (two pageable
-        # copies cost ~25 us of a 0.4 ms request); the block is reused once its previous copy has completed
+        # copies cost ~25 us of a 0.4 ms request); the block is reused once its previous copy has completed.  The block is
+        # the calling thread's own (_staging): it is filled outside the enqueue lock, beside other threads' device work
         cat_bytes = B * nc * 8
         ex_off = (cat_bytes + B * nn_ * 4 + 7) // 8 * 8                 # the int64 exclusion block, 8-byte aligned
         m_off = ex_off + (0 if exclude is None else exclude.size * 8)   # the int64 mask words
@@ -191,14 +190,19 @@ class AdRecommenderInference:
             hv[m_off:m_off + 2 * B * 8].view(np.int64).reshape(2, B)[:] = masks
         if weights is not None:
             hv[w_off:w_off + B * 4].view(np.float32)[:] = weights
-        blk = host.to(dev, non_blocking=True)
-        done.record(torch.cuda.current_stream(dev))
-        cat = blk[:cat_bytes].view(torch.int64).view(B, nc)
-        x = blk[cat_bytes:cat_bytes + B * nn_ * 4].view(torch.float32).view(B, nn_)
-        out = torch.empty_like(x)
-        lib = _lib.load()
-        _lib.check(lib.amdrec_prep_numerical(_lib.ptr(x), _lib.ptr(self._pp_dev[1]), _lib.ptr(self._pp_dev[2]),
-                                             _lib.ptr(out), x.shape[0], x.shape[1], _lib.stream_ptr(dev)))
+        with _lib.GATE.enqueue:
+            pp_dev = getattr(self, "_pp_dev", (None,))
+            if pp_dev[0] is not pp:
+                pp_dev = self._pp_dev = (pp, torch.from_numpy(pp.mean.astype(np.float32)).to(dev),
+                                         torch.from_numpy(pp.scale.astype(np.float32)).to(dev))
+            blk = host.to(dev, non_blocking=True)
+            done.record(torch.cuda.current_stream(dev))
+            cat = blk[:cat_bytes].view(torch.int64).view(B, nc)
+            x = blk[cat_bytes:cat_bytes + B * nn_ * 4].view(torch.float32).view(B, nn_)
+            out = torch.empty_like(x)
+            lib = _lib.load()
+            _lib.check(lib.amdrec_prep_numerical(_lib.ptr(x), _lib.ptr(pp_dev[1]), _lib.ptr(pp_dev[2]),
+                                                 _lib.ptr(out), x.shape[0], x.shape[1], _lib.stream_ptr(dev)))
         res = (cat, out)
         if exclude is not None:
             res += (blk[ex_off:m_off].view(torch.int64).view(exclude.shape),)
@@ -211,8 +215,11 @@ class AdRecommenderInference:
     def _staging(self, nbytes: int, slot: str = "in"):
         """Pinned host block of at least ``nbytes`` + the event of its last use (waited for before it is handed out again).
         ``slot``: blocks of different slots are different memory, so the inputs ("in"), a separately shipped exclusion
-        block ("excl") and the results ("out") of one call never wait for each other."""
-        st = self.__dict__.setdefault("_stage_bufs", {})
+        block ("excl") and the results ("out") of one call never wait for each other.  The blocks belong to the calling
+        THREAD (``_per_thread``): a block's event only says that its last copy has completed, not that the thread that
+        ordered the copy has finished reading the block, so a block shared by two threads could be overwritten under the
+        one still converting its results."""
+        st = self._per_thread().__dict__.setdefault("stage_bufs", {})
         size = 256
         while size < nbytes:
             size *= 2
@@ -222,6 +229,13 @@ class AdRecommenderInference:
         else:
             ent[1].synchronize()
         return ent[0][:nbytes], ent[1]
+
+    def _per_thread(self):
+        """The calling thread's part of this object's state: its pinned staging blocks and its timing events."""
+        tl = self.__dict__.get("_thread_state")
+        if tl is None:
+            tl = self.__dict__.setdefault("_thread_state", threading.local())      # (setdefault: one winner among threads)
+        return tl
 
     HEADS_MODES = ("all", "ctr_first")
 
@@ -421,11 +435,14 @@ class AdRecommenderInference:
         un = _lib.require_gpu(user_numerical, "user_numerical")
         excluded = exclude_ad_ids is not None and exclude_ad_ids.shape[-1] > 0
         masked = require_all is not None or require_any is not None
-        cand_pos, cand_scores = self._stage1(uc, un, stage1_k, check_indices, exclude_ad_ids if excluded else None,
-                                             (require_all, require_any), cap1, stage1_boost)
-        # (excluded: "a slot can be unfilled" - true after a filtered stage 1 as well)
-        out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded or masked or cap1 is not None,
-                           heads=heads, max_per_group=cap, auction=auction, diversity=div)
+        # one calling thread at a time enqueues (amdrec._lib.Gate): the launches below hand their intermediate results to
+        # each other through the process-wide workspace, and the lazily built state is built in here
+        with _lib.GATE.serving(), _lib.GATE.enqueue:
+            cand_pos, cand_scores = self._stage1(uc, un, stage1_k, check_indices, exclude_ad_ids if excluded else None,
+                                                 (require_all, require_any), cap1, stage1_boost)
+            # (excluded: "a slot can be unfilled" - true after a filtered stage 1 as well)
+            out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded or masked or cap1 is not None,
+                               heads=heads, max_per_group=cap, auction=auction, diversity=div)
         out["candidate_scores"] = cand_scores
         return out
 
@@ -459,14 +476,15 @@ class AdRecommenderInference:
         projected again.  Rows of the table beyond the index's old ntotal (a table longer than the corpus) are dropped.
         Out of place throughout: a graph captured before the call keeps replaying the corpus it was captured with (stale,
         consistent); capture again to serve the new one.  Synchronises with the host once (the survivor count)."""
-        removed, kept = self.faiss_index.remove_ids(ad_ids, return_kept=True)
-        if not removed:
-            return 0
-        old = self.ad_features
-        new = _rows_edit.gather_rows(old, kept)
-        self.transformer_ranker.compact_ad_cache(old, kept, new)
-        self._swap_ad_table(old, new)
-        return removed
+        with _lib.GATE.enqueue:                  # (index, table and caches change together under a serving thread's feet)
+            removed, kept = self.faiss_index.remove_ids(ad_ids, return_kept=True)
+            if not removed:
+                return 0
+            old = self.ad_features
+            new = _rows_edit.gather_rows(old, kept)
+            self.transformer_ranker.compact_ad_cache(old, kept, new)
+            self._swap_ad_table(old, new)
+            return removed
 
     def add_ads(self, embeddings, ad_features, ad_ids=None, tags=None, groups=None, bids=None, boosts=None) -> None:
         """Insert ads: ``embeddings`` [m, d] go to the index (FAISSIndex.add: ``ad_ids`` as there; required once ads have been
@@ -489,12 +507,14 @@ class AdRecommenderInference:
                              dtype=torch.int64, device=self.device)
         if feats.numel() and bool(((feats < 0) | (feats >= cards)).any().item()):
             raise IndexError("index out of range in self: an ad_features row is outside the ranker's ad embedding tables")
-        n_old = idx.index.ntotal
-        idx.add(embeddings, ad_ids, tags=tags, groups=groups, bids=bids, boosts=boosts)   # (refuses before it commits anything)
-        new = torch.cat([old[:n_old], feats])
-        if old.shape[0] == n_old:
-            self.transformer_ranker.extend_ad_cache(old, new)
-        self._swap_ad_table(old, new)
+        with _lib.GATE.enqueue:
+            old = self.ad_features
+            n_old = idx.index.ntotal
+            idx.add(embeddings, ad_ids, tags=tags, groups=groups, bids=bids, boosts=boosts)   # (refuses before it commits anything)
+            new = torch.cat([old[:n_old], feats])
+            if old.shape[0] == n_old:
+                self.transformer_ranker.extend_ad_cache(old, new)
+            self._swap_ad_table(old, new)
 
     def _swap_ad_table(self, old, new):
         """Install ``new`` as the ad-feature table.  A "valid" verdict of the once-per-table check (_ad_table_valid) is
@@ -555,14 +575,15 @@ class AdRecommenderInference:
         excl = self._host_exclusions(exclude_ad_ids, n, stage1_k)
         masks = self._host_masks(require_all, require_any, n)
         wts = None if stage1_boost is None else _boost.as_weights(stage1_boost, n)
-        uc, un, *rest = self.preprocess_batch(user_data_list, excl, masks, wts)
-        excl = rest.pop(0) if excl is not None else None
-        masks = rest.pop(0) if masks is not None else None
-        wts = rest.pop(0) if wts is not None else None
-        return self.recommend_tensors(uc, un, top_k, stage1_k, return_scores, _encoded=True, _exclude_dev=excl,
-                                      _masks_dev=masks, _boost_dev=wts, max_per_group=max_per_group,
-                                      stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve,
-                                      diversity=diversity, diversity_pool=diversity_pool)
+        with _lib.GATE.serving():
+            uc, un, *rest = self.preprocess_batch(user_data_list, excl, masks, wts)
+            excl = rest.pop(0) if excl is not None else None
+            masks = rest.pop(0) if masks is not None else None
+            wts = rest.pop(0) if wts is not None else None
+            return self.recommend_tensors(uc, un, top_k, stage1_k, return_scores, _encoded=True, _exclude_dev=excl,
+                                          _masks_dev=masks, _boost_dev=wts, max_per_group=max_per_group,
+                                          stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve,
+                                          diversity=diversity, diversity_pool=diversity_pool)
 
     def _check_caps(self, max_per_group, stage1_max_per_group):
         """The two cap arguments -> (cap or None, stage-1 cap or None); refusals before the library is touched."""
@@ -657,100 +678,107 @@ class AdRecommenderInference:
         auction = self._check_auction(rank_by, reserve)
         div = self._check_diversity(diversity, diversity_pool, top_k, auction)
         t0 = time.time()
-        dev = self.device
-        uc = user_categorical.to(dev)
-        un = user_numerical.to(dev)
-        n = uc.shape[0]
-        if not n:
-            return []
-        excl = _exclude_dev
-        if excl is None and exclude_ad_ids is not None:
-            hb = self._host_exclusions(exclude_ad_ids, n, stage1_k)
-            if hb is not None:
-                host, done = self._staging(hb.size * 8, "excl")
-                host.numpy().view(np.int64).reshape(hb.shape)[:] = hb
-                excl = host.to(dev, non_blocking=True).view(torch.int64).view(hb.shape)
+        with _lib.GATE.serving():
+            # host side first, beside other threads' enqueues: the inputs' copies to the device (torch ops: they use no
+            # workspace), the option blocks converted and written into staging blocks that are this thread's own
+            dev = self.device
+            uc = user_categorical.to(dev)
+            un = user_numerical.to(dev)
+            n = uc.shape[0]
+            if not n:
+                return []
+            excl = _exclude_dev
+            if excl is None and exclude_ad_ids is not None:
+                hb = self._host_exclusions(exclude_ad_ids, n, stage1_k)
+                if hb is not None:
+                    host, done = self._staging(hb.size * 8, "excl")
+                    host.numpy().view(np.int64).reshape(hb.shape)[:] = hb
+                    excl = host.to(dev, non_blocking=True).view(torch.int64).view(hb.shape)
+                    done.record(torch.cuda.current_stream(dev))
+            masks = _masks_dev
+            if masks is None:
+                hm = self._host_masks(require_all, require_any, n)
+                if hm is not None:
+                    host, done = self._staging(hm.size * 8, "masks")
+                    host.numpy().view(np.int64).reshape(hm.shape)[:] = hm
+                    masks = host.to(dev, non_blocking=True).view(torch.int64).view(hm.shape)
+                    done.record(torch.cuda.current_stream(dev))
+            wts = _boost_dev
+            if wts is None and stage1_boost is not None:
+                hw = _boost.as_weights(stage1_boost, n)
+                host, done = self._staging(hw.size * 4, "boost")
+                host.numpy().view(np.float32)[:] = hw
+                wts = host.to(dev, non_blocking=True).view(torch.float32)
                 done.record(torch.cuda.current_stream(dev))
-        masks = _masks_dev
-        if masks is None:
-            hm = self._host_masks(require_all, require_any, n)
-            if hm is not None:
-                host, done = self._staging(hm.size * 8, "masks")
-                host.numpy().view(np.int64).reshape(hm.shape)[:] = hm
-                masks = host.to(dev, non_blocking=True).view(torch.int64).view(hm.shape)
-                done.record(torch.cuda.current_stream(dev))
-        wts = _boost_dev
-        if wts is None and stage1_boost is not None:
-            hw = _boost.as_weights(stage1_boost, n)
-            host, done = self._staging(hw.size * 4, "boost")
-            host.numpy().view(np.float32)[:] = hw
-            wts = host.to(dev, non_blocking=True).view(torch.float32)
-            done.record(torch.cuda.current_stream(dev))
-        tasks = list(self.transformer_ranker.prediction_heads.keys())        # the ranker's task order (= out["tasks"])
-        ev = self.__dict__.get("_ev")
-        if ev is None:
-            ev = self.__dict__["_ev"] = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        ids_b, sc_b = n * top_k * 8, len(tasks) * n * top_k * 4
-        au_b = 0 if auction is None else n * top_k * 4                       # ecpm, then prices, behind the scores
-        dv_b = 0 if div is None else n * top_k * 4                           # diversity_values, there instead (never both)
-        blk = torch.empty(ids_b + sc_b + 2 * au_b + dv_b + 8, dtype=torch.uint8, device=dev)
-        ad_ids = blk[:ids_b].view(torch.int64).view(n, top_k)
-        scores = blk[ids_b:ids_b + sc_b].view(torch.float32).view(len(tasks), n, top_k)
-        outs = (ad_ids, scores)
-        if auction is not None:
-            outs += tuple(blk[ids_b + sc_b + i * au_b:ids_b + sc_b + (i + 1) * au_b].view(torch.float32).view(n, top_k)
-                          for i in range(2))
-        if div is not None:
-            outs += (blk[ids_b + sc_b:ids_b + sc_b + dv_b].view(torch.float32).view(n, top_k),)
-        verdict = blk[ids_b + sc_b + 2 * au_b + dv_b:].view(torch.int32)     # [2]: nonzero = an index out of range
-        trusted = _encoded and self.preprocessor is not None and self._encoder_fits()
-        if trusted:
-            verdict.zero_()
-        else:
-            if uc.dim() != 2 or uc.shape[1] != len(self._user_limits()[0]):
-                raise ValueError(f"user_categorical must be [B, {len(self._user_limits()[0])}]")
-            ucl = uc.long()
-            verdict.copy_(((ucl < 0) | (ucl >= self._user_limits()[1])).any().to(torch.int32).expand(2))
-        if not self._ad_table_valid():
-            raise IndexError("index out of range in self")                    # (the ad-feature table, transformer_ranker.py:322)
-        st = torch.cuda.current_stream(dev)
-        ev[0].record(st)
-        cand_pos, _ = self._stage1(uc, un, stage1_k, False, excl, (None, None) if masks is None else (masks[0], masks[1]), cap1,
-                                   wts)
-        ev[1].record(st)
-        out = self._stage2(uc, un, cand_pos, top_k, False, out=outs,
-                           excluded=excl is not None or masks is not None or cap1 is not None, max_per_group=cap,
-                           auction=auction, diversity=div)
-        assert list(out["tasks"]) == tasks
-        host, done = self._staging(blk.numel(), "out")
-        host.copy_(blk, non_blocking=True)
-        ev[2].record(st)
-        done.record(st)
-        ev[2].synchronize()
-        hv = host.numpy()
-        if int(hv[ids_b + sc_b + 2 * au_b + dv_b:].view(np.int32)[0]):
-            raise IndexError("index out of range in self")                    # torch.nn.Embedding's message
-        ids = hv[:ids_b].view(np.int64).reshape(n, top_k).tolist()
-        sc = hv[ids_b:ids_b + sc_b].view(np.float32).reshape(len(tasks), n, top_k).tolist() if return_scores else None
-        au = None if auction is None else hv[ids_b + sc_b:ids_b + sc_b + 2 * au_b].view(np.float32).reshape(2, n, top_k).tolist()
-        dv = None if div is None else hv[ids_b + sc_b:ids_b + sc_b + dv_b].view(np.float32).reshape(n, top_k).tolist()
-        t2 = time.time()
-        # stage 1 = its GPU time (tower + search, as the reference brackets them); stage 2 = the rest of the call's wall time
-        # (ranker, selection, the copy back and the list conversion: what the reference's second bracket holds)
-        total_ms = (t2 - t0) * 1000 / n
-        stage1_ms = min(ev[0].elapsed_time(ev[1]) / n, total_ms)
-        res = []
-        for b in range(n):
-            r = {"ad_ids": ids[b],
-                 "timing": {"stage1_ms": stage1_ms, "stage2_ms": total_ms - stage1_ms, "total_ms": total_ms}}
-            if return_scores:
-                r["scores"] = {t: sc[i][b] for i, t in enumerate(tasks)}
-            if au is not None:
-                r["ecpm"], r["prices"] = au[0][b], au[1][b]
-            if dv is not None:
-                r["diversity_values"] = dv[b]
-            res.append(r)
-        return res
+            # the enqueue, one calling thread at a time (amdrec._lib.Gate); the wait for the device and the list conversion
+            # behind it run beside other threads' enqueues, on staging blocks and events that are this thread's own
+            with _lib.GATE.enqueue:
+                tasks = list(self.transformer_ranker.prediction_heads.keys())        # the ranker's task order (= out["tasks"])
+                tl = self._per_thread()                                          # the timing events are the calling thread's own
+                ev = getattr(tl, "ev", None)
+                if ev is None:
+                    ev = tl.ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                ids_b, sc_b = n * top_k * 8, len(tasks) * n * top_k * 4
+                au_b = 0 if auction is None else n * top_k * 4                       # ecpm, then prices, behind the scores
+                dv_b = 0 if div is None else n * top_k * 4                           # diversity_values, there instead (never both)
+                blk = torch.empty(ids_b + sc_b + 2 * au_b + dv_b + 8, dtype=torch.uint8, device=dev)
+                ad_ids = blk[:ids_b].view(torch.int64).view(n, top_k)
+                scores = blk[ids_b:ids_b + sc_b].view(torch.float32).view(len(tasks), n, top_k)
+                outs = (ad_ids, scores)
+                if auction is not None:
+                    outs += tuple(blk[ids_b + sc_b + i * au_b:ids_b + sc_b + (i + 1) * au_b].view(torch.float32).view(n, top_k)
+                                  for i in range(2))
+                if div is not None:
+                    outs += (blk[ids_b + sc_b:ids_b + sc_b + dv_b].view(torch.float32).view(n, top_k),)
+                verdict = blk[ids_b + sc_b + 2 * au_b + dv_b:].view(torch.int32)     # [2]: nonzero = an index out of range
+                trusted = _encoded and self.preprocessor is not None and self._encoder_fits()
+                if trusted:
+                    verdict.zero_()
+                else:
+                    if uc.dim() != 2 or uc.shape[1] != len(self._user_limits()[0]):
+                        raise ValueError(f"user_categorical must be [B, {len(self._user_limits()[0])}]")
+                    ucl = uc.long()
+                    verdict.copy_(((ucl < 0) | (ucl >= self._user_limits()[1])).any().to(torch.int32).expand(2))
+                if not self._ad_table_valid():
+                    raise IndexError("index out of range in self")                    # (the ad-feature table, transformer_ranker.py:322)
+                st = torch.cuda.current_stream(dev)
+                ev[0].record(st)
+                cand_pos, _ = self._stage1(uc, un, stage1_k, False, excl,
+                                           (None, None) if masks is None else (masks[0], masks[1]), cap1, wts)
+                ev[1].record(st)
+                out = self._stage2(uc, un, cand_pos, top_k, False, out=outs,
+                                   excluded=excl is not None or masks is not None or cap1 is not None, max_per_group=cap,
+                                   auction=auction, diversity=div)
+                assert list(out["tasks"]) == tasks
+                host, done = self._staging(blk.numel(), "out")
+                host.copy_(blk, non_blocking=True)
+                ev[2].record(st)
+                done.record(st)
+            ev[2].synchronize()
+            hv = host.numpy()
+            if int(hv[ids_b + sc_b + 2 * au_b + dv_b:].view(np.int32)[0]):
+                raise IndexError("index out of range in self")                    # torch.nn.Embedding's message
+            ids = hv[:ids_b].view(np.int64).reshape(n, top_k).tolist()
+            sc = hv[ids_b:ids_b + sc_b].view(np.float32).reshape(len(tasks), n, top_k).tolist() if return_scores else None
+            au = None if auction is None else hv[ids_b + sc_b:ids_b + sc_b + 2 * au_b].view(np.float32).reshape(2, n, top_k).tolist()
+            dv = None if div is None else hv[ids_b + sc_b:ids_b + sc_b + dv_b].view(np.float32).reshape(n, top_k).tolist()
+            t2 = time.time()
+            # stage 1 = its GPU time (tower + search, as the reference brackets them); stage 2 = the rest of the call's wall time
+            # (ranker, selection, the copy back and the list conversion: what the reference's second bracket holds)
+            total_ms = (t2 - t0) * 1000 / n
+            stage1_ms = min(ev[0].elapsed_time(ev[1]) / n, total_ms)
+            res = []
+            for b in range(n):
+                r = {"ad_ids": ids[b],
+                     "timing": {"stage1_ms": stage1_ms, "stage2_ms": total_ms - stage1_ms, "total_ms": total_ms}}
+                if return_scores:
+                    r["scores"] = {t: sc[i][b] for i, t in enumerate(tasks)}
+                if au is not None:
+                    r["ecpm"], r["prices"] = au[0][b], au[1][b]
+                if dv is not None:
+                    r["diversity_values"] = dv[b]
+                res.append(r)
+            return res
 
 
 class TwoStageRetriever:
@@ -793,19 +821,25 @@ class TwoStageRetriever:
         un = user_numerical.to(self.device, dtype=torch.float32)
         excl = None if exclude_ad_ids is None else [exclude_ad_ids]
         if ad_features_lookup is None:                                            # :329-331
-            emb = self.two_tower_model.get_user_embeddings(uc, un)
             blk = _exclude.as_block(excl, 1)
-            ids, dist = self.faiss_index.search_device(
-                emb[:1] if blk is not None else emb, stage1_k,
-                exclude=None if blk is None else torch.from_numpy(blk).to(self.device), max_per_group=cap1,
-                boost_weight=stage1_boost)
-            return ids[0].tolist(), dist[0].tolist()
-        if self._rec is None or self._rec_table is not ad_features_lookup:
-            self._rec = AdRecommenderInference(device=str(self.device), two_tower_model=self.two_tower_model,
-                                               transformer_ranker=self.transformer_ranker,
-                                               faiss_index=self.faiss_index, ad_features=ad_features_lookup)
-            self._rec_table = ad_features_lookup
-        r = self._rec.recommend_tensors(uc[:1], un[:1], stage2_k, stage1_k,       # one synchronisation, indices validated
+            # threads: the enqueue under the process-wide lock, like AdRecommenderInference (amdrec._lib.Gate); the read-back
+            # outside it
+            with _lib.GATE.serving():
+                with _lib.GATE.enqueue:
+                    emb = self.two_tower_model.get_user_embeddings(uc, un)
+                    ids, dist = self.faiss_index.search_device(
+                        emb[:1] if blk is not None else emb, stage1_k,
+                        exclude=None if blk is None else torch.from_numpy(blk).to(self.device), max_per_group=cap1,
+                        boost_weight=stage1_boost)
+                return ids[0].tolist(), dist[0].tolist()
+        with _lib.GATE.enqueue:                                                   # (one builder of the lazy recommender)
+            rec = self._rec
+            if rec is None or self._rec_table is not ad_features_lookup:
+                rec = AdRecommenderInference(device=str(self.device), two_tower_model=self.two_tower_model,
+                                             transformer_ranker=self.transformer_ranker,
+                                             faiss_index=self.faiss_index, ad_features=ad_features_lookup)
+                self._rec, self._rec_table = rec, ad_features_lookup
+        r = rec.recommend_tensors(uc[:1], un[:1], stage2_k, stage1_k,             # one synchronisation, indices validated
                                         exclude_ad_ids=excl, max_per_group=cap, stage1_max_per_group=cap1,
                                         rank_by=rank_by, reserve=reserve, diversity=diversity,
                                         diversity_pool=diversity_pool, stage1_boost=stage1_boost)[0]
@@ -821,6 +855,14 @@ class GraphedRecommender:
                  max_exclude: int = 0, eligibility: bool = False, max_per_group: Optional[int] = None,
                  stage1_max_per_group: Optional[int] = None, rank_by: Optional[str] = None, reserve: bool = False,
                  diversity: Optional[float] = None, diversity_pool: int = 64, stage1_boost: bool = False):
+        # the capture gate first: while another thread captures, the runtime is in its global capture mode, and the
+        # allocations and fills of the static buffers below would already disturb it.  Refused before the device is touched
+        with _lib.GATE.capturing():
+            self._init(rec, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group, stage1_max_per_group,
+                       rank_by, reserve, diversity, diversity_pool, stage1_boost)
+
+    def _init(self, rec, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group, stage1_max_per_group,
+              rank_by, reserve, diversity, diversity_pool, stage1_boost):
         self.rec, self.batch_size, self.top_k, self.stage1_k = rec, batch_size, top_k, stage1_k
         # the per-group caps: scalars fixed at capture (the group keys are those of capture time, pinned below)
         self.max_per_group, self.stage1_max_per_group = rec._check_caps(max_per_group, stage1_max_per_group)
@@ -857,6 +899,17 @@ class GraphedRecommender:
             rec.faiss_index._check_boost(self._boost_w, self.eligibility)
             caps.update(stage1_boost=self._boost_w)
         # sizing + warm-up pass on the shared workspace (packs weights, sets kernel attributes)
+        # the capture swaps the process-wide workspace and the runtime's capture mode is global: not beside other threads'
+        # calls (amdrec._lib.Gate: refused, either way round - __init__ holds the gate), and no other thread enqueues in between
+        self._replay_lock, self._replay_owner, self._replay_depth = threading.Lock(), None, 0
+        with _lib.GATE.enqueue:
+            self._capture(rec, dev, top_k, stage1_k, warmup, ma, my, caps)
+        # pin every device buffer the kernel nodes point at: a later load_state_dict / index.add() / larger eager search
+        # then makes the graph stale (documented) but can never leave it with dangling pointers
+        self._pinned = (rec.two_tower_model.user_tower._packed, rec.transformer_ranker._packed, rec.ad_features,
+                        rec.transformer_ranker._ad_cache, *rec.faiss_index.resident_tensors())
+
+    def _capture(self, rec, dev, top_k, stage1_k, warmup, ma, my, caps):
         probe = _lib.MeasuringArena(_lib.Workspace())
         with _lib.WORKSPACE.private(probe):
             for _ in range(max(1, warmup)):
@@ -873,15 +926,40 @@ class GraphedRecommender:
                 self._out = rec.recommend_device(self._uc, self._un, top_k, stage1_k, exclude_ad_ids=self._ex, require_all=ma,
                                                  require_any=my, **caps)
         torch.cuda.synchronize(dev)
-        # pin every device buffer the kernel nodes point at: a later load_state_dict / index.add() / larger eager search
-        # then makes the graph stale (documented) but can never leave it with dangling pointers
-        self._pinned = (rec.two_tower_model.user_tower._packed, rec.transformer_ranker._packed, rec.ad_features,
-                        rec.transformer_ranker._ad_cache, *rec.faiss_index.resident_tensors())
 
-    @torch.no_grad()
+    def replaying(self):
+        """The scope of one replay: entered by ``__call__``, and by a caller that wants to keep the static output buffers to
+        itself until it has read them.  A second thread that enters while it is held gets AmdrecError - it does not wait:
+        one GraphedRecommender serves one thread at a time (threads)."""
+        return _lib._Scope(self._enter_replay, self._exit_replay)
+
+    def _enter_replay(self):
+        me = threading.get_ident()
+        with self._replay_lock:
+            if self._replay_owner not in (None, me):
+                raise _lib.AmdrecError("this GraphedRecommender is being replayed by another thread: its outputs are static "
+                                       "buffers, one thread at a time (INTEGRATION.md, threads)")
+            self._replay_owner, self._replay_depth = me, self._replay_depth + 1
+
+    def _exit_replay(self):
+        with self._replay_lock:
+            self._replay_depth -= 1
+            if not self._replay_depth:
+                self._replay_owner = None
+
     def __call__(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor,
                  exclude: Optional[torch.Tensor] = None, require_all: Optional[torch.Tensor] = None,
                  require_any: Optional[torch.Tensor] = None, reserve=None, stage1_boost=None):
+        """One replay - arguments and result: ``_replay`` - inside ``replaying()`` and the serving scope: a replay that
+        overlaps another thread's replay of this object, or another thread's capture, raises AmdrecError before it has
+        touched the static buffers."""
+        with self.replaying(), _lib.GATE.serving():
+            return self._replay(user_categorical, user_numerical, exclude, require_all, require_any, reserve, stage1_boost)
+
+    @torch.no_grad()
+    def _replay(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor,
+                exclude: Optional[torch.Tensor] = None, require_all: Optional[torch.Tensor] = None,
+                require_any: Optional[torch.Tensor] = None, reserve=None, stage1_boost=None):
         """Device tensors [batch_size, ...] -> the same dict as recommend_device (static output buffers,
         overwritten by the next call).  ``exclude``: device int64 [batch_size, E <= max_exclude] ad ids (negative =
         padding), copied into the graph's block; None = nothing excluded (the block is filled with -1).  ``require_all`` /
