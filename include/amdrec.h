@@ -37,7 +37,9 @@ extern "C" {
                                * amdrec_ivf_scan_grouped_mixed_eligible, amdrec_ivfpq_scan_finite_eligible, added exports; then
                                * the per-group caps: amdrec_select_topk_capped, amdrec_group_cap_compact, added exports; then
                                * auction ranking: amdrec_select_topk_auction, an added export; then
-                               * per-ad score boosts: amdrec_flat_search_boosted, amdrec_flat_search_mixed_boosted, added exports) */
+                               * per-ad score boosts: amdrec_flat_search_boosted, amdrec_flat_search_mixed_boosted, added exports; then
+                               * the same boosts in the inverted-list scans: amdrec_ivf_scan[_grouped[_mixed]][_eligible]_boosted and
+                               * amdrec_ivf_filter_bounds_boosted, added exports) */
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -216,6 +218,73 @@ int amdrec_ivf_scan_grouped_mixed_eligible(const float* lists, int64_t ld, const
                                            const float* tau_lo /*[nq]*/, int64_t* pool_fill /*[nq]*/, void* stream,
                                            const uint64_t* list_tags /*[N], list order*/, const uint64_t* require_all /*[nq]*/,
                                            const uint64_t* require_any /*[nq]*/);
+/* Stage-1 score boosts in the list scans: the three scans above, and their *_eligible twins, under the retrieval key of
+ * amdrec_flat_search_boosted,
+ *     s(q, r) = ip(q, r) + weight[q] * boost[r],
+ * where ip is, bit for bit, the score the twin without the boost files for the row, t = weight[q] * boost[r] one rounded
+ * fp32 multiply and s = ip + t one rounded fp32 add (never fused); s is what the key holds, under the scans' own rule (a NaN
+ * s is filed as -inf).  Each entry takes the argument list of its twin plus two device pointers, both required and 4-byte
+ * aligned (checked with the other arguments, before the first HIP call):
+ *   list_boosts [N]  one float per LIST-ORDER row, list_boosts[r] = boost of corpus row row_pos[r]; exactly N values read,
+ *   weight      [nq] indexed by the query numbers of the call, as require_all / require_any are.
+ * Slot mode files key(s) where the twin files key(ip) (key 0 for an ineligible pair as before); filter mode keeps a row when
+ * s >= tau[q * ld_tau] - with tau[q] = the k-th BOOSTED score over a subset of the probes, still a lower bound of the final
+ * k-th boosted score, the two-phase search stays exact.  The bf16 prefilter nominates on fl(bf16 score + t) >= tau_lo[q] and
+ * files fl(fp32 re-score + t); its tau_lo comes from amdrec_ivf_filter_bounds_boosted (the plain entry's arguments + weight
+ * and boost_max, a finite host upper bound of max |boost|), which widens the plain bound for the two roundings:
+ *     tau_lo = tau - eps_q - c (|weight[q]| boost_max + ||q|| (M + D) + eps_q),   c = 3e-7 >= 5 * 2^-24
+ * (derivation: csrc/ivf.hip, above ivf_filter_bounds_kernel).  A non-finite bound re-scores every row, as in the plain entry.
+ * The probes are the caller's: a boost does not change which lists are scanned. */
+int amdrec_ivf_scan_boosted(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                            const int64_t* list_off, const float* queries, int64_t nq, int64_t ld_queries,
+                            const int64_t* probes, const int64_t* pool_base, int nprobe, uint64_t* pool_keys,
+                            int64_t pool_ld, int64_t pos_offset, void* stream, const float* list_boosts /*[N], list order*/,
+                            const float* weight /*[nq]*/);
+int amdrec_ivf_scan_eligible_boosted(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                                     const int64_t* list_off, const float* queries, int64_t nq, int64_t ld_queries,
+                                     const int64_t* probes, const int64_t* pool_base, int nprobe, uint64_t* pool_keys,
+                                     int64_t pool_ld, int64_t pos_offset, void* stream,
+                                     const uint64_t* list_tags /*[N], list order*/, const uint64_t* require_all /*[nq]*/,
+                                     const uint64_t* require_any /*[nq]*/, const float* list_boosts /*[N], list order*/,
+                                     const float* weight /*[nq]*/);
+int amdrec_ivf_scan_grouped_boosted(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                                    const int64_t* list_off, int nlist, int64_t max_list_rows, const float* queries,
+                                    int64_t ld_queries, const int64_t* group_off, const int64_t* qtile_prefix,
+                                    int64_t qtile_bound, int qtile, const int64_t* pair_query, const int64_t* pair_probe,
+                                    const int64_t* pool_base, int nprobe, uint64_t* pool_keys, int64_t pool_ld,
+                                    int64_t pos_offset, const float* tau /*or NULL*/, int64_t ld_tau,
+                                    int64_t* pool_fill /*[nq] or NULL*/, void* stream,
+                                    const float* list_boosts /*[N], list order*/, const float* weight /*[nq]*/);
+int amdrec_ivf_scan_grouped_eligible_boosted(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                                             const int64_t* list_off, int nlist, int64_t max_list_rows, const float* queries,
+                                             int64_t ld_queries, const int64_t* group_off, const int64_t* qtile_prefix,
+                                             int64_t qtile_bound, int qtile, const int64_t* pair_query,
+                                             const int64_t* pair_probe, const int64_t* pool_base, int nprobe,
+                                             uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset,
+                                             const float* tau /*or NULL*/, int64_t ld_tau, int64_t* pool_fill /*[nq] or NULL*/,
+                                             void* stream, const uint64_t* list_tags /*[N], list order*/,
+                                             const uint64_t* require_all /*[nq]*/, const uint64_t* require_any /*[nq]*/,
+                                             const float* list_boosts /*[N], list order*/, const float* weight /*[nq]*/);
+int amdrec_ivf_filter_bounds_boosted(const float* queries, int64_t nq, int64_t ld_queries, int dim,
+                                     const uint16_t* queries_bf16, int64_t ld_queries_bf16,
+                                     const float* max_norm /*device float[2]*/, const float* tau, int64_t ld_tau,
+                                     float* tau_lo /*[nq]*/, void* stream, const float* weight /*[nq]*/, float boost_max);
+int amdrec_ivf_scan_grouped_mixed_boosted(const float* lists, int64_t ld, const uint16_t* lists_bf16, int64_t ld_bf16, int dim,
+                                          const int64_t* row_pos, const int64_t* list_off, int nlist, int64_t max_list_rows,
+                                          const float* queries, int64_t ld_queries, const uint16_t* queries_bf16,
+                                          int64_t ld_queries_bf16, const int64_t* group_off, const int64_t* qtile_prefix,
+                                          int64_t qtile_bound, int qtile, const int64_t* pair_query, uint64_t* pool_keys,
+                                          int64_t pool_ld, int64_t pos_offset, const float* tau, int64_t ld_tau,
+                                          const float* tau_lo /*[nq]*/, int64_t* pool_fill /*[nq]*/, void* stream,
+                                          const float* list_boosts /*[N], list order*/, const float* weight /*[nq]*/);
+int amdrec_ivf_scan_grouped_mixed_eligible_boosted(
+    const float* lists, int64_t ld, const uint16_t* lists_bf16, int64_t ld_bf16, int dim, const int64_t* row_pos,
+    const int64_t* list_off, int nlist, int64_t max_list_rows, const float* queries, int64_t ld_queries,
+    const uint16_t* queries_bf16, int64_t ld_queries_bf16, const int64_t* group_off, const int64_t* qtile_prefix,
+    int64_t qtile_bound, int qtile, const int64_t* pair_query, uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset,
+    const float* tau, int64_t ld_tau, const float* tau_lo /*[nq]*/, int64_t* pool_fill /*[nq]*/, void* stream,
+    const uint64_t* list_tags /*[N], list order*/, const uint64_t* require_all /*[nq]*/, const uint64_t* require_any /*[nq]*/,
+    const float* list_boosts /*[N], list order*/, const float* weight /*[nq]*/);
 /* Step 1 as a dense key table (replaces the `index.search` of faiss's IndexFlatIP quantizer inside IndexIVFFlat.search,
  * faiss_retrieval.py:50-55, :150-155): keys[q][c] = 64-bit (score of query q against centroid c, ~c) for every centroid -
  * the pool format of amdrec_ivf_select, which then yields the nprobe best centroids per query (score desc, lower centroid

@@ -56,6 +56,20 @@ _SIGNATURES = {
                                          _i32, _vp, _i64, _i64, _fp, _i64, _vp, _vp, _vp, _vp, _vp],
     "amdrec_ivf_scan_grouped_mixed_eligible": [_fp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i64, _fp, _i64, _vp, _i64, _vp, _vp,
                                                _i64, _i32, _vp, _vp, _i64, _i64, _fp, _i64, _fp, _vp, _vp, _vp, _vp, _vp],
+    # the *_boosted list scans: their twin's arguments + (list_boosts, weight); the boosted bound: + (weight, boost_max)
+    "amdrec_ivf_scan_boosted": [_fp, _i64, _i32, _vp, _vp, _fp, _i64, _i64, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _fp, _fp],
+    "amdrec_ivf_scan_eligible_boosted": [_fp, _i64, _i32, _vp, _vp, _fp, _i64, _i64, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp,
+                                         _vp, _fp, _fp],
+    "amdrec_ivf_scan_grouped_boosted": [_fp, _i64, _i32, _vp, _vp, _i32, _i64, _fp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp,
+                                        _i32, _vp, _i64, _i64, _fp, _i64, _vp, _vp, _fp, _fp],
+    "amdrec_ivf_scan_grouped_eligible_boosted": [_fp, _i64, _i32, _vp, _vp, _i32, _i64, _fp, _i64, _vp, _vp, _i64, _i32, _vp, _vp,
+                                                 _vp, _i32, _vp, _i64, _i64, _fp, _i64, _vp, _vp, _vp, _vp, _vp, _fp, _fp],
+    "amdrec_ivf_filter_bounds_boosted": [_fp, _i64, _i64, _i32, _vp, _i64, _fp, _fp, _i64, _fp, _vp, _fp, C.c_float],
+    "amdrec_ivf_scan_grouped_mixed_boosted": [_fp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i64, _fp, _i64, _vp, _i64, _vp, _vp,
+                                              _i64, _i32, _vp, _vp, _i64, _i64, _fp, _i64, _fp, _vp, _vp, _fp, _fp],
+    "amdrec_ivf_scan_grouped_mixed_eligible_boosted": [_fp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i64, _fp, _i64, _vp, _i64, _vp,
+                                                       _vp, _i64, _i32, _vp, _vp, _i64, _i64, _fp, _i64, _fp, _vp, _vp, _vp, _vp,
+                                                       _vp, _fp, _fp],
     "amdrec_ivfpq_scan_finite_eligible": [_vp, _i32, _vp, _vp, _vp, _i32, _i64, _fp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp,
                                           _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
     "amdrec_ivf_select": [_vp, _i64, _vp, _i64, _i32, _fp, _vp, _vp],

@@ -1,7 +1,8 @@
 """Per-ad score boosts in the Flat search ("let retrieval see the bid": expected revenue, quality score, freshness,
 cold-start exploration bonus - any per-ad prior that should lift an ad into the candidate set, not only reorder it).
 
-The rule (Flat index, both engines, every dimension; IVF / IVFPQ raise NotImplementedError - the follow-up).
+The rule (Flat index, both engines, every dimension; IVF-Flat with ``list_boosts``: below; IVFPQ, and IVF without the
+flag, raise NotImplementedError).
 
 Per ad.  One float32 ``boost``, finite, any sign.  A row never given one has 0.0; an index that never saw one keeps no
 tensor and writes the file it always wrote; -0.0 is stored as +0.0.
@@ -26,6 +27,33 @@ The key is evaluated inside the corpus pass - sample, filter, re-score and fix-u
 over k + E <= AMDREC_MAX_K rows, so a boost can lift a row from any similarity rank.  ``exclude=`` and ``max_per_group=``
 wrap the search and compose; eligibility masks together with a boost are the follow-up (NotImplementedError).
 
+Stage-1 score boosts in the inverted-list scans (IVF-Flat, opt-in per index: ``FAISSIndex(index_type="IVF",
+list_boosts=True)`` or ``enable_list_boosts()`` on a built or loaded index; the flag is a field of the saved header, a file
+without it loads as off; Flat ignores the flag; IVFPQ with the flag raises NotImplementedError - its scan holds L2 distances
+of codes and its refine stage would have to re-rank under the same key).
+
+Without the flag nothing changes: ``add(boosts=)``, ``set_boosts``, ``boost_weight=`` and ``stage1_boost=`` on an IVF or
+IVFPQ index raise what they always raised, before the library is touched.
+
+With the flag ``add(boosts=)`` / ``set_boosts`` / ``get_boosts`` work as on Flat (same validation, same ``_boost_max``),
+the index keeps ``list_boosts = boosts[row_pos]`` next to its lists (4 bytes per ad, made with the list layout and again
+when ``set_boosts`` swaps the tensor - never at search time; a captured graph pins the copy it was captured with), and the
+searches and the pipeline calls take the weight.  ``ShardedRecommender`` and ``MicroBatcher`` still do not.
+
+The result is the INDEX'S OWN result under the boosted key: per query the exact top-k under ``s`` of the rows of the lists
+the PLAIN search probes.  The probes are chosen by similarity alone - a boosted ad in a list that is not probed is not
+found; that is what IVF means.  ``ip`` is, bit for bit, the score the plain search on the same scan path writes for the
+row (the pair scan's fma chain, the grouped scans' MFMA value, the prefilter's fp32 re-score chain); ``t`` and ``s`` are
+the two rounded operations above; then the list scans' own rule applies to ``s``: a NaN ``s`` files as -inf (the row ranks
+last, it is not dropped); order: ``s`` descending, ties to the lower position; fewer than k probed rows leave the -inf / -1
+tail; ``w_q == 0`` gives the plain search's positions; ``boost_weight=None`` launches the kernels it always launched.  In
+the two-phase scan the first phase's threshold is the k-th BOOSTED score of the nearest probes - still a lower bound of the
+final k-th boosted score, so the scan stays exact -, and the bf16 prefilter's nomination bound is widened for the two
+roundings (``amdrec_ivf_filter_bounds_boosted``).
+
+Boost together with masks on an IVF index that has both ``list_tags`` and ``list_boosts``: the exact top-k under ``s`` of
+the ELIGIBLE probed rows.  Flat with a boost and masks keeps raising.
+
 This module holds the host helpers (no GPU needed for anything but the final copy).
 """
 from __future__ import annotations
@@ -39,7 +67,14 @@ FOLLOW_UP_MASKS = ("a stage-1 boost together with eligibility masks (require_all
                    "boosted kernels do not test the predicate yet - that is the follow-up (DESIGN.md, 'Stage-1 score boosts')")
 
 
+LIST_BOOSTS_IVFPQ = ("list_boosts on an IVFPQ index is not implemented: its scan holds squared L2 distances of codes, not inner "
+                     "products, and its refine stage would have to re-rank under the same key (DESIGN.md, 'Stage-1 score boosts "
+                     "in the inverted-list scans')")
+
+
 def follow_up_index(index_type: str) -> str:
+    """What an index that does not take boosts raises: IVFPQ, and IVF without ``list_boosts`` (the wording predates the
+    opt-in and is pinned by tests)."""
     return (f"stage-1 score boosts are implemented for the Flat index only; the {index_type} list scans do not add the term "
             "yet - that is the follow-up (DESIGN.md, 'Stage-1 score boosts')")
 

@@ -85,7 +85,8 @@ class _Handle:
 class FAISSIndex:
     def __init__(self, dimension: int, index_type: str = "IVF", nlist: int = 100, nprobe: int = 10,
                  use_gpu: bool = False, device=None, verbose: bool = False, prefilter: str = "bf16", pq_m: int = 8,
-                 refine: Optional[str] = None, refine_factor: int = 4, list_tags: bool = False):
+                 refine: Optional[str] = None, refine_factor: int = 4, list_tags: bool = False,
+                 list_boosts: bool = False):
         """``use_gpu`` is accepted for signature compatibility; the index always lives on the
         HIP device (``device`` or the current one) - there is no CPU engine.
         ``prefilter`` (Flat only): "bf16" keeps a bf16 copy of the corpus next to the fp32 one and searches with
@@ -98,7 +99,14 @@ class FAISSIndex:
         ``list_tags`` (IVF / IVFPQ; ignored for Flat, which takes masks anyway): the index also keeps its tag words in list
         order (8 bytes per ad next to the lists, rebuilt with the list layout) and its searches take ``require_all`` /
         ``require_any``: the predicate is tested inside the list scans.  Without it an IVF / IVFPQ index refuses masks;
-        ``enable_list_tags()`` opts in an index that is already built or loaded."""
+        ``enable_list_tags()`` opts in an index that is already built or loaded.
+        ``list_boosts`` (IVF; ignored for Flat, which takes boosts anyway; IVFPQ raises NotImplementedError): the index also
+        keeps its stage-1 score boosts in list order (4 bytes per ad next to the lists, rebuilt with the list layout) and takes
+        ``add(boosts=)`` / ``set_boosts`` / ``boost_weight=``: the key s = ip + w_q * boost[r] is evaluated inside the list
+        scans (amdrec.boost has the rule).  Without it an IVF index refuses boosts; ``enable_list_boosts()`` opts in an index
+        that is already built or loaded."""
+        if index_type == "IVFPQ" and list_boosts:
+            raise NotImplementedError(_boost.LIST_BOOSTS_IVFPQ)
         if prefilter not in ("bf16", "fp32"):
             raise ValueError("prefilter must be 'bf16' or 'fp32'")
         self.prefilter = prefilter
@@ -109,6 +117,7 @@ class FAISSIndex:
         self.pq_m = int(pq_m)
         self.refine, self.refine_factor = refine, refine_factor
         self.list_tags = bool(list_tags)
+        self.list_boosts = bool(list_boosts)
         self.use_gpu = use_gpu
         self.verbose = verbose
         self.device = torch.device(device if device is not None else "cuda")
@@ -213,6 +222,8 @@ class FAISSIndex:
         self._trained = True
         if getattr(self, "list_tags", False):
             self._ivf.tag_source = self._ensure_tags
+        if self._takes_list_boosts():
+            self._ivf.boost_source = self._boost_tensor
 
     def enable_list_tags(self):
         """Opt an IVF / IVFPQ index that is already built (or was loaded from a file saved without the flag) into eligibility
@@ -222,6 +233,29 @@ class FAISSIndex:
         if self._ivf is not None:
             self._ivf.tag_source = self._ensure_tags
             self._ivf.refresh_list_tags()
+
+    def _takes_list_boosts(self) -> bool:
+        """An IVF index that opted into boosts in its list scans (``list_boosts=True`` / ``enable_list_boosts()``)."""
+        return self.index_type == "IVF" and getattr(self, "list_boosts", False)
+
+    def _takes_boosts(self) -> bool:
+        return self.index_type == "Flat" or self._takes_list_boosts()
+
+    def _boost_tensor(self) -> Optional[torch.Tensor]:
+        """The boosts [capacity], or None for an index that never saw one (it keeps no list-order copy either)."""
+        return getattr(self, "_boosts", None)
+
+    def enable_list_boosts(self):
+        """Opt an IVF index that is already built (or was loaded from a file saved without the flag) into stage-1 score
+        boosts: from now on it keeps its boosts in list order (made here when the lists are laid out, else with the layout)
+        and takes ``add(boosts=)`` / ``set_boosts`` / ``boost_weight=``.  The flag is saved with the index.  Nothing to do for
+        Flat; IVFPQ raises NotImplementedError (its scan holds L2 distances of codes: out of scope)."""
+        if self.index_type == "IVFPQ":
+            raise NotImplementedError(_boost.LIST_BOOSTS_IVFPQ)
+        self.list_boosts = True
+        if self._ivf is not None and self.index_type == "IVF":
+            self._ivf.boost_source = self._boost_tensor
+            self._ivf.refresh_list_boosts()
 
     def _shadow_rows(self, lo, hi):
         """(Re)build rows [lo, hi) of the bf16 shadow from the fp32 rows and fold their norms into _maxnorm."""
@@ -319,14 +353,16 @@ class FAISSIndex:
     def set_boosts(self, boosts):
         """Replace the stage-1 score boost of every row: ``boosts`` [ntotal] numbers (amdrec.boost: finite, any sign).  Out
         of place - a new tensor is swapped in and the old one is never written -, so a search in flight or a captured
-        graph keeps the boosts it started with."""
-        if self.index_type != "Flat":
+        graph keeps the boosts it started with.  Flat, and IVF with ``list_boosts`` (the list-order copy follows the swap)."""
+        if not self._takes_boosts():
             raise NotImplementedError(_boost.follow_up_index(self.index_type))
         vals, bmax = _boost.device_boosts(boosts, self._n, self.device)
         new = torch.zeros((self._ids.shape[0],), dtype=torch.float32, device=self.device)
         new[:self._n].copy_(vals)
         self._boosts = new
         self._boost_max = bmax
+        if self._ivf is not None:                                    # list_boosts: the list-order copy follows the swap
+            self._ivf.refresh_list_boosts()
 
     def get_boosts(self) -> torch.Tensor:
         """The boosts, device float32 [ntotal] (a copy; 0.0 everywhere for an index that never saw a boost)."""
@@ -335,14 +371,15 @@ class FAISSIndex:
         return self._boosts[:self._n].clone()
 
     def _check_boost(self, boost_weight, masked: bool = False) -> bool:
-        """Was a stage-1 boost weight passed?  Refused before the library is touched: a weight on an IVF / IVFPQ index or
-        together with eligibility masks (NotImplementedError, the follow-up), a weight on an index without boosts, a
+        """Was a stage-1 boost weight passed?  Refused before the library is touched: a weight on an IVFPQ index, on an IVF
+        index without ``list_boosts``, or on a Flat index together with eligibility masks (NotImplementedError, the
+        follow-up; an IVF index with ``list_tags`` and ``list_boosts`` takes both), a weight on an index without boosts, a
         non-finite scalar weight."""
         if boost_weight is None:
             return False
-        if self.index_type != "Flat":
+        if not self._takes_boosts():
             raise NotImplementedError(_boost.follow_up_index(self.index_type))
-        if masked:
+        if masked and self.index_type == "Flat":
             raise NotImplementedError(_boost.FOLLOW_UP_MASKS)
         if getattr(self, "_boosts", None) is None:
             raise ValueError("boost_weight on an index without boosts: give them with add(..., boosts=) or set_boosts()")
@@ -415,9 +452,9 @@ class FAISSIndex:
         and an index that never sees a group keeps no group tensor at all.
         ``bids``: one float32 bid per added row (amdrec.auction; finite, >= 0); without it the rows get 1.0, and an index
         that never sees a bid keeps no bid tensor at all.
-        ``boosts`` (Flat): one float32 stage-1 score boost per added row (amdrec.boost; finite, any sign); without it the
+        ``boosts`` (Flat; IVF with ``list_boosts``): one float32 stage-1 score boost per added row (amdrec.boost; finite, any sign); without it the
         rows get 0.0, and an index that never sees a boost keeps no boost tensor at all."""
-        if boosts is not None and self.index_type != "Flat":
+        if boosts is not None and not self._takes_boosts():
             raise NotImplementedError(_boost.follow_up_index(self.index_type))
         if ad_ids is None and not self._default_ids_ok:
             raise ValueError("add() without ad_ids after remove_ids(): default ids are corpus positions, and the removal has "
@@ -620,11 +657,14 @@ class FAISSIndex:
         with or without refine -, so a row can come back short (unfilled tail) although the corpus holds more ads of other
         groups beyond its K1 best.  An index without group keys and a cap <= 0 raise ValueError before the library is
         touched.
-        ``boost_weight`` (Flat only; None: the plain search, not one launch more): a number or a device float32 [nq], the
-        queries' weights w_q on the per-ad boosts (``add(boosts=)`` / ``set_boosts``): the exact top-k under
+        ``boost_weight`` (Flat; IVF with ``list_boosts``; None: the plain search, not one launch more): a number or a device
+        float32 [nq], the queries' weights w_q on the per-ad boosts (``add(boosts=)`` / ``set_boosts``): the exact top-k under
         s = ip + w_q * boost[r], s returned as the score (amdrec.boost has the rule), evaluated inside the corpus pass.
-        ``exclude`` and ``max_per_group`` wrap the boosted search; together with masks, and on IVF / IVFPQ, it raises
-        NotImplementedError; on an index without boosts ValueError."""
+        IVF: the index's own result under that key - the exact top-k under s of the rows of the lists the PLAIN search
+        probes (the probes are chosen by similarity alone: a boosted ad in an unprobed list is not found); with masks on an
+        index that also has ``list_tags``, of the eligible ones.
+        ``exclude`` and ``max_per_group`` wrap the boosted search; on Flat together with masks, on IVF without
+        ``list_boosts`` and on IVFPQ it raises NotImplementedError; on an index without boosts ValueError."""
         masked = self._check_masks(require_all, require_any)
         boosted = self._check_boost(boost_weight, masked)
         cap = self._check_group_cap(max_per_group)
@@ -655,11 +695,12 @@ class FAISSIndex:
         boost = None
         if boosted:
             boost = (self._boosts, _boost.device_weights(boost_weight, nq, self.device), self._boost_max)
+        list_boost = boost[1:] if boosted and self.index_type == "IVF" else None
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         pos = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         off = pos_offset if return_positions else 0
         if self.index_type == "IVF":
-            self._ivf.search(self._xb, self._n, q, k, self.nprobe, scores, pos, pos_offset=off, elig=masks)
+            self._ivf.search(self._xb, self._n, q, k, self.nprobe, scores, pos, pos_offset=off, elig=masks, boost=list_boost)
         elif self.index_type == "IVFPQ":                              # scores = squared L2 distances, ascending
             self._pq.search(q, k, self.nprobe, scores, pos, pos_offset=off, elig=masks)
         elif self._mixed:
@@ -846,6 +887,8 @@ class FAISSIndex:
                 header["refine"], header["refine_factor"] = self.refine, int(self.refine_factor)
         if self.index_type != "Flat" and self.list_tags:             # (absent: no list-order tags, as every earlier file)
             header["list_tags"] = True
+        if self._takes_list_boosts():                                # (absent: no list-order boosts, as every earlier file)
+            header["list_boosts"] = True
         if self._host_ids is not None:
             header["host_ids"] = [_encode_id(x) for x in self._host_ids]     # typed: ids round-trip as what they were
         hj = json.dumps(header).encode()
@@ -878,6 +921,7 @@ class FAISSIndex:
         self.pq_m = int(header.get("pq_m", self.pq_m))
         self.refine, self.refine_factor = header.get("refine"), int(header.get("refine_factor", 4))
         self.list_tags = bool(header.get("list_tags", False))
+        self.list_boosts = bool(header.get("list_boosts", False))
         self._create_index()
         n = header["ntotal"]
         self._reserve(n)

@@ -17,6 +17,9 @@ Search = coarse probes -> [nearest eighth of the probes: grouped scan -> select 
 score >= tau] -> select (exact: tau is the k-th score over a subset of the candidates, hence a lower bound of the final one).
 Eligibility masks (opt-in, ``FAISSIndex(list_tags=True)``): ``InvertedLists`` also keeps the tag words in list order and every
 scan of a masked search is its ``*_eligible`` twin ("Eligibility masks in the inverted-list scans").
+Stage-1 score boosts (opt-in, ``FAISSIndex(list_boosts=True)``): ``InvertedLists`` also keeps the boosts in list order and
+every scan of a boosted search is its ``*_boosted`` twin - same probes, same phases, the key s = ip + w_q * boost[r] where
+the plain scan files ip ("Stage-1 score boosts in the inverted-list scans").
 Sharding: the centroids are SHARED by all ranks (``amdrec.sharded.share_ivf_centroids``); a rank
 files its own rows under them and holds its slice of every list, so the union of the ranks' scans is exactly the
 unsharded scan and the merged top-k is bit-identical to the unsharded IVF result.
@@ -158,6 +161,11 @@ class InvertedLists:
         self.tag_source = None
         self.list_tags: Optional[torch.Tensor] = None
         self._list_tags_of = None
+        # Stage-1 score boosts in the list scans (FAISSIndex(list_boosts=True)), kept the same way: boost_source() -> the
+        # owner's boosts in insertion order (float32 [>= n], None while it has none); list_boosts = boosts[spos], 4 bytes per row
+        self.boost_source = None
+        self.list_boosts: Optional[torch.Tensor] = None
+        self._list_boosts_of = None
 
     # -- build ----------------------------------------------------------------------------
     @classmethod
@@ -227,6 +235,8 @@ class InvertedLists:
         self._top_rows = np.cumsum(np.sort(counts.cpu().numpy())[::-1].astype(np.int64))
         self.list_tags = self._list_tags_of = None
         self.refresh_list_tags()
+        self.list_boosts = self._list_boosts_of = None
+        self.refresh_list_boosts()
         return self.lists
 
     def refresh_list_tags(self) -> Optional[torch.Tensor]:
@@ -241,6 +251,35 @@ class InvertedLists:
             self.list_tags = gather_rows(tags, self.lists.spos, self.lists.n)
             self._list_tags_of = tags
         return self.list_tags
+
+    def refresh_list_boosts(self) -> Optional[torch.Tensor]:
+        """list_boosts of the current layout from the owner's current boost tensor, under refresh_list_tags' rules
+        (amdrec_rows_gather, out of place; a copy stands while it was made from this very tensor for this very layout)."""
+        if self.boost_source is None or self.lists is None:
+            return None
+        boosts = self.boost_source()
+        if boosts is None:                                           # an index that never saw a boost keeps no copy
+            self.list_boosts = self._list_boosts_of = None
+            return None
+        if self.list_boosts is None or self._list_boosts_of is not boosts:
+            self.list_boosts = gather_rows(boosts, self.lists.spos, self.lists.n)
+            self._list_boosts_of = boosts
+        return self.list_boosts
+
+    def boost_tail(self, boost, nq: int):
+        """``boost`` = (weights device float32 [nq], boost_max) -> f(s): the two trailing pointers of a *_boosted scan for the
+        queries from s on (the weights are offset with the queries)."""
+        if self.boost_source is None:
+            raise ValueError("a stage-1 boost needs list-order boosts: FAISSIndex(list_boosts=True) or enable_list_boosts()")
+        lb = self.refresh_list_boosts()
+        if lb is None:
+            raise ValueError("boost_weight on an index without boosts: give them with add(..., boosts=) or set_boosts()")
+        w = _lib.require_gpu(boost[0], "boost_weight", torch.float32)
+        if w.shape != (nq,) or not w.is_contiguous():
+            raise ValueError(f"boost_weight must be a contiguous float32 [{nq}], got {tuple(w.shape)}")
+        if lb.shape != (self.lists.n,):
+            raise ValueError("list_boosts does not match the list layout")
+        return lambda s: (_lib.ptr(lb), _lib.ptr(w[s:]))
 
     def elig_tail(self, elig, nq: int):
         """``elig`` = (require_all, require_any) device int64 [nq] -> f(s): the three trailing pointers of an *_eligible scan
@@ -339,7 +378,7 @@ class InvertedLists:
     def resident_tensors(self) -> list:
         """Every device tensor kept between calls (a captured graph's kernels point at them)."""
         kept = [self.centroids, self.assign, self._nlist_count, self._sel_scratch, self._sel_tickets, self.list_tags,
-                *(self.lists or ())]
+                self.list_boosts, *(self.lists or ())]
         return [t for t in kept if isinstance(t, torch.Tensor)]
 
     # -- persistence ----------------------------------------------------------------------
@@ -393,10 +432,13 @@ class IVFState(InvertedLists):
 
     # -- search ---------------------------------------------------------------------------
     def search(self, xb: torch.Tensor, n: int, q: torch.Tensor, k: int, nprobe: int, out_scores: torch.Tensor,
-               out_pos: torch.Tensor, pos_offset: int = 0, elig=None):
+               out_pos: torch.Tensor, pos_offset: int = 0, elig=None, boost=None):
         """``elig``: (require_all, require_any) device int64 [nq] -> every scan of the search is its *_eligible twin over
         ``list_tags`` (same probes, same phases, same tiles; the first phase's tau is the k-th ELIGIBLE score); None: the
-        plain scans, nothing else."""
+        plain scans, nothing else.
+        ``boost``: (weights device float32 [nq], boost_max) -> every scan is its *_boosted twin over ``list_boosts`` (same
+        probes - chosen by similarity alone -, same phases; the first phase's tau is the k-th BOOSTED score and the prefilter's
+        bound is amdrec_ivf_filter_bounds_boosted's); with ``elig`` the *_eligible_boosted twins; None: nothing changes."""
         lib = _lib.load()
         nq = q.shape[0]
         if nq == 0:
@@ -406,8 +448,10 @@ class IVFState(InvertedLists):
             out_pos.fill_(-1)
             return
         xs, spos, off, _, max_len, _ = self._build_lists(xb, n)
-        tail = (lambda s: ()) if elig is None else self.elig_tail(elig, nq)      # noqa: E731
-        sfx = "" if elig is None else "_eligible"
+        etail = (lambda s: ()) if elig is None else self.elig_tail(elig, nq)      # noqa: E731
+        btail = (lambda s: ()) if boost is None else self.boost_tail(boost, nq)   # noqa: E731
+        tail = lambda s: (*etail(s), *btail(s))                                   # noqa: E731
+        sfx = ("" if elig is None else "_eligible") + ("" if boost is None else "_boosted")
         nprobe = search_nprobe(nprobe, self.nlist)
         base = torch.empty((nq, nprobe), dtype=torch.int64, device=self.device)
         n_pool = torch.empty((nq,), dtype=torch.int64, device=self.device)
@@ -434,8 +478,12 @@ class IVFState(InvertedLists):
             self.group(w, probes[s:, col0:], nprobe, m, ncol, base[s:], n_out, qt)
             if tau is not None and mixed:
                 # bf16 prefilter: tau_lo = tau - eps_q, nominate on the bf16 shadow, re-score the nominated rows in fp32
-                _lib.check(lib.amdrec_ivf_filter_bounds(_lib.ptr(q[s:]), m, q.stride(0), self.dim, _lib.ptr(q16[s:]), q16.stride(0),
-                                                        _lib.ptr(mx16), _lib.ptr(tau), tau.stride(0), _lib.ptr(tau_lo[s:]), st()))
+                bounds = (_lib.ptr(q[s:]), m, q.stride(0), self.dim, _lib.ptr(q16[s:]), q16.stride(0), _lib.ptr(mx16), _lib.ptr(tau),
+                          tau.stride(0), _lib.ptr(tau_lo[s:]), st())
+                if boost is None:
+                    _lib.check(lib.amdrec_ivf_filter_bounds(*bounds))
+                else:                              # widened for the two roundings of the boosted key (csrc/ivf.hip)
+                    _lib.check(lib.amdrec_ivf_filter_bounds_boosted(*bounds, btail(s)[1], _lib.C.c_float(float(boost[1]))))
                 _lib.check(getattr(lib, "amdrec_ivf_scan_grouped_mixed" + sfx)(
                     _lib.ptr(xs), xs.stride(0), _lib.ptr(xs16), xs16.stride(0), self.dim, _lib.ptr(spos), _lib.ptr(off),
                     self.nlist, max_len, _lib.ptr(q[s:]), q.stride(0), _lib.ptr(q16[s:]), q16.stride(0), _lib.ptr(goff),

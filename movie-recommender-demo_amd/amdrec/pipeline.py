@@ -419,10 +419,11 @@ class AdRecommenderInference:
         A non-number ``lam``: TypeError; ``lam`` outside [0, 1], a pool below ``top_k``, above 128 or with pool x dimension >
         32768, a pool without ``diversity``, and ``diversity`` with "ecpm": ValueError; on an IVFPQ index: NotImplementedError.
         ``stage1_boost`` (None: the plain search, the launches of ever): a number or a device float32 [B], the users' weights
-        on the index's per-ad boosts (FAISSIndex.add(boosts=) / set_boosts; amdrec.boost has the rule; Flat index): stage 1
-        is the exact top-stage1_k under similarity + w x boost[ad], so an ad with a large bid (boost = beta x log(bid)) reaches
-        the ranker - and the auction - from any similarity rank; candidate_scores are the boosted scores.  Stage 2 never
-        reads them and is unchanged.  On an index without boosts, a non-finite number: ValueError; with masks, on IVF / IVFPQ:
+        on the index's per-ad boosts (FAISSIndex.add(boosts=) / set_boosts; amdrec.boost has the rule; Flat index, or IVF with
+        ``list_boosts``): stage 1 is the exact top-stage1_k under similarity + w x boost[ad], so an ad with a large bid
+        (boost = beta x log(bid)) reaches the ranker - and the auction - from any similarity rank (on IVF: from any rank inside
+        the probed lists); candidate_scores are the boosted scores.  Stage 2 never reads them and is unchanged.  On an index
+        without boosts, a non-finite number: ValueError; on Flat with masks, on IVF without ``list_boosts``, on IVFPQ:
         NotImplementedError.
         ``check_indices``: an out-of-range user index or ad-table row raises IndexError; an unfilled slot does not."""
         if heads is not None:

@@ -2,6 +2,7 @@
 // and the two scoring rules every path that files a key must agree on.
 #pragma once
 #include "common.hpp"
+#include "topk_utils.hpp"
 
 namespace amdrec {
 
@@ -46,6 +47,59 @@ struct ListElig {
     __device__ __forceinline__ Mask mask(long long q) const { return q >= 0 ? Mask{all[q], any[q]} : Mask{0ull, 0ull}; }
     static __device__ __forceinline__ bool ok(Tag t, Mask m) { return (t & m.all) == m.all && (m.any == 0ull || (t & m.any) != 0ull); }
 };
+
+// ---- stage-1 score boosts in the list scans (the *_boosted scan entries; amdrec.h has the contract) --------------------------
+// The flat search's key s = ip + w_q * boost[r] (topk_utils.hpp: boost_term, boost_add - two rounded fp32 operations, never a
+// fused multiply-add) over LIST-ORDER boosts: list_boosts[r] is the boost of list-order row r (the index keeps list_boosts =
+// boosts[row_pos] next to its lists), read where the row's position and tag are read: one coalesced 4-byte load per row.  A
+// query's weight is read where its threshold / pool offset is read.  The type sits next to the eligibility type: ListNoBoost,
+// an empty one, in the scans without a boost - their kernels are the ones they were -, ListBoost in the *_boosted ones.
+struct ListNoBoost {
+    static constexpr bool on = false;
+    struct Row {};
+    struct Weight {};
+    __device__ __forceinline__ ListNoBoost at(long long) const { return {}; }
+    __device__ __forceinline__ Row row(long long) const { return {}; }
+    __device__ __forceinline__ Weight w(long long) const { return {}; }
+    struct Term {};
+    static __device__ __forceinline__ Term term(Weight, Row) { return {}; }
+    static __device__ __forceinline__ float add(float ip, Term) { return ip; }
+    static __device__ __forceinline__ float apply(float ip, Weight, Row) { return ip; }
+};
+struct ListBoost {
+    static constexpr bool on = true;
+    const float* boosts;     // [N], list order
+    const float* weight;     // [nq]
+    using Row = float;
+    using Weight = float;
+    __device__ __forceinline__ ListBoost at(long long r0) const { return {boosts + r0, weight}; }   // rows counted from r0
+    __device__ __forceinline__ Row row(long long r) const { return boosts[r]; }
+    // q < 0: no query in this accumulator register (nothing is loaded; the caller drops the register's elements)
+    __device__ __forceinline__ Weight w(long long q) const { return q >= 0 ? weight[q] : 0.f; }
+    using Term = float;      // t = w_q * boost[r], one rounded multiply
+    static __device__ __forceinline__ Term term(Weight w, Row b) { return boost_term(w, b); }
+    static __device__ __forceinline__ float add(float ip, Term t) { return boost_add(ip, t); }   // one rounded add
+    static __device__ __forceinline__ float apply(float ip, Weight w, Row b) { return add(ip, term(w, b)); }
+};
+
+// A scan kernel's trailing arguments -> its two types: the eligibility pointers first (ListNoElig: none), then the boost's
+// (ListNoBoost: none).  One overload per combination, picked by the argument types.
+template <class EL, class BO>
+struct ListPreds {
+    [[no_unique_address]] EL el;
+    [[no_unique_address]] BO bo;
+};
+__device__ __forceinline__ ListPreds<ListNoElig, ListNoBoost> list_preds() { return {}; }
+__device__ __forceinline__ ListPreds<ListElig, ListNoBoost> list_preds(const uint64_t* tags, const uint64_t* all, const uint64_t* any) {
+    return {{tags, all, any}, {}};
+}
+__device__ __forceinline__ ListPreds<ListNoElig, ListBoost> list_preds(const float* boosts, const float* weight) {
+    return {{}, {boosts, weight}};
+}
+__device__ __forceinline__ ListPreds<ListElig, ListBoost> list_preds(const uint64_t* tags, const uint64_t* all, const uint64_t* any,
+                                                                     const float* boosts, const float* weight) {
+    return {{tags, all, any}, {boosts, weight}};
+}
 
 // The list of query tile y of amdrec_ivf_group (blockIdx.y of a grouped scan): l with qt_prefix[l] <= y < qt_prefix[l+1];
 // the caller has returned for y >= qt_prefix[nlist].  The kernels keep the rest of the frame (list_off / group_off / p0 and

@@ -7,6 +7,7 @@
 //   ivf_select : per query, exact k largest keys of its pool: 64-bit LDS-histogram radix select
 //                (6 passes), compaction, bitonic sort.  Keys are unique (lists are disjoint), so the
 //                selection is exact and deterministic for every input - no sampling, no fix-up.
+#include <tuple>
 #include "gemm_core.hpp"
 #include "topk_utils.hpp"
 #include "invlists.hpp"
@@ -19,14 +20,19 @@ namespace amdrec {
 // (list_tags, all, any) for ListElig.  The scans below take them the same way.  This scan is a slot mode: an ineligible
 // (query, row) slot is stored as key 0, the select's EMPTY-slot value - stored, not skipped: the pool is not cleared
 // between searches.
-template <class EL = ListNoElig, class... EP>
+// BO (ListNoBoost or ListBoost, invlists.hpp): the stage-1 score boost, taken the same way - its pointers (list_boosts,
+// weight) follow the eligibility pointers; ListNoBoost adds none.  A boosted scan files s = ip + w_q * boost[r] (boost_add /
+// boost_term: two rounded operations) where the plain one files ip, under the same rules (rank_last, key 0 when ineligible).
+template <class EL = ListNoElig, class BO = ListNoBoost, class... EP>
 __global__ __launch_bounds__(256) void ivf_scan_kernel(const float* xs, long long ld, int d, const long long* spos,
                                                        const long long* list_off, const float* Q, long long ldq,
                                                        const long long* probes, const long long* base, int nprobe,
                                                        unsigned long long* keys, long long pool_ld,
-                                                       long long pos_offset, EP... elig) {
+                                                       long long pos_offset, EP... tail) {
     __shared__ __attribute__((aligned(16))) float qv[2048];
-    const EL el{elig...};
+    const ListPreds<EL, BO> preds = list_preds(tail...);
+    const EL el = preds.el;
+    [[maybe_unused]] const BO bo = preds.bo;
     const int q = blockIdx.y, p = blockIdx.x;
     const long long l = probes[(long long)q * nprobe + p];
     if (l < 0) return;
@@ -49,6 +55,7 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const float* xs, long lon
     const int d4 = d >> 2;
     constexpr int NW = 4, U = 8;
     const typename EL::Mask mq = el.mask(q);
+    [[maybe_unused]] const typename BO::Weight wq = bo.w(q);
     for (long long row0 = rb; row0 < r1; row0 += NW * U) {
         float part[U];
         const f32x4* xr[U];
@@ -78,7 +85,12 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const float* xs, long lon
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
             const long long r = row0 + w * U + u;
-            if constexpr (EL::on) {
+            if constexpr (BO::on) {
+                if (lane == 0 && r < r1) {
+                    const float s = BO::apply(a, wq, bo.row(r));
+                    dst[r - r0] = EL::ok(el.tag(r), mq) ? make_key(rank_last(s), (uint32_t)(spos[r] + pos_offset)) : 0ull;
+                }
+            } else if constexpr (EL::on) {
                 if (lane == 0 && r < r1)
                     dst[r - r0] = EL::ok(el.tag(r), mq) ? make_key(rank_last(a), (uint32_t)(spos[r] + pos_offset)) : 0ull;
             } else {
@@ -106,9 +118,9 @@ struct GatherRows {
     }
 };
 
-template <class EL>
+template <class EL, class BO = ListNoBoost>
 struct EpiIvfKeysT {
-    static constexpr const char* name = EL::on ? "ivf_scan_elig" : "ivf_scan";
+    static constexpr const char* name = BO::on ? (EL::on ? "ivf_scan_elig_boost" : "ivf_scan_boost") : (EL::on ? "ivf_scan_elig" : "ivf_scan");
     static constexpr double out_bytes_per_elem = 2.0;
     static constexpr size_t lds_bytes(int) { return 0; }
     const long long* spos;      // positions of this list's rows
@@ -128,6 +140,9 @@ struct EpiIvfKeysT {
     // eligibility (rows counted from the list's first, as spos): slot mode stores key 0, the select's empty-slot value, for
     // an ineligible (query, row) element; filter mode tests the predicate with the threshold and does not append the row
     [[no_unique_address]] EL el;
+    // boost (rows counted from the list's first, as spos): both modes see s = BO::apply(ip, w_q, boost[row]) where the plain
+    // scan sees ip - the slot's key, and the value compared with tau (the k-th BOOSTED score of the first phase)
+    [[no_unique_address]] BO bo;
     template <class A>
     __device__ void operator()(A& acc, float*) const {
         constexpr int TP = A::TP, TQ = A::TQ;
@@ -138,11 +153,13 @@ struct EpiIvfKeysT {
         // longer than the tile's MFMAs on short lists.
         long long rowq[TQ], posq[TQ];
         typename EL::Tag tagq[TQ];
+        [[maybe_unused]] typename BO::Row bq[TQ];
 #pragma unroll
         for (int j = 0; j < TQ; ++j) {
             rowq[j] = acc.q(j, lane);                             // row inside the list
             posq[j] = rowq[j] < list_rows ? spos[rowq[j]] + pos_offset : -1;
             tagq[j] = rowq[j] < list_rows ? el.tag(rowq[j]) : typename EL::Tag{};
+            if constexpr (BO::on) bq[j] = rowq[j] < list_rows ? bo.row(rowq[j]) : typename BO::Row{};
         }
 #pragma unroll
         for (int i = 0; i < TP; ++i) {
@@ -167,6 +184,12 @@ struct EpiIvfKeysT {
                     for (int j = 0; j < TQ; ++j) okb |= (uint64_t)EL::ok(tagq[j], mv[r]) << (r * TQ + j);
             }
             (void)okb;
+            // the queries' weights, with the tau / base loads
+            [[maybe_unused]] typename BO::Weight wv[16];
+            if constexpr (BO::on) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) wv[r] = bo.w(qv[r]);
+            }
             if (tau != nullptr) {
                 float tv[16];
 #pragma unroll
@@ -175,7 +198,7 @@ struct EpiIvfKeysT {
                 for (int r = 0; r < 16; ++r) {
 #pragma unroll
                     for (int j = 0; j < TQ; ++j) {
-                        const float sc = rank_last(acc.v[i][j][r]);
+                        const float sc = rank_last(BO::apply(acc.v[i][j][r], wv[r], bq[j]));
                         if (sc >= tv[r] && posq[j] >= 0 && (!EL::on || ((okb >> (r * TQ + j)) & 1ull)))
                             (keys + qv[r] * pool_ld)[atomicAdd(&fill[qv[r]], 1ull)] = make_key(sc, (uint32_t)posq[j]);
                     }
@@ -198,9 +221,10 @@ struct EpiIvfKeysT {
                 for (int j = 0; j < TQ; ++j) {
                     if (posq[j] < 0) continue;
                     if constexpr (EL::on)
-                        dst[rowq[j]] = ((okb >> (r * TQ + j)) & 1ull) ? make_key(rank_last(acc.v[i][j][r]), (uint32_t)posq[j]) : 0ull;
+                        dst[rowq[j]] = ((okb >> (r * TQ + j)) & 1ull)
+                                           ? make_key(rank_last(BO::apply(acc.v[i][j][r], wv[r], bq[j])), (uint32_t)posq[j]) : 0ull;
                     else
-                        dst[rowq[j]] = make_key(rank_last(acc.v[i][j][r]), (uint32_t)posq[j]);
+                        dst[rowq[j]] = make_key(rank_last(BO::apply(acc.v[i][j][r], wv[r], bq[j])), (uint32_t)posq[j]);
                 }
             }
         }
@@ -218,9 +242,10 @@ struct EpiIvfKeysT {
 // appended if that exact score passes tau.  The pool holds exact fp32 keys as before; nothing downstream changes.
 // Hits of a whole tile are collected in one list in LDS (the staging area, free after the K loop), then the workgroup's
 // waves share them; a hit that finds the list full is re-scored by its own lane, in the same summation order (rescore1).
-template <class EL>
+template <class EL, class BO = ListNoBoost>
 struct EpiIvfPrefilterT {
-    static constexpr const char* name = EL::on ? "ivf_scan_bf16_elig" : "ivf_scan_bf16";
+    static constexpr const char* name = BO::on ? (EL::on ? "ivf_scan_bf16_elig_boost" : "ivf_scan_bf16_boost")
+                                               : (EL::on ? "ivf_scan_bf16_elig" : "ivf_scan_bf16");
     static constexpr double out_bytes_per_elem = 0.0;
     static constexpr size_t lds_bytes(int) { return 0; }        // reuses the staging tiles (checked against their size below)
     const long long* spos;      // positions of this list's rows
@@ -242,6 +267,11 @@ struct EpiIvfPrefilterT {
     // an ineligible row costs neither a list slot nor the fp32 row read of the re-score; rescore16 / rescore1 / keep only
     // ever see eligible rows
     [[no_unique_address]] EL el;
+    // boost (rows counted from the list's first, as spos): nomination compares boost_add(bf16 score, t) with tau_lo - the
+    // bound widened for the two roundings, ivf_filter_bounds_kernel -; keep files boost_add(fp32 re-score, t) with the
+    // same t (an overflow hit passes its own, a listed hit reads the row's boost and the query's weight again), so
+    // rescore16 and rescore1 hits file the same value
+    [[no_unique_address]] BO bo;
     // fp32 score of (list row, query) by the 16 lanes of a quarter wave (sub = lane & 15); every lane returns the sum
     __device__ __forceinline__ float rescore16(long long row, long long q, int sub) const {
         const f32x4* xr = reinterpret_cast<const f32x4*>(xs + row * ld);
@@ -283,7 +313,9 @@ struct EpiIvfPrefilterT {
     }
     // the threshold is the k-th score of the first phase, computed by the fp32 MFMA; the re-score sums in another order
     // (1e-7-level differences): a slack towards KEEPING never costs exactness, the select decides
-    __device__ __forceinline__ void keep(float sc, long long row, long long q) const {
+    // (bt: the pair's boost term, the one its nomination added to the bf16 score)
+    __device__ __forceinline__ void keep(float sc, long long row, long long q, typename BO::Term bt = {}) const {
+        if constexpr (BO::on) sc = BO::add(sc, bt);
         sc = rank_last(sc);
         const float t = tau[q * ld_tau];
         if (sc >= t - 1e-6f * fmaxf(1.f, fabsf(t)) || t == -INFINITY)
@@ -304,10 +336,12 @@ struct EpiIvfPrefilterT {
         unsigned long long* hits = reinterpret_cast<unsigned long long*>(smem + 4);     // (query << 32) | row in the list
         long long rowq[TQ];
         typename EL::Tag tagq[TQ];
+        [[maybe_unused]] typename BO::Row bq[TQ];
 #pragma unroll
         for (int j = 0; j < TQ; ++j) {
             rowq[j] = acc.q(j, lane);
             tagq[j] = rowq[j] < list_rows ? el.tag(rowq[j]) : typename EL::Tag{};
+            if constexpr (BO::on) bq[j] = rowq[j] < list_rows ? bo.row(rowq[j]) : typename BO::Row{};
         }
         // member -> query -> prefilter threshold for all of this lane's accumulator rows at once: two dependent round
         // trips per tile (fetched round by round they were eight)
@@ -324,6 +358,13 @@ struct EpiIvfPrefilterT {
         for (int i = 0; i < TP; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) tv[i][r] = qv[i][r] >= 0 ? tau_lo[qv[i][r]] : __builtin_nanf("");
+        [[maybe_unused]] typename BO::Weight wv[TP][16];                   // the queries' weights, with the tau_lo loads
+        if constexpr (BO::on) {
+#pragma unroll
+            for (int i = 0; i < TP; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) wv[i][r] = bo.w(qv[i][r]);
+        }
         // eligibility: the two mask words of the tile's BP queries go to the END of the staging area (one query per thread:
         // pair_q -> all / any, in flight with the pair_q -> tau_lo loads above; the nomination list gives up BP * 16 bytes)
         // and a hit reads its query's pair from there.  Held in registers - sixteen pairs per lane, or folded into a bit
@@ -348,7 +389,8 @@ struct EpiIvfPrefilterT {
             for (int r = 0; r < 16; ++r)
 #pragma unroll
                 for (int j = 0; j < TQ; ++j) {
-                    const float a = acc.v[i][j][r];
+                    [[maybe_unused]] const typename BO::Term t = BO::term(wv[i][r], bq[j]);
+                    const float a = BO::add(acc.v[i][j][r], t);
                     // NaN approx (NaN rows / queries): re-score, the exact path decides; NaN threshold: member absent
                     if ((a >= tv[i][r] || (!(a == a) && tv[i][r] == tv[i][r])) && rowq[j] < list_rows) {
                         if constexpr (EL::on) {
@@ -359,7 +401,8 @@ struct EpiIvfPrefilterT {
                         if (slot < CAP) {
                             hits[slot] = ((unsigned long long)(uint32_t)qv[i][r] << 32) | (unsigned long long)rowq[j];
                         } else {
-                            keep(rescore1(rowq[j], qv[i][r]), rowq[j], qv[i][r]);
+                            if constexpr (BO::on) keep(rescore1(rowq[j], qv[i][r]), rowq[j], qv[i][r], t);
+                            else keep(rescore1(rowq[j], qv[i][r]), rowq[j], qv[i][r]);
                         }
                     }
                 }
@@ -373,13 +416,21 @@ struct EpiIvfPrefilterT {
             const long long q0 = (long long)(e0 >> 32), r0 = (long long)(e0 & 0xffffffffull);
             const long long q1 = (long long)(e1 >> 32), r1 = (long long)(e1 & 0xffffffffull);
             const float s0 = rescore16(r0, q0, sub), s1 = rescore16(r1, q1, sub);
-            if (sub == 0) { keep(s0, r0, q0); keep(s1, r1, q1); }
+            if constexpr (BO::on) {
+                if (sub == 0) { keep(s0, r0, q0, BO::term(bo.w(q0), bo.row(r0))); keep(s1, r1, q1, BO::term(bo.w(q1), bo.row(r1))); }
+            } else {
+                if (sub == 0) { keep(s0, r0, q0); keep(s1, r1, q1); }
+            }
         }
         if (h < n) {
             const unsigned long long e0 = hits[h];
             const long long q0 = (long long)(e0 >> 32), r0 = (long long)(e0 & 0xffffffffull);
             const float s0 = rescore16(r0, q0, sub);
-            if (sub == 0) keep(s0, r0, q0);
+            if constexpr (BO::on) {
+                if (sub == 0) keep(s0, r0, q0, BO::term(bo.w(q0), bo.row(r0)));
+            } else {
+                if (sub == 0) keep(s0, r0, q0);
+            }
         }
         __syncthreads();                                                  // the staging tiles are the next row tile's again
     }
@@ -387,9 +438,23 @@ struct EpiIvfPrefilterT {
 
 // tau_lo[q] = tau[q] - eps_q for the prefilter above: one wave per query (||q||, ||bf16(q) - q|| from the two copies of the
 // query, M / D from the list shadow's max_norm).  tau = -inf (fewer than k rows in the first phase) stays -inf.
+//
+// BOOSTED scans (BP = weight [nq], boost_max): nomination compares fl(a + t) with tau_lo, where a is the bf16 score, t =
+// fl(w_q * boost[r]) the term both sides share, and a row must be nominated whenever its exact key s = fl(ip + t) >= tau.
+// With u = 2^-24, fl(x) >= x - u |x| and |ip - a| <= eps_q:
+//     fl(a + t) >= (a + t) - u |a + t| >= (ip + t) - eps_q - u |a + t| >= s - u |ip + t| - eps_q - u |a + t|
+//               >= tau - eps_q - u (|ip + t| + |a + t|),
+// and |ip + t| <= P, |a + t| <= P + eps_q for P = |w_q| boost_max + ||q|| (M + D)  (|t| <= |w_q| boost_max (1 + u), folded
+// into the factor below).  So tau_lo = tau - eps_q - 2u (P + eps_q) nominates every such row; the kernel takes 5u for 2u: the
+// two subtractions that form tau_lo round too (each by at most u times a value no larger than P + eps_q), and a bound that
+// is too low costs re-scores, never a row.  A non-finite P (a NaN / inf weight) re-scores everything, like a non-finite eps.
+__device__ __forceinline__ float boost_bound_slack(long long q, float qn, float eps, float md, const float* weight, float boost_max) {
+    return 3.0e-7f * (fabsf(weight[q]) * boost_max + qn * md + eps);
+}
+template <class... BP>
 __global__ __launch_bounds__(256) void ivf_filter_bounds_kernel(const float* Q, long long ldq, const uint16_t* Q16, long long ldq16,
                                                                 int d, long long nq, const float* max_norm, const float* tau,
-                                                                long long ld_tau, float* tau_lo) {
+                                                                long long ld_tau, float* tau_lo, BP... bp) {
     const int lane = threadIdx.x & 63;
     const long long q = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= nq) return;
@@ -405,18 +470,25 @@ __global__ __launch_bounds__(256) void ivf_filter_bounds_kernel(const float* Q, 
     if (lane == 0) {
         const float eps = eps_bound(sqrtf(qn), sqrtf(dqn) * 1.0001f, max_norm[0], max_norm[1], d);
         const float t = tau[q * ld_tau];
-        tau_lo[q] = (eps < INFINITY) ? t - eps : -INFINITY;               // NaN / inf norms: everything is re-scored
+        if constexpr (sizeof...(BP) == 0) {
+            tau_lo[q] = (eps < INFINITY) ? t - eps : -INFINITY;           // NaN / inf norms: everything is re-scored
+        } else {
+            const float slack = boost_bound_slack(q, sqrtf(qn), eps, max_norm[0] + max_norm[1], bp...);
+            tau_lo[q] = (eps < INFINITY && slack < INFINITY) ? t - eps - slack : -INFINITY;
+        }
     }
 }
 
-template <class S, class EL = ListNoElig, class... EP>
+template <class S, class EL = ListNoElig, class BO = ListNoBoost, class... EP>
 __global__ __launch_bounds__(S::NT, 2) void ivf_group_scan_mixed_kernel(
     const float* xs, long long ld, const uint16_t* xs16, long long ld16, int d, int ksteps, const long long* spos,
     const long long* list_off, const float* Q, long long ldq, const uint16_t* Q16, long long ldq16, const long long* goff,
     const long long* qt_prefix, int nlist, const long long* pair_q, unsigned long long* keys, long long pool_ld,
-    long long pos_offset, const float* tau, long long ld_tau, const float* tau_lo, unsigned long long* fill, EP... elig) {
+    long long pos_offset, const float* tau, long long ld_tau, const float* tau_lo, unsigned long long* fill, EP... tail) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const EL el{elig...};
+    const ListPreds<EL, BO> preds = list_preds(tail...);
+    const EL el = preds.el;
+    const BO bo = preds.bo;
     const long long y = blockIdx.y;
     if (y >= qt_prefix[nlist]) return;
     const int l = tile_list(y, qt_prefix, nlist);
@@ -426,8 +498,8 @@ __global__ __launch_bounds__(S::NT, 2) void ivf_group_scan_mixed_kernel(
     // the bf16 matrices as float matrices of d / 2 columns (gemm_core.hpp, Shape::BF16)
     GatherRows lp{reinterpret_cast<const float*>(Q16), pair_q + g0, g, (int)(ldq16 / 2), d / 2};
     DenseRows lq{reinterpret_cast<const float*>(xs16 + r0 * ld16), len, (int)(ld16 / 2), d / 2, 30, 1ll << 30};
-    EpiIvfPrefilterT<EL> epi{spos + r0, len, pair_q + g0, g, keys, pool_ld, pos_offset, tau, ld_tau, tau_lo, fill,
-                             xs + r0 * ld, ld, Q, ldq, d, el.at(r0)};
+    EpiIvfPrefilterT<EL, BO> epi{spos + r0, len, pair_q + g0, g, keys, pool_ld, pos_offset, tau, ld_tau, tau_lo, fill,
+                                 xs + r0 * ld, ld, Q, ldq, d, el.at(r0), bo.at(r0)};
     const long long p0 = (y - qt_prefix[l]) * S::BP;
     for (long long row0 = (long long)blockIdx.x * S::BQ; row0 < len; row0 += (long long)gridDim.x * S::BQ)
         gemm_block<S>(lp, lq, epi, ksteps, p0, row0, smem);
@@ -486,14 +558,16 @@ template <bool BF16> using ShapeIvfS = Shape<2, 2, 1, 2, false, BF16>;    // 64 
 template <bool BF16> using ShapeIvf32S = Shape<1, 4, 1, 1, false, BF16>;  // 32 queries x 128 list rows
 // (double-buffered staging - one barrier per K-step - measured at the per-rank shape: 0.817 against 0.799 ms, not kept)
 
-template <class S, class EL = ListNoElig, class... EP>
+template <class S, class EL = ListNoElig, class BO = ListNoBoost, class... EP>
 __global__ __launch_bounds__(S::NT, 2) void ivf_group_scan_kernel(
     const float* xs, long long ld, int d, int ksteps, const long long* spos, const long long* list_off,
     const float* Q, long long ldq, const long long* goff, const long long* qt_prefix, int nlist,
     const long long* pair_q, const long long* pair_p, const long long* base, int nprobe, unsigned long long* keys,
-    long long pool_ld, long long pos_offset, const float* tau, long long ld_tau, unsigned long long* fill, EP... elig) {
+    long long pool_ld, long long pos_offset, const float* tau, long long ld_tau, unsigned long long* fill, EP... tail) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const EL el{elig...};
+    const ListPreds<EL, BO> preds = list_preds(tail...);
+    const EL el = preds.el;
+    const BO bo = preds.bo;
     const long long y = blockIdx.y;
     if (y >= qt_prefix[nlist]) return;
     const int l = tile_list(y, qt_prefix, nlist);
@@ -502,8 +576,8 @@ __global__ __launch_bounds__(S::NT, 2) void ivf_group_scan_kernel(
     const long long g0 = goff[l], g = goff[l + 1] - g0;
     GatherRows lp{Q, pair_q + g0, g, (int)ldq, d};
     DenseRows lq{xs + r0 * ld, len, (int)ld, d, 30, 1ll << 30};
-    EpiIvfKeysT<EL> epi{spos + r0, len, pair_q + g0, pair_p + g0, g, base, nprobe, keys, pool_ld, pos_offset, tau, ld_tau, fill,
-                        el.at(r0)};
+    EpiIvfKeysT<EL, BO> epi{spos + r0, len, pair_q + g0, pair_p + g0, g, base, nprobe, keys, pool_ld, pos_offset, tau, ld_tau, fill,
+                            el.at(r0), bo.at(r0)};
     const long long p0 = (y - qt_prefix[l]) * S::BP;
     // gridDim.x workgroups share the list's row tiles (round 4: the host no longer launches one workgroup per row tile of
     // the LONGEST list - on short lists three of four workgroups found no rows after paying for the tile search)
@@ -879,23 +953,49 @@ static int elig_check(ListElig el) {
     REQUIRE(((uintptr_t)el.any % 8) == 0, "require_any must be 8-byte aligned");
     return AMDREC_OK;
 }
-// the kernel instantiation of a predicate: K<ListNoElig>, or K<ListElig, its three pointers>
-#define AMDREC_LIST_ELIG_ARGS ListElig, const uint64_t*, const uint64_t*, const uint64_t*
-// launches `kern` with the eligibility pointers after the arguments every instantiation takes (ListNoElig: none)
-template <class Kern, class... Args>
-static void launch_with(ListNoElig, Kern kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
-    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+// ---- the boost pointers of the *_boosted scans ----
+// Both required and 4-byte aligned, checked with the other arguments before the first HIP call.  A scan entry and its
+// *_boosted / *_eligible_boosted twins are the same host template: ListNoBoost checks and passes nothing.
+static int boost_check(ListNoBoost) { return AMDREC_OK; }
+static int boost_check(ListBoost bo) {
+    REQUIRE(bo.boosts != nullptr, "list_boosts is null");
+    REQUIRE(bo.weight != nullptr, "weight is null");
+    REQUIRE(((uintptr_t)bo.boosts % 4) == 0, "list_boosts must be 4-byte aligned");
+    REQUIRE(((uintptr_t)bo.weight % 4) == 0, "weight must be 4-byte aligned");
+    return AMDREC_OK;
 }
-template <class Kern, class... Args>
-static void launch_with(ListElig el, Kern kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
-    hipLaunchKernelGGL(kern, grid, block, lds, st, args..., el.tags, el.all, el.any);
+static int boost_max_check(float boost_max) {
+    REQUIRE(boost_max >= 0.f && boost_max < INFINITY, "boost_max must be a finite bound of max |boost|");
+    return AMDREC_OK;
 }
+// the kernel instantiation of (EL, BO) inside a host template over them: K<prefix..., EL, BO, EL's three pointers (ListElig),
+// BO's two (ListBoost)>; the plain one is K<prefix...>.  The prefix ends in its comma (or is empty).
+#define AMDREC_LIST_ELIG_PTRS const uint64_t*, const uint64_t*, const uint64_t*
+#define AMDREC_LIST_BOOST_PTRS const float*, const float*
+#define AMDREC_LIST_KERNEL(K, ...) [] { \
+    if constexpr (EL::on && BO::on) return K<__VA_ARGS__ ListElig, ListBoost, AMDREC_LIST_ELIG_PTRS, AMDREC_LIST_BOOST_PTRS>; \
+    else if constexpr (EL::on) return K<__VA_ARGS__ ListElig, ListNoBoost, AMDREC_LIST_ELIG_PTRS>; \
+    else if constexpr (BO::on) return K<__VA_ARGS__ ListNoElig, ListBoost, AMDREC_LIST_BOOST_PTRS>; \
+    else return K<__VA_ARGS__ ListNoElig, ListNoBoost>; }()
+// launches `kern` with the eligibility pointers, then the boost pointers, after the arguments every instantiation takes
+static std::tuple<> list_tail(ListNoElig) { return {}; }
+static std::tuple<const uint64_t*, const uint64_t*, const uint64_t*> list_tail(ListElig el) { return {el.tags, el.all, el.any}; }
+static std::tuple<> list_tail(ListNoBoost) { return {}; }
+static std::tuple<const float*, const float*> list_tail(ListBoost bo) { return {bo.boosts, bo.weight}; }
+template <class EL, class BO, class Kern, class... Args>
+static void launch_with(EL el, BO bo, Kern kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    std::apply([&](auto... tail) { hipLaunchKernelGGL(kern, grid, block, lds, st, args..., tail...); },
+               std::tuple_cat(list_tail(el), list_tail(bo)));
+}
+// the ProfScope tag of a scan: base, base_elig, base_boost or base_elig_boost
+#define AMDREC_LIST_TAG(base) \
+    (BO::on ? (EL::on ? base "_elig_boost" : base "_boost") : (EL::on ? base "_elig" : base))
 
-template <class EL>
+template <class EL, class BO = ListNoBoost>
 static int ivf_scan_impl(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
                          const int64_t* list_off, const float* queries, int64_t nq, int64_t ld_queries,
                          const int64_t* probes, const int64_t* pool_base, int nprobe, uint64_t* pool_keys,
-                         int64_t pool_ld, int64_t pos_offset, void* stream, EL el) {
+                         int64_t pool_ld, int64_t pos_offset, void* stream, EL el, BO bo = {}) {
     REQUIRE(dim >= 4 && dim % 4 == 0 && dim <= 2048, "dim=%d must be a multiple of 4 in [4,2048]", dim);
     REQUIRE(nprobe >= 1 && nprobe <= 65535, "nprobe out of range");
     if (nq <= 0) return AMDREC_OK;
@@ -903,14 +1003,12 @@ static int ivf_scan_impl(const float* lists, int64_t ld, int dim, const int64_t*
     REQUIRE(lists && row_pos && list_off && queries && probes && pool_base && pool_keys, "null pointer");
     REQUIRE(ld % 4 == 0 && ld >= dim && ld_queries >= dim, "bad leading dimension");
     if (int rc = elig_check(el)) return rc;
+    if (int rc = boost_check(bo)) return rc;
     long long splits = 2048 / ((long long)nprobe * nq);            // ~2048 workgroups in all
     splits = splits < 1 ? 1 : (splits > 64 ? 64 : splits);
-    ProfScope prof(EL::on ? "ivf_scan_pairs_elig" : "ivf_scan_pairs", 0.0, 0.0, reinterpret_cast<hipStream_t>(stream));
-    auto kern = [] {
-        if constexpr (EL::on) return ivf_scan_kernel<AMDREC_LIST_ELIG_ARGS>;
-        else return ivf_scan_kernel<>;
-    }();
-    launch_with(el, kern, dim3(nprobe, (unsigned)nq, (unsigned)splits), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    ProfScope prof(AMDREC_LIST_TAG("ivf_scan_pairs"), 0.0, 0.0, reinterpret_cast<hipStream_t>(stream));
+    auto kern = AMDREC_LIST_KERNEL(ivf_scan_kernel, );
+    launch_with(el, bo, kern, dim3(nprobe, (unsigned)nq, (unsigned)splits), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                 lists, (long long)ld, dim, (const long long*)row_pos, (const long long*)list_off, queries,
                 (long long)ld_queries, (const long long*)probes, (const long long*)pool_base, nprobe,
                 (unsigned long long*)pool_keys, (long long)pool_ld, (long long)pos_offset);
@@ -935,6 +1033,26 @@ extern "C" int amdrec_ivf_scan_eligible(const float* lists, int64_t ld, int dim,
                          pool_ld, pos_offset, stream, ListElig{list_tags, require_all, require_any});
 }
 
+extern "C" int amdrec_ivf_scan_boosted(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                                       const int64_t* list_off, const float* queries, int64_t nq, int64_t ld_queries,
+                                       const int64_t* probes, const int64_t* pool_base, int nprobe, uint64_t* pool_keys,
+                                       int64_t pool_ld, int64_t pos_offset, void* stream, const float* list_boosts,
+                                       const float* weight) {
+    return ivf_scan_impl(lists, ld, dim, row_pos, list_off, queries, nq, ld_queries, probes, pool_base, nprobe, pool_keys,
+                         pool_ld, pos_offset, stream, ListNoElig{}, ListBoost{list_boosts, weight});
+}
+
+extern "C" int amdrec_ivf_scan_eligible_boosted(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                                                const int64_t* list_off, const float* queries, int64_t nq, int64_t ld_queries,
+                                                const int64_t* probes, const int64_t* pool_base, int nprobe,
+                                                uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset, void* stream,
+                                                const uint64_t* list_tags, const uint64_t* require_all,
+                                                const uint64_t* require_any, const float* list_boosts, const float* weight) {
+    return ivf_scan_impl(lists, ld, dim, row_pos, list_off, queries, nq, ld_queries, probes, pool_base, nprobe, pool_keys,
+                         pool_ld, pos_offset, stream, ListElig{list_tags, require_all, require_any},
+                         ListBoost{list_boosts, weight});
+}
+
 // Workgroup columns per (list, query tile): an eighth of the LONGEST list's row tiles, each looping over its share of the
 // list's tiles.  Round 3 launched one workgroup per row tile of the longest list for every (list, query tile): list lengths
 // spread 0 .. 4x the mean, so three of four workgroups found no rows - after paying for the tile search - and at the
@@ -950,8 +1068,8 @@ constexpr long long SHORT_LIST_ROWS = 1536;
 
 // Both grouped kernels are launched here, so the two phases of one search cannot disagree about geometry; `args`: the
 // kernel's arguments
-template <class S, auto Kernel, class EL, class... Args>
-static hipError_t launch_grouped(EL el, const char* tag, long long max_list_rows, long long qtile_bound, hipStream_t st, Args... args) {
+template <class S, auto Kernel, class EL, class BO, class... Args>
+static hipError_t launch_grouped(EL el, BO bo, const char* tag, long long max_list_rows, long long qtile_bound, hipStream_t st, Args... args) {
     static PerDeviceOnce attr_done;
     if (attr_done.pending()) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -960,20 +1078,25 @@ static hipError_t launch_grouped(EL el, const char* tag, long long max_list_rows
         attr_done.mark();
     }
     ProfScope prof(tag, 0.0, 0.0, st);
-    launch_with(el, Kernel, dim3((unsigned)scan_columns(max_list_rows, S::BQ), (unsigned)qtile_bound), dim3(S::NT),
+    launch_with(el, bo, Kernel, dim3((unsigned)scan_columns(max_list_rows, S::BQ), (unsigned)qtile_bound), dim3(S::NT),
                 S::LDS_BYTES, st, args...);
     return hipGetLastError();
 }
 
 // f(shape, ProfScope tag) for the tile of (qtile, short_lists = the longest list has at most SHORT_LIST_ROWS rows)
-// (ELIG: the tags of the filtered instantiations end in _elig)
-template <bool BF16, bool ELIG, class F>
+// (the tags of the filtered instantiations end in _elig, of the boosted ones in _boost, of both in _elig_boost)
+template <bool BF16, class EL, class BO, class F>
 static hipError_t with_scan_shape(int qtile, bool short_lists, F&& f) {
 #define AMDREC_SCAN_TAG(tile) \
-    (BF16 ? (ELIG ? "ivf_scan_grouped_bf16_" tile "_elig" : "ivf_scan_grouped_bf16_" tile) \
-          : (ELIG ? "ivf_scan_grouped_" tile "_elig" : "ivf_scan_grouped_" tile))
-    if (qtile == 64)
-        return short_lists ? f(ShapeIvfS<BF16>{}, AMDREC_SCAN_TAG("64x128")) : f(ShapeIvf<BF16>{}, AMDREC_SCAN_TAG("64x256"));
+    (BF16 ? AMDREC_LIST_TAG("ivf_scan_grouped_bf16_" tile) : AMDREC_LIST_TAG("ivf_scan_grouped_" tile))
+    // fp32 scan with BOTH predicates: the 64 x 256 tile spills (255 VGPRs + 16 bytes of scratch; the filtered one alone sits
+    // at 248), so long lists take the 64 x 128 tile too (220 VGPRs, no scratch) - twice the row tiles per list, same keys
+    if (qtile == 64) {
+        if constexpr (!BF16 && EL::on && BO::on)
+            return f(ShapeIvfS<BF16>{}, AMDREC_SCAN_TAG("64x128"));
+        else
+            return short_lists ? f(ShapeIvfS<BF16>{}, AMDREC_SCAN_TAG("64x128")) : f(ShapeIvf<BF16>{}, AMDREC_SCAN_TAG("64x256"));
+    }
     return short_lists ? f(ShapeIvf32S<BF16>{}, AMDREC_SCAN_TAG("32x128")) : f(ShapeIvf32<BF16>{}, AMDREC_SCAN_TAG("32x256"));
 #undef AMDREC_SCAN_TAG
 }
@@ -1003,14 +1126,14 @@ struct GroupedArgs {
     bool leading_dims() const { return ld % 4 == 0 && ld >= dim && ld_queries >= dim && ld_queries % 4 == 0; }
 };
 
-template <class EL>
+template <class EL, class BO = ListNoBoost>
 static int scan_grouped_impl(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
                              const int64_t* list_off, int nlist, int64_t max_list_rows,
                              const float* queries, int64_t ld_queries, const int64_t* group_off,
                              const int64_t* qtile_prefix, int64_t qtile_bound, int qtile,
                              const int64_t* pair_query, const int64_t* pair_probe, const int64_t* pool_base,
                              int nprobe, uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset,
-                             const float* tau, int64_t ld_tau, int64_t* pool_fill, void* stream, EL el) {
+                             const float* tau, int64_t ld_tau, int64_t* pool_fill, void* stream, EL el, BO bo = {}) {
     const GroupedArgs a{lists, ld, dim, row_pos, list_off, max_list_rows, queries, ld_queries, group_off, qtile_prefix, qtile_bound,
                         qtile, pair_query, pool_keys};
     if (int rc = a.check_dim(4)) return rc;
@@ -1022,14 +1145,12 @@ static int scan_grouped_impl(const float* lists, int64_t ld, int dim, const int6
     REQUIRE(a.pointers() && pair_probe && (pool_base || tau), "null pointer");
     REQUIRE(a.leading_dims(), "bad leading dimension");
     if (int rc = elig_check(el)) return rc;
-    const hipError_t e = with_scan_shape<false, EL::on>(qtile, max_list_rows <= SHORT_LIST_ROWS, [&](auto shape, const char* tag) {
+    if (int rc = boost_check(bo)) return rc;
+    const hipError_t e = with_scan_shape<false, EL, BO>(qtile, max_list_rows <= SHORT_LIST_ROWS, [&](auto shape, const char* tag) {
         using S = decltype(shape);
-        constexpr auto kern = [] {
-            if constexpr (EL::on) return ivf_group_scan_kernel<S, AMDREC_LIST_ELIG_ARGS>;
-            else return ivf_group_scan_kernel<S>;
-        }();
+        constexpr auto kern = AMDREC_LIST_KERNEL(ivf_group_scan_kernel, S,);
         return launch_grouped<S, kern>(
-            el, tag, max_list_rows, qtile_bound, reinterpret_cast<hipStream_t>(stream), lists, ld, dim, (dim + BK - 1) / BK,
+            el, bo, tag, max_list_rows, qtile_bound, reinterpret_cast<hipStream_t>(stream), lists, ld, dim, (dim + BK - 1) / BK,
             (const long long*)row_pos, (const long long*)list_off, queries, ld_queries, (const long long*)group_off,
             (const long long*)qtile_prefix, nlist, (const long long*)pair_query, (const long long*)pair_probe,
             (const long long*)pool_base, nprobe, (unsigned long long*)pool_keys, pool_ld, pos_offset, tau, ld_tau,
@@ -1065,29 +1186,80 @@ extern "C" int amdrec_ivf_scan_grouped_eligible(const float* lists, int64_t ld, 
                              pos_offset, tau, ld_tau, pool_fill, stream, ListElig{list_tags, require_all, require_any});
 }
 
-extern "C" int amdrec_ivf_filter_bounds(const float* queries, int64_t nq, int64_t ld_queries, int dim,
-                                        const uint16_t* queries_bf16, int64_t ld_queries_bf16, const float* max_norm,
-                                        const float* tau, int64_t ld_tau, float* tau_lo, void* stream) {
+extern "C" int amdrec_ivf_scan_grouped_boosted(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                                               const int64_t* list_off, int nlist, int64_t max_list_rows,
+                                               const float* queries, int64_t ld_queries, const int64_t* group_off,
+                                               const int64_t* qtile_prefix, int64_t qtile_bound, int qtile,
+                                               const int64_t* pair_query, const int64_t* pair_probe, const int64_t* pool_base,
+                                               int nprobe, uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset,
+                                               const float* tau, int64_t ld_tau, int64_t* pool_fill, void* stream,
+                                               const float* list_boosts, const float* weight) {
+    return scan_grouped_impl(lists, ld, dim, row_pos, list_off, nlist, max_list_rows, queries, ld_queries, group_off,
+                             qtile_prefix, qtile_bound, qtile, pair_query, pair_probe, pool_base, nprobe, pool_keys, pool_ld,
+                             pos_offset, tau, ld_tau, pool_fill, stream, ListNoElig{}, ListBoost{list_boosts, weight});
+}
+
+extern "C" int amdrec_ivf_scan_grouped_eligible_boosted(const float* lists, int64_t ld, int dim, const int64_t* row_pos,
+                                                        const int64_t* list_off, int nlist, int64_t max_list_rows,
+                                                        const float* queries, int64_t ld_queries, const int64_t* group_off,
+                                                        const int64_t* qtile_prefix, int64_t qtile_bound, int qtile,
+                                                        const int64_t* pair_query, const int64_t* pair_probe,
+                                                        const int64_t* pool_base, int nprobe, uint64_t* pool_keys,
+                                                        int64_t pool_ld, int64_t pos_offset, const float* tau, int64_t ld_tau,
+                                                        int64_t* pool_fill, void* stream, const uint64_t* list_tags,
+                                                        const uint64_t* require_all, const uint64_t* require_any,
+                                                        const float* list_boosts, const float* weight) {
+    return scan_grouped_impl(lists, ld, dim, row_pos, list_off, nlist, max_list_rows, queries, ld_queries, group_off,
+                             qtile_prefix, qtile_bound, qtile, pair_query, pair_probe, pool_base, nprobe, pool_keys, pool_ld,
+                             pos_offset, tau, ld_tau, pool_fill, stream, ListElig{list_tags, require_all, require_any},
+                             ListBoost{list_boosts, weight});
+}
+
+// BP: nothing, or (weight [nq], boost_max) of the boosted bound
+template <class... BP>
+static int filter_bounds_impl(const char* tag, const float* queries, int64_t nq, int64_t ld_queries, int dim,
+                              const uint16_t* queries_bf16, int64_t ld_queries_bf16, const float* max_norm,
+                              const float* tau, int64_t ld_tau, float* tau_lo, void* stream, BP... bp) {
     REQUIRE(dim >= 8 && dim % 8 == 0 && dim <= 2048, "dim=%d must be a multiple of 8 in [8,2048]", dim);
     if (nq <= 0) return AMDREC_OK;
     REQUIRE(queries && queries_bf16 && max_norm && tau && tau_lo, "null pointer");
     REQUIRE(ld_queries >= dim && ld_queries_bf16 >= dim && ld_tau >= 1, "bad leading dimension");
-    ProfScope prof("ivf_filter_bounds", 0.0, 0.0, reinterpret_cast<hipStream_t>(stream));
-    hipLaunchKernelGGL(ivf_filter_bounds_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    ProfScope prof(tag, 0.0, 0.0, reinterpret_cast<hipStream_t>(stream));
+    hipLaunchKernelGGL(ivf_filter_bounds_kernel<BP...>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        queries, (long long)ld_queries, queries_bf16, (long long)ld_queries_bf16, dim, (long long)nq, max_norm, tau,
-                       (long long)ld_tau, tau_lo);
+                       (long long)ld_tau, tau_lo, bp...);
     HIP_TRY(hipGetLastError());
     return AMDREC_OK;
 }
 
-template <class EL>
+extern "C" int amdrec_ivf_filter_bounds(const float* queries, int64_t nq, int64_t ld_queries, int dim,
+                                        const uint16_t* queries_bf16, int64_t ld_queries_bf16, const float* max_norm,
+                                        const float* tau, int64_t ld_tau, float* tau_lo, void* stream) {
+    return filter_bounds_impl("ivf_filter_bounds", queries, nq, ld_queries, dim, queries_bf16, ld_queries_bf16, max_norm, tau,
+                              ld_tau, tau_lo, stream);
+}
+
+extern "C" int amdrec_ivf_filter_bounds_boosted(const float* queries, int64_t nq, int64_t ld_queries, int dim,
+                                                const uint16_t* queries_bf16, int64_t ld_queries_bf16, const float* max_norm,
+                                                const float* tau, int64_t ld_tau, float* tau_lo, void* stream,
+                                                const float* weight, float boost_max) {
+    if (nq > 0) {
+        REQUIRE(weight != nullptr, "weight is null");
+        REQUIRE(((uintptr_t)weight % 4) == 0, "weight must be 4-byte aligned");
+    }
+    if (int rc = boost_max_check(boost_max)) return rc;
+    return filter_bounds_impl("ivf_filter_bounds_boost", queries, nq, ld_queries, dim, queries_bf16, ld_queries_bf16, max_norm,
+                              tau, ld_tau, tau_lo, stream, weight, boost_max);
+}
+
+template <class EL, class BO = ListNoBoost>
 static int scan_grouped_mixed_impl(const float* lists, int64_t ld, const uint16_t* lists_bf16, int64_t ld_bf16, int dim,
                                    const int64_t* row_pos, const int64_t* list_off, int nlist, int64_t max_list_rows,
                                    const float* queries, int64_t ld_queries, const uint16_t* queries_bf16,
                                    int64_t ld_queries_bf16, const int64_t* group_off, const int64_t* qtile_prefix,
                                    int64_t qtile_bound, int qtile, const int64_t* pair_query, uint64_t* pool_keys,
                                    int64_t pool_ld, int64_t pos_offset, const float* tau, int64_t ld_tau,
-                                   const float* tau_lo, int64_t* pool_fill, void* stream, EL el) {
+                                   const float* tau_lo, int64_t* pool_fill, void* stream, EL el, BO bo = {}) {
     const GroupedArgs a{lists, ld, dim, row_pos, list_off, max_list_rows, queries, ld_queries, group_off, qtile_prefix, qtile_bound,
                         qtile, pair_query, pool_keys};
     if (int rc = a.check_dim(8)) return rc;
@@ -1101,14 +1273,12 @@ static int scan_grouped_mixed_impl(const float* lists, int64_t ld, const uint16_
     REQUIRE(((uintptr_t)lists % 16) == 0 && ((uintptr_t)lists_bf16 % 16) == 0 && ((uintptr_t)queries % 16) == 0 &&
                 ((uintptr_t)queries_bf16 % 16) == 0, "lists / queries must be 16-byte aligned");
     if (int rc = elig_check(el)) return rc;
-    const hipError_t e = with_scan_shape<true, EL::on>(qtile, max_list_rows <= SHORT_LIST_ROWS, [&](auto shape, const char* tag) {
+    if (int rc = boost_check(bo)) return rc;
+    const hipError_t e = with_scan_shape<true, EL, BO>(qtile, max_list_rows <= SHORT_LIST_ROWS, [&](auto shape, const char* tag) {
         using S = decltype(shape);
-        constexpr auto kern = [] {
-            if constexpr (EL::on) return ivf_group_scan_mixed_kernel<S, AMDREC_LIST_ELIG_ARGS>;
-            else return ivf_group_scan_mixed_kernel<S>;
-        }();
+        constexpr auto kern = AMDREC_LIST_KERNEL(ivf_group_scan_mixed_kernel, S,);
         return launch_grouped<S, kern>(
-            el, tag, max_list_rows, qtile_bound, reinterpret_cast<hipStream_t>(stream), lists, ld, lists_bf16, ld_bf16, dim,
+            el, bo, tag, max_list_rows, qtile_bound, reinterpret_cast<hipStream_t>(stream), lists, ld, lists_bf16, ld_bf16, dim,
             (dim / 2 + BK - 1) / BK, (const long long*)row_pos, (const long long*)list_off, queries, ld_queries, queries_bf16,
             ld_queries_bf16, (const long long*)group_off, (const long long*)qtile_prefix, nlist, (const long long*)pair_query,
             (unsigned long long*)pool_keys, pool_ld, pos_offset, tau, ld_tau, tau_lo, (unsigned long long*)pool_fill);
@@ -1141,6 +1311,32 @@ extern "C" int amdrec_ivf_scan_grouped_mixed_eligible(
                                    ld_queries, queries_bf16, ld_queries_bf16, group_off, qtile_prefix, qtile_bound, qtile,
                                    pair_query, pool_keys, pool_ld, pos_offset, tau, ld_tau, tau_lo, pool_fill, stream,
                                    ListElig{list_tags, require_all, require_any});
+}
+
+extern "C" int amdrec_ivf_scan_grouped_mixed_boosted(
+    const float* lists, int64_t ld, const uint16_t* lists_bf16, int64_t ld_bf16, int dim, const int64_t* row_pos,
+    const int64_t* list_off, int nlist, int64_t max_list_rows, const float* queries, int64_t ld_queries,
+    const uint16_t* queries_bf16, int64_t ld_queries_bf16, const int64_t* group_off, const int64_t* qtile_prefix,
+    int64_t qtile_bound, int qtile, const int64_t* pair_query, uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset,
+    const float* tau, int64_t ld_tau, const float* tau_lo, int64_t* pool_fill, void* stream, const float* list_boosts,
+    const float* weight) {
+    return scan_grouped_mixed_impl(lists, ld, lists_bf16, ld_bf16, dim, row_pos, list_off, nlist, max_list_rows, queries,
+                                   ld_queries, queries_bf16, ld_queries_bf16, group_off, qtile_prefix, qtile_bound, qtile,
+                                   pair_query, pool_keys, pool_ld, pos_offset, tau, ld_tau, tau_lo, pool_fill, stream,
+                                   ListNoElig{}, ListBoost{list_boosts, weight});
+}
+
+extern "C" int amdrec_ivf_scan_grouped_mixed_eligible_boosted(
+    const float* lists, int64_t ld, const uint16_t* lists_bf16, int64_t ld_bf16, int dim, const int64_t* row_pos,
+    const int64_t* list_off, int nlist, int64_t max_list_rows, const float* queries, int64_t ld_queries,
+    const uint16_t* queries_bf16, int64_t ld_queries_bf16, const int64_t* group_off, const int64_t* qtile_prefix,
+    int64_t qtile_bound, int qtile, const int64_t* pair_query, uint64_t* pool_keys, int64_t pool_ld, int64_t pos_offset,
+    const float* tau, int64_t ld_tau, const float* tau_lo, int64_t* pool_fill, void* stream, const uint64_t* list_tags,
+    const uint64_t* require_all, const uint64_t* require_any, const float* list_boosts, const float* weight) {
+    return scan_grouped_mixed_impl(lists, ld, lists_bf16, ld_bf16, dim, row_pos, list_off, nlist, max_list_rows, queries,
+                                   ld_queries, queries_bf16, ld_queries_bf16, group_off, qtile_prefix, qtile_bound, qtile,
+                                   pair_query, pool_keys, pool_ld, pos_offset, tau, ld_tau, tau_lo, pool_fill, stream,
+                                   ListElig{list_tags, require_all, require_any}, ListBoost{list_boosts, weight});
 }
 
 extern "C" int amdrec_ivf_coarse_keys(const float* centroids, int nlist, int64_t ld_centroids, int dim, const float* queries,

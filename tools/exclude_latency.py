@@ -2,9 +2,10 @@
 rows), batch B in {1, 32, 512}, k = 500 and E in {0, 64, 512}: search time (HIP events, mean of REPS searches over ROT
 rotating query batches and exclusion blocks) for k, for k + E without a list, and for k with the list; the compaction kernel
 alone (amdrec_profile_* tag exclude_compact); then recommend_device end to end at B = 512 with and without a 64-entry list.
-usage: python tools/exclude_latency.py [--out FILE] [--plain-only] [--pkg DIR] [--n ROWS]
+usage: python tools/exclude_latency.py [--out FILE] [--plain-only] [--ivf-only] [--pkg DIR] [--n ROWS]
   --plain-only : only the cells without a list (search at k, recommend_device without exclude_ad_ids): runs on any commit,
-                 for the A/B of the exclude=None path against the parent (--pkg = that commit's movie-recommender-demo_amd)."""
+                 for the A/B of the exclude=None path against the parent (--pkg = that commit's movie-recommender-demo_amd).
+  --ivf-only   : the searches of IVF(100,10) and IVF(1024,32) alone, no pipeline (the A/B of a change to the list scans)."""
 import argparse
 import json
 import os
@@ -13,6 +14,7 @@ import sys
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
 ap.add_argument("--plain-only", action="store_true")
+ap.add_argument("--ivf-only", action="store_true")
 ap.add_argument("--pkg", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "movie-recommender-demo_amd"))
 ap.add_argument("--n", type=int, default=1_000_000)
 ARGS = ap.parse_args()
@@ -23,6 +25,8 @@ from amdrec import _lib, synth  # noqa: E402
 from amdrec.index import FAISSIndex  # noqa: E402
 
 INDEXES = (("Flat", {}), ("IVF", {"nlist": 100, "nprobe": 10}), ("IVFPQ", {"nlist": 100, "nprobe": 10}))
+if ARGS.ivf_only:
+    INDEXES = (("IVF", {"nlist": 100, "nprobe": 10}), ("IVF", {"nlist": 1024, "nprobe": 32}))
 BATCHES, K, WIDTHS, REPS, ROT = (1, 32, 512), 500, (0, 64, 512), 20, 4
 
 
@@ -69,7 +73,7 @@ def run_searches(x, g, out):
         idx.add(x)
         for B in BATCHES:
             qs = [torch.randn((B, 256), generator=g, device=dev) for _ in range(ROT)]
-            rec = {"index": name, "n": x.shape[0], "B": B, "k": K,
+            rec = {"index": name, **kw, "n": x.shape[0], "B": B, "k": K,
                    "search_k_ms": round(timed(lambda i: idx.search_device(qs[i % ROT], K)), 4)}
             if not ARGS.plain_only:
                 for E in WIDTHS:
@@ -127,7 +131,8 @@ def main():
     run_searches(x, g, out)
     del x
     torch.cuda.empty_cache()
-    run_pipeline(ARGS.n, out)
+    if not ARGS.ivf_only:
+        run_pipeline(ARGS.n, out)
     if ARGS.out:
         with open(ARGS.out, "w") as f:
             json.dump({"device": torch.cuda.get_device_name(0), "plain_only": ARGS.plain_only, "reps": REPS,

@@ -25,6 +25,9 @@ def demangle(names):
         d = re.sub(r"\(.*", "", d).replace("amdrec::", "")
         for t in SAME:
             d = d.replace(", " + t + ">", ">").replace(", " + t + " >", " >").replace("<" + t + ">", "")
+            d = d.replace(", " + t + ", ", ", ")             # ... or in front of a trailing pack: f<S, A, NAME, P...> is f<S, A, P...>
+        if SAME:
+            d = d.replace("<>", "")                          # a kernel that gained an (empty) trailing pack: f<> is f
         res[n] = re.sub(r"^void (\w+)$", r"\1", d.replace("> >", ">>"))
     return res
 
