@@ -292,6 +292,25 @@ int amdrec_ivf_scan_grouped_mixed_eligible_boosted(
  * keys: 16-byte aligned; ld_keys even and >= nlist (an odd nlist's last pair writes one padding key). */
 int amdrec_ivf_coarse_keys(const float* centroids, int nlist, int64_t ld_centroids, int dim, const float* queries,
                            int64_t nq, int64_t ld_queries, uint64_t* keys /*[nq][ld_keys]*/, int64_t ld_keys, void* stream);
+/* Aware probes (opt-in per index; amdrec/probes.py has the rule): the same table with the request's masks and boost weight
+ * applied per LIST through per-list summaries.  keys[q][l] = 0 - the empty slot amdrec_ivf_select skips - when list l is
+ * empty (list_len[l] == 0) or, with masks, (tag_or[l] & require_all[q]) != require_all[q] or (require_any[q] != 0 and
+ * (tag_or[l] & require_any[q]) == 0); else the key of s = c + w * b (two rounded fp32 operations; b = boost_hi[l] for
+ * w = weight[q] >= 0, boost_lo[l] otherwise) with c the score amdrec_ivf_coarse_keys files, bit for bit; s = c without a
+ * weight.  tag_or / require_all / require_any: all three or none (NULL); boost_hi / boost_lo / weight likewise.  The per-list
+ * arrays are 16-byte aligned and hold nlist entries (nothing is read beyond); an odd nlist's padding key is written as 0. */
+int amdrec_ivf_coarse_keys_aware(const float* centroids, int nlist, int64_t ld_centroids, int dim, const float* queries,
+                                 int64_t nq, int64_t ld_queries, uint64_t* keys /*[nq][ld_keys]*/, int64_t ld_keys,
+                                 const int64_t* list_len /*[nlist]*/, const uint64_t* tag_or /*[nlist]*/,
+                                 const uint64_t* require_all /*[nq]*/, const uint64_t* require_any /*[nq]*/,
+                                 const float* boost_hi /*[nlist]*/, const float* boost_lo /*[nlist]*/,
+                                 const float* weight /*[nq]*/, void* stream);
+/* The summaries: tag_or[l] = OR of list_tags over list l's rows [list_off[l], list_off[l+1]) (list_tags NULL: not written),
+ * boost_hi[l] / boost_lo[l] = max / min of list_boosts over them (list_boosts NULL: not written); an empty list gets 0 / 0.0.
+ * Exact (order-independent reductions, no atomics).  Made when the list-order copies are made, never at search time. */
+int amdrec_ivf_list_summaries(const int64_t* list_off /*[nlist+1]*/, int nlist, const uint64_t* list_tags /*[N] or NULL*/,
+                              const float* list_boosts /*[N] or NULL*/, uint64_t* tag_or /*[nlist]*/, float* boost_hi /*[nlist]*/,
+                              float* boost_lo /*[nlist]*/, void* stream);
 int amdrec_ivf_select(const uint64_t* pool_keys, int64_t pool_ld, const int64_t* pool_count /*[nq]*/,
                       int64_t nq, int k, float* out_scores /*[nq][k]*/, int64_t* out_pos /*[nq][k]*/,
                       void* stream);

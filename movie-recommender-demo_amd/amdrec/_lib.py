@@ -75,6 +75,9 @@ _SIGNATURES = {
     "amdrec_ivf_select": [_vp, _i64, _vp, _i64, _i32, _fp, _vp, _vp],
     "amdrec_ivf_select_split": [_vp, _i64, _vp, _i64, _i32, _i32, _fp, _vp, _vp, _sz, _vp, _vp],
     "amdrec_ivf_coarse_keys": [_fp, _i32, _i64, _i32, _fp, _i64, _i64, _vp, _i64, _vp],
+    # amdrec_ivf_coarse_keys' arguments up to ld_keys + (list_len, tag_or, require_all, require_any, boost_hi, boost_lo, weight)
+    "amdrec_ivf_coarse_keys_aware": [_fp, _i32, _i64, _i32, _fp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _fp, _fp, _fp, _vp],
+    "amdrec_ivf_list_summaries": [_vp, _i32, _vp, _fp, _vp, _fp, _fp, _vp],
     "amdrec_ivf_group": [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp],
     "amdrec_ivf_assign": [_fp, _i64, _i64, _i32, _fp, _i32, _i64, _vp, _fp, _vp, _sz, _vp],
     "amdrec_ivf_kmeans_workspace": [_i64, _i32, _i32, C.POINTER(_sz)],

@@ -42,7 +42,9 @@ searches and the pipeline calls take the weight.  ``ShardedRecommender`` and ``M
 
 The result is the INDEX'S OWN result under the boosted key: per query the exact top-k under ``s`` of the rows of the lists
 the PLAIN search probes.  The probes are chosen by similarity alone - a boosted ad in a list that is not probed is not
-found; that is what IVF means.  ``ip`` is, bit for bit, the score the plain search on the same scan path writes for the
+found; that is what IVF means.  (Opt-in per index, ``FAISSIndex(aware_probes=True)`` / ``enable_aware_probes()``: the coarse
+key of a boosted search becomes <q, centroid> + w_q * the list's largest boost - smallest for w_q < 0 -, so a list that
+holds a strongly boosted ad is probed for it; amdrec.probes has the rule.)  ``ip`` is, bit for bit, the score the plain search on the same scan path writes for the
 row (the pair scan's fma chain, the grouped scans' MFMA value, the prefilter's fp32 re-score chain); ``t`` and ``s`` are
 the two rounded operations above; then the list scans' own rule applies to ``s``: a NaN ``s`` files as -inf (the row ranks
 last, it is not dropped); order: ``s`` descending, ties to the lower position; fewer than k probed rows leave the -inf / -1

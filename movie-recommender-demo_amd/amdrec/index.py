@@ -26,7 +26,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, boost as _boost, auction as _auction, eligible as _eligible, exclude as _exclude, group_cap as _group_cap, ivf, ivfpq, rows_edit as _rows_edit
+from . import _lib, boost as _boost, auction as _auction, eligible as _eligible, exclude as _exclude, group_cap as _group_cap, ivf, ivfpq, probes as _probes, rows_edit as _rows_edit
 
 _MAGIC = b"AMDRECIX1"
 ADD_BATCH = 1 << 18            # IVFPQ add: rows normalised and encoded per batch (256 MB of fp32 at d = 256)
@@ -86,7 +86,7 @@ class FAISSIndex:
     def __init__(self, dimension: int, index_type: str = "IVF", nlist: int = 100, nprobe: int = 10,
                  use_gpu: bool = False, device=None, verbose: bool = False, prefilter: str = "bf16", pq_m: int = 8,
                  refine: Optional[str] = None, refine_factor: int = 4, list_tags: bool = False,
-                 list_boosts: bool = False):
+                 list_boosts: bool = False, aware_probes: bool = False):
         """``use_gpu`` is accepted for signature compatibility; the index always lives on the
         HIP device (``device`` or the current one) - there is no CPU engine.
         ``prefilter`` (Flat only): "bf16" keeps a bf16 copy of the corpus next to the fp32 one and searches with
@@ -104,6 +104,11 @@ class FAISSIndex:
         keeps its stage-1 score boosts in list order (4 bytes per ad next to the lists, rebuilt with the list layout) and takes
         ``add(boosts=)`` / ``set_boosts`` / ``boost_weight=``: the key s = ip + w_q * boost[r] is evaluated inside the list
         scans (amdrec.boost has the rule).  Without it an IVF index refuses boosts; ``enable_list_boosts()`` opts in an index
+        that is already built or loaded.
+        ``aware_probes`` (IVF / IVFPQ; ignored for Flat): the index also keeps per-list summaries of its list-order tags and
+        boosts (24 bytes per list) and a search that carries masks and / or a boost weight chooses its ``nprobe`` lists among
+        those that can hold an eligible row, by similarity plus the list's best boost term (amdrec.probes has the rule); a
+        search with neither, and ``probe_policy="similarity"``, probe as always.  ``enable_aware_probes()`` opts in an index
         that is already built or loaded."""
         if index_type == "IVFPQ" and list_boosts:
             raise NotImplementedError(_boost.LIST_BOOSTS_IVFPQ)
@@ -118,6 +123,7 @@ class FAISSIndex:
         self.refine, self.refine_factor = refine, refine_factor
         self.list_tags = bool(list_tags)
         self.list_boosts = bool(list_boosts)
+        self.aware_probes = bool(aware_probes)
         self.use_gpu = use_gpu
         self.verbose = verbose
         self.device = torch.device(device if device is not None else "cuda")
@@ -224,6 +230,21 @@ class FAISSIndex:
             self._ivf.tag_source = self._ensure_tags
         if self._takes_list_boosts():
             self._ivf.boost_source = self._boost_tensor
+        if self._aware():
+            self._ivf.aware_probes = True
+
+    def _aware(self) -> bool:
+        """An IVF / IVFPQ index that opted into aware probes (``aware_probes=True`` / ``enable_aware_probes()``)."""
+        return bool(getattr(self, "aware_probes", False)) and self.index_type != "Flat"
+
+    def enable_aware_probes(self):
+        """Opt an IVF / IVFPQ index that is already built (or was loaded from a file saved without the flag) into aware probes
+        (amdrec.probes): from now on it keeps the per-list summaries of its list-order tags and boosts (made here when those
+        copies stand, else with them) and a search with masks and / or a boost weight chooses its probes among the feasible
+        lists.  The flag is saved with the index.  Nothing to do for Flat."""
+        self.aware_probes = True
+        if self._ivf is not None and self.index_type != "Flat":
+            self._ivf.enable_aware_probes()
 
     def enable_list_tags(self):
         """Opt an IVF / IVFPQ index that is already built (or was loaded from a file saved without the flag) into eligibility
@@ -627,7 +648,7 @@ class FAISSIndex:
                       return_positions: bool = False, pos_offset: int = 0, exclude: Optional[torch.Tensor] = None,
                       _exclude_positions: bool = False, require_all: Optional[torch.Tensor] = None,
                       require_any: Optional[torch.Tensor] = None, max_per_group: Optional[int] = None,
-                      group_overfetch: int = 2, boost_weight=None):
+                      group_overfetch: int = 2, boost_weight=None, probe_policy: Optional[str] = None):
         """Device-to-device search, asynchronous on the current stream.
         -> (ids int64 [nq,k], scores float32 [nq,k]) on the device.  ``return_positions``: corpus
         positions (+ ``pos_offset``, the shard's first global row) instead of ids, -1 = unfilled.
@@ -649,6 +670,8 @@ class FAISSIndex:
         launch more.  With ``exclude`` the filtered search runs for k + E.  IVF / IVFPQ: the index's own result restricted
         to eligible rows - the exact top-k, in its own order and with its own scores, of the eligible rows of the probed
         lists (IVFPQ refine re-ranks the best eligible candidates); without ``list_tags`` they raise NotImplementedError.
+        The probed lists are the most similar ones whatever the masks, unless the index opted into ``aware_probes``
+        (``probe_policy`` below): then they are the most similar lists that can hold an eligible row.
         ``max_per_group`` (None: no cap, not one launch more): at most that many rows of one group (``add(groups=)`` /
         ``set_groups``; negative keys are never capped) per query, greedy in the result's order (amdrec.group_cap).  The
         search runs as above - masks and exclusion included - for ``K1 = min(k * group_overfetch, AMDREC_MAX_K - E)``
@@ -661,19 +684,26 @@ class FAISSIndex:
         float32 [nq], the queries' weights w_q on the per-ad boosts (``add(boosts=)`` / ``set_boosts``): the exact top-k under
         s = ip + w_q * boost[r], s returned as the score (amdrec.boost has the rule), evaluated inside the corpus pass.
         IVF: the index's own result under that key - the exact top-k under s of the rows of the lists the PLAIN search
-        probes (the probes are chosen by similarity alone: a boosted ad in an unprobed list is not found); with masks on an
-        index that also has ``list_tags``, of the eligible ones.
+        probes (the probes are chosen by similarity alone: a boosted ad in an unprobed list is not found - unless the index
+        opted into ``aware_probes``, whose coarse key adds w_q times the list's best boost); with masks on an index that also
+        has ``list_tags``, of the eligible ones.
         ``exclude`` and ``max_per_group`` wrap the boosted search; on Flat together with masks, on IVF without
-        ``list_boosts`` and on IVFPQ it raises NotImplementedError; on an index without boosts ValueError."""
+        ``list_boosts`` and on IVFPQ it raises NotImplementedError; on an index without boosts ValueError.
+        ``probe_policy`` (IVF / IVFPQ; Flat has no probes): None = the index's ``aware_probes`` flag decides; "similarity" =
+        the plain probes also on a flagged index (A/B runs); "aware" on an index without the flag raises ValueError before the
+        library is touched.  Under the aware policy a search with masks and / or a boost weight probes the ``nprobe`` best
+        FEASIBLE lists of amdrec.probes' rule and the result is the masked / boosted result over those lists; a search with
+        neither probes as always, launch for launch."""
+        aware = _probes.check_policy(probe_policy, self._aware())
         masked = self._check_masks(require_all, require_any)
         boosted = self._check_boost(boost_weight, masked)
         cap = self._check_group_cap(max_per_group)
         if cap is not None:
             return self._search_capped(queries, k, normalize, return_positions, pos_offset, exclude, _exclude_positions,
-                                       require_all, require_any, cap, group_overfetch, boost_weight)
+                                       require_all, require_any, cap, group_overfetch, boost_weight, probe_policy)
         if exclude is not None and exclude.shape[-1] > 0:
             return self._search_excluding(queries, k, normalize, return_positions, pos_offset, exclude, _exclude_positions,
-                                          require_all, require_any, boost_weight)
+                                          require_all, require_any, boost_weight, probe_policy)
         q = _lib.require_gpu(queries, "queries")
         if q.dim() != 2 or q.shape[1] != self.dimension:
             raise ValueError(f"expected [nq, {self.dimension}] queries, got {tuple(q.shape)}")
@@ -700,9 +730,10 @@ class FAISSIndex:
         pos = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         off = pos_offset if return_positions else 0
         if self.index_type == "IVF":
-            self._ivf.search(self._xb, self._n, q, k, self.nprobe, scores, pos, pos_offset=off, elig=masks, boost=list_boost)
+            self._ivf.search(self._xb, self._n, q, k, self.nprobe, scores, pos, pos_offset=off, elig=masks, boost=list_boost,
+                             **({"aware": True} if aware else {}))
         elif self.index_type == "IVFPQ":                              # scores = squared L2 distances, ascending
-            self._pq.search(q, k, self.nprobe, scores, pos, pos_offset=off, elig=masks)
+            self._pq.search(q, k, self.nprobe, scores, pos, pos_offset=off, elig=masks, **({"aware": True} if aware else {}))
         elif self._mixed:
             flat_search_mixed(self._xb, self._xb16, self._maxnorm, self._n, q, k, scores, pos, pos_offset=off,
                               n_fixup=self.n_fixup_out, elig=elig, boost=boost)
@@ -725,13 +756,13 @@ class FAISSIndex:
         return ids, scores
 
     def _search_excluding(self, queries, k, normalize, return_positions, pos_offset, exclude, exclude_positions,
-                          require_all=None, require_any=None, boost_weight=None):
+                          require_all=None, require_any=None, boost_weight=None, probe_policy=None):
         """search_device with an exclusion block: the unfiltered search for kc = k + E, the remap to ids where ids are not
         positions, amdrec_exclude_compact on the ids, and the id path's treatment of unfilled slots after that."""
         kc = _exclude.check_exclude(k, exclude.shape[-1])              # (before the library is touched)
         excl = _lib.require_gpu(exclude, "exclude", torch.int64)
         pos_c, sc_c = self.search_device(queries, kc, normalize=normalize, return_positions=True, require_all=require_all,
-                                         require_any=require_any, boost_weight=boost_weight)
+                                         require_any=require_any, boost_weight=boost_weight, probe_policy=probe_policy)
         fill = float("inf") if self.index_type == "IVFPQ" else float("-inf")
         if self._identity or exclude_positions:                      # the keys to match are the positions themselves
             pos, scores, _ = _exclude.compact(pos_c, sc_c, None, excl, k, fill)
@@ -744,14 +775,14 @@ class FAISSIndex:
         return self._finish_compacted(pos, scores, return_positions, pos_offset)
 
     def _search_capped(self, queries, k, normalize, return_positions, pos_offset, exclude, exclude_positions, require_all,
-                       require_any, cap, group_overfetch, boost_weight=None):
+                       require_any, cap, group_overfetch, boost_weight=None, probe_policy=None):
         """search_device under a per-group cap: the search as it is (masks and exclusion included) for K1 positions,
         amdrec_group_cap_compact by position to k, and the id path's treatment of unfilled slots after that."""
         E = 0 if exclude is None else int(exclude.shape[-1])
         k1 = _group_cap.overfetch_k(k, group_overfetch, E)             # (before the library is touched)
         pos_c, sc_c = self.search_device(queries, k1, normalize=normalize, return_positions=True, exclude=exclude,
                                          _exclude_positions=exclude_positions, require_all=require_all, require_any=require_any,
-                                         boost_weight=boost_weight)
+                                         boost_weight=boost_weight, probe_policy=probe_policy)
         fill = float("inf") if self.index_type == "IVFPQ" else float("-inf")
         pos, scores = _group_cap.compact(pos_c, sc_c, self._groups, self._n, cap, k, fill)
         return self._finish_compacted(pos, scores, return_positions, pos_offset)
@@ -796,19 +827,22 @@ class FAISSIndex:
         return self._host_pos[1]
 
     def search(self, query_embeddings, k: int = 100, return_distances: bool = True, exclude=None, require_all=None,
-               require_any=None, max_per_group: Optional[int] = None, group_overfetch: int = 2, boost_weight=None):
+               require_any=None, max_per_group: Optional[int] = None, group_overfetch: int = 2, boost_weight=None,
+               probe_policy: Optional[str] = None):
         """faiss_retrieval.py:129-166.  numpy in, numpy out: (ad_ids, distances).  ``exclude``: one sequence of ad ids per
         query (or an integer array [nq, E], negative = padding) that must not be returned: see search_device.
         ``require_all`` / ``require_any``: the queries' eligibility masks, one 64-bit word each (one int for all queries, a
         sequence of ints, a uint64 / int64 array): see search_device.  ``max_per_group`` / ``group_overfetch``: the per-group
         cap on every query's result: see search_device.  ``boost_weight``: the stage-1 boost weight, one number for every
-        query or a sequence of one per query: see search_device."""
+        query or a sequence of one per query: see search_device.  ``probe_policy``: None / "similarity" / "aware", how an IVF / IVFPQ
+        index with ``aware_probes`` chooses its probes: see search_device."""
+        _probes.check_policy(probe_policy, self._aware())
         masked = self._check_masks(require_all, require_any)
         cap = (self._check_group_cap(max_per_group), group_overfetch)
         nq = len(query_embeddings)
         w = self._boost_weights(boost_weight, nq, masked)
         return self._search(query_embeddings, k, return_distances, self._exclude_block(exclude, nq),
-                            _eligible.device_masks(require_all, require_any, nq, self.device), cap, w)
+                            _eligible.device_masks(require_all, require_any, nq, self.device), cap, w, probe_policy)
 
     def _boost_weights(self, boost_weight, nq: int, masked: bool) -> Optional[torch.Tensor]:
         """The ``boost_weight`` argument of search / batch_search -> device float32 [nq] (None: no boost), every value
@@ -817,7 +851,8 @@ class FAISSIndex:
             return None
         return torch.from_numpy(_boost.as_weights(boost_weight, nq)).to(self.device)
 
-    def _search(self, query_embeddings, k, return_distances, excl, masks=(None, None), cap=(None, 2), boost_weight=None):
+    def _search(self, query_embeddings, k, return_distances, excl, masks=(None, None), cap=(None, 2), boost_weight=None,
+                probe_policy=None):
         """search with the exclusion lists already as a device block (_exclude_block), the masks as device words and the
         per-group cap as (max_per_group or None, group_overfetch)."""
         q = self._to_device_f32(query_embeddings)
@@ -825,12 +860,14 @@ class FAISSIndex:
         if self._host_ids is not None:
             pos, scores = self.search_device(q, k, normalize=True, return_positions=True, exclude=excl,
                                              _exclude_positions=True, require_all=masks[0], require_any=masks[1],
-                                             max_per_group=cap[0], group_overfetch=cap[1], boost_weight=boost_weight)
+                                             max_per_group=cap[0], group_overfetch=cap[1], boost_weight=boost_weight,
+                                             **({} if probe_policy is None else {"probe_policy": probe_policy}))
             idm = np.asarray(self._host_ids, dtype=object)
             ad_ids = idm[pos.cpu().numpy()]                          # pos == -1 -> id_map[-1]
         else:
             ids, scores = self.search_device(q, k, normalize=True, exclude=excl, require_all=masks[0], require_any=masks[1],
-                                             max_per_group=cap[0], group_overfetch=cap[1], boost_weight=boost_weight)
+                                             max_per_group=cap[0], group_overfetch=cap[1], boost_weight=boost_weight,
+                                             **({} if probe_policy is None else {"probe_policy": probe_policy}))
             ad_ids = ids.cpu().numpy()
         distances = scores.cpu().numpy()
         self._log(f"Search completed in {(time.time() - t0) * 1000:.2f}ms for {len(q)} queries")
@@ -839,11 +876,13 @@ class FAISSIndex:
         return ad_ids
 
     def batch_search(self, query_embeddings, k: int = 100, batch_size: int = 1000, exclude=None, require_all=None,
-                     require_any=None, max_per_group: Optional[int] = None, group_overfetch: int = 2, boost_weight=None):
+                     require_any=None, max_per_group: Optional[int] = None, group_overfetch: int = 2, boost_weight=None,
+                     probe_policy: Optional[str] = None):
         """faiss_retrieval.py:168-194.  ``exclude`` (as in search) is padded once, to the longest list of the whole call,
         and sliced with the queries: the chunking does not change the result.  ``require_all`` / ``require_any`` (as in
         search) are sliced with the queries too.  ``max_per_group`` / ``group_overfetch`` (as in search) hold per query."""
         all_ids, all_d = [], []
+        _probes.check_policy(probe_policy, self._aware())
         masked = self._check_masks(require_all, require_any)
         w = self._boost_weights(boost_weight, len(query_embeddings), masked)      # (sliced with the queries, like the masks)
         cap = (self._check_group_cap(max_per_group), group_overfetch)
@@ -853,7 +892,7 @@ class FAISSIndex:
             ids, d = self._search(query_embeddings[i:i + batch_size], k, True,
                                   None if excl is None else excl[i:i + batch_size],
                                   (None, None) if ma is None else (ma[i:i + batch_size], my[i:i + batch_size]), cap,
-                                  None if w is None else w[i:i + batch_size])
+                                  None if w is None else w[i:i + batch_size], probe_policy)
             all_ids.append(ids)
             all_d.append(d)
         return np.vstack(all_ids), np.vstack(all_d)
@@ -889,6 +928,8 @@ class FAISSIndex:
             header["list_tags"] = True
         if self._takes_list_boosts():                                # (absent: no list-order boosts, as every earlier file)
             header["list_boosts"] = True
+        if self._aware():                                            # (absent: probes by similarity alone, as every earlier file)
+            header["aware_probes"] = True
         if self._host_ids is not None:
             header["host_ids"] = [_encode_id(x) for x in self._host_ids]     # typed: ids round-trip as what they were
         hj = json.dumps(header).encode()
@@ -922,6 +963,7 @@ class FAISSIndex:
         self.refine, self.refine_factor = header.get("refine"), int(header.get("refine_factor", 4))
         self.list_tags = bool(header.get("list_tags", False))
         self.list_boosts = bool(header.get("list_boosts", False))
+        self.aware_probes = bool(header.get("aware_probes", False))
         self._create_index()
         n = header["ntotal"]
         self._reserve(n)

@@ -20,6 +20,9 @@ scan of a masked search is its ``*_eligible`` twin ("Eligibility mask
 Stage-1 score boosts (opt-in, ``FAISSIndex(list_boosts=True)``): ``InvertedLists`` also keeps the boosts in list order and
 every scan of a boosted search is its ``*_boosted`` twin - same probes, same phases, the key s = ip + w_q * boost[r] where
 the plain scan files ip ("Stage-1 score boosts in the inverted-list scans").
+Aware probes (opt-in, ``FAISSIndex(aware_probes=True)``): ``InvertedLists`` also keeps per-list summaries of those two copies
+(``amdrec_ivf_list_summaries``) and the coarse step of a masked / boosted search picks the nprobe best FEASIBLE lists
+(``amdrec_ivf_coarse_keys_aware``; amdrec.probes has the rule; DESIGN.md, "Aware probes").  The scans are untouched.
 Sharding: the centroids are SHARED by all ranks (``amdrec.sharded.share_ivf_centroids``); a rank
 files its own rows under them and holds its slice of every list, so the union of the ranks' scans is exactly the
 unsharded scan and the merged top-k is bit-identical to the unsharded IVF result.
@@ -166,6 +169,13 @@ class InvertedLists:
         self.boost_source = None
         self.list_boosts: Optional[torch.Tensor] = None
         self._list_boosts_of = None
+        # Aware probes (FAISSIndex(aware_probes=True); amdrec.probes has the rule): per-list summaries of the two list-order
+        # copies - list_tag_or [nlist] int64 (OR of a list's tag words), list_boost_hi / list_boost_lo [nlist] float32 (max /
+        # min of its boosts) - made by refresh_list_tags / refresh_list_boosts with the copy they summarise, as NEW tensors
+        self.aware_probes = False
+        self.list_tag_or: Optional[torch.Tensor] = None
+        self.list_boost_hi: Optional[torch.Tensor] = None
+        self.list_boost_lo: Optional[torch.Tensor] = None
 
     # -- build ----------------------------------------------------------------------------
     @classmethod
@@ -233,11 +243,23 @@ class InvertedLists:
         # rows of the p longest lists, p = 1 .. nlist: the tight host-side bound of a query's candidate pool
         # (its nprobe probed lists cannot hold more than the nprobe longest; once per list rebuild, like max above)
         self._top_rows = np.cumsum(np.sort(counts.cpu().numpy())[::-1].astype(np.int64))
-        self.list_tags = self._list_tags_of = None
+        self.list_tags = self._list_tags_of = self.list_tag_or = None
         self.refresh_list_tags()
-        self.list_boosts = self._list_boosts_of = None
+        self.list_boosts = self._list_boosts_of = self.list_boost_hi = self.list_boost_lo = None
         self.refresh_list_boosts()
         return self.lists
+
+    def _summaries(self, list_tags=None, list_boosts=None):
+        """amdrec_ivf_list_summaries over the current layout -> (tag_or, boost_hi, boost_lo), new tensors (None where the
+        input is None)."""
+        dev = self.device
+        tag_or = None if list_tags is None else torch.zeros(self.nlist, dtype=torch.int64, device=dev)
+        hi = None if list_boosts is None else torch.zeros(self.nlist, dtype=torch.float32, device=dev)
+        lo = None if list_boosts is None else torch.zeros(self.nlist, dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().amdrec_ivf_list_summaries(_lib.ptr(self.lists.off), self.nlist, _lib.ptr(list_tags),
+                                                         _lib.ptr(list_boosts), _lib.ptr(tag_or), _lib.ptr(hi), _lib.ptr(lo),
+                                                         _lib.stream_ptr(dev)))
+        return tag_or, hi, lo
 
     def refresh_list_tags(self) -> Optional[torch.Tensor]:
         """list_tags of the current layout from the owner's current tag tensor (amdrec_rows_gather, out of place: a search in
@@ -250,6 +272,9 @@ class InvertedLists:
         if self.list_tags is None or self._list_tags_of is not tags:
             self.list_tags = gather_rows(tags, self.lists.spos, self.lists.n)
             self._list_tags_of = tags
+            self.list_tag_or = None
+        if self.aware_probes and self.list_tag_or is None:           # the summary stands and falls with the copy it summarises
+            self.list_tag_or = self._summaries(list_tags=self.list_tags)[0]
         return self.list_tags
 
     def refresh_list_boosts(self) -> Optional[torch.Tensor]:
@@ -259,12 +284,21 @@ class InvertedLists:
             return None
         boosts = self.boost_source()
         if boosts is None:                                           # an index that never saw a boost keeps no copy
-            self.list_boosts = self._list_boosts_of = None
+            self.list_boosts = self._list_boosts_of = self.list_boost_hi = self.list_boost_lo = None
             return None
         if self.list_boosts is None or self._list_boosts_of is not boosts:
             self.list_boosts = gather_rows(boosts, self.lists.spos, self.lists.n)
             self._list_boosts_of = boosts
+            self.list_boost_hi = self.list_boost_lo = None
+        if self.aware_probes and self.list_boost_hi is None:
+            _, self.list_boost_hi, self.list_boost_lo = self._summaries(list_boosts=self.list_boosts)
         return self.list_boosts
+
+    def enable_aware_probes(self):
+        """From now on the summaries are kept (made here for the list-order copies that already stand)."""
+        self.aware_probes = True
+        self.refresh_list_tags()
+        self.refresh_list_boosts()
 
     def boost_tail(self, boost, nq: int):
         """``boost`` = (weights device float32 [nq], boost_max) -> f(s): the two trailing pointers of a *_boosted scan for the
@@ -310,10 +344,65 @@ class InvertedLists:
         nbytes = nq * self.coarse_ld * 8
         return nbytes if nbytes <= POOL_BYTES and nprobe <= _lib.MAX_K and nq < (1 << 24) else 0
 
-    def coarse_probes(self, q: torch.Tensor, nprobe: int, keys: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def aware_table_rows(self, nq: int) -> int:
+        """Queries per fill of the aware key table: all of them when their table fits POOL_BYTES, else the chunk that does (the
+        flat search, the plain path's way out, cannot apply the rule)."""
+        return max(1, min(nq, (1 << 24) - 1, POOL_BYTES // (self.coarse_ld * 8)))
+
+    def aware_table_bytes(self, nq: int) -> int:
+        return self.aware_table_rows(nq) * self.coarse_ld * 8
+
+    def _aware_probes(self, q: torch.Tensor, nprobe: int, keys: Optional[torch.Tensor], elig, boost) -> torch.Tensor:
+        """coarse_probes under amdrec.probes' rule: amdrec_ivf_coarse_keys_aware + the pool select (a key of 0 - an infeasible
+        list - is the empty slot the select skips: fewer feasible lists than nprobe leave a -1 tail), in query chunks of
+        ``aware_table_rows`` when the table of all queries does not fit."""
+        if not self.aware_probes:
+            raise ValueError("masks / a boost weight in the coarse step need the per-list summaries: "
+                             "FAISSIndex(aware_probes=True) or enable_aware_probes()")
+        if self.lists is None:
+            raise ValueError("aware probes need the list layout (made by the first search after an add)")
+        if nprobe > _lib.MAX_K:
+            raise ValueError(f"nprobe {nprobe} exceeds AMDREC_MAX_K = {_lib.MAX_K}, the most probes a search selects")
+        nq = q.shape[0]
+        tag_or = ma = my = hi = lo = w = None
+        if elig is not None:
+            self.elig_tail(elig, nq)                                 # (validates; refreshes list_tags and with it the summary)
+            tag_or, (ma, my) = self.list_tag_or, elig
+        if boost is not None:
+            self.boost_tail(boost, nq)
+            hi, lo, w = self.list_boost_hi, self.list_boost_lo, boost[0]
+        cs = torch.empty((nq, nprobe), dtype=torch.float32, device=self.device)
+        probes = torch.empty((nq, nprobe), dtype=torch.int64, device=self.device)
+        if not nq:
+            return probes
+        lib = _lib.load()
+        rows = self.aware_table_rows(nq)
+        nbytes = rows * self.coarse_ld * 8
+        if keys is None or keys.numel() < nbytes:
+            keys = _lib.WORKSPACE.get(nbytes, self.device)
+        if self._nlist_count is None or self._nlist_count.numel() < rows:
+            self._nlist_count = torch.full((max(rows, 512),), self.nlist, dtype=torch.int64, device=self.device)
+        at = lambda t, s: None if t is None else _lib.ptr(t[s:])     # noqa: E731
+        for s in range(0, nq, rows):
+            m = min(rows, nq - s)
+            _lib.check(lib.amdrec_ivf_coarse_keys_aware(
+                _lib.ptr(self.centroids), self.nlist, self.centroids.stride(0), self.dim, _lib.ptr(q[s:]), m, q.stride(0),
+                _lib.ptr(keys), self.coarse_ld, _lib.ptr(self.lists.lens), _lib.ptr(tag_or), at(ma, s), at(my, s), _lib.ptr(hi),
+                _lib.ptr(lo), at(w, s), _lib.stream_ptr(self.device)))
+            _lib.check(lib.amdrec_ivf_select(_lib.ptr(keys), self.coarse_ld, _lib.ptr(self._nlist_count), m, nprobe,
+                                             _lib.ptr(cs[s:]), _lib.ptr(probes[s:]), _lib.stream_ptr(self.device)))
+        return probes
+
+    def coarse_probes(self, q: torch.Tensor, nprobe: int, keys: Optional[torch.Tensor] = None, elig=None,
+                      boost=None) -> torch.Tensor:
         """-> int64 [nq, nprobe]: the nprobe best centroids of each query by inner product (IndexFlatIP quantizer; -1 = none).
         A dense key table (in ``keys``, else in ``coarse_table_bytes`` of the shared workspace) + the pool select, or, when
-        the table does not fit, the flat search."""
+        the table does not fit, the flat search.
+        ``elig`` = (require_all, require_any) device int64 [nq] and / or ``boost`` = (weights device float32 [nq], boost_max),
+        on an index with ``aware_probes``: the nprobe best FEASIBLE lists under amdrec.probes' rule instead (-1 = fewer
+        feasible lists than nprobe); both None: the plain path above, launch for launch."""
+        if elig is not None or boost is not None:
+            return self._aware_probes(q, nprobe, keys, elig, boost)
         nq, nbytes = q.shape[0], self.coarse_table_bytes(q.shape[0], nprobe)
         cs = torch.empty((nq, nprobe), dtype=torch.float32, device=self.device)
         probes = torch.empty((nq, nprobe), dtype=torch.int64, device=self.device)
@@ -378,7 +467,7 @@ class InvertedLists:
     def resident_tensors(self) -> list:
         """Every device tensor kept between calls (a captured graph's kernels point at them)."""
         kept = [self.centroids, self.assign, self._nlist_count, self._sel_scratch, self._sel_tickets, self.list_tags,
-                self.list_boosts, *(self.lists or ())]
+                self.list_boosts, self.list_tag_or, self.list_boost_hi, self.list_boost_lo, *(self.lists or ())]
         return [t for t in kept if isinstance(t, torch.Tensor)]
 
     # -- persistence ----------------------------------------------------------------------
@@ -432,13 +521,15 @@ class IVFState(InvertedLists):
 
     # -- search ---------------------------------------------------------------------------
     def search(self, xb: torch.Tensor, n: int, q: torch.Tensor, k: int, nprobe: int, out_scores: torch.Tensor,
-               out_pos: torch.Tensor, pos_offset: int = 0, elig=None, boost=None):
+               out_pos: torch.Tensor, pos_offset: int = 0, elig=None, boost=None, aware: bool = False):
         """``elig``: (require_all, require_any) device int64 [nq] -> every scan of the search is its *_eligible twin over
         ``list_tags`` (same probes, same phases, same tiles; the first phase's tau is the k-th ELIGIBLE score); None: the
         plain scans, nothing else.
         ``boost``: (weights device float32 [nq], boost_max) -> every scan is its *_boosted twin over ``list_boosts`` (same
         probes - chosen by similarity alone -, same phases; the first phase's tau is the k-th BOOSTED score and the prefilter's
-        bound is amdrec_ivf_filter_bounds_boosted's); with ``elig`` the *_eligible_boosted twins; None: nothing changes."""
+        bound is amdrec_ivf_filter_bounds_boosted's); with ``elig`` the *_eligible_boosted twins; None: nothing changes.
+        ``aware`` (an index with ``aware_probes``): the probes of a search with ``elig`` and / or ``boost`` are chosen under
+        amdrec.probes' rule - the coarse step sees the masks and the weight; everything after the probes is what it was."""
         lib = _lib.load()
         nq = q.shape[0]
         if nq == 0:
@@ -461,10 +552,11 @@ class IVFState(InvertedLists):
         qtile = QTILE_SPARSE if min(chunk, nq) * nprobe < SPARSE_PAIRS_PER_LIST * self.nlist else QTILE
         if grouped:
             chunk = min(chunk, grouped_chunk_limit(self.nlist, nprobe))
-        w = self.workspace(chunk, nprobe, pool_ld, self.coarse_table_bytes(nq, nprobe))
+        aware = aware and (elig is not None or boost is not None)
+        w = self.workspace(chunk, nprobe, pool_ld, self.aware_table_bytes(nq) if aware else self.coarse_table_bytes(nq, nprobe))
         ws, pair_q, pair_p, goff, qtp = w.pool, w.pair_q, w.pair_p, w.goff, w.qtp
         # 1. coarse quantizer: nprobe best centroids per query (key table in the workspace, or the flat search)
-        probes = self.coarse_probes(q, nprobe, w.keys)
+        probes = self.coarse_probes(q, nprobe, w.keys, elig=elig, boost=boost) if aware else self.coarse_probes(q, nprobe, w.keys)
         st = lambda: _lib.stream_ptr(self.device)      # noqa: E731  (per call: check() ends the call's device scope)
 
         def group_and_scan(s, m, col0, ncol, tau=None, fill=None, n_out=None):

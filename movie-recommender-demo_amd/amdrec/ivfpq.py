@@ -199,9 +199,10 @@ class IVFPQState:
         return self.ivf.coarse_probes(q, nprobe)
 
     def search(self, q: torch.Tensor, k: int, nprobe: int, out_dist: torch.Tensor, out_pos: torch.Tensor,
-               pos_offset: int = 0, elig=None):
+               pos_offset: int = 0, elig=None, aware: bool = False):
         """``elig``: (require_all, require_any) device int64 [nq] -> the code scan is amdrec_ivfpq_scan_finite_eligible over the
         coarse level's ``list_tags``; with refine the re-rank then orders the best ELIGIBLE candidates and needs no masks.
+        ``aware`` (an index with ``aware_probes``): the probes of a masked search are the best FEASIBLE lists (amdrec.probes).
         q: L2-normalised queries.  -> out_dist [nq, k] squared L2 distances (ascending, +inf = unfilled): approximate
         (from the codes), or with refine exact for the kept rows; out_pos [nq, k] positions + pos_offset (-1 = unfilled)."""
         nq = q.shape[0]
@@ -212,14 +213,14 @@ class IVFPQState:
             out_pos.fill_(-1)
             return
         if self.rows is None:
-            self._search_codes(q, k, nprobe, out_dist, out_pos, pos_offset, elig=elig)
+            self._search_codes(q, k, nprobe, out_dist, out_pos, pos_offset, elig=elig, aware=aware)
             return
         # steps 1-4 for k' candidates (scores = -approximate distance: only their order matters), then
         # 5. the exact re-rank of those candidates from the kept rows
         kc = refine_candidates(k, self.refine_factor)
         cand_score = torch.empty((nq, kc), dtype=torch.float32, device=self.device)
         cand_pos = torch.empty((nq, kc), dtype=torch.int64, device=self.device)
-        self._search_codes(q, kc, nprobe, cand_score, cand_pos, 0, distances=False, elig=elig)
+        self._search_codes(q, kc, nprobe, cand_score, cand_pos, 0, distances=False, elig=elig, aware=aware)
         self.rerank(q, cand_pos, k, out_dist, out_pos, pos_offset)
 
     def rerank(self, q: torch.Tensor, cand_pos: torch.Tensor, k: int, out_dist: torch.Tensor, out_pos: torch.Tensor,
@@ -244,7 +245,7 @@ class IVFPQState:
                 _lib.ptr(self._rr_tickets) if split else None, _lib.stream_ptr(self.device)))
 
     def _search_codes(self, q: torch.Tensor, k: int, nprobe: int, out_dist: torch.Tensor, out_pos: torch.Tensor,
-                      pos_offset: int = 0, distances: bool = True, elig=None):
+                      pos_offset: int = 0, distances: bool = True, elig=None, aware: bool = False):
         """Steps 1-4: the k best rows of the probed lists by the codes' table-lookup distance (``distances`` False: out_dist
         keeps the select's scores, -distance)."""
         lib = _lib.load()
@@ -260,11 +261,12 @@ class IVFPQState:
         pool_ld = ivf.pool_rows_bound(nprobe)
         chunk = max(1, min(nq, 65535, POOL_BYTES // (pool_ld * 8), TABLE_BYTES // (nprobe * self.m * KSUB * 4),
                            grouped_chunk_limit(self.nlist, nprobe)))
-        w = ivf.workspace(chunk, nprobe, pool_ld, ivf.coarse_table_bytes(nq, nprobe),
+        aware = aware and elig is not None
+        w = ivf.workspace(chunk, nprobe, pool_ld, ivf.aware_table_bytes(nq) if aware else ivf.coarse_table_bytes(nq, nprobe),
                           extra_bytes=chunk * nprobe * self.m * KSUB * 4)
         tables = w.extra.view(torch.float32)
         # 1. coarse quantizer: the IVF index's (dense key table + pool select, or the flat search beyond its limits)
-        probes = ivf.coarse_probes(q, nprobe, w.keys)
+        probes = ivf.coarse_probes(q, nprobe, w.keys, elig=elig) if aware else ivf.coarse_probes(q, nprobe, w.keys)
         c = self.centroids
         for s in range(0, nq, chunk):
             m = min(chunk, nq - s)
