@@ -39,7 +39,8 @@ extern "C" {
                                * auction ranking: amdrec_select_topk_auction, an added export; then
                                * per-ad score boosts: amdrec_flat_search_boosted, amdrec_flat_search_mixed_boosted, added exports; then
                                * the same boosts in the inverted-list scans: amdrec_ivf_scan[_grouped[_mixed]][_eligible]_boosted and
-                               * amdrec_ivf_filter_bounds_boosted, added exports) */
+                               * amdrec_ivf_filter_bounds_boosted, added exports; then
+                               * value ranking: amdrec_select_topk_value, amdrec_select_topk_value_auction, added exports) */
 #define AMDREC_MAX_K 2048
 
 int amdrec_abi_version(void);
@@ -876,6 +877,49 @@ int amdrec_select_topk_diverse(const float* logits /*[n_tasks][ld]*/, int64_t ld
                                int max_per_group /*0: no cap*/, int64_t* out_ids /*[n_users][top_k]*/,
                                float* out_scores /*[n_tasks][n_users][top_k]*/, int32_t* out_slots /*or NULL*/,
                                float* out_values /*[n_users][top_k]*/, void* stream);
+
+/* Value ranking (two more exports added to ABI v14, every other entry as it was): the selections above ordered by a weighted
+ * blend of EVERY task's probability instead of the ranking task alone.  weights (device float32 [n_users][n_tasks]) are per
+ * user; n_tasks <= AMDREC_MAX_TASKS.  For candidate slot i of user u (a candidate iff cand_pos >= 0; cand_pos is REQUIRED):
+ *   p_t = the probability amdrec_select_topk reports for logits[t].  The tasks are visited in order t = 0 .. n_tasks - 1; a
+ *   term whose weight is 0 (either sign) is skipped and its logit has no influence, NaN included; y_t = p_t, in the auction
+ *   variant y_r = e = b * p_r for r = rank_task, b = bid_of[cand_pos] (1.0 for a position >= n_bid_rows, which is never
+ *   read); x_t = w_t * y_t; v = the first unskipped x_t, then v = v + x_t.  Every product, sum, difference and quotient here
+ *   is one rounded fp32 operation, never contracted.  All weights zero: v = +0.0.
+ * Order: v descending (-0.0 and +0.0 tie), slot ascending, a NaN v after every other candidate in slot order; a slot that is
+ * no candidate never wins.  max_per_group > 0: the greedy cap of amdrec_select_topk_capped in that order; 0: no cap, group_of
+ * is not looked at and may be NULL.  The first top_k accepted candidates win; out_ids / out_scores / out_slots as
+ * amdrec_select_topk, out_values[u][rank] = v, formed from the probabilities that out_scores reports: the blend of out_scores
+ * (and out_ecpm) equals it bit for bit.  A NaN output is the canonical quiet NaN; the unfilled tail reads id -1, slot -1,
+ * probabilities 0.0, value 0.0.  With weights 1.0 * onehot(r) the order is by p_r: amdrec_select_topk's for a user whose p_r
+ * are pairwise distinct - NOT the logit order in general, because saturated sigmoids tie and resolve by slot.
+ *
+ * amdrec_select_topk_value_auction: reserve (device [n_users], may be NULL): a candidate is dropped iff !(v >= reserve[u]),
+ * as in amdrec_select_topk_auction.  floor = max(reserve[u] or 0, v of the candidate the same selection reports at the next
+ * rank - for the last rank the (top_k + 1)-th accepted one; a missing or NaN one counts 0).  q = the chain with term r left
+ * out (a chain of its own, +0.0 when nothing is left), d = w_r * p_r, num = floor - q.  out_price = NaN where the winner's v
+ * is NaN, 0.0 where !(num > 0), 0.0 where !(d > 0) (the bid does not hold the rank), else min(b, num / d).  out_ecpm = e.
+ * The tail reads eCPM 0.0 and price 0.0.  With weights 1.0 * onehot(rank_task) ids, slots, eCPMs and prices are
+ * amdrec_select_topk_auction's bit for bit.
+ * One launch, no workspace; every argument is validated before the first HIP call; n_users <= 0 returns OK without looking
+ * at a pointer. */
+int amdrec_select_topk_value(const float* logits /*[n_tasks][ld]*/, int64_t ld_logits, int n_tasks,
+                             const int64_t* cand_ids /*[n_users][k_c]*/, const int64_t* cand_pos /*[n_users][k_c]*/,
+                             int64_t n_users, int k_c, int top_k, const float* weights /*[n_users][n_tasks]*/,
+                             const int64_t* group_of /*[n_group_rows]; NULL without a cap*/, int64_t n_group_rows,
+                             int max_per_group /*0: no cap*/, int64_t* out_ids /*[n_users][top_k]*/,
+                             float* out_scores /*[n_tasks][n_users][top_k]*/, int32_t* out_slots /*or NULL*/,
+                             float* out_values /*[n_users][top_k]*/, void* stream);
+int amdrec_select_topk_value_auction(const float* logits /*[n_tasks][ld]*/, int64_t ld_logits, int n_tasks, int rank_task,
+                                     const int64_t* cand_ids /*[n_users][k_c]*/, const int64_t* cand_pos /*[n_users][k_c]*/,
+                                     int64_t n_users, int k_c, int top_k, const float* weights /*[n_users][n_tasks]*/,
+                                     const float* bid_of /*[n_bid_rows], by cand_pos*/, int64_t n_bid_rows,
+                                     const float* reserve /*[n_users] or NULL*/,
+                                     const int64_t* group_of /*[n_group_rows]; NULL without a cap*/, int64_t n_group_rows,
+                                     int max_per_group /*0: no cap*/, int64_t* out_ids /*[n_users][top_k]*/,
+                                     float* out_scores /*[n_tasks][n_users][top_k]*/, int32_t* out_slots /*or NULL*/,
+                                     float* out_values /*[n_users][top_k]*/, float* out_ecpm /*[n_users][top_k]*/,
+                                     float* out_price /*[n_users][top_k]*/, void* stream);
 
 #ifdef __cplusplus
 }

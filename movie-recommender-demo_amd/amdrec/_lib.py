@@ -127,6 +127,13 @@ _SIGNATURES = {
     # max_per_group), its outputs + (out_values, stream)
     "amdrec_select_topk_diverse": [_fp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _fp, _i64, _i64, _i32, C.c_float, _i32,
                                    _vp, _i64, _i32, _vp, _fp, _vp, _fp, _vp],
+    # (logits, ld, n_tasks, cand_ids, cand_pos, n_users, k_c, top_k, weights, group_of, n_group_rows, max_per_group, out_ids,
+    # out_scores, out_slots, out_values, stream)
+    "amdrec_select_topk_value": [_fp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _fp, _vp, _i64, _i32, _vp, _fp, _vp, _fp, _vp],
+    # the same with rank_task behind n_tasks, (bid_of, n_bid_rows, reserve) behind weights and (out_ecpm, out_price) behind
+    # out_values
+    "amdrec_select_topk_value_auction": [_fp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _fp, _fp, _i64, _fp, _vp, _i64, _i32,
+                                         _vp, _fp, _vp, _fp, _fp, _fp, _vp],
     "amdrec_group_cap_compact": [_vp, _fp, _i64, _i32, _vp, _i64, _i32, _i32, C.c_float, _vp, _fp, _vp],
 }
 _RESTYPE = {"amdrec_last_error": C.c_char_p}

@@ -28,7 +28,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import _lib, boost as _boost, auction as _auction, diversity as _diversity, eligible as _eligible, exclude as _exclude, \
+from . import _lib, boost as _boost, auction as _auction, diversity as _diversity, value as _value, eligible as _eligible, exclude as _exclude, \
     rows_edit as _rows_edit
 from .index import FAISSIndex
 from .ranker import TransformerRanker
@@ -269,7 +269,7 @@ class AdRecommenderInference:
                                               require_any=masks[1], max_per_group=max_per_group, boost_weight=boost_weight)
 
     def _stage2(self, uc, un, cand_pos, top_k, check_indices, ids_are_positions=False, mark=None, out=None,
-                excluded=False, heads=None, max_per_group=None, auction=None, diversity=None):
+                excluded=False, heads=None, max_per_group=None, auction=None, diversity=None, head_weights=None):
         """Ranker + selection over stage 1's positions ``cand_pos`` [B, stage1_k].  A negative position is a slot the search
         could not fill: no candidate.  The ranker still computes a (finite, unspecified) logit for it - every gather clamps
         the row - and the selection, which is handed the positions, ranks it after every real candidate: it is reported only
@@ -282,7 +282,10 @@ class AdRecommenderInference:
         over the index's bids (amdrec.auction has the rule), the cap inside it, and the result gains ``ecpm`` / ``prices``.
         ``diversity`` (validated by the caller, None: the selections above): ``(lam, pool)`` - the selection is
         amdrec_select_topk_diverse over the index's rows as they are at this call (amdrec.diversity has the rule), the cap
-        inside it, and the result gains ``diversity_values``."""
+        inside it, and the result gains ``diversity_values``.
+        ``head_weights`` (validated by the caller, None: the selections above): amdrec.value.check_head_weights' result or a
+        static [B, n_tasks] buffer - the selection is amdrec_select_topk_value (``_value_auction`` with ``auction``), the cap
+        inside it, every head on every candidate whatever ``heads_mode`` says, and the result gains ``values``."""
         lib = _lib.load()
         B, stage1_k = cand_pos.shape
         rk = self.transformer_ranker
@@ -292,7 +295,7 @@ class AdRecommenderInference:
         # selection on that one logit row, the other heads on the winners.  A ranker or shape that cannot run it takes the
         # all-heads path below: the same results
         mode = self.heads_mode if heads is None else heads
-        ctr_first = mode != "all" and self.heads_mode_effective(mode)[0] == "ctr_first" and \
+        ctr_first = head_weights is None and mode != "all" and self.heads_mode_effective(mode)[0] == "ctr_first" and \
             rk.ctr_first_ready(self.ad_features, B * stage1_k, B * top_k)
         if ctr_first:
             tasks = rk._packed.tasks
@@ -323,7 +326,32 @@ class AdRecommenderInference:
                                             cand_pos.numel(), _lib.stream_ptr(uc.device)))
         # mid / tail: what an entry takes between top_k and out_ids / behind out_slots
         mid, ecpm, prices, values = (), None, None, None
-        if auction is not None:
+        if head_weights is not None:
+            # the value entries: the weights, (the bids and the reserve,) the groups in the middle, the values (and eCPMs and
+            # prices) behind the slots; no rank_task in the plain one.  The cap (0: none) rides in the same launch
+            w = _value.weights_tensor(head_weights, B, uc.device)
+            groups = (_lib.ptr(idx._groups) if max_per_group else None, idx._n if max_per_group else 0, max_per_group or 0)
+            values = out[2] if out is not None else torch.empty((B, top_k), dtype=torch.float32, device=uc.device)
+            if auction is not None:
+                reserve = _auction.reserve_tensor(_auction.check_reserve(auction[0], B), B, uc.device)
+                if out is not None:
+                    ecpm, prices = out[3], out[4]
+                else:
+                    ecpm = torch.empty((B, top_k), dtype=torch.float32, device=uc.device)
+                    prices = torch.empty((B, top_k), dtype=torch.float32, device=uc.device)
+                if B:
+                    _lib.check(lib.amdrec_select_topk_value_auction(
+                        _lib.ptr(logits), logits.stride(0), len(tasks), tasks.index("ctr"), _lib.ptr(cand_ids), _lib.ptr(cand_pos),
+                        B, stage1_k, top_k, _lib.ptr(w), _lib.ptr(idx._bids), idx._n, _lib.ptr(reserve), *groups,
+                        _lib.ptr(ad_ids), _lib.ptr(scores), None, _lib.ptr(values), _lib.ptr(ecpm), _lib.ptr(prices),
+                        _lib.stream_ptr(uc.device)))
+            elif B:
+                _lib.check(lib.amdrec_select_topk_value(
+                    _lib.ptr(logits), logits.stride(0), len(tasks), _lib.ptr(cand_ids), _lib.ptr(cand_pos), B, stage1_k, top_k,
+                    _lib.ptr(w), *groups, _lib.ptr(ad_ids), _lib.ptr(scores), None, _lib.ptr(values),
+                    _lib.stream_ptr(uc.device)))
+            select = None
+        elif auction is not None:
             # the auction entry: the selection's arguments with the bids, the reserve and the groups in the middle and two
             # outputs more; the cap (0: none) rides in the same launch
             select = lib.amdrec_select_topk_auction
@@ -349,7 +377,9 @@ class AdRecommenderInference:
             select, tail = lib.amdrec_select_topk, ()
         else:                                    # the same arguments, then the groups: the cap runs inside the selection
             select, tail = lib.amdrec_select_topk_capped, (_lib.ptr(idx._groups), idx._n, max_per_group)
-        if B and ctr_first:
+        if select is None:
+            pass                                 # (launched above)
+        elif B and ctr_first:
             # the selection as ever, on the one logit row: ad ids, plane 0 of scores and the winning slots; then the winners'
             # other tasks into planes 1 ..
             slots = torch.empty((B, top_k), dtype=torch.int32, device=uc.device)
@@ -367,6 +397,8 @@ class AdRecommenderInference:
             res["ecpm"], res["prices"] = ecpm, prices
         if diversity is not None:
             res["diversity_values"] = values
+        if head_weights is not None:
+            res["values"] = values
         return res
 
     @torch.no_grad()
@@ -376,7 +408,7 @@ class AdRecommenderInference:
                          require_all: Optional[torch.Tensor] = None, require_any: Optional[torch.Tensor] = None,
                          max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                          rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                         diversity_pool: int = 64, stage1_boost=None):
+                         diversity_pool: int = 64, stage1_boost=None, head_weights=None):
         """[B,6] / [B,13] device tensors -> dict of device tensors, no host synchronisation:
         ad_ids [B,top_k] int64, scores [3,B,top_k] float32 (sigmoid of the logits), candidate_ids
         [B,stage1_k], candidate_scores [B,stage1_k], logits [3, B*stage1_k].  candidate_scores are the index's own
@@ -425,6 +457,17 @@ class AdRecommenderInference:
         the probed lists); candidate_scores are the boosted scores.  Stage 2 never reads them and is unchanged.  On an index
         without boosts, a non-finite number: ValueError; on Flat with masks, on IVF without ``list_boosts``, on IVFPQ:
         NotImplementedError.
+        ``head_weights`` (None: the CTR order, the launches of ever): stage 2 orders a user's candidates by the blend
+        sum_t w_t x p_t of EVERY head's probability (amdrec.value has the rule), inside the selection launch: a dict by task
+        name (a missing task is 0), a sequence of ``len(tasks)`` numbers in the ranker's task order, or a device float32
+        [B, n_tasks] tensor of per-user weights (its values are the caller's).  ``max_per_group`` applies in that order; with
+        ``rank_by="ecpm"`` the CTR term is bid x pCTR, ``reserve`` is compared with the value and ``prices`` is the smallest
+        bid that keeps the rank under the blend.  The dict gains ``values``, float32 [B, top_k] (0.0 in the unfilled tail).
+        The blend needs every head on every candidate: an instance whose ``heads_mode`` is "ctr_first" runs such a call on
+        all heads (``logit_tasks`` says so).  One-hot CTR weights order by pCTR, which ties where sigmoids saturate: not
+        the logit order of the plain call in general.  Bools, non-numbers, a tensor of another dtype or device: TypeError;
+        non-finite or all-zero scalars, an unknown task, a wrong length or shape, under "ecpm" a scalar CTR weight <= 0,
+        together with ``diversity`` or an explicit ``heads="ctr_first"``: ValueError.
         ``check_indices``: an out-of-range user index or ad-table row raises IndexError; an unfilled slot does not."""
         if heads is not None:
             self._check_heads(heads)
@@ -432,6 +475,8 @@ class AdRecommenderInference:
         cap, cap1 = self._check_caps(max_per_group, stage1_max_per_group)          # (before the library is touched)
         auction = self._check_auction(rank_by, reserve)
         div = self._check_diversity(diversity, diversity_pool, top_k, auction)
+        hw = self._check_head_weights(head_weights, None if user_categorical is None else user_categorical.shape[0], auction,
+                                      diversity, heads)
         uc = _lib.require_gpu(user_categorical, "user_categorical")
         un = _lib.require_gpu(user_numerical, "user_numerical")
         excluded = exclude_ad_ids is not None and exclude_ad_ids.shape[-1] > 0
@@ -443,7 +488,7 @@ class AdRecommenderInference:
                                                  (require_all, require_any), cap1, stage1_boost)
             # (excluded: "a slot can be unfilled" - true after a filtered stage 1 as well)
             out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded or masked or cap1 is not None,
-                               heads=heads, max_per_group=cap, auction=auction, diversity=div)
+                               heads=heads, max_per_group=cap, auction=auction, diversity=div, head_weights=hw)
         out["candidate_scores"] = cand_scores
         return out
 
@@ -451,7 +496,7 @@ class AdRecommenderInference:
                 max_exclude: int = 0, eligibility: bool = False, max_per_group: Optional[int] = None,
                 stage1_max_per_group: Optional[int] = None, rank_by: Optional[str] = None,
                 reserve: bool = False, diversity: Optional[float] = None,
-                diversity_pool: int = 64, stage1_boost: bool = False) -> "GraphedRecommender":
+                diversity_pool: int = 64, stage1_boost: bool = False, head_weights: bool = False) -> "GraphedRecommender":
         """Capture one recommend_device call for a fixed batch shape into a HIP graph (the ~40 kernel
         launches of a request are host-launch-bound at small batch: 1.76 ms eager at B = 1) and return a
         replayer.  Weights, index and ad table must not change afterwards.  ``max_exclude`` > 0: the graph also holds a
@@ -465,9 +510,12 @@ class AdRecommenderInference:
         ``reserve`` argument fills.  ``diversity`` / ``diversity_pool`` (recommend_device): scalars fixed at capture, like
         ``max_per_group``; the rows are those of capture time.  ``stage1_boost=True``: the graph holds a static
         [batch_size] float32 weight buffer and runs the boosted search (the replayer's ``stage1_boost`` fills it, zeros
-        without one; the boosts are those of capture time); False captures the graph as ever."""
+        without one; the boosts are those of capture time); False captures the graph as ever.  ``head_weights=True``: the
+        graph holds a static [batch_size, n_tasks] float32 weight buffer and runs the value selection of recommend_device
+        (the replayer's ``head_weights`` fills it; until then, and without one, it holds 1.0 for the CTR head and 0.0 for the
+        others); False captures the graph as ever."""
         return GraphedRecommender(self, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group,
-                                  stage1_max_per_group, rank_by, reserve, diversity, diversity_pool, stage1_boost)
+                                  stage1_max_per_group, rank_by, reserve, diversity, diversity_pool, stage1_boost, head_weights)
 
     # -- live corpus: ads leave and enter without a rebuild of the index or of the ranker's per-ad caches ------------------
     def remove_ads(self, ad_ids) -> int:
@@ -531,13 +579,14 @@ class AdRecommenderInference:
                       return_scores: bool = True, exclude_ad_ids=None, require_all: int = 0, require_any: int = 0,
                       max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                       rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                      diversity_pool: int = 64, stage1_boost=None) -> dict:
+                      diversity_pool: int = 64, stage1_boost=None, head_weights=None) -> dict:
         """inference.py:199-288.  ``exclude_ad_ids``: the ad ids this user must not be shown (a sequence of integers).
         ``require_all`` / ``require_any``: this request's eligibility masks (64-bit integers; 0 and 0: no constraint, the
         plain search).  ``max_per_group`` / ``stage1_max_per_group``: the per-group caps of recommend_device.  ``rank_by`` /
         ``reserve``: the auction of recommend_device (the dict gains ``ecpm`` and ``prices``).  ``diversity`` /
         ``diversity_pool``: its diversified selection (the dict gains ``diversity_values``).  ``stage1_boost``: this request's
-        weight on the per-ad boosts in stage 1 (a number; recommend_device).  Fewer than
+        weight on the per-ad boosts in stage 1 (a number; recommend_device).  ``head_weights``: the value ranking of
+        recommend_device, a dict by task name or a sequence of numbers (the dict gains ``values``).  Fewer than
         ``top_k`` real candidates: as batch_recommend."""
         masked = bool(require_all) or bool(require_any)
         return self.batch_recommend([user_data], top_k=top_k, stage1_k=stage1_k, return_scores=return_scores,
@@ -545,13 +594,14 @@ class AdRecommenderInference:
                                     require_all=[require_all] if masked else None,
                                     require_any=[require_any] if masked else None, max_per_group=max_per_group,
                                     stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve,
-                                    diversity=diversity, diversity_pool=diversity_pool, stage1_boost=stage1_boost)[0]
+                                    diversity=diversity, diversity_pool=diversity_pool, stage1_boost=stage1_boost,
+                                    head_weights=head_weights)[0]
 
     def batch_recommend(self, user_data_list: list, top_k: int = 10, stage1_k: int = 500,
                         return_scores: bool = True, exclude_ad_ids=None, require_all=None, require_any=None,
                         max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                         rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                        diversity_pool: int = 64, stage1_boost=None) -> list:
+                        diversity_pool: int = 64, stage1_boost=None, head_weights=None) -> list:
         """inference.py:290-331 - but one device pass for the whole list instead of a serial loop.
         ``timing`` reports the batch's stage times divided by the number of users.  ``exclude_ad_ids``: one sequence of
         ad ids per user (recommend_device has the meaning); the padded block travels in the input staging block.
@@ -566,10 +616,14 @@ class AdRecommenderInference:
         in the same result block: no copy and no synchronisation more.  ``diversity`` / ``diversity_pool``: the diversified
         selection of recommend_device; every user's dict gains a ``"diversity_values"`` list of length ``top_k``, in the same
         block.  ``stage1_boost``: the stage-1 boost weight of recommend_device, one number for every user or a sequence of
-        one per user; the weights travel in the input staging block: no copy and no synchronisation more."""
+        one per user; the weights travel in the input staging block: no copy and no synchronisation more.
+        ``head_weights``: the value ranking of recommend_device, for every user of the list; every user's dict gains a
+        ``"values"`` list of length ``top_k``, in the same result block."""
         self.faiss_index._check_boost(stage1_boost, require_all is not None or require_any is not None)
         self._check_caps(max_per_group, stage1_max_per_group)
-        self._check_diversity(diversity, diversity_pool, top_k, self._check_auction(rank_by, reserve))
+        auction = self._check_auction(rank_by, reserve)
+        self._check_diversity(diversity, diversity_pool, top_k, auction)
+        self._check_head_weights(head_weights, len(user_data_list) or None, auction, diversity)
         if not user_data_list:
             return []
         n = len(user_data_list)
@@ -584,7 +638,7 @@ class AdRecommenderInference:
             return self.recommend_tensors(uc, un, top_k, stage1_k, return_scores, _encoded=True, _exclude_dev=excl,
                                           _masks_dev=masks, _boost_dev=wts, max_per_group=max_per_group,
                                           stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve,
-                                          diversity=diversity, diversity_pool=diversity_pool)
+                                          diversity=diversity, diversity_pool=diversity_pool, head_weights=head_weights)
 
     def _check_caps(self, max_per_group, stage1_max_per_group):
         """The two cap arguments -> (cap or None, stage-1 cap or None); refusals before the library is touched."""
@@ -601,6 +655,14 @@ class AdRecommenderInference:
         """The ``diversity`` / ``diversity_pool`` arguments -> None (today's selection) or ``(lam, pool)``; refusals before the
         library is touched (amdrec.diversity.check_diversity).  ``auction``: _check_auction's result."""
         return _diversity.check_index_diversity(self.faiss_index, diversity, diversity_pool, top_k, auction is not None)
+
+    def _check_head_weights(self, head_weights, n_users, auction, diversity, heads=None):
+        """The ``head_weights`` argument -> None (today's selections) or amdrec.value.check_head_weights' result; refusals before
+        the library is touched.  ``auction``: _check_auction's result; ``diversity``: the caller's argument."""
+        if head_weights is None:
+            return None
+        return _value.check_head_weights(head_weights, self.transformer_ranker.prediction_heads.keys(), n_users,
+                                         auction is not None, diversity is not None, heads)
 
     def _host_masks(self, require_all, require_any, n: int) -> Optional[np.ndarray]:
         """The two mask arguments of the reference-API calls -> int64 [2, n] on the host (None: neither given)."""
@@ -659,7 +721,7 @@ class AdRecommenderInference:
     def recommend_tensors(self, user_categorical, user_numerical, top_k=10, stage1_k=500, return_scores=True,
                           _encoded=False, exclude_ad_ids=None, _exclude_dev=None, require_all=None, require_any=None,
                           _masks_dev=None, max_per_group=None, stage1_max_per_group=None, rank_by=None, reserve=None,
-                          diversity=None, diversity_pool=64, stage1_boost=None, _boost_dev=None):
+                          diversity=None, diversity_pool=64, stage1_boost=None, _boost_dev=None, head_weights=None):
         """Tensor-level entry (cf. TwoStageRetriever.retrieve_and_rank, faiss_retrieval.py:283-369); result dicts follow
         inference.py:272-288.  ONE host synchronisation per call (round 3 had four: the tower's index flag, the stage-1
         timing sync, the ranker's index flag, the result copy - each exposing the launch work queued behind it): indices
@@ -672,12 +734,15 @@ class AdRecommenderInference:
         ``stage1_max_per_group``: the per-group caps of recommend_device.  ``rank_by`` / ``reserve``: its auction; ``ecpm`` and
         ``prices`` ride in the same result block and copy.  ``diversity`` / ``diversity_pool``: its diversified selection;
         ``diversity_values`` rides there too.  ``stage1_boost``: the users' stage-1 boost weights as in batch_recommend,
-        shipped through pinned memory like the masks."""
+        shipped through pinned memory like the masks.  ``head_weights``: its value ranking; ``values`` rides in the result block
+        too, behind ``ecpm`` and ``prices`` where the auction runs: still one copy, one synchronisation."""
         if _boost_dev is None:
             self.faiss_index._check_boost(stage1_boost, require_all is not None or require_any is not None)
         cap, cap1 = self._check_caps(max_per_group, stage1_max_per_group)
         auction = self._check_auction(rank_by, reserve)
         div = self._check_diversity(diversity, diversity_pool, top_k, auction)
+        head_w = self._check_head_weights(head_weights, None if user_categorical is None else user_categorical.shape[0], auction,
+                                      diversity)
         t0 = time.time()
         with _lib.GATE.serving():
             # host side first, beside other threads' enqueues: the inputs' copies to the device (torch ops: they use no
@@ -722,16 +787,20 @@ class AdRecommenderInference:
                 ids_b, sc_b = n * top_k * 8, len(tasks) * n * top_k * 4
                 au_b = 0 if auction is None else n * top_k * 4                       # ecpm, then prices, behind the scores
                 dv_b = 0 if div is None else n * top_k * 4                           # diversity_values, there instead (never both)
-                blk = torch.empty(ids_b + sc_b + 2 * au_b + dv_b + 8, dtype=torch.uint8, device=dev)
+                va_b = 0 if head_w is None else n * top_k * 4                            # values, behind all of them (never with dv_b)
+                end_b = ids_b + sc_b + 2 * au_b + dv_b + va_b
+                blk = torch.empty(end_b + 8, dtype=torch.uint8, device=dev)
                 ad_ids = blk[:ids_b].view(torch.int64).view(n, top_k)
                 scores = blk[ids_b:ids_b + sc_b].view(torch.float32).view(len(tasks), n, top_k)
                 outs = (ad_ids, scores)
+                if head_w is not None:                                               # (_stage2 takes out[2] = values, then ecpm, prices)
+                    outs += (blk[end_b - va_b:end_b].view(torch.float32).view(n, top_k),)
                 if auction is not None:
                     outs += tuple(blk[ids_b + sc_b + i * au_b:ids_b + sc_b + (i + 1) * au_b].view(torch.float32).view(n, top_k)
                                   for i in range(2))
                 if div is not None:
                     outs += (blk[ids_b + sc_b:ids_b + sc_b + dv_b].view(torch.float32).view(n, top_k),)
-                verdict = blk[ids_b + sc_b + 2 * au_b + dv_b:].view(torch.int32)     # [2]: nonzero = an index out of range
+                verdict = blk[end_b:].view(torch.int32)                              # [2]: nonzero = an index out of range
                 trusted = _encoded and self.preprocessor is not None and self._encoder_fits()
                 if trusted:
                     verdict.zero_()
@@ -749,7 +818,7 @@ class AdRecommenderInference:
                 ev[1].record(st)
                 out = self._stage2(uc, un, cand_pos, top_k, False, out=outs,
                                    excluded=excl is not None or masks is not None or cap1 is not None, max_per_group=cap,
-                                   auction=auction, diversity=div)
+                                   auction=auction, diversity=div, head_weights=head_w)
                 assert list(out["tasks"]) == tasks
                 host, done = self._staging(blk.numel(), "out")
                 host.copy_(blk, non_blocking=True)
@@ -757,12 +826,13 @@ class AdRecommenderInference:
                 done.record(st)
             ev[2].synchronize()
             hv = host.numpy()
-            if int(hv[ids_b + sc_b + 2 * au_b + dv_b:].view(np.int32)[0]):
+            if int(hv[end_b:].view(np.int32)[0]):
                 raise IndexError("index out of range in self")                    # torch.nn.Embedding's message
             ids = hv[:ids_b].view(np.int64).reshape(n, top_k).tolist()
             sc = hv[ids_b:ids_b + sc_b].view(np.float32).reshape(len(tasks), n, top_k).tolist() if return_scores else None
             au = None if auction is None else hv[ids_b + sc_b:ids_b + sc_b + 2 * au_b].view(np.float32).reshape(2, n, top_k).tolist()
             dv = None if div is None else hv[ids_b + sc_b:ids_b + sc_b + dv_b].view(np.float32).reshape(n, top_k).tolist()
+            va = None if head_w is None else hv[end_b - va_b:end_b].view(np.float32).reshape(n, top_k).tolist()
             t2 = time.time()
             # stage 1 = its GPU time (tower + search, as the reference brackets them); stage 2 = the rest of the call's wall time
             # (ranker, selection, the copy back and the list conversion: what the reference's second bracket holds)
@@ -778,6 +848,8 @@ class AdRecommenderInference:
                     r["ecpm"], r["prices"] = au[0][b], au[1][b]
                 if dv is not None:
                     r["diversity_values"] = dv[b]
+                if va is not None:
+                    r["values"] = va[b]
                 res.append(r)
             return res
 
@@ -804,7 +876,7 @@ class TwoStageRetriever:
                           stage2_k: int = 10, ad_features_lookup=None, exclude_ad_ids=None,
                           max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                           rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                          diversity_pool: int = 64, stage1_boost=None):
+                          diversity_pool: int = 64, stage1_boost=None, head_weights=None):
         """``exclude_ad_ids``: the ad ids the (first) user must not be shown, a sequence of integers.  With a table, the two
         lists have length ``stage2_k``; a user with fewer real candidates gets -1 / 0.0 in the tail (batch_recommend).
         ``stage1_max_per_group`` / ``max_per_group``: the per-group caps on the candidates and on the ranked result
@@ -813,11 +885,17 @@ class TwoStageRetriever:
         probabilities, in eCPM order); without a table they are checked and change nothing.  ``diversity`` /
         ``diversity_pool``: the diversified selection of recommend_device for the ranked result (ids and CTR probabilities, in
         pick order); without a table they are checked and change nothing.  ``stage1_boost``: the (first) user's weight on the
-        per-ad boosts in stage 1, a number (recommend_device), with or without a table."""
+        per-ad boosts in stage 1, a number (recommend_device), with or without a table.  ``head_weights``: the value ranking
+        of recommend_device for the ranked result (ids and CTR probabilities, in value order); without a table it is checked
+        and changes nothing."""
         idx = self.faiss_index
         idx._check_boost(stage1_boost)
         cap, cap1 = idx._check_group_cap(max_per_group), idx._check_group_cap(stage1_max_per_group, "stage1_max_per_group")
-        _diversity.check_index_diversity(idx, diversity, diversity_pool, stage2_k, idx._check_auction(rank_by, reserve)[0])
+        auction = idx._check_auction(rank_by, reserve)[0]
+        _diversity.check_index_diversity(idx, diversity, diversity_pool, stage2_k, auction)
+        if head_weights is not None:
+            _value.check_head_weights(head_weights, self.transformer_ranker.prediction_heads.keys(), None, auction,
+                                      diversity is not None)
         uc = user_categorical.to(self.device)
         un = user_numerical.to(self.device, dtype=torch.float32)
         excl = None if exclude_ad_ids is None else [exclude_ad_ids]
@@ -843,7 +921,9 @@ class TwoStageRetriever:
         r = rec.recommend_tensors(uc[:1], un[:1], stage2_k, stage1_k,             # one synchronisation, indices validated
                                         exclude_ad_ids=excl, max_per_group=cap, stage1_max_per_group=cap1,
                                         rank_by=rank_by, reserve=reserve, diversity=diversity,
-                                        diversity_pool=diversity_pool, stage1_boost=stage1_boost)[0]
+                                        diversity_pool=diversity_pool, stage1_boost=stage1_boost,
+                                        head_weights=head_weights if not isinstance(head_weights, torch.Tensor)
+                                        else head_weights[:1])[0]
         return r["ad_ids"], r["scores"]["ctr"]                                    # :359-369 (ids, ctr probabilities)
 
 
@@ -855,15 +935,16 @@ class GraphedRecommender:
     def __init__(self, rec: AdRecommenderInference, batch_size: int, top_k: int, stage1_k: int, warmup: int = 2,
                  max_exclude: int = 0, eligibility: bool = False, max_per_group: Optional[int] = None,
                  stage1_max_per_group: Optional[int] = None, rank_by: Optional[str] = None, reserve: bool = False,
-                 diversity: Optional[float] = None, diversity_pool: int = 64, stage1_boost: bool = False):
+                 diversity: Optional[float] = None, diversity_pool: int = 64, stage1_boost: bool = False,
+                 head_weights: bool = False):
         # the capture gate first: while another thread captures, the runtime is in its global capture mode, and the
         # allocations and fills of the static buffers below would already disturb it.  Refused before the device is touched
         with _lib.GATE.capturing():
             self._init(rec, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group, stage1_max_per_group,
-                       rank_by, reserve, diversity, diversity_pool, stage1_boost)
+                       rank_by, reserve, diversity, diversity_pool, stage1_boost, head_weights)
 
     def _init(self, rec, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group, stage1_max_per_group,
-              rank_by, reserve, diversity, diversity_pool, stage1_boost):
+              rank_by, reserve, diversity, diversity_pool, stage1_boost, head_weights=False):
         self.rec, self.batch_size, self.top_k, self.stage1_k = rec, batch_size, top_k, stage1_k
         # the per-group caps: scalars fixed at capture (the group keys are those of capture time, pinned below)
         self.max_per_group, self.stage1_max_per_group = rec._check_caps(max_per_group, stage1_max_per_group)
@@ -877,6 +958,13 @@ class GraphedRecommender:
         if rec._check_diversity(diversity, diversity_pool, top_k, () if auction else None) is not None:
             caps.update(diversity=diversity, diversity_pool=diversity_pool)
         self._reserve = None
+        # value ranking: head_weights=True gives the graph a static [batch_size, n_tasks] weight buffer (1.0 for the CTR head
+        # until the replayer fills it) and the value selection; the refusals are recommend_device's
+        self._head_w, self._auction = None, auction
+        if head_weights:
+            self._tasks = list(rec.transformer_ranker.prediction_heads.keys())
+            self._head_default = tuple(1.0 if t == "ctr" else 0.0 for t in self._tasks)
+            _value.check_head_weights(self._head_default, self._tasks, None, auction, diversity is not None)
         self.max_exclude = int(max_exclude)
         _exclude.check_exclude(stage1_k, self.max_exclude)
         dev = rec.ad_features.device
@@ -894,6 +982,9 @@ class GraphedRecommender:
             if reserve:
                 self._reserve = torch.zeros((batch_size,), dtype=torch.float32, device=dev)
             caps.update(rank_by=rank_by, reserve=self._reserve)
+        if head_weights:
+            self._head_w = _value.weights_tensor(self._head_default, batch_size, dev)
+            caps.update(head_weights=self._head_w)
         # static stage-1 boost weights (zeros = the plain search's positions); None: the graph runs the plain search
         self._boost_w = torch.zeros((batch_size,), dtype=torch.float32, device=dev) if stage1_boost else None
         if stage1_boost:
@@ -950,17 +1041,18 @@ class GraphedRecommender:
 
     def __call__(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor,
                  exclude: Optional[torch.Tensor] = None, require_all: Optional[torch.Tensor] = None,
-                 require_any: Optional[torch.Tensor] = None, reserve=None, stage1_boost=None):
+                 require_any: Optional[torch.Tensor] = None, reserve=None, stage1_boost=None, head_weights=None):
         """One replay - arguments and result: ``_replay`` - inside ``replaying()`` and the serving scope: a replay that
         overlaps another thread's replay of this object, or another thread's capture, raises AmdrecError before it has
         touched the static buffers."""
         with self.replaying(), _lib.GATE.serving():
-            return self._replay(user_categorical, user_numerical, exclude, require_all, require_any, reserve, stage1_boost)
+            return self._replay(user_categorical, user_numerical, exclude, require_all, require_any, reserve, stage1_boost,
+                                head_weights)
 
     @torch.no_grad()
     def _replay(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor,
                 exclude: Optional[torch.Tensor] = None, require_all: Optional[torch.Tensor] = None,
-                require_any: Optional[torch.Tensor] = None, reserve=None, stage1_boost=None):
+                require_any: Optional[torch.Tensor] = None, reserve=None, stage1_boost=None, head_weights=None):
         """Device tensors [batch_size, ...] -> the same dict as recommend_device (static output buffers,
         overwritten by the next call).  ``exclude``: device int64 [batch_size, E <= max_exclude] ad ids (negative =
         padding), copied into the graph's block; None = nothing excluded (the block is filled with -1).  ``require_all`` /
@@ -968,7 +1060,17 @@ class GraphedRecommender:
         constraint); a graph captured without ``eligibility`` raises ValueError for them.  ``reserve``: a float >= 0 or a
         device float32 [batch_size], copied into the graph's reserve buffer (None = zeros); a graph captured without
         ``reserve=True`` raises ValueError for it.  ``stage1_boost``: a number or a device float32 [batch_size], copied into
-        the graph's weight buffer (None = zeros); a graph captured without ``stage1_boost=True`` raises ValueError for it."""
+        the graph's weight buffer (None = zeros); a graph captured without ``stage1_boost=True`` raises ValueError for it.
+        ``head_weights``: a dict, a sequence or a device float32 [batch_size, n_tasks] as recommend_device takes them, written
+        into the graph's weight buffer (None = 1.0 for the CTR head, 0.0 for the others); a graph captured without
+        ``head_weights=True`` raises ValueError for it."""
+        if head_weights is not None:
+            if self._head_w is None:
+                raise ValueError("captured without head_weights=True: this graph ranks by the CTR head and takes no weights")
+            head_weights = _value.check_head_weights(head_weights, self._tasks, self.batch_size, self._auction)
+        if self._head_w is not None:
+            _value.weights_tensor(self._head_default if head_weights is None else head_weights, self.batch_size,
+                                  self._head_w.device, out=self._head_w)
         if stage1_boost is not None:
             if self._boost_w is None:
                 raise ValueError("captured without stage1_boost=True: this graph runs the plain search and takes no boost weight")

@@ -272,7 +272,8 @@ class ShardedRecommender:
 
     @torch.no_grad()
     def recommend_device(self, user_categorical, user_numerical, top_k: int = 10, stage1_k: int = 500,
-                         verify: bool = True, max_per_group=None, stage1_max_per_group=None, rank_by=None, reserve=None):
+                         verify: bool = True, max_per_group=None, stage1_max_per_group=None, rank_by=None, reserve=None,
+                         head_weights=None):
         """Global user batch (identical on every rank) -> this rank's users' results:
         dict(ad_ids [nq,top_k], scores [3,nq,top_k], user_offset q0, candidate_ids, candidate_scores).
         With short lists and ``verify`` (default) the proof of exactness is checked on the host before returning (one tiny
@@ -281,13 +282,16 @@ class ShardedRecommender:
         ``max_per_group`` / ``stage1_max_per_group`` (AdRecommenderInference.recommend_device): not available on the sharded
         path - a shard holds the group keys of its own rows only, the merged candidates' positions are global - and raise
         NotImplementedError.  So do ``rank_by="ecpm"`` and any ``reserve`` (auction ranking): a shard holds the bids of its
-        own rows only."""
+        own rows only.  So does ``head_weights`` (value ranking), in step with them."""
         if max_per_group is not None or stage1_max_per_group is not None:
             raise NotImplementedError("per-group caps (max_per_group / stage1_max_per_group) are not available on the sharded "
                                       "serving path (DESIGN.md, 'Per-advertiser caps': out of scope)")
         if rank_by == "ecpm" or reserve is not None:
             raise NotImplementedError('auction ranking (rank_by="ecpm" / reserve) is not available on the sharded serving path '
                                       "(DESIGN.md, 'Auction ranking': out of scope)")
+        if head_weights is not None:
+            raise NotImplementedError("value ranking (head_weights) is not available on the sharded serving path "
+                                      "(DESIGN.md, 'Value ranking': out of scope)")
         kq = self.list_k(stage1_k)
         if not (kq < stage1_k and verify):
             return self._step(user_categorical, user_numerical, top_k, stage1_k, kq)
@@ -430,11 +434,12 @@ class ShardedRecommender:
 
     @torch.no_grad()
     def recommend_all(self, user_categorical, user_numerical, top_k: int = 10, stage1_k: int = 500,
-                      max_per_group=None, stage1_max_per_group=None, rank_by=None, reserve=None):
+                      max_per_group=None, stage1_max_per_group=None, rank_by=None, reserve=None, head_weights=None):
         """Same, then all-gather the final [nq, top_k] results so every rank holds all users
         (~60 KB at 512 x 10).  Requires n_users % world == 0."""
         out = self.recommend_device(user_categorical, user_numerical, top_k, stage1_k, max_per_group=max_per_group,
-                                    stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve)
+                                    stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve,
+                                    head_weights=head_weights)
         B = user_categorical.shape[0]
         if B % self.world:
             raise ValueError("recommend_all needs n_users divisible by the world size")

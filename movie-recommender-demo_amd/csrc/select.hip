@@ -7,7 +7,12 @@
 // Order everywhere: (key desc, candidate slot asc), a NaN score last, a slot that is no candidate never.
 // amdrec_select_topk_diverse (amdrec/diversity.py) builds on the same key function, cap helpers and winner write-out with a
 // kernel of its own further down: the plain order gives it a pool, which it re-orders by similarity-discounted relevance.
+// amdrec_select_topk_value / _value_auction (amdrec/value.py has the rule) are the frame's VALUE switch: the key is the
+// weighted blend of every task's probability, the winner write-out reports it, and the auction solves its price from it.
+// Their arguments ride behind SelectArgs in a struct of their own, so the instantiations without the switch keep their
+// kernel arguments - and their instruction streams - as they were.
 #include <optional>
+#include <type_traits>
 #include "../../include/amdrec.h"
 #include "common.hpp"
 #include "topk_utils.hpp"
@@ -38,6 +43,54 @@ struct SelectArgs {
     int cap;
 };
 
+// what the VALUE instantiations take on top: the users' blend weights and the winners' values
+struct ValueArgs : SelectArgs {
+    const float* weights;        // [n_users][n_tasks]
+    float* out_values;           // [n_users][top_k]
+};
+template <bool VALUE>
+using SelectArgsOf = std::conditional_t<VALUE, ValueArgs, SelectArgs>;
+
+// one user's blend weights, wave-uniform (VALUE; the other instantiations carry an empty one)
+struct BlendWeights {
+    float w[AMDREC_MAX_TASKS];
+};
+struct NoWeights {};
+template <bool VALUE>
+using WeightsOf = std::conditional_t<VALUE, BlendWeights, NoWeights>;
+
+// user u's weights through scalar registers: u is wave-uniform (n_users < 2^31 in the VALUE entries)
+__device__ __forceinline__ BlendWeights load_weights(const ValueArgs& a, long long u) {
+    const long long us = __builtin_amdgcn_readfirstlane((int)u);
+    BlendWeights bw;
+#pragma unroll
+    for (int t = 0; t < AMDREC_MAX_TASKS; ++t) bw.w[t] = t < a.n_tasks ? a.weights[us * a.n_tasks + t] : 0.0f;
+    return bw;
+}
+__device__ __forceinline__ NoWeights load_weights(const SelectArgs&, long long) { return NoWeights{}; }
+
+// The blend of amdrec/value.py: the tasks in order, a term with weight 0 (either sign) skipped - its y is never looked at -,
+// x_t = w_t * y_t, v = the first x_t, then v = v + x_t; every product and sum one rounded fp32 operation (boost_term /
+// boost_add: this file is compiled with contraction on).  `skip`: a task left out whatever its weight (the price's q; -1:
+// none).  Nothing left: +0.0.
+__device__ __forceinline__ float value_sub(float x, float y) {
+#pragma clang fp contract(off)
+    return x - y;
+}
+__device__ __forceinline__ float blend(const BlendWeights& bw, const float (&y)[AMDREC_MAX_TASKS], int n_tasks, int skip) {
+    float v = 0.0f;
+    bool first = true;
+#pragma unroll
+    for (int t = 0; t < AMDREC_MAX_TASKS; ++t) {
+        if (t < n_tasks && t != skip && bw.w[t] != 0.0f) {                     // (wave-uniform)
+            const float x = boost_term(bw.w[t], y[t]);
+            v = first ? x : boost_add(v, x);
+            first = false;
+        }
+    }
+    return v;
+}
+
 // the bid of corpus position pos >= 0: bid_of[pos], or 1.0 for a position beyond the array, which is never read
 __device__ __forceinline__ float bid_at(const float* bid_of, long long n_rows, long long pos) {
     return pos < n_rows ? bid_of[pos] : 1.0f;
@@ -62,34 +115,115 @@ __device__ __forceinline__ long long candidate_pos(const SelectArgs& a, long lon
 // search never filled (negative position); it lies below every real key, NaN scores included, so it can only appear behind
 // all real candidates, where it reads id -1 / probability 0 like the tail of a list shorter than top_k.  The score is the
 // ranking task's logit, or (AUCTION) e = bid * sigmoid_prob(logit), dropped (key 0) iff a reserve is given and !(e >= rv),
-// which drops a NaN e as well.  A NaN score ranks last.
-template <bool AUCTION>
-__device__ __forceinline__ unsigned long long candidate_key(const SelectArgs& a, long long u, int i, long long pos, float rv) {
+// which drops a NaN e as well.  A NaN score ranks last.  VALUE: the score is the blend v of the tasks' probabilities under
+// the user's weights bw (AUCTION: with e in the ranking task's place), the reserve compared with v; the logits of the tasks
+// with a nonzero weight are independent loads and go out together with the bid's.
+template <bool AUCTION, bool VALUE = false>
+__device__ __forceinline__ unsigned long long candidate_key(const SelectArgsOf<VALUE>& a, long long u, int i, long long pos,
+                                                            float rv, const WeightsOf<VALUE>& bw = {}) {
     if (pos < 0) return 0ull;
-    float s = a.logits[(long long)a.rank_task * a.ld + u * a.k_c + i];
-    if constexpr (AUCTION) {
-        s = bid_at(a.bid_of, a.n_bid_rows, pos) * sigmoid_prob(s);
-        if (a.reserve && !(s >= rv)) return 0ull;
+    float s;
+    if constexpr (VALUE) {
+        float y[AMDREC_MAX_TASKS];
+#pragma unroll
+        for (int t = 0; t < AMDREC_MAX_TASKS; ++t)
+            y[t] = (t < a.n_tasks && bw.w[t] != 0.0f) ? a.logits[(long long)t * a.ld + u * a.k_c + i] : 0.0f;
+        float b = 1.0f;
+        if constexpr (AUCTION) b = bid_at(a.bid_of, a.n_bid_rows, pos);
+#pragma unroll
+        for (int t = 0; t < AMDREC_MAX_TASKS; ++t) {
+            if (t < a.n_tasks && bw.w[t] != 0.0f) {                            // (wave-uniform)
+                y[t] = sigmoid_prob(y[t]);
+                if constexpr (AUCTION) y[t] = t == a.rank_task ? boost_term(b, y[t]) : y[t];
+            }
+        }
+        s = blend(bw, y, a.n_tasks, -1);
+        if constexpr (AUCTION)
+            if (a.reserve && !(s >= rv)) return 0ull;
+    } else {
+        s = a.logits[(long long)a.rank_task * a.ld + u * a.k_c + i];
+        if constexpr (AUCTION) {
+            s = bid_at(a.bid_of, a.n_bid_rows, pos) * sigmoid_prob(s);
+            if (a.reserve && !(s >= rv)) return 0ull;
+        }
     }
     return (s == s) ? make_key(s, (uint32_t)i) : ((unsigned long long)(~(uint32_t)i) | (1ull << 32));
 }
 
 // Result slot r of user u: winner `key` (0: the unfilled tail, which reads id -1 / slot -1 / probability +0.0).  AUCTION:
 // next_e = key_floor_ecpm of the candidate the selection would report at rank r + 1; price = min(bid, max(reserve, next_e) /
-// p), 0 where that floor is 0, NaN for a NaN eCPM; NaN outputs are the canonical quiet NaN.
-template <bool AUCTION>
-__device__ __forceinline__ void write_winner(const SelectArgs& a, unsigned long long key, long long u, int r, float next_e) {
+// p), 0 where that floor is 0, NaN for a NaN eCPM; NaN outputs are the canonical quiet NaN.  VALUE: next_e is the next
+// rank's v in the same sense; the winner's v, and for the price its q (the blend without the ranking task) and d = w_r * p_r,
+// are formed again from the probabilities written here, so that out_values is the blend of out_scores (and out_ecpm) bit for
+// bit; price = min(bid, (floor - q) / d), 0 where !(floor - q > 0) or !(d > 0), NaN for a NaN v.
+template <bool AUCTION, bool VALUE = false>
+__device__ __forceinline__ void write_winner(const SelectArgsOf<VALUE>& a, unsigned long long key, long long u, int r,
+                                             float next_e, const WeightsOf<VALUE>& bw = {}) {
     const bool valid = key != 0ull;
     const int slot = valid ? (int)key_pos(key) : -1;
     const long long o = u * a.top_k + r;
     a.out_ids[o] = valid ? a.cand_ids[u * a.k_c + slot] : -1;
     if (a.out_slots) a.out_slots[o] = slot;
     float p = 0.0f;
-    for (int t = 0; t < a.n_tasks; ++t) {
-        const float x = valid ? a.logits[(long long)t * a.ld + u * a.k_c + slot] : -INFINITY;
-        const float s = sigmoid_prob(x);
-        a.out_scores[((long long)t * a.n_users + u) * a.top_k + r] = s;
-        if constexpr (AUCTION) p = t == a.rank_task ? s : p;
+    if constexpr (VALUE) {
+        float y[AMDREC_MAX_TASKS];
+#pragma unroll
+        for (int t = 0; t < AMDREC_MAX_TASKS; ++t) {
+            y[t] = 0.0f;
+            if (t < a.n_tasks) {
+                const float x = valid ? a.logits[(long long)t * a.ld + u * a.k_c + slot] : -INFINITY;
+                y[t] = sigmoid_prob(x);
+                a.out_scores[((long long)t * a.n_users + u) * a.top_k + r] = y[t];
+            }
+        }
+        float v = 0.0f, e = 0.0f, price = 0.0f;
+        if (valid) {
+            float b = 1.0f;
+            if constexpr (AUCTION) {
+                b = bid_at(a.bid_of, a.n_bid_rows, a.cand_pos[u * a.k_c + slot]);
+#pragma unroll
+                for (int t = 0; t < AMDREC_MAX_TASKS; ++t) {
+                    p = t == a.rank_task ? y[t] : p;
+                    y[t] = t == a.rank_task ? boost_term(b, y[t]) : y[t];
+                    e = t == a.rank_task ? y[t] : e;
+                }
+            }
+            v = blend(bw, y, a.n_tasks, -1);
+            if constexpr (AUCTION) {
+                if (v != v) {
+                    price = __builtin_nanf("");
+                } else {
+                    float w_r = 0.0f;
+#pragma unroll
+                    for (int t = 0; t < AMDREC_MAX_TASKS; ++t) w_r = t == a.rank_task ? bw.w[t] : w_r;
+                    const float q = blend(bw, y, a.n_tasks, a.rank_task);
+                    const float d = boost_term(w_r, p);
+                    float fl = next_e;
+                    const float base = a.reserve ? a.reserve[u] : 0.0f;
+                    fl = base > fl ? base : fl;
+                    const float num = value_sub(fl, q);
+                    if (num > 0.0f && d > 0.0f) {
+                        const float g = num / d;
+                        price = g < b ? g : b;
+                    }
+                }
+                e = e != e ? __builtin_nanf("") : e;
+            }
+            v = v != v ? __builtin_nanf("") : v;
+        }
+        a.out_values[o] = v;
+        if constexpr (AUCTION) {
+            a.out_ecpm[o] = e;
+            a.out_price[o] = price;
+        }
+        return;
+    } else {
+        for (int t = 0; t < a.n_tasks; ++t) {
+            const float x = valid ? a.logits[(long long)t * a.ld + u * a.k_c + slot] : -INFINITY;
+            const float s = sigmoid_prob(x);
+            a.out_scores[((long long)t * a.n_users + u) * a.top_k + r] = s;
+            if constexpr (AUCTION) p = t == a.rank_task ? s : p;
+        }
     }
     if constexpr (AUCTION) {
         float e = 0.0f, price = 0.0f;
@@ -124,20 +258,23 @@ __device__ __forceinline__ void write_winner(const SelectArgs& a, unsigned long 
 // the cap every lane retires its remaining keys of the group - a saturated group never wins a later round.  AUCTION: one
 // round more; lane top_k keeps the runner-up, found under the same cap bookkeeping as every winner, and a lane's price needs
 // the next lane's eCPM, one __shfl.
-template <int KPL, bool AUCTION, bool CAPPED>
-__global__ __launch_bounds__(256) void select_wave_kernel(SelectArgs a) {
+// VALUE: the user's weights are loaded once, into scalar registers; the key build reads up to n_tasks logits per slot, the
+// rounds are the same, and the price's next v takes next_e's route.
+template <int KPL, bool AUCTION, bool CAPPED, bool VALUE = false>
+__global__ __launch_bounds__(256) void select_wave_kernel(SelectArgsOf<VALUE> a) {
     const int lane = threadIdx.x & 63;
     const long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (u >= a.n_users) return;                                // wave-uniform
     float rv = 0.0f;
     if constexpr (AUCTION) rv = a.reserve ? a.reserve[u] : 0.0f;
+    const WeightsOf<VALUE> bw = load_weights(a, u);
     unsigned long long key[KPL];
     long long grp[CAPPED ? KPL : 1];
 #pragma unroll
     for (int j = 0; j < KPL; ++j) {
         const int i = lane + 64 * j;
         const long long pos = candidate_pos(a, u, i);
-        key[j] = candidate_key<AUCTION>(a, u, i, pos, rv);
+        key[j] = candidate_key<AUCTION, VALUE>(a, u, i, pos, rv, bw);
         if constexpr (CAPPED) grp[j] = group_at(a.group_of, a.n_group_rows, pos);
     }
     unsigned long long mine = 0ull;                            // lane r keeps the candidate of rank r (and its group): the
@@ -183,7 +320,7 @@ __global__ __launch_bounds__(256) void select_wave_kernel(SelectArgs a) {
     }
     float next_e = 0.0f;
     if constexpr (AUCTION) next_e = __shfl(key_floor_ecpm(mine), (lane + 1) & 63, 64);     // (every lane takes part)
-    if (lane < a.top_k) write_winner<AUCTION>(a, mine, u, lane, next_e);
+    if (lane < a.top_k) write_winner<AUCTION, VALUE>(a, mine, u, lane, next_e, bw);
 }
 
 // Sort shape (up to AMDREC_MAX_K candidates, any top_k): one workgroup of 512 per user, a bitonic sort of the keys in LDS.
@@ -195,8 +332,8 @@ __global__ __launch_bounds__(256) void select_wave_kernel(SelectArgs a) {
 constexpr int SORT_NT = 512;
 constexpr int SORT_ROUNDS = AMDREC_MAX_K / SORT_NT;
 
-template <bool AUCTION, bool CAPPED>
-__global__ __launch_bounds__(SORT_NT) void select_sort_kernel(SelectArgs a) {
+template <bool AUCTION, bool CAPPED, bool VALUE = false>
+__global__ __launch_bounds__(SORT_NT) void select_sort_kernel(SelectArgsOf<VALUE> a) {
     __shared__ __attribute__((aligned(16))) unsigned long long keys[AMDREC_MAX_K];
     __shared__ float floor_e[(AUCTION && CAPPED) ? AMDREC_MAX_K + 1 : 1];
     const long long u = blockIdx.x;
@@ -205,14 +342,16 @@ __global__ __launch_bounds__(SORT_NT) void select_sort_kernel(SelectArgs a) {
     while (P < a.k_c) P <<= 1;
     float rv = 0.0f;
     if constexpr (AUCTION) rv = a.reserve ? a.reserve[u] : 0.0f;
-    for (int i = tid; i < P; i += SORT_NT) keys[i] = candidate_key<AUCTION>(a, u, i, candidate_pos(a, u, i), rv);
+    const WeightsOf<VALUE> bw = load_weights(a, u);
+    for (int i = tid; i < P; i += SORT_NT) keys[i] = candidate_key<AUCTION, VALUE>(a, u, i, candidate_pos(a, u, i), rv, bw);
     if constexpr (AUCTION && CAPPED)
         for (int i = tid; i <= a.top_k; i += SORT_NT) floor_e[i] = 0.0f;     // a rank nobody fills: no candidate, floor 0
     __syncthreads();
     bitonic_desc(keys, P);                                     // (ends behind a block barrier)
     if constexpr (!CAPPED) {
         for (int i = tid; i < a.top_k; i += SORT_NT)
-            write_winner<AUCTION>(a, i < P ? keys[i] : 0ull, u, i, (AUCTION && i + 1 < P) ? key_floor_ecpm(keys[i + 1]) : 0.0f);
+            write_winner<AUCTION, VALUE>(a, i < P ? keys[i] : 0ull, u, i,
+                                         (AUCTION && i + 1 < P) ? key_floor_ecpm(keys[i + 1]) : 0.0f, bw);
     } else {
         __shared__ __attribute__((aligned(16))) long long grp[AMDREC_MAX_K];
         __shared__ int wave_total[SORT_ROUNDS][SORT_NT / 64];
@@ -240,8 +379,9 @@ __global__ __launch_bounds__(SORT_NT) void select_sort_kernel(SelectArgs a) {
         }
 #pragma unroll
         for (int r = 0; r < SORT_ROUNDS; ++r)
-            if (keep[r] && slot[r] < a.top_k) write_winner<AUCTION>(a, key[r], u, slot[r], AUCTION ? floor_e[slot[r] + 1] : 0.0f);
-        for (int i = kept + tid; i < a.top_k; i += SORT_NT) write_winner<AUCTION>(a, 0ull, u, i, 0.0f);
+            if (keep[r] && slot[r] < a.top_k)
+                write_winner<AUCTION, VALUE>(a, key[r], u, slot[r], AUCTION ? floor_e[slot[r] + 1] : 0.0f, bw);
+        for (int i = kept + tid; i < a.top_k; i += SORT_NT) write_winner<AUCTION, VALUE>(a, 0ull, u, i, 0.0f, bw);
     }
 }
 
@@ -483,21 +623,23 @@ __global__ __launch_bounds__(DIV_NT) void select_diverse_kernel(SelectArgs a, Di
     }
 }
 
-template <bool AUCTION, bool CAPPED>
-static void launch_select(const SelectArgs& a, hipStream_t st) {
+template <bool AUCTION, bool CAPPED, bool VALUE = false>
+static void launch_select(const SelectArgsOf<VALUE>& a, hipStream_t st) {
     if (a.top_k <= 32 && a.k_c <= 512) {                       // one wave per user, no sort
         const dim3 grid((unsigned)((a.n_users + 3) / 4));
-        if (a.k_c <= 128) hipLaunchKernelGGL((select_wave_kernel<2, AUCTION, CAPPED>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((select_wave_kernel<8, AUCTION, CAPPED>), grid, dim3(256), 0, st, a);
+        if (a.k_c <= 128) hipLaunchKernelGGL((select_wave_kernel<2, AUCTION, CAPPED, VALUE>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((select_wave_kernel<8, AUCTION, CAPPED, VALUE>), grid, dim3(256), 0, st, a);
     } else {
-        hipLaunchKernelGGL((select_sort_kernel<AUCTION, CAPPED>), dim3((unsigned)a.n_users), dim3(SORT_NT), 0, st, a);
+        hipLaunchKernelGGL((select_sort_kernel<AUCTION, CAPPED, VALUE>), dim3((unsigned)a.n_users), dim3(SORT_NT), 0, st, a);
     }
 }
 
-// What the three entries share: the checks of the common arguments, the pick of shape and KPL, the launch.  auction: the
+// What the entries share: the checks of the common arguments, the pick of shape and KPL, the launch.  auction: the
 // order is by eCPM and out_ecpm / out_price are written; a.cap > 0: the cap applies.  prof_tag (nullptr: not timed) and
-// prof_bytes are the launch's ProfScope.
-static int select_any(const SelectArgs& a, bool auction, const char* prof_tag, double prof_bytes, void* stream) {
+// prof_bytes are the launch's ProfScope.  A = ValueArgs: the VALUE instantiations (the entry has checked its own fields).
+template <class A>
+static int select_any(const A& a, bool auction, const char* prof_tag, double prof_bytes, void* stream) {
+    constexpr bool VALUE = std::is_same_v<A, ValueArgs>;
     REQUIRE(a.n_tasks >= 1 && a.rank_task >= 0 && a.rank_task < a.n_tasks, "bad task index");
     REQUIRE(a.k_c >= 1 && a.k_c <= AMDREC_MAX_K, "candidates per user must be in [1,%d]", AMDREC_MAX_K);
     REQUIRE(a.top_k >= 1 && a.top_k <= AMDREC_MAX_K, "top_k out of range");
@@ -508,11 +650,28 @@ static int select_any(const SelectArgs& a, bool auction, const char* prof_tag, d
     std::optional<ProfScope> prof;
     if (prof_tag) prof.emplace(prof_tag, 0.0, prof_bytes, st);
     const bool capped = a.cap > 0;
-    if (auction && capped) launch_select<true, true>(a, st);
-    else if (auction) launch_select<true, false>(a, st);
-    else if (capped) launch_select<false, true>(a, st);
-    else launch_select<false, false>(a, st);
+    if (auction && capped) launch_select<true, true, VALUE>(a, st);
+    else if (auction) launch_select<true, false, VALUE>(a, st);
+    else if (capped) launch_select<false, true, VALUE>(a, st);
+    else launch_select<false, false, VALUE>(a, st);
     HIP_TRY(hipGetLastError());
+    return AMDREC_OK;
+}
+
+// The two value entries' own checks, before the first HIP call (select_any has the common ones): 0 = fine.
+static int check_value_args(int n_tasks, int64_t n_users, const void* cand_pos, const void* weights, const void* group_of,
+                            int64_t n_group_rows, int max_per_group, const void* out_values) {
+    REQUIRE(n_tasks >= 1 && n_tasks <= AMDREC_MAX_TASKS, "n_tasks=%d out of range [1, %d]", n_tasks, AMDREC_MAX_TASKS);
+    REQUIRE(max_per_group >= 0 && max_per_group <= AMDREC_MAX_K, "max_per_group=%d out of range [0, %d] (0: no cap)",
+            max_per_group, AMDREC_MAX_K);
+    REQUIRE(n_group_rows >= 0, "n_group_rows=%lld is negative", (long long)n_group_rows);
+    if (n_users > 0) {                                         // (no user: nothing to do, and no pointer is looked at)
+        REQUIRE(n_users <= 2147483647ll, "n_users=%lld: at most 2^31 - 1 users per call", (long long)n_users);
+        REQUIRE(cand_pos != nullptr, "null pointer: cand_pos (the value selection's candidates are decided by position)");
+        REQUIRE(weights != nullptr, "null pointer: weights");
+        REQUIRE(out_values != nullptr, "null pointer: out_values");
+        REQUIRE(max_per_group == 0 || group_of != nullptr || n_group_rows == 0, "null pointer: group_of");
+    }
     return AMDREC_OK;
 }
 
@@ -569,6 +728,41 @@ extern "C" int amdrec_select_topk_auction(const float* logits, int64_t ld_logits
                        bid_of, (long long)n_bid_rows, reserve, out_ecpm, out_price,
                        capped ? (const long long*)group_of : nullptr, capped ? (long long)n_group_rows : 0, max_per_group};
     return select_any(a, true, "select_topk_auction", (double)n_users * k_c * (capped ? 24.0 : 16.0), stream);
+}
+
+extern "C" int amdrec_select_topk_value(const float* logits, int64_t ld_logits, int n_tasks, const int64_t* cand_ids,
+                                        const int64_t* cand_pos, int64_t n_users, int k_c, int top_k, const float* weights,
+                                        const int64_t* group_of, int64_t n_group_rows, int max_per_group, int64_t* out_ids,
+                                        float* out_scores, int32_t* out_slots, float* out_values, void* stream) {
+    if (const int rc = check_value_args(n_tasks, n_users, cand_pos, weights, group_of, n_group_rows, max_per_group, out_values))
+        return rc;
+    const bool capped = max_per_group > 0;
+    const ValueArgs a{{logits, (long long)ld_logits, n_tasks, 0, (const long long*)cand_ids, (const long long*)cand_pos,
+                       k_c, top_k, (long long)n_users, (long long*)out_ids, out_scores, out_slots,
+                       nullptr, 0, nullptr, nullptr, nullptr,
+                       capped ? (const long long*)group_of : nullptr, capped ? (long long)n_group_rows : 0, max_per_group},
+                      weights, out_values};
+    return select_any(a, false, "select_topk_value", (double)n_users * k_c * (16.0 + 4.0 * n_tasks + (capped ? 8.0 : 0.0)), stream);
+}
+
+extern "C" int amdrec_select_topk_value_auction(const float* logits, int64_t ld_logits, int n_tasks, int rank_task,
+                                                const int64_t* cand_ids, const int64_t* cand_pos, int64_t n_users, int k_c,
+                                                int top_k, const float* weights, const float* bid_of, int64_t n_bid_rows,
+                                                const float* reserve, const int64_t* group_of, int64_t n_group_rows,
+                                                int max_per_group, int64_t* out_ids, float* out_scores, int32_t* out_slots,
+                                                float* out_values, float* out_ecpm, float* out_price, void* stream) {
+    if (const int rc = check_value_args(n_tasks, n_users, cand_pos, weights, group_of, n_group_rows, max_per_group, out_values))
+        return rc;
+    REQUIRE(n_bid_rows >= 0, "n_bid_rows=%lld is negative", (long long)n_bid_rows);
+    if (n_users > 0) REQUIRE(bid_of != nullptr || n_bid_rows == 0, "null pointer: bid_of");
+    const bool capped = max_per_group > 0;
+    const ValueArgs a{{logits, (long long)ld_logits, n_tasks, rank_task, (const long long*)cand_ids, (const long long*)cand_pos,
+                       k_c, top_k, (long long)n_users, (long long*)out_ids, out_scores, out_slots,
+                       bid_of, (long long)n_bid_rows, reserve, out_ecpm, out_price,
+                       capped ? (const long long*)group_of : nullptr, capped ? (long long)n_group_rows : 0, max_per_group},
+                      weights, out_values};
+    return select_any(a, true, "select_topk_value_auction",
+                      (double)n_users * k_c * (16.0 + 4.0 * n_tasks + (capped ? 8.0 : 0.0)), stream);
 }
 
 extern "C" int amdrec_select_topk_diverse(const float* logits, int64_t ld_logits, int n_tasks, int rank_task,

@@ -7,7 +7,9 @@ usage: python tools/isa_diff.py resources parent.remarks branch.remarks [tu]
 tu: the translation unit's name for the headings (default: the branch file's name up to its first dot + ".hip")
 --same NAME (repeatable, after the other arguments): a template argument that the branch added with a default, e.g.
 ListNoElig - kernels are paired by demangled name with ", NAME" / "<NAME>" removed, so f<S, NAME> (or f<NAME>) of the branch
-is judged against the parent's f<S> (or f)."""
+is judged against the parent's f<S> (or f).
+--same-branch NAME: the same, applied to the branch's names alone - for an added trailing argument whose default (false, 0)
+also occurs among the parent's own arguments, where --same would rename the parent's kernels too."""
 import difflib
 import os
 import re
@@ -16,13 +18,16 @@ import sys
 
 
 SAME = []           # --same: template arguments dropped from the demangled names
+SAME_BRANCH = []    # --same-branch: a trailing template argument dropped from the branch's demangled names only
 
 
-def demangle(names):
+def demangle(names, branch=False):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
     res = {}
     for n, d in zip(names, out):
         d = re.sub(r"\(.*", "", d).replace("amdrec::", "")
+        for t in SAME_BRANCH if branch else []:
+            d = d[:-len(", " + t + ">")] + ">" if d.endswith(", " + t + ">") else d
         for t in SAME:
             d = d.replace(", " + t + ">", ">").replace(", " + t + " >", " >").replace("<" + t + ">", "")
             d = d.replace(", " + t + ", ", ", ")             # ... or in front of a trailing pack: f<S, A, NAME, P...> is f<S, A, P...>
@@ -32,9 +37,9 @@ def demangle(names):
     return res
 
 
-def by_name(table):
+def by_name(table, branch=False):
     """mangled name -> value  =>  demangled (and --same-normalised) name -> value"""
-    names = demangle(sorted(table))
+    names = demangle(sorted(table), branch)
     return {names[n]: v for n, v in table.items()}
 
 
@@ -80,10 +85,14 @@ def main():
         i = argv.index("--same")
         SAME.append(argv[i + 1])
         del argv[i:i + 2]
+    while "--same-branch" in argv:
+        i = argv.index("--same-branch")
+        SAME_BRANCH.append(argv[i + 1])
+        del argv[i:i + 2]
     mode, a, b = argv[:3]
     tu = argv[3] if len(argv) > 3 else os.path.basename(b).split(".")[0] + ".hip"
     if mode == "resources":
-        ra, rb = by_name(resources(a)), by_name(resources(b))
+        ra, rb = by_name(resources(a)), by_name(resources(b), True)
         names = {n: n for n in set(ra) | set(rb)}
         cols = [("VGPR", "VGPRs"), ("AGPR", "AGPRs"), ("SGPR", "TotalSGPRs"), ("scratch", "ScratchSize [bytes/lane]"),
                 ("spilled VGPRs", "VGPRs Spill"), ("LDS", "LDS Size [bytes/block]"), ("occ", "Occupancy [waves/SIMD]")]
@@ -101,7 +110,7 @@ def main():
         print(f"\n{len(set(ra) & set(rb))} kernels in both, {bad} outside the conditions; {len(set(ra) - set(rb))} only in the "
               f"parent (old), {len(set(rb) - set(ra))} only in the branch (new)")
         return 1 if bad else 0
-    ka, kb = by_name(kernels(a)), by_name(kernels(b))
+    ka, kb = by_name(kernels(a)), by_name(kernels(b), True)
     names = {n: n for n in set(ka) | set(kb)}
     differ = 0
     print(f"Instruction streams of {tu}'s kernels, parent against branch (comments, .loc / .file lines and metadata stripped)\n")
