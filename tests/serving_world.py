@@ -23,7 +23,7 @@ class World:
         self.tt_sd = synth.two_tower_state(self.user, self.ad, self.nnum, seed=201)
         self.rk_sd = synth.ranker_state(self.user, self.ad, self.nnum, seed=202, cross_scale=1.0 / 16)
         self.table = synth.ad_features(self.ad, N_ADS, seed=203)
-        self.tags, self.groups, self.bids = coherence.row_attrs(204, N_ADS)
+        self.tags, self.groups, self.bids = coherence.row_attrs(204, N_ADS)[:3]
         self.boosts = np.random.default_rng(205).uniform(-0.2, 0.2, N_ADS).astype(np.float32)
         classes = {c: [f"cat_{j}" for j in range(card)] for c, card in self.user.items()}
         self.pp = Preprocessor(classes, list(synth.NUM_COLS), np.full(self.nnum, 1.5), np.full(self.nnum, 0.7))

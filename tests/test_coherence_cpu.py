@@ -3,7 +3,10 @@ per-ad cache is keyed by the table itself, not by numbers a second table can rep
 the remedy); and the seeded walks of tests/test_coherence_walk_gpu.py contain every rule and every stale-state transition
 they are there for (tests/coherence.py)."""
 import copy
+import hashlib
 import io
+import json
+import os
 import pickle
 import weakref
 
@@ -194,6 +197,55 @@ def test_corpus_model_follows_the_index_rules():
     assert c.remove([7, 9, 11]) == 3 and c.n == 0 and c.rows.shape == (0, 4)
 
 
+def test_corpus_model_carries_boosts():
+    """float32; a row never given one has 0.0; -0.0 is stored as +0.0 (amdrec.boost); carried through add, remove, set_boosts."""
+    from amdrec import boost
+    c = co.CorpusModel(4)
+    c.add(np.ones((3, 4)), [5, 7, 5], boosts=[0.25, -0.0, -1.5])
+    c.add(np.zeros((2, 4)), [9, 11])
+    assert c.boosts.dtype == np.float32 and c.boosts.tolist() == [0.25, 0.0, -1.5, 0.0, 0.0]
+    assert not np.signbit(c.boosts).tolist()[1] and np.array_equal(c.boosts[:3], boost.as_boosts([0.25, -0.0, -1.5], 3))
+    assert c.remove([5]) == 2 and c.boosts.tolist() == [0.0, 0.0, 0.0] and c.tags.tolist() == [0, 0, 0]
+    c.set_boosts(np.array([-0.0, 2.0, -3.0]))
+    assert c.boosts.dtype == np.float32 and c.boosts.tolist() == [0.0, 2.0, -3.0] and not np.signbit(c.boosts[0])
+    assert c.remove([7, 9, 11]) == 3 and c.boosts.shape == (0,)
+    # the values the steps write: mixed sign, up to BOOST_SCALE, exact zeros of both signs among them
+    b = co.row_attrs(7, 4000)[3]
+    assert b.dtype == np.float32 and np.abs(b).max() <= co.BOOST_SCALE and (b > 0.4).any() and (b < -0.4).any()
+    assert 500 < (b == 0).sum() < 1500 and np.signbit(b[b == 0]).any() and not np.signbit(b[b == 0]).all()
+    big = co.big_boosts(7, 37, 16.0)
+    assert np.abs(big).max() == big[0] == 8.0 and np.array_equal(big[1:], (co.row_attrs(7, 37)[3] * np.float32(16))[1:])
+
+
+# ---- the walks of before the option walks: walk() and row_attrs' first three values give what they gave ----------------------
+def _digest(steps):
+    return hashlib.sha256(repr(steps).encode()).hexdigest()
+
+
+def test_the_existing_walks_have_not_moved():
+    """tests/golden/coherence_walks.json was written from the walk generator as it was before it knew option walks: a sha256
+    of repr(steps) per entry of INDEX_WALKS and PIPELINE_WALKS, called as tests/test_coherence_walk_gpu.py calls it."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "coherence_walks.json")) as f:
+        golden = json.load(f)
+    assert (co.INDEX_WALKS, co.PIPELINE_WALKS) == (((33, "ints", 30), (60, "ints", 30), (70, "strings", 30)),
+                                                   {"Flat": (2, 20), "IVF": (8, 20)})
+    assert co.PROBES == ((1, 10), (33, 500), (512, 100), (3, 2000)) and co.VARIANTS == ("plain", "exclude", "masks", "cap", "all")
+    assert len(co.INDEX_RULES) == 9 and len(co.PIPELINE_RULES) == 9
+    assert set(golden["index"]) == {f"{seed}/{scheme}/{n}" for seed, scheme, n in co.INDEX_WALKS}
+    for seed, scheme, n in co.INDEX_WALKS:
+        assert _digest(co.walk(seed, co.INDEX_RULES, n, scheme)) == golden["index"][f"{seed}/{scheme}/{n}"], (seed, scheme)
+    assert set(golden["pipeline"]) == set(co.PIPELINE_WALKS)
+    for index_type, (seed, n) in co.PIPELINE_WALKS.items():
+        steps = co.walk(seed, co.PIPELINE_RULES, n, "unique", n0=co.PIPELINE_ADS, add_sizes=co.PIPELINE_ADD_SIZES, bulk=0)
+        assert _digest(steps) == golden["pipeline"][index_type], index_type
+    for scheme in co.ID_SCHEMES:
+        assert _digest(co.initial_step(scheme)) == golden["initial_step"][scheme], scheme
+    for key, want in golden["row_attrs"].items():
+        vseed, m = map(int, key.split("/"))
+        got = co.row_attrs(vseed, m)
+        assert len(got) == 4 and hashlib.sha256(b"".join(a.tobytes() for a in got[:3])).hexdigest() == want, key
+
+
 def test_select_path_is_the_host_rule():
     """tests.coherence.select_path against amdrec.ivf's own dispatch arithmetic."""
     from amdrec import ivf
@@ -249,3 +301,89 @@ def test_pipeline_walk_seeds_cover_every_rule(index_type):
     later = {r for r, _ in steps[cap[0] + 1:]}
     assert later & {"remove_ads", "add_ads"} and later & {"tower_update", "ranker_update", "load_state_dict"}
     assert {a["mode"] for r, a in steps if r == "heads"} >= {"ctr_first"}
+
+
+# ---- the option walks (tests/test_coherence_options_gpu.py) ---------------------------------------------------------------------
+def test_reserve_and_boost_bound_rules_are_the_index_rules():
+    """The walk's picture of the long-lived index's boost bound, rule by rule, on a seed that has every rule."""
+    seed, scheme, n = co.INDEX_WALKS_OPTIONS[0]
+    for rule, a in co.walk(seed, co.INDEX_RULES_OPTIONS, n, scheme):
+        vals = co.step_boosts(rule, a)
+        if rule in ("set_boosts", "remove_set_boosts", "reload"):
+            assert a["bound_after"] == a["true_after"], rule                      # replaced / recomputed
+        elif rule in ("add", "add_big_boosts") and vals is not None:
+            assert a["bound_after"] == max(a["bound_before"], float(np.abs(vals).max())), rule
+        else:
+            assert a["bound_after"] == a["bound_before"], rule                    # removals included: the bound stays
+        assert a["bound_after"] >= a["true_after"]
+        if rule == "add_big_boosts":
+            assert float(np.abs(vals).max()) == co.BOOST_SCALE * a["scale"] >= 4 * a["bound_before"] > 0
+
+
+@pytest.mark.parametrize("seed,scheme,n_steps", co.INDEX_WALKS_OPTIONS)
+def test_index_option_walk_seeds_cover_every_rule_and_transition(seed, scheme, n_steps):
+    steps = co.walk(seed, co.INDEX_RULES_OPTIONS, n_steps, scheme)
+    assert steps == co.walk(seed, co.INDEX_RULES_OPTIONS, n_steps, scheme) and len(steps) == n_steps          # pure
+    assert {r for r, _ in steps} == set(co.INDEX_RULES_OPTIONS) > set(co.INDEX_RULES)
+    found = co.transitions_options(steps)
+    missing = (set(co.REQUIRED_TRANSITIONS) | set(co.REQUIRED_TRANSITIONS_OPTIONS) | {"mixed_second_phase"}) - found
+    assert not missing, missing
+    sizes = {a["m"] for r, a in steps if r == "add"}
+    assert co.BULK_ADD in sizes and sizes & set(co.ADD_SIZES)
+    assert {a["value"] for r, a in steps if r == "nprobe"} >= {co.NLIST}
+    assert co.initial_step(scheme, options=True)["boosts"] is True
+    adds = [a for r, a in steps if r == "add"]
+    assert any(a["boosts"] for a in adds) and any(not a["boosts"] for a in adds)
+    for i, (r, a) in enumerate(steps):
+        if "removed" in a:
+            assert len(a["ids"]) > len(set(a["ids"])) and a["removed"] > 0
+        if "set_" in r and r not in ("remove_set_tags", "remove_set_boosts"):
+            assert a["n_before"] > 0
+        if r == "remove_big_boosts":
+            # exactly the rows of the last add_big_boosts that are still there - here: all of them -, and the bound outlives them
+            last = [b for q, b in steps[:i] if q == "add_big_boosts"][-1]
+            assert set(a["ids"]) - {10**12, 10**12 + 1, "no-such-ad-0", "no-such-ad-1"} == set(last["ids"])
+            assert a["removed"] == last["m"] and a["bound_after"] == a["bound_before"] > a["true_after"]
+    assert steps[-1][1]["n_after"] > 500
+    ids = {type(x) for r, a in steps if "m" in a for x in a["ids"]}
+    assert ids == ({str} if scheme == "strings" else {int})
+
+
+@pytest.mark.parametrize("index_type", list(co.PIPELINE_WALKS_OPTIONS))
+def test_pipeline_option_walk_seeds_cover_every_rule(index_type):
+    seed, n_steps = co.PIPELINE_WALKS_OPTIONS[index_type]
+    steps = co.walk(seed, co.PIPELINE_RULES_OPTIONS, n_steps, "unique", n0=co.PIPELINE_ADS, add_sizes=co.PIPELINE_ADD_SIZES,
+                    bulk=0)
+    rules = [r for r, _ in steps]
+    assert set(rules) == set(co.PIPELINE_RULES_OPTIONS) > set(co.PIPELINE_RULES) and len(steps) == n_steps
+    assert "remove_then_add_same_count" in co.transitions_options(steps)
+    cap = rules.index("capture")
+    assert cap < n_steps - 4, "a graph must live through later steps"
+    later = set(rules[cap + 1:])
+    assert later & {"remove_ads", "add_ads"} and later & {"tower_update", "ranker_update", "load_state_dict"}
+    assert "set_boosts" in later, "a graph captured with stage1_boost must outlive a swap of the boosts"
+    assert {a["mode"] for r, a in steps if r == "heads"} >= {"ctr_first"} and rules.index("heads") < n_steps - 2
+    adds = [a["boosts"] for r, a in steps if r == "add_ads"]
+    assert any(adds) and not all(adds)
+    assert steps[-1][1]["n_after"] > 0
+
+
+@pytest.mark.parametrize("kind", list(co.LATE_WALKS))
+def test_late_opt_in_walks_enable_every_flag_once(kind):
+    steps = co.late_walk(kind)
+    assert steps == co.late_walk(kind)
+    rules = [r for r, _ in steps]
+    assert [r for r in rules if r in co.LATE_ENABLES[kind]] == list(co.LATE_ENABLES[kind])      # once each, in this order
+    assert set(co.LATE_RULES) <= set(rules) and not rules[0].startswith("enable_")
+    assert steps[0][1]["flags"] == () and steps[-1][1]["n_after"] > 500
+    want = tuple(e[len("enable_"):] for e in co.LATE_ENABLES[kind] if e.startswith("enable_"))
+    assert steps[-1][1]["flags"] == want
+    for (r0, a0), (r1, a1) in zip(steps, steps[1:]):
+        assert a1["n_before"] == a0["n_after"] and a1["flags"][:len(a0["flags"])] == a0["flags"]
+        assert not (r0 in co.LATE_ENABLES[kind] and r1 in co.LATE_ENABLES[kind])
+    # the two kinds meet "a list-order copy" and "the flag of its summaries" in both orders
+    f = co.LATE_ENABLES
+    assert f["ivf"].index("enable_list_tags") < f["ivf"].index("enable_aware_probes") < f["ivf"].index("enable_list_boosts")
+    assert f["ivfpq"].index("enable_aware_probes") < f["ivfpq"].index("enable_list_tags") and "enable_list_boosts" not in f["ivfpq"]
+    last = max(i for i, r in enumerate(rules) if r in co.LATE_ENABLES[kind])
+    assert {"add", "remove", "reload"} & set(rules[last + 1:]), "the last opt-in must live through a later step"

@@ -47,7 +47,7 @@ def pool():
 
 # ---- the index walk ----------------------------------------------------------------------------------------------------------
 def _attrs(args):
-    tags, groups, bids = co.row_attrs(args["vseed"], args["m"])
+    tags, groups, bids = co.row_attrs(args["vseed"], args["m"])[:3]
     return dict(tags=tags if args["tags"] else None, groups=groups if args["groups"] else None,
                 bids=bids if args["bids"] else None)
 
@@ -274,7 +274,7 @@ def test_pipeline_walk(index_type, tmp_path):
             return tt.get_ad_embeddings(_dev(feats))
 
     def attrs(args):
-        tags, groups, bids = co.row_attrs(args["vseed"], args["m"])
+        tags, groups, bids = co.row_attrs(args["vseed"], args["m"])[:3]
         return dict(tags=tags if args["tags"] else None, groups=groups if args["groups"] else None,
                     bids=bids if args["bids"] else None)
 
