@@ -40,8 +40,10 @@ extern "C" {
                                * per-ad score boosts: amdrec_flat_search_boosted, amdrec_flat_search_mixed_boosted, added exports; then
                                * the same boosts in the inverted-list scans: amdrec_ivf_scan[_grouped[_mixed]][_eligible]_boosted and
                                * amdrec_ivf_filter_bounds_boosted, added exports; then
-                               * value ranking: amdrec_select_topk_value, amdrec_select_topk_value_auction, added exports) */
+                               * value ranking: amdrec_select_topk_value, amdrec_select_topk_value_auction, added exports; then
+                               * candidate injection: amdrec_include_merge, an added export) */
 #define AMDREC_MAX_K 2048
+#define AMDREC_MAX_INCLUDE 64 /* entries of a per-request must-consider list (amdrec_include_merge) */
 
 int amdrec_abi_version(void);
 const char* amdrec_last_error(void);
@@ -735,6 +737,29 @@ int amdrec_exclude_compact(const int64_t* keys /*[nq][kc]*/, const float* scores
                            const int64_t* exclude /*[nq][ld_exclude]*/, int n_exclude, int64_t ld_exclude, int k,
                            int64_t fill_key, float fill_score, int64_t fill_carry, int64_t* out_keys /*[nq][k]*/,
                            float* out_scores /*[nq][k]*/, int64_t* out_carry /*[nq][k] or NULL*/, void* stream);
+
+/* Per-request must-consider lists (added to ABI v14 without a version step: a new export, every other entry as it was).  The
+ * search ran for k entries per query: pos / scores [nq][k], ordered by score descending, ties to the lower position, unfilled
+ * slots (position < 0) last.  include[q][0 .. n_include) are corpus POSITIONS the query must also consider.  An entry counts
+ * when it lies in [0, n_rows), no earlier entry of the list holds it, row X[p] passes the query's masks (tags / require_all /
+ * require_any, all three or all NULL: (tags[p] & all) == all and (any == 0 or (tags[p] & any) != 0)), its id (ids[p], or p
+ * where ids is NULL) is not in exclude[q][0 .. n_exclude) (NULL: no exclusion block; negative entries are padding), and its
+ * score - the searches' fp32 re-score chain of <X[p], Q[q]>, plus boost_w[q] * boosts[p] as two rounded operations where
+ * boosts is given - is not NaN.  Entries that count and that the result already holds change nothing: those columns stay as
+ * they are.  The m others are merged in: max(0, f + m - k) of the result's f filled columns that the list does not name
+ * leave, lowest rank first, and the output is the rest and the m in the same order, unfilled slots (-1, -inf) last.
+ * out_injected (may be NULL) is 1 exactly in the slots of the m.  One launch, one workgroup per query, no workspace.
+ * 1 <= n_include <= min(k, AMDREC_MAX_INCLUDE), k <= AMDREC_MAX_K, d % 4 == 0, d <= 2048, n_rows < 2^32, X 16-byte aligned
+ * with ldx % 4 == 0; outputs must not alias inputs. */
+int amdrec_include_merge(const int64_t* pos /*[nq][k]*/, const float* scores /*[nq][k]*/, int64_t nq, int k,
+                         const int64_t* include /*[nq][ld_include]*/, int n_include, int64_t ld_include,
+                         const float* X /*[n_rows][ldx]*/, int64_t ldx, int64_t n_rows, int d, const float* Q /*[nq][ldq]*/,
+                         int64_t ldq, const int64_t* tags /*[n_rows] or NULL*/, const int64_t* require_all /*[nq] or NULL*/,
+                         const int64_t* require_any /*[nq] or NULL*/, const int64_t* exclude /*[nq][ld_exclude] or NULL*/,
+                         int n_exclude, int64_t ld_exclude, const int64_t* ids /*[n_rows] or NULL*/,
+                         const float* boosts /*[n_rows] or NULL*/, const float* boost_w /*[nq] or NULL*/,
+                         int64_t* out_pos /*[nq][k]*/, float* out_scores /*[nq][k]*/, uint8_t* out_injected /*[nq][k] or NULL*/,
+                         void* stream);
 
 /* Live corpus: removing rows without recomputing any (two more exports added to ABI v14, every other entry as it was).  A
  * removal is an order-preserving compaction of every per-row array the caller keeps: amdrec_remove_plan says which rows stay,

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("AMDREC_LIB_PATH") or os.path.join(os.path.dirname(_HE
 
 ABI_VERSION = 14
 MAX_K = 2048
+MAX_INCLUDE = 64
 
 
 class AmdrecError(RuntimeError):
@@ -106,6 +107,10 @@ _SIGNATURES = {
     "amdrec_l2_normalize": [_fp, _i64, _fp, _i64, _i64, _i32, _vp],
     "amdrec_remap_ids": [_vp, _vp, _i64, _vp, _i64, _vp],
     "amdrec_exclude_compact": [_vp, _fp, _vp, _i64, _i32, _vp, _i32, _i64, _i32, _i64, C.c_float, _i64, _vp, _fp, _vp, _vp],
+    # (pos, scores, nq, k, include, n_include, ld_include, X, ldx, n_rows, d, Q, ldq, tags, require_all, require_any, exclude,
+    # n_exclude, ld_exclude, ids, boosts, boost_w, out_pos, out_scores, out_injected, stream)
+    "amdrec_include_merge": [_vp, _fp, _i64, _i32, _vp, _i32, _i64, _fp, _i64, _i64, _i32, _fp, _i64, _vp, _vp, _vp, _vp, _i32,
+                             _i64, _vp, _fp, _fp, _vp, _fp, _vp, _vp],
     "amdrec_remove_plan_workspace": [_i64, C.POINTER(_sz)],
     "amdrec_remove_plan": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp],
     "amdrec_rows_gather": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp],

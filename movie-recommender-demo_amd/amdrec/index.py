@@ -26,7 +26,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, boost as _boost, auction as _auction, eligible as _eligible, exclude as _exclude, group_cap as _group_cap, ivf, ivfpq, probes as _probes, rows_edit as _rows_edit
+from . import _lib, boost as _boost, auction as _auction, eligible as _eligible, exclude as _exclude, group_cap as _group_cap, include as _include, ivf, ivfpq, probes as _probes, rows_edit as _rows_edit
 
 _MAGIC = b"AMDRECIX1"
 ADD_BATCH = 1 << 18            # IVFPQ add: rows normalised and encoded per batch (256 MB of fp32 at d = 256)
@@ -160,6 +160,7 @@ class FAISSIndex:
         self.n_fixup_out: Optional[torch.Tensor] = None    # Flat: device int32[1] that receives the C entry's n_fixup (diagnostics)
         self._host_ids: Optional[list] = None   # only for non-integer ids
         self._host_pos = None          # (len(_host_ids), {id: [positions]}) for exclusion lists, built on first use
+        self._id_table = None          # custom integer ids: (sorted ids, their positions) for include lists, built on first use
         self._default_ids_ok = True    # False once remove_ids has moved rows: a default id (= position) could repeat a kept id
         self._trained = self.index_type == "Flat"
         self._keeps_rows = self.index_type != "IVFPQ"    # IVFPQ: codes only, no fp32 corpus on the device
@@ -556,6 +557,7 @@ class FAISSIndex:
         elif self._ivf is not None:
             self._ivf.append(x, self._n)
         self._n += m
+        self._id_table = None
         self._log(f"Added embeddings in {time.time() - t0:.2f}s")
         self._log(f"Total index size: {self._n}")
 
@@ -602,6 +604,7 @@ class FAISSIndex:
         if self._host_ids is not None:
             self._host_ids = [self._host_ids[p] for p in kept.cpu().tolist()]
         self._host_pos = None                    # (keyed by len(_host_ids) alone: a later add of as many rows would revive it)
+        self._id_table = None
         self._ids = gather(self._ids)
         if self._tags is not None:
             self._tags = gather(self._tags)
@@ -636,6 +639,7 @@ class FAISSIndex:
                 ([] if self._groups is None else [self._groups]) +
                 ([] if getattr(self, "_bids", None) is None else [self._bids]) +
                 ([] if getattr(self, "_boosts", None) is None else [self._boosts]) +
+                list(getattr(self, "_id_table", None) or ()) +
                 (self._state.resident_tensors() if self._state else []))
 
     @property
@@ -648,7 +652,9 @@ class FAISSIndex:
                       return_positions: bool = False, pos_offset: int = 0, exclude: Optional[torch.Tensor] = None,
                       _exclude_positions: bool = False, require_all: Optional[torch.Tensor] = None,
                       require_any: Optional[torch.Tensor] = None, max_per_group: Optional[int] = None,
-                      group_overfetch: int = 2, boost_weight=None, probe_policy: Optional[str] = None):
+                      group_overfetch: int = 2, boost_weight=None, probe_policy: Optional[str] = None,
+                      include: Optional[torch.Tensor] = None, return_injected: bool = False,
+                      _include_positions: bool = False):
         """Device-to-device search, asynchronous on the current stream.
         -> (ids int64 [nq,k], scores float32 [nq,k]) on the device.  ``return_positions``: corpus
         positions (+ ``pos_offset``, the shard's first global row) instead of ids, -1 = unfilled.
@@ -693,30 +699,44 @@ class FAISSIndex:
         the plain probes also on a flagged index (A/B runs); "aware" on an index without the flag raises ValueError before the
         library is touched.  Under the aware policy a search with masks and / or a boost weight probes the ``nprobe`` best
         FEASIBLE lists of amdrec.probes' rule and the result is the masked / boosted result over those lists; a search with
-        neither probes as always, launch for launch."""
+        neither probes as always, launch for launch.
+        ``include`` (Flat, IVF; None or I = 0: the plain search, not one launch more): device int64 [nq, I], per query the ad
+        ids that must be considered whatever their similarity rank (negative = padding; I <= min(k, 64)): the call's own
+        result - masks, exclusion, boost weight and probe policy as given - with every listed ad that is known, eligible,
+        not excluded and not NaN-scored merged in at its exact score, the result's lowest-ranked unlisted entries making room
+        (amdrec.include has the rule; one launch of amdrec_include_merge behind the search).  Rows are read by position, so
+        an IVF index returns a listed ad of an unprobed list too.  Custom integer ids resolve through a table built on first
+        use (the lowest position of a repeated id); unknown ids are ignored.  With ``max_per_group`` it raises ValueError
+        (the order of cap and injection is undecided), on IVFPQ NotImplementedError.  ``return_injected``: the call returns
+        (ids, scores, injected) with ``injected`` bool [nq, k], True where a slot holds a merged-in ad (all False without a
+        list)."""
+        listed = include is not None and include.shape[-1] > 0
+        if listed:                                                   # (refused before the library is touched)
+            _include.check_include(k, include.shape[-1])
+            if max_per_group is not None:
+                raise ValueError(_include.CAP_ORDER)
+            if self.index_type == "IVFPQ":
+                raise NotImplementedError(_include.IVFPQ)
         aware = _probes.check_policy(probe_policy, self._aware())
         masked = self._check_masks(require_all, require_any)
         boosted = self._check_boost(boost_weight, masked)
         cap = self._check_group_cap(max_per_group)
+        if listed:
+            return self._search_including(queries, k, normalize, return_positions, pos_offset, exclude, _exclude_positions,
+                                          require_all, require_any, boost_weight, probe_policy, include, _include_positions,
+                                          return_injected)
+        if return_injected:
+            ids, scores = self.search_device(queries, k, normalize, return_positions, pos_offset, exclude, _exclude_positions,
+                                             require_all, require_any, max_per_group, group_overfetch, boost_weight,
+                                             probe_policy)
+            return ids, scores, torch.zeros(ids.shape, dtype=torch.bool, device=ids.device)
         if cap is not None:
             return self._search_capped(queries, k, normalize, return_positions, pos_offset, exclude, _exclude_positions,
                                        require_all, require_any, cap, group_overfetch, boost_weight, probe_policy)
         if exclude is not None and exclude.shape[-1] > 0:
             return self._search_excluding(queries, k, normalize, return_positions, pos_offset, exclude, _exclude_positions,
                                           require_all, require_any, boost_weight, probe_policy)
-        q = _lib.require_gpu(queries, "queries")
-        if q.dim() != 2 or q.shape[1] != self.dimension:
-            raise ValueError(f"expected [nq, {self.dimension}] queries, got {tuple(q.shape)}")
-        if normalize:
-            # faiss.normalize_L2 on the wrapper's copy (:146-147): ONE out-of-place launch (a float32 contiguous input is
-            # read where it lies; the caller's tensor is never written) instead of a copy launch + an in-place one
-            src = q.to(dtype=torch.float32).contiguous()
-            q = torch.empty_like(src)
-            if src.shape[0]:
-                _lib.check(_lib.load().amdrec_l2_normalize(_lib.ptr(src), src.stride(0), _lib.ptr(q), q.stride(0), src.shape[0],
-                                                           self.dimension, _lib.stream_ptr(self.device)))
-        else:
-            q = q.contiguous()
+        q = self._search_queries(queries, normalize)
         nq = q.shape[0]
         elig = masks = None
         if masked:
@@ -774,6 +794,64 @@ class FAISSIndex:
             _, scores, pos = _exclude.compact(ids_c, sc_c, pos_c, excl, k, fill, want_keys=False)
         return self._finish_compacted(pos, scores, return_positions, pos_offset)
 
+    def _search_queries(self, queries, normalize) -> torch.Tensor:
+        """The ``queries`` argument of search_device -> the contiguous [nq, dimension] block the kernels read."""
+        q = _lib.require_gpu(queries, "queries")
+        if q.dim() != 2 or q.shape[1] != self.dimension:
+            raise ValueError(f"expected [nq, {self.dimension}] queries, got {tuple(q.shape)}")
+        if not normalize:
+            return q.contiguous()
+        # faiss.normalize_L2 on the wrapper's copy (:146-147): ONE out-of-place launch (a float32 contiguous input is
+        # read where it lies; the caller's tensor is never written) instead of a copy launch + an in-place one
+        src = q.to(dtype=torch.float32).contiguous()
+        q = torch.empty_like(src)
+        if src.shape[0]:
+            _lib.check(_lib.load().amdrec_l2_normalize(_lib.ptr(src), src.stride(0), _lib.ptr(q), q.stride(0), src.shape[0],
+                                                       self.dimension, _lib.stream_ptr(self.device)))
+        return q
+
+    def _id_positions(self, ids: torch.Tensor) -> torch.Tensor:
+        """Ad ids (int64 tensor on the index's device) -> corpus positions, -1 where no row carries the id (and for the
+        negative padding); with repeated ids the lowest position.  Identity ids are their own positions (whoever reads
+        them range-checks).  Custom integer ids go through a table that is built on first use - a stable sort of the ids -
+        and dropped by add, remove_ids and load."""
+        if self._identity:
+            return ids
+        if self._id_table is None:
+            self._id_table = _include.build_id_table(self._ids[:self._n])
+        return _include.lookup_positions(self._id_table, ids)
+
+    def _search_including(self, queries, k, normalize, return_positions, pos_offset, exclude, exclude_positions, require_all,
+                          require_any, boost_weight, probe_policy, include, include_positions, return_injected):
+        """search_device with an include block: the search as it is (masks, exclusion and boost included) by position on
+        the queries normalised here, amdrec_include_merge on its result, and the id path's treatment of unfilled slots."""
+        if getattr(self, "_host_ids", None) is not None and not include_positions:
+            raise TypeError("an include list of ad ids on an index with non-integer ids: search / batch_search resolve such "
+                            "ids on the host; search_device takes integer ids only")
+        incl = _lib.require_gpu(include, "include", torch.int64)
+        q = self._search_queries(queries, normalize)
+        nq = q.shape[0]
+        if q.dtype != torch.float32:
+            raise ValueError(f"queries must be float32, got {q.dtype}")
+        if incl.dim() != 2 or incl.shape[0] != nq:
+            raise ValueError(f"include must be int64 [{nq}, I], got {tuple(incl.shape)}")
+        pos_r, sc_r = self.search_device(q, k, normalize=False, return_positions=True, exclude=exclude,
+                                         _exclude_positions=exclude_positions, require_all=require_all,
+                                         require_any=require_any, boost_weight=boost_weight, probe_policy=probe_policy)
+        excluded = exclude is not None and exclude.shape[-1] > 0
+        elig = boost = None
+        if require_all is not None or require_any is not None:
+            elig = (self._ensure_tags(), *_eligible.device_masks(require_all, require_any, nq, self.device))
+        if boost_weight is not None:
+            boost = (self._boosts, _boost.device_weights(boost_weight, nq, self.device))
+        pos, scores, inj = _include.merge(
+            pos_r, sc_r, incl if include_positions else self._id_positions(incl), self._xb, self._n, q, elig=elig,
+            exclude=exclude if excluded else None,
+            ids=None if (self._identity or exclude_positions or not excluded) else self._ids, boost=boost,
+            want_injected=return_injected)
+        out = self._finish_compacted(pos, scores, return_positions, pos_offset)
+        return (*out, inj.view(torch.bool)) if return_injected else out
+
     def _search_capped(self, queries, k, normalize, return_positions, pos_offset, exclude, exclude_positions, require_all,
                        require_any, cap, group_overfetch, boost_weight=None, probe_policy=None):
         """search_device under a per-group cap: the search as it is (masks and exclusion included) for K1 positions,
@@ -828,21 +906,47 @@ class FAISSIndex:
 
     def search(self, query_embeddings, k: int = 100, return_distances: bool = True, exclude=None, require_all=None,
                require_any=None, max_per_group: Optional[int] = None, group_overfetch: int = 2, boost_weight=None,
-               probe_policy: Optional[str] = None):
+               probe_policy: Optional[str] = None, include=None):
         """faiss_retrieval.py:129-166.  numpy in, numpy out: (ad_ids, distances).  ``exclude``: one sequence of ad ids per
         query (or an integer array [nq, E], negative = padding) that must not be returned: see search_device.
         ``require_all`` / ``require_any``: the queries' eligibility masks, one 64-bit word each (one int for all queries, a
         sequence of ints, a uint64 / int64 array): see search_device.  ``max_per_group`` / ``group_overfetch``: the per-group
         cap on every query's result: see search_device.  ``boost_weight``: the stage-1 boost weight, one number for every
         query or a sequence of one per query: see search_device.  ``probe_policy``: None / "similarity" / "aware", how an IVF / IVFPQ
-        index with ``aware_probes`` chooses its probes: see search_device."""
+        index with ``aware_probes`` chooses its probes: see search_device.  ``include``: one sequence of ad ids per query (or
+        an integer array [nq, I], negative = padding) that must be considered whatever their similarity rank: see
+        search_device; ids of any type on an index with host-side object ids."""
+        nq = len(query_embeddings)
+        incl = self._include_block(include, nq, k, max_per_group)
         _probes.check_policy(probe_policy, self._aware())
         masked = self._check_masks(require_all, require_any)
         cap = (self._check_group_cap(max_per_group), group_overfetch)
-        nq = len(query_embeddings)
         w = self._boost_weights(boost_weight, nq, masked)
         return self._search(query_embeddings, k, return_distances, self._exclude_block(exclude, nq),
-                            _eligible.device_masks(require_all, require_any, nq, self.device), cap, w, probe_policy)
+                            _eligible.device_masks(require_all, require_any, nq, self.device), cap, w, probe_policy,
+                            None if incl is None else torch.from_numpy(incl).to(self.device))
+
+    def _include_block(self, include, nq: int, k: int, max_per_group=None) -> Optional[np.ndarray]:
+        """The ``include`` argument of search / batch_search -> host int64 [nq, I] (None: no list), refused as search_device
+        refuses it, before the library is touched.  With host-side object ids the block holds corpus POSITIONS: the first
+        position of each listed id (ids not in the index are ignored)."""
+        if include is None:
+            return None
+        if getattr(self, "_host_ids", None) is None:
+            blk = _include.as_block(include, nq)
+        else:
+            if len(include) != nq:
+                raise ValueError(f"{len(include)} include lists for {nq} queries")
+            where = self._host_positions()
+            blk = _include.pad_inclusions([[where[x][0] for x in dict.fromkeys(row) if x in where] for row in include])
+            blk = blk if blk.shape[1] else None
+        if blk is not None:
+            _include.check_include(k, blk.shape[1])
+            if max_per_group is not None:
+                raise ValueError(_include.CAP_ORDER)
+            if self.index_type == "IVFPQ":
+                raise NotImplementedError(_include.IVFPQ)
+        return blk
 
     def _boost_weights(self, boost_weight, nq: int, masked: bool) -> Optional[torch.Tensor]:
         """The ``boost_weight`` argument of search / batch_search -> device float32 [nq] (None: no boost), every value
@@ -852,7 +956,7 @@ class FAISSIndex:
         return torch.from_numpy(_boost.as_weights(boost_weight, nq)).to(self.device)
 
     def _search(self, query_embeddings, k, return_distances, excl, masks=(None, None), cap=(None, 2), boost_weight=None,
-                probe_policy=None):
+                probe_policy=None, incl=None):
         """search with the exclusion lists already as a device block (_exclude_block), the masks as device words and the
         per-group cap as (max_per_group or None, group_overfetch)."""
         q = self._to_device_f32(query_embeddings)
@@ -861,13 +965,15 @@ class FAISSIndex:
             pos, scores = self.search_device(q, k, normalize=True, return_positions=True, exclude=excl,
                                              _exclude_positions=True, require_all=masks[0], require_any=masks[1],
                                              max_per_group=cap[0], group_overfetch=cap[1], boost_weight=boost_weight,
-                                             **({} if probe_policy is None else {"probe_policy": probe_policy}))
+                                             **({} if probe_policy is None else {"probe_policy": probe_policy}),
+                                             **({} if incl is None else {"include": incl, "_include_positions": True}))
             idm = np.asarray(self._host_ids, dtype=object)
             ad_ids = idm[pos.cpu().numpy()]                          # pos == -1 -> id_map[-1]
         else:
             ids, scores = self.search_device(q, k, normalize=True, exclude=excl, require_all=masks[0], require_any=masks[1],
                                              max_per_group=cap[0], group_overfetch=cap[1], boost_weight=boost_weight,
-                                             **({} if probe_policy is None else {"probe_policy": probe_policy}))
+                                             **({} if probe_policy is None else {"probe_policy": probe_policy}),
+                                             **({} if incl is None else {"include": incl}))
             ad_ids = ids.cpu().numpy()
         distances = scores.cpu().numpy()
         self._log(f"Search completed in {(time.time() - t0) * 1000:.2f}ms for {len(q)} queries")
@@ -877,11 +983,14 @@ class FAISSIndex:
 
     def batch_search(self, query_embeddings, k: int = 100, batch_size: int = 1000, exclude=None, require_all=None,
                      require_any=None, max_per_group: Optional[int] = None, group_overfetch: int = 2, boost_weight=None,
-                     probe_policy: Optional[str] = None):
+                     probe_policy: Optional[str] = None, include=None):
         """faiss_retrieval.py:168-194.  ``exclude`` (as in search) is padded once, to the longest list of the whole call,
         and sliced with the queries: the chunking does not change the result.  ``require_all`` / ``require_any`` (as in
-        search) are sliced with the queries too.  ``max_per_group`` / ``group_overfetch`` (as in search) hold per query."""
+        search) are sliced with the queries too.  ``max_per_group`` / ``group_overfetch`` (as in search) hold per query.
+        ``include`` (as in search) is padded once, like ``exclude``, and sliced with the queries."""
         all_ids, all_d = [], []
+        incl = self._include_block(include, len(query_embeddings), k, max_per_group)
+        incl = None if incl is None else torch.from_numpy(incl).to(self.device)
         _probes.check_policy(probe_policy, self._aware())
         masked = self._check_masks(require_all, require_any)
         w = self._boost_weights(boost_weight, len(query_embeddings), masked)      # (sliced with the queries, like the masks)
@@ -892,7 +1001,8 @@ class FAISSIndex:
             ids, d = self._search(query_embeddings[i:i + batch_size], k, True,
                                   None if excl is None else excl[i:i + batch_size],
                                   (None, None) if ma is None else (ma[i:i + batch_size], my[i:i + batch_size]), cap,
-                                  None if w is None else w[i:i + batch_size], probe_policy)
+                                  None if w is None else w[i:i + batch_size], probe_policy,
+                                  None if incl is None else incl[i:i + batch_size])
             all_ids.append(ids)
             all_d.append(d)
         return np.vstack(all_ids), np.vstack(all_d)
@@ -986,6 +1096,7 @@ class FAISSIndex:
         self._identity = header["identity_ids"]
         hid = header.get("host_ids")
         self._host_ids = None if hid is None else [_decode_id(x) for x in hid]
+        self._id_table = None
         cls, extra = self._state_class()
         if cls is not None:
             self._set_state(cls.from_arrays(arrays, self.device, *extra[1:]))

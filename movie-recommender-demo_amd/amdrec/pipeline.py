@@ -28,7 +28,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import _lib, boost as _boost, auction as _auction, diversity as _diversity, value as _value, eligible as _eligible, exclude as _exclude, \
+from . import _lib, boost as _boost, auction as _auction, diversity as _diversity, value as _value, eligible as _eligible, exclude as _exclude, include as _include, \
     rows_edit as _rows_edit
 from .index import FAISSIndex
 from .ranker import TransformerRanker
@@ -257,13 +257,20 @@ class AdRecommenderInference:
         return mode, None
 
     # -- the device hot path ------------------------------------------------------------------
-    def _stage1(self, uc, un, stage1_k, check_indices, exclude=None, masks=(None, None), max_per_group=None, boost_weight=None):
+    def _stage1(self, uc, un, stage1_k, check_indices, exclude=None, masks=(None, None), max_per_group=None, boost_weight=None,
+                include=None):
         # the tower's launch also applies the search's query normalisation (faiss_retrieval.py:147): one launch fewer
         emb = self.two_tower_model.user_tower.encode(uc, un, check_indices=check_indices, renormalize=True)   # :223-227
         # exclude (device int64 [B, E] ad ids, or None): removed here, so the ranker only ever sees eligible ads
         # masks (device int64 [B] require_all / require_any, or None): tested inside the search, likewise
         # max_per_group (stage1_max_per_group, or None): the per-group cap on the candidate list (FAISSIndex.search_device)
         # boost_weight (stage1_boost: a number or device float32 [B], or None): the retrieval key ip + w * boost[ad], likewise
+        # include (include_ad_ids: device int64 [B, I] ad ids, or None): merged into the search's result (amdrec.include); the
+        # call then returns (positions, scores, injected)
+        if include is not None:
+            return self.faiss_index.search_device(emb, stage1_k, normalize=False, return_positions=True, exclude=exclude,
+                                                  require_all=masks[0], require_any=masks[1], max_per_group=max_per_group,
+                                                  boost_weight=boost_weight, include=include, return_injected=True)
         return self.faiss_index.search_device(emb, stage1_k, normalize=False,                  # :230-232
                                               return_positions=True, exclude=exclude, require_all=masks[0],
                                               require_any=masks[1], max_per_group=max_per_group, boost_weight=boost_weight)
@@ -408,7 +415,8 @@ class AdRecommenderInference:
                          require_all: Optional[torch.Tensor] = None, require_any: Optional[torch.Tensor] = None,
                          max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                          rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                         diversity_pool: int = 64, stage1_boost=None, head_weights=None):
+                         diversity_pool: int = 64, stage1_boost=None, head_weights=None,
+                         include_ad_ids: Optional[torch.Tensor] = None):
         """[B,6] / [B,13] device tensors -> dict of device tensors, no host synchronisation:
         ad_ids [B,top_k] int64, scores [3,B,top_k] float32 (sigmoid of the logits), candidate_ids
         [B,stage1_k], candidate_scores [B,stage1_k], logits [3, B*stage1_k].  candidate_scores are the index's own
@@ -468,9 +476,19 @@ class AdRecommenderInference:
         the logit order of the plain call in general.  Bools, non-numbers, a tensor of another dtype or device: TypeError;
         non-finite or all-zero scalars, an unknown task, a wrong length or shape, under "ecpm" a scalar CTR weight <= 0,
         together with ``diversity`` or an explicit ``heads="ctr_first"``: ValueError.
+        ``include_ad_ids`` (None or I = 0: the plain search, the launches of ever): device int64 [B, I <= min(stage1_k, 64)],
+        per user the ad ids that must reach the ranker whatever their similarity rank (negative = padding): retargeting
+        lists, guaranteed campaigns, cart items, freshly added ads, exploration slots.  Stage 1 merges every listed ad that
+        is known, eligible under the masks, not excluded and not NaN-scored into its result at its exact (boosted) score,
+        the lowest-ranked unlisted candidates making room (amdrec.include has the rule; Flat and IVF - on IVF also from an
+        unprobed list); the dict gains ``candidate_injected``, bool [B, stage1_k], True where a candidate came from the
+        list alone.  Stage 2 is unchanged: caps, auction, diversity, value ranking and "ctr_first" take the merged
+        positions.  Wider than 64 or than stage1_k, or together with ``stage1_max_per_group`` (the order of cap and
+        injection is undecided): ValueError; on an IVFPQ index: NotImplementedError.
         ``check_indices``: an out-of-range user index or ad-table row raises IndexError; an unfilled slot does not."""
         if heads is not None:
             self._check_heads(heads)
+        listed = self._check_include(include_ad_ids, stage1_k, stage1_max_per_group)
         self.faiss_index._check_boost(stage1_boost, require_all is not None or require_any is not None)
         cap, cap1 = self._check_caps(max_per_group, stage1_max_per_group)          # (before the library is touched)
         auction = self._check_auction(rank_by, reserve)
@@ -484,19 +502,36 @@ class AdRecommenderInference:
         # one calling thread at a time enqueues (amdrec._lib.Gate): the launches below hand their intermediate results to
         # each other through the process-wide workspace, and the lazily built state is built in here
         with _lib.GATE.serving(), _lib.GATE.enqueue:
-            cand_pos, cand_scores = self._stage1(uc, un, stage1_k, check_indices, exclude_ad_ids if excluded else None,
-                                                 (require_all, require_any), cap1, stage1_boost)
+            cand_pos, cand_scores, *injected = self._stage1(uc, un, stage1_k, check_indices, exclude_ad_ids if excluded else None,
+                                                            (require_all, require_any), cap1, stage1_boost,
+                                                            include_ad_ids if listed else None)
             # (excluded: "a slot can be unfilled" - true after a filtered stage 1 as well)
             out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded or masked or cap1 is not None,
                                heads=heads, max_per_group=cap, auction=auction, diversity=div, head_weights=hw)
         out["candidate_scores"] = cand_scores
+        if injected:
+            out["candidate_injected"] = injected[0]
         return out
+
+    def _check_include(self, include, stage1_k, stage1_max_per_group) -> bool:
+        """Was an include list passed (a block [B, I] with I > 0)?  Refused before the library is touched, as
+        FAISSIndex.search_device refuses it: a list wider than 64 or than stage1_k, a list together with the stage-1 cap,
+        a list on an IVFPQ index."""
+        if include is None or include.shape[-1] == 0:
+            return False
+        _include.check_include(stage1_k, include.shape[-1])
+        if stage1_max_per_group is not None:
+            raise ValueError(_include.CAP_ORDER)
+        if self.faiss_index.index_type == "IVFPQ":
+            raise NotImplementedError(_include.IVFPQ)
+        return True
 
     def capture(self, batch_size: int, top_k: int = 10, stage1_k: int = 500, warmup: int = 2,
                 max_exclude: int = 0, eligibility: bool = False, max_per_group: Optional[int] = None,
                 stage1_max_per_group: Optional[int] = None, rank_by: Optional[str] = None,
                 reserve: bool = False, diversity: Optional[float] = None,
-                diversity_pool: int = 64, stage1_boost: bool = False, head_weights: bool = False) -> "GraphedRecommender":
+                diversity_pool: int = 64, stage1_boost: bool = False, head_weights: bool = False,
+                max_include: int = 0) -> "GraphedRecommender":
         """Capture one recommend_device call for a fixed batch shape into a HIP graph (the ~40 kernel
         launches of a request are host-launch-bound at small batch: 1.76 ms eager at B = 1) and return a
         replayer.  Weights, index and ad table must not change afterwards.  ``max_exclude`` > 0: the graph also holds a
@@ -513,9 +548,13 @@ class AdRecommenderInference:
         without one; the boosts are those of capture time); False captures the graph as ever.  ``head_weights=True``: the
         graph holds a static [batch_size, n_tasks] float32 weight buffer and runs the value selection of recommend_device
         (the replayer's ``head_weights`` fills it; until then, and without one, it holds 1.0 for the CTR head and 0.0 for the
-        others); False captures the graph as ever."""
+        others); False captures the graph as ever.  ``max_include`` > 0: the graph also holds a static
+        [batch_size, max_include] include buffer (-1 = padding until filled) and the merge step of recommend_device's
+        ``include_ad_ids``, which the replayer's ``include`` argument fills; the id table is that of capture time; 0
+        captures the graph as ever."""
         return GraphedRecommender(self, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group,
-                                  stage1_max_per_group, rank_by, reserve, diversity, diversity_pool, stage1_boost, head_weights)
+                                  stage1_max_per_group, rank_by, reserve, diversity, diversity_pool, stage1_boost, head_weights,
+                                  max_include)
 
     # -- live corpus: ads leave and enter without a rebuild of the index or of the ranker's per-ad caches ------------------
     def remove_ads(self, ad_ids) -> int:
@@ -579,15 +618,16 @@ class AdRecommenderInference:
                       return_scores: bool = True, exclude_ad_ids=None, require_all: int = 0, require_any: int = 0,
                       max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                       rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                      diversity_pool: int = 64, stage1_boost=None, head_weights=None) -> dict:
+                      diversity_pool: int = 64, stage1_boost=None, head_weights=None, include_ad_ids=None) -> dict:
         """inference.py:199-288.  ``exclude_ad_ids``: the ad ids this user must not be shown (a sequence of integers).
         ``require_all`` / ``require_any``: this request's eligibility masks (64-bit integers; 0 and 0: no constraint, the
         plain search).  ``max_per_group`` / ``stage1_max_per_group``: the per-group caps of recommend_device.  ``rank_by`` /
         ``reserve``: the auction of recommend_device (the dict gains ``ecpm`` and ``prices``).  ``diversity`` /
         ``diversity_pool``: its diversified selection (the dict gains ``diversity_values``).  ``stage1_boost``: this request's
         weight on the per-ad boosts in stage 1 (a number; recommend_device).  ``head_weights``: the value ranking of
-        recommend_device, a dict by task name or a sequence of numbers (the dict gains ``values``).  Fewer than
-        ``top_k`` real candidates: as batch_recommend."""
+        recommend_device, a dict by task name or a sequence of numbers (the dict gains ``values``).  ``include_ad_ids``: the
+        ad ids that must reach the ranker for this user whatever their similarity rank (a sequence of integers;
+        recommend_device).  Fewer than ``top_k`` real candidates: as batch_recommend."""
         masked = bool(require_all) or bool(require_any)
         return self.batch_recommend([user_data], top_k=top_k, stage1_k=stage1_k, return_scores=return_scores,
                                     exclude_ad_ids=None if exclude_ad_ids is None else [exclude_ad_ids],
@@ -595,13 +635,14 @@ class AdRecommenderInference:
                                     require_any=[require_any] if masked else None, max_per_group=max_per_group,
                                     stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve,
                                     diversity=diversity, diversity_pool=diversity_pool, stage1_boost=stage1_boost,
-                                    head_weights=head_weights)[0]
+                                    head_weights=head_weights,
+                                    include_ad_ids=None if include_ad_ids is None else [include_ad_ids])[0]
 
     def batch_recommend(self, user_data_list: list, top_k: int = 10, stage1_k: int = 500,
                         return_scores: bool = True, exclude_ad_ids=None, require_all=None, require_any=None,
                         max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                         rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                        diversity_pool: int = 64, stage1_boost=None, head_weights=None) -> list:
+                        diversity_pool: int = 64, stage1_boost=None, head_weights=None, include_ad_ids=None) -> list:
         """inference.py:290-331 - but one device pass for the whole list instead of a serial loop.
         ``timing`` reports the batch's stage times divided by the number of users.  ``exclude_ad_ids``: one sequence of
         ad ids per user (recommend_device has the meaning); the padded block travels in the input staging block.
@@ -618,7 +659,10 @@ class AdRecommenderInference:
         block.  ``stage1_boost``: the stage-1 boost weight of recommend_device, one number for every user or a sequence of
         one per user; the weights travel in the input staging block: no copy and no synchronisation more.
         ``head_weights``: the value ranking of recommend_device, for every user of the list; every user's dict gains a
-        ``"values"`` list of length ``top_k``, in the same result block."""
+        ``"values"`` list of length ``top_k``, in the same result block.  ``include_ad_ids``: one sequence of ad ids per user
+        (or an integer array [n, I], negative = padding) that must reach the ranker (recommend_device); the padded block
+        travels through pinned memory like the exclusions: no synchronisation more."""
+        incl = self._host_inclusions(include_ad_ids, len(user_data_list), stage1_k, stage1_max_per_group)
         self.faiss_index._check_boost(stage1_boost, require_all is not None or require_any is not None)
         self._check_caps(max_per_group, stage1_max_per_group)
         auction = self._check_auction(rank_by, reserve)
@@ -638,7 +682,8 @@ class AdRecommenderInference:
             return self.recommend_tensors(uc, un, top_k, stage1_k, return_scores, _encoded=True, _exclude_dev=excl,
                                           _masks_dev=masks, _boost_dev=wts, max_per_group=max_per_group,
                                           stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve,
-                                          diversity=diversity, diversity_pool=diversity_pool, head_weights=head_weights)
+                                          diversity=diversity, diversity_pool=diversity_pool, head_weights=head_weights,
+                                          _include_host=incl)
 
     def _check_caps(self, max_per_group, stage1_max_per_group):
         """The two cap arguments -> (cap or None, stage-1 cap or None); refusals before the library is touched."""
@@ -678,6 +723,14 @@ class AdRecommenderInference:
         blk = _exclude.as_block(exclude_ad_ids, n)
         if blk is not None:
             _exclude.check_exclude(stage1_k, blk.shape[1])
+        return blk
+
+    def _host_inclusions(self, include_ad_ids, n: int, stage1_k: int, stage1_max_per_group=None) -> Optional[np.ndarray]:
+        """One id list per user -> the padded int64 [n, I] host block (None: no list, or every list empty); refused as
+        recommend_device refuses it, before the library is touched."""
+        blk = _include.as_block(include_ad_ids, n)
+        if blk is not None:
+            self._check_include(blk, stage1_k, stage1_max_per_group)
         return blk
 
     def _user_limits(self):
@@ -721,7 +774,8 @@ class AdRecommenderInference:
     def recommend_tensors(self, user_categorical, user_numerical, top_k=10, stage1_k=500, return_scores=True,
                           _encoded=False, exclude_ad_ids=None, _exclude_dev=None, require_all=None, require_any=None,
                           _masks_dev=None, max_per_group=None, stage1_max_per_group=None, rank_by=None, reserve=None,
-                          diversity=None, diversity_pool=64, stage1_boost=None, _boost_dev=None, head_weights=None):
+                          diversity=None, diversity_pool=64, stage1_boost=None, _boost_dev=None, head_weights=None,
+                          include_ad_ids=None, _include_host=None):
         """Tensor-level entry (cf. TwoStageRetriever.retrieve_and_rank, faiss_retrieval.py:283-369); result dicts follow
         inference.py:272-288.  ONE host synchronisation per call (round 3 had four: the tower's index flag, the stage-1
         timing sync, the ranker's index flag, the result copy - each exposing the launch work queued behind it): indices
@@ -735,7 +789,12 @@ class AdRecommenderInference:
         ``prices`` ride in the same result block and copy.  ``diversity`` / ``diversity_pool``: its diversified selection;
         ``diversity_values`` rides there too.  ``stage1_boost``: the users' stage-1 boost weights as in batch_recommend,
         shipped through pinned memory like the masks.  ``head_weights``: its value ranking; ``values`` rides in the result block
-        too, behind ``ecpm`` and ``prices`` where the auction runs: still one copy, one synchronisation."""
+        too, behind ``ecpm`` and ``prices`` where the auction runs: still one copy, one synchronisation.
+        ``include_ad_ids``: one sequence of ad ids per user that must reach the ranker (recommend_device), shipped as one
+        padded block through pinned memory like the exclusions."""
+        hi = _include_host
+        if hi is None and include_ad_ids is not None and user_categorical is not None:
+            hi = self._host_inclusions(include_ad_ids, user_categorical.shape[0], stage1_k, stage1_max_per_group)
         if _boost_dev is None:
             self.faiss_index._check_boost(stage1_boost, require_all is not None or require_any is not None)
         cap, cap1 = self._check_caps(max_per_group, stage1_max_per_group)
@@ -776,6 +835,12 @@ class AdRecommenderInference:
                 host.numpy().view(np.float32)[:] = hw
                 wts = host.to(dev, non_blocking=True).view(torch.float32)
                 done.record(torch.cuda.current_stream(dev))
+            incl = None
+            if hi is not None:
+                host, done = self._staging(hi.size * 8, "incl")
+                host.numpy().view(np.int64).reshape(hi.shape)[:] = hi
+                incl = host.to(dev, non_blocking=True).view(torch.int64).view(hi.shape)
+                done.record(torch.cuda.current_stream(dev))
             # the enqueue, one calling thread at a time (amdrec._lib.Gate); the wait for the device and the list conversion
             # behind it run beside other threads' enqueues, on staging blocks and events that are this thread's own
             with _lib.GATE.enqueue:
@@ -813,8 +878,8 @@ class AdRecommenderInference:
                     raise IndexError("index out of range in self")                    # (the ad-feature table, transformer_ranker.py:322)
                 st = torch.cuda.current_stream(dev)
                 ev[0].record(st)
-                cand_pos, _ = self._stage1(uc, un, stage1_k, False, excl,
-                                           (None, None) if masks is None else (masks[0], masks[1]), cap1, wts)
+                cand_pos, *_ = self._stage1(uc, un, stage1_k, False, excl,
+                                            (None, None) if masks is None else (masks[0], masks[1]), cap1, wts, incl)
                 ev[1].record(st)
                 out = self._stage2(uc, un, cand_pos, top_k, False, out=outs,
                                    excluded=excl is not None or masks is not None or cap1 is not None, max_per_group=cap,
@@ -876,7 +941,7 @@ class TwoStageRetriever:
                           stage2_k: int = 10, ad_features_lookup=None, exclude_ad_ids=None,
                           max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                           rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                          diversity_pool: int = 64, stage1_boost=None, head_weights=None):
+                          diversity_pool: int = 64, stage1_boost=None, head_weights=None, include_ad_ids=None):
         """``exclude_ad_ids``: the ad ids the (first) user must not be shown, a sequence of integers.  With a table, the two
         lists have length ``stage2_k``; a user with fewer real candidates gets -1 / 0.0 in the tail (batch_recommend).
         ``stage1_max_per_group`` / ``max_per_group``: the per-group caps on the candidates and on the ranked result
@@ -887,8 +952,16 @@ class TwoStageRetriever:
         pick order); without a table they are checked and change nothing.  ``stage1_boost``: the (first) user's weight on the
         per-ad boosts in stage 1, a number (recommend_device), with or without a table.  ``head_weights``: the value ranking
         of recommend_device for the ranked result (ids and CTR probabilities, in value order); without a table it is checked
-        and changes nothing."""
+        and changes nothing.  ``include_ad_ids``: the ad ids that must be candidates for the (first) user whatever their
+        similarity rank, a sequence of integers (recommend_device), with or without a table."""
         idx = self.faiss_index
+        incl = None if include_ad_ids is None else _include.as_block([include_ad_ids], 1)
+        if incl is not None:                                                      # (refused before the library is touched)
+            _include.check_include(stage1_k, incl.shape[1])
+            if stage1_max_per_group is not None:
+                raise ValueError(_include.CAP_ORDER)
+            if idx.index_type == "IVFPQ":
+                raise NotImplementedError(_include.IVFPQ)
         idx._check_boost(stage1_boost)
         cap, cap1 = idx._check_group_cap(max_per_group), idx._check_group_cap(stage1_max_per_group, "stage1_max_per_group")
         auction = idx._check_auction(rank_by, reserve)[0]
@@ -907,9 +980,10 @@ class TwoStageRetriever:
                 with _lib.GATE.enqueue:
                     emb = self.two_tower_model.get_user_embeddings(uc, un)
                     ids, dist = self.faiss_index.search_device(
-                        emb[:1] if blk is not None else emb, stage1_k,
+                        emb[:1] if blk is not None or incl is not None else emb, stage1_k,
                         exclude=None if blk is None else torch.from_numpy(blk).to(self.device), max_per_group=cap1,
-                        boost_weight=stage1_boost)
+                        boost_weight=stage1_boost,
+                        **({} if incl is None else {"include": torch.from_numpy(incl).to(self.device)}))
                 return ids[0].tolist(), dist[0].tolist()
         with _lib.GATE.enqueue:                                                   # (one builder of the lazy recommender)
             rec = self._rec
@@ -923,7 +997,7 @@ class TwoStageRetriever:
                                         rank_by=rank_by, reserve=reserve, diversity=diversity,
                                         diversity_pool=diversity_pool, stage1_boost=stage1_boost,
                                         head_weights=head_weights if not isinstance(head_weights, torch.Tensor)
-                                        else head_weights[:1])[0]
+                                        else head_weights[:1], _include_host=incl)[0]
         return r["ad_ids"], r["scores"]["ctr"]                                    # :359-369 (ids, ctr probabilities)
 
 
@@ -936,15 +1010,15 @@ class GraphedRecommender:
                  max_exclude: int = 0, eligibility: bool = False, max_per_group: Optional[int] = None,
                  stage1_max_per_group: Optional[int] = None, rank_by: Optional[str] = None, reserve: bool = False,
                  diversity: Optional[float] = None, diversity_pool: int = 64, stage1_boost: bool = False,
-                 head_weights: bool = False):
+                 head_weights: bool = False, max_include: int = 0):
         # the capture gate first: while another thread captures, the runtime is in its global capture mode, and the
         # allocations and fills of the static buffers below would already disturb it.  Refused before the device is touched
         with _lib.GATE.capturing():
             self._init(rec, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group, stage1_max_per_group,
-                       rank_by, reserve, diversity, diversity_pool, stage1_boost, head_weights)
+                       rank_by, reserve, diversity, diversity_pool, stage1_boost, head_weights, max_include)
 
     def _init(self, rec, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group, stage1_max_per_group,
-              rank_by, reserve, diversity, diversity_pool, stage1_boost, head_weights=False):
+              rank_by, reserve, diversity, diversity_pool, stage1_boost, head_weights=False, max_include=0):
         self.rec, self.batch_size, self.top_k, self.stage1_k = rec, batch_size, top_k, stage1_k
         # the per-group caps: scalars fixed at capture (the group keys are those of capture time, pinned below)
         self.max_per_group, self.stage1_max_per_group = rec._check_caps(max_per_group, stage1_max_per_group)
@@ -967,6 +1041,12 @@ class GraphedRecommender:
             _value.check_head_weights(self._head_default, self._tasks, None, auction, diversity is not None)
         self.max_exclude = int(max_exclude)
         _exclude.check_exclude(stage1_k, self.max_exclude)
+        # the include list: a static [batch_size, max_include] block (-1 = padding = nothing listed); None: no merge step
+        self.max_include = int(max_include)
+        if self.max_include < 0:
+            raise ValueError(f"max_include={max_include}: the width of the include block, >= 0")
+        if self.max_include:
+            rec._check_include(torch.empty((0, self.max_include)), stage1_k, stage1_max_per_group)
         dev = rec.ad_features.device
         n_cat = len(rec.two_tower_model.user_tower._names)
         n_num = rec.two_tower_model.user_tower._n_num
@@ -990,6 +1070,10 @@ class GraphedRecommender:
         if stage1_boost:
             rec.faiss_index._check_boost(self._boost_w, self.eligibility)
             caps.update(stage1_boost=self._boost_w)
+        self._in = None
+        if self.max_include:
+            self._in = torch.full((batch_size, self.max_include), -1, dtype=torch.int64, device=dev)
+            caps.update(include_ad_ids=self._in)
         # sizing + warm-up pass on the shared workspace (packs weights, sets kernel attributes)
         # the capture swaps the process-wide workspace and the runtime's capture mode is global: not beside other threads'
         # calls (amdrec._lib.Gate: refused, either way round - __init__ holds the gate), and no other thread enqueues in between
@@ -1041,18 +1125,20 @@ class GraphedRecommender:
 
     def __call__(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor,
                  exclude: Optional[torch.Tensor] = None, require_all: Optional[torch.Tensor] = None,
-                 require_any: Optional[torch.Tensor] = None, reserve=None, stage1_boost=None, head_weights=None):
+                 require_any: Optional[torch.Tensor] = None, reserve=None, stage1_boost=None, head_weights=None,
+                 include: Optional[torch.Tensor] = None):
         """One replay - arguments and result: ``_replay`` - inside ``replaying()`` and the serving scope: a replay that
         overlaps another thread's replay of this object, or another thread's capture, raises AmdrecError before it has
         touched the static buffers."""
         with self.replaying(), _lib.GATE.serving():
             return self._replay(user_categorical, user_numerical, exclude, require_all, require_any, reserve, stage1_boost,
-                                head_weights)
+                                head_weights, include)
 
     @torch.no_grad()
     def _replay(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor,
                 exclude: Optional[torch.Tensor] = None, require_all: Optional[torch.Tensor] = None,
-                require_any: Optional[torch.Tensor] = None, reserve=None, stage1_boost=None, head_weights=None):
+                require_any: Optional[torch.Tensor] = None, reserve=None, stage1_boost=None, head_weights=None,
+                include: Optional[torch.Tensor] = None):
         """Device tensors [batch_size, ...] -> the same dict as recommend_device (static output buffers,
         overwritten by the next call).  ``exclude``: device int64 [batch_size, E <= max_exclude] ad ids (negative =
         padding), copied into the graph's block; None = nothing excluded (the block is filled with -1).  ``require_all`` /
@@ -1063,7 +1149,13 @@ class GraphedRecommender:
         the graph's weight buffer (None = zeros); a graph captured without ``stage1_boost=True`` raises ValueError for it.
         ``head_weights``: a dict, a sequence or a device float32 [batch_size, n_tasks] as recommend_device takes them, written
         into the graph's weight buffer (None = 1.0 for the CTR head, 0.0 for the others); a graph captured without
-        ``head_weights=True`` raises ValueError for it."""
+        ``head_weights=True`` raises ValueError for it.  ``include``: device int64 [batch_size, I <= max_include] ad ids
+        (negative = padding), copied into the graph's include block; None = nothing listed (the block is filled with -1); a
+        graph captured without ``max_include`` raises ValueError for it."""
+        if include is not None and (self._in is None or include.dim() != 2 or include.shape[0] != self.batch_size
+                                    or include.shape[1] > self.max_include or include.dtype != torch.int64):
+            raise ValueError(f"captured with max_include={self.max_include} for batch {self.batch_size}, got an include block "
+                             f"of shape {tuple(include.shape)} ({include.dtype})")
         if head_weights is not None:
             if self._head_w is None:
                 raise ValueError("captured without head_weights=True: this graph ranks by the CTR head and takes no weights")
@@ -1114,6 +1206,11 @@ class GraphedRecommender:
                 self._ex.fill_(-1)
             if exclude is not None:
                 self._ex[:, :exclude.shape[1]].copy_(exclude)
+        if self._in is not None:
+            if include is None or include.shape[1] < self.max_include:
+                self._in.fill_(-1)
+            if include is not None:
+                self._in[:, :include.shape[1]].copy_(include)
         self._uc.copy_(user_categorical)
         self._un.copy_(user_numerical)
         self._graph.replay()
