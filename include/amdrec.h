@@ -41,7 +41,11 @@ extern "C" {
                                * the same boosts in the inverted-list scans: amdrec_ivf_scan[_grouped[_mixed]][_eligible]_boosted and
                                * amdrec_ivf_filter_bounds_boosted, added exports; then
                                * value ranking: amdrec_select_topk_value, amdrec_select_topk_value_auction, added exports; then
-                               * candidate injection: amdrec_include_merge, an added export) */
+                               * candidate injection: amdrec_include_merge, an added export; then
+                               * exploration: amdrec_select_topk_sampled, an added export.
+                               * A library that reports v14 may therefore carry any prefix of these additions: a caller that
+                               * needs one of them probes for the symbol (dlsym; amdrec._lib.exported_symbols() lists what the
+                               * Python binding requires and load() fails on a library that lacks one)) */
 #define AMDREC_MAX_K 2048
 #define AMDREC_MAX_INCLUDE 64 /* entries of a per-request must-consider list (amdrec_include_merge) */
 
@@ -945,6 +949,34 @@ int amdrec_select_topk_value_auction(const float* logits /*[n_tasks][ld]*/, int6
                                      float* out_scores /*[n_tasks][n_users][top_k]*/, int32_t* out_slots /*or NULL*/,
                                      float* out_values /*[n_users][top_k]*/, float* out_ecpm /*[n_users][top_k]*/,
                                      float* out_price /*[n_users][top_k]*/, void* stream);
+
+/* Exploration (one more export added to ABI v14, every other entry as it was): amdrec_select_topk_capped with a sampled
+ * order behind a greedy prefix, and the probability of every pick.  Its arguments in the same order, then temperature
+ * (device float32 [n_users]), seeds (device uint64 [n_users]), greedy (the prefix g, one value per call) and out_propensity.
+ * max_per_group == 0: no cap, group_of is not looked at and may be NULL.  cand_pos is REQUIRED.  Per user u:
+ *   mix64(x): x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31 (mod 2^64);
+ *   h_i = mix64(mix64(seeds[u]) ^ (uint64) cand_ids[u][i]); U_i = ((h_i >> 41) + 0.5) * 2^-23; G_i = -log(-log(U_i)) in fp64;
+ *   for a finite logit z_i of rank_task: x_i = (double) z_i / (double) temperature[u], k_i = (float)(x_i + G_i).
+ *   Sampled order S: +inf logits in slot order, then the finite ones by (k desc, slot asc), then -inf logits in slot order,
+ *   then NaN logits in slot order.  A user with !(temperature[u] > 0) is served greedily: S = amdrec_select_topk's order.
+ *   The first `greedy` winners are amdrec_select_topk_capped's (amdrec_select_topk's without a cap); the walk then goes on
+ *   over S, skipping what is chosen, with the group counts carried over, until top_k winners stand or S is used up.
+ *   out_propensity[u][rank] = 1.0 for a rank below `greedy`, for a greedily served user and for a winner whose logit is not
+ *   finite; else exp(x_w - m) / sum_{i in R} exp(x_i - m) in fp64, rounded once to fp32 (it may round to 0.0), R = the
+ *   finite-logit candidates not yet chosen whose group is not full, m = their largest x.
+ * out_ids / out_scores / out_slots as amdrec_select_topk; the unfilled tail reads id -1, slot -1, probabilities 0.0,
+ * propensity 0.0.  The noise is keyed on the ad id: it does not depend on the candidate order or on the batch.
+ * 1 <= top_k <= 128, 0 <= greedy <= top_k, 1 <= k_c <= AMDREC_MAX_K, 0 <= max_per_group <= AMDREC_MAX_K.  One launch, one
+ * workgroup per user, no workspace; every argument is validated before the first HIP call; n_users <= 0 returns OK without
+ * looking at a pointer. */
+int amdrec_select_topk_sampled(const float* logits /*[n_tasks][ld]*/, int64_t ld_logits, int n_tasks, int rank_task,
+                               const int64_t* cand_ids /*[n_users][k_c]*/, const int64_t* cand_pos /*[n_users][k_c]*/,
+                               int64_t n_users, int k_c, int top_k, int64_t* out_ids /*[n_users][top_k]*/,
+                               float* out_scores /*[n_tasks][n_users][top_k]*/, int32_t* out_slots /*or NULL*/,
+                               const int64_t* group_of /*[n_group_rows]; NULL without a cap*/, int64_t n_group_rows,
+                               int max_per_group /*0: no cap*/, const float* temperature /*[n_users]*/,
+                               const uint64_t* seeds /*[n_users]*/, int greedy, float* out_propensity /*[n_users][top_k]*/,
+                               void* stream);
 
 #ifdef __cplusplus
 }

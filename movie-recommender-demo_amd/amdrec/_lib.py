@@ -139,6 +139,9 @@ _SIGNATURES = {
     # out_values
     "amdrec_select_topk_value_auction": [_fp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _fp, _fp, _i64, _fp, _vp, _i64, _i32,
                                          _vp, _fp, _vp, _fp, _fp, _fp, _vp],
+    # amdrec_select_topk_capped's arguments up to max_per_group + (temperature, seeds, greedy, out_propensity, stream)
+    "amdrec_select_topk_sampled": [_fp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _fp, _vp, _vp, _i64, _i32, _fp, _vp,
+                                   _i32, _fp, _vp],
     "amdrec_group_cap_compact": [_vp, _fp, _i64, _i32, _vp, _i64, _i32, _i32, C.c_float, _vp, _fp, _vp],
 }
 _RESTYPE = {"amdrec_last_error": C.c_char_p}

@@ -28,7 +28,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import _lib, boost as _boost, auction as _auction, diversity as _diversity, value as _value, eligible as _eligible, exclude as _exclude, include as _include, \
+from . import _lib, boost as _boost, auction as _auction, diversity as _diversity, value as _value, explore as _explore, eligible as _eligible, exclude as _exclude, include as _include, \
     rows_edit as _rows_edit
 from .index import FAISSIndex
 from .ranker import TransformerRanker
@@ -153,7 +153,7 @@ class AdRecommenderInference:
         return torch.tensor([cat], dtype=torch.long), torch.from_numpy(num[None, :])
 
     def preprocess_batch(self, user_data_list: list, exclude: Optional[np.ndarray] = None,
-                         masks: Optional[np.ndarray] = None, weights: Optional[np.ndarray] = None):
+                         masks: Optional[np.ndarray] = None, weights: Optional[np.ndarray] = None, draws=None):
         """Batch form of preprocess_user_features with the numerical transform on the device: categorical strings
         are label-encoded on the host (dictionary lookups), raw numericals are shipped as one float32 block and
         log1p / standardised by amdrec_prep_numerical.  -> (user_categorical [B,6] int64, user_numerical [B,13]
@@ -161,7 +161,8 @@ class AdRecommenderInference:
         staging block and copy; the result is then (user_categorical, user_numerical, exclude on the device).  ``masks``
         (int64 [2, B]: the users' require_all and require_any words, amdrec.eligible) ride there too and come back last,
         as a device [2, B].  ``weights`` (float32 [B]: the users' stage-1 boost weights, amdrec.boost) ride behind them and
-        come back after them, as a device float32 [B]."""
+        come back after them, as a device float32 [B].  ``draws`` (amdrec.explore.host_arrays: float32 [B] temperatures and
+        uint64 [B] seeds) ride behind those and come back last, as a device float32 [B] and a device int64 [B]."""
         pp = self.preprocessor
         if pp is None:
             raise ValueError("no preprocessor loaded")
@@ -175,9 +176,15 @@ class AdRecommenderInference:
         ex_off = (cat_bytes + B * nn_ * 4 + 7) // 8 * 8                 # the int64 exclusion block, 8-byte aligned
         m_off = ex_off + (0 if exclude is None else exclude.size * 8)   # the int64 mask words
         w_off = m_off + (0 if masks is None else 2 * B * 8)             # the float32 boost weights
-        host, done = self._staging(w_off + B * 4 if weights is not None else (m_off + 2 * B * 8 if masks is not None else
-                                   (cat_bytes + B * nn_ * 4 if exclude is None else m_off)))
+        used = w_off + B * 4 if weights is not None else (m_off + 2 * B * 8 if masks is not None else
+                                                          (cat_bytes + B * nn_ * 4 if exclude is None else m_off))
+        s_off = (used + 7) // 8 * 8                                     # the uint64 seeds, 8-byte aligned, then the temperatures
+        t_off = s_off + B * 8
+        host, done = self._staging(used if draws is None else t_off + B * 4)
         hv = host.numpy()
+        if draws is not None:
+            hv[s_off:t_off].view(np.uint64)[:] = draws[1]
+            hv[t_off:t_off + B * 4].view(np.float32)[:] = draws[0]
         if nc:
             hv[:cat_bytes].view(np.int64).reshape(B, nc)[:] = [[pp.encode(c, u["categorical"].get(c, "missing")) for c in cols]
                                                                for u in user_data_list]
@@ -210,6 +217,8 @@ class AdRecommenderInference:
             res += (blk[m_off:m_off + 2 * B * 8].view(torch.int64).view(2, B),)
         if weights is not None:
             res += (blk[w_off:w_off + B * 4].view(torch.float32),)
+        if draws is not None:
+            res += (blk[t_off:t_off + B * 4].view(torch.float32), blk[s_off:t_off].view(torch.int64))
         return res
 
     def _staging(self, nbytes: int, slot: str = "in"):
@@ -276,7 +285,7 @@ class AdRecommenderInference:
                                               require_any=masks[1], max_per_group=max_per_group, boost_weight=boost_weight)
 
     def _stage2(self, uc, un, cand_pos, top_k, check_indices, ids_are_positions=False, mark=None, out=None,
-                excluded=False, heads=None, max_per_group=None, auction=None, diversity=None, head_weights=None):
+                excluded=False, heads=None, max_per_group=None, auction=None, diversity=None, head_weights=None, explore=None):
         """Ranker + selection over stage 1's positions ``cand_pos`` [B, stage1_k].  A negative position is a slot the search
         could not fill: no candidate.  The ranker still computes a (finite, unspecified) logit for it - every gather clamps
         the row - and the selection, which is handed the positions, ranks it after every real candidate: it is reported only
@@ -292,7 +301,10 @@ class AdRecommenderInference:
         inside it, and the result gains ``diversity_values``.
         ``head_weights`` (validated by the caller, None: the selections above): amdrec.value.check_head_weights' result or a
         static [B, n_tasks] buffer - the selection is amdrec_select_topk_value (``_value_auction`` with ``auction``), the cap
-        inside it, every head on every candidate whatever ``heads_mode`` says, and the result gains ``values``."""
+        inside it, every head on every candidate whatever ``heads_mode`` says, and the result gains ``values``.
+        ``explore`` (validated by the caller, None: the selections above): ``(temperature, seeds, greedy)``, device float32 [B],
+        device int64 [B] and the greedy prefix - the selection is amdrec_select_topk_sampled (amdrec.explore has the rule), the
+        cap inside it, in either heads mode, and the result gains ``propensities``."""
         lib = _lib.load()
         B, stage1_k = cand_pos.shape
         rk = self.transformer_ranker
@@ -380,6 +392,14 @@ class AdRecommenderInference:
             values = out[2] if out is not None and len(out) == 3 else \
                 torch.empty((B, top_k), dtype=torch.float32, device=uc.device)
             tail = (_lib.ptr(values),)
+        elif explore is not None:
+            # the sampled entry: the capped one's arguments (cap 0: none), then the temperatures, the seeds, the prefix and one
+            # output more
+            select = lib.amdrec_select_topk_sampled
+            values = out[2] if out is not None and len(out) == 3 else \
+                torch.empty((B, top_k), dtype=torch.float32, device=uc.device)
+            tail = (_lib.ptr(idx._groups) if max_per_group else None, idx._n if max_per_group else 0, max_per_group or 0,
+                    _lib.ptr(explore[0]), _lib.ptr(explore[1]), explore[2], _lib.ptr(values))
         elif max_per_group is None:
             select, tail = lib.amdrec_select_topk, ()
         else:                                    # the same arguments, then the groups: the cap runs inside the selection
@@ -406,6 +426,8 @@ class AdRecommenderInference:
             res["diversity_values"] = values
         if head_weights is not None:
             res["values"] = values
+        if explore is not None:
+            res["propensities"] = values
         return res
 
     @torch.no_grad()
@@ -416,7 +438,8 @@ class AdRecommenderInference:
                          max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                          rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
                          diversity_pool: int = 64, stage1_boost=None, head_weights=None,
-                         include_ad_ids: Optional[torch.Tensor] = None):
+                         include_ad_ids: Optional[torch.Tensor] = None, explore=None, explore_seed=None,
+                         explore_from: int = 0):
         """[B,6] / [B,13] device tensors -> dict of device tensors, no host synchronisation:
         ad_ids [B,top_k] int64, scores [3,B,top_k] float32 (sigmoid of the logits), candidate_ids
         [B,stage1_k], candidate_scores [B,stage1_k], logits [3, B*stage1_k].  candidate_scores are the index's own
@@ -485,6 +508,19 @@ class AdRecommenderInference:
         list alone.  Stage 2 is unchanged: caps, auction, diversity, value ranking and "ctr_first" take the merged
         positions.  Wider than 64 or than stage1_k, or together with ``stage1_max_per_group`` (the order of cap and
         injection is undecided): ValueError; on an IVFPQ index: NotImplementedError.
+        ``explore`` (None: the arg-max selections above, the launches of ever): the temperature of a sampled selection
+        (amdrec.explore has the rule) - a number >= 0 for every user or a device float32 [B] of the caller's values; a user
+        whose temperature is not > 0 is served greedily.  Stage 2 then draws the ``top_k`` ads without replacement with
+        probabilities proportional to exp(CTR logit / temperature) (Plackett-Luce, by Gumbel-perturbed keys), inside the
+        selection launch, under ``max_per_group`` where that is given and in either heads mode (bit-identical between them);
+        the dict gains ``propensities``, float32 [B, top_k]: the conditional probability the policy gave each pick (1.0 for a
+        forced pick, 0.0 in the unfilled tail; a pick of vanishing probability may read 0.0).  ``explore_seed`` (required
+        with ``explore``): a Python int in [0, 2^64) - user ``u`` draws with ``(seed + u) mod 2^64`` - or a device int64 [B]
+        of bit patterns; the noise is keyed on seed and ad id, so the same seed draws the same ads whatever the candidate
+        order.  ``explore_from``: the first that many ranks stay the arg-max winners (propensity 1.0) and the draw fills the
+        rest.  One without the other, ``explore_from`` without ``explore`` or outside [0, top_k], ``top_k`` > 128, a negative
+        or non-finite temperature, a seed outside 64 bits, a wrong shape, together with "ecpm", ``reserve``,
+        ``head_weights`` or ``diversity``: ValueError; bools, non-numbers, a tensor of another dtype or device: TypeError.
         ``check_indices``: an out-of-range user index or ad-table row raises IndexError; an unfilled slot does not."""
         if heads is not None:
             self._check_heads(heads)
@@ -495,8 +531,14 @@ class AdRecommenderInference:
         div = self._check_diversity(diversity, diversity_pool, top_k, auction)
         hw = self._check_head_weights(head_weights, None if user_categorical is None else user_categorical.shape[0], auction,
                                       diversity, heads)
+        ex = _explore.check_explore(explore, explore_seed, explore_from, top_k,
+                                    None if user_categorical is None else user_categorical.shape[0], auction is not None,
+                                    head_weights is not None, diversity is not None)
         uc = _lib.require_gpu(user_categorical, "user_categorical")
         un = _lib.require_gpu(user_numerical, "user_numerical")
+        if ex is not None:
+            ex = (_explore.temperature_tensor(ex.temperature, uc.shape[0], uc.device),
+                  _explore.seed_tensor(ex.seed, uc.shape[0], uc.device), ex.greedy)
         excluded = exclude_ad_ids is not None and exclude_ad_ids.shape[-1] > 0
         masked = require_all is not None or require_any is not None
         # one calling thread at a time enqueues (amdrec._lib.Gate): the launches below hand their intermediate results to
@@ -507,7 +549,7 @@ class AdRecommenderInference:
                                                             include_ad_ids if listed else None)
             # (excluded: "a slot can be unfilled" - true after a filtered stage 1 as well)
             out = self._stage2(uc, un, cand_pos, top_k, check_indices, excluded=excluded or masked or cap1 is not None,
-                               heads=heads, max_per_group=cap, auction=auction, diversity=div, head_weights=hw)
+                               heads=heads, max_per_group=cap, auction=auction, diversity=div, head_weights=hw, explore=ex)
         out["candidate_scores"] = cand_scores
         if injected:
             out["candidate_injected"] = injected[0]
@@ -531,7 +573,7 @@ class AdRecommenderInference:
                 stage1_max_per_group: Optional[int] = None, rank_by: Optional[str] = None,
                 reserve: bool = False, diversity: Optional[float] = None,
                 diversity_pool: int = 64, stage1_boost: bool = False, head_weights: bool = False,
-                max_include: int = 0) -> "GraphedRecommender":
+                max_include: int = 0, explore: bool = False, explore_from: int = 0) -> "GraphedRecommender":
         """Capture one recommend_device call for a fixed batch shape into a HIP graph (the ~40 kernel
         launches of a request are host-launch-bound at small batch: 1.76 ms eager at B = 1) and return a
         replayer.  Weights, index and ad table must not change afterwards.  ``max_exclude`` > 0: the graph also holds a
@@ -551,10 +593,14 @@ class AdRecommenderInference:
         others); False captures the graph as ever.  ``max_include`` > 0: the graph also holds a static
         [batch_size, max_include] include buffer (-1 = padding until filled) and the merge step of recommend_device's
         ``include_ad_ids``, which the replayer's ``include`` argument fills; the id table is that of capture time; 0
-        captures the graph as ever."""
+        captures the graph as ever.  ``explore=True``: the graph runs the sampled selection of recommend_device with the
+        greedy prefix ``explore_from`` (a scalar fixed at capture) and holds static [batch_size] temperature and seed buffers
+        that the replayer's ``explore`` / ``explore_seed`` fill (zeros until then: every user is served greedily); a replay
+        without them redraws with the buffers as they stand - the same seeds, hence the same draw for the same candidates.
+        False captures the graph as ever."""
         return GraphedRecommender(self, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group,
                                   stage1_max_per_group, rank_by, reserve, diversity, diversity_pool, stage1_boost, head_weights,
-                                  max_include)
+                                  max_include, explore, explore_from)
 
     # -- live corpus: ads leave and enter without a rebuild of the index or of the ranker's per-ad caches ------------------
     def remove_ads(self, ad_ids) -> int:
@@ -618,7 +664,8 @@ class AdRecommenderInference:
                       return_scores: bool = True, exclude_ad_ids=None, require_all: int = 0, require_any: int = 0,
                       max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                       rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                      diversity_pool: int = 64, stage1_boost=None, head_weights=None, include_ad_ids=None) -> dict:
+                      diversity_pool: int = 64, stage1_boost=None, head_weights=None, include_ad_ids=None, explore=None,
+                      explore_seed=None, explore_from: int = 0) -> dict:
         """inference.py:199-288.  ``exclude_ad_ids``: the ad ids this user must not be shown (a sequence of integers).
         ``require_all`` / ``require_any``: this request's eligibility masks (64-bit integers; 0 and 0: no constraint, the
         plain search).  ``max_per_group`` / ``stage1_max_per_group``: the per-group caps of recommend_device.  ``rank_by`` /
@@ -627,7 +674,9 @@ class AdRecommenderInference:
         weight on the per-ad boosts in stage 1 (a number; recommend_device).  ``head_weights``: the value ranking of
         recommend_device, a dict by task name or a sequence of numbers (the dict gains ``values``).  ``include_ad_ids``: the
         ad ids that must reach the ranker for this user whatever their similarity rank (a sequence of integers;
-        recommend_device).  Fewer than ``top_k`` real candidates: as batch_recommend."""
+        recommend_device).  ``explore`` / ``explore_seed`` / ``explore_from``: the sampled selection of recommend_device for
+        this request - a temperature, a seed in [0, 2^64), the greedy prefix; the dict gains a ``"propensities"`` list: log
+        it with the impression.  Fewer than ``top_k`` real candidates: as batch_recommend."""
         masked = bool(require_all) or bool(require_any)
         return self.batch_recommend([user_data], top_k=top_k, stage1_k=stage1_k, return_scores=return_scores,
                                     exclude_ad_ids=None if exclude_ad_ids is None else [exclude_ad_ids],
@@ -636,13 +685,15 @@ class AdRecommenderInference:
                                     stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve,
                                     diversity=diversity, diversity_pool=diversity_pool, stage1_boost=stage1_boost,
                                     head_weights=head_weights,
-                                    include_ad_ids=None if include_ad_ids is None else [include_ad_ids])[0]
+                                    include_ad_ids=None if include_ad_ids is None else [include_ad_ids], explore=explore,
+                                    explore_seed=explore_seed, explore_from=explore_from)[0]
 
     def batch_recommend(self, user_data_list: list, top_k: int = 10, stage1_k: int = 500,
                         return_scores: bool = True, exclude_ad_ids=None, require_all=None, require_any=None,
                         max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                         rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                        diversity_pool: int = 64, stage1_boost=None, head_weights=None, include_ad_ids=None) -> list:
+                        diversity_pool: int = 64, stage1_boost=None, head_weights=None, include_ad_ids=None, explore=None,
+                        explore_seed=None, explore_from: int = 0) -> list:
         """inference.py:290-331 - but one device pass for the whole list instead of a serial loop.
         ``timing`` reports the batch's stage times divided by the number of users.  ``exclude_ad_ids``: one sequence of
         ad ids per user (recommend_device has the meaning); the padded block travels in the input staging block.
@@ -661,29 +712,39 @@ class AdRecommenderInference:
         ``head_weights``: the value ranking of recommend_device, for every user of the list; every user's dict gains a
         ``"values"`` list of length ``top_k``, in the same result block.  ``include_ad_ids``: one sequence of ad ids per user
         (or an integer array [n, I], negative = padding) that must reach the ranker (recommend_device); the padded block
-        travels through pinned memory like the exclusions: no synchronisation more."""
+        travels through pinned memory like the exclusions: no synchronisation more.  ``explore`` / ``explore_seed`` /
+        ``explore_from``: the sampled selection of recommend_device - one temperature for every user or a sequence of one per
+        user, one seed (user ``u`` of the list draws with ``(seed + u) mod 2^64``) or a sequence of one per user; both travel in
+        the input staging block, and every user's dict gains a ``"propensities"`` list of length ``top_k``, in the same
+        result block: no copy and no synchronisation more."""
         incl = self._host_inclusions(include_ad_ids, len(user_data_list), stage1_k, stage1_max_per_group)
         self.faiss_index._check_boost(stage1_boost, require_all is not None or require_any is not None)
         self._check_caps(max_per_group, stage1_max_per_group)
         auction = self._check_auction(rank_by, reserve)
         self._check_diversity(diversity, diversity_pool, top_k, auction)
         self._check_head_weights(head_weights, len(user_data_list) or None, auction, diversity)
+        ex = _explore.check_explore(explore, explore_seed, explore_from, top_k, len(user_data_list) or None, auction is not None,
+                                    head_weights is not None, diversity is not None, per_user=True)
         if not user_data_list:
             return []
         n = len(user_data_list)
         excl = self._host_exclusions(exclude_ad_ids, n, stage1_k)
         masks = self._host_masks(require_all, require_any, n)
         wts = None if stage1_boost is None else _boost.as_weights(stage1_boost, n)
+        draws = None if ex is None else _explore.host_arrays(ex, n)
         with _lib.GATE.serving():
-            uc, un, *rest = self.preprocess_batch(user_data_list, excl, masks, wts)
+            uc, un, *rest = self.preprocess_batch(user_data_list, excl, masks, wts, draws)
             excl = rest.pop(0) if excl is not None else None
             masks = rest.pop(0) if masks is not None else None
             wts = rest.pop(0) if wts is not None else None
+            kw = {}
+            if draws is not None:                # (the device views of the staged temperatures and seeds: checked above)
+                kw = dict(explore=rest[0], explore_seed=rest[1], explore_from=ex.greedy)
             return self.recommend_tensors(uc, un, top_k, stage1_k, return_scores, _encoded=True, _exclude_dev=excl,
                                           _masks_dev=masks, _boost_dev=wts, max_per_group=max_per_group,
                                           stage1_max_per_group=stage1_max_per_group, rank_by=rank_by, reserve=reserve,
                                           diversity=diversity, diversity_pool=diversity_pool, head_weights=head_weights,
-                                          _include_host=incl)
+                                          _include_host=incl, **kw)
 
     def _check_caps(self, max_per_group, stage1_max_per_group):
         """The two cap arguments -> (cap or None, stage-1 cap or None); refusals before the library is touched."""
@@ -775,7 +836,7 @@ class AdRecommenderInference:
                           _encoded=False, exclude_ad_ids=None, _exclude_dev=None, require_all=None, require_any=None,
                           _masks_dev=None, max_per_group=None, stage1_max_per_group=None, rank_by=None, reserve=None,
                           diversity=None, diversity_pool=64, stage1_boost=None, _boost_dev=None, head_weights=None,
-                          include_ad_ids=None, _include_host=None):
+                          include_ad_ids=None, _include_host=None, explore=None, explore_seed=None, explore_from=0):
         """Tensor-level entry (cf. TwoStageRetriever.retrieve_and_rank, faiss_retrieval.py:283-369); result dicts follow
         inference.py:272-288.  ONE host synchronisation per call (round 3 had four: the tower's index flag, the stage-1
         timing sync, the ranker's index flag, the result copy - each exposing the launch work queued behind it): indices
@@ -791,7 +852,9 @@ class AdRecommenderInference:
         shipped through pinned memory like the masks.  ``head_weights``: its value ranking; ``values`` rides in the result block
         too, behind ``ecpm`` and ``prices`` where the auction runs: still one copy, one synchronisation.
         ``include_ad_ids``: one sequence of ad ids per user that must reach the ranker (recommend_device), shipped as one
-        padded block through pinned memory like the exclusions."""
+        padded block through pinned memory like the exclusions.  ``explore`` / ``explore_seed`` / ``explore_from``: its
+        sampled selection - numbers, one number per user (shipped through pinned memory like the boost weights) or device
+        tensors; ``propensities`` rides in the result block behind the scores: still one copy, one synchronisation."""
         hi = _include_host
         if hi is None and include_ad_ids is not None and user_categorical is not None:
             hi = self._host_inclusions(include_ad_ids, user_categorical.shape[0], stage1_k, stage1_max_per_group)
@@ -802,6 +865,9 @@ class AdRecommenderInference:
         div = self._check_diversity(diversity, diversity_pool, top_k, auction)
         head_w = self._check_head_weights(head_weights, None if user_categorical is None else user_categorical.shape[0], auction,
                                       diversity)
+        ex = _explore.check_explore(explore, explore_seed, explore_from, top_k,
+                                    None if user_categorical is None else user_categorical.shape[0], auction is not None,
+                                    head_weights is not None, diversity is not None, per_user=True)
         t0 = time.time()
         with _lib.GATE.serving():
             # host side first, beside other threads' enqueues: the inputs' copies to the device (torch ops: they use no
@@ -841,6 +907,20 @@ class AdRecommenderInference:
                 host.numpy().view(np.int64).reshape(hi.shape)[:] = hi
                 incl = host.to(dev, non_blocking=True).view(torch.int64).view(hi.shape)
                 done.record(torch.cuda.current_stream(dev))
+            draw = None
+            if ex is not None:
+                temp, seed = ex.temperature, ex.seed
+                if isinstance(temp, np.ndarray) or isinstance(seed, np.ndarray):     # one per user: [seeds | temperatures], one copy
+                    ht, hs = _explore.host_arrays(ex._replace(temperature=0.0 if isinstance(temp, torch.Tensor) else temp,
+                                                              seed=0 if isinstance(seed, torch.Tensor) else seed), n)
+                    host, done = self._staging(n * 12, "explore")
+                    host.numpy()[:n * 8].view(np.uint64)[:] = hs
+                    host.numpy()[n * 8:].view(np.float32)[:] = ht
+                    blk_e = host.to(dev, non_blocking=True)
+                    done.record(torch.cuda.current_stream(dev))
+                    temp = temp if isinstance(temp, torch.Tensor) else blk_e[n * 8:].view(torch.float32)
+                    seed = seed if isinstance(seed, torch.Tensor) else blk_e[:n * 8].view(torch.int64)
+                draw = (_explore.temperature_tensor(temp, n, dev), _explore.seed_tensor(seed, n, dev), ex.greedy)
             # the enqueue, one calling thread at a time (amdrec._lib.Gate); the wait for the device and the list conversion
             # behind it run beside other threads' enqueues, on staging blocks and events that are this thread's own
             with _lib.GATE.enqueue:
@@ -853,7 +933,8 @@ class AdRecommenderInference:
                 au_b = 0 if auction is None else n * top_k * 4                       # ecpm, then prices, behind the scores
                 dv_b = 0 if div is None else n * top_k * 4                           # diversity_values, there instead (never both)
                 va_b = 0 if head_w is None else n * top_k * 4                            # values, behind all of them (never with dv_b)
-                end_b = ids_b + sc_b + 2 * au_b + dv_b + va_b
+                pr_b = 0 if draw is None else n * top_k * 4                          # propensities, behind the scores (alone there)
+                end_b = ids_b + sc_b + 2 * au_b + dv_b + va_b + pr_b
                 blk = torch.empty(end_b + 8, dtype=torch.uint8, device=dev)
                 ad_ids = blk[:ids_b].view(torch.int64).view(n, top_k)
                 scores = blk[ids_b:ids_b + sc_b].view(torch.float32).view(len(tasks), n, top_k)
@@ -865,6 +946,8 @@ class AdRecommenderInference:
                                   for i in range(2))
                 if div is not None:
                     outs += (blk[ids_b + sc_b:ids_b + sc_b + dv_b].view(torch.float32).view(n, top_k),)
+                if draw is not None:
+                    outs += (blk[ids_b + sc_b:ids_b + sc_b + pr_b].view(torch.float32).view(n, top_k),)
                 verdict = blk[end_b:].view(torch.int32)                              # [2]: nonzero = an index out of range
                 trusted = _encoded and self.preprocessor is not None and self._encoder_fits()
                 if trusted:
@@ -883,7 +966,7 @@ class AdRecommenderInference:
                 ev[1].record(st)
                 out = self._stage2(uc, un, cand_pos, top_k, False, out=outs,
                                    excluded=excl is not None or masks is not None or cap1 is not None, max_per_group=cap,
-                                   auction=auction, diversity=div, head_weights=head_w)
+                                   auction=auction, diversity=div, head_weights=head_w, explore=draw)
                 assert list(out["tasks"]) == tasks
                 host, done = self._staging(blk.numel(), "out")
                 host.copy_(blk, non_blocking=True)
@@ -898,6 +981,7 @@ class AdRecommenderInference:
             au = None if auction is None else hv[ids_b + sc_b:ids_b + sc_b + 2 * au_b].view(np.float32).reshape(2, n, top_k).tolist()
             dv = None if div is None else hv[ids_b + sc_b:ids_b + sc_b + dv_b].view(np.float32).reshape(n, top_k).tolist()
             va = None if head_w is None else hv[end_b - va_b:end_b].view(np.float32).reshape(n, top_k).tolist()
+            pr = None if draw is None else hv[ids_b + sc_b:ids_b + sc_b + pr_b].view(np.float32).reshape(n, top_k).tolist()
             t2 = time.time()
             # stage 1 = its GPU time (tower + search, as the reference brackets them); stage 2 = the rest of the call's wall time
             # (ranker, selection, the copy back and the list conversion: what the reference's second bracket holds)
@@ -915,6 +999,8 @@ class AdRecommenderInference:
                     r["diversity_values"] = dv[b]
                 if va is not None:
                     r["values"] = va[b]
+                if pr is not None:
+                    r["propensities"] = pr[b]
                 res.append(r)
             return res
 
@@ -941,7 +1027,8 @@ class TwoStageRetriever:
                           stage2_k: int = 10, ad_features_lookup=None, exclude_ad_ids=None,
                           max_per_group: Optional[int] = None, stage1_max_per_group: Optional[int] = None,
                           rank_by: Optional[str] = None, reserve=None, diversity: Optional[float] = None,
-                          diversity_pool: int = 64, stage1_boost=None, head_weights=None, include_ad_ids=None):
+                          diversity_pool: int = 64, stage1_boost=None, head_weights=None, include_ad_ids=None, explore=None,
+                          explore_seed=None, explore_from: int = 0):
         """``exclude_ad_ids``: the ad ids the (first) user must not be shown, a sequence of integers.  With a table, the two
         lists have length ``stage2_k``; a user with fewer real candidates gets -1 / 0.0 in the tail (batch_recommend).
         ``stage1_max_per_group`` / ``max_per_group``: the per-group caps on the candidates and on the ranked result
@@ -953,7 +1040,10 @@ class TwoStageRetriever:
         per-ad boosts in stage 1, a number (recommend_device), with or without a table.  ``head_weights``: the value ranking
         of recommend_device for the ranked result (ids and CTR probabilities, in value order); without a table it is checked
         and changes nothing.  ``include_ad_ids``: the ad ids that must be candidates for the (first) user whatever their
-        similarity rank, a sequence of integers (recommend_device), with or without a table."""
+        similarity rank, a sequence of integers (recommend_device), with or without a table.  ``explore`` / ``explore_seed`` /
+        ``explore_from``: the sampled selection of recommend_device for the ranked result, a temperature, a seed and the
+        greedy prefix (ids and CTR probabilities, in pick order; the tuple carries no propensities - a caller that logs them
+        uses recommend_ads); without a table they are checked and change nothing."""
         idx = self.faiss_index
         incl = None if include_ad_ids is None else _include.as_block([include_ad_ids], 1)
         if incl is not None:                                                      # (refused before the library is touched)
@@ -969,6 +1059,8 @@ class TwoStageRetriever:
         if head_weights is not None:
             _value.check_head_weights(head_weights, self.transformer_ranker.prediction_heads.keys(), None, auction,
                                       diversity is not None)
+        ex = _explore.check_explore(explore, explore_seed, explore_from, stage2_k, None, bool(auction), head_weights is not None,
+                                    diversity is not None)
         uc = user_categorical.to(self.device)
         un = user_numerical.to(self.device, dtype=torch.float32)
         excl = None if exclude_ad_ids is None else [exclude_ad_ids]
@@ -997,7 +1089,11 @@ class TwoStageRetriever:
                                         rank_by=rank_by, reserve=reserve, diversity=diversity,
                                         diversity_pool=diversity_pool, stage1_boost=stage1_boost,
                                         head_weights=head_weights if not isinstance(head_weights, torch.Tensor)
-                                        else head_weights[:1], _include_host=incl)[0]
+                                        else head_weights[:1], _include_host=incl,
+                                        **({} if ex is None else dict(
+                                            explore=ex.temperature[:1] if isinstance(ex.temperature, torch.Tensor) else ex.temperature,
+                                            explore_seed=ex.seed[:1] if isinstance(ex.seed, torch.Tensor) else ex.seed,
+                                            explore_from=ex.greedy)))[0]
         return r["ad_ids"], r["scores"]["ctr"]                                    # :359-369 (ids, ctr probabilities)
 
 
@@ -1010,15 +1106,17 @@ class GraphedRecommender:
                  max_exclude: int = 0, eligibility: bool = False, max_per_group: Optional[int] = None,
                  stage1_max_per_group: Optional[int] = None, rank_by: Optional[str] = None, reserve: bool = False,
                  diversity: Optional[float] = None, diversity_pool: int = 64, stage1_boost: bool = False,
-                 head_weights: bool = False, max_include: int = 0):
+                 head_weights: bool = False, max_include: int = 0, explore: bool = False, explore_from: int = 0):
         # the capture gate first: while another thread captures, the runtime is in its global capture mode, and the
         # allocations and fills of the static buffers below would already disturb it.  Refused before the device is touched
         with _lib.GATE.capturing():
             self._init(rec, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group, stage1_max_per_group,
-                       rank_by, reserve, diversity, diversity_pool, stage1_boost, head_weights, max_include)
+                       rank_by, reserve, diversity, diversity_pool, stage1_boost, head_weights, max_include, explore,
+                       explore_from)
 
     def _init(self, rec, batch_size, top_k, stage1_k, warmup, max_exclude, eligibility, max_per_group, stage1_max_per_group,
-              rank_by, reserve, diversity, diversity_pool, stage1_boost, head_weights=False, max_include=0):
+              rank_by, reserve, diversity, diversity_pool, stage1_boost, head_weights=False, max_include=0, explore=False,
+              explore_from=0):
         self.rec, self.batch_size, self.top_k, self.stage1_k = rec, batch_size, top_k, stage1_k
         # the per-group caps: scalars fixed at capture (the group keys are those of capture time, pinned below)
         self.max_per_group, self.stage1_max_per_group = rec._check_caps(max_per_group, stage1_max_per_group)
@@ -1039,6 +1137,14 @@ class GraphedRecommender:
             self._tasks = list(rec.transformer_ranker.prediction_heads.keys())
             self._head_default = tuple(1.0 if t == "ctr" else 0.0 for t in self._tasks)
             _value.check_head_weights(self._head_default, self._tasks, None, auction, diversity is not None)
+        # exploration: explore=True gives the graph static [batch_size] temperature and seed buffers (zeros: every user served
+        # greedily, until the replayer fills them) and the sampled selection; the prefix is fixed at capture; the refusals
+        # are recommend_device's
+        if not isinstance(explore, bool):
+            raise TypeError(f"capture(explore=) takes True or False (the replayer takes the temperatures), got {explore!r}")
+        ex = _explore.check_explore(0.0 if explore else None, 0 if explore else None, explore_from, top_k, None, auction,
+                                    bool(head_weights), diversity is not None)
+        self._temp = self._seed = None
         self.max_exclude = int(max_exclude)
         _exclude.check_exclude(stage1_k, self.max_exclude)
         # the include list: a static [batch_size, max_include] block (-1 = padding = nothing listed); None: no merge step
@@ -1074,6 +1180,10 @@ class GraphedRecommender:
         if self.max_include:
             self._in = torch.full((batch_size, self.max_include), -1, dtype=torch.int64, device=dev)
             caps.update(include_ad_ids=self._in)
+        if ex is not None:
+            self._temp = torch.zeros((batch_size,), dtype=torch.float32, device=dev)
+            self._seed = torch.zeros((batch_size,), dtype=torch.int64, device=dev)
+            caps.update(explore=self._temp, explore_seed=self._seed, explore_from=ex.greedy)
         # sizing + warm-up pass on the shared workspace (packs weights, sets kernel attributes)
         # the capture swaps the process-wide workspace and the runtime's capture mode is global: not beside other threads'
         # calls (amdrec._lib.Gate: refused, either way round - __init__ holds the gate), and no other thread enqueues in between
@@ -1126,19 +1236,19 @@ class GraphedRecommender:
     def __call__(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor,
                  exclude: Optional[torch.Tensor] = None, require_all: Optional[torch.Tensor] = None,
                  require_any: Optional[torch.Tensor] = None, reserve=None, stage1_boost=None, head_weights=None,
-                 include: Optional[torch.Tensor] = None):
+                 include: Optional[torch.Tensor] = None, explore=None, explore_seed=None):
         """One replay - arguments and result: ``_replay`` - inside ``replaying()`` and the serving scope: a replay that
         overlaps another thread's replay of this object, or another thread's capture, raises AmdrecError before it has
         touched the static buffers."""
         with self.replaying(), _lib.GATE.serving():
             return self._replay(user_categorical, user_numerical, exclude, require_all, require_any, reserve, stage1_boost,
-                                head_weights, include)
+                                head_weights, include, explore, explore_seed)
 
     @torch.no_grad()
     def _replay(self, user_categorical: torch.Tensor, user_numerical: torch.Tensor,
                 exclude: Optional[torch.Tensor] = None, require_all: Optional[torch.Tensor] = None,
                 require_any: Optional[torch.Tensor] = None, reserve=None, stage1_boost=None, head_weights=None,
-                include: Optional[torch.Tensor] = None):
+                include: Optional[torch.Tensor] = None, explore=None, explore_seed=None):
         """Device tensors [batch_size, ...] -> the same dict as recommend_device (static output buffers,
         overwritten by the next call).  ``exclude``: device int64 [batch_size, E <= max_exclude] ad ids (negative =
         padding), copied into the graph's block; None = nothing excluded (the block is filled with -1).  ``require_all`` /
@@ -1151,7 +1261,20 @@ class GraphedRecommender:
         into the graph's weight buffer (None = 1.0 for the CTR head, 0.0 for the others); a graph captured without
         ``head_weights=True`` raises ValueError for it.  ``include``: device int64 [batch_size, I <= max_include] ad ids
         (negative = padding), copied into the graph's include block; None = nothing listed (the block is filled with -1); a
-        graph captured without ``max_include`` raises ValueError for it."""
+        graph captured without ``max_include`` raises ValueError for it.  ``explore`` / ``explore_seed``: the temperatures
+        and seeds as recommend_device takes them, each written into the graph's buffer when given; one that is not given
+        leaves its buffer as it stands (a replay without a new seed redraws with the old ones); a graph captured without
+        ``explore=True`` raises ValueError for them."""
+        if explore is not None or explore_seed is not None:
+            if self._temp is None:
+                raise ValueError("captured without explore=True: this graph takes the arg-max and holds no temperatures or seeds")
+            # (each is checked as recommend_device checks it; the other's place is taken by a valid stand-in)
+            ex = _explore.check_explore(0.0 if explore is None else explore, 0 if explore_seed is None else explore_seed, 0,
+                                        self.top_k, self.batch_size)
+            if explore is not None:
+                _explore.temperature_tensor(ex.temperature, self.batch_size, self._temp.device, out=self._temp)
+            if explore_seed is not None:
+                _explore.seed_tensor(ex.seed, self.batch_size, self._seed.device, out=self._seed)
         if include is not None and (self._in is None or include.dim() != 2 or include.shape[0] != self.batch_size
                                     or include.shape[1] > self.max_include or include.dtype != torch.int64):
             raise ValueError(f"captured with max_include={self.max_include} for batch {self.batch_size}, got an include block "

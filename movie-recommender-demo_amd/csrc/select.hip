@@ -11,6 +11,8 @@
 // weighted blend of every task's probability, the winner write-out reports it, and the auction solves its price from it.
 // Their arguments ride behind SelectArgs in a struct of their own, so the instantiations without the switch keep their
 // kernel arguments - and their instruction streams - as they were.
+// amdrec_select_topk_sampled (amdrec/explore.py) is a kernel of its own as well: the plain order's prefix, then a
+// Plackett-Luce draw by Gumbel-perturbed keys under the same cap, with each winner's conditional pick probability.
 #include <optional>
 #include <type_traits>
 #include "../../include/amdrec.h"
@@ -623,6 +625,224 @@ __global__ __launch_bounds__(DIV_NT) void select_diverse_kernel(SelectArgs a, Di
     }
 }
 
+// ---- sampled selection (amdrec_select_topk_sampled, amdrec/explore.py has the rule) -----------------------------------------
+// One workgroup of 512 per user, one dynamic LDS area: two key arrays for the sorts, the candidates' x = z / T and group keys
+// by slot, and the group keys of the walk in walk order.  Phase A: the plain order P (candidate_key, sort_keys_desc), the cap's
+// below_group_cap filter and compaction as in the sort shape above; the first g accepted entries (top_k for a user that is
+// served greedily) are the prefix winners.  Phase B: the perturbed keys of the candidates not yet chosen, sorted, and the same
+// filter over [the prefix winners, the sampled order]: an entry is accepted iff fewer than cap earlier entries of that walk
+// share its group, which is the greedy rule with the prefix's counts carried over.  Phase C: the ranks behind the prefix in
+// order; xs[i] holds x_i while candidate i is in R (finite logit, not chosen, its group not full) and a NaN otherwise; a rank
+// costs two fixed-order block reductions in fp64 (the maximum, then the sum of exp(x - m)), after which the winner leaves R
+// and, where its group is now full, so does its group.  Every loop bound is k_c, top_k or the block size.
+constexpr int SMP_NT = SORT_NT, SMP_NW = SMP_NT / 64, SMP_MAX_TOP = 128;
+constexpr size_t smp_lds_bytes(int n_al) { return (size_t)(5 * n_al + SMP_MAX_TOP) * 8; }
+constexpr size_t SMP_MAX_LDS = smp_lds_bytes(AMDREC_MAX_K);
+
+struct SampleArgs {
+    const float* temperature;                // [n_users]
+    const unsigned long long* seeds;         // [n_users]
+    int greedy;
+    float* out_propensity;                   // [n_users][top_k]
+};
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
+    x ^= x >> 30;
+    x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27;
+    x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+
+// the Gumbel noise of ad `id` under the user's mixed seed: U has 23 random bits and lies strictly inside (0, 1)
+__device__ __forceinline__ double gumbel_of(unsigned long long mixed_seed, long long id) {
+    const unsigned long long h = mix64(mixed_seed ^ (unsigned long long)id);
+    const float U = ((float)(h >> 41) + 0.5f) * 1.1920928955078125e-07f;         // (exact: 24 significant bits)
+    return -log(-log((double)U));
+}
+
+// The sampled order's key of a candidate with logit z at slot i: +inf logits first (high word above every score image), then
+// the finite ones by k = (float)(x + G), then -inf logits (high word 2: below every score image, above the NaN plane), then
+// NaN logits (candidate_key's NaN plane); the slot in the low word, so that each class is in slot order.
+__device__ __forceinline__ unsigned long long sampled_key(float z, int i, double x, double G) {
+    const unsigned long long low = (unsigned long long)(~(uint32_t)i);
+    if (z != z) return low | (1ull << 32);
+    if (z == INFINITY) return low | (0xffffffffull << 32);
+    if (z == -INFINITY) return low | (2ull << 32);
+    return make_key((float)(x + G), (uint32_t)i);
+}
+
+// fixed-order block reductions of one double per thread (SMP_NT threads, red[2][SMP_NW] in LDS: the two calls of a rank
+// alternate between the halves, so that one barrier per call suffices)
+template <bool MAX>
+__device__ __forceinline__ double block_reduce_f64(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double other = __shfl_xor(v, o, 64);
+        v = MAX ? (other > v ? other : v) : v + other;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double r = red[0];
+#pragma unroll
+    for (int w = 1; w < SMP_NW; ++w) r = MAX ? (red[w] > r ? red[w] : r) : r + red[w];
+    return r;
+}
+
+// The cap's filter and compaction over the sorted keys `sorted`[0 .. k_c) that continue a walk of n_before accepted entries
+// (their groups in grp_seq[0 .. n_before)): the accepted entries of walk rank < top_k go to win_key.  Returns the
+// number accepted.  All threads call; begins and ends behind a block barrier.
+__device__ __forceinline__ int sampled_walk(const unsigned long long* sorted, int k_c, int n_before, int limit, bool capped,
+                                            int cap, const long long* grp_slot, long long* grp_seq,
+                                            unsigned long long* win_key, int (*wave_total)[SMP_NW]) {
+    const int tid = threadIdx.x;
+    unsigned long long key[SORT_ROUNDS];
+    long long g[SORT_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < SORT_ROUNDS; ++r) {
+        const int i = r * SMP_NT + tid;
+        key[r] = i < k_c ? sorted[i] : 0ull;
+        g[r] = key[r] != 0ull ? grp_slot[key_pos(key[r])] : -1ll;
+        if (i < k_c) grp_seq[n_before + i] = g[r];
+    }
+    __syncthreads();
+    bool keep[SORT_ROUNDS];
+    int slot[SORT_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < SORT_ROUNDS; ++r)
+        keep[r] = key[r] != 0ull && (!capped || g[r] < 0 || below_group_cap(grp_seq, n_before + r * SMP_NT + tid, g[r], cap));
+    const int kept = compact_slots<SMP_NT, SORT_ROUNDS>(keep, slot, wave_total);
+#pragma unroll
+    for (int r = 0; r < SORT_ROUNDS; ++r)
+        if (keep[r] && n_before + slot[r] < limit) win_key[n_before + slot[r]] = key[r];
+    __syncthreads();
+    return kept;
+}
+
+__global__ __launch_bounds__(SMP_NT) void select_sampled_kernel(SelectArgs a, SampleArgs s, int n_al) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smp_lds[];
+    __shared__ unsigned long long win_key[SMP_MAX_TOP];        // per rank: the winner's key (its slot in the low word); 0: none
+    __shared__ float win_prop[SMP_MAX_TOP];
+    __shared__ int wave_total[SORT_ROUNDS][SMP_NW];
+    __shared__ double red[2][SMP_NW];
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(smp_lds);
+    unsigned long long* other = keys + n_al;
+    double* xs = reinterpret_cast<double*>(other + n_al);
+    long long* grp_slot = reinterpret_cast<long long*>(xs + n_al);
+    long long* grp_seq = grp_slot + n_al;                      // [n_al + SMP_MAX_TOP]
+    const long long u = blockIdx.x;
+    const int tid = threadIdx.x;
+    const bool capped = a.cap > 0;
+    const float T = s.temperature[u];
+    const bool explore = T > 0.0f;                             // (zero, negative, NaN: served greedily)
+    const int g_u = explore ? s.greedy : a.top_k;
+    const double nan64 = __builtin_nan("");
+
+    if (tid < SMP_MAX_TOP) {
+        win_key[tid] = 0ull;
+        win_prop[tid] = 0.0f;
+    }
+    for (int i = tid; i < a.k_c; i += SMP_NT) {
+        const long long pos = a.cand_pos[u * a.k_c + i];
+        keys[i] = candidate_key<false>(a, u, i, pos, 0.0f);
+        grp_slot[i] = capped ? group_at(a.group_of, a.n_group_rows, pos) : -1ll;
+    }
+    __syncthreads();
+
+    // ---- phase A: the greedy prefix
+    int n_pre = 0;
+    if (g_u > 0) {                                             // workgroup-uniform
+        const unsigned long long* sorted = sort_keys_desc<SMP_NT, 1>(keys, other, a.k_c, 128);    // (an instantiation of its own)
+        const int kept = sampled_walk(sorted, a.k_c, 0, g_u, capped, a.cap, grp_slot, grp_seq, win_key, wave_total);
+        n_pre = kept < g_u ? kept : g_u;
+    }
+    int n_win = n_pre;
+    // (a prefix shorter than g: the plain walk has used every candidate the cap lets through, nothing is left to draw)
+    if (n_pre == g_u && g_u < a.top_k) {                       // workgroup-uniform
+        // ---- phase B: the perturbed keys of the candidates that are left, their order, the walk behind the prefix
+        if (tid < n_pre) {
+            const int w = (int)key_pos(win_key[tid]);
+            grp_seq[tid] = grp_slot[w];
+            win_prop[tid] = 1.0f;
+        }
+        const unsigned long long ms = mix64(s.seeds[u]);
+        for (int i = tid; i < a.k_c; i += SMP_NT) {
+            const long long pos = a.cand_pos[u * a.k_c + i];
+            unsigned long long key = 0ull;
+            double x = nan64;
+            if (pos >= 0) {
+                const float z = a.logits[(long long)a.rank_task * a.ld + u * a.k_c + i];
+                const bool finite = z == z && z != INFINITY && z != -INFINITY;
+                if (finite) x = (double)z / (double)T;
+                key = sampled_key(z, i, x, finite ? gumbel_of(ms, a.cand_ids[u * a.k_c + i]) : 0.0);
+            }
+            keys[i] = key;
+            xs[i] = x;
+        }
+        __syncthreads();
+        if (tid < n_pre) {                                     // the prefix winners are chosen: out of the order and out of R
+            const int w = (int)key_pos(win_key[tid]);
+            keys[w] = 0ull;
+            xs[w] = nan64;
+        }
+        __syncthreads();
+        if (capped) {                                          // a group the prefix has filled is out of R
+            for (int i = tid; i < a.k_c; i += SMP_NT) {
+                const long long gi = grp_slot[i];
+                if (gi < 0) continue;
+                int seen = 0;
+                for (int j = 0; j < n_pre; ++j) seen += grp_seq[j] == gi;
+                if (seen >= a.cap) xs[i] = nan64;
+            }
+        }
+        const unsigned long long* sorted = sort_keys_desc<SMP_NT, 1>(keys, other, a.k_c, 128);    // (an instantiation of its own)
+        const int kept = sampled_walk(sorted, a.k_c, n_pre, a.top_k, capped, a.cap, grp_slot, grp_seq, win_key, wave_total);
+        n_win = n_pre + kept < a.top_k ? n_pre + kept : a.top_k;
+
+        // ---- phase C: the propensities of the ranks behind the prefix
+        for (int j = n_pre; j < n_win; ++j) {
+            const int w = (int)key_pos(win_key[j]);
+            const double xw = xs[w];
+            float p = 1.0f;                                    // a winner outside F was forced
+            if (xw == xw) {                                    // workgroup-uniform
+                double m = -INFINITY;
+                for (int i = tid; i < a.k_c; i += SMP_NT) {
+                    const double x = xs[i];
+                    m = x > m ? x : m;                         // (a NaN never replaces m)
+                }
+                m = block_reduce_f64<true>(m, red[0]);
+                double sum = 0.0;
+                for (int i = tid; i < a.k_c; i += SMP_NT) {
+                    const double x = xs[i];
+                    if (x == x) sum += exp(x - m);
+                }
+                sum = block_reduce_f64<false>(sum, red[1]);
+                p = (float)(exp(xw - m) / sum);
+            }
+            __syncthreads();                                   // every read of xs is done
+            if (tid == 0) win_prop[j] = p;
+            const long long gw = grp_slot[w];
+            bool full = false;
+            if (capped && gw >= 0) {                           // workgroup-uniform
+                int seen = 0;
+                for (int r = 0; r <= j; ++r) seen += grp_slot[key_pos(win_key[r])] == gw;
+                full = seen >= a.cap;
+            }
+            for (int i = tid; i < a.k_c; i += SMP_NT)
+                if (i == w || (full && grp_slot[i] == gw)) xs[i] = nan64;
+            __syncthreads();
+        }
+    } else if (tid < n_pre) {
+        win_prop[tid] = 1.0f;
+    }
+    __syncthreads();
+    for (int r = tid; r < a.top_k; r += SMP_NT) {
+        write_winner<false>(a, win_key[r], u, r, 0.0f);
+        s.out_propensity[u * a.top_k + r] = win_prop[r];
+    }
+}
+
 template <bool AUCTION, bool CAPPED, bool VALUE = false>
 static void launch_select(const SelectArgsOf<VALUE>& a, hipStream_t st) {
     if (a.top_k <= 32 && a.k_c <= 512) {                       // one wave per user, no sort
@@ -763,6 +983,51 @@ extern "C" int amdrec_select_topk_value_auction(const float* logits, int64_t ld_
                       weights, out_values};
     return select_any(a, true, "select_topk_value_auction",
                       (double)n_users * k_c * (16.0 + 4.0 * n_tasks + (capped ? 8.0 : 0.0)), stream);
+}
+
+extern "C" int amdrec_select_topk_sampled(const float* logits, int64_t ld_logits, int n_tasks, int rank_task,
+                                          const int64_t* cand_ids, const int64_t* cand_pos, int64_t n_users, int k_c, int top_k,
+                                          int64_t* out_ids, float* out_scores, int32_t* out_slots, const int64_t* group_of,
+                                          int64_t n_group_rows, int max_per_group, const float* temperature,
+                                          const uint64_t* seeds, int greedy, float* out_propensity, void* stream) {
+    REQUIRE(n_tasks >= 1 && rank_task >= 0 && rank_task < n_tasks, "bad task index");
+    REQUIRE(k_c >= 1 && k_c <= AMDREC_MAX_K, "candidates per user must be in [1,%d]", AMDREC_MAX_K);
+    REQUIRE(top_k >= 1 && top_k <= SMP_MAX_TOP, "top_k=%d out of range [1, %d] (one block reduction per sampled rank)", top_k,
+            SMP_MAX_TOP);
+    REQUIRE(greedy >= 0 && greedy <= top_k, "greedy=%d out of range [0, top_k=%d]", greedy, top_k);
+    REQUIRE(max_per_group >= 0 && max_per_group <= AMDREC_MAX_K, "max_per_group=%d out of range [0, %d] (0: no cap)",
+            max_per_group, AMDREC_MAX_K);
+    REQUIRE(n_group_rows >= 0, "n_group_rows=%lld is negative", (long long)n_group_rows);
+    if (n_users <= 0) return AMDREC_OK;                        // (no user: nothing to do, and no pointer is looked at)
+    const bool capped = max_per_group > 0;
+    REQUIRE(n_users <= 2147483647ll, "n_users=%lld: at most 2^31 - 1 users per call", (long long)n_users);
+    REQUIRE(cand_pos != nullptr, "null pointer: cand_pos (the sampled selection's candidates are decided by position)");
+    REQUIRE(!capped || group_of != nullptr || n_group_rows == 0, "null pointer: group_of");
+    REQUIRE(temperature != nullptr && seeds != nullptr && out_propensity != nullptr,
+            "null pointer: temperature, seeds or out_propensity");
+    REQUIRE(logits && cand_ids && out_ids && out_scores, "null pointer");
+    REQUIRE((reinterpret_cast<uintptr_t>(seeds) & 7) == 0 && (reinterpret_cast<uintptr_t>(cand_ids) & 7) == 0 &&
+                (reinterpret_cast<uintptr_t>(cand_pos) & 7) == 0 && (reinterpret_cast<uintptr_t>(out_ids) & 7) == 0 &&
+                (reinterpret_cast<uintptr_t>(group_of) & 7) == 0,
+            "seeds, cand_ids, cand_pos, out_ids and group_of must be 8-byte aligned");
+    REQUIRE(((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(temperature) |
+              reinterpret_cast<uintptr_t>(out_scores) | reinterpret_cast<uintptr_t>(out_propensity) |
+              reinterpret_cast<uintptr_t>(out_slots)) & 3) == 0,
+            "logits, temperature, out_scores, out_propensity and out_slots must be 4-byte aligned");
+    REQUIRE(ld_logits >= n_users * k_c, "ld_logits too small");
+    const SelectArgs a{logits, (long long)ld_logits, n_tasks, rank_task, (const long long*)cand_ids, (const long long*)cand_pos,
+                       k_c, top_k, (long long)n_users, (long long*)out_ids, out_scores, out_slots,
+                       nullptr, 0, nullptr, nullptr, nullptr,
+                       capped ? (const long long*)group_of : nullptr, capped ? (long long)n_group_rows : 0, max_per_group};
+    const SampleArgs s{temperature, (const unsigned long long*)seeds, greedy, out_propensity};
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int n_al = k_c <= 1024 ? 1024 : AMDREC_MAX_K;        // (the run sort's second array holds 1024 or 2048 keys)
+    static PerDeviceOnce attr;
+    HIP_TRY(attr.set_dynamic_lds(reinterpret_cast<const void*>(select_sampled_kernel), SMP_MAX_LDS));
+    ProfScope prof("select_topk_sampled", 0.0, (double)n_users * k_c * (capped ? 28.0 : 20.0), st);
+    hipLaunchKernelGGL(select_sampled_kernel, dim3((unsigned)n_users), dim3(SMP_NT), smp_lds_bytes(n_al), st, a, s, n_al);
+    HIP_TRY(hipGetLastError());
+    return AMDREC_OK;
 }
 
 extern "C" int amdrec_select_topk_diverse(const float* logits, int64_t ld_logits, int n_tasks, int rank_task,

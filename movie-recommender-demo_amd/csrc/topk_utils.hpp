@@ -59,6 +59,10 @@ __device__ inline int find_bin_desc(const int* hist, int& r, int* scratch /*[NT+
 // bit spliced out of p), so every lane does useful work.  A pair with st < 32 lies inside the 64 consecutive
 // elements owned by one wave's pair group, and a wave's LDS operations execute in order, so those stages need
 // only a wave-level fence; block barriers are paid for st >= 32 and at the end of each outer stage.
+// SITE (here and in the two sorts below): an instantiation of its own for a caller whose arrays are not the other callers'.
+// The kernels of a translation unit that call one instantiation with the same LDS arrays get those arrays folded into it as
+// constants; a further caller with other arrays would undo that for all of them, so it takes SITE != 0 and leaves theirs alone.
+template <int SITE = 0>
 __device__ inline void bitonic_desc(unsigned long long* buf, int P) {
     const int tid = threadIdx.x, nt = blockDim.x;
     const int half = P >> 1;
@@ -84,7 +88,7 @@ __device__ inline void bitonic_desc(unsigned long long* buf, int P) {
 // `src`, and every key finds its final position as its index in its own run + the number of larger keys in each other run
 // (a binary search per run: the runs are sorted and the keys unique).  ~4 us at 1024 keys against ~17 for the all-LDS
 // bitonic network (66 stages, most of them behind a block barrier) - the single-query search's finalize was the sort.
-template <int R>
+template <int R, int SITE = 0>
 __device__ inline void sort_desc_runs(unsigned long long* src, unsigned long long* dst, int m) {
     static_assert(R == 2 || R == 4, "two or four keys per lane");
     constexpr int RUN = 64 * R, STEPS = R == 2 ? 8 : 9;      // binary search over 0 .. RUN
@@ -159,7 +163,7 @@ __device__ __forceinline__ float eps_bound(float qn, float dqn, float M, float D
 // block of other than 512 threads - the all-LDS network sorts `keys` in place (cheap for a few hundred keys; 66 stages, most
 // behind a block barrier, for 2048); between, the per-wave run sort writes `other` (>= 1024 keys for m <= 1024, else 2048;
 // its keys must be unique: a fixed ~4 us whatever the count).  All threads call.
-template <int NT>
+template <int NT, int SITE = 0>
 __device__ inline const unsigned long long* sort_keys_desc(unsigned long long* keys, unsigned long long* other, int m,
                                                            int network_max) {
     const int tid = threadIdx.x;
@@ -167,8 +171,8 @@ __device__ inline const unsigned long long* sort_keys_desc(unsigned long long* k
         if (m > network_max && m <= 2048) {
             for (int i = tid; i < (m <= 1024 ? 1024 : 2048); i += NT) other[i] = 0ull;   // the run sort places no zero key
             __syncthreads();
-            if (m <= 1024) sort_desc_runs<2>(keys, other, m);
-            else sort_desc_runs<4>(keys, other, m);
+            if (m <= 1024) sort_desc_runs<2, SITE>(keys, other, m);
+            else sort_desc_runs<4, SITE>(keys, other, m);
             return other;
         }
     }
@@ -176,7 +180,7 @@ __device__ inline const unsigned long long* sort_keys_desc(unsigned long long* k
     while (P < m) P <<= 1;
     for (int i = m + tid; i < P; i += NT) keys[i] = 0ull;
     __syncthreads();
-    bitonic_desc(keys, P);
+    bitonic_desc<SITE>(keys, P);
     return keys;
 }
 

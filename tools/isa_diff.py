@@ -1,9 +1,13 @@
-"""Dev tool: codegen gate between two builds of one translation unit.  Inputs per side: the device assembly
+r"""Dev tool: codegen gate between two builds of one translation unit.  Inputs per side: the device assembly
 (hipcc <product flags> --cuda-device-only -S) and the remarks of -Rpass-analysis=kernel-resource-usage (stderr of that
 compile).  Prints the resource table (parent | branch per kernel) or the per-kernel diff of the instruction streams with
 comments, .loc / .file / .cfi lines, labels' debug suffixes, local labels' function ordinals and metadata stripped.
 usage: python tools/isa_diff.py resources parent.remarks branch.remarks [tu]
        python tools/isa_diff.py isa parent.s branch.s [tu]
+       python tools/isa_diff.py functions parent.s branch.s [tu] [--rename REGEX REPLACEMENT]...
+functions: like isa, but over EVERY function of the unit - kernels and the device functions that stayed out of line - paired
+by MANGLED name, each --rename applied (re.sub) to the names and to the instruction lines of both sides first: for a helper
+that gained a defaulted template argument, e.g. --rename '(sort_keys_descILi\d+E)Li0E' '\1'.  One summary line per unit.
 tu: the translation unit's name for the headings (default: the branch file's name up to its first dot + ".hip")
 --same NAME (repeatable, after the other arguments): a template argument that the branch added with a default, e.g.
 ListNoElig - kernels are paired by demangled name with ", NAME" / "<NAME>" removed, so f<S, NAME> (or f<NAME>) of the branch
@@ -56,7 +60,7 @@ def resources(path):
     return res
 
 
-def kernels(path):
+def kernels(path, everything=False):
     """kernel name -> its instruction lines (between the kernel's label and its s_endpgm / .Lfunc_end).  Local labels
     (.LBB<n>_<m>, .LJTI<n>_<m>, .LCPI<n>_<m>) lose <n>, the function's ordinal in the translation unit: a kernel that joins or
     leaves the unit renumbers every later function without moving an instruction."""
@@ -76,7 +80,7 @@ def kernels(path):
         if not s or s.startswith((".loc", ".file", ".cfi", ".p2align", ".section", ".amdhsa", ".end_amdhsa", ".Ltmp", ".type", ".size", ".text")):
             continue
         cur.append(s)
-    return {k: v for k, v in out.items() if any(i.startswith("s_endpgm") for i in v)}
+    return out if everything else {k: v for k, v in out.items() if any(i.startswith("s_endpgm") for i in v)}
 
 
 def main():
@@ -89,8 +93,25 @@ def main():
         i = argv.index("--same-branch")
         SAME_BRANCH.append(argv[i + 1])
         del argv[i:i + 2]
+    renames = []
+    while "--rename" in argv:
+        i = argv.index("--rename")
+        renames.append((re.compile(argv[i + 1]), argv[i + 2]))
+        del argv[i:i + 3]
     mode, a, b = argv[:3]
     tu = argv[3] if len(argv) > 3 else os.path.basename(b).split(".")[0] + ".hip"
+    if mode == "functions":
+        def renamed(text):
+            for pat, rep in renames:
+                text = pat.sub(rep, text)
+            return text
+        fa, fb = ({renamed(k): [renamed(i) for i in v] for k, v in kernels(f, True).items() if not k.startswith("__hip_cuid_")}
+                  for f in (a, b))
+        both = sorted(set(fa) & set(fb))
+        differ = [k for k in both if fa[k] != fb[k]]
+        print(f"{tu}: {len(both)} functions and kernels in both, {len(both) - len(differ)} identical, different: {differ}; only in "
+              f"the parent: {sorted(set(fa) - set(fb))}; only in the branch: {sorted(set(fb) - set(fa))}")
+        return 1 if differ else 0
     if mode == "resources":
         ra, rb = by_name(resources(a)), by_name(resources(b), True)
         names = {n: n for n in set(ra) | set(rb)}
